@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the SketchEdit inference hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--batch 32] [--dtype f32|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--batch 32] [--dtype f32|bf16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when --dump-outputs DIR is given
+(DIR/composed.npy (B,3,H,W) and DIR/mask.npy (B,1,H,W), float32: what a caller of the timed path receives; a fixed, seeded
+sample of whole images when the output passes 60 MiB), and prints the line.  Everything else the line can carry (the
+objects below, the per-layer table, the forward-only leg of N > 1) is measured only with --full.
 
 Both forms work for N > 1: started WITHOUT a launcher (no WORLD_SIZE in the environment), `python bench.py --gpus N`
 starts its own N rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / a free MASTER_PORT), relays
@@ -16,7 +21,7 @@ resident in HBM.  With N > 1 every rank runs its own batch shard (weak scaling, 
 step, on a side stream under the next step's forward; every step's gather is complete before the closing fence.
 Rank 0 prints ONE JSON line (metric images/sec = N*B*K / max-over-ranks time).
 
-Extra objects in the line:
+Extra objects in the line (--full; null in a plain run):
   roofline     -- the dominant kernel label: EXECUTED multiply-add FLOPs per launch (what its MFMA pipe really runs:
                   24/72 of the reference-defined FLOPs for the hybrid Winograd F(2,3)xF(4,3) kernel, 16/36 for
                   F(2x2,3x3)) / average launch duration
@@ -27,7 +32,7 @@ Extra objects in the line:
                   while this run is still alive; null when rocprofv3 is not usable (see `traffic_source`).
   secondary    -- BASELINE.json configs 3 (512x512 batch 8 fp32) and 5 (512x512 batch 16 bf16) timed in the same invocation
                   after the headline (12 steps each between device fences), with their executed-FLOP fractions and the
-                  parity of their own last timed step; only at the default invocation (--no-secondary skips them).
+                  parity of their own last timed step; only at the default shape (--no-secondary skips them).
   cpu_baseline -- the oracle (CPU restatement of the reference, oracle/sketchedit_oracle.py) timed on the
                   host cores of this box at the sizes SURVEY.md 8d names; reported, not the target.
 """
@@ -645,6 +650,29 @@ def e2e_child(size, batch, timeout_s=240):
         return {"metric": "e2e_images_per_sec", "value": None, "error": repr(e)}
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20      # --dump-outputs writes at most this much array data (under 64 MB with the .npy headers)
+
+
+def dump_outputs(d, packed, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the packed (N,4,H,W) fp32 output of the last timed step (planes 0-2 composite, plane 3 soft mask) as
+    d/composed.npy (N,3,H,W) and d/mask.npy (N,1,H,W).  When all N images pass `budget`, a fixed sample of whole images is
+    written instead (seed 0, ascending indices): the same images for the same arguments, whichever build runs.
+    Returns the image indices written."""
+    n = packed.shape[0]
+    per_image = packed[0].numel() * 4
+    keep = min(n, budget // per_image)
+    if keep < 1:
+        raise SystemExit("bench.py: one %dx%d output image is %d bytes, more than --dump-outputs writes (%d)"
+                         % (packed.shape[2], packed.shape[3], per_image, budget))
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    sel = packed if keep == n else packed[torch.from_numpy(idx).to(packed.device)]
+    a = sel.detach().float().cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "composed.npy"), np.ascontiguousarray(a[:, 0:3]))
+    np.save(os.path.join(d, "mask.npy"), np.ascontiguousarray(a[:, 3:4]))
+    return idx
+
+
 def main():
     faulthandler.enable()
     if "--cpu-all-cores-probe" in sys.argv[1:]:
@@ -688,7 +716,19 @@ def main():
     ap.add_argument("--e2e-encode-threads", action="store_true", help="encoder THREADS in the main process instead of processes (GIL-bound near 2000 images/s)")
     ap.add_argument("--e2e-cap-seconds", type=float, default=3.0, help="seconds per host-codec capability leg (decode, encode, both)")
     ap.add_argument("--no-e2e", action="store_true", help="default invocation: skip the end-to-end child run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/composed.npy and DIR/mask.npy (float32, at most 60 MiB: "
+                         "a fixed, seeded sample of whole images beyond that)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel profiler pass and roofline (with the rocprofv3 "
+                         "traffic child runs), parity of the timed output against the CPU oracle, the CPU baseline, the secondary "
+                         "configurations and the end-to-end leg, --layers, and for N > 1 the forward-only leg; the --no-* options "
+                         "switch single legs off again")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.layers and not args.full:
+        ap.error("--layers is a figure of the profiler pass: it needs --full")
     if args.dry_run_topology:
         os.write(real_stdout, (json.dumps(dry_run_topology(max(1, args.gpus), args)) + "\n").encode())
         return
@@ -804,27 +844,42 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives from its last step: the gathered batch with N > 1, else this rank's own
+        g = state.get("graph_out")
+        if use_dist:
+            last = gathered_sets[state["last"]]
+        elif g:
+            last = torch.cat([g["composed"], g["mask"]], 1)
+        else:
+            last = outs[state["last"]]
+        idx = dump_outputs(args.dump_outputs, last)
+        if len(idx) < last.shape[0]:
+            print("bench.py: --dump-outputs wrote images %s of %d" % (idx.tolist(), last.shape[0]), file=sys.stderr)
     timed_image0 = None                                   # image 0 of the LAST timed step (parity leg)
-    if rank == 0:
+    if rank == 0 and args.full:
         g = state.get("graph_out")
         timed_image0 = torch.cat([g["composed"][0:1], g["mask"][0:1]], 1) if g else outs[state["last"]][0:1].clone()
     per_rank_ms, fwd_only_ms = None, None
     if use_dist:
         # diagnostics for the first real multi-GPU run (VERDICT r4 'Next round' 8), outside the timed region: every rank's own
-        # ms/step, and the forward alone (no gather) over a few steps -- ms_per_step minus that is the EXPOSED part of the gather
-        nfo = max(1, min(args.steps, 10))
-        torch.cuda.synchronize(dev)
-        tf = time.perf_counter()
-        for _ in range(nfo):
-            forward(outs[0])
-        torch.cuda.synchronize(dev)
-        fwd_only = 1e3 * (time.perf_counter() - tf) / nfo
+        # ms/step, and (--full) the forward alone (no gather) over a few steps -- ms_per_step minus that is the EXPOSED part of
+        # the gather
+        fwd_only = float("nan")
+        if args.full:
+            nfo = max(1, min(args.steps, 10))
+            torch.cuda.synchronize(dev)
+            tf = time.perf_counter()
+            for _ in range(nfo):
+                forward(outs[0])
+            torch.cuda.synchronize(dev)
+            fwd_only = 1e3 * (time.perf_counter() - tf) / nfo
         cdev = dev if args.backend == "nccl" else "cpu"
         mine = torch.tensor([1e3 * elapsed / args.steps, fwd_only], dtype=torch.float64, device=cdev)
         allr = [torch.zeros(2, dtype=torch.float64, device=cdev) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank_ms = [round(float(a[0]), 4) for a in allr]
-        fwd_only_ms = [round(float(a[1]), 4) for a in allr]
+        fwd_only_ms = [round(float(a[1]), 4) for a in allr] if args.full else None
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
@@ -846,7 +901,7 @@ def main():
     # ---- per-kernel timing pass (HIP events on the launch stream), not part of the timed region
     peak = MFMA_PEAK_TFLOPS[args.dtype]
     roofline, kernels, full_rep, nprof, violations = None, None, None, 3, []
-    if rank == 0:
+    if rank == 0 and args.full:
         eng.profile(True)
         for _ in range(nprof):
             eng.inference_packed(img, sk, FLAGS, outs[0], low_latency=low_latency)
@@ -898,7 +953,7 @@ def main():
                                                   max(sum(r["total_ms"] for r in mfma), 1e-9), 3)}
         if world == 1 and not args.no_traffic and not args.force_dist:
             child = ["--steps", "1", "--warmup", "1", "--size", str(S), "--batch", str(B), "--dtype", args.dtype,
-                     "--low-latency", args.low_latency, "--no-cpu-baseline", "--no-parity", "--no-traffic", "--no-secondary"]
+                     "--low-latency", args.low_latency, "--full", "--no-cpu-baseline", "--no-parity", "--no-traffic", "--no-secondary"]
             tr, src = pmc_traffic(child)
             roofline["traffic"] = tr.get(dom["kernel"]) if tr else None
             roofline["traffic_source"] = src
@@ -912,7 +967,7 @@ def main():
 
     # ---- parity of this very run against the oracle on image 0 (CPU, rank 0)
     parity = None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         from oracle import sketchedit_oracle as O
         WM = {k: torch.from_numpy(v) for k, v in synth.make_state_dict("M", 0).items()}
         WG = {k: torch.from_numpy(v) for k, v in synth.make_state_dict("G", 0).items()}
@@ -946,13 +1001,13 @@ def main():
                                            "tolerance": "3e-2 max-abs, 3e-3 mean-abs (tests/test_gpu_bf16.py)"}})
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     # ---- BASELINE configs 3 (512x512 batch 8 fp32) and 5 (512x512 batch 16 bf16), after the headline's timed region and its
     # own legs; only at the headline invocation (one GPU, 256x256 batch 32 fp32, eager)
     secondary = None
-    if (rank == 0 and world == 1 and not args.no_secondary and not args.force_dist and not args.graph and (S, B, args.dtype) == (256, 32, "f32")
+    if (rank == 0 and world == 1 and args.full and not args.no_secondary and not args.force_dist and not args.graph and (S, B, args.dtype) == (256, 32, "f32")
             and args.low_latency == "auto"):
         secondary = [secondary_config(dev_index, 512, 8, "f32"), secondary_config(dev_index, 512, 16, "bf16")]
         if not args.no_e2e:
@@ -985,7 +1040,7 @@ def main():
                                        "per_rank_forward_only_ms": fwd_only_ms,
                                        # what the side-stream overlap did not hide (slowest rank): ms/step with the gather
                                        # minus the forward alone, un-timed leg of min(steps, 10) forwards
-                                       "exposed_gather_ms": round(max(per_rank_ms) - max(fwd_only_ms), 4)}
+                                       "exposed_gather_ms": round(max(per_rank_ms) - max(fwd_only_ms), 4) if fwd_only_ms else None}
                                       if use_dist else None)},
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "secondary": secondary, "kernels": kernels,
             "layers": ({r["layer"]: {"ms": round(r["total_ms"] / nprof, 4), "n": r["launches"] // nprof,
@@ -1002,7 +1057,8 @@ def main():
             violations += sec.pop("rate_violations", []) if "rate_violations" in sec else []
         # every printed executed rate must be physically possible: none above peak x 1.08; otherwise the line says so and
         # the run FAILS (exit code 4) -- a number above the roofline is a bookkeeping bug to fix, not to publish
-        line["rate_check"] = {"ok": not violations, "rule": "executed_tflops <= MFMA peak x %.2f for every label" % PEAK_HEADROOM, "violations": violations}
+        line["rate_check"] = ({"ok": not violations, "rule": "executed_tflops <= MFMA peak x %.2f for every label" % PEAK_HEADROOM, "violations": violations}
+                              if args.full else None)
         os.write(real_stdout, (json.dumps(line) + "\n").encode())
         if violations:
             print("bench.py: executed rate above the MFMA peak: %r" % (violations,), file=sys.stderr)

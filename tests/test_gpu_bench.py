@@ -23,7 +23,7 @@ def _one_json_line(out):
 
 @pytest.mark.timeout(900)
 def test_bench_prints_one_contract_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL, cwd=ROOT, capture_output=True, text=True, timeout=850)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + SMALL, cwd=ROOT, capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _one_json_line(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -39,11 +39,46 @@ def test_bench_prints_one_contract_line():
 
 
 @pytest.mark.timeout(900)
+def test_bench_plain_run_dumps_what_its_last_timed_step_computed(tmp_path):
+    """The plain run (no --full): the headline keys with nothing measured beside them, exactly --steps timed steps, and
+    --dump-outputs writes the outputs of the last timed step -- checked against the CPU oracle on the same seeded inputs."""
+    import numpy as np
+    import torch
+    from oracle import sketchedit_oracle as O
+    from parity_util import composed_for_hard_mask
+    from sketchedit_amd import synth
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "2", "--size", "64",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=850)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _one_json_line(r.stdout)
+    assert d["metric"] == "images/sec" and d["unit"] == "images/sec" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("roofline", "kernels", "parity", "cpu_baseline", "secondary", "layers", "rate_check"):
+        assert d[k] is None, k
+    assert sorted(os.listdir(out)) == ["composed.npy", "mask.npy"]
+    comp, mask = np.load(out / "composed.npy"), np.load(out / "mask.npy")
+    assert comp.shape == (2, 3, 64, 64) and mask.shape == (2, 1, 64, 64)
+    assert comp.dtype == np.float32 and mask.dtype == np.float32
+    WM = {k: torch.from_numpy(v) for k, v in synth.make_state_dict("M", 0).items()}
+    WG = {k: torch.from_numpy(v) for k, v in synth.make_state_dict("G", 0).items()}
+    img, sk = synth.make_inputs(2, 64, 64, seed=1234)
+    for i in range(2):
+        ref = O.inference(WM, WG, img[i:i + 1], sk[i:i + 1])
+        assert np.abs(mask[i:i + 1] - ref["mask"].numpy()).max() < 1e-3
+        want, _ = composed_for_hard_mask(O, WG, img[i:i + 1], sk[i:i + 1], ref["mask"], ref["hard_mask"], ref["composed"],
+                                         torch.from_numpy(mask[i:i + 1] > 0.5).float())
+        assert np.abs(comp[i:i + 1] - want.numpy()).max() < 1e-3
+
+
+@pytest.mark.timeout(900)
 def test_bench_two_ranks_share_the_gpu_over_gloo():
     # plain `python bench.py --gpus 2`: no external launcher, bench.py starts its own ranks (the form the driver's N=1
     # command takes at N=2/4/8)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device", "0",
-           "--check-gather", "--no-parity"] + SMALL
+           "--check-gather", "--no-parity", "--full"] + SMALL
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -667,3 +667,37 @@ def test_bench_dry_run_topology_needs_no_gpu():
     assert d["collective"]["bytes_per_rank_per_step"] == 32 * 4 * 256 * 256 * 4
     assert d["environment"]["NCCL_MAX_NCHANNELS_would_be"] == "4"
     assert all(r["threads"] >= 1 for r in d["ranks"]) and d["host"]["cpus_effective"] >= 1
+
+
+def test_bench_dump_outputs_whole_or_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: the packed (N,4,H,W) output as composed.npy / mask.npy in float32; past the byte budget, a
+    sample of whole images that is the same from run to run, within the budget."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("se_bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    packed = torch.from_numpy(np.random.default_rng(5).standard_normal((10, 4, 8, 8)).astype(np.float32))
+    idx = bench.dump_outputs(str(tmp_path / "all"), packed)
+    assert idx.tolist() == list(range(10))
+    comp, mask = np.load(tmp_path / "all" / "composed.npy"), np.load(tmp_path / "all" / "mask.npy")
+    assert comp.dtype == np.float32 and mask.dtype == np.float32
+    assert np.array_equal(comp, packed[:, 0:3].numpy()) and np.array_equal(mask, packed[:, 3:4].numpy())
+    budget = 3 * 4 * 8 * 8 * 4 + 100                              # room for three images
+    i1 = bench.dump_outputs(str(tmp_path / "s1"), packed, budget=budget)
+    i2 = bench.dump_outputs(str(tmp_path / "s2"), packed, budget=budget)
+    assert len(i1) == 3 and i1.tolist() == sorted(set(i1.tolist())) and i1.tolist() == i2.tolist()
+    comp, mask = np.load(tmp_path / "s1" / "composed.npy"), np.load(tmp_path / "s1" / "mask.npy")
+    assert comp.nbytes + mask.nbytes <= budget
+    assert np.array_equal(comp, packed[i1, 0:3].numpy()) and np.array_equal(mask, packed[i1, 3:4].numpy())
+    assert np.array_equal(np.load(tmp_path / "s2" / "composed.npy"), comp)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "none"), packed, budget=100)
+
+
+def test_bench_plain_options_need_no_gpu():
+    """--steps below 1 and --layers without --full are refused before any GPU work; --help names --full and --dump-outputs."""
+    for bad in (["--steps", "0"], ["--layers"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and not r.stdout.strip(), r.stderr[-2000:]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stderr + r.stdout and "--dump-outputs" in r.stderr + r.stdout

@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of the fp32 bench line under environment settings: tools/ab.sh "A=1" "B=2 C=3" ...   (first run: default)
 cd ${GRAFT_REPO_ROOT:-.}; mkdir -p gpurun_out/ab
-Q="--no-cpu-baseline --no-parity --no-traffic ${BENCH_ARGS:-}"
+Q="--full --no-cpu-baseline --no-parity --no-traffic ${BENCH_ARGS:-}"
 run() { tag=$1; shift; env "$@" python bench.py $Q > gpurun_out/ab/"$tag".json 2>/dev/null
 python - "$tag" <<'PY'
 import json,sys

@@ -3,7 +3,7 @@
 #   usage: tools/ab_variants.sh "name1 name2 ..." [bench args...]
 names=$1; shift
 root=${GRAFT_REPO_ROOT:-$(pwd)}; cd $root
-Q="--no-cpu-baseline --no-parity --no-traffic --no-secondary --steps 30"
+Q="--full --no-cpu-baseline --no-parity --no-traffic --no-secondary --steps 30"
 for rep in 1 2; do
   for v in $names; do
     if [ $v == new ]; then unset SKETCHEDIT_HIP_LIB; else export SKETCHEDIT_HIP_LIB=$root/tools/_build/lib_$v.so; fi

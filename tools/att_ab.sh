@@ -3,7 +3,7 @@
 # switched by environment (se_attention.hip: SE_ATT_FUSED, SE_ATT_FUSED_BF16, SE_ATT_PTILDE_LDS, SE_ATT_STATS_LDS, SE_ATT_E16,
 # SE_ATT_SYM), alternating, per-label times from the in-library profiler.   usage: tools/att_ab.sh [reps]
 root=${GRAFT_REPO_ROOT:-$(pwd)}; cd $root
-Q="--no-cpu-baseline --no-parity --no-traffic --no-secondary --steps 20"
+Q="--full --no-cpu-baseline --no-parity --no-traffic --no-secondary --steps 20"
 run() { # label, env..., -- bench args
   label=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift

@@ -1,7 +1,7 @@
 #!/bin/bash
 # per-layer timing tables (in-library HIP events) of the three headline configurations
 root=${GRAFT_REPO_ROOT:-$(pwd)}; cd $root; out=$root/gpurun_out/layers; mkdir -p $out
-Q="--no-cpu-baseline --no-parity --no-traffic --no-secondary --layers --steps 20"
+Q="--full --no-cpu-baseline --no-parity --no-traffic --no-secondary --layers --steps 20"
 python bench.py $Q > $out/c2.json 2>/dev/null
 python bench.py $Q --dtype bf16 --size 512 --batch 16 > $out/c5.json 2>/dev/null
 python - $out <<'PY'

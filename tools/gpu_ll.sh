@@ -1,7 +1,7 @@
 #!/bin/bash
 # batch-1 latency A/B (low-latency mode): usage tools/gpu_ll.sh  [env assignments to compare against the default]
 cd ${GRAFT_REPO_ROOT:-.}; mkdir -p gpurun_out/ll
-Q="--no-cpu-baseline --no-parity --no-traffic --steps 50 --batch 1"
+Q="--full --no-cpu-baseline --no-parity --no-traffic --steps 50 --batch 1"
 run() { tag=$1; shift; env "$@" python bench.py $Q --size 256 > gpurun_out/ll/${tag}_256.json 2>/dev/null; env "$@" python bench.py $Q --size 512 > gpurun_out/ll/${tag}_512.json 2>/dev/null
 python - $tag <<'PY'
 import json,sys

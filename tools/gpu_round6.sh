@@ -6,7 +6,7 @@
 #   tools/gpu_round6.sh probe      where the e2e loop loses time (tools/e2e_probe.py)
 cmd=${1:-suite}
 root=${GRAFT_REPO_ROOT:-$(pwd)}; out=$root/gpurun_out/r6_$cmd; mkdir -p $out; cd $root
-Q="--no-cpu-baseline --no-parity --no-traffic --no-secondary"
+Q="--full --no-cpu-baseline --no-parity --no-traffic --no-secondary"
 case $cmd in
 suite)
   timeout 1700 python -m pytest tests -m gpu -q --tb=short -x > $out/pytest.log 2>&1; echo "pytest rc=$?" >> $out/pytest.log; tail -n 6 $out/pytest.log

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/layers.sh [layer-name-substring]  -- per-layer timing table of one bench step (developer aid)
-python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-parity --layers 2>/dev/null | python -c "
+python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-parity --layers 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 flt=sys.argv[1] if len(sys.argv)>1 else ''

@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/lay
-Q="--dtype bf16 --size 512 --batch 16 --no-cpu-baseline --no-parity --no-traffic --steps 10 --warmup 3 --layers"
+Q="--full --dtype bf16 --size 512 --batch 16 --no-cpu-baseline --no-parity --no-traffic --steps 10 --warmup 3 --layers"
 python bench.py $Q > gpurun_out/lay/r.json 2>/dev/null
 python - <<'PY'
 import json

@@ -11,7 +11,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-parity --no-traffic --no-secondary"
+Q="--full --no-cpu-baseline --no-parity --no-traffic --no-secondary"
 profile() {   # name, bench args
   name=$1; shift
   cd /tmp
@@ -48,9 +48,9 @@ profile() {   # name, bench args
 cd $root
 for cfg in $cfgs; do
   case $cfg in
-    c2) python bench.py > $out/c2_bench.json 2> $out/c2_bench.err; tail -c 400 $out/c2_bench.json; profile c2 ;;
-    c3) python bench.py --size 512 --batch 8 --steps 30 --no-cpu-baseline > $out/c3_bench.json 2> $out/c3_bench.err; profile c3 --size 512 --batch 8 ;;
-    c5) python bench.py --dtype bf16 --size 512 --batch 16 --steps 30 --no-cpu-baseline > $out/c5_bf16_bench.json 2> $out/c5_bf16_bench.err; profile c5_bf16 --dtype bf16 --size 512 --batch 16 ;;
+    c2) python bench.py --full > $out/c2_bench.json 2> $out/c2_bench.err; tail -c 400 $out/c2_bench.json; profile c2 ;;
+    c3) python bench.py --full --size 512 --batch 8 --steps 30 --no-cpu-baseline > $out/c3_bench.json 2> $out/c3_bench.err; profile c3 --size 512 --batch 8 ;;
+    c5) python bench.py --full --dtype bf16 --size 512 --batch 16 --steps 30 --no-cpu-baseline > $out/c5_bf16_bench.json 2> $out/c5_bf16_bench.err; profile c5_bf16 --dtype bf16 --size 512 --batch 16 ;;
     b1) for s in 256 512; do
           SE_ATT_V1=1 python bench.py --size $s --batch 1 --low-latency off $Q --steps 50 > $out/b1_${s}_round1_kernels.json 2>/dev/null
           python bench.py --size $s --batch 1 --low-latency off $Q --steps 50 > $out/b1_${s}_default.json 2>/dev/null

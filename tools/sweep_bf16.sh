@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/sweep
-Q="--dtype bf16 --size 512 --batch 16 --no-cpu-baseline --no-parity --no-traffic --steps 10 --warmup 3"
+Q="--full --dtype bf16 --size 512 --batch 16 --no-cpu-baseline --no-parity --no-traffic --steps 10 --warmup 3"
 run() { tag=$1; shift; env "$@" python bench.py $Q > gpurun_out/sweep/$tag.json 2>/dev/null; python - gpurun_out/sweep/$tag.json $tag <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]).read().splitlines() if l.startswith("{")][-1]); k=d["kernels"]
