@@ -184,7 +184,10 @@ int se_gated_conv2d_ex(se_ctx* ctx, void* stream, const float* x, const float* x
                        const float* b_host, float* y, int B, int Cin, int Cin1, int H, int W, int Cout, int k, int stride,
                        int rate, int act, int upsample, int exec_flags);
 /* cam_1 + cam_2 (models/networks/splitcam.py:57-108,147-174 as configured at editline_g.py:35-42,
- * 203-207): x (B,96,h,w), mask_full (B,1,4h,4w) -> out (B,96,h,w); similar_out (B,L,hs,ws) may be NULL. */
+ * 203-207): x (B,96,h,w), mask_full (B,1,4h,4w) -> out (B,96,h,w); similar_out (B,L,hs,ws) may be NULL.
+ * similar_out is the materialised score matrix: where R Rp 4 >= 2^31 (R = h/2 * w/2, Rp = R rounded up to 32 keys, 64 in
+ * bf16; from h x w = 153 x 153 on, i.e. 1224 x 1224 inputs) the attention runs in the streaming form, which never forms
+ * it, and a non-NULL similar_out is refused (non-zero return, se_last_error); out alone works at every size. */
 int se_attention(se_ctx* ctx, void* stream, const float* x, const float* mask_full, float* out, float* similar_out,
                  int B, int h, int w);
 /* the same with exec_flags (SE_FLAG_BF16: x is rounded to bf16 on the way in, out is the bf16 result widened to fp32) */

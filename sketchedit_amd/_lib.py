@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SKETCHEDIT_HIP_LIB points at another build of the same library (developer builds, e.g. tools/wino_trace.py)
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_misc.hip",
+SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip",
            "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
@@ -551,6 +551,15 @@ class Engine:
         B, C, h, w = x.shape
         assert C == 96
         hs, ws = (h - 4) // 2 + 1, (w - 4) // 2 + 1
+        if want_similar:
+            # se_attention_ex refuses `similar_out` where the R x R scores cannot be formed (R Rp 4 >= 2^31, R = h/2 * w/2,
+            # Rp = R rounded up to 32 / 64 keys): the streaming form runs there.  Checked first: the output alone is L x L floats.
+            R = (h // 2) * (w // 2)
+            chunk = 64 if bf16 else 32
+            if R * ((R + chunk - 1) // chunk * chunk) * 4 >= 2 ** 31:
+                raise SketchEditHipError("se_attention_ex: similar_out (the %d x %d score matrix) is not available on a %dx%d "
+                                         "feature map: it runs in the streaming form, which never forms it"
+                                         % (hs * ws, hs * ws, h, w))
         out = torch.empty_like(x)
         sim = torch.empty((B, hs * ws, hs, ws), dtype=torch.float32, device=x.device) if want_similar else None
         if self.lib.se_attention_ex(self.h, self._stream(), _ptr(x), _ptr(mask_full), _ptr(out), _ptr(sim), B, h, w,

@@ -1675,21 +1675,47 @@ int att_row_stride(int R, bool bf) {
   return Rp;
 }
 
+// Which attention form runs on an h x w feature map: ATT_STREAMING (se_att_stream.hip: nothing R x R) wherever the
+// materialised space-to-depth form cannot address its R x R matrices with 32-bit offsets (R Rp 4 >= 2^31), and everywhere
+// with SE_ATT_STREAM=1 unless `similar_out` -- P itself -- is asked for; otherwise the materialised form (ATT_V2), or the
+// patch form (ATT_V1) when SE_ATT_V1=1 in fp32.  `similar_out` is refused exactly where R Rp 4 >= 2^31, whatever the options
+// (Engine.attention checks the same rule before it allocates the L x L output).
+enum { ATT_V1 = 0, ATT_V2 = 1, ATT_STREAMING = 2 };
+int att_form(int h, int w, bool bf, bool want_similar) {
+  const int R = (h / 2) * (w / 2), Rp = att_row_stride(R, bf);
+  const bool fits = (double)R * Rp * 4.0 < 2147483648.0;
+  const bool v2 = attention_v2_enabled() || bf;       // the bf16 path exists in the space-to-depth form only
+  if (want_similar && !fits) return ATT_STREAMING;       // (run_attention refuses: similar_out is P itself)
+  if (opt(OPT_ATT_STREAM) == 1 && !want_similar) return ATT_STREAMING;
+  if (!v2) return ATT_V1;
+  return fits ? ATT_V2 : ATT_STREAMING;
+}
+
 int run_attention(se_ctx* c, Plan& P, Act& x, const float* mask_full, Act& out, float* similar_nchw) {
   const int h = x.H, w = x.W, B = P.B;
   const int hs = (h - 4) / 2 + 1, ws = (w - 4) / 2 + 1, L = hs * ws, Lp = (L + 31) & ~31;
   const bool bf = c->bf16;
-  const bool v2 = attention_v2_enabled() || bf;       // the bf16 path exists in the space-to-depth form only
+  const int form = att_form(h, w, bf, similar_nchw != nullptr);
+  const bool v2 = form == ATT_V2, stream = form == ATT_STREAMING;
   const int hc = h / 2, wc = w / 2, R = hc * wc;
   const int Rp = att_row_stride(R, bf);
   const int guard = (wc + 8 + 63) & ~63;               // floats; att2_ptilde_kernel reads up to wc + 5 columns outside a row
-  if (v2 && (double)R * Rp * 4.0 >= 2147483648.0) return P.rc = fail(c, "attention: %dx%d feature map too large", h, w);
+  if (stream && similar_nchw)
+    return P.rc = fail(c, "attention: similar_out (the %d x %d score matrix) is not available on a %dx%d feature map: "
+                          "it runs in the streaming form, which never forms it", L, L, h, w);
+  // the patch form addresses the L x Lp scores with 32-bit offsets
+  if (form == ATT_V1 && (double)L * Lp * 4.0 >= 2147483648.0)
+    return P.rc = fail(c, "attention (SE_ATT_V1 patch form): %dx%d feature map too large", h, w);
   // fp32 scratch is sized in floats whatever the activation type
   float* part = P.alloc_raw((size_t)B * COLREDUCE_SPLITS * 96);
   float* rn = P.alloc_raw((size_t)B * 96);
   float* xn = P.alloc_raw(bf ? ((size_t)B * h * w * 96 + 1) / 2 : (size_t)B * h * w * 96);
   float *valid = nullptr, *S = nullptr, *S2 = nullptr, *xT = nullptr, *stats = nullptr;
-  if (v2) {
+  if (stream) {      // O(R): validR, kmul, kadd; (max, 1 / sum) per query; V^T plus the tail the out pass may read
+    valid = P.alloc_raw(3 * (size_t)B * Rp);
+    stats = P.alloc_raw((size_t)B * R * 2);
+    xT = P.alloc_raw((bf ? (size_t)B * 4 * 96 * Rp / 2 : (size_t)B * 4 * 96 * Rp) + att_stream_xt_tail());
+  } else if (v2) {
     valid = P.alloc_raw(7 * ((size_t)B * Rp + guard) + (size_t)B * 768 + (size_t)B * hc * 384);      // validR, kmul, kadd (+ fp16-E form: kadd2, ea4, ea, eb), each behind its guard band; emean, epart
     stats = P.alloc_raw((size_t)B * R * 2);    // fused streaming pass: (row max, 1 / row sum) per query
     xT = P.alloc_raw(bf ? (size_t)B * 4 * 96 * Rp / 2 : (size_t)B * 4 * 96 * Rp);
@@ -1707,7 +1733,12 @@ int run_attention(se_ctx* c, Plan& P, Act& x, const float* mask_full, Act& out, 
     a.x = x.p; a.rn = rn; a.xn = xn; a.hard = mask_full; a.out = out.p;
     a.B = B; a.h = h; a.w = w; a.hs = hs; a.ws = ws; a.L = L; a.Lp = Lp;
     a.scale = 10.f; a.th = 0.1f;                        // editline_g.py:35-38
-    if (v2) {
+    if (stream) {
+      a.hc = hc; a.wc = wc; a.R = R; a.Rp = Rp; a.bf16 = bf ? 1 : 0;
+      a.validR = valid; a.kmul = valid + (size_t)B * Rp; a.kadd = valid + 2 * (size_t)B * Rp;
+      a.xT = xT; a.stats = stats;
+      HIPCHK(c, launch_attention_stream(a, c->st));
+    } else if (v2) {
       a.hc = hc; a.wc = wc; a.R = R; a.Rp = Rp; a.bf16 = bf ? 1 : 0;
       a.validR = valid + guard; a.xT = xT; a.E = S + guard; a.P = S2; a.stats = stats; a.guard = guard; a.similar = similar_nchw;
       a.kmul = valid + ((size_t)B * Rp + guard) + guard; a.kadd = valid + 2 * ((size_t)B * Rp + guard) + guard;
@@ -2452,7 +2483,17 @@ int se_attention_ex(se_ctx* c, void* stream, const float* x, const float* mask_f
   begin_call(c, stream, exec_flags & SE_FLAG_BF16);
   const bool bf = c->bf16;
   const int R = (h / 2) * (w / 2), Rp = att_row_stride(R, true) + 64;
-  const size_t bytes = ((size_t)B * h * w * 96 * 3 + 2 * (size_t)B * R * Rp + (size_t)B * Rp * (7 + 4 * 96) + 64 * 96 * B + 2 * (size_t)B * R + 9 * (size_t)(w / 2 + 72) + (size_t)B * (768 + (h / 2) * 384)) * 4 + (1 << 16);
+  // refusals of run_attention, before anything is allocated: similar_out at a streaming size, the patch form beyond its range
+  const int form = att_form(h, w, bf, similar_out != nullptr);
+  const int L = ((h - 4) / 2 + 1) * ((w - 4) / 2 + 1), Lp = (L + 31) & ~31;
+  if (form == ATT_STREAMING && similar_out)
+    return fail(c, "attention: similar_out (the %d x %d score matrix) is not available on a %dx%d feature map: "
+                   "it runs in the streaming form, which never forms it", L, L, h, w);
+  if (form == ATT_V1 && (double)L * Lp * 4.0 >= 2147483648.0)
+    return fail(c, "attention (SE_ATT_V1 patch form): %dx%d feature map too large", h, w);
+  // the R x R matrices E and P exist in the materialised form only (the streaming form's scratch is O(R))
+  const size_t rr = form == ATT_STREAMING ? 0 : 2 * (size_t)B * R * Rp;
+  const size_t bytes = ((size_t)B * h * w * 96 * 3 + rr + (size_t)B * Rp * (7 + 4 * 96) + 64 * 96 * B + 2 * (size_t)B * R + 9 * (size_t)(w / 2 + 72) + (size_t)B * (768 + (h / 2) * 384)) * 4 + (1 << 16);
   char* ws = nullptr;
   HIPCHK(c, hipMalloc(&ws, bytes));
   c->arena.reset(ws, bytes, false);

@@ -1564,6 +1564,15 @@ static bool att_fused(bool bf16, int Rp, int wc) {
   return f32mode < 0 ? (Rp <= 1024 || att_lds_form(wc)) : f32mode == 1;
 }
 
+// The O(R) preparation shared by the materialised form and the streaming form (se_att_stream.hip, via launch_att2_prep):
+// xn, the key tables, the transposed values.  The caller checks the guard precondition and opens the profiler scope.
+template <bool BF16>
+static void enqueue_att2_prep(const AttParams& p, hipStream_t st) {
+  const long n = (long)p.B * p.h * p.w * (BF16 ? 12 : 24);
+  hipLaunchKernelGGL(att2_prep_kernel<BF16>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(att2_transpose_kernel<BF16>, dim3(p.Rp / 32, 4, p.B), dim3(256), 0, st, p);
+}
+
 template <bool BF16>
 static hipError_t launch_attention_v2_t(const AttParams& p0, hipStream_t st) {
   AttParams p = p0;
@@ -1582,8 +1591,7 @@ static hipError_t launch_attention_v2_t(const AttParams& p0, hipStream_t st) {
     // GEMM itself as finite values; an unguarded read is multiplied by kmul = 0, which only a finite value survives.)
     if (p.guard < p.wc + 8 || ((n + 255) / 256) * 256 < (long)p.guard) return hipErrorInvalidValue;
     ProfScope ps_(st, PL_ATT_PREP);
-    hipLaunchKernelGGL(att2_prep_kernel<BF16>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(att2_transpose_kernel<BF16>, dim3(p.Rp / 32, 4, p.B), dim3(256), 0, st, p);
+    enqueue_att2_prep<BF16>(p, st);
     if (p.e16) {      // offsets of the fp16-E form (att2_emean1_kernel)
       const long nr = (long)p.B * p.Rp;
       hipLaunchKernelGGL(att2_emean1_kernel<BF16>, dim3(p.hc, p.B), dim3(384), 0, st, p);
@@ -1754,6 +1762,15 @@ static hipError_t launch_attention_v2_t(const AttParams& p0, hipStream_t st) {
   }
   return hipGetLastError();
 }
+hipError_t launch_att2_prep(const AttParams& p, hipStream_t st) {
+  const long n = (long)p.B * p.h * p.w * (p.bf16 ? 12 : 24);
+  if (((n + 255) / 256) * 256 < (long)p.guard) return hipErrorInvalidValue;
+  ProfScope ps_(st, PL_ATT_PREP);
+  if (p.bf16) enqueue_att2_prep<true>(p, st);
+  else enqueue_att2_prep<false>(p, st);
+  return hipGetLastError();
+}
+
 static hipError_t launch_attention_v2(const AttParams& p, hipStream_t st) {
   return p.bf16 ? launch_attention_v2_t<true>(p, st) : launch_attention_v2_t<false>(p, st);
 }

@@ -14,7 +14,8 @@ namespace se {
 // figures.  Off by default; when off the launch wrappers add nothing.
 // ---------------------------------------------------------------------------------------------
 enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL_WINO_N192, PL_WINO_N96, PL_WINO_UP96, PL_SMALL_CONV, PL_PACK, PL_COLREDUCE,
-                 PL_ATT_PREP, PL_ATT_SCORE, PL_ATT_SOFTMAX, PL_ATT_BOXSUM, PL_ATT_PV, PL_LAYOUT, PL_COUNT };
+                 PL_ATT_PREP, PL_ATT_SCORE, PL_ATT_SOFTMAX, PL_ATT_BOXSUM, PL_ATT_PV, PL_LAYOUT,
+                 PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -54,7 +55,8 @@ hipError_t ensure_max_lds(const void* func, int bytes);
   X(GCONV_FAST, 1) X(GCONV_VARIANT_N192, 0) X(GCONV_VARIANT_N96, 0) X(GCONV_VARIANT_N48, 0) X(GCONV_VARIANT_N24, 0) \
   X(LL_STAGES, 2) X(FORK_DEFAULT, 1) X(LL_WINO_MIN_WG, 64) X(LL_WINO48_MIN_WG, 128)                                                                                               \
   X(ATT_V1, 0) X(ATT_FUSED, -1) X(ATT_FUSED_BF16, -1) X(ATT_PTILDE_LDS, 1) X(ATT_STATS_LDS, 1) X(ATT_E16, 1)      \
-  X(ATT_SYM, 1) X(ATT_PV_PT, -1)
+  X(ATT_SYM, 1) X(ATT_PV_PT, -1)                                                                                \
+  X(ATT_STREAM, 0)       /* attention form: 0 by size (streaming where R Rp 4 >= 2^31), 1 streaming wherever possible */
 enum Opt {
 #define X(name, dflt) OPT_##name,
   SE_OPTIONS(X)
@@ -338,5 +340,11 @@ struct AttParams {
 };
 hipError_t launch_attention(const AttParams& p, hipStream_t st);    // p.E != null: space-to-depth form, else the patch form
 bool attention_v2_enabled();
+// O(R) preparation of the space-to-depth form: xn, key tables (validR, kmul, kadd), transposed values xT (att2_prep, _transpose)
+hipError_t launch_att2_prep(const AttParams& p, hipStream_t st);
+// streaming form (se_att_stream.hip): E = P = null; needs xn, xT (plus att_stream_xt_tail() zeroed floats behind it), validR,
+// kmul, kadd, stats ([B][R][2]); nothing R x R
+hipError_t launch_attention_stream(const AttParams& p, hipStream_t st);
+int att_stream_xt_tail();
 
 }  // namespace se
