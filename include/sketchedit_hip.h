@@ -150,6 +150,43 @@ int se_inference_u8io(se_ctx* ctx, void* stream, const unsigned char* image_u8, 
 int se_quantize_u8(se_ctx* ctx, void* stream, const float* composed, const float* mask, unsigned char* rgb_out,
                    unsigned char* mask_u8_out, int B, int H, int W);
 
+/* ---- the demo's per-request steps on the device (demo.py:39-73, process_image) --------------------------------------
+ * Pillow's `Image.resize` of an 'L' or 'RGB' uint8 image, bit for bit: the resampling filters below (values as
+ * PIL.Image.Resampling; demo.py uses the default, BICUBIC).  NEAREST, a box and reducing_gap are not provided.  Per axis
+ * the host computes Pillow's fixed-point coefficient table in double precision (cached in the ctx per (in, out, filter),
+ * the 64 most recently used); the device runs a horizontal pass into a uint8 intermediate and a vertical pass, int32
+ * accumulation, each pass skipped where its axis keeps its size (both unchanged: a copy).  The intermediate and the
+ * tables live in the ctx (device memory it grows as needed); a call that uses them on another stream than the previous
+ * one is ordered after it through an event. */
+enum { SE_RESAMPLE_LANCZOS = 1, SE_RESAMPLE_BILINEAR = 2, SE_RESAMPLE_BICUBIC = 3 };
+
+/* in (B,Hin,Win,C) uint8 -> out (B,Hout,Wout,C) uint8, C in {1, 3}: Image.resize((Wout, Hout), filter) of every image.  A
+ * filter longer than the kernels take (a bicubic downscale by more than ~2000x) is refused. */
+int se_resize_u8(se_ctx* ctx, void* stream, const unsigned char* in, int B, int Hin, int Win, int C, unsigned char* out,
+                 int Hout, int Wout, int filter);
+
+/* demo.py:40-56 for ONE request: image_u8 (Hi,Wi,3) RGB and sketch_u8 (Hs,Ws) 'L' uint8, raw sizes (the sketch's may differ
+ * from the image's) -> the forward's fp32 inputs at the working size H x W (multiples of 8, >= 16):
+ * image_out (3,H,W) = (v/255 - 0.5)/0.5 of the BICUBIC resize (the table se_dequantize_u8 uses), sketch_out (1,H,W) =
+ * (resized v > 0).  The last resize pass writes these directly.  The outputs may point into a batch (a request's slot of a
+ * (B,3,H,W) / (B,1,H,W) pair).  Either pair may be NULL.  Bit-identical to the host steps with Pillow and torch. */
+int se_prepare_u8(se_ctx* ctx, void* stream, const unsigned char* image_u8, int Hi, int Wi, const unsigned char* sketch_u8, int Hs,
+                  int Ws, float* image_out, float* sketch_out, int H, int W);
+
+/* The whole of demo.py's process_image for B requests of one raw size as one call: se_prepare_u8 at the working size
+ * (Hi/8*8, Wi/8*8), the forward with the fused output quantisation of se_inference_u8 (the demo's clamp cannot change a
+ * value: see se_quantize_u8), and the BICUBIC resize of the uint8 result back to Hi x Wi.  image_u8 (B,Hi,Wi,3),
+ * sketch_u8 (B,Hs,Ws), rgb_out (B,Hi,Wi,3), all uint8 device arrays.  A working size under 16 is refused, as the demo's
+ * host path refuses it.  flags as se_inference_u8; workspace: se_edit_u8_workspace_bytes(ctx, B, Hi, Wi). */
+int se_edit_u8(se_ctx* ctx, void* stream, const unsigned char* image_u8, const unsigned char* sketch_u8, unsigned char* rgb_out,
+               void* workspace, size_t workspace_bytes, int B, int Hi, int Wi, int Hs, int Ws, int flags);
+size_t se_edit_u8_workspace_bytes(se_ctx* ctx, int B, int Hi, int Wi);
+
+/* Host only (no HIP call, no ctx): the coefficient table the resize uses for one axis.  Returns ksize, the taps per output
+ * (-1: bad arguments); when bounds (2*out ints: first input index, tap count) and k (cap >= out*ksize ints, fixed point
+ * with 22 fractional bits, rows zero padded to ksize) are given, fills them.  Lets a test compare the tables with Pillow's. */
+int se_resample_coeffs(int in, int out, int filter, int* bounds, int* k, size_t cap);
+
 /* ---- measurement support (no reference counterpart; used by bench.py) ----------------------------
  * se_profile_enable(ctx, 1): wrap every kernel launch of subsequent forwards in a pair of HIP events
  * recorded on the launch stream; se_profile_report synchronises the device and writes a JSON array

@@ -15,10 +15,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SKETCHEDIT_HIP_LIB points at another build of the same library (developer builds, e.g. tools/wino_trace.py)
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip",
+SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
            "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
+RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
 FLAG_USE_CAM, FLAG_POOL_MAX, FLAG_NO_MASK_CC, FLAG_NO_MASK_COARSE, FLAG_JOINT_TRAIN_INP = 1, 2, 4, 8, 16
 FLAG_LOW_LATENCY, FLAG_GRAPH, FLAG_PACKED_OUT, FLAG_BF16, FLAG_CONSERVATIVE = 32, 64, 128, 256, 512   # execution options (include/sketchedit_hip.h)
 # Which calls run in the low-latency mode unless the caller says otherwise: at most three 256x256 images' worth of pixels, or ONE
@@ -33,7 +34,8 @@ LOW_LATENCY_MAX_SINGLE_IMAGE = 512 * 512
 SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_weights", "se_weights_ready",
            "se_workspace_bytes", "se_netM_forward", "se_netM_forward_ex", "se_netG_forward", "se_netG_forward_taps", "se_inference", "se_inference_u8", "se_gated_conv2d",
            "se_gated_conv2d_ex", "se_attention", "se_attention_ex", "se_quantize_u8", "se_dequantize_u8", "se_inference_u8io", "se_profile_enable",
-           "se_profile_report", "se_debug_set_option", "se_debug_get_option", "se_debug_reset_options"]
+           "se_profile_report", "se_debug_set_option", "se_debug_get_option", "se_debug_reset_options",
+           "se_resize_u8", "se_prepare_u8", "se_edit_u8", "se_edit_u8_workspace_bytes", "se_resample_coeffs"]
 
 
 class SketchEditHipError(RuntimeError):
@@ -146,6 +148,16 @@ def load_library():
         lib.se_dequantize_u8.restype = ci
         lib.se_inference_u8io.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]
         lib.se_inference_u8io.restype = ci
+        lib.se_resize_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci]
+        lib.se_resize_u8.restype = ci
+        lib.se_prepare_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, c_f, c_f, ci, ci]
+        lib.se_prepare_u8.restype = ci
+        lib.se_edit_u8.argtypes = [vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ci, ci]
+        lib.se_edit_u8.restype = ci
+        lib.se_edit_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
+        lib.se_edit_u8_workspace_bytes.restype = sz
+        lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
+        lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
         lib.se_profile_enable.restype = ci
         lib.se_profile_report.argtypes = [vp, ctypes.c_char_p, sz]
@@ -222,6 +234,18 @@ def _check_dev(*ts):
             raise SketchEditHipError("expected contiguous float32 CUDA(HIP) tensors")
 
 
+def upload_u8(a, device):
+    """A uint8 array (numpy or tensor) on the device.  np.asarray of a PIL image is read-only: torch warns about wrapping it
+    without a copy, but the wrapper is only read, to upload it."""
+    import warnings
+    import torch
+    if isinstance(a, np.ndarray):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            a = torch.from_numpy(np.ascontiguousarray(a))
+    return a.to(device, non_blocking=True).contiguous()
+
+
 def _check_dev_u8(*ts):
     import torch
     for t in ts:
@@ -281,10 +305,13 @@ class Engine:
 
     # ---- workspace -----------------------------------------------------------------------------
     def workspace(self, B, H, W):
-        import torch
         need = self.lib.se_workspace_bytes(self.h, B, H, W)
         if need == 0:
             self._err("se_workspace_bytes")
+        return self._workspace_bytes(need)
+
+    def _workspace_bytes(self, need):
+        import torch
         with self._ws_lock:
             cur = torch.cuda.current_stream(self.device)
             if self._ws is None or self._ws.numel() < need:
@@ -481,6 +508,68 @@ class Engine:
                                       ws.numel(), B, H, W, flags):
             self._err("se_inference_u8io")
         return rgb, m8
+
+    # ---- the demo's per-request steps (demo.py:39-73) on the device ---------------------------------------------------
+    def resize_u8(self, x, size, filter=RESAMPLE_BICUBIC, out=None):
+        """Pillow's Image.resize((W, H), filter) of every image of x, bit for bit (se_resize_u8): x (B,Hin,Win,C) with C in
+        {1, 3}, or (B,Hin,Win) for C = 1, uint8 on the device; size = (H, W) -> the same layout at H x W."""
+        import torch
+        _check_dev_u8(x)
+        flat = x.dim() == 3
+        B, Hin, Win = x.shape[:3]
+        C = 1 if flat else x.shape[3]
+        H, W = size
+        if out is None:
+            out = torch.empty((B, H, W) if flat else (B, H, W, C), dtype=torch.uint8, device=x.device)
+        _check_dev_u8(out)
+        if out.numel() != B * H * W * C:
+            raise SketchEditHipError("resize_u8: `out` has %d elements, expected %d" % (out.numel(), B * H * W * C))
+        if self.lib.se_resize_u8(self.h, self._stream(), _ptr(x), B, Hin, Win, C, _ptr(out), H, W, int(filter)):
+            self._err("se_resize_u8")
+        return out
+
+    def prepare_u8(self, image_u8, sketch_u8, H, W, out=None):
+        """demo.py:40-56 for ONE request (se_prepare_u8): image_u8 (Hi,Wi,3) RGB and sketch_u8 (Hs,Ws) uint8 on the device
+        (raw sizes; they may differ) -> (image (1,3,H,W), sketch (1,1,H,W)) fp32 at the working size H x W.
+        `out` = (image, sketch): contiguous fp32 tensors of those sizes, e.g. one request's slot of a batch."""
+        import torch
+        _check_dev_u8(image_u8, sketch_u8)
+        Hi, Wi = image_u8.shape[:2]
+        Hs, Ws = sketch_u8.shape[:2]
+        if image_u8.shape[2:] != (3,) or sketch_u8.dim() != 2:
+            raise SketchEditHipError("prepare_u8: expected image (H,W,3) and sketch (H,W) uint8 arrays")
+        if out is None:
+            out = (torch.empty((1, 3, H, W), dtype=torch.float32, device=image_u8.device),
+                   torch.empty((1, 1, H, W), dtype=torch.float32, device=image_u8.device))
+        image, sketch = out
+        _check_dev(image, sketch)
+        if image.numel() != 3 * H * W or sketch.numel() != H * W:
+            raise SketchEditHipError("prepare_u8: `out` tensors do not hold one %dx%d request" % (H, W))
+        if self.lib.se_prepare_u8(self.h, self._stream(), _ptr(image_u8), Hi, Wi, _ptr(sketch_u8), Hs, Ws, _ptr(image),
+                                  _ptr(sketch), H, W):
+            self._err("se_prepare_u8")
+        return image, sketch
+
+    def edit_u8(self, image_u8, sketch_u8, flags, low_latency=None):
+        """demo.py's process_image for B requests of one raw size as ONE library call (se_edit_u8): image_u8 (B,Hi,Wi,3),
+        sketch_u8 (B,Hs,Ws) uint8 on the device -> rgb (B,Hi,Wi,3) uint8 on the device.  The working size is
+        (Hi//8*8, Wi//8*8); low_latency: None = by the size of the forward (B at the working size)."""
+        import torch
+        _check_dev_u8(image_u8, sketch_u8)
+        B, Hi, Wi, _ = image_u8.shape
+        Hs, Ws = sketch_u8.shape[1:3]
+        if sketch_u8.dim() != 3 or sketch_u8.shape[0] != B:
+            raise SketchEditHipError("edit_u8: expected sketch (B,H,W) uint8")
+        need = self.lib.se_edit_u8_workspace_bytes(self.h, B, Hi, Wi)
+        if need == 0:
+            self._err("se_edit_u8_workspace_bytes")
+        ws = self._workspace_bytes(need)
+        rgb = torch.empty((B, Hi, Wi, 3), dtype=torch.uint8, device=image_u8.device)
+        flags = (flags & 31) | self.exec_flags(B, Hi // 8 * 8, Wi // 8 * 8, low_latency, False)
+        if self.lib.se_edit_u8(self.h, self._stream(), _ptr(image_u8), _ptr(sketch_u8), _ptr(rgb), _ptr(ws), ws.numel(), B, Hi,
+                               Wi, Hs, Ws, flags):
+            self._err("se_edit_u8")
+        return rgb
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):
         """Inference into ONE (B,4,H,W) buffer `out`: planes 0-2 composed, plane 3 the soft mask -- the unit the

@@ -10,6 +10,7 @@
 #include "se_kernels.h"
 
 #include <cstdarg>
+#include <cstdint>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -179,6 +180,21 @@ struct se_ctx {
   };
   unsigned long long graph_clock = 0;
   std::vector<GraphEntry> graphs;                     // SE_FLAG_GRAPH: captured forwards, keyed by every argument
+  // Pillow-exact resize (se_resize.hip): coefficient tables per (in, out, filter), least recently used evicted beyond 64;
+  // the uint8 intermediate of the two passes; the stream the last resize ran on (a call on another stream waits for it)
+  struct ResampleTable {
+    int in, out, filter, ksize;
+    std::vector<int> host;            // bounds (2 out) then weights (out ksize): the upload's source, kept while cached
+    int* dev = nullptr;
+    unsigned long long last_use = 0;
+  };
+  std::vector<ResampleTable> rs_tables;
+  unsigned long long rs_clock = 0;
+  unsigned char* rs_scratch = nullptr;
+  size_t rs_scratch_bytes = 0;
+  hipStream_t rs_stream = nullptr;
+  bool rs_used = false;
+  hipEvent_t rs_event = nullptr;
 };
 
 namespace {
@@ -1883,12 +1899,125 @@ void evict_lru_graph(se_ctx* c) {
   c->graphs.erase(c->graphs.begin() + lru);
 }
 
+// ---- Pillow-exact resize (se_resize.hip): the ctx's tables and intermediate, and the one host routine behind the C-ABI ----
+// Every resize resource is used in the order of ONE stream: a call on another stream than the previous one first waits for
+// the previous stream's work (event), so freeing or overwriting a resource only needs that stream drained.
+int rs_enter(se_ctx* c, hipStream_t st) {
+  if (c->rs_used && c->rs_stream != st) {
+    if (!c->rs_event) HIPCHK(c, hipEventCreateWithFlags(&c->rs_event, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->rs_event, c->rs_stream));
+    HIPCHK(c, hipStreamWaitEvent(st, c->rs_event, 0));
+  }
+  c->rs_stream = st;
+  c->rs_used = true;
+  return 0;
+}
+
+const se_ctx::ResampleTable* rs_table(se_ctx* c, int in, int out, int filter) {
+  for (auto& t : c->rs_tables)
+    if (t.in == in && t.out == out && t.filter == filter) { t.last_use = ++c->rs_clock; return &t; }
+  const int ksize = resample_ksize(in, out, filter);
+  if (ksize < 0) { fail(c, "resize: bad arguments (in %d, out %d, filter %d)", in, out, filter); return nullptr; }
+  if (ksize > RESAMPLE_MAX_KSIZE) { fail(c, "resize: %d -> %d needs %d taps per output, more than the kernels take (%d)", in, out, ksize, RESAMPLE_MAX_KSIZE); return nullptr; }
+  if (c->rs_tables.size() >= 64) {
+    size_t lru = 0;
+    for (size_t i = 1; i < c->rs_tables.size(); ++i)
+      if (c->rs_tables[i].last_use < c->rs_tables[lru].last_use) lru = i;
+    (void)hipStreamSynchronize(c->rs_stream);       // earlier resizes may still read it
+    (void)hipFree(c->rs_tables[lru].dev);
+    c->rs_tables.erase(c->rs_tables.begin() + lru);
+  }
+  se_ctx::ResampleTable t;
+  t.in = in; t.out = out; t.filter = filter; t.ksize = ksize;
+  t.host.resize((size_t)out * (2 + ksize));
+  resample_coeffs(in, out, filter, t.host.data(), t.host.data() + 2 * (size_t)out);
+  hipError_t e = hipMalloc(&t.dev, t.host.size() * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpyAsync(t.dev, t.host.data(), t.host.size() * sizeof(int), hipMemcpyHostToDevice, c->rs_stream);
+  if (e != hipSuccess) {
+    if (t.dev) (void)hipFree(t.dev);
+    fail(c, "resize: coefficient upload failed: %s", hipGetErrorString(e));
+    return nullptr;
+  }
+  t.last_use = ++c->rs_clock;
+  c->rs_tables.push_back(std::move(t));
+  return &c->rs_tables.back();
+}
+
+unsigned char* rs_scratch(se_ctx* c, size_t bytes) {
+  if (bytes > c->rs_scratch_bytes) {
+    if (c->rs_scratch) {
+      (void)hipStreamSynchronize(c->rs_stream);
+      (void)hipFree(c->rs_scratch);
+      c->rs_scratch = nullptr; c->rs_scratch_bytes = 0;
+    }
+    const size_t sz = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+    if (hipMalloc(&c->rs_scratch, sz) != hipSuccess) { c->rs_scratch = nullptr; fail(c, "resize: cannot allocate %zu bytes", sz); return nullptr; }
+    c->rs_scratch_bytes = sz;
+  }
+  return c->rs_scratch;
+}
+
+// in (B,Hin,Win,C) uint8 -> the resize to Hout x Wout, written as `o` says (o.H, o.W are set here).  Called under the ctx lock.
+int resize_locked(se_ctx* c, hipStream_t st, const unsigned char* in, int B, int Hin, int Win, int C, ResizeOut o, int Hout,
+                  int Wout, int filter) {
+  if (!in || (o.mode == RESIZE_OUT_U8 ? !o.u8 : !o.f32)) return fail(c, "null pointer argument");
+  if (B < 1 || B > 65535 || Hin < 1 || Win < 1 || Hout < 1 || Wout < 1 || Hin > 65535 || Hout > 65535 || (C != 1 && C != 3))
+    return fail(c, "resize: bad shape B=%d %dx%dx%d -> %dx%d (C in {1, 3}, heights and B < 65536)", B, Hin, Win, C, Hout, Wout);
+  if (filter != SE_RESAMPLE_BILINEAR && filter != SE_RESAMPLE_BICUBIC && filter != SE_RESAMPLE_LANCZOS)
+    return fail(c, "resize: unsupported filter %d", filter);
+  if (o.mode == RESIZE_OUT_IMAGE_F32) o.lut = c->lut8;
+  if (rs_enter(c, st)) return 1;
+  set_profiler(&c->prof);
+  o.H = Hout; o.W = Wout;
+  const bool need_h = Win != Wout, need_v = Hin != Hout;
+  if (!need_h && !need_v) {       // Image.resize returns a copy
+    if (o.mode == RESIZE_OUT_U8) {
+      HIPCHK(c, hipMemcpyAsync(o.u8, in, (size_t)B * Hin * Win * C, hipMemcpyDeviceToDevice, st));
+      return 0;
+    }
+    // the dequantisation kernel moves 4 pixels per lane (dword loads, float4 stores)
+    if (((size_t)Hin * Win) % 4 || ((uintptr_t)in & 3) || ((uintptr_t)o.f32 & 15))
+      return fail(c, "resize: an unresized fp32 output needs H W %% 4 == 0, a 4-byte aligned input and a 16-byte aligned output");
+    // (the kernel stages the whole table in LDS whichever output it writes: always the ctx's table, never o.lut)
+    if (o.mode == RESIZE_OUT_IMAGE_F32 && C == 3)
+      HIPCHK(c, launch_dequantize_u8(in, nullptr, c->lut8, o.f32, nullptr, B, Hin, Win, st));
+    else if (o.mode == RESIZE_OUT_SKETCH_F32 && C == 1)
+      HIPCHK(c, launch_dequantize_u8(nullptr, in, c->lut8, nullptr, o.f32, B, Hin, Win, st));
+    else
+      return fail(c, "resize: fp32 outputs are a 3-channel image or a 1-channel sketch");
+    return 0;
+  }
+  const se_ctx::ResampleTable* th = need_h ? rs_table(c, Win, Wout, filter) : nullptr;
+  const se_ctx::ResampleTable* tv = need_v ? rs_table(c, Hin, Hout, filter) : nullptr;
+  if ((need_h && !th) || (need_v && !tv)) return 1;
+  // the second lookup may have moved the table vector: look the first table up again (it is the most recently used
+  // entry, so the second lookup did not evict it)
+  if (need_h && need_v) th = rs_table(c, Win, Wout, filter);
+  const unsigned char* src = in;
+  if (need_h) {
+    ResizeOut oh = o;
+    if (need_v) {
+      unsigned char* mid = rs_scratch(c, (size_t)B * Hin * Wout * C);
+      if (!mid) return 1;
+      oh.mode = RESIZE_OUT_U8; oh.u8 = mid; oh.H = Hin;
+      src = mid;
+    }
+    const int* d = th->dev;
+    HIPCHK(c, launch_resample_h(in, d, d + 2 * (size_t)Wout, th->host.data(), th->ksize, B, Hin, Win, Wout, C, oh, st));
+  }
+  if (need_v) {
+    const int* d = tv->dev;
+    HIPCHK(c, launch_resample_v(src, d, d + 2 * (size_t)Hout, tv->ksize, B, Hin, Hout, Wout, C, o, st));
+  }
+  return 0;
+}
+
 }  // namespace
 
 // ====================================================================================================
 extern "C" {
 
-const char* se_version(void) { return "sketchedit_hip 0.1 (gfx950)"; }
+const char* se_version(void) { return "sketchedit_hip 0.2 (gfx950)"; }
 
 int se_create(int device_id, se_ctx** out) {
   if (!out) return 1;
@@ -1967,6 +2096,9 @@ void se_destroy(se_ctx* c) {
   if (c->wconv1_j4.d_wdw) (void)hipFree(c->wconv1_j4.d_wdw);
   if (c->zeros) (void)hipFree(c->zeros);
   if (c->lut8) (void)hipFree(c->lut8);
+  for (auto& t : c->rs_tables) (void)hipFree(t.dev);
+  if (c->rs_scratch) (void)hipFree(c->rs_scratch);
+  if (c->rs_event) (void)hipEventDestroy(c->rs_event);
   for (auto& e : c->prof.pool) (void)hipEventDestroy(e);
   drop_graphs(c);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -2298,6 +2430,88 @@ int se_quantize_u8(se_ctx* c, void* stream, const float* composed, const float* 
   set_profiler(&c->prof);
   HIPCHK(c, launch_quantize_u8(composed, mask, rgb_out, mask_u8_out, B, H, W, (hipStream_t)stream));
   return 0;
+}
+
+// ---- the demo's per-request steps (demo.py:39-73) on the device -----------------------------------------------------
+int se_resize_u8(se_ctx* c, void* stream, const unsigned char* in, int B, int Hin, int Win, int C, unsigned char* out, int Hout,
+                 int Wout, int filter) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  ResizeOut o{RESIZE_OUT_U8, out, nullptr, nullptr, 0, 0};
+  return resize_locked(c, (hipStream_t)stream, in, B, Hin, Win, C, o, Hout, Wout, filter);
+}
+
+namespace {
+// demo.py:40-56 for B requests of one raw size: the BICUBIC resizes, written as the forward's fp32 inputs
+int prepare_locked(se_ctx* c, hipStream_t st, const unsigned char* image_u8, int B, int Hi, int Wi, const unsigned char* sketch_u8,
+                   int Hs, int Ws, float* image_out, float* sketch_out, int H, int W) {
+  if (check_dims(c, B, H, W)) return 1;
+  if ((image_out && !image_u8) || (sketch_out && !sketch_u8)) return fail(c, "null pointer argument");
+  if (image_out) {
+    ResizeOut o{RESIZE_OUT_IMAGE_F32, nullptr, image_out, c->lut8, 0, 0};
+    if (resize_locked(c, st, image_u8, B, Hi, Wi, 3, o, H, W, SE_RESAMPLE_BICUBIC)) return 1;
+  }
+  if (sketch_out) {
+    ResizeOut o{RESIZE_OUT_SKETCH_F32, nullptr, sketch_out, nullptr, 0, 0};
+    if (resize_locked(c, st, sketch_u8, B, Hs, Ws, 1, o, H, W, SE_RESAMPLE_BICUBIC)) return 1;
+  }
+  return 0;
+}
+
+// working size of a raw request (demo.py:43-45), or an error where the host path refuses it
+int edit_dims(se_ctx* c, int B, int Hi, int Wi, int* H, int* W) {
+  *H = Hi / 8 * 8; *W = Wi / 8 * 8;
+  if (B < 1 || *H < 16 || *W < 16) return fail(c, "image too small: %dx%d (working size %dx%d, needs >= 16)", Wi, Hi, *W, *H);
+  return 0;
+}
+}  // namespace
+
+int se_prepare_u8(se_ctx* c, void* stream, const unsigned char* image_u8, int Hi, int Wi, const unsigned char* sketch_u8, int Hs,
+                  int Ws, float* image_out, float* sketch_out, int H, int W) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  return prepare_locked(c, (hipStream_t)stream, image_u8, 1, Hi, Wi, sketch_u8, Hs, Ws, image_out, sketch_out, H, W);
+}
+
+size_t se_edit_u8_workspace_bytes(se_ctx* c, int B, int Hi, int Wi) {
+  if (!c) return 0;
+  int H, W;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (edit_dims(c, B, Hi, Wi, &H, &W)) return 0;
+  }
+  const size_t fwd = se_workspace_bytes(c, B, H, W);
+  if (!fwd) return 0;
+  // + the uint8 result at the working size, in front of the forward's part
+  return fwd + (((size_t)B * H * W * 3 + 255) & ~(size_t)255);
+}
+
+// [uint8 result at the working size | the workspace of se_inference_u8io: arenas, masks, fp32 image and sketch at its end]
+int se_edit_u8(se_ctx* c, void* stream, const unsigned char* image_u8, const unsigned char* sketch_u8, unsigned char* rgb_out,
+               void* ws, size_t ws_bytes, int B, int Hi, int Wi, int Hs, int Ws, int flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  int H, W;
+  if (edit_dims(c, B, Hi, Wi, &H, &W)) return 1;
+  if (check_dims(c, B, H, W)) return 1;
+  if (!image_u8 || !sketch_u8 || !rgb_out || !ws) return fail(c, "null pointer argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
+  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  const size_t plane = ((size_t)B * H * W * 4 + 255) & ~(size_t)255, rgbw = ((size_t)B * H * W * 3 + 255) & ~(size_t)255;
+  if (ws_bytes < rgbw + 6 * plane) return fail(c, "workspace too small: %zu bytes", ws_bytes);
+  unsigned char* rgb_work = (unsigned char*)ws;
+  char* fws = (char*)ws + rgbw;
+  const size_t fws_bytes = ws_bytes - rgbw;
+  float* image = (float*)(fws + fws_bytes - 4 * plane);      // where se_inference_u8io keeps them
+  float* sketch = (float*)(fws + fws_bytes - plane);
+  const hipStream_t st = (hipStream_t)stream;
+  if (prepare_locked(c, st, image_u8, B, Hi, Wi, sketch_u8, Hs, Ws, image, sketch, H, W)) return 1;
+  if (inference_u8_locked(c, stream, image, sketch, rgb_work, nullptr, fws, fws_bytes, B, H, W, flags, 4)) return 1;
+  ResizeOut o{RESIZE_OUT_U8, rgb_out, nullptr, nullptr, 0, 0};
+  return resize_locked(c, st, rgb_work, B, H, W, 3, o, Hi, Wi, SE_RESAMPLE_BICUBIC);
 }
 
 // ---- measurement support (bench.py): per-kernel HIP-event timing ---------------------------------

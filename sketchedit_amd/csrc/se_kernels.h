@@ -15,7 +15,7 @@ namespace se {
 // ---------------------------------------------------------------------------------------------
 enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL_WINO_N192, PL_WINO_N96, PL_WINO_UP96, PL_SMALL_CONV, PL_PACK, PL_COLREDUCE,
                  PL_ATT_PREP, PL_ATT_SCORE, PL_ATT_SOFTMAX, PL_ATT_BOXSUM, PL_ATT_PV, PL_LAYOUT,
-                 PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_COUNT };
+                 PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -346,5 +346,29 @@ hipError_t launch_att2_prep(const AttParams& p, hipStream_t st);
 // kmul, kadd, stats ([B][R][2]); nothing R x R
 hipError_t launch_attention_stream(const AttParams& p, hipStream_t st);
 int att_stream_xt_tail();
+
+// ---------------------------------------------------------------------------------------------
+// Pillow-exact uint8 resampling (se_resize.hip; the resize steps of demo.py:39-73).  Coefficient tables per axis:
+// bounds[2 * out] = (first input index, tap count), kk[out * ksize] = fixed-point weights (22 fractional bits).
+// ---------------------------------------------------------------------------------------------
+int resample_ksize(int in, int out, int filter);            // taps per output (the table's row length), -1 for bad arguments
+int resample_coeffs(int in, int out, int filter, int* bounds, int* kk);     // host only; returns ksize
+enum { RESIZE_OUT_U8 = 0, RESIZE_OUT_IMAGE_F32 = 1, RESIZE_OUT_SKETCH_F32 = 2 };
+// what the LAST pass writes: uint8 (B,H,W,C); or the forward's fp32 NCHW inputs -- (B,C,H,W) = lut[v], or (v > 0)
+struct ResizeOut {
+  int mode;
+  unsigned char* u8;
+  float* f32;
+  const float* lut;    // RESIZE_OUT_IMAGE_F32: 256 floats (the ctx's dequantisation table)
+  int H, W;            // output size of the whole resize
+};
+// horizontal pass: (B, Hrows, Win, C) -> (B, Hrows, Wout, C); h_bounds = the host copy of d_bounds (LDS sizing)
+hipError_t launch_resample_h(const unsigned char* in, const int* d_bounds, const int* d_kk, const int* h_bounds, int ksize,
+                             int B, int Hrows, int Win, int Wout, int C, const ResizeOut& o, hipStream_t st);
+// vertical pass: (B, Hin, W, C) -> (B, Hout, W, C)
+hipError_t launch_resample_v(const unsigned char* in, const int* d_bounds, const int* d_kk, int ksize, int B, int Hin, int Hout,
+                             int W, int C, const ResizeOut& o, hipStream_t st);
+// largest tap count the kernels take (48 KiB of LDS per block): a bicubic downscale by more than ~2000x is refused
+constexpr int RESAMPLE_MAX_KSIZE = 8191;
 
 }  // namespace se

@@ -24,6 +24,10 @@ KERNEL_LABELS = {
     # the rest
     "small_conv_kernel": "small_conv", "pack_": "pack", "colreduce": "colreduce", "vecbias_kernel": "colreduce",
     "nchw_to_nhwc": "layout", "nhwc_to_nchw": "layout", "nhwc16_to_nchw": "layout", "quantize_u8_kernel": "layout",
+    "dequant_u8_kernel": "layout",
+    # the demo's per-request resizes (se_resize.hip)
+    "(anonymous namespace)::resample_h_kernel": "resize_h", "(anonymous namespace)::resample_v_kernel": "resize_v",
+    "resample_h_kernel": "resize_h", "resample_v_kernel": "resize_v",
 }
 
 

@@ -111,6 +111,25 @@ class EditLine2Model(torch.nn.Module):
             return eng.inference_u8(inputs.float().contiguous(), line.float().contiguous(), _lib.flags_from_opt(self.opt),
                                     low_latency=self._mode_for(inputs.shape[0], inputs.shape[2], inputs.shape[3], low_latency))
 
+    def edit_u8(self, image_u8, sketch_u8, low_latency=None):
+        """demo.py:39-73 (process_image) after the image decode: raw uint8 arrays in, the edited image at the raw size out,
+        every step on the device in one library call (se_edit_u8) -- the resizes to and from the working size
+        (Hi//8*8, Wi//8*8) are Pillow's BICUBIC bit for bit, so the result is byte-identical to the host steps.
+        image_u8 (Hi,Wi,3) RGB and sketch_u8 (Hs,Ws) 'L' (numpy arrays or tensors; the sketch's raw size may differ), or the
+        same with a leading batch dimension for B requests of one raw size -> rgb uint8 on the device, same layout.
+        `low_latency` as in forward, by the forward's size at the working resolution."""
+        if self.training:
+            raise NotImplementedError("call model.eval() first: only the eval branch of generate_fake exists here")
+        dev = torch.device("cuda", self.opt.gpu_ids[0])
+        iu8, su8 = _lib.upload_u8(image_u8, dev), _lib.upload_u8(sketch_u8, dev)
+        single = iu8.dim() == 3
+        if single:
+            iu8, su8 = iu8[None], su8[None]
+        rgb = self.engine().edit_u8(iu8, su8, _lib.flags_from_opt(self.opt),
+                                    low_latency=self._mode_for(iu8.shape[0], iu8.shape[1] // 8 * 8, iu8.shape[2] // 8 * 8,
+                                                               low_latency))
+        return rgb[0] if single else rgb
+
     def forward(self, data, mode, low_latency=None):
         """`low_latency` (no reference counterpart): None = by this call's own size, True / False = pinned.  Results are
         bit-identical across batch compositions only WITHIN one mode (include/sketchedit_hip.h), so callers whose batch size

@@ -28,6 +28,24 @@ def _to_tensors(img, mask):
     return x[None], m[None, None], (w_raw, h_raw)
 
 
+def _device_inputs(img, mask):
+    """What the device path takes from a request (device_io=True): the image as an RGB uint8 array and the sketch as one
+    uint8 plane -- mode 'L' as is, 'RGB' its channel 0 (Pillow resamples channels independently, so that is the plane
+    `(mask.resize(...))[..., 0]` comes from).  None for any other sketch mode ('1', 'P', 'RGBA', ...: Pillow resamples
+    those differently), which then takes the host preparation.  Sizes under the working minimum raise as _to_tensors does."""
+    img = img.convert("RGB")
+    w_raw, h_raw = img.size
+    if h_raw // 8 * 8 < 16 or w_raw // 8 * 8 < 16:
+        raise ValueError("image too small: %dx%d" % (w_raw, h_raw))
+    if mask.mode == "L":
+        m = np.asarray(mask)
+    elif mask.mode == "RGB":
+        m = np.ascontiguousarray(np.asarray(mask)[..., 0])
+    else:
+        return None
+    return np.asarray(img), m
+
+
 def _to_image(generated, size_raw):
     """demo.py:62-70: clamp, (x+1)/2*255, uint8, HWC, resize back to the request's size."""
     import torch
@@ -45,10 +63,21 @@ def _accepts_low_latency(model):
         return False
 
 
-def process_image(model, img, mask, low_latency=None):
+def process_image(model, img, mask, low_latency=None, device_io=False):
     """One request, as demo.py:39-73 handles it: PIL image + PIL sketch/mask in, PIL result out.  `low_latency` pins the
-    library's execution mode (EditLine2Model.forward); None = by call size."""
+    library's execution mode (EditLine2Model.forward); None = by call size.
+
+    device_io=True (an EditLine2Model): only the decoded uint8 arrays cross to the device; the resizes to and from the
+    working size (Pillow-exact), the normalisation, the forward and the output quantisation run there as one library call
+    (EditLine2Model.edit_u8) -- byte-identical to the host steps.  A sketch of another mode than 'L' / 'RGB' takes the host
+    path."""
     import torch
+    if device_io:
+        arrays = _device_inputs(img, mask)
+        if arrays is not None:
+            from PIL import Image
+            rgb = model.edit_u8(arrays[0], arrays[1], low_latency=low_latency)
+            return Image.fromarray(rgb.cpu().numpy())
     x, m, size_raw = _to_tensors(img, mask)
     with torch.no_grad():
         if low_latency is None:
@@ -88,20 +117,30 @@ class BatchingServer:
 
     `models` = one model per GPU (create_models_for_gpus): every model gets its own worker thread, all workers pull
     groups from the one shared queue -- dynamic batching across the GPUs of the node; an idle GPU
-    takes the next group, so the load balances itself.  `model` = the single-GPU form."""
+    takes the next group, so the load balances itself.  `model` = the single-GPU form.
 
-    def __init__(self, model=None, max_batch=32, max_wait_s=0.005, models=None, mode_policy="pinned"):
+    device_io=True (EditLine2Model workers): `submit` only decodes the request to uint8 arrays (_device_inputs); the worker
+    uploads them, resizes and normalises each request into its slot of the group's batch on the device
+    (Engine.prepare_u8), runs one forward with fused output quantisation for the group and resizes each result back to its
+    raw size on the device (Engine.resize_u8).  Byte-identical to the host steps; a request whose sketch mode the device
+    path does not take is prepared on the host and joins the same group."""
+
+    def __init__(self, model=None, max_batch=32, max_wait_s=0.005, models=None, mode_policy="pinned", device_io=False):
         if mode_policy not in ("pinned", "by_size"):
             raise ValueError(mode_policy)
         self.mode_policy = mode_policy
+        self.device_io = bool(device_io)
         self.models = list(models) if models is not None else [model]
         if not self.models or any(m is None for m in self.models):
             raise ValueError("BatchingServer needs a model (or a list of models, one per GPU)")
+        if self.device_io and not all(hasattr(m, "engine") and hasattr(m, "inference_u8") for m in self.models):
+            raise ValueError("device_io=True needs EditLine2Model workers (their library engine runs the request steps)")
         self.model = self.models[0]
         self._has_knob = [_accepts_low_latency(m) for m in self.models]
         self.max_batch, self.max_wait_s = max_batch, max_wait_s
         self._lock = threading.Condition()
-        self._queue = []          # (x, m, size_raw, slot, arrival time)
+        self._queue = []          # (working shape (1,3,H,W), request, size_raw, slot, arrival time); request = (x, m) fp32
+        #                           tensors prepared on the host, or the uint8 arrays (image, sketch) of the device path
         self._stop = False
         self.batches = []         # sizes of the batches that were run (observability / tests)
         self.batches_by_model = [0] * len(self.models)
@@ -111,12 +150,18 @@ class BatchingServer:
             t.start()
 
     def submit(self, img, mask):
-        x, m, size_raw = _to_tensors(img, mask)
+        arrays = _device_inputs(img, mask) if self.device_io else None
+        if arrays is not None:
+            h_raw, w_raw = arrays[0].shape[:2]
+            key, req, size_raw = (1, 3, h_raw // 8 * 8, w_raw // 8 * 8), arrays, (w_raw, h_raw)
+        else:
+            x, m, size_raw = _to_tensors(img, mask)
+            key, req = tuple(x.shape), (x, m)
         slot = {"done": threading.Event(), "out": None, "err": None}
         with self._lock:
             if self._stop:
                 raise RuntimeError("server is closed")
-            self._queue.append((x, m, size_raw, slot, time.monotonic()))
+            self._queue.append((key, req, size_raw, slot, time.monotonic()))
             self._lock.notify_all()
         slot["done"].wait()
         if slot["err"] is not None:
@@ -138,23 +183,23 @@ class BatchingServer:
         instead of stacking."""
         with self._lock:
             while True:
-                head = next((q for q in self._queue if tuple(q[0].shape) not in self._collecting), None)
+                head = next((q for q in self._queue if q[0] not in self._collecting), None)
                 if head is None:
                     if self._stop and not self._queue:
                         return None                   # stopped and drained
                     self._lock.wait(0.05 if self._stop else None)
                     continue
-                shape = tuple(head[0].shape)
+                shape = head[0]
                 self._collecting.add(shape)
                 try:
                     deadline = head[4] + self.max_wait_s
                     while True:
-                        n = sum(1 for q in self._queue if tuple(q[0].shape) == shape)
+                        n = sum(1 for q in self._queue if q[0] == shape)
                         left = deadline - time.monotonic()
                         if n >= self.max_batch or left <= 0 or self._stop:
                             break
                         self._lock.wait(left)
-                    group = [q for q in self._queue if tuple(q[0].shape) == shape][:self.max_batch]
+                    group = [q for q in self._queue if q[0] == shape][:self.max_batch]
                     taken = {id(q) for q in group}    # (list.remove would compare the tensors inside the tuples)
                     self._queue = [q for q in self._queue if id(q) not in taken]
                 finally:
@@ -168,6 +213,33 @@ class BatchingServer:
             return None
         from ._lib import Engine
         return Engine.is_low_latency(self.max_batch, shape[2], shape[3])
+
+    def _run_device(self, k, group):
+        """device_io: every request prepared into its slot of one (B,3,H,W) / (B,1,H,W) pair on the device, one forward with
+        fused quantisation (the group's execution mode as _forward's), each result resized back to its raw size there."""
+        import torch
+        from PIL import Image
+        from . import _lib
+        model = self.models[k]
+        eng = model.engine()
+        _, _, H, W = group[0][0]
+        dev = torch.device("cuda", eng.device)
+        image = torch.empty((len(group), 3, H, W), dtype=torch.float32, device=dev)
+        sketch = torch.empty((len(group), 1, H, W), dtype=torch.float32, device=dev)
+        for i, q in enumerate(group):
+            req = q[1]
+            if isinstance(req[0], np.ndarray):
+                eng.prepare_u8(_lib.upload_u8(req[0], dev), _lib.upload_u8(req[1], dev), H, W, out=(image[i:i + 1], sketch[i:i + 1]))
+            else:                                      # a sketch mode the device path does not take: prepared on the host
+                image[i:i + 1].copy_(req[0])
+                sketch[i:i + 1].copy_(req[1])
+        low_latency = self._mode(group[0][0]) if self._has_knob[k] else None
+        rgb, _ = model.inference_u8({"image": image, "mask": sketch}, low_latency=low_latency)
+        outs = []
+        for i, q in enumerate(group):
+            w_raw, h_raw = q[2]
+            outs.append(Image.fromarray(eng.resize_u8(rgb[i:i + 1], (h_raw, w_raw))[0].cpu().numpy()))
+        return outs
 
     def _forward(self, k, x, m):
         model = self.models[k]
@@ -184,15 +256,19 @@ class BatchingServer:
             if not group:                 # another worker took the requests this one was waiting with
                 continue
             try:
-                x = torch.cat([q[0] for q in group], 0)
-                m = torch.cat([q[1] for q in group], 0)
-                with torch.no_grad():
-                    generated, _ = self._forward(k, x, m)
+                if self.device_io:
+                    outs = self._run_device(k, group)
+                else:
+                    x = torch.cat([q[1][0] for q in group], 0)
+                    m = torch.cat([q[1][1] for q in group], 0)
+                    with torch.no_grad():
+                        generated, _ = self._forward(k, x, m)
+                    outs = [_to_image(generated[i:i + 1], q[2]) for i, q in enumerate(group)]
                 with self._lock:
                     self.batches.append(len(group))
                     self.batches_by_model[k] += 1
-                for i, q in enumerate(group):
-                    q[3]["out"] = _to_image(generated[i:i + 1], q[2])
+                for q, out in zip(group, outs):
+                    q[3]["out"] = out
             except Exception as e:      # deliver the failure to every waiting caller
                 for q in group:
                     q[3]["err"] = e
