@@ -1098,7 +1098,7 @@ int try_rtile(se_ctx* c, const Layer& L, bool bf, const float* src0, int C0, con
 // two polyphase sub-images of 8 columns (and at most 8 rows) share one 8 x 16 raw tile (rconv16b_kernel, p.dual)
 static bool rconv16_dual_ok(const Layer& L, const LayerDef& d, int Hin, int Win) {
   if (opt(OPT_RCONV16_DUAL) == 0) return false;
-  return rconv16_small_tiles() && L.d_w16s && (d.rate % 2) == 0 && Win / d.rate == 8 && Hin / d.rate <= 8 && Hin / d.rate >= 4;
+  return L.d_w16s && (d.rate % 2) == 0 && Win / d.rate == 8 && Hin / d.rate <= 8 && Hin / d.rate >= 4;
 }
 
 int run_gconv16(se_ctx* c, const Layer& L, const float* src0, int C0, const float* src1, int C1, int src1_vec, float* dst,
@@ -1107,13 +1107,13 @@ int run_gconv16(se_ctx* c, const Layer& L, const float* src0, int C0, const floa
   if (!L.d_w16) return fail(c, "layer %s: no bf16 weight image", d.name);
   if ((C0 + C1) != L.CGp16 * 8) return fail(c, "layer %s: bf16 source channels %d+%d != packed %d", d.name, C0, C1, L.CGp16 * 8);
   // the dominant shape (96 -> 192, 3x3, stride 1) runs in the raw-tile form when its polyphase sub-images are large
-  // enough to fill 16 x 16 tiles reasonably (se_rconv16.hip); SE_RCONV16=0 keeps it on the gather-GEMM
+  // enough to fill 8 x 16 tiles reasonably (se_rconv16.hip); SE_RCONV16=0 keeps it on the gather-GEMM
   const bool use_rconv = opt(OPT_RCONV16) != 0;
   // conv11 of netG: the spatially constant second source folded into a bias table (run_gconv / launch_vecbias), the layer on
   // the 8 x 16 raw-tile kernel with the first source alone
   {
     if (opt(OPT_VECBIAS) != 0 && use_rconv && !c->low_latency && src1 && src1_vec && c->vbias_ws && c->vec32 && L.d_w16s && L.d_wv16 &&
-        rconv16_small_tiles() && d.k == 3 && d.stride == 1 && d.rate == 1 && !d.up && d.cin == 192 && d.cout == 192 && C0 == 96 && C1 == 96 &&
+        d.k == 3 && d.stride == 1 && d.rate == 1 && !d.up && d.cin == 192 && d.cout == 192 && C0 == 96 && C1 == 96 &&
         Hin >= 12 && Win >= 12 && (long long)B * Hin * Win * 192 < (1ll << 31)) {
       HIPCHK(c, launch_vecbias(L.d_wv16, c->vec32, c->vbias_ws, B, 96, c->st, 1));
       RConvParams rp;
@@ -1129,19 +1129,18 @@ int run_gconv16(se_ctx* c, const Layer& L, const float* src0, int C0, const floa
     }
   }
   if (use_rconv && !c->low_latency && d.k == 3 && d.stride == 1 && !d.up && d.cin == 96 && d.cout == 192 && !src1 && C0 == 96 &&
-      (Hin % d.rate) == 0 && (Win % d.rate) == 0 && L.nch16 == 14 && (long long)B * Hin * Win * 192 < (1ll << 31) &&
+      (Hin % d.rate) == 0 && (Win % d.rate) == 0 && L.nch16 == 14 && L.d_w16s && (long long)B * Hin * Win * 192 < (1ll << 31) &&
       ((Hin / d.rate >= 12 && Win / d.rate >= 12) || rconv16_dual_ok(L, d, Hin, Win))) {
     RConvParams rp;
     memset(&rp, 0, sizeof rp);
-    const bool small = rconv16_small_tiles() && L.d_w16s;     // 8 x 16 tiles, 32-k step image, no K padding
     // sub-images of 8 x 8 (dilation 16 at 128 x 128, 8 at 64 x 64): two phases share an 8 x 16 tile (SE_RCONV16_DUAL=0: gather-GEMM)
     rp.dual = !(Hin / d.rate >= 12 && Win / d.rate >= 12);
-    rp.src = src0; rp.wpk = small ? L.d_w16s : L.d_w16; rp.bias = L.d_b; rp.dst = dst;
+    rp.src = src0; rp.wpk = L.d_w16s; rp.bias = L.d_b; rp.dst = dst;
     rp.B = B; rp.h = Hin; rp.w = Win; rp.d = d.rate; rp.hs = Hin / d.rate; rp.ws = Win / d.rate;
-    rp.ty = small ? (rp.hs + 7) / 8 : (rp.hs + 15) / 16; rp.tx = (rp.ws + 15) / 16;
+    rp.ty = (rp.hs + 7) / 8; rp.tx = (rp.ws + 15) / 16;
     rp.act = d.act; rp.xcd = xcd_remap_enabled();
     const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-    set_launch_cost(alg, 2.0 * 2.0 * (double)B * Hin * Win * 96, d.name, 2.0 * (double)B * Hin * Win * 192.0 * (small ? 864.0 : 896.0));
+    set_launch_cost(alg, 2.0 * 2.0 * (double)B * Hin * Win * 96, d.name, 2.0 * (double)B * Hin * Win * 192.0 * 864.0);
     HIPCHK(c, launch_rconv16(rp, c->st));
     return 0;
   }
@@ -1203,6 +1202,22 @@ int run_gconv16(se_ctx* c, const Layer& L, const float* src0, int C0, const floa
 }
 
 // ---- launching one gated conv -----------------------------------------------------------------------
+// parameters of a Winograd launch on tiles of 2 rows x `tcols` columns of an h x w source at dilation d (no second source,
+// no folded bias: the caller sets those)
+static WinoParams wino_params(const float* src, const float* upk, const float* bias, float* dst, int B, int h, int w, int d,
+                              int tcols, int act) {
+  WinoParams wp;
+  memset(&wp, 0, sizeof wp);
+  wp.src = src; wp.upk = upk; wp.bias = bias; wp.dst = dst;
+  wp.B = B; wp.h = h; wp.w = w; wp.d = d; wp.th = h / 2; wp.tw = w / tcols;
+  wp.total_tiles = B * wp.th * wp.tw; wp.act = act;
+  wp.xcd = xcd_remap_enabled();
+  udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
+  udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
+  udiv_magic_host((unsigned)wp.d, &wp.div_d_m, &wp.div_d_l);
+  return wp;
+}
+
 int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float* src1, int C1, int src1_vec, float* dst,
               int B, int Hin, int Win, int* Ho_, int* Wo_) {
   const LayerDef& d = L.def;
@@ -1234,6 +1249,7 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
   const bool wino_src_ok = (!src1 && C0 == 96 && d.cin == 96) || (src1 && C0 == 96 && C1 == 96 && d.cin == 192);
   // the kernel addresses a source through 32-bit byte offsets (96 floats per pixel)
   const bool wino_addr_ok = (long long)B * Hin * Win * 384 < (1ll << 31);
+  const double alg3x3 = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;     // the Winograd layers' cost as the reference defines it
   if (use_wino && !d.up && L.d_u && wino_src_ok && !wino_addr_ok) {
     static bool said = false;
     if (!said) {
@@ -1244,20 +1260,12 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
   }
   if (use_wino && !d.up && L.d_u && wino_src_ok && wino_addr_ok && (Hin % (2 * d.rate)) == 0 && (Win % (2 * d.rate)) == 0 &&
       wino_grid_ok(((long)(Hin / 2) * (Win / 2) + 63) / 64, true)) {
-    WinoParams wp;
-    memset(&wp, 0, sizeof wp);
-    wp.src = src0; wp.src1 = src1; wp.src1_vec = src1_vec;
-    wp.upk = L.d_u; wp.bias = L.d_b; wp.dst = dst;
     // A spatially constant second source is folded into a per-image, per-border-configuration bias (launch_vecbias) and
     // the layer runs as the SINGLE-source kernel: half the positions' K, 311 -> 170 us at 256x256 B=32 (SE_VECBIAS=0: the
     // two-source kernel reads the vector as a second input)
-    const bool vecbias_on = opt(OPT_VECBIAS) != 0;
-    bool folded = false;
-    if (vecbias_on && src1 && src1_vec && d.rate == 1 && L.d_u1 && L.d_wv && c->vbias_ws && Hin >= 2 && Win >= 2) {
-      HIPCHK(c, launch_vecbias(L.d_wv, src1, c->vbias_ws, B, 96, c->st));
-      wp.src1 = nullptr; wp.src1_vec = 0; wp.upk = L.d_u1; wp.vbias = c->vbias_ws;
-      folded = true;
-    }
+    const bool folded = opt(OPT_VECBIAS) != 0 && src1 && src1_vec && d.rate == 1 && L.d_u1 && L.d_wv && c->vbias_ws && Hin >= 2 && Win >= 2;
+    if (folded) HIPCHK(c, launch_vecbias(L.d_wv, src1, c->vbias_ws, B, 96, c->st));
+    const float* s1 = folded ? nullptr : src1;
     // Hybrid F(2,3) x F(4,3) (se_wino24.hip) for the single-source form where the width allows 4-column tiles: 24 instead of
     // 32 positions per 8 outputs.  SE_WINOGRAD_F43=0: F(2x2,3x3) everywhere; 1 (default): the hybrid kernel everywhere; 2: netG
     // only (netM's soft mask feeds the 0.5 threshold, editline2_model.py:346-347).  Measured in round 5 over 72 images / 4.7 M
@@ -1268,24 +1276,19 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
     const int f43_mode = opt(OPT_WINOGRAD_F43);
     // SE_FLAG_CONSERVATIVE is mode 2 for this call, chosen by the caller through the ABI instead of the process-wide table
     const bool f43_net_ok = c->cur_net == SE_NET_G || (f43_mode == 1 && !c->conservative);
-    const bool f43 = (f43_mode == 1 || f43_mode == 2) && f43_net_ok && (wp.src1 ? (!wp.src1_vec && L.d_u24b) : L.d_u24 != nullptr) && L.d_ub24 && (Win % (4 * d.rate)) == 0;
-    wp.B = B; wp.h = Hin; wp.w = Win; wp.d = d.rate; wp.th = Hin / 2; wp.tw = f43 ? Win / 4 : Win / 2;
-    wp.total_tiles = B * wp.th * wp.tw; wp.act = d.act;
-    wp.xcd = xcd_remap_enabled();
-    udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
-    udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
-    udiv_magic_host((unsigned)wp.d, &wp.div_d_m, &wp.div_d_l);
+    const bool f43 = (f43_mode == 1 || f43_mode == 2) && f43_net_ok && (s1 ? (!src1_vec && L.d_u24b) : L.d_u24 != nullptr) && L.d_ub24 && (Win % (4 * d.rate)) == 0;
+    WinoParams wp = f43 ? wino_params(src0, s1 ? L.d_u24b : L.d_u24, L.d_ub24, dst, B, Hin, Win, d.rate, 4, d.act)
+                        : wino_params(src0, folded ? L.d_u1 : L.d_u, L.d_b, dst, B, Hin, Win, d.rate, 2, d.act);
+    wp.src1 = s1; wp.src1_vec = folded ? 0 : src1_vec; wp.vbias = folded ? c->vbias_ws : nullptr;
     if ((double)B * Hin * Win * 384.0 >= 2147483648.0) return fail(c, "layer %s: tensor exceeds 2^31 bytes", d.name);
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
     if (f43) {
-      wp.upk = wp.src1 ? L.d_u24b : L.d_u24; wp.bias = L.d_ub24;
       // 24 of 72 products per 2x4 outputs; with the vector source folded away only the first source's half of K is executed
-      set_launch_cost(alg, 4.0 * 2.0 * (double)B * Hin * Win * 96, d.name, alg * 24.0 / 72.0 * (folded ? 0.5 : 1.0));
+      set_launch_cost(alg3x3, 4.0 * 2.0 * (double)B * Hin * Win * 96, d.name, alg3x3 * 24.0 / 72.0 * (folded ? 0.5 : 1.0));
       HIPCHK(c, launch_wino24(wp, c->st));
       return 0;
     }
     // F(2x2,3x3): 16 of 36 products; with the vector source folded away only the first source's half of K is executed
-    set_launch_cost(alg, 4.0 * 2.0 * (double)B * Hin * Win * 96, d.name, alg * 16.0 / 36.0 * (folded ? 0.5 : 1.0));
+    set_launch_cost(alg3x3, 4.0 * 2.0 * (double)B * Hin * Win * 96, d.name, alg3x3 * 16.0 / 36.0 * (folded ? 0.5 : 1.0));
     HIPCHK(c, launch_wino(wp, c->st));
     return 0;
   }
@@ -1294,17 +1297,8 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
     if (use_wino && opt(OPT_WINOGRAD_F43) != 0 && !d.up && !src1 && C0 == 48 && d.cin == 48 && d.cout == 192 && d.stride == 1 && L.d_u24 && L.d_ub24 &&
         (long long)B * Hin * Win * 384 < (1ll << 31) && (Hin % (2 * d.rate)) == 0 && (Win % (4 * d.rate)) == 0 &&
         wino_grid_ok(((long)(Hin / 2) * (Win / 4) + 31) / 32, true)) {
-      WinoParams wp;
-      memset(&wp, 0, sizeof wp);
-      wp.src = src0; wp.upk = L.d_u24; wp.bias = L.d_ub24; wp.dst = dst;
-      wp.B = B; wp.h = Hin; wp.w = Win; wp.d = d.rate; wp.th = Hin / 2; wp.tw = Win / 4;
-      wp.total_tiles = B * wp.th * wp.tw; wp.act = d.act;
-      wp.xcd = xcd_remap_enabled();
-      udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
-      udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
-      udiv_magic_host((unsigned)wp.d, &wp.div_d_m, &wp.div_d_l);
-      const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-      set_launch_cost(alg, 4.0 * ((double)B * Hin * Win * 48 + (double)B * Hin * Win * 96), d.name, alg * 24.0 / 72.0);
+      const WinoParams wp = wino_params(src0, L.d_u24, L.d_ub24, dst, B, Hin, Win, d.rate, 4, d.act);
+      set_launch_cost(alg3x3, 4.0 * ((double)B * Hin * Win * 48 + (double)B * Hin * Win * 96), d.name, alg3x3 * 24.0 / 72.0);
       HIPCHK(c, launch_wino24_c48(wp, c->st));
       return 0;
     }
@@ -1312,17 +1306,8 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
   const bool use_wino48 = opt(OPT_WINOGRAD48) != 0;
   if (use_wino && use_wino48 && !d.up && L.d_u && L.d_ub && !src1 && C0 == 48 && d.cin == 48 && (long long)B * Hin * Win * 192 < (1ll << 31) &&
       (Hin % (2 * d.rate)) == 0 && (Win % (2 * d.rate)) == 0 && wino_grid_ok(((long)(Hin / 2) * (Win / 2) + 63) / 64)) {
-    WinoParams wp;
-    memset(&wp, 0, sizeof wp);
-    wp.src = src0; wp.upk = L.d_u; wp.bias = L.d_ub; wp.dst = dst;
-    wp.B = B; wp.h = Hin; wp.w = Win; wp.d = d.rate; wp.th = Hin / 2; wp.tw = Win / 2;
-    wp.total_tiles = B * wp.th * wp.tw; wp.act = d.act;
-    wp.xcd = xcd_remap_enabled();
-    udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
-    udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
-    udiv_magic_host((unsigned)wp.d, &wp.div_d_m, &wp.div_d_l);
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-    set_launch_cost(alg, 4.0 * 2.0 * (double)B * Hin * Win * 48, d.name, alg * 16.0 / 36.0);
+    const WinoParams wp = wino_params(src0, L.d_u, L.d_ub, dst, B, Hin, Win, d.rate, 2, d.act);
+    set_launch_cost(alg3x3, 4.0 * 2.0 * (double)B * Hin * Win * 48, d.name, alg3x3 * 16.0 / 36.0);
     HIPCHK(c, launch_wino48(wp, c->st));
     return 0;
   }
@@ -1330,17 +1315,8 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
   if (use_wino && use_wino48 && !d.up && L.d_u && L.d_ub && !src1 && C0 == 24 && d.cin == 24 && d.cout == 96 && d.stride == 1 &&
       (long long)B * Hin * Win * 192 < (1ll << 31) && (Hin % (2 * d.rate)) == 0 && (Win % (2 * d.rate)) == 0 &&
       wino_grid_ok(((long)(Hin / 2) * (Win / 2) + 63) / 64)) {
-    WinoParams wp;
-    memset(&wp, 0, sizeof wp);
-    wp.src = src0; wp.upk = L.d_u; wp.bias = L.d_ub; wp.dst = dst;
-    wp.B = B; wp.h = Hin; wp.w = Win; wp.d = d.rate; wp.th = Hin / 2; wp.tw = Win / 2;
-    wp.total_tiles = B * wp.th * wp.tw; wp.act = d.act;
-    wp.xcd = xcd_remap_enabled();
-    udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
-    udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
-    udiv_magic_host((unsigned)wp.d, &wp.div_d_m, &wp.div_d_l);
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-    set_launch_cost(alg, 4.0 * ((double)B * Hin * Win * 24 + (double)B * Hin * Win * 48), d.name, alg * 16.0 / 36.0);
+    const WinoParams wp = wino_params(src0, L.d_u, L.d_ub, dst, B, Hin, Win, d.rate, 2, d.act);
+    set_launch_cost(alg3x3, 4.0 * ((double)B * Hin * Win * 24 + (double)B * Hin * Win * 48), d.name, alg3x3 * 16.0 / 36.0);
     HIPCHK(c, launch_wino48_c24(wp, c->st));
     return 0;
   }
@@ -1348,18 +1324,9 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
   if (use_wino && use_winoup && d.up && L.d_u && L.d_ub && !src1 && C0 == 96 && d.cin == 96 &&
       (long long)B * Hin * Win * 384 < (1ll << 31) && (Hin % 2) == 0 && (Win % 2) == 0 &&
       wino_grid_ok(4 * (((long)(Hin / 2) * (Win / 2) + 63) / 64))) {
-    WinoParams wp;
-    memset(&wp, 0, sizeof wp);
-    wp.src = src0; wp.upk = L.d_u; wp.bias = L.d_ub; wp.dst = dst;
-    wp.B = B; wp.h = Hin; wp.w = Win; wp.d = 1; wp.th = Hin / 2; wp.tw = Win / 2;
-    wp.total_tiles = B * wp.th * wp.tw; wp.act = d.act;
-    wp.xcd = xcd_remap_enabled();
-    udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
-    udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
-    udiv_magic_host(1u, &wp.div_d_m, &wp.div_d_l);
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-    set_launch_cost(alg, 4.0 * ((double)B * Hin * Win * 96 + (double)B * Ho * Wo * 48), d.name,
-                    alg * 9.0 / 36.0);                       // F(2x2,2x2) on the sub-pixel classes: 9 of 36 products
+    const WinoParams wp = wino_params(src0, L.d_u, L.d_ub, dst, B, Hin, Win, 1, 2, d.act);
+    set_launch_cost(alg3x3, 4.0 * ((double)B * Hin * Win * 96 + (double)B * Ho * Wo * 48), d.name,
+                    alg3x3 * 9.0 / 36.0);                       // F(2x2,2x2) on the sub-pixel classes: 9 of 36 products
     HIPCHK(c, launch_winoup(wp, c->st));
     return 0;
   }
@@ -1368,18 +1335,9 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
   if (use_wino && use_winoup && use_winoup48 && d.up && L.d_u && L.d_ub && !src1 && C0 == 48 && d.cin == 48 && d.cout == 48 &&
       (long long)B * Hin * Win * 192 < (1ll << 31) && (long long)B * Ho * Wo * 96 < (1ll << 31) && (Hin % 2) == 0 && (Win % 2) == 0 &&
       wino_grid_ok(4 * (((long)(Hin / 2) * (Win / 2) + 63) / 64))) {
-    WinoParams wp;
-    memset(&wp, 0, sizeof wp);
-    wp.src = src0; wp.upk = L.d_u; wp.bias = L.d_ub; wp.dst = dst;
-    wp.B = B; wp.h = Hin; wp.w = Win; wp.d = 1; wp.th = Hin / 2; wp.tw = Win / 2;
-    wp.total_tiles = B * wp.th * wp.tw; wp.act = d.act;
-    wp.xcd = xcd_remap_enabled();
-    udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
-    udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
-    udiv_magic_host(1u, &wp.div_d_m, &wp.div_d_l);
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-    set_launch_cost(alg, 4.0 * ((double)B * Hin * Win * 48 + (double)B * Ho * Wo * 24), d.name,
-                    alg * 9.0 / 36.0 * 28.0 / 27.0);         // 9 of 36 products, 28 k-halves executed for 27 of work
+    const WinoParams wp = wino_params(src0, L.d_u, L.d_ub, dst, B, Hin, Win, 1, 2, d.act);
+    set_launch_cost(alg3x3, 4.0 * ((double)B * Hin * Win * 48 + (double)B * Ho * Wo * 24), d.name,
+                    alg3x3 * 9.0 / 36.0 * 28.0 / 27.0);         // 9 of 36 products, 28 k-halves executed for 27 of work
     HIPCHK(c, launch_winoup48(wp, c->st));
     return 0;
   }
@@ -1691,37 +1649,29 @@ int att_row_stride(int R, bool bf) {
   return Rp;
 }
 
-// Which attention form runs on an h x w feature map: ATT_STREAMING (se_att_stream.hip: nothing R x R) wherever the
+// Whether attention on an h x w feature map runs in the streaming form (se_att_stream.hip: nothing R x R): wherever the
 // materialised space-to-depth form cannot address its R x R matrices with 32-bit offsets (R Rp 4 >= 2^31), and everywhere
-// with SE_ATT_STREAM=1 unless `similar_out` -- P itself -- is asked for; otherwise the materialised form (ATT_V2), or the
-// patch form (ATT_V1) when SE_ATT_V1=1 in fp32.  `similar_out` is refused exactly where R Rp 4 >= 2^31, whatever the options
-// (Engine.attention checks the same rule before it allocates the L x L output).
-enum { ATT_V1 = 0, ATT_V2 = 1, ATT_STREAMING = 2 };
-int att_form(int h, int w, bool bf, bool want_similar) {
+// with SE_ATT_STREAM=1 unless `similar_out` -- P itself -- is asked for.  `similar_out` is refused exactly where
+// R Rp 4 >= 2^31, whatever the options (Engine.attention checks the same rule before it allocates the L x L output).
+bool att_streaming(int h, int w, bool bf, bool want_similar) {
   const int R = (h / 2) * (w / 2), Rp = att_row_stride(R, bf);
   const bool fits = (double)R * Rp * 4.0 < 2147483648.0;
-  const bool v2 = attention_v2_enabled() || bf;       // the bf16 path exists in the space-to-depth form only
-  if (want_similar && !fits) return ATT_STREAMING;       // (run_attention refuses: similar_out is P itself)
-  if (opt(OPT_ATT_STREAM) == 1 && !want_similar) return ATT_STREAMING;
-  if (!v2) return ATT_V1;
-  return fits ? ATT_V2 : ATT_STREAMING;
+  if (want_similar && !fits) return true;              // (run_attention refuses: similar_out is P itself)
+  if (opt(OPT_ATT_STREAM) == 1 && !want_similar) return true;
+  return !fits;
 }
 
 int run_attention(se_ctx* c, Plan& P, Act& x, const float* mask_full, Act& out, float* similar_nchw) {
   const int h = x.H, w = x.W, B = P.B;
   const int hs = (h - 4) / 2 + 1, ws = (w - 4) / 2 + 1, L = hs * ws, Lp = (L + 31) & ~31;
   const bool bf = c->bf16;
-  const int form = att_form(h, w, bf, similar_nchw != nullptr);
-  const bool v2 = form == ATT_V2, stream = form == ATT_STREAMING;
+  const bool stream = att_streaming(h, w, bf, similar_nchw != nullptr);
   const int hc = h / 2, wc = w / 2, R = hc * wc;
   const int Rp = att_row_stride(R, bf);
   const int guard = (wc + 8 + 63) & ~63;               // floats; att2_ptilde_kernel reads up to wc + 5 columns outside a row
   if (stream && similar_nchw)
     return P.rc = fail(c, "attention: similar_out (the %d x %d score matrix) is not available on a %dx%d feature map: "
                           "it runs in the streaming form, which never forms it", L, L, h, w);
-  // the patch form addresses the L x Lp scores with 32-bit offsets
-  if (form == ATT_V1 && (double)L * Lp * 4.0 >= 2147483648.0)
-    return P.rc = fail(c, "attention (SE_ATT_V1 patch form): %dx%d feature map too large", h, w);
   // fp32 scratch is sized in floats whatever the activation type
   float* part = P.alloc_raw((size_t)B * COLREDUCE_SPLITS * 96);
   float* rn = P.alloc_raw((size_t)B * 96);
@@ -1731,15 +1681,12 @@ int run_attention(se_ctx* c, Plan& P, Act& x, const float* mask_full, Act& out, 
     valid = P.alloc_raw(3 * (size_t)B * Rp);
     stats = P.alloc_raw((size_t)B * R * 2);
     xT = P.alloc_raw((bf ? (size_t)B * 4 * 96 * Rp / 2 : (size_t)B * 4 * 96 * Rp) + att_stream_xt_tail());
-  } else if (v2) {
+  } else {
     valid = P.alloc_raw(7 * ((size_t)B * Rp + guard) + (size_t)B * 768 + (size_t)B * hc * 384);      // validR, kmul, kadd (+ fp16-E form: kadd2, ea4, ea, eb), each behind its guard band; emean, epart
     stats = P.alloc_raw((size_t)B * R * 2);    // fused streaming pass: (row max, 1 / row sum) per query
     xT = P.alloc_raw(bf ? (size_t)B * 4 * 96 * Rp / 2 : (size_t)B * 4 * 96 * Rp);
     S = P.alloc_raw((size_t)B * R * Rp + 2 * guard);       // E (fp32) between two guard bands; three-pass form: then P~
     S2 = P.alloc_raw(bf ? (size_t)B * R * Rp / 2 : (size_t)B * R * Rp);      // P (fp32 / bf16)
-  } else {
-    valid = P.alloc_raw((size_t)B * Lp);
-    S = P.alloc_raw((size_t)B * L * Lp);
   }
   if (P.rc) return P.rc;
   if (!c->dry) {
@@ -1754,7 +1701,7 @@ int run_attention(se_ctx* c, Plan& P, Act& x, const float* mask_full, Act& out, 
       a.validR = valid; a.kmul = valid + (size_t)B * Rp; a.kadd = valid + 2 * (size_t)B * Rp;
       a.xT = xT; a.stats = stats;
       HIPCHK(c, launch_attention_stream(a, c->st));
-    } else if (v2) {
+    } else {
       a.hc = hc; a.wc = wc; a.R = R; a.Rp = Rp; a.bf16 = bf ? 1 : 0;
       a.validR = valid + guard; a.xT = xT; a.E = S + guard; a.P = S2; a.stats = stats; a.guard = guard; a.similar = similar_nchw;
       a.kmul = valid + ((size_t)B * Rp + guard) + guard; a.kadd = valid + 2 * ((size_t)B * Rp + guard) + guard;
@@ -1762,13 +1709,6 @@ int run_attention(se_ctx* c, Plan& P, Act& x, const float* mask_full, Act& out, 
       a.ea = valid + 5 * ((size_t)B * Rp + guard) + guard; a.eb = valid + 6 * ((size_t)B * Rp + guard) + guard;
       a.emean = valid + 7 * ((size_t)B * Rp + guard); a.epart = a.emean + (size_t)B * 768;
       HIPCHK(c, launch_attention(a, c->st));
-    } else {
-      a.valid = valid; a.S = S;
-      HIPCHK(c, launch_attention(a, c->st));
-      if (similar_nchw) {
-        // (B, Lk, hs, ws) <- S[b][i][j]: "channel" j, pixel i
-        HIPCHK(c, launch_nhwc_to_nchw(S, similar_nchw, B, L, Lp, hs, ws, c->st));
-      }
     }
   }
   P.release(S2); P.release(S); P.release(xT); P.release(stats); P.release(valid);
@@ -1828,7 +1768,7 @@ int pass_size(se_ctx* c, int B, int H, int W, int flags) {
 se_ctx::Peaks plan_peaks(se_ctx* c, int which, int B, int H, int W, int flags, bool want_maskim) {
   const std::vector<long long> key = {which, B, H, W,
                                       flags & (SE_FLAG_USE_CAM | SE_FLAG_JOINT_TRAIN_INP | SE_FLAG_LOW_LATENCY | SE_FLAG_BF16),
-                                      want_maskim ? 1 : 0, attention_v2_enabled() ? 1 : 0, opt_epoch(), c->serial ? 1 : 0};
+                                      want_maskim ? 1 : 0, c->fork2 ? 1 : 0, opt_epoch(), c->serial ? 1 : 0};
   auto it = c->peaks.find(key);
   if (it != c->peaks.end()) return it->second;
   const bool dry0 = c->dry, ll0 = c->low_latency, bf0 = c->bf16;
@@ -2697,16 +2637,14 @@ int se_attention_ex(se_ctx* c, void* stream, const float* x, const float* mask_f
   begin_call(c, stream, exec_flags & SE_FLAG_BF16);
   const bool bf = c->bf16;
   const int R = (h / 2) * (w / 2), Rp = att_row_stride(R, true) + 64;
-  // refusals of run_attention, before anything is allocated: similar_out at a streaming size, the patch form beyond its range
-  const int form = att_form(h, w, bf, similar_out != nullptr);
-  const int L = ((h - 4) / 2 + 1) * ((w - 4) / 2 + 1), Lp = (L + 31) & ~31;
-  if (form == ATT_STREAMING && similar_out)
+  // the refusal of run_attention, before anything is allocated: similar_out at a streaming size
+  const bool streaming = att_streaming(h, w, bf, similar_out != nullptr);
+  const int L = ((h - 4) / 2 + 1) * ((w - 4) / 2 + 1);
+  if (streaming && similar_out)
     return fail(c, "attention: similar_out (the %d x %d score matrix) is not available on a %dx%d feature map: "
                    "it runs in the streaming form, which never forms it", L, L, h, w);
-  if (form == ATT_V1 && (double)L * Lp * 4.0 >= 2147483648.0)
-    return fail(c, "attention (SE_ATT_V1 patch form): %dx%d feature map too large", h, w);
   // the R x R matrices E and P exist in the materialised form only (the streaming form's scratch is O(R))
-  const size_t rr = form == ATT_STREAMING ? 0 : 2 * (size_t)B * R * Rp;
+  const size_t rr = streaming ? 0 : 2 * (size_t)B * R * Rp;
   const size_t bytes = ((size_t)B * h * w * 96 * 3 + rr + (size_t)B * Rp * (7 + 4 * 96) + 64 * 96 * B + 2 * (size_t)B * R + 9 * (size_t)(w / 2 + 72) + (size_t)B * (768 + (h / 2) * 384)) * 4 + (1 << 16);
   char* ws = nullptr;
   HIPCHK(c, hipMalloc(&ws, bytes));

@@ -7,13 +7,8 @@
 //   S[j,i] *= (mean over patch j of (1 - avgpool4(mask)) > 0.1)  multiplicative zero        :49-53,90,104
 //   P       = softmax_j(10 * S)                                                            :105
 //   out     = fold(P^T V), V = raw patches of x, overlap-add without normalisation        :138-153
-// Three kernels: scores (gather-GEMM, both operands gathered from NHWC x / xn, written query-major
-// so the softmax axis is contiguous), row softmax, and P.V fused with the fold as a gather: an output
-// pixel of parity class (py,px) sums the <=4 patches covering it, i.e. one GEMM with
-// K = 4 (covering patch) x L (keys) -- deterministic, no atomics.
-//
-// That is the round-1 patch form (att_* kernels, SE_ATT_V1=1).  What runs is the space-to-depth form of round 2 (att2_*,
-// DESIGN.md 3.3), in this file in launch order:
+// What runs is the space-to-depth form of round 2 (att2_* kernels; derivation in the block comment in
+// front of att2_prep_kernel), in this file in launch order:
 //   att2_prep / att2_transpose          keys (fp32: y = x sqrt(rn) for both operands of a bitwise symmetric E), key tables, V^T
 //   att2_emean1/2, att2_eoff, _eoff4    bf16 mode: row / column offsets of the doubly centred fp16 E
 //   att2_pair                           E GEMM (fp32: tiles on / right of the diagonal only, mirrored; panel order per XCD)
@@ -27,315 +22,15 @@
 
 namespace se {
 
-__global__ void att_prep_kernel(const AttParams p) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  const long nx = (long)p.B * p.h * p.w * 24;    // granules
-  if (idx < nx) {
-    const int cg = idx % 24;
-    const long pix = idx / 24;
-    const int b = pix / (p.h * p.w);
-    const f32x4 v = *(const f32x4*)(p.x + idx * 4);
-    const f32x4 r = *(const f32x4*)(p.rn + b * 96 + cg * 4);
-    *(f32x4*)(p.xn + idx * 4) = v * r;
-  }
-  if (idx < (long)p.B * p.Lp) {
-    const int b = idx / p.Lp, j = idx - (long)b * p.Lp;
-    float val = 0.f;
-    if (j < p.L) {
-      const int jy = j / p.ws, jx = j - jy * p.ws;
-      const int H = p.h * 4, W = p.w * 4;
-      // the 4x4 patch of the avg-pooled map covers a 16x16 full-resolution window; for a {0,1} mask the
-      // sum is an integer <= 256, so the mean is exact and the > 0.1 test is order independent
-      float hole = 0.f;
-      for (int yy = 0; yy < 16; ++yy)
-        for (int xx = 0; xx < 16; ++xx) hole += p.hard[((long)b * H + jy * 8 + yy) * W + jx * 8 + xx];
-      const float mm = 1.f - hole * (1.f / 256.f);
-      val = mm > p.th ? 1.f : 0.f;
-    }
-    p.valid[idx] = val;
-  }
-}
-
-// S[b][i][j] = scale * valid[j] * <K_j, Q_i>
-template <int NT, int PT>
-__global__ __launch_bounds__(256) void att_score_kernel(const AttParams p) {
-  constexpr int PIX = PT * 64, NP = NT * 16;
-  constexpr int XBYTES = PIX * 128, WBYTES = NP * 128;
-  constexpr int NX = PT * 2, NW = (NT * 2 + 3) / 4;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Xb = smem;
-  char* Wb = smem + 2 * XBYTES;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.z;
-  const int q0 = blockIdx.x * PIX, k0 = blockIdx.y * NP;
-  // byte offset of the patch origin of a query / key row inside THIS image, or an out-of-range offset: both
-  // operands are staged through buffer resources (hardware zero fill, one VALU add per granule; se_gconv.hip)
-  auto origin = [&](int i) -> unsigned {
-    if (i >= p.L) return 0x80000000u;
-    const int py = i / p.ws, px = i - py * p.ws;
-    return (unsigned)(((2 * py) * p.w + 2 * px) * 384);
-  };
-  const se_i32x4 rs_q = make_rsrc(p.x + (size_t)b * p.h * p.w * 96, (unsigned)p.h * p.w * 96u * 4u);
-  const se_i32x4 rs_k = make_rsrc(p.xn + (size_t)b * p.h * p.w * 96, (unsigned)p.h * p.w * 96u * 4u);
-  unsigned qo[NX], ko[NW];
-#pragma unroll
-  for (int i = 0; i < NX; ++i) qo[i] = origin(q0 + (i * 4 + w) * 8 + (lane >> 3));
-#pragma unroll
-  for (int j = 0; j < NW; ++j) ko[j] = (j * 4 + w) < NT * 2 ? origin(k0 + (j * 4 + w) * 8 + (lane >> 3)) : 0x80000000u;
-
-  const int s_log = (lane & 7) ^ (4 * (w & 1) + (lane >> 4));
-  int off0, off1;
-  frag_offsets(lane, off0, off1);
-  const unsigned lds_x = lds_addr_of(Xb), lds_w = lds_addr_of(Wb);
-
-  auto stage = [&](int ch, int buf) {
-    const int gi = ch * 8 + s_log;                 // granule of the 16 taps x 24 channel-groups
-    const int tap = (gi * 2731) >> 16, cg = gi - tap * 24;      // gi / 24 for gi < 4096
-    const unsigned doff = (unsigned)((__mul24(tap >> 2, p.w) + (tap & 3)) * 384 + cg * 16);
-    const unsigned xdst = lds_x + buf * XBYTES, wdst = lds_w + buf * WBYTES;
-#pragma unroll
-    for (int i = 0; i < NX; ++i) bufdma16(qo[i] + doff, rs_q, xdst + (i * 4 + w) * 1024);
-#pragma unroll
-    for (int j = 0; j < NW; ++j) {
-      const int rbk = j * 4 + w;
-      if (rbk < NT * 2) bufdma16(ko[j] + doff, rs_k, wdst + rbk * 1024);
-    }
-  };
-
-  f32x4 acc[NT][PT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int pt = 0; pt < PT; ++pt) acc[nt][pt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  constexpr int NCH = 48;   // 16 taps * 96 ch / 32
-  stage(0, 0);
-  dma_wait_all();
-  __syncthreads();
-  for (int ch = 0; ch < NCH; ++ch) {
-    const int buf = ch & 1;
-    if (ch + 1 < NCH) stage(ch + 1, buf ^ 1);
-    mfma_chunk<NT, PT>(acc, Wb + buf * WBYTES, Xb + buf * XBYTES + w * PT * 2048, off0, off1);
-    dma_wait_all();
-    __syncthreads();
-  }
-  const int q = lane >> 4;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int j = k0 + nt * 16 + q * 4;
-    if (j >= p.Lp) continue;
-    const f32x4 v = *(const f32x4*)(p.valid + (long)b * p.Lp + j);
-#pragma unroll
-    for (int pt = 0; pt < PT; ++pt) {
-      const int i = q0 + (w * PT + pt) * 16 + (lane & 15);
-      if (i < p.L) *(f32x4*)(p.S + ((long)b * p.L + i) * p.Lp + j) = acc[nt][pt] * v * p.scale;
-    }
-  }
-}
-
-// softmax over keys j < L of each query row; pad columns [L, Lp) are set to 0.  One wave per row.
-__global__ __launch_bounds__(256) void att_softmax_kernel(const AttParams p) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long)p.B * p.L) return;
-  float* s = p.S + row * p.Lp;
-  float m = -INFINITY;
-  for (int j = lane; j < p.L; j += 64) m = fmaxf(m, s[j]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float sum = 0.f;
-  for (int j = lane; j < p.L; j += 64) {
-    const float e = expf(s[j] - m);
-    s[j] = e;
-    sum += e;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  const float inv = 1.f / sum;
-  for (int j = lane; j < p.Lp; j += 64) s[j] = j < p.L ? s[j] * inv : 0.f;
-}
-
-// out[b, pos, c] = sum over the <=4 patches covering pos of sum_j P[i][j] * x[b, 2j + (ky,kx), c]
-template <int PT>
-__global__ __launch_bounds__(256) void att_pv_kernel(const AttParams p) {
-  constexpr int NT = 6;
-  constexpr int PIX = PT * 64;
-  constexpr int XBYTES = PIX * 128, VBYTES = 32 * 384;
-  constexpr int NX = PT * 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Xb = smem;                        // P tiles  [PIX][32 keys]
-  char* Vb = smem + 2 * XBYTES;           // V tiles  [32 keys][96 ch]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.z, cls = blockIdx.y, py = cls >> 1, px = cls & 1;
-  const int ch_ = p.h >> 1, cw_ = p.w >> 1;      // class image size
-  const int t0 = blockIdx.x * PIX;
-  // Staging through buffer resources of THIS image's score matrix and value tensor (32-bit offsets, hardware zero
-  // fill for out-of-range lanes; se_gconv.hip fast path): per P row one byte offset and a 4-bit validity mask over
-  // the (a, bb) patch combos, per V granule the key's pixel offset -- 3 VALU per staged granule in the loop.
-  const int s_log = (lane & 7) ^ (4 * (w & 1) + (lane >> 4));
-  const se_i32x4 rs_S = make_rsrc(p.S + (size_t)b * p.L * p.Lp, (unsigned)p.L * p.Lp * 4u);
-  const se_i32x4 rs_x = make_rsrc(p.x + (size_t)b * p.h * p.w * 96, (unsigned)p.h * p.w * 96u * 4u);
-  unsigned xoff[NX], xinv[NX];
-#pragma unroll
-  for (int i = 0; i < NX; ++i) {
-    const int r = t0 + (i * 4 + w) * 8 + (lane >> 3);
-    const bool rowok = r < ch_ * cw_;
-    const int ry = rowok ? r / cw_ : 0, rx = rowok ? r - (r / cw_) * cw_ : 0;
-    xoff[i] = (unsigned)((ry * p.ws + rx) * p.Lp + s_log * 4) * 4u;
-    unsigned m = 0;
-#pragma unroll
-    for (int combo = 0; combo < 4; ++combo) {
-      const int iy = ry - (combo >> 1), ix = rx - (combo & 1);
-      if (rowok && (unsigned)iy < (unsigned)p.hs && (unsigned)ix < (unsigned)p.ws) m |= 1u << combo;
-    }
-    xinv[i] = ~m;
-  }
-  int off0, off1;
-  frag_offsets(lane, off0, off1);
-  const unsigned lds_x = lds_addr_of(Xb), lds_v = lds_addr_of(Vb);
-  const int jchunks = p.Lp >> 5;
-  const int nch = 4 * jchunks;
-  // V staging role: 3 pieces per wave; piece it -> granule gidx = it*64 + lane -> key row jr, channel group cg
-  int vjr[3];
-  unsigned vcoff[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int gidx = (k * 4 + w) * 64 + lane;
-    vjr[k] = gidx / 24;
-    // bank swizzle: key rows j and j+4 (read by lane groups q and q+1 of one ds_read_b32) would hit the same 16 banks
-    // (row stride 96 floats = 3 bank rows); rows with bit 2 set keep their granules swapped in blocks of 4
-    vcoff[k] = (unsigned)((gidx - vjr[k] * 24) ^ (((vjr[k] >> 2) & 1) << 2)) * 16u;
-  }
-  unsigned ws_m;
-  int ws_l;
-  {   // x / ws for x < 2^32 (se_device.h udiv_magic), divisor uniform
-    int ll = 0;
-    while ((1u << ll) < (unsigned)p.ws) ++ll;
-    ws_l = ll;
-    ws_m = (unsigned)((((unsigned long long)1 << 32) * (((unsigned long long)1 << ll) - (unsigned)p.ws)) / (unsigned)p.ws + 1);
-  }
-
-  auto stage = [&](int ch, int buf) {
-    const int combo = ch / jchunks, jc = ch - combo * jchunks;      // uniform
-    const int a = combo >> 1, bb = combo & 1;
-    const unsigned xdst = lds_x + buf * XBYTES, vdst = lds_v + buf * VBYTES;
-    const unsigned xdelta = (unsigned)((jc * 32 - (a * p.ws + bb) * p.Lp) * 4);      // uniform
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-      const unsigned m = (unsigned)__builtin_amdgcn_sbfe((int)xinv[i], combo, 1);      // all ones: outside -> zeros
-      bufdma16((xoff[i] + xdelta) | m, rs_S, xdst + (i * 4 + w) * 1024);
-    }
-    // V tile: key j -> pixel (2jy + py + 2a, 2jx + px + 2bb), 96 channels = 24 granules
-    const unsigned vbase = (unsigned)(((py + 2 * a) * p.w + px + 2 * bb) * 384);        // uniform
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int j = jc * 32 + vjr[k];
-      const int jy = (int)udiv_magic((unsigned)j, ws_m, ws_l), jx = j - jy * p.ws;
-      const unsigned off = (unsigned)(__mul24(jy, p.w) + jx) * 768u + vbase + vcoff[k];
-      bufdma16(j < p.L ? off : 0x80000000u, rs_x, vdst + (k * 4 + w) * 1024);
-    }
-  };
-
-  f32x4 acc[NT][PT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int pt = 0; pt < PT; ++pt) acc[nt][pt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  stage(0, 0);
-  dma_wait_all();
-  __syncthreads();
-  for (int ch = 0; ch < nch; ++ch) {
-    const int buf = ch & 1;
-    if (ch + 1 < nch) stage(ch + 1, buf ^ 1);
-    const char* Xt = Xb + buf * XBYTES + w * PT * 2048;
-    const float* Vt = (const float*)(Vb + buf * VBYTES);
-    const int vsw = ((lane >> 4) & 1) << 4;          // (j >> 2) & 1 == (lane >> 4) & 1: see the V staging swizzle
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const int off = half ? off1 : off0;
-      f32x4 xb[PT];
-#pragma unroll
-      for (int pt = 0; pt < PT; ++pt) xb[pt] = *(const f32x4*)(Xt + pt * 2048 + off);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int j = half * 16 + (lane >> 4) * 4 + r;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          const float a = Vt[j * 96 + ((nt * 16 + (lane & 15)) ^ vsw)];
-#pragma unroll
-          for (int pt = 0; pt < PT; ++pt)
-            acc[nt][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xb[pt][r], acc[nt][pt], 0, 0, 0);
-        }
-      }
-    }
-    dma_wait_all();
-    __syncthreads();
-  }
-  const int q = lane >> 4;
-#pragma unroll
-  for (int pt = 0; pt < PT; ++pt) {
-    const int i = t0 + (w * PT + pt) * 16 + (lane & 15);
-    if (i >= ch_ * cw_) continue;
-    const int yy = i / cw_, xx = i - yy * cw_;
-    float* o = p.out + ((long)(b * p.h + 2 * yy + py) * p.w + 2 * xx + px) * 96;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) *(f32x4*)(o + nt * 16 + q * 4) = acc[nt][pt];
-  }
-}
-
-static hipError_t launch_attention_v1(const AttParams& p, hipStream_t st) {
-  {
-    const long n = (long)p.B * p.h * p.w * 24;
-    ProfScope ps_(st, PL_ATT_PREP);
-    hipLaunchKernelGGL(att_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
-  }
-  {
-    constexpr int NT = 4, PT = 4;
-    constexpr int LDS = 2 * PT * 64 * 128 + 2 * NT * 16 * 128;
-    {
-    hipError_t e = ensure_max_lds((const void*)att_score_kernel<NT, PT>, LDS);
-    if (e != hipSuccess) return e;
-  }
-    dim3 grid((p.L + PT * 64 - 1) / (PT * 64), (p.L + NT * 16 - 1) / (NT * 16), p.B);
-    set_launch_cost(2.0 * p.B * (double)p.L * p.L * 1536.0, 0.0);
-    ProfScope ps_(st, PL_ATT_SCORE);
-    hipLaunchKernelGGL((att_score_kernel<NT, PT>), grid, dim3(256), LDS, st, p);
-  }
-  {
-    const long rows = (long)p.B * p.L;
-    ProfScope ps_(st, PL_ATT_SOFTMAX);
-    hipLaunchKernelGGL(att_softmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p);
-  }
-  {
-    constexpr int PT = 4;
-    constexpr int LDS = 2 * PT * 64 * 128 + 2 * 32 * 384;
-    {
-    hipError_t e = ensure_max_lds((const void*)att_pv_kernel<PT>, LDS);
-    if (e != hipSuccess) return e;
-  }
-    const int cpix = (p.h >> 1) * (p.w >> 1);
-    dim3 grid((cpix + PT * 64 - 1) / (PT * 64), 4, p.B);
-    set_launch_cost(2.0 * p.B * (double)p.L * p.L * 1536.0, 0.0);
-    ProfScope ps_(st, PL_ATT_PV);
-    hipLaunchKernelGGL((att_pv_kernel<PT>), grid, dim3(256), LDS, st, p);
-  }
-  return hipGetLastError();
-}
-
-
 // =====================================================================================================================
-// Space-to-depth form ("v2", the default).  The 4x4 patches at stride 2 overlap: tap (ky,kx) of patch i is pixel
+// Space-to-depth form.  The 4x4 patches at stride 2 overlap: tap (ky,kx) of patch i is pixel
 // 2i + (ky,kx), so a score is a sum of per-pixel dot products that neighbouring (query, key) pairs share,
 //   S[i][j] = sum_{d in {0,1}^2} E[i+d][j+d],   E[r][s] = sum_{cls, c} x[2r+cls][c] * xn[2s+cls][c]
 // with r, s on the class grid hc x wc = h/2 x w/2 (i, j on its (hc-1) x (wc-1) sub-grid) and cls the 4 pixel parities:
 // E is ONE GEMM of the space-to-depth tensors, K = 4*96 = 384 instead of 16*96 = 1536 per score.  The same
 // identity on the output side: an output pixel of class cls at grid position r sums P over the <= 4 patches covering it,
 //   out[2r+cls] = sum_s P~[r][s] * x[2s+cls],      P~[r][s] = sum_{d} P[r-d][s-d],
-// one GEMM with K = R = hc*wc instead of 4*L.  Together 3.75x fewer multiply-adds than the patch form above
+// one GEMM with K = R = hc*wc instead of 4*L.  Together 3.75x fewer multiply-adds than the patch form
 // (2*R^2*384*2 vs 2*L^2*1536*2 per image), and both GEMMs run the shared 32-k chunk core with b128 fragments
 // (the values are staged transposed, [class][channel][key], so the A operand is k-contiguous).
 // Kernels: prep (xn, key validity, transposed values) -> E GEMM -> row softmax (forms S from E on the fly; one wave per
@@ -1718,34 +1413,15 @@ static hipError_t launch_attention_v2_t(const AttParams& p0, hipStream_t st) {
     const long big_grid = (long)((p.R + 255) / 256) * 4 * p.B;
     set_launch_cost(2.0 * p.B * (double)p.L * p.L * 1536.0, (BF16 ? 2.0 : 4.0) * 2.0 * p.B * (double)p.h * p.w * 96, nullptr,
                     2.0 * p.B * 4.0 * (double)p.R * p.Rp * 96.0);
-    // pixel tile of the large-batch form, chosen on the GPU (SE_ATT_PV_PT overrides): 256 pixels (PT = 4) need 88 KB of LDS --
-    // ONE workgroup per CU; 128 (fp32) / 192 (bf16) fit two, whose barrier and DMA waits overlap: fp32 784 -> 747 us at
-    // 512x512 B=8, bf16 307 -> 247 us at 512x512 B=16 (same box, round 3)
-    const int pvpt = opt(OPT_ATT_PV_PT) > 0 ? opt(OPT_ATT_PV_PT) : (BF16 ? 3 : 2);
-    if (big_grid >= 512 && pvpt == 4) {
-      constexpr int PT = 4, NT = 6;
+    // pixel tile of the large-batch form, chosen on the GPU: 256 pixels (PT = 4) need 88 KB of LDS -- ONE workgroup per CU;
+    // 128 (fp32) / 192 (bf16) fit two, whose barrier and DMA waits overlap: fp32 784 -> 747 us at 512x512 B=8, bf16
+    // 307 -> 247 us at 512x512 B=16 (same box, round 3)
+    if (big_grid >= 512) {
+      constexpr int PT = BF16 ? 3 : 2, NT = 6;
       constexpr int LDS = 2 * PT * 64 * 128 + 2 * NT * 16 * 128;
       hipError_t e = ensure_max_lds((const void*)att2_pv_kernel<PT, NT, BF16>, LDS);
       if (e != hipSuccess) return e;
-      dim3 grid((unsigned)big_grid);
-      set_launch_grid((long)grid.x);
-      ProfScope ps_(st, PL_ATT_PV);
-      hipLaunchKernelGGL((att2_pv_kernel<PT, NT, BF16>), grid, dim3(256), LDS, st, p);
-    } else if (big_grid >= 512 && pvpt == 3) {
-      constexpr int PT = 3, NT = 6;
-      constexpr int LDS = 2 * PT * 64 * 128 + 2 * NT * 16 * 128;
-      hipError_t e = ensure_max_lds((const void*)att2_pv_kernel<PT, NT, BF16>, LDS);
-      if (e != hipSuccess) return e;
-      dim3 grid((unsigned)(((p.R + 191) / 192) * 4 * p.B));
-      set_launch_grid((long)grid.x);
-      ProfScope ps_(st, PL_ATT_PV);
-      hipLaunchKernelGGL((att2_pv_kernel<PT, NT, BF16>), grid, dim3(256), LDS, st, p);
-    } else if (big_grid >= 512 && pvpt == 2) {
-      constexpr int PT = 2, NT = 6;
-      constexpr int LDS = 2 * PT * 64 * 128 + 2 * NT * 16 * 128;
-      hipError_t e = ensure_max_lds((const void*)att2_pv_kernel<PT, NT, BF16>, LDS);
-      if (e != hipSuccess) return e;
-      dim3 grid((unsigned)(((p.R + 127) / 128) * 4 * p.B));
+      dim3 grid((unsigned)(((p.R + PT * 64 - 1) / (PT * 64)) * 4 * p.B));
       set_launch_grid((long)grid.x);
       ProfScope ps_(st, PL_ATT_PV);
       hipLaunchKernelGGL((att2_pv_kernel<PT, NT, BF16>), grid, dim3(256), LDS, st, p);
@@ -1771,16 +1447,8 @@ hipError_t launch_att2_prep(const AttParams& p, hipStream_t st) {
   return hipGetLastError();
 }
 
-static hipError_t launch_attention_v2(const AttParams& p, hipStream_t st) {
-  return p.bf16 ? launch_attention_v2_t<true>(p, st) : launch_attention_v2_t<false>(p, st);
-}
-
-// SE_ATT_V1=1 selects the patch form (materialised L x L scores, K = 1536 / 4L) for A/B measurements
 hipError_t launch_attention(const AttParams& p, hipStream_t st) {
-  return p.E ? launch_attention_v2(p, st) : launch_attention_v1(p, st);
-}
-bool attention_v2_enabled() {
-  return opt(OPT_ATT_V1) == 0;
+  return p.bf16 ? launch_attention_v2_t<true>(p, st) : launch_attention_v2_t<false>(p, st);
 }
 
 }  // namespace se

@@ -48,14 +48,11 @@ hipError_t ensure_max_lds(const void* func, int bytes);
   X(RTILE_DENSE, 1)      /* 0: channel-padded K for the 5x5 first layers */                                    \
   X(RTILE_D5W, 1)        /* 0: 5x5 first layers on the direct dense-K kernel */                                \
   X(TEST_OFFSET_LIMIT, 0) /* test aid, se_debug_set_option only: byte range of the 32-bit-offset kernels (0: 2^31) */ \
-  X(RCONV16, 1) X(RCONV16_DUAL, 1) X(RCONV16_TILE, 8) X(RCONV96, 1) X(VECBIAS, 1)                              \
+  X(RCONV16, 1) X(RCONV16_DUAL, 1) X(RCONV96, 1) X(VECBIAS, 1)                                                  \
   X(WINOGRAD, 1) X(WINOGRAD48, 1) X(WINOGRAD_UP, 1) X(WINOGRAD_UP48, 1)                                         \
   X(WINOGRAD_F43, 1)     /* hybrid F(2,3)xF(4,3): 0 off, 1 everywhere, 2 netG only */ \
-  X(WINO48_TILES, 64) X(WINOUP_TILES, 64)                                                                       \
-  X(GCONV_FAST, 1) X(GCONV_VARIANT_N192, 0) X(GCONV_VARIANT_N96, 0) X(GCONV_VARIANT_N48, 0) X(GCONV_VARIANT_N24, 0) \
-  X(LL_STAGES, 2) X(FORK_DEFAULT, 1) X(LL_WINO_MIN_WG, 64) X(LL_WINO48_MIN_WG, 128)                                                                                               \
-  X(ATT_V1, 0) X(ATT_FUSED, -1) X(ATT_FUSED_BF16, -1) X(ATT_PTILDE_LDS, 1) X(ATT_STATS_LDS, 1) X(ATT_E16, 1)      \
-  X(ATT_SYM, 1) X(ATT_PV_PT, -1)                                                                                \
+  X(GCONV_FAST, 1) X(FORK_DEFAULT, 1) X(LL_WINO_MIN_WG, 64) X(LL_WINO48_MIN_WG, 128)                            \
+  X(ATT_FUSED, -1) X(ATT_FUSED_BF16, -1) X(ATT_PTILDE_LDS, 1) X(ATT_STATS_LDS, 1) X(ATT_E16, 1) X(ATT_SYM, 1)   \
   X(ATT_STREAM, 0)       /* attention form: 0 by size (streaming where R Rp 4 >= 2^31), 1 streaming wherever possible */
 enum Opt {
 #define X(name, dflt) OPT_##name,
@@ -174,20 +171,18 @@ hipError_t launch_winoup48(const WinoParams& p, hipStream_t st);
 // ---------------------------------------------------------------------------------------------
 struct RConvParams {
   const void* src;     // bf16 NHWC [B][h][w][96]
-  const void* wpk;     // bf16 weights: image of pack_layer16 [14 chunks][192 rows][64 k] (16 x 16 tiles) or of
-                       // pack_rconv16 [27 steps][12 row tiles][16 rows][32 k] (8 x 16 tiles)
+  const void* wpk;     // bf16 weights: image of pack_rconv16 [27 steps][12 row tiles][16 rows][32 k]
   const float* bias;   // [192] packed-row order (features, then gates)
   void* dst;           // bf16 NHWC [B][h][w][96]
   int B, h, w, d;      // dilation d; h % d == 0 and w % d == 0
   int hs, ws;          // polyphase sub-image size h/d x w/d
-  int ty, tx;          // tiles per sub-image (16 x 16, or 8 rows x 16 columns)
+  int ty, tx;          // 8 x 16 tiles per sub-image
   int act;             // 0 ELU, 1 ReLU
   int xcd;             // 1: XCD-aware tile order
-  const float* vbias;  // optional [B][9][192] fp32: folded vector source (launch_vecbias; d == 1; 8 x 16 tiles only)
-  int dual;            // 8 x 16 tiles only: ws == 8, d even -- two phases (py, px), (py, px + 1) side by side in one tile
+  const float* vbias;  // optional [B][9][192] fp32: folded vector source (launch_vecbias; d == 1)
+  int dual;            // ws == 8, d even: two phases (py, px), (py, px + 1) side by side in one tile
 };
 hipError_t launch_rconv16(const RConvParams& p, hipStream_t st);
-bool rconv16_small_tiles();   // 8 x 16 tiles, two workgroups per CU (default) / SE_RCONV16_TILE=16
 
 // ---------------------------------------------------------------------------------------------
 // Raw-tile form of the 96-row bf16 gated convs, stride 1 (se_rconv96.hip): 3x3 48 -> 96 / 24 -> 96, gen_deconv 96 -> 96
@@ -308,8 +303,8 @@ struct AttParams {
   const float* rn;     // [B][96]  1/sqrt(sum x^2 + 1e-8)
   float* xn;           // NHWC [B][h][w][96]   workspace: x * rn (keys)
   const float* hard;   // (B,1,4h,4w) full-resolution hole mask
-  float* valid;        // [B][Lp]  workspace: key validity {0,1}
-  float* S;            // [B][L][Lp] workspace: scores, query-major
+  float* valid;        // unused (kept so that no kernel's argument offsets move)
+  float* S;            // unused (likewise)
   float* out;          // NHWC [B][h][w][96]
   int B, h, w, hs, ws, L, Lp;
   float scale;         // softmax scale (10)
@@ -338,8 +333,7 @@ struct AttParams {
   int sym;             // set by the launcher: att2_pair_kernel computes the tiles on / right of the diagonal and mirrors them (fp32)
   int symT;            //   ... computed tiles per image (1-D grid)
 };
-hipError_t launch_attention(const AttParams& p, hipStream_t st);    // p.E != null: space-to-depth form, else the patch form
-bool attention_v2_enabled();
+hipError_t launch_attention(const AttParams& p, hipStream_t st);    // materialised space-to-depth form (E, P non-null)
 // O(R) preparation of the space-to-depth form: xn, key tables (validR, kmul, kadd), transposed values xT (att2_prep, _transpose)
 hipError_t launch_att2_prep(const AttParams& p, hipStream_t st);
 // streaming form (se_att_stream.hip): E = P = null; needs xn, xT (plus att_stream_xt_tail() zeroed floats behind it), validR,

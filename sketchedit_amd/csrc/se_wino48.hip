@@ -10,7 +10,7 @@
 //   * 96 packed rows in the MIXED order (8 features + their 8 gates per 16-row tile, gate exchange by a lane
 //     swap in the epilogue), so a wave owns 3 row tiles x 32 tiles: 5 LDS fragment reads per 24 MFMAs (7 in
 //     se_wino.hip) and the same 24 + 96 accumulator registers.
-//   * One workgroup = 8 waves = 128 tiles; a lane stages TWO granules per iteration (same tile and slot in both
+//   * One workgroup = 4 waves = 64 tiles; a lane stages TWO granules per iteration (same tile and slot in both
 //     k-halves), from two offset sets: one for the even, one for the odd position of the pair.
 //
 // CIN = 24 (round 5: xconv3 / pmconv3 of netG, 24 -> 96 at the 128x128 level -- editline_g.py:63,75 -- two launches of 195 us
@@ -388,8 +388,9 @@ __global__ __launch_bounds__(TILES * 4, 2) void wino48_kernel(const WinoParams p
   W48_TRACE_DUMP();
 }
 
-// 64 tiles / 4 waves / 80 KB per workgroup (default): two workgroups share a CU, one's prologue, fold and epilogue run
-// under the other's MFMAs.  SE_WINO48_TILES=128 selects the 8-wave, one-workgroup-per-CU shape of round 1.
+// 64 tiles / 4 waves / 80 KB per workgroup: two workgroups share a CU, one's prologue, fold and epilogue run under the
+// other's MFMAs.  The trace build runs the 8-wave, one-workgroup-per-CU shape of round 1 (128 tiles), for which its stamps
+// are laid out.
 template <int TILES, int CIN = 48>
 static hipError_t launch_wino48_t(const WinoParams& p, hipStream_t st) {
   constexpr int LDS = 3 * TILES * 128 + 4 * 96 * 128 + 8 * TILES * 4 * 4 + (W48_TRACE_LDS ? 2 * 48 * 8 * 8 : 0);     // X ring + W ring 48 KB + source offsets
@@ -403,10 +404,7 @@ static hipError_t launch_wino48_t(const WinoParams& p, hipStream_t st) {
   hipLaunchKernelGGL((wino48_kernel<TILES, CIN>), dim3(grid), dim3(TILES * 4), LDS, st, p);
   return hipGetLastError();
 }
-hipError_t launch_wino48(const WinoParams& p, hipStream_t st) {
-  const bool big = W48_TRACE_LDS || opt(OPT_WINO48_TILES) == 128;
-  return big ? launch_wino48_t<128>(p, st) : launch_wino48_t<64>(p, st);
-}
+hipError_t launch_wino48(const WinoParams& p, hipStream_t st) { return launch_wino48_t<W48_TRACE_LDS ? 128 : 64>(p, st); }
 // 24 -> 96 (src NHWC 24 channels; upk [16 positions][96 MIXED rows][32 k: channels 0-23, then zeros], pack_wino48 with cin 24)
 hipError_t launch_wino48_c24(const WinoParams& p, hipStream_t st) { return launch_wino48_t<64, 24>(p, st); }
 

@@ -8,7 +8,7 @@
 // 9 transform positions x K=96 instead of 4 taps x K=96 per 4 outputs (16/9 fewer multiply-adds than the sub-pixel
 // form, 4x fewer than the reference-defined layer); every coefficient is 0 or +-1.  The four class workgroups of a tile
 // group run side by side on one XCD (class_tile, se_device.h) so that they share the source tile through its L2.
-// Structure, pipeline and epilogue as se_wino48.hip (96 MIXED rows, a wave = 3 row tiles x 32 tiles, 128 tiles per
+// Structure, pipeline and epilogue as se_wino48.hip (96 MIXED rows, a wave = 3 row tiles x 32 tiles, 64 tiles per
 // workgroup, two staged granules per lane), loop as se_wino.hip (27 iterations = 9 positions x 3 chunks, fold at the
 // first chunk of the next position).  Source pixels whose B^T factor is structurally zero are not loaded.
 #include "se_device.h"
@@ -279,9 +279,9 @@ __global__ __launch_bounds__(TILES * 4, 2) void winoup_kernel(const WinoParams p
   }
 }
 
-// 64 tiles / 4 waves / 78 KB per workgroup (default): two workgroups per CU (se_wino48.hip); SE_WINOUP_TILES=128: 8 waves
-template <int TILES>
-static hipError_t launch_winoup_t(const WinoParams& p, hipStream_t st) {
+// 64 tiles / 4 waves / 78 KB per workgroup: two workgroups per CU (se_wino48.hip)
+hipError_t launch_winoup(const WinoParams& p, hipStream_t st) {
+  constexpr int TILES = 64;
   constexpr int LDS = 3 * TILES * 128 + 4 * 96 * 128 + 6 * TILES * 4 * 4;     // X ring + W ring 48 KB + source offsets
   {
     hipError_t e = ensure_max_lds((const void*)winoup_kernel<TILES>, LDS);
@@ -292,10 +292,6 @@ static hipError_t launch_winoup_t(const WinoParams& p, hipStream_t st) {
   ProfScope ps_(st, PL_WINO_UP96);
   hipLaunchKernelGGL(winoup_kernel<TILES>, dim3(grid), dim3(TILES * 4), LDS, st, p);
   return hipGetLastError();
-}
-hipError_t launch_winoup(const WinoParams& p, hipStream_t st) {
-  const bool big = opt(OPT_WINOUP_TILES) == 128;
-  return big ? launch_winoup_t<128>(p, st) : launch_winoup_t<64>(p, st);
 }
 
 }  // namespace se

@@ -16,10 +16,10 @@ KERNEL_LABELS = {
     "rtilew2_kernel": "gconv_n24", "rtilew_kernel": "gconv_n24", "rtile_kernel<2": "gconv_n24", "gconv_kernel<2": "gconv_n24",
     "dtail_kernel": "dtail",
     # attention
-    "att2_pair_kernel": "att_score", "att_score_kernel": "att_score", "att2_pv_kernel": "att_pv", "att_pv_kernel": "att_pv",
-    "att2_softmax": "att_softmax", "att2_stats": "att_softmax", "att_softmax_kernel": "att_softmax",
+    "att2_pair_kernel": "att_score", "att2_pv_kernel": "att_pv",
+    "att2_softmax": "att_softmax", "att2_stats": "att_softmax",
     "att2_boxsum": "att_boxsum", "att2_ptilde": "att_boxsum",
-    "att2_prep": "att_prep", "att2_transpose": "att_prep", "att2_emean": "att_prep", "att2_eoff": "att_prep", "att_prep_kernel": "att_prep",
+    "att2_prep": "att_prep", "att2_transpose": "att_prep", "att2_emean": "att_prep", "att2_eoff": "att_prep",
     "att2_similar": "layout",
     # the rest
     "small_conv_kernel": "small_conv", "pack_": "pack", "colreduce": "colreduce", "vecbias_kernel": "colreduce",

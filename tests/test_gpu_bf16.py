@@ -97,7 +97,7 @@ RCONV = [(1, 16, 16, "elu"), (1, 32, 48, "relu"), (1, 22, 18, "elu"), (2, 24, 32
 
 @pytest.mark.parametrize("case", RCONV, ids=["d%d-%dx%d-%s" % c for c in RCONV])
 def test_op_rconv16_raw_tile_bf16(eng, case):
-    """96 -> 192 3x3 stride 1 in the raw-tile form (se_rconv16.hip): exact and ragged 16x16 tiles, the image borders (zero
+    """96 -> 192 3x3 stride 1 in the raw-tile form (se_rconv16.hip): exact and ragged 8x16 tiles, the image borders (zero
     padding through the buffer range check), dilations through the polyphase sub-images."""
     from oracle import sketchedit_oracle as O
     d, H, W, act = case

@@ -512,6 +512,10 @@ def test_developer_switches_are_a_table_read_once():
         _lib.set_option("SE_NO_SUCH_SWITCH", 1)
     with pytest.raises(_lib.SketchEditHipError):
         _lib.get_option("SE_WINOGRAD_F43_SKIP")           # removed in round 5
+    for retired in ("SE_ATT_V1", "SE_GCONV_VARIANT_N192", "SE_GCONV_VARIANT_N96", "SE_GCONV_VARIANT_N48", "SE_GCONV_VARIANT_N24",
+                    "SE_LL_STAGES", "SE_RCONV16_TILE", "SE_WINOUP_TILES", "SE_WINO48_TILES", "SE_ATT_PV_PT"):
+        with pytest.raises(_lib.SketchEditHipError):
+            _lib.get_option(retired)                      # A/B-only variants, retired with their kernels
     # a fresh process takes its initial values from the environment -- except the test aid, which only the call can set
     code = ("from sketchedit_amd import _lib; print(_lib.get_option('SE_WINOGRAD_F43'), _lib.get_option('SE_ATT_E16'), "
             "_lib.get_option('SE_TEST_OFFSET_LIMIT'))")

@@ -16,20 +16,16 @@ fi
 tail -n 40 $out/pytest.log
 if [ "$3" == "nobench" ]; then exit 0; fi
 Q="--full --no-cpu-baseline --no-parity --no-traffic --no-secondary"
-# batch-1 latency: round-1 kernels (SE_ATT_V1 patch-form attention, default launch shapes) vs the low-latency mode
-SE_ATT_V1=1 timeout 300 python bench.py --batch 1 --low-latency off $Q --steps 30 > $out/b1_256_r01.json 2> $out/b1_256_r01.err
+# batch-1 latency: default launch shapes vs the low-latency mode
 timeout 300 python bench.py --batch 1 --low-latency off $Q --steps 30 > $out/b1_256_default.json 2> $out/b1_256_default.err
 timeout 300 python bench.py --batch 1 --low-latency on $Q --steps 30 --layers > $out/b1_256_lowlat.json 2> $out/b1_256_lowlat.err
 timeout 300 python bench.py --batch 1 --low-latency on --graph $Q --steps 30 > $out/b1_256_graph.json 2> $out/b1_256_graph.err
-SE_ATT_V1=1 timeout 300 python bench.py --size 512 --batch 1 --low-latency off $Q --steps 20 > $out/b1_512_r01.json 2> $out/b1_512_r01.err
 timeout 300 python bench.py --size 512 --batch 1 --low-latency off $Q --steps 20 > $out/b1_512_default.json 2> $out/b1_512_default.err
 timeout 300 python bench.py --size 512 --batch 1 --low-latency on $Q --steps 20 > $out/b1_512_lowlat.json 2> $out/b1_512_lowlat.err
 timeout 300 python bench.py --size 512 --batch 1 --low-latency on --graph $Q --steps 20 > $out/b1_512_graph.json 2> $out/b1_512_graph.err
 timeout 300 python bench.py --size 512 --batch 1 --low-latency off --graph $Q --steps 20 > $out/b1_512_default_graph.json 2> $out/b1_512_default_graph.err
-# config 2 / config 3 lines, old vs new attention
-SE_ATT_V1=1 timeout 300 python bench.py $Q --layers > $out/c2_attv1.json 2> $out/c2_attv1.err
+# config 2 / config 3 lines
 timeout 300 python bench.py $Q --layers > $out/c2.json 2> $out/c2.err
-SE_ATT_V1=1 timeout 300 python bench.py --size 512 --batch 8 $Q --steps 20 > $out/c3_attv1.json 2> $out/c3_attv1.err
 timeout 300 python bench.py --size 512 --batch 8 $Q --steps 20 --layers > $out/c3.json 2> $out/c3.err
 # config 5 (bf16): 512x512 batch 16, and the config-2 shape for comparison
 timeout 300 python bench.py --dtype bf16 --size 512 --batch 16 $Q --steps 20 --layers > $out/c5_bf16.json 2> $out/c5_bf16.err

@@ -52,7 +52,6 @@ for cfg in $cfgs; do
     c3) python bench.py --full --size 512 --batch 8 --steps 30 --no-cpu-baseline > $out/c3_bench.json 2> $out/c3_bench.err; profile c3 --size 512 --batch 8 ;;
     c5) python bench.py --full --dtype bf16 --size 512 --batch 16 --steps 30 --no-cpu-baseline > $out/c5_bf16_bench.json 2> $out/c5_bf16_bench.err; profile c5_bf16 --dtype bf16 --size 512 --batch 16 ;;
     b1) for s in 256 512; do
-          SE_ATT_V1=1 python bench.py --size $s --batch 1 --low-latency off $Q --steps 50 > $out/b1_${s}_round1_kernels.json 2>/dev/null
           python bench.py --size $s --batch 1 --low-latency off $Q --steps 50 > $out/b1_${s}_default.json 2>/dev/null
           python bench.py --size $s --batch 1 --low-latency on $Q --steps 50 --layers > $out/b1_${s}_lowlat.json 2>/dev/null
           python bench.py --size $s --batch 1 --low-latency on --graph $Q --steps 50 > $out/b1_${s}_lowlat_graph.json 2>/dev/null
