@@ -1,5 +1,5 @@
-// Host side of libsketchedit_hip.so: context, weight repacking, workspace arena and the forward
-// plans of netM / netG / inference behind the C-ABI declared in include/sketchedit_hip.h.
+// Host side of libsketchedit_hip.so: context, workspace arena, kernel dispatch and the forward plans of
+// netM / netG / inference behind the C-ABI declared in include/sketchedit_hip.h (weight images: se_pack.hip).
 //
 // Layer tables restate the reference constructors
 //   DeepFillC2Generator.__init__  /root/reference/models/networks/editline_g.py:44-100
@@ -8,6 +8,7 @@
 // editline2_model.py:128-133,338-370).
 #include "../../include/sketchedit_hip.h"
 #include "se_kernels.h"
+#include "se_pack.h"
 
 #include <cstdarg>
 #include <cstdint>
@@ -17,6 +18,7 @@
 #include <algorithm>
 #include <map>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -24,12 +26,6 @@ using namespace se;
 
 namespace {
 
-enum { ACT_ELU = 0, ACT_RELU = 1, ACT_NONE = 2 };
-
-struct LayerDef {
-  const char* name;
-  int cin, cout, k, stride, rate, act, up;
-};
 
 #define ENC(p)                                                                                    \
   {p "2_downsample", 24, 96, 3, 2, 1, ACT_ELU, 0}, {p "3", 48, 96, 3, 1, 1, ACT_ELU, 0},          \
@@ -64,34 +60,6 @@ const LayerDef M_LAYERS[] = {
 };
 const int NG = sizeof(G_LAYERS) / sizeof(LayerDef), NM = sizeof(M_LAYERS) / sizeof(LayerDef);
 
-struct Layer {
-  LayerDef def;
-  std::vector<float> w, b;    // host copies in checkpoint layout
-  bool have_w = false, have_b = false, packed = false;
-  // packed device image
-  int cfg = -1, NP = 0, nch = 0, G = 0, CGp = 0, T = 0, C0 = 0, C1 = 0;
-  float* d_w = nullptr;
-  float* d_b = nullptr;
-  float* d_u = nullptr;       // Winograd-transformed weights (eligible layers only)
-  float* d_ub = nullptr;      // bias in the row order of the 48 -> 96 Winograd kernel (MIXED tiles)
-  // bf16 image (BASELINE config 5): same row order and slot swizzle, 64 bf16 k-values per 128-byte row, 8-channel granules
-  float* d_w16 = nullptr;
-  int nch16 = 0, CGp16 = 0;
-  float* d_w16d = nullptr;    // bf16, 5x5 layers whose stored input has <= 4 real channels: pair-of-taps image (pack_layer16_d4, se_rtile.hip)
-  float* d_w16s = nullptr;    // 96 -> 192 3x3 only: the 32-k step image of the 8 x 16 raw-tile kernel (se_rconv16.hip)
-  float* d_w96 = nullptr;     // 96-row stride-1 layers: the 32-k step image of se_rconv96.hip
-  float* d_u1 = nullptr;      // two-source 96+96 -> 192 layers: Winograd image of the FIRST source's 96 channels alone, and
-  float* d_wv = nullptr;      //   the second source's direct weights [9 taps][96][192 packed rows] (vector source folded into a bias)
-  float* d_wv16 = nullptr;    //   the same rounded to bf16 (kept as fp32 values) for the bf16 mode
-  float* d_u24 = nullptr;     // 96 -> 192 3x3: image of the hybrid F(2,3) x F(4,3) kernel (first 96 input channels), se_wino24.hip
-  float* d_ub24 = nullptr;    //   and the bias in its MIXED row order
-  float* d_u24b = nullptr;    //   two-source layers: the image over both sources (6 chunks per position)
-  float* d_wx = nullptr;      // 24 -> 24 3x3: image of the F(2,3)-along-x raw-tile kernel (se_rtilew.hip)
-  float* d_wx2 = nullptr;     //   and of its two-dimensional F(2x2,3x3) form
-  float* d_wd = nullptr;      // 5x5 layers with padding channels in their stored input (fp32): dense-K image (se_rtile.hip)
-  float* d_wdw = nullptr;     //   and the image of its F(2,5)-along-x form (rtile_dense5w_kernel)
-  int dense = 0, nchd = 0;    //   real channels per pixel (3 or 5), 32-k chunks of the dense image
-};
 
 // ---- workspace arena: first-fit free list over [0, cap) in bytes, 256-B aligned ------------------
 struct Arena {
@@ -216,23 +184,6 @@ int fail(se_ctx* c, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(c, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-// ---- weight packing -------------------------------------------------------------------------------
-// Build the LDS image [nch][NP][32] of a gated conv: row n = packed output channel, k = flattened
-// (tap, packed input channel); the 16-B slot s of row n is stored at physical slot s ^ ((n>>1)&7).
-// cin_map[pc] = checkpoint input channel of packed channel pc, or -1 for zero padding.
-float bf16_round(float f);
-bool wino_eligible_layer(const LayerDef& d);
-int pack_wino(se_ctx* c, Layer& L);
-int pack_wino24(se_ctx* c, Layer& L);
-int pack_rtilew(se_ctx* c, Layer& L);
-bool wino48_eligible_layer(const LayerDef& d);
-int pack_wino48(se_ctx* c, Layer& L);
-int pack_wino48_c24(se_ctx* c, Layer& L);
-bool winoup_eligible_layer(const LayerDef& d);
-int pack_winoup(se_ctx* c, Layer& L);
-bool winoup48_eligible_layer(const LayerDef& d);
-int pack_winoup48(se_ctx* c, Layer& L);
-
 int xcd_remap_enabled() { return opt(OPT_XCD_REMAP); }     // SE_XCD_REMAP=0 switches the XCD-aware tile order off (A/B measurements)
 
 // Every raw-tile / Winograd / gather kernel addresses its source through a buffer resource with 32-bit BYTE offsets and uses
@@ -243,723 +194,6 @@ int xcd_remap_enabled() { return opt(OPT_XCD_REMAP); }     // SE_XCD_REMAP=0 swi
 long long addr_limit() {
   const int v = opt(OPT_TEST_OFFSET_LIMIT);
   return v > 0 ? (long long)v : (1ll << 31);
-}
-
-int choose_cfg(int G) {
-  if (G <= 16) return GC_N24;
-  if (G <= 24) return GC_N48;
-  if (G <= 48) return GC_N96;
-  if (G <= 96) return GC_N192;
-  return -1;
-}
-
-int out_channel_of_row(int cfg, int n, int G, int cout) {
-  // returns checkpoint output channel for packed row n (features [0,G), gates [G,2G)), or -1
-  const int NP = gconv_np(cfg);
-  if (!gconv_mixed(cfg)) {
-    const int NF = NP / 32;  // feature tiles
-    const int nt = n / 16, r = n % 16;
-    if (nt < NF) { int f = nt * 16 + r; return f < G ? f : -1; }
-    int g = (nt - NF) * 16 + r;
-    return g < G ? G + g : -1;
-  }
-  const int nt = n / 16, r = n % 16;
-  if (r < 8) { int f = nt * 8 + r; return f < G ? f : -1; }
-  int g = nt * 8 + (r - 8);
-  return g < G ? G + g : -1;
-}
-
-int pack_layer(se_ctx* c, Layer& L, const std::vector<int>& cin_map) {
-  const LayerDef& d = L.def;
-  const int G = d.cout / 2;
-  const int cfg = choose_cfg(G);
-  if (cfg < 0 || (G % 4)) return fail(c, "layer %s: unsupported gated width %d", d.name, G);
-  const int NP = gconv_np(cfg);
-  const int Cp = (int)cin_map.size();          // packed channels per tap (multiple of 4)
-  // gen_deconv (nearest x2 + 3x3) is packed in its sub-pixel form: 4 output parity classes, each a 2x2 conv on
-  // the source grid; tap a of class py sums the kernel rows that land on source row yy + a - 1 + py:
-  //   py=0: a=0 <- {ky 0}, a=1 <- {ky 1,2};   py=1: a=0 <- {ky 0,1}, a=1 <- {ky 2}      (same for columns)
-  const bool up2 = d.up != 0;
-  const int KW = up2 ? 2 : d.k;
-  const int T = KW * KW;
-  const int K = T * Cp;
-  const int nch = (K + 31) / 32;
-  const int ncls = up2 ? 4 : 1;
-  std::vector<float> img((size_t)ncls * nch * NP * 32, 0.f), bias(NP, 0.f);
-  auto lo = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2); };
-  auto hi = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2); };
-  for (int cls = 0; cls < ncls; ++cls) {
-    const int py = cls >> 1, px = cls & 1;
-    for (int n = 0; n < NP; ++n) {
-      const int oc = out_channel_of_row(cfg, n, G, d.cout);
-      if (oc < 0) continue;
-      bias[n] = L.b[oc];
-      for (int kf = 0; kf < K; ++kf) {
-        const int tap = kf / Cp, pc = kf % Cp;
-        const int ic = cin_map[pc];
-        if (ic < 0) continue;
-        const int ty = tap / KW, tx = tap % KW;
-        float v = 0.f;
-        if (up2) {
-          for (int ky = lo(py, ty); ky <= hi(py, ty); ++ky)
-            for (int kx = lo(px, tx); kx <= hi(px, tx); ++kx) v += L.w[(((size_t)oc * d.cin + ic) * 3 + ky) * 3 + kx];
-        } else {
-          v = L.w[(((size_t)oc * d.cin + ic) * d.k + ty) * d.k + tx];
-        }
-        const int ch = kf / 32, kin = kf % 32, s = kin / 4, e = kin % 4;
-        const int ps = s ^ ((n >> 1) & 7);
-        img[(((size_t)cls * nch + ch) * NP + n) * 32 + ps * 4 + e] = v;
-      }
-    }
-  }
-  if (L.d_w) (void)hipFree(L.d_w);
-  if (L.d_b) (void)hipFree(L.d_b);
-  HIPCHK(c, hipMalloc(&L.d_w, img.size() * 4));
-  HIPCHK(c, hipMalloc(&L.d_b, bias.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_w, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-  L.cfg = cfg; L.NP = NP; L.nch = nch; L.G = G; L.CGp = Cp / 4; L.T = T;
-  L.packed = true;
-  if (wino_eligible_layer(d) && Cp == d.cin) return pack_wino(c, L);
-  if (d.k == 3 && d.stride == 1 && !d.up && d.cin == 48 && d.cout == 192 && d.act != ACT_NONE && Cp == d.cin) return pack_wino24(c, L);      // xconv5
-  if (d.k == 3 && d.stride == 1 && !d.up && d.rate == 1 && d.cin == 24 && d.cout == 24 && d.act != ACT_NONE && Cp == d.cin) return pack_rtilew(c, L);   // conv16
-  if (wino48_eligible_layer(d) && Cp == d.cin) return pack_wino48(c, L);
-  if (d.k == 3 && d.stride == 1 && !d.up && d.cin == 24 && d.cout == 96 && d.act != ACT_NONE && Cp == d.cin) return pack_wino48_c24(c, L);   // xconv3, pmconv3
-  if (winoup_eligible_layer(d) && Cp == d.cin) return pack_winoup(c, L);
-  if (winoup48_eligible_layer(d) && Cp == d.cin) return pack_winoup48(c, L);
-  return 0;
-}
-
-// Dense-K image of a 5x5 first layer (se_rtile.hip rtile_dense5_kernel): k = tap * Cd + channel over the Cd channels the
-// stored input really carries (cin_map[pc] = checkpoint input channel of stored channel pc), no channel padding; in the
-// last chunk the real k are packed instruction-major (k-step (half, r) holds the four k of lane groups 0..3), so the
-// kernel issues exactly ceil(K / 4) MFMA k-steps.  Rows in the MIXED order of the N=48 configuration, slot swizzle as
-// pack_layer.
-int pack_layer_dense(se_ctx* c, Layer& L, const std::vector<int>& cin_map) {
-  const LayerDef& d = L.def;
-  const int Cd = (int)cin_map.size();
-  const int G = d.cout / 2, NP = 48, T = d.k * d.k, K = T * Cd, nch = (K + 31) / 32;
-  std::vector<float> img((size_t)nch * NP * 32, 0.f);
-  for (int n = 0; n < NP; ++n) {
-    const int oc = out_channel_of_row(GC_N48, n, G, d.cout);
-    if (oc < 0) continue;
-    for (int kf = 0; kf < K; ++kf) {
-      const int tap = kf / Cd, ic = cin_map[kf % Cd], ty = tap / d.k, tx = tap % d.k;
-      const int ch = kf / 32;
-      int kin = kf % 32;
-      {      // dense_kin: j-th k of a chunk -> k-step j / 4, lane group j % 4 (instruction-major).  In the last chunk that packs the
-             // real k into the first k-steps (the others are not issued); in every chunk it makes the four lane groups of one
-             // k-step read four CONSECUTIVE dwords of the dense tile (bank-conflict-free; k-major order: 32-50 % conflict cycles)
-        const int j = kin, step = j / 4, g = j % 4;
-        kin = (step / 4) * 16 + g * 4 + (step % 4);
-      }
-      const int s_ = kin / 4, e = kin % 4, ps = s_ ^ ((n >> 1) & 7);
-      img[((size_t)ch * NP + n) * 32 + ps * 4 + e] = L.w[(((size_t)oc * d.cin + ic) * d.k + ty) * d.k + tx];
-    }
-  }
-  if (L.d_wd) (void)hipFree(L.d_wd);
-  HIPCHK(c, hipMalloc(&L.d_wd, img.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_wd, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  L.dense = Cd; L.nchd = nch;
-  // F(2,5)-along-x form (rtile_dense5w_kernel): U[nu][ky][c] = sum_kx Gx[nu][kx] w[ky][kx]; one chunk per position with
-  // k = ky * Cd + c in the same instruction-major order
-  {
-    static const double Gx[6][5] = {{1. / 4, 0., 0., 0., 0.}, {-1. / 6, -1. / 6, -1. / 6, -1. / 6, -1. / 6}, {-1. / 6, 1. / 6, -1. / 6, 1. / 6, -1. / 6},
-                                    {1. / 24, 1. / 12, 1. / 6, 1. / 3, 2. / 3}, {1. / 24, -1. / 12, 1. / 6, -1. / 3, 2. / 3}, {0., 0., 0., 0., 1.}};
-    std::vector<float> imw((size_t)6 * NP * 32, 0.f);
-    for (int n = 0; n < NP; ++n) {
-      const int oc = out_channel_of_row(GC_N48, n, G, d.cout);
-      if (oc < 0) continue;
-      for (int j = 0; j < 5 * Cd; ++j) {
-        const int ky = j / Cd, ic = cin_map[j % Cd];
-        const float* g = &L.w[(((size_t)oc * d.cin + ic) * 5 + ky) * 5];
-        const int step = j / 4, gq = j % 4, kin = (step / 4) * 16 + gq * 4 + (step % 4);
-        const int s_ = kin / 4, e = kin % 4, ps = s_ ^ ((n >> 1) & 7);
-        for (int nu = 0; nu < 6; ++nu) {
-          double u = 0.;
-          for (int kx = 0; kx < 5; ++kx) u += Gx[nu][kx] * (double)g[kx];
-          imw[((size_t)nu * NP + n) * 32 + ps * 4 + e] = (float)u;
-        }
-      }
-    }
-    if (L.d_wdw) (void)hipFree(L.d_wdw);
-    HIPCHK(c, hipMalloc(&L.d_wdw, imw.size() * 4));
-    HIPCHK(c, hipMemcpy(L.d_wdw, imw.data(), imw.size() * 4, hipMemcpyHostToDevice));
-  }
-  return 0;
-}
-
-// fp32 -> bf16, round to nearest even (the rounding of v_cvt_pk_bf16_f32 and of torch's .to(bfloat16))
-unsigned short bf16_bits(float f) {
-  unsigned u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);   // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-float bf16_round(float f) {
-  const unsigned u = (unsigned)bf16_bits(f) << 16;
-  float r;
-  memcpy(&r, &u, 4);
-  return r;
-}
-
-// bf16 image of a gated conv: [class][chunk of 64 k][NP rows][64 bf16], k = flattened (tap, packed input channel) with the
-// channels of a tap padded to a multiple of 8 (one 16-byte granule = 8 channels); slot s of row n at s ^ ((n>>1)&7).
-// The sub-pixel sums of gen_deconv are formed in fp32 and rounded once.
-int pack_layer16(se_ctx* c, Layer& L, const std::vector<int>& cin_map) {
-  const LayerDef& d = L.def;
-  const int G = d.cout / 2;
-  const int cfg = choose_cfg(G);
-  if (cfg < 0 || (G % 4)) return fail(c, "layer %s: unsupported gated width %d", d.name, G);
-  const int NP = gconv_np(cfg);
-  const int Cp = (int)cin_map.size();          // packed channels per tap (multiple of 8)
-  const bool up2 = d.up != 0;
-  const int KW = up2 ? 2 : d.k;
-  const int T = KW * KW;
-  const int K = T * Cp;
-  const int nch = (K + 63) / 64;
-  const int ncls = up2 ? 4 : 1;
-  std::vector<unsigned short> img((size_t)ncls * nch * NP * 64, 0);
-  auto lo = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2); };
-  auto hi = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2); };
-  for (int cls = 0; cls < ncls; ++cls) {
-    const int py = cls >> 1, px = cls & 1;
-    for (int n = 0; n < NP; ++n) {
-      const int oc = out_channel_of_row(cfg, n, G, d.cout);
-      if (oc < 0) continue;
-      for (int kf = 0; kf < K; ++kf) {
-        const int tap = kf / Cp, pc = kf % Cp;
-        const int ic = cin_map[pc];
-        if (ic < 0) continue;
-        const int ty = tap / KW, tx = tap % KW;
-        float v = 0.f;
-        if (up2) {
-          for (int ky = lo(py, ty); ky <= hi(py, ty); ++ky)
-            for (int kx = lo(px, tx); kx <= hi(px, tx); ++kx) v += L.w[(((size_t)oc * d.cin + ic) * 3 + ky) * 3 + kx];
-        } else {
-          v = L.w[(((size_t)oc * d.cin + ic) * d.k + ty) * d.k + tx];
-        }
-        const int ch = kf / 64, kin = kf % 64, s_ = kin / 8, e = kin % 8;
-        const int ps = s_ ^ ((n >> 1) & 7);
-        img[(((size_t)cls * nch + ch) * NP + n) * 64 + ps * 8 + e] = bf16_bits(v);
-      }
-    }
-  }
-  if (L.d_w16) (void)hipFree(L.d_w16);
-  HIPCHK(c, hipMalloc(&L.d_w16, img.size() * 2));
-  HIPCHK(c, hipMemcpy(L.d_w16, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-  L.nch16 = nch; L.CGp16 = Cp / 8;
-  return 0;
-}
-
-// bf16 pair-of-taps image of a 5x5 first layer whose stored NHWC8 input carries at most four real channels (rtile_kernel<3, 8,
-// true, true>): granule gi = 3 ky + j (j = 0..2) holds the taps (ky, 2j) and (ky, 2j + 1) x stored channels 0-3, i.e. element
-// e = 4 (kx & 1) + c; kx = 5 does not exist (zero).  15 granules -> 2 chunks of 64 k; rows in the MIXED N=48 order, slot swizzle
-// as pack_layer16.  cin4[c] = checkpoint input channel of stored channel c, or -1.
-int pack_layer16_d4(se_ctx* c, Layer& L, const int (&cin4)[4]) {
-  const LayerDef& d = L.def;
-  const int G = d.cout / 2, NP = 48, nch = 2;
-  std::vector<unsigned short> img((size_t)nch * NP * 64, 0);
-  for (int n = 0; n < NP; ++n) {
-    const int oc = out_channel_of_row(GC_N48, n, G, d.cout);
-    if (oc < 0) continue;
-    for (int ky = 0; ky < 5; ++ky)
-      for (int kx = 0; kx < 5; ++kx)
-        for (int cc = 0; cc < 4; ++cc) {
-          const int ic = cin4[cc];
-          if (ic < 0) continue;
-          const int gi = 3 * ky + kx / 2, e = 4 * (kx & 1) + cc;
-          const int ch = gi / 8, s_ = gi % 8, ps = s_ ^ ((n >> 1) & 7);
-          img[((size_t)ch * NP + n) * 64 + ps * 8 + e] = bf16_bits(L.w[(((size_t)oc * d.cin + ic) * 5 + ky) * 5 + kx]);
-        }
-  }
-  if (L.d_w16d) (void)hipFree(L.d_w16d);
-  HIPCHK(c, hipMalloc(&L.d_w16d, img.size() * 2));
-  HIPCHK(c, hipMemcpy(L.d_w16d, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// bf16 image for rconv16b_kernel (96 -> 192, 3x3): [27 steps = tap * 3 + 32-channel group][12 row tiles][16 rows][32 k],
-// rows in the N=192 order (features, then gates); granule g (8 k) of row r at slot g ^ F[r >> 2], F = {0, 2, 3, 1}.
-int pack_rconv16(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  static const int F[4] = {0, 2, 3, 1};
-  std::vector<unsigned short> img((size_t)27 * 192 * 32, 0);
-  for (int n = 0; n < 192; ++n) {
-    const int oc = out_channel_of_row(GC_N192, n, 96, 192);
-    const int rt = n / 16, r = n % 16;
-    for (int s = 0; s < 27; ++s) {
-      const int tap = s / 3, kk = s % 3, ty = tap / 3, tx = tap % 3;
-      for (int e = 0; e < 32; ++e) {
-        const int ic = kk * 32 + e, g = e / 8;
-        const float v = L.w[(((size_t)oc * d.cin + ic) * 3 + ty) * 3 + tx];
-        img[((size_t)s * 12 + rt) * 512 + r * 32 + ((g ^ F[r >> 2]) * 8) + (e % 8)] = bf16_bits(v);
-      }
-    }
-  }
-  if (L.d_w16s) (void)hipFree(L.d_w16s);
-  HIPCHK(c, hipMalloc(&L.d_w16s, img.size() * 2));
-  HIPCHK(c, hipMemcpy(L.d_w16s, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// bf16 image for rconv96_kernel (96 packed rows: 3x3 24/48 -> 96, gen_deconv 96 -> 96):
-// [class][step][6 row tiles][16 rows][32 k], k = granule (8 channels) index tap * CG + cg, four granules per step; rows in
-// the N=96 order (features, then gates); granule g of row r at slot g ^ F[r >> 2], F = {0, 2, 3, 1}.
-bool rconv96_eligible(const LayerDef& d) {
-  if (d.cout != 96 || d.rate != 1 || d.k != 3 || d.act == ACT_NONE) return false;
-  if (d.stride == 2) return !d.up && d.cin == 24;                     // stride 2: the 24 -> 96 downsampling layers
-  if (d.stride != 1) return false;
-  return d.up ? d.cin == 96 : (d.cin == 48 || d.cin == 24);
-}
-int pack_rconv96(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  static const int F[4] = {0, 2, 3, 1};
-  const bool up2 = d.up != 0;
-  const int KW = up2 ? 2 : 3, T = KW * KW, CG = d.cin / 8, NG = T * CG, nstep = (NG + 3) / 4, ncls = up2 ? 4 : 1;
-  std::vector<unsigned short> img((size_t)ncls * nstep * 96 * 32, 0);
-  auto lo = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2); };
-  auto hi = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2); };
-  for (int cls = 0; cls < ncls; ++cls) {
-    const int py = cls >> 1, px = cls & 1;
-    for (int n = 0; n < 96; ++n) {
-      const int oc = out_channel_of_row(GC_N96, n, 48, 96);
-      const int rt = n / 16, r = n % 16;
-      for (int gi = 0; gi < NG; ++gi) {
-        const int tap = gi / CG, cg = gi % CG, ty = tap / KW, tx = tap % KW, s_ = gi / 4, g = gi % 4;
-        for (int e = 0; e < 8; ++e) {
-          const int ic = cg * 8 + e;
-          float v = 0.f;
-          if (up2) {
-            for (int ky = lo(py, ty); ky <= hi(py, ty); ++ky)
-              for (int kx = lo(px, tx); kx <= hi(px, tx); ++kx) v += L.w[(((size_t)oc * d.cin + ic) * 3 + ky) * 3 + kx];
-          } else {
-            v = L.w[(((size_t)oc * d.cin + ic) * 3 + ty) * 3 + tx];
-          }
-          img[(((size_t)cls * nstep + s_) * 6 + rt) * 512 + r * 32 + ((g ^ F[r >> 2]) * 8) + e] = bf16_bits(v);
-        }
-      }
-    }
-  }
-  if (L.d_w96) (void)hipFree(L.d_w96);
-  HIPCHK(c, hipMalloc(&L.d_w96, img.size() * 2));
-  HIPCHK(c, hipMemcpy(L.d_w96, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// Winograd F(2x2,3x3) weights: U[pos] = (G g G^T)[xi][nu] per (out, in) pair, packed per position like a 1x1
-// conv Cin -> 192 (Cin = 96, or 192 for the two-source layers) in the N=192 row order (features then gates)
-// with the same slot swizzle.
-bool wino_eligible_layer(const LayerDef& d) {
-  return d.k == 3 && d.stride == 1 && !d.up && (d.cin == 96 || d.cin == 192) && d.cout == 192 && d.act != ACT_NONE;
-}
-int pack_wino(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  static const float Gm[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-  const int NP = 192, nch = d.cin / 32;
-  std::vector<float> img((size_t)16 * nch * NP * 32, 0.f);
-  for (int n = 0; n < NP; ++n) {
-    const int oc = out_channel_of_row(GC_N192, n, 96, 192);
-    for (int ic = 0; ic < d.cin; ++ic) {
-      const float* g = &L.w[((size_t)oc * d.cin + ic) * 9];
-      float t[4][3];
-      for (int i = 0; i < 4; ++i)
-        for (int kx = 0; kx < 3; ++kx) t[i][kx] = Gm[i][0] * g[kx] + Gm[i][1] * g[3 + kx] + Gm[i][2] * g[6 + kx];
-      for (int xi = 0; xi < 4; ++xi)
-        for (int nu = 0; nu < 4; ++nu) {
-          const float u = t[xi][0] * Gm[nu][0] + t[xi][1] * Gm[nu][1] + t[xi][2] * Gm[nu][2];
-          const int pos = xi * 4 + nu, ch = ic / 32, kin = ic % 32, s_ = kin / 4, e = kin % 4;
-          const int ps = s_ ^ ((n >> 1) & 7);
-          img[(((size_t)pos * nch + ch) * NP + n) * 32 + ps * 4 + e] = u;
-        }
-    }
-  }
-  if (L.d_u) (void)hipFree(L.d_u);
-  HIPCHK(c, hipMalloc(&L.d_u, img.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_u, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  if (d.cin == 192) {
-    // for a spatially constant second source (conv11 of netG: the pooled style vector) the layer runs as the single-source
-    // kernel on the first 96 channels plus a per-image bias table (launch_vecbias): the first source's Winograd image
-    // ([16 positions][3 chunks][192][32], the first three chunks of every position of `img`) and the second source's
-    // DIRECT weights [tap][channel][packed row]
-    std::vector<float> img1((size_t)16 * 3 * NP * 32), wv((size_t)9 * 96 * NP);
-    for (int pos = 0; pos < 16; ++pos)
-      memcpy(&img1[(size_t)pos * 3 * NP * 32], &img[(size_t)pos * nch * NP * 32], (size_t)3 * NP * 32 * 4);
-    for (int n = 0; n < NP; ++n) {
-      const int oc = out_channel_of_row(GC_N192, n, 96, 192);
-      for (int t = 0; t < 9; ++t)
-        for (int ch = 0; ch < 96; ++ch) wv[((size_t)t * 96 + ch) * NP + n] = L.w[((size_t)oc * d.cin + 96 + ch) * 9 + t];
-    }
-    if (L.d_u1) (void)hipFree(L.d_u1);
-    if (L.d_wv) (void)hipFree(L.d_wv);
-    if (L.d_wv16) (void)hipFree(L.d_wv16);
-    HIPCHK(c, hipMalloc(&L.d_u1, img1.size() * 4));
-    HIPCHK(c, hipMalloc(&L.d_wv, wv.size() * 4));
-    HIPCHK(c, hipMalloc(&L.d_wv16, wv.size() * 4));
-    HIPCHK(c, hipMemcpy(L.d_u1, img1.data(), img1.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(L.d_wv, wv.data(), wv.size() * 4, hipMemcpyHostToDevice));
-    for (auto& v : wv) v = bf16_round(v);
-    HIPCHK(c, hipMemcpy(L.d_wv16, wv.data(), wv.size() * 4, hipMemcpyHostToDevice));
-  }
-  return pack_wino24(c, L);
-}
-
-// 24 -> 24 layers (se_rtilew.hip): U[nu][ky] = G g[ky][.] with the F(2,3) G along x; k = ky * 24 + channel in three 32-k
-// chunks per position (72 k, the third chunk half empty), 24 PHYSICAL rows -- tile 0 = features 0-7, gates 0-7; then
-// features 8-11, gates 8-11 (the padding rows of the second MIXED tile read these again) --, slot swizzle by physical row.
-int pack_rtilew(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  static const float Gm[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-  const int G = d.cout / 2;      // 12
-  std::vector<float> img((size_t)4 * 3 * 24 * 32, 0.f);
-  for (int prow = 0; prow < 24; ++prow) {
-    const int oc = prow < 8 ? prow : prow < 16 ? G + (prow - 8) : prow < 20 ? 8 + (prow - 16) : G + 8 + (prow - 20);
-    for (int ic = 0; ic < 24; ++ic)
-      for (int ky = 0; ky < 3; ++ky) {
-        const float* g = &L.w[(((size_t)oc * d.cin + ic) * 3 + ky) * 3];
-        for (int nu = 0; nu < 4; ++nu) {
-          const float u = Gm[nu][0] * g[0] + Gm[nu][1] * g[1] + Gm[nu][2] * g[2];
-          const int k = ky * 24 + ic, ch = k / 32, kin = k % 32, s_ = kin / 4, e = kin % 4;
-          const int ps = s_ ^ ((prow >> 1) & 7);
-          img[(((size_t)nu * 3 + ch) * 24 + prow) * 32 + ps * 4 + e] = u;
-        }
-      }
-  }
-  if (L.d_wx) (void)hipFree(L.d_wx);
-  HIPCHK(c, hipMalloc(&L.d_wx, img.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_wx, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  // two-dimensional form: U = G g G^T per position; a row holds its 24 k as channels 0-15 in slots 0-3 and channels
-  // 16 + 2q, 17 + 2q in slot 4 + q, elements 0, 1 for even q and 2, 3 for odd q (k-half 1 issues two k-steps; the halves keep
-  // the 8-byte fragment reads of lane groups q, q ^ 1 off each other's banks, se_rtilew.hip)
-  std::vector<float> img2((size_t)16 * 24 * 32, 0.f);
-  for (int prow = 0; prow < 24; ++prow) {
-    const int oc = prow < 8 ? prow : prow < 16 ? G + (prow - 8) : prow < 20 ? 8 + (prow - 16) : G + 8 + (prow - 20);
-    for (int ic = 0; ic < 24; ++ic) {
-      const float* g = &L.w[((size_t)oc * d.cin + ic) * 9];
-      float t[4][3];
-      for (int i = 0; i < 4; ++i)
-        for (int kx = 0; kx < 3; ++kx) t[i][kx] = Gm[i][0] * g[kx] + Gm[i][1] * g[3 + kx] + Gm[i][2] * g[6 + kx];
-      for (int pos = 0; pos < 16; ++pos) {
-        const int xi = pos >> 2, nu = pos & 3;
-        const float u = t[xi][0] * Gm[nu][0] + t[xi][1] * Gm[nu][1] + t[xi][2] * Gm[nu][2];
-        const int s_ = ic < 16 ? ic / 4 : 4 + (ic - 16) / 2, e = ic < 16 ? ic % 4 : (ic - 16) % 2 + 2 * (((ic - 16) / 2) & 1);
-        const int ps = s_ ^ ((prow >> 1) & 7);
-        img2[((size_t)pos * 24 + prow) * 32 + ps * 4 + e] = u;
-      }
-    }
-  }
-  if (L.d_wx2) (void)hipFree(L.d_wx2);
-  HIPCHK(c, hipMalloc(&L.d_wx2, img2.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_wx2, img2.data(), img2.size() * 4, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// Hybrid F(2,3) x F(4,3) image of the same layers (se_wino24.hip): U = Gy g Gx^T (4 x 6 positions) of the FIRST 96 input
-// channels, 72 iterations in the kernel's order -- stage (xi, h) -> chunk -> j with column position nu = {0,1,2}[j] (h = 0)
-// or {5,3,4}[j] (h = 1) --, 192 rows in the MIXED order (tile t = features 8t..8t+7, then their gates), slot swizzle as
-// everywhere.  U is formed in double and rounded once (Gx holds 1/6, 1/12, 1/24).
-int pack_wino24(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  static const double Gy[4][3] = {{1., 0., 0.}, {.5, .5, .5}, {.5, -.5, .5}, {0., 0., 1.}};
-  static const double Gx[6][3] = {{1. / 4, 0., 0.}, {-1. / 6, -1. / 6, -1. / 6}, {-1. / 6, 1. / 6, -1. / 6},
-                                  {1. / 24, 1. / 12, 1. / 6}, {1. / 24, -1. / 12, 1. / 6}, {0., 0., 1.}};
-  static const int NU[2][3] = {{0, 1, 2}, {5, 3, 4}};
-  const int NP = 192;
-  // two images for the two-source layers: the first source alone (vector source folded into a bias: conv11) and both
-  // sources (allconv11: 6 chunks per position)
-  // (a 48-channel layer -- xconv5 -- has one image of 2 chunks per position, the second half empty)
-  const int nchk_first = d.cin == 48 ? 2 : 3, nchk_last = d.cin == 48 ? 2 : d.cin / 32;
-  for (int nchk = nchk_first; nchk <= nchk_last; nchk += 3) {
-  std::vector<float> img((size_t)24 * nchk * NP * 32, 0.f), bias(NP, 0.f);
-  for (int n = 0; n < NP; ++n) {
-    const int t = n / 16, r = n % 16;
-    const int oc = r < 8 ? t * 8 + r : 96 + t * 8 + (r - 8);
-    bias[n] = L.b[oc];
-    for (int ic = 0; ic < nchk * 32 && ic < d.cin; ++ic) {
-      const float* g = &L.w[((size_t)oc * d.cin + ic) * 9];
-      double tt[4][3];
-      for (int i = 0; i < 4; ++i)
-        for (int kx = 0; kx < 3; ++kx) tt[i][kx] = Gy[i][0] * g[kx] + Gy[i][1] * g[3 + kx] + Gy[i][2] * g[6 + kx];
-      for (int xi = 0; xi < 4; ++xi)
-        for (int h = 0; h < 2; ++h)
-          for (int j = 0; j < 3; ++j) {
-            const int nu = NU[h][j];
-            const double u = tt[xi][0] * Gx[nu][0] + tt[xi][1] * Gx[nu][1] + tt[xi][2] * Gx[nu][2];
-            const int chunk = ic / 32, kin = ic % 32, s_ = kin / 4, e = kin % 4;
-            const int it = ((xi * 2 + h) * nchk + chunk) * 3 + j;
-            const int ps = s_ ^ ((n >> 1) & 7);
-            img[((size_t)it * NP + n) * 32 + ps * 4 + e] = (float)u;
-          }
-    }
-  }
-  float*& du = nchk <= 3 ? L.d_u24 : L.d_u24b;
-  if (du) (void)hipFree(du);
-  HIPCHK(c, hipMalloc(&du, img.size() * 4));
-  HIPCHK(c, hipMemcpy(du, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  if (nchk <= 3) {
-    if (L.d_ub24) (void)hipFree(L.d_ub24);
-    HIPCHK(c, hipMalloc(&L.d_ub24, bias.size() * 4));
-    HIPCHK(c, hipMemcpy(L.d_ub24, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-  }
-  }
-  return 0;
-}
-
-// 48 -> 96 layers (se_wino48.hip): 24 iterations = 8 position pairs x 3 chunks; chunk c of pair pp holds in its
-// k-half h the 16-channel group ((2c+h) % 3) of position 2pp + ((2c+h) >= 3).  Rows in the MIXED order: tile t =
-// features 8t..8t+7, then their gates.
-bool wino48_eligible_layer(const LayerDef& d) {
-  return d.k == 3 && d.stride == 1 && !d.up && d.cin == 48 && d.cout == 96 && d.act != ACT_NONE;
-}
-int pack_wino48(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  static const float Gm[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-  const int NP = 96;
-  std::vector<float> img((size_t)24 * NP * 32, 0.f), bias(NP, 0.f);
-  for (int n = 0; n < NP; ++n) {
-    const int t = n / 16, r = n % 16;
-    const int oc = r < 8 ? t * 8 + r : 48 + t * 8 + (r - 8);
-    bias[n] = L.b[oc];
-    for (int ic = 0; ic < 48; ++ic) {
-      const float* g = &L.w[((size_t)oc * d.cin + ic) * 9];
-      float tt[4][3];
-      for (int i = 0; i < 4; ++i)
-        for (int kx = 0; kx < 3; ++kx) tt[i][kx] = Gm[i][0] * g[kx] + Gm[i][1] * g[3 + kx] + Gm[i][2] * g[6 + kx];
-      for (int pos = 0; pos < 16; ++pos) {
-        const int xi = pos >> 2, nu = pos & 3;
-        const float u = tt[xi][0] * Gm[nu][0] + tt[xi][1] * Gm[nu][1] + tt[xi][2] * Gm[nu][2];
-        const int pp = pos >> 1, u6 = (pos & 1) * 3 + ic / 16;        // index of the 16-channel group in the pair
-        const int it = pp * 3 + u6 / 2, kin = (u6 % 2) * 16 + ic % 16;
-        const int s_ = kin / 4, e = kin % 4;
-        const int ps = s_ ^ ((n >> 1) & 7);
-        img[((size_t)it * NP + n) * 32 + ps * 4 + e] = u;
-      }
-    }
-  }
-  if (L.d_u) (void)hipFree(L.d_u);
-  if (L.d_ub) (void)hipFree(L.d_ub);
-  HIPCHK(c, hipMalloc(&L.d_u, img.size() * 4));
-  HIPCHK(c, hipMalloc(&L.d_ub, bias.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_u, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(L.d_ub, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// 24 -> 96 layers on the same kernel (se_wino48.hip, CIN = 24): one iteration per position, U[pos] as a [96 MIXED rows][32 k]
-// tile: channels 0-15 in slots 0-3, channels 16 + 2q, 17 + 2q in elements 0, 1 of slot 4 + q (k-half 1 issues two k-steps:
-// a k-step takes one element of every slot), elements 2, 3 zero.
-int pack_wino48_c24(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  static const float Gm[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-  const int NP = 96;
-  std::vector<float> img((size_t)16 * NP * 32, 0.f), bias(NP, 0.f);
-  for (int n = 0; n < NP; ++n) {
-    const int t = n / 16, r = n % 16;
-    const int oc = r < 8 ? t * 8 + r : 48 + t * 8 + (r - 8);
-    bias[n] = L.b[oc];
-    for (int ic = 0; ic < 24; ++ic) {
-      const float* g = &L.w[((size_t)oc * d.cin + ic) * 9];
-      float tt[4][3];
-      for (int i = 0; i < 4; ++i)
-        for (int kx = 0; kx < 3; ++kx) tt[i][kx] = Gm[i][0] * g[kx] + Gm[i][1] * g[3 + kx] + Gm[i][2] * g[6 + kx];
-      for (int pos = 0; pos < 16; ++pos) {
-        const int xi = pos >> 2, nu = pos & 3;
-        const float u = tt[xi][0] * Gm[nu][0] + tt[xi][1] * Gm[nu][1] + tt[xi][2] * Gm[nu][2];
-        const int s_ = ic < 16 ? ic / 4 : 4 + (ic - 16) / 2, e = ic < 16 ? ic % 4 : (ic - 16) % 2, ps = s_ ^ ((n >> 1) & 7);
-        img[((size_t)pos * NP + n) * 32 + ps * 4 + e] = u;
-      }
-    }
-  }
-  if (L.d_u) (void)hipFree(L.d_u);
-  if (L.d_ub) (void)hipFree(L.d_ub);
-  HIPCHK(c, hipMalloc(&L.d_u, img.size() * 4));
-  HIPCHK(c, hipMalloc(&L.d_ub, bias.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_u, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(L.d_ub, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// gen_deconv 96 -> 96 (se_wino_up.hip): per output parity class the pre-summed 2x2 weights g (pack_layer) are
-// transformed with G = [1 0; 1 1; 0 1]: U = G g G^T (3x3 positions), 27 iterations = 9 positions x 3 chunks of 32
-// channels, rows in the MIXED order.
-bool winoup_eligible_layer(const LayerDef& d) {
-  return d.k == 3 && d.stride == 1 && d.up && d.cin == 96 && d.cout == 96 && d.act != ACT_NONE;
-}
-int pack_winoup(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  static const float Gm[3][2] = {{1.f, 0.f}, {1.f, 1.f}, {0.f, 1.f}};
-  const int NP = 96;
-  std::vector<float> img((size_t)4 * 27 * NP * 32, 0.f), bias(NP, 0.f);
-  auto lo = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2); };
-  auto hi = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2); };
-  for (int cls = 0; cls < 4; ++cls) {
-    const int py = cls >> 1, px = cls & 1;
-    for (int n = 0; n < NP; ++n) {
-      const int t = n / 16, r = n % 16;
-      const int oc = r < 8 ? t * 8 + r : 48 + t * 8 + (r - 8);
-      bias[n] = L.b[oc];
-      for (int ic = 0; ic < 96; ++ic) {
-        float g[2][2];
-        for (int a = 0; a < 2; ++a)
-          for (int b = 0; b < 2; ++b) {
-            float v = 0.f;
-            for (int ky = lo(py, a); ky <= hi(py, a); ++ky)
-              for (int kx = lo(px, b); kx <= hi(px, b); ++kx) v += L.w[(((size_t)oc * d.cin + ic) * 3 + ky) * 3 + kx];
-            g[a][b] = v;
-          }
-        for (int xi = 0; xi < 3; ++xi)
-          for (int nu = 0; nu < 3; ++nu) {
-            float u = 0.f;
-            for (int a = 0; a < 2; ++a)
-              for (int b = 0; b < 2; ++b) u += Gm[xi][a] * Gm[nu][b] * g[a][b];
-            const int it = (xi * 3 + nu) * 3 + ic / 32, kin = ic % 32;
-            const int s_ = kin / 4, e = kin % 4;
-            const int ps = s_ ^ ((n >> 1) & 7);
-            img[(((size_t)cls * 27 + it) * NP + n) * 32 + ps * 4 + e] = u;
-          }
-      }
-    }
-  }
-  if (L.d_u) (void)hipFree(L.d_u);
-  if (L.d_ub) (void)hipFree(L.d_ub);
-  HIPCHK(c, hipMalloc(&L.d_u, img.size() * 4));
-  HIPCHK(c, hipMalloc(&L.d_ub, bias.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_u, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(L.d_ub, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// gen_deconv 48 -> 48 (se_wino_up48.hip): U = G g G^T per class as above; 14 iterations in the pairing of pack_wino48
-// (chunk c of pair pp holds in k-half h the 16-channel group ((2c+h) % 3) of position 2pp + ((2c+h) >= 3)); position 8
-// has no partner: the second k-half of iteration 13 stays zero.  48 rows in the MIXED order (8 features + their gates).
-bool winoup48_eligible_layer(const LayerDef& d) {
-  return d.k == 3 && d.stride == 1 && d.up && d.cin == 48 && d.cout == 48 && d.act != ACT_NONE;
-}
-int pack_winoup48(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  static const float Gm[3][2] = {{1.f, 0.f}, {1.f, 1.f}, {0.f, 1.f}};
-  const int NP = 48, NIT = 14;
-  std::vector<float> img((size_t)4 * NIT * NP * 32, 0.f), bias(NP, 0.f);
-  auto lo = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2); };
-  auto hi = [](int par, int a) { return par == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2); };
-  for (int cls = 0; cls < 4; ++cls) {
-    const int py = cls >> 1, px = cls & 1;
-    for (int n = 0; n < NP; ++n) {
-      const int t = n / 16, r = n % 16;
-      const int oc = r < 8 ? t * 8 + r : 24 + t * 8 + (r - 8);
-      bias[n] = L.b[oc];
-      for (int ic = 0; ic < 48; ++ic) {
-        float g[2][2];
-        for (int a = 0; a < 2; ++a)
-          for (int b = 0; b < 2; ++b) {
-            float v = 0.f;
-            for (int ky = lo(py, a); ky <= hi(py, a); ++ky)
-              for (int kx = lo(px, b); kx <= hi(px, b); ++kx) v += L.w[(((size_t)oc * d.cin + ic) * 3 + ky) * 3 + kx];
-            g[a][b] = v;
-          }
-        for (int pos = 0; pos < 9; ++pos) {
-          const int xi = pos / 3, nu = pos % 3;
-          float u = 0.f;
-          for (int a = 0; a < 2; ++a)
-            for (int b = 0; b < 2; ++b) u += Gm[xi][a] * Gm[nu][b] * g[a][b];
-          const int pp = pos >> 1, u6 = (pos & 1) * 3 + ic / 16;        // index of the 16-channel group in the pair
-          const int it = pp * 3 + u6 / 2, kin = (u6 % 2) * 16 + ic % 16;
-          const int s_ = kin / 4, e = kin % 4;
-          const int ps = s_ ^ ((n >> 1) & 7);
-          img[(((size_t)cls * NIT + it) * NP + n) * 32 + ps * 4 + e] = u;
-        }
-      }
-    }
-  }
-  if (L.d_u) (void)hipFree(L.d_u);
-  if (L.d_ub) (void)hipFree(L.d_ub);
-  HIPCHK(c, hipMalloc(&L.d_u, img.size() * 4));
-  HIPCHK(c, hipMalloc(&L.d_ub, bias.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_u, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(L.d_ub, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-  return 0;
-}
-
-int pack_small(se_ctx* c, Layer& L) {
-  // raw 3x3 conv 12 -> cout: [cout][9][12]
-  const LayerDef& d = L.def;
-  std::vector<float> img((size_t)d.cout * 9 * 12);
-  for (int oc = 0; oc < d.cout; ++oc)
-    for (int t = 0; t < 9; ++t)
-      for (int ic = 0; ic < 12; ++ic) img[((size_t)oc * 9 + t) * 12 + ic] = L.w[(((size_t)oc * 12 + ic) * 3 + t / 3) * 3 + t % 3];
-  if (L.d_w) (void)hipFree(L.d_w);
-  if (L.d_b) (void)hipFree(L.d_b);
-  HIPCHK(c, hipMalloc(&L.d_w, img.size() * 4));
-  HIPCHK(c, hipMalloc(&L.d_b, d.cout * 4));
-  HIPCHK(c, hipMemcpy(L.d_w, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(L.d_b, L.b.data(), d.cout * 4, hipMemcpyHostToDevice));
-  // bf16 mode: the same fp32 kernel with bf16-rounded weights (every conv weight is rounded in that mode)
-  for (auto& v : img) v = bf16_round(v);
-  if (L.d_w16) (void)hipFree(L.d_w16);
-  HIPCHK(c, hipMalloc(&L.d_w16, img.size() * 4));
-  HIPCHK(c, hipMemcpy(L.d_w16, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  L.packed = true;
-  return 0;
-}
-
-std::vector<int> identity_map(int cin) {
-  const int Cp = (cin + 3) & ~3;
-  std::vector<int> m(Cp, -1);
-  for (int i = 0; i < cin; ++i) m[i] = i;
-  return m;
-}
-
-std::vector<int> identity_map8(int cin) {      // bf16: channels of a tap padded to whole 8-channel granules
-  const int Cp = (cin + 7) & ~7;
-  std::vector<int> m(Cp, -1);
-  for (int i = 0; i < cin; ++i) m[i] = i;
-  return m;
-}
-
-int pack_net_layer(se_ctx* c, Layer& L) {
-  const LayerDef& d = L.def;
-  if (d.act == ACT_NONE) return pack_small(c, L);
-  {
-    // bf16 images: conv16's 12 gated outputs are stored with a 16-channel stride, so conv17 is not a gated layer and
-    // everything else reads whole granules
-    if (std::string(d.name) == "wconv1" && d.cin == 5) {
-      Layer& J = c->wconv1_j4;
-      J.def = d; J.w = L.w; J.b = L.b; J.have_w = J.have_b = true;
-      const int rc = pack_layer16(c, J, std::vector<int>{0, 1, 2, 4, -1, -1, -1, -1});
-      if (rc) return rc;
-      if (pack_layer16_d4(c, J, {0, 1, 2, 4})) return 1;
-    }
-    // 5x5 first layers with at most four real input channels: the pair-of-taps image beside the 8-channel-granule one
-    if (d.k == 5 && d.stride == 1 && d.rate == 1 && d.cout == 48 && d.cin >= 3 && d.cin <= 4) {
-      const int m4[4] = {0, 1, 2, d.cin == 4 ? 3 : -1};
-      if (pack_layer16_d4(c, L, m4)) return 1;
-    }
-    const int rc = pack_layer16(c, L, identity_map8(d.cin));
-    if (rc) return rc;
-    // (cin == 192: the image of the FIRST source's 96 channels, for the folded-vector form of conv11)
-    if (d.k == 3 && d.stride == 1 && !d.up && (d.cin == 96 || d.cin == 192) && d.cout == 192 && pack_rconv16(c, L)) return 1;
-    if (rconv96_eligible(d) && pack_rconv96(c, L)) return 1;
-  }
-  // 5x5 first layers whose stored input has padding channels (5 of 8, 3 of 4): dense-K image beside the padded one
-  if (d.k == 5 && d.stride == 1 && d.rate == 1 && d.cout == 48 && d.cin >= 3 && d.cin <= 5) {
-    std::vector<int> id(d.cin);
-    for (int i = 0; i < d.cin; ++i) id[i] = i;
-    if (pack_layer_dense(c, L, id)) return 1;
-  }
-  std::vector<int> m;
-  if (d.k == 5 && d.cin == 5) { m.assign(8, -1); for (int i = 0; i < 5; ++i) m[i] = i; }   // NHWC8 inputs
-  else m = identity_map(d.cin);
-  if (std::string(d.name) == "wconv1" && d.cin == 5) {
-    // editline_g.py:132-133: with joint_train_inp the style branch sees guide * 0, so its first layer is a 4-channel
-    // conv (image*mask, mask) with the guide column of the weights dropped: K = 100 instead of 200 (NHWC8 padding)
-    Layer& J = c->wconv1_j4;
-    J.def = d; J.w = L.w; J.b = L.b; J.have_w = J.have_b = true;
-    const int rc = pack_layer(c, J, std::vector<int>{0, 1, 2, 4});
-    if (rc) return rc;
-    if (pack_layer_dense(c, J, std::vector<int>{0, 1, 2, 4})) return 1;
-  }
-  return pack_layer(c, L, m);
 }
 
 // ---- narrow layers in raw-tile form (se_rtile.hip): returns 0 and sets *done when the layer was launched there ------
@@ -975,8 +209,9 @@ int try_rtile(se_ctx* c, const Layer& L, bool bf, const float* src0, int C0, con
     if (c->low_latency && tiles < opt(OPT_RTILE_LL_MIN)) return 0;
   }
   const int es = bf ? 2 : 4, gran = bf ? 8 : 4;
-  const int CG = bf ? L.CGp16 : L.CGp, nch = bf ? L.nch16 : L.nch;
-  const float* wimg = bf ? L.d_w16 : L.d_w;
+  const DirectImage& di = L.direct[bf];
+  const int CG = di.CG, nch = di.nch;
+  const float* wimg = di.w;
   if (!wimg || C0 != CG * gran) return 0;
   // 24 -> 24 3x3: F(2,3) along x on the raw tile (se_rtilew.hip): 160 instead of 224 MFMAs per wave.  SE_RTILE_WX=0: the direct form
   {
@@ -1092,6 +327,49 @@ int try_rtile(se_ctx* c, const Layer& L, bool bf, const float* src0, int C0, con
   return 0;
 }
 
+// ---- the direct gather-GEMM (se_gconv.hip) on the image of one precision: the fallback of every gated conv ----------
+int run_gather(se_ctx* c, const Layer& L, bool bf, const float* src0, int C0, const float* src1, int C1, int src1_vec, float* dst,
+               int B, int Hin, int Win, int Ho, int Wo, int pad) {
+  const LayerDef& d = L.def;
+  const DirectImage& di = L.direct[bf];
+  const int es = bf ? 2 : 4, gran = bf ? 8 : 4;
+  GConvParams p;
+  memset(&p, 0, sizeof p);
+  p.bf16 = bf ? 1 : 0;
+  p.src0 = src0; p.src1 = src1 ? src1 : src0; p.wpk = di.w; p.bias = L.d_b; p.dst = dst; p.zeros = c->zeros;
+  p.B = B; p.Hin = Hin; p.Win = Win; p.Ho = d.up ? Hin : Ho; p.Wo = d.up ? Win : Wo;   // up2: rows walk the source grid
+  p.up2 = d.up ? 1 : 0; p.OH = Ho; p.OW = Wo;
+  p.C0 = C0; p.C1 = C1 ? C1 : C0; p.C0g = C0 / gran; p.CG = di.CG;
+  const int KW = d.up ? 2 : d.k;
+  p.T = L.T; p.KW = KW; p.stride = d.stride; p.dil = d.rate; p.pad = pad;
+  p.magicCG = (65536 + di.CG - 1) / di.CG; p.magicKW = 256 / KW + 1; p.magicKH = L.T / KW;
+  for (int gi = 0; gi < di.nch * 8 + 8; ++gi)
+    if (((gi * p.magicCG) >> 16) != gi / di.CG) return fail(c, "layer %s: magic division check failed", d.name);
+  for (int t = 0; t <= L.T + 8; ++t)
+    if (((t * p.magicKW) >> 8) != t / KW) return fail(c, "layer %s: magic tap division check failed", d.name);
+  const int Gs = bf ? (L.G + 7) & ~7 : L.G;      // stored channel stride of the output
+  // 32-bit byte offsets (sentinel 0x80000000): source and destination below 2^31 BYTES
+  if ((double)B * Hin * Win * (C0 > C1 ? C0 : C1) * es >= 2147483648.0 || (double)B * Ho * Wo * Gs * es >= 2147483648.0)
+    return fail(c, "layer %s: a tensor of this launch exceeds 2^31 bytes (32-bit byte offsets) -- split the batch", d.name);
+  for (int j = 0; j < p.magicKH; ++j) p.rep |= 1u << (j * KW);
+  udiv_magic_host((unsigned)(p.Ho * p.Wo), &p.div_hw_m, &p.div_hw_l);
+  udiv_magic_host((unsigned)p.Wo, &p.div_w_m, &p.div_w_l);
+  p.Hlim = Hin; p.Wlim = Win;
+  p.src1_vec = src1_vec; p.nch = di.nch; p.G = Gs; p.act = d.act; p.total_pix = B * p.Ho * p.Wo;
+  p.xcd = xcd_remap_enabled();
+  p.np_full = L.NP; p.nf_full = L.NP / 32; p.small_grid = c->low_latency ? 1 : 0;
+  // algorithmic cost as the reference defines the layer (3x3 on the upsampled grid for gen_deconv)
+  {
+    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * d.k * d.k;
+    // executed: the packed K (channels padded to granules, taps x channels padded to whole chunks) and row (NP) sizes the
+    // MFMAs really run over; the sub-pixel form of gen_deconv runs 4 classes x 4 taps instead of 9 taps on the upsampled grid
+    const double exec = 2.0 * (double)B * p.Ho * p.Wo * (d.up ? 4.0 : 1.0) * L.NP * (di.nch * (bf ? 64.0 : 32.0));
+    set_launch_cost(alg, (double)es * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name, exec);
+  }
+  HIPCHK(c, launch_gconv(L.cfg, p, c->st));
+  return 0;
+}
+
 // ---- bf16 mode: every gated conv is the direct gather-GEMM on v_mfma_f32_16x16x32_bf16 (se_gconv.hip, BF16) -----------
 // (The Winograd transforms would have to run in fp32 on bf16 data and round the transformed tiles again; at 16x the
 // MFMA rate the layers are bound by the LDS fill, not by multiply-adds, so there is nothing for them to buy.)
@@ -1104,8 +382,8 @@ static bool rconv16_dual_ok(const Layer& L, const LayerDef& d, int Hin, int Win)
 int run_gconv16(se_ctx* c, const Layer& L, const float* src0, int C0, const float* src1, int C1, int src1_vec, float* dst,
                 int B, int Hin, int Win, int Ho, int Wo, int pad) {
   const LayerDef& d = L.def;
-  if (!L.d_w16) return fail(c, "layer %s: no bf16 weight image", d.name);
-  if ((C0 + C1) != L.CGp16 * 8) return fail(c, "layer %s: bf16 source channels %d+%d != packed %d", d.name, C0, C1, L.CGp16 * 8);
+  if (!L.direct[1].w) return fail(c, "layer %s: no bf16 weight image", d.name);
+  if ((C0 + C1) != L.direct[1].CG * 8) return fail(c, "layer %s: bf16 source channels %d+%d != packed %d", d.name, C0, C1, L.direct[1].CG * 8);
   // the dominant shape (96 -> 192, 3x3, stride 1) runs in the raw-tile form when its polyphase sub-images are large
   // enough to fill 8 x 16 tiles reasonably (se_rconv16.hip); SE_RCONV16=0 keeps it on the gather-GEMM
   const bool use_rconv = opt(OPT_RCONV16) != 0;
@@ -1129,7 +407,7 @@ int run_gconv16(se_ctx* c, const Layer& L, const float* src0, int C0, const floa
     }
   }
   if (use_rconv && !c->low_latency && d.k == 3 && d.stride == 1 && !d.up && d.cin == 96 && d.cout == 192 && !src1 && C0 == 96 &&
-      (Hin % d.rate) == 0 && (Win % d.rate) == 0 && L.nch16 == 14 && L.d_w16s && (long long)B * Hin * Win * 192 < (1ll << 31) &&
+      (Hin % d.rate) == 0 && (Win % d.rate) == 0 && L.direct[1].nch == 14 && L.d_w16s && (long long)B * Hin * Win * 192 < (1ll << 31) &&
       ((Hin / d.rate >= 12 && Win / d.rate >= 12) || rconv16_dual_ok(L, d, Hin, Win))) {
     RConvParams rp;
     memset(&rp, 0, sizeof rp);
@@ -1167,38 +445,7 @@ int run_gconv16(se_ctx* c, const Layer& L, const float* src0, int C0, const floa
     if (try_rtile(c, L, true, src0, C0, src1, dst, B, Hin, Win, Ho, Wo, pad, &done)) return 1;
     if (done) return 0;
   }
-  GConvParams p;
-  memset(&p, 0, sizeof p);
-  p.bf16 = 1;
-  p.src0 = src0; p.src1 = src1 ? src1 : src0; p.wpk = L.d_w16; p.bias = L.d_b; p.dst = dst; p.zeros = c->zeros;
-  p.B = B; p.Hin = Hin; p.Win = Win; p.Ho = d.up ? Hin : Ho; p.Wo = d.up ? Win : Wo;
-  p.up2 = d.up ? 1 : 0; p.OH = Ho; p.OW = Wo;
-  p.C0 = C0; p.C1 = C1 ? C1 : C0; p.C0g = C0 / 8; p.CG = L.CGp16;
-  const int KW = d.up ? 2 : d.k;
-  p.T = L.T; p.KW = KW; p.stride = d.stride; p.dil = d.rate; p.pad = pad;
-  p.magicCG = (65536 + L.CGp16 - 1) / L.CGp16; p.magicKW = 256 / KW + 1; p.magicKH = L.T / KW;
-  for (int gi = 0; gi < L.nch16 * 8 + 8; ++gi)
-    if (((gi * p.magicCG) >> 16) != gi / L.CGp16) return fail(c, "layer %s: magic division check failed", d.name);
-  for (int t = 0; t <= L.T + 8; ++t)
-    if (((t * p.magicKW) >> 8) != t / KW) return fail(c, "layer %s: magic tap division check failed", d.name);
-  const int Gs = (L.G + 7) & ~7;                 // stored channel stride of the output
-  // 32-bit byte offsets (sentinel 0x80000000): source and destination below 2^31 BYTES
-  if ((double)B * Hin * Win * (C0 > C1 ? C0 : C1) * 2.0 >= 2147483648.0 || (double)B * Ho * Wo * Gs * 2.0 >= 2147483648.0)
-    return fail(c, "layer %s: a tensor of this launch exceeds 2^31 bytes (32-bit byte offsets) -- split the batch", d.name);
-  for (int j = 0; j < p.magicKH; ++j) p.rep |= 1u << (j * KW);
-  udiv_magic_host((unsigned)(p.Ho * p.Wo), &p.div_hw_m, &p.div_hw_l);
-  udiv_magic_host((unsigned)p.Wo, &p.div_w_m, &p.div_w_l);
-  p.Hlim = Hin; p.Wlim = Win;
-  p.src1_vec = src1_vec; p.nch = L.nch16; p.G = Gs; p.act = d.act; p.total_pix = B * p.Ho * p.Wo;
-  p.xcd = xcd_remap_enabled();
-  p.np_full = L.NP; p.nf_full = L.NP / 32; p.small_grid = c->low_latency ? 1 : 0;
-  {
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * d.k * d.k;
-    const double exec = 2.0 * (double)B * p.Ho * p.Wo * (d.up ? 4.0 : 1.0) * L.NP * (L.nch16 * 64.0);
-    set_launch_cost(alg, 2.0 * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name, exec);
-  }
-  HIPCHK(c, launch_gconv(L.cfg, p, c->st));
-  return 0;
+  return run_gather(c, L, true, src0, C0, src1, C1, src1_vec, dst, B, Hin, Win, Ho, Wo, pad);
 }
 
 // ---- launching one gated conv -----------------------------------------------------------------------
@@ -1219,18 +466,13 @@ static WinoParams wino_params(const float* src, const float* upk, const float* b
 }
 
 int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float* src1, int C1, int src1_vec, float* dst,
-              int B, int Hin, int Win, int* Ho_, int* Wo_) {
+              int B, int Hin, int Win) {
   const LayerDef& d = L.def;
-  const int pad = d.rate * (d.k - 1) / 2;                               // utils.py:20
-  int Ho, Wo;
-  if (d.up) { Ho = 2 * Hin; Wo = 2 * Win; }
-  else { Ho = (Hin + 2 * pad - d.rate * (d.k - 1) - 1) / d.stride + 1; Wo = (Win + 2 * pad - d.rate * (d.k - 1) - 1) / d.stride + 1; }
-  if (Ho_) *Ho_ = Ho;
-  if (Wo_) *Wo_ = Wo;
-  if (c->dry) return 0;
+  const ConvShape sh = conv_shape(d, Hin, Win);
+  const int Ho = sh.Ho, Wo = sh.Wo, pad = sh.pad;
   if (!L.packed) return fail(c, "layer %s: weights not loaded", d.name);
   if (c->bf16) return run_gconv16(c, L, src0, C0, src1, C1, src1_vec, dst, B, Hin, Win, Ho, Wo, pad);
-  if ((C0 + C1) != L.CGp * 4) return fail(c, "layer %s: source channels %d+%d != packed %d", d.name, C0, C1, L.CGp * 4);
+  if ((C0 + C1) != L.direct[0].CG * 4) return fail(c, "layer %s: source channels %d+%d != packed %d", d.name, C0, C1, L.direct[0].CG * 4);
   // Low-latency mode (SE_FLAG_LOW_LATENCY, one or two images): the Winograd kernels' 64/128-tile workgroups would
   // occupy 16-32 of the 256 CUs, so every gated conv takes the direct kernel in its small-grid shape instead
   // (launch_gconv: 64-pixel tiles, rows split over blockIdx.y).  2.25x more multiply-adds on ~10x more CUs.
@@ -1346,41 +588,7 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
     if (try_rtile(c, L, false, src0, C0, src1, dst, B, Hin, Win, Ho, Wo, pad, &done)) return 1;
     if (done) return 0;
   }
-  GConvParams p;
-  memset(&p, 0, sizeof p);
-  p.src0 = src0; p.src1 = src1 ? src1 : src0; p.wpk = L.d_w; p.bias = L.d_b; p.dst = dst; p.zeros = c->zeros;
-  p.B = B; p.Hin = Hin; p.Win = Win; p.Ho = d.up ? Hin : Ho; p.Wo = d.up ? Win : Wo;   // up2: rows walk the source grid
-  p.up2 = d.up ? 1 : 0; p.OH = Ho; p.OW = Wo;
-  p.C0 = C0; p.C1 = C1 ? C1 : C0; p.C0g = C0 / 4; p.CG = L.CGp;
-  const int KW = d.up ? 2 : d.k;
-  p.T = L.T; p.KW = KW; p.stride = d.stride; p.dil = d.rate; p.pad = pad;
-  p.magicCG = (65536 + L.CGp - 1) / L.CGp; p.magicKW = 256 / KW + 1; p.magicKH = L.T / KW;
-  for (int gi = 0; gi < L.nch * 8 + 8; ++gi)
-    if (((gi * p.magicCG) >> 16) != gi / L.CGp) return fail(c, "layer %s: magic division check failed", d.name);
-  for (int t = 0; t <= L.T + 8; ++t)
-    if (((t * p.magicKW) >> 8) != t / KW) return fail(c, "layer %s: magic tap division check failed", d.name);
-  // 32-bit byte offsets (sentinel 0x80000000): source and destination below 2^31 BYTES
-  if ((double)B * Hin * Win * (C0 > C1 ? C0 : C1) * 4.0 >= 2147483648.0 || (double)B * Ho * Wo * L.G * 4.0 >= 2147483648.0)
-    return fail(c, "layer %s: a tensor of this launch exceeds 2^31 bytes (32-bit byte offsets) -- split the batch", d.name);
-  p.ushift = 0;
-  p.rep = 0;
-  for (int j = 0; j < p.magicKH; ++j) p.rep |= 1u << (j * KW);
-  udiv_magic_host((unsigned)(p.Ho * p.Wo), &p.div_hw_m, &p.div_hw_l);
-  udiv_magic_host((unsigned)p.Wo, &p.div_w_m, &p.div_w_l);
-  p.Hlim = Hin; p.Wlim = Win;
-  p.src1_vec = src1_vec; p.nch = L.nch; p.G = L.G; p.act = d.act; p.total_pix = B * p.Ho * p.Wo;
-  p.xcd = xcd_remap_enabled();
-  p.np_full = L.NP; p.nf_full = L.NP / 32; p.small_grid = c->low_latency ? 1 : 0;
-  // algorithmic cost as the reference defines the layer (3x3 on the upsampled grid for gen_deconv)
-  {
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * d.k * d.k;
-    // executed: the packed K (channels padded to granules, taps x channels padded to 32) and row (NP) sizes the MFMAs
-    // really run over; the sub-pixel form of gen_deconv runs 4 classes x 4 taps instead of 9 taps on the upsampled grid
-    const double exec = 2.0 * (double)B * p.Ho * p.Wo * (d.up ? 4.0 : 1.0) * L.NP * (L.nch * 32.0);
-    set_launch_cost(alg, 4.0 * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name, exec);
-  }
-  HIPCHK(c, launch_gconv(L.cfg, p, c->st));
-  return 0;
+  return run_gather(c, L, false, src0, C0, src1, C1, src1_vec, dst, B, Hin, Win, Ho, Wo, pad);
 }
 
 struct Act {   // an NHWC activation living in the arena
@@ -1457,14 +665,10 @@ struct Plan {
   Act conv_layer(Layer& L, Act& in, bool rel = true, const float* src1 = nullptr, int C1 = 0, int vec = 0) {
     Act out;
     if (rc) return out;
-    int Ho = 0, Wo = 0;
-    // dry pass to get shape
-    bool dry = c->dry; c->dry = true;
-    run_gconv(c, L, nullptr, 0, nullptr, 0, 0, nullptr, B, in.H, in.W, &Ho, &Wo);
-    c->dry = dry;
-    out = alloc(Ho, Wo, L.def.cout / 2);
+    const ConvShape sh = conv_shape(L.def, in.H, in.W);
+    out = alloc(sh.Ho, sh.Wo, L.def.cout / 2);
     if (rc) return out;
-    if (!c->dry) rc = run_gconv(c, L, in.p, in.C, src1, C1, vec, out.p, B, in.H, in.W, nullptr, nullptr);
+    if (!c->dry) rc = run_gconv(c, L, in.p, in.C, src1, C1, vec, out.p, B, in.H, in.W);
     if (rel) free(in);
     return out;
   }
@@ -1506,7 +710,7 @@ int small(Plan& P, const char* name, Act& in, int mode, float* out_nchw, float* 
     if (!L.packed) return P.rc = fail(c, "layer %s: weights not loaded", name);
     SmallConvParams sp;
     memset(&sp, 0, sizeof sp);
-    sp.x = in.p; sp.w = c->bf16 ? L.d_w16 : L.d_w; sp.b = L.d_b; sp.B = P.B; sp.H = in.H; sp.W = in.W; sp.cout = L.def.cout;
+    sp.x = in.p; sp.w = L.direct[c->bf16].w; sp.b = L.d_b; sp.B = P.B; sp.H = in.H; sp.W = in.W; sp.cout = L.def.cout;
     sp.bf16 = c->bf16 ? 1 : 0;
     sp.mode = mode; sp.out_nchw = out_nchw; sp.hard = hard; sp.img = img; sp.mask = mask; sp.xnow = xnow;
     sp.composed = composed; sp.no_mask_coarse = no_mask_coarse;
@@ -2007,33 +1211,7 @@ int se_create(int device_id, se_ctx** out) {
 void se_destroy(se_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  for (auto* net : {&c->G, &c->M})
-    for (auto& kv : *net) {
-      if (kv.second.d_w) (void)hipFree(kv.second.d_w);
-      if (kv.second.d_b) (void)hipFree(kv.second.d_b);
-      if (kv.second.d_u) (void)hipFree(kv.second.d_u);
-      if (kv.second.d_ub) (void)hipFree(kv.second.d_ub);
-      if (kv.second.d_w16) (void)hipFree(kv.second.d_w16);
-      if (kv.second.d_w16s) (void)hipFree(kv.second.d_w16s);
-      if (kv.second.d_w16d) (void)hipFree(kv.second.d_w16d);
-      if (kv.second.d_w96) (void)hipFree(kv.second.d_w96);
-      if (kv.second.d_wd) (void)hipFree(kv.second.d_wd);
-      if (kv.second.d_wdw) (void)hipFree(kv.second.d_wdw);
-      if (kv.second.d_u1) (void)hipFree(kv.second.d_u1);
-      if (kv.second.d_wv) (void)hipFree(kv.second.d_wv);
-      if (kv.second.d_wv16) (void)hipFree(kv.second.d_wv16);
-      if (kv.second.d_wx) (void)hipFree(kv.second.d_wx);
-      if (kv.second.d_wx2) (void)hipFree(kv.second.d_wx2);
-      if (kv.second.d_u24) (void)hipFree(kv.second.d_u24);
-      if (kv.second.d_ub24) (void)hipFree(kv.second.d_ub24);
-      if (kv.second.d_u24b) (void)hipFree(kv.second.d_u24b);
-    }
-  if (c->wconv1_j4.d_w) (void)hipFree(c->wconv1_j4.d_w);
-  if (c->wconv1_j4.d_b) (void)hipFree(c->wconv1_j4.d_b);
-  if (c->wconv1_j4.d_w16) (void)hipFree(c->wconv1_j4.d_w16);
-  if (c->wconv1_j4.d_w16d) (void)hipFree(c->wconv1_j4.d_w16d);
-  if (c->wconv1_j4.d_wd) (void)hipFree(c->wconv1_j4.d_wd);
-  if (c->wconv1_j4.d_wdw) (void)hipFree(c->wconv1_j4.d_wdw);
+  c->G.clear(); c->M.clear(); c->wconv1_j4 = Layer();       // the layers' device images
   if (c->zeros) (void)hipFree(c->zeros);
   if (c->lut8) (void)hipFree(c->lut8);
   for (auto& t : c->rs_tables) (void)hipFree(t.dev);
@@ -2083,7 +1261,17 @@ int se_load_weights(se_ctx* c, int net_id, const char* name, const float* host, 
   } else {
     return fail(c, "unexpected key %s", name);
   }
-  if (L.have_w && L.have_b) return pack_net_layer(c, L);
+  if (!L.have_w || !L.have_b) return 0;
+  std::vector<int> chans(d.cin);
+  std::iota(chans.begin(), chans.end(), 0);
+  if (pack_layer_images(L, chans, c->err)) return 1;
+  if (std::string(d.name) == "wconv1" && d.cin == 5) {
+    // editline_g.py:132-133: with joint_train_inp the style branch sees guide * 0, so its first layer is a 4-channel
+    // conv (image*mask, mask) with the guide column of the weights dropped: K = 100 instead of 200 (NHWC8 padding)
+    Layer& J = c->wconv1_j4;
+    J.def = d; J.w = L.w; J.b = L.b; J.have_w = J.have_b = true;
+    return pack_layer_images(J, {0, 1, 2, 4}, c->err);
+  }
   return 0;
 }
 
@@ -2534,91 +1722,58 @@ int se_gated_conv2d_ex(se_ctx* c, void* stream, const float* x, const float* x1,
   const bool bf = c->bf16;
   if (!x1) Cin1 = 0;
   if (x1 && ((Cin % 4) || (Cin1 % 4))) return fail(c, "two-source conv: channel counts must be multiples of 4");
-  Layer L;
-  static const char* nm = "test";
+  if (bf && x1 && ((Cin % 8) || (Cin1 % 8))) return fail(c, "two-source bf16 conv: channel counts must be multiples of 8");
   const int CinT = Cin + Cin1;
-  L.def = LayerDef{nm, CinT, Cout, k, stride, rate, act, upsample};
+  Layer L;
+  L.def = LayerDef{"test", CinT, Cout, k, stride, rate, act, upsample};
+  const bool raw = small_layer(L.def);
+  if (raw && (k != 3 || CinT != 12 || x1 || (Cout != 1 && Cout != 3) || stride != 1 || rate != 1 || upsample))
+    return fail(c, "raw conv: only 3x3 12->{1,3}");
+  if (!raw && (Cout % 8)) return fail(c, "gated conv needs Cout %% 8 == 0");
   L.w.assign(w_host, w_host + (size_t)Cout * CinT * k * k);
   L.b.assign(b_host, b_host + Cout);
-  if (bf && x1 && ((Cin % 8) || (Cin1 % 8))) return fail(c, "two-source bf16 conv: channel counts must be multiples of 8");
+  std::vector<int> chans(CinT);
+  std::iota(chans.begin(), chans.end(), 0);
+  if (pack_layer_images(L, chans, c->err)) return 1;
   const int Cp = bf ? (Cin + 7) & ~7 : (Cin + 3) & ~3;
-  float *xin = nullptr, *x1in = nullptr, *yout = nullptr, *vb_test = nullptr;
-  int rc = 0;
-  HIPCHK(c, hipMalloc(&xin, (size_t)B * H * W * Cp * 4));
-  rc = (bf ? launch_nchw_to_nhwc16 : launch_nchw_to_nhwc)(x, xin, B, Cin, Cp, H, W, c->st) != hipSuccess;
+  DevBuf xin, x1in, yout, vb_test;
+  // launches on c->st read these buffers and the layer's images: every return drains the stream before they are freed
+  struct Drain {
+    se_ctx* c;
+    ~Drain() {
+      (void)hipStreamSynchronize(c->st);
+      c->vbias_ws = nullptr; c->vec32 = nullptr;
+    }
+  } drain{c};
+  HIPCHK(c, xin.alloc((size_t)B * H * W * Cp * 4));
+  int rc = (bf ? launch_nchw_to_nhwc16 : launch_nchw_to_nhwc)(x, xin, B, Cin, Cp, H, W, c->st) != hipSuccess;
   if (!rc && x1) {
     // second source of the virtual concat (editline_g.py:166-167,211): a tensor (B,Cin1,H,W) or a per-image vector (B,Cin1)
     const size_t n1 = x1_is_vector ? (size_t)B * Cin1 : (size_t)B * H * W * Cin1;
-    HIPCHK(c, hipMalloc(&x1in, n1 * 4));
+    HIPCHK(c, x1in.alloc(n1 * 4));
     if (x1_is_vector && !bf) rc = hipMemcpyAsync(x1in, x1, n1 * 4, hipMemcpyDeviceToDevice, c->st) != hipSuccess;
     else if (x1_is_vector) rc = launch_nchw_to_nhwc16(x1, x1in, B, Cin1, Cin1, 1, 1, c->st) != hipSuccess;
     else rc = (bf ? launch_nchw_to_nhwc16 : launch_nchw_to_nhwc)(x1, x1in, B, Cin1, Cin1, H, W, c->st) != hipSuccess;
   }
-  const bool raw = (act == ACT_NONE) || Cout == 3;    // utils.py:27
   if (!rc && raw) {
-    if (k != 3 || CinT != 12 || x1 || (Cout != 1 && Cout != 3) || stride != 1 || rate != 1 || upsample) rc = fail(c, "raw conv: only 3x3 12->{1,3}");
-    if (!rc) rc = pack_small(c, L);
-    if (!rc) {
-      SmallConvParams sp;
-      memset(&sp, 0, sizeof sp);
-      sp.x = xin; sp.w = bf ? L.d_w16 : L.d_w; sp.b = L.d_b; sp.B = B; sp.H = H; sp.W = W; sp.cout = Cout; sp.mode = 4;
-      sp.bf16 = bf ? 1 : 0;
-      sp.out_nchw = y;
-      rc = launch_small_conv(sp, c->st) != hipSuccess;
-    }
+    SmallConvParams sp;
+    memset(&sp, 0, sizeof sp);
+    sp.x = xin; sp.w = L.direct[bf].w; sp.b = L.d_b; sp.B = B; sp.H = H; sp.W = W; sp.cout = Cout; sp.mode = 4;
+    sp.bf16 = bf ? 1 : 0;
+    sp.out_nchw = y;
+    rc = launch_small_conv(sp, c->st) != hipSuccess;
   } else if (!rc) {
-    if (Cout % 8) rc = fail(c, "gated conv needs Cout %% 8 == 0");
-    if (!rc) rc = pack_layer(c, L, identity_map(CinT));
-    if (!rc && !bf && k == 5 && stride == 1 && rate == 1 && Cout == 48 && !Cin1 && !upsample && Cin >= 3 && Cin <= 5) {
-      std::vector<int> id(Cin);
-      for (int i = 0; i < Cin; ++i) id[i] = i;
-      rc = pack_layer_dense(c, L, id);
+    const ConvShape sh = conv_shape(L.def, H, W);
+    const int Gs = bf ? (Cout / 2 + 7) & ~7 : Cout / 2;
+    HIPCHK(c, yout.alloc((size_t)B * sh.Ho * sh.Wo * Gs * 4));
+    if (x1in && x1_is_vector) {               // scratch of the folded vector source (the forwards take it from the workspace)
+      HIPCHK(c, vb_test.alloc((size_t)B * 9 * 192 * 4));
+      c->vbias_ws = vb_test;
+      c->vec32 = bf ? x1 : nullptr;           // bf16 mode: the caller's fp32 vector (x1in is its bf16 rounding)
     }
-    if (!rc && bf) rc = pack_layer16(c, L, identity_map8(CinT));
-    if (!rc && bf && k == 5 && stride == 1 && rate == 1 && Cout == 48 && !Cin1 && !upsample && Cin >= 3 && Cin <= 4) {
-      const int m4[4] = {0, 1, 2, Cin == 4 ? 3 : -1};
-      rc = pack_layer16_d4(c, L, m4);
-    }
-    if (!rc && bf && k == 3 && stride == 1 && !upsample && Cout == 192 && ((CinT == 96 && !Cin1) || (CinT == 192 && Cin1 == 96))) rc = pack_rconv16(c, L);
-    if (!rc && bf && !Cin1 && rconv96_eligible(L.def)) rc = pack_rconv96(c, L);
-    if (!rc) {
-      int Ho, Wo;
-      c->dry = true; run_gconv(c, L, nullptr, 0, nullptr, 0, 0, nullptr, B, H, W, &Ho, &Wo); c->dry = false;
-      const int Gs = bf ? (Cout / 2 + 7) & ~7 : Cout / 2;
-      HIPCHK(c, hipMalloc(&yout, (size_t)B * Ho * Wo * Gs * 4));
-      if (x1in && x1_is_vector) {               // scratch of the folded vector source (the forwards take it from the workspace)
-        HIPCHK(c, hipMalloc(&vb_test, (size_t)B * 9 * 192 * 4));
-        c->vbias_ws = vb_test;
-        c->vec32 = bf ? x1 : nullptr;           // bf16 mode: the caller's fp32 vector (x1in is its bf16 rounding)
-      }
-      rc = run_gconv(c, L, xin, Cp, x1in, Cin1, x1_is_vector, yout, B, H, W, nullptr, nullptr);
-      if (!rc) rc = (bf ? launch_nhwc16_to_nchw : launch_nhwc_to_nchw)(yout, y, B, Cout / 2, Gs, Ho, Wo, c->st) != hipSuccess;
-    }
+    rc = run_gconv(c, L, xin, Cp, x1in, Cin1, x1_is_vector, yout, B, H, W);
+    if (!rc) rc = (bf ? launch_nhwc16_to_nchw : launch_nhwc_to_nchw)(yout, y, B, Cout / 2, Gs, sh.Ho, sh.Wo, c->st) != hipSuccess;
   }
-  (void)hipStreamSynchronize(c->st);
-  if (xin) (void)hipFree(xin);
-  if (x1in) (void)hipFree(x1in);
-  if (yout) (void)hipFree(yout);
-  if (L.d_w) (void)hipFree(L.d_w);
-  if (L.d_b) (void)hipFree(L.d_b);
-  if (L.d_u) (void)hipFree(L.d_u);
-  if (L.d_ub) (void)hipFree(L.d_ub);
-  if (L.d_w16) (void)hipFree(L.d_w16);
-  if (L.d_w16s) (void)hipFree(L.d_w16s);
-  if (L.d_w16d) (void)hipFree(L.d_w16d);
-  if (L.d_w96) (void)hipFree(L.d_w96);
-  if (L.d_wd) (void)hipFree(L.d_wd);
-  if (L.d_wdw) (void)hipFree(L.d_wdw);
-  if (L.d_u1) (void)hipFree(L.d_u1);
-  if (L.d_wv) (void)hipFree(L.d_wv);
-  if (L.d_wv16) (void)hipFree(L.d_wv16);
-  if (L.d_wx) (void)hipFree(L.d_wx);
-  if (L.d_wx2) (void)hipFree(L.d_wx2);
-  if (L.d_u24) (void)hipFree(L.d_u24);
-  if (L.d_ub24) (void)hipFree(L.d_ub24);
-  if (L.d_u24b) (void)hipFree(L.d_u24b);
-  if (vb_test) (void)hipFree(vb_test);
-  c->vbias_ws = nullptr; c->vec32 = nullptr;
   return rc;
 }
 

@@ -70,7 +70,7 @@ long long opt_epoch();                            // number of opt_set / opt_res
 // Gather-GEMM gated convolution (the hot kernel).
 //   D[n][p] = sum_k Wp[n][k] * X[p][k]   n: packed output channels, p: output pixels,
 //   k: flattened (tap, channel) in 32-float chunks.  X rows are gathered on the fly from
-//   one or two NHWC sources (im2col-free); Wp is packed on the host (se_api.hip pack_layer).
+//   one or two NHWC sources (im2col-free); Wp is packed on the host (se_pack.hip pack_layer).
 // ---------------------------------------------------------------------------------------------
 struct GConvParams {
   const float* src0;   // NHWC [B][Hin][Win][C0]  (fp32, or bf16 when `bf16` is set -- the pointer types stay float*)

@@ -3,7 +3,7 @@
 //   * gen_deconv 96 -> 96 (nearest x2 + 3x3) as its four 2x2 sub-pixel classes on the source grid.
 // The structure is that of rconv16b_kernel (se_rconv16.hip -- read that header first): the input tile of a 16 x 16 block
 // of outputs with its halo is DMA'd into LDS once, pixel-major, and every tap's B fragments are read straight from it;
-// the weights stream in 32-k steps ([class][step][6 row tiles][16 rows][32 k], pack_rconv96 in se_api.hip) through a ring
+// the weights stream in 32-k steps ([class][step][6 row tiles][16 rows][32 k], pack_rconv96 in se_pack.hip) through a ring
 // of three 6 KB slots; 4 waves, each all 96 rows x 64 pixels (4 tile rows), so the gate is a register epilogue;
 // 49 - 73 KB of LDS: two workgroups per CU.  The gather-GEMM these layers ran on staged every pixel 9 (4) times and sat
 // at 23 % MFMA-busy.
