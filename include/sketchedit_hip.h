@@ -182,6 +182,40 @@ int se_edit_u8(se_ctx* ctx, void* stream, const unsigned char* image_u8, const u
                void* workspace, size_t workspace_bytes, int B, int Hi, int Wi, int Hs, int Ws, int flags);
 size_t se_edit_u8_workspace_bytes(se_ctx* ctx, int B, int Hi, int Wi);
 
+/* ---- editing sessions: a frame that stays on the device, edited in place through a window ----------------
+ * The forward runs on an H x W window of a larger uint8 frame and the result is pasted back in place; only the window is
+ * touched, read or moved.  A window edit is DEFINED as the inference above on the contiguous crop, pasted by the rule of
+ * se_window_paste_u8 -- the network sees the window only.  B requests per call, each with its own frame; every step is one
+ * launch for the whole group (the records travel through a small table the ctx owns).  wins is a HOST array of B records.
+ * H, W multiples of 8, >= 16; every window inside its frame (0 <= y0, y0 + H <= Hi, likewise x); violations return non-zero
+ * before anything is enqueued and se_last_error names the argument. */
+typedef struct se_window {
+  unsigned char* frame_u8;        /* (Hi,Wi,3) RGB uint8, device, contiguous: read by gather, written by paste */
+  const unsigned char* sketch_u8; /* the sketch OF THE WINDOW: (H,W) uint8, device (used by gather only) */
+  int Hi, Wi, y0, x0;             /* frame size and the window's top-left corner; y0, x0 need NOT be multiples of 8 */
+} se_window;
+
+/* the window of each frame -> image_out (B,3,H,W) fp32 through the table se_dequantize_u8 uses, sketch_u8 > 0 -> sketch_out
+ * (B,1,H,W): bit-identical to se_dequantize_u8 on a contiguous crop.  Either output may be NULL; outputs 16-byte aligned. */
+int se_window_gather_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int H, int W, float* image_out, float* sketch_out);
+/* mask_u8 (B,H,W) (the forward's quantised soft mask) -> hits_out (B,4) int32, DEVICE: pixels with mask_u8 >= 128 on the
+ * window's top / bottom / left / right one-pixel edge; a side that lies on the frame's own edge reports 0.  (>= 128 on the
+ * quantised mask rather than > 0.5 on the float: the statistic is computable from what the uint8 path produces.) */
+int se_window_border_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int H, int W, const unsigned char* mask_u8,
+                        int* hits_out);
+/* frame[y0 + y, x0 + x, :] = rgb[b, y, x, :] WHERE mask_u8[b, y, x] > 0; every other byte of the frame is untouched, so pixels
+ * the edit did not select stay byte-identical, inside the window too.  rgb (B,H,W,3), mask_u8 (B,H,W), 4-byte aligned.  Two
+ * requests of one call must not name overlapping windows of one frame (or frames that overlap in memory): refused. */
+int se_window_paste_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int H, int W, const unsigned char* rgb,
+                       const unsigned char* mask_u8);
+/* gather -> the forward of se_inference_u8 (fused quantisation) -> border -> paste if commit != 0, as one call without a host
+ * synchronisation.  rgb_out (B,H,W,3), mask_u8_out (B,H,W), hits_out (B,4) int32: device, each may be NULL (the workspace then
+ * holds it).  flags as se_inference_u8; workspace: se_edit_window_u8_workspace_bytes(ctx, B, H, W).  With commit != 0 the
+ * aliasing rule of se_window_paste_u8 applies. */
+int se_edit_window_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int H, int W, unsigned char* rgb_out,
+                      unsigned char* mask_u8_out, int* hits_out, int commit, void* workspace, size_t workspace_bytes, int flags);
+size_t se_edit_window_u8_workspace_bytes(se_ctx* ctx, int B, int H, int W);
+
 /* Host only (no HIP call, no ctx): the coefficient table the resize uses for one axis.  Returns ksize, the taps per output
  * (-1: bad arguments); when bounds (2*out ints: first input index, tap count) and k (cap >= out*ksize ints, fixed point
  * with 22 fractional bits, rows zero padded to ksize) are given, fills them.  Lets a test compare the tables with Pillow's. */

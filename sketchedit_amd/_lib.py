@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -35,7 +35,8 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
            "se_workspace_bytes", "se_netM_forward", "se_netM_forward_ex", "se_netG_forward", "se_netG_forward_taps", "se_inference", "se_inference_u8", "se_gated_conv2d",
            "se_gated_conv2d_ex", "se_attention", "se_attention_ex", "se_quantize_u8", "se_dequantize_u8", "se_inference_u8io", "se_profile_enable",
            "se_profile_report", "se_debug_set_option", "se_debug_get_option", "se_debug_reset_options",
-           "se_resize_u8", "se_prepare_u8", "se_edit_u8", "se_edit_u8_workspace_bytes", "se_resample_coeffs"]
+           "se_resize_u8", "se_prepare_u8", "se_edit_u8", "se_edit_u8_workspace_bytes", "se_resample_coeffs",
+           "se_window_gather_u8", "se_window_border_u8", "se_window_paste_u8", "se_edit_window_u8", "se_edit_window_u8_workspace_bytes"]
 
 
 class SketchEditHipError(RuntimeError):
@@ -45,6 +46,13 @@ class SketchEditHipError(RuntimeError):
 class NetGTaps(ctypes.Structure):
     """se_netG_taps (include/sketchedit_hip.h): optional intermediate outputs of netG, device pointers or NULL"""
     _fields_ = [("pmconv6", ctypes.c_void_p), ("attn_out", ctypes.c_void_p), ("style_vec", ctypes.c_void_p)]
+
+
+class Window(ctypes.Structure):
+    """se_window (include/sketchedit_hip.h): one request of a window edit -- its resident frame, the window's sketch (device
+    pointers) and where the window lies in the frame"""
+    _fields_ = [("frame_u8", ctypes.c_void_p), ("sketch_u8", ctypes.c_void_p), ("Hi", ctypes.c_int), ("Wi", ctypes.c_int),
+                ("y0", ctypes.c_int), ("x0", ctypes.c_int)]
 
 
 def build_library(force=False, verbose=False, extra_flags=()):
@@ -156,6 +164,16 @@ def load_library():
         lib.se_edit_u8.restype = ci
         lib.se_edit_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
         lib.se_edit_u8_workspace_bytes.restype = sz
+        lib.se_window_gather_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, c_f, c_f]
+        lib.se_window_gather_u8.restype = ci
+        lib.se_window_border_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, vp, vp]
+        lib.se_window_border_u8.restype = ci
+        lib.se_window_paste_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, vp, vp]
+        lib.se_window_paste_u8.restype = ci
+        lib.se_edit_window_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, vp, vp, vp, ci, vp, sz, ci]
+        lib.se_edit_window_u8.restype = ci
+        lib.se_edit_window_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
+        lib.se_edit_window_u8_workspace_bytes.restype = sz
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -570,6 +588,89 @@ class Engine:
                                Wi, Hs, Ws, flags):
             self._err("se_edit_u8")
         return rgb
+
+    # ---- editing sessions: window edits of resident frames (include/sketchedit_hip.h) -----------------------
+    @staticmethod
+    def _windows(frames, origins, sketches=None):
+        """The se_window records of a group: frames[i] (Hi,Wi,3) uint8 on the device, origins[i] = (y0, x0), sketches[i] the
+        window's (H,W) uint8 sketch on the device (gather only)."""
+        n = len(frames)
+        if n < 1 or len(origins) != n or (sketches is not None and len(sketches) != n):
+            raise SketchEditHipError("window call: one frame, one origin (and one sketch) per request")
+        wins = (Window * n)()
+        for i, (f, (y0, x0)) in enumerate(zip(frames, origins)):
+            _check_dev_u8(f)
+            if f.dim() != 3 or f.shape[2] != 3:
+                raise SketchEditHipError("window call: a frame is a (Hi,Wi,3) uint8 array")
+            sk = None
+            if sketches is not None:
+                sk = sketches[i]
+                _check_dev_u8(sk)
+            wins[i] = Window(f.data_ptr(), sk.data_ptr() if sk is not None else None, f.shape[0], f.shape[1], int(y0), int(x0))
+        return wins
+
+    def window_gather_u8(self, frames, origins, sketches, H, W):
+        """se_window_gather_u8: the H x W window at origins[i] = (y0, x0) of every frame and its sketch -> the forward's inputs
+        (image (B,3,H,W), sketch (B,1,H,W)) fp32, bit-identical to dequantize_u8 of the contiguous crops.  One launch."""
+        import torch
+        wins = self._windows(frames, origins, sketches)
+        for sk in sketches:
+            if tuple(sk.shape) != (H, W):
+                raise SketchEditHipError("window_gather_u8: a sketch is the window's (H,W) uint8 plane")
+        B, dev = len(frames), frames[0].device
+        image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        sketch = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        if self.lib.se_window_gather_u8(self.h, self._stream(), wins, B, H, W, _ptr(image), _ptr(sketch)):
+            self._err("se_window_gather_u8")
+        return image, sketch
+
+    def window_border_u8(self, frames, origins, mask_u8):
+        """se_window_border_u8: mask_u8 (B,H,W) uint8 -> (B,4) int32 on the device: pixels >= 128 on the top / bottom / left /
+        right edge of each window; a side on its frame's own edge counts 0."""
+        import torch
+        _check_dev_u8(mask_u8)
+        B, H, W = mask_u8.shape
+        wins = self._windows(frames, origins)
+        if len(frames) != B:
+            raise SketchEditHipError("window_border_u8: one frame per mask")
+        hits = torch.empty((B, 4), dtype=torch.int32, device=mask_u8.device)
+        if self.lib.se_window_border_u8(self.h, self._stream(), wins, B, H, W, _ptr(mask_u8), _ptr(hits)):
+            self._err("se_window_border_u8")
+        return hits
+
+    def window_paste_u8(self, frames, origins, rgb, mask_u8):
+        """se_window_paste_u8, in place: frames[i][y0 + y, x0 + x] = rgb[i, y, x] where mask_u8[i, y, x] > 0; rgb (B,H,W,3),
+        mask_u8 (B,H,W) uint8 on the device.  Overlapping windows of one frame in one call are refused."""
+        _check_dev_u8(rgb, mask_u8)
+        B, H, W = mask_u8.shape
+        if tuple(rgb.shape) != (B, H, W, 3) or len(frames) != B:
+            raise SketchEditHipError("window_paste_u8: expected rgb (B,H,W,3), mask_u8 (B,H,W) and one frame per request")
+        wins = self._windows(frames, origins)
+        if self.lib.se_window_paste_u8(self.h, self._stream(), wins, B, H, W, _ptr(rgb), _ptr(mask_u8)):
+            self._err("se_window_paste_u8")
+
+    def edit_window_u8(self, frames, origins, sketches, H, W, flags, commit=True, low_latency=None):
+        """se_edit_window_u8: gather, the forward with fused quantisation, the border counts and (commit) the paste into the
+        frames, as ONE library call without a host synchronisation.  -> (rgb (B,H,W,3) uint8, mask_u8 (B,H,W) uint8,
+        hits (B,4) int32), on the device.  low_latency: None = by the size of the forward, (B, H, W) of the WINDOW."""
+        import torch
+        wins = self._windows(frames, origins, sketches)
+        for sk in sketches:
+            if tuple(sk.shape) != (H, W):
+                raise SketchEditHipError("edit_window_u8: a sketch is the window's (H,W) uint8 plane")
+        B, dev = len(frames), frames[0].device
+        need = self.lib.se_edit_window_u8_workspace_bytes(self.h, B, H, W)
+        if need == 0:
+            self._err("se_edit_window_u8_workspace_bytes")
+        ws = self._workspace_bytes(need)
+        rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        m8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        hits = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
+        if self.lib.se_edit_window_u8(self.h, self._stream(), wins, B, H, W, _ptr(rgb), _ptr(m8), _ptr(hits), 1 if commit else 0,
+                                      _ptr(ws), ws.numel(), flags):
+            self._err("se_edit_window_u8")
+        return rgb, m8, hits
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):
         """Inference into ONE (B,4,H,W) buffer `out`: planes 0-2 composed, plane 3 the soft mask -- the unit the

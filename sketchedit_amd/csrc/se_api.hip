@@ -163,6 +163,18 @@ struct se_ctx {
   hipStream_t rs_stream = nullptr;
   bool rs_used = false;
   hipEvent_t rs_event = nullptr;
+  // window edits (se_window.hip): the se_window records of a call reach the device through a ring -- pinned host memory and
+  // its device mirror, a call takes the next B records of both.  The ring has two halves: a half is reused only after the
+  // event recorded when it was last left, i.e. after every copy and kernel that used it (win_put).  Like the resize
+  // resources it is used in the order of one stream; a call on another stream waits for the previous one's work.
+  se_window* win_host = nullptr;
+  se_window* win_dev = nullptr;
+  size_t win_cap = 0, win_pos = 0;
+  hipEvent_t win_half_done[2] = {nullptr, nullptr};
+  bool win_half_used[2] = {false, false};
+  hipStream_t win_stream = nullptr;
+  bool win_used = false;
+  hipEvent_t win_event = nullptr;
 };
 
 namespace {
@@ -1217,6 +1229,10 @@ void se_destroy(se_ctx* c) {
   for (auto& t : c->rs_tables) (void)hipFree(t.dev);
   if (c->rs_scratch) (void)hipFree(c->rs_scratch);
   if (c->rs_event) (void)hipEventDestroy(c->rs_event);
+  if (c->win_host) (void)hipHostFree(c->win_host);
+  if (c->win_dev) (void)hipFree(c->win_dev);
+  for (hipEvent_t e : c->win_half_done) if (e) (void)hipEventDestroy(e);
+  if (c->win_event) (void)hipEventDestroy(c->win_event);
   for (auto& e : c->prof.pool) (void)hipEventDestroy(e);
   drop_graphs(c);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -1640,6 +1656,177 @@ int se_edit_u8(se_ctx* c, void* stream, const unsigned char* image_u8, const uns
   if (inference_u8_locked(c, stream, image, sketch, rgb_work, nullptr, fws, fws_bytes, B, H, W, flags, 4)) return 1;
   ResizeOut o{RESIZE_OUT_U8, rgb_out, nullptr, nullptr, 0, 0};
   return resize_locked(c, st, rgb_work, B, H, W, 3, o, Hi, Wi, SE_RESAMPLE_BICUBIC);
+}
+
+// ---- editing sessions: window edits of a resident frame (se_window.hip) ------------------------------
+namespace {
+
+// every argument check of the window calls, on the host, before anything is enqueued
+int win_check(se_ctx* c, const se_window* wins, int B, int H, int W, bool need_sketch, bool writes) {
+  if (check_dims(c, B, H, W)) return 1;
+  if (!wins) return fail(c, "null pointer argument: wins");
+  if (B > 65535 || (long long)B * H * W / 1024 >= (1ll << 31)) return fail(c, "window: B=%d %dx%d is more than one launch takes", B, H, W);
+  for (int i = 0; i < B; ++i) {
+    const se_window& w = wins[i];
+    if (!w.frame_u8) return fail(c, "wins[%d].frame_u8 is null", i);
+    if (need_sketch && !w.sketch_u8) return fail(c, "wins[%d].sketch_u8 is null", i);
+    if (w.Hi < 1 || w.Wi < 1) return fail(c, "wins[%d]: bad frame size Hi=%d Wi=%d", i, w.Hi, w.Wi);
+    if (w.y0 < 0 || (long long)w.y0 + H > w.Hi)
+      return fail(c, "wins[%d].y0=%d: rows [%d, %lld) of the window lie outside the frame (Hi=%d)", i, w.y0, w.y0, (long long)w.y0 + H, w.Hi);
+    if (w.x0 < 0 || (long long)w.x0 + W > w.Wi)
+      return fail(c, "wins[%d].x0=%d: columns [%d, %lld) of the window lie outside the frame (Wi=%d)", i, w.x0, w.x0, (long long)w.x0 + W, w.Wi);
+  }
+  if (!writes) return 0;
+  // the paste of one launch runs concurrently for all requests: their windows must not share a byte
+  for (int i = 0; i < B; ++i)
+    for (int j = i + 1; j < B; ++j) {
+      const se_window &a = wins[i], &b = wins[j];
+      const uintptr_t a0 = (uintptr_t)a.frame_u8, a1 = a0 + (size_t)a.Hi * a.Wi * 3, b0 = (uintptr_t)b.frame_u8, b1 = b0 + (size_t)b.Hi * b.Wi * 3;
+      if (a1 <= b0 || b1 <= a0) continue;                 // frames apart in memory
+      if (a0 != b0 || a.Wi != b.Wi || a.Hi != b.Hi)
+        return fail(c, "wins[%d] and wins[%d]: frames overlap in memory without being the same frame", i, j);
+      if (a.y0 < b.y0 + H && b.y0 < a.y0 + H && a.x0 < b.x0 + W && b.x0 < a.x0 + W)
+        return fail(c, "wins[%d] and wins[%d] name overlapping windows of one frame", i, j);
+    }
+  return 0;
+}
+
+// the records of one call -> the next B slots of the ctx's ring, copied to the device on `st`; returns the device address
+const se_window* win_put(se_ctx* c, hipStream_t st, const se_window* wins, int B) {
+  auto bad = [c](const char* what, hipError_t e) { fail(c, "window table: %s failed: %s", what, hipGetErrorString(e)); return (const se_window*)nullptr; };
+  hipError_t e;
+  if (c->win_used && c->win_stream != st) {
+    if (!c->win_event && (e = hipEventCreateWithFlags(&c->win_event, hipEventDisableTiming)) != hipSuccess) return bad("hipEventCreate", e);
+    if ((e = hipEventRecord(c->win_event, c->win_stream)) != hipSuccess) return bad("hipEventRecord", e);
+    if ((e = hipStreamWaitEvent(st, c->win_event, 0)) != hipSuccess) return bad("hipStreamWaitEvent", e);
+  }
+  if ((size_t)B * 2 > c->win_cap) {       // (first use, or a group larger than half the ring: a new ring)
+    if (c->win_used) (void)hipStreamSynchronize(c->win_stream);
+    if (c->win_host) (void)hipHostFree(c->win_host);
+    if (c->win_dev) (void)hipFree(c->win_dev);
+    c->win_host = nullptr; c->win_dev = nullptr; c->win_cap = 0; c->win_pos = 0;
+    c->win_half_used[0] = c->win_half_used[1] = false;
+    size_t cap = 1024;
+    while (cap < (size_t)B * 2) cap *= 2;
+    if ((e = hipHostMalloc((void**)&c->win_host, cap * sizeof(se_window), hipHostMallocDefault)) != hipSuccess) { c->win_host = nullptr; return bad("hipHostMalloc", e); }
+    if ((e = hipMalloc((void**)&c->win_dev, cap * sizeof(se_window))) != hipSuccess) { c->win_dev = nullptr; return bad("hipMalloc", e); }
+    for (hipEvent_t& ev : c->win_half_done)
+      if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bad("hipEventCreate", e);
+    c->win_cap = cap;
+  }
+  c->win_stream = st;
+  c->win_used = true;
+  // win_pos = the next free record; a half is left when the group does not fit into what remains of it
+  const size_t half = c->win_cap / 2;
+  int h = c->win_pos <= half ? 0 : 1;                // (win_pos == half: half 0 is full, the group will not fit, it is left below)
+  size_t off = c->win_pos - (size_t)h * half;
+  if (off + (size_t)B > half) {       // leave this half: everything that used it is enqueued by now
+    if ((e = hipEventRecord(c->win_half_done[h], st)) != hipSuccess) return bad("hipEventRecord", e);
+    h ^= 1;
+    off = 0;
+    c->win_pos = (size_t)h * half;
+    // entering a half used before: its last user was enqueued at least half a ring of records ago, so this returns at once
+    if (c->win_half_used[h] && (e = hipEventSynchronize(c->win_half_done[h])) != hipSuccess) return bad("hipEventSynchronize", e);
+  }
+  c->win_half_used[h] = true;
+  se_window* hst = c->win_host + c->win_pos;
+  se_window* dev = c->win_dev + c->win_pos;
+  memcpy(hst, wins, (size_t)B * sizeof(se_window));
+  if ((e = hipMemcpyAsync(dev, hst, (size_t)B * sizeof(se_window), hipMemcpyHostToDevice, st)) != hipSuccess) return bad("hipMemcpyAsync", e);
+  c->win_pos += (size_t)B;
+  return dev;
+}
+
+bool aligned_to(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }
+
+size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+}  // namespace
+
+int se_window_gather_u8(se_ctx* c, void* stream, const se_window* wins, int B, int H, int W, float* image_out, float* sketch_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (win_check(c, wins, B, H, W, sketch_out != nullptr, false)) return 1;
+  if (!aligned_to(image_out, 16) || !aligned_to(sketch_out, 16)) return fail(c, "image_out / sketch_out must be 16-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  const se_window* d = win_put(c, (hipStream_t)stream, wins, B);
+  if (!d) return 1;
+  HIPCHK(c, launch_window_gather(d, c->lut8, image_out, sketch_out, B, H, W, (hipStream_t)stream));
+  return 0;
+}
+
+int se_window_border_u8(se_ctx* c, void* stream, const se_window* wins, int B, int H, int W, const unsigned char* mask_u8,
+                        int* hits_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (win_check(c, wins, B, H, W, false, false)) return 1;
+  if (!mask_u8 || !hits_out) return fail(c, "null pointer argument: mask_u8 / hits_out");
+  if (!aligned_to(hits_out, 4)) return fail(c, "hits_out must be 4-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  const se_window* d = win_put(c, (hipStream_t)stream, wins, B);
+  if (!d) return 1;
+  HIPCHK(c, launch_window_border(d, mask_u8, hits_out, B, H, W, (hipStream_t)stream));
+  return 0;
+}
+
+int se_window_paste_u8(se_ctx* c, void* stream, const se_window* wins, int B, int H, int W, const unsigned char* rgb,
+                       const unsigned char* mask_u8) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (win_check(c, wins, B, H, W, false, true)) return 1;
+  if (!rgb || !mask_u8) return fail(c, "null pointer argument: rgb / mask_u8");
+  if (!aligned_to(rgb, 4) || !aligned_to(mask_u8, 4)) return fail(c, "rgb / mask_u8 must be 4-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  const se_window* d = win_put(c, (hipStream_t)stream, wins, B);
+  if (!d) return 1;
+  HIPCHK(c, launch_window_paste(d, rgb, mask_u8, B, H, W, (hipStream_t)stream));
+  return 0;
+}
+
+// the uint8 result, the uint8 mask and the border counts in front of the forward's part (used where the caller passes NULL)
+size_t se_edit_window_u8_workspace_bytes(se_ctx* c, int B, int H, int W) {
+  if (!c) return 0;
+  const size_t fwd = se_workspace_bytes(c, B, H, W);
+  if (!fwd) return 0;
+  return fwd + pad256((size_t)B * H * W * 3) + pad256((size_t)B * H * W) + pad256((size_t)B * 4 * sizeof(int));
+}
+
+// [uint8 result | uint8 mask | counts | the workspace of se_inference_u8io: arenas, masks, fp32 image and sketch at its end]
+int se_edit_window_u8(se_ctx* c, void* stream, const se_window* wins, int B, int H, int W, unsigned char* rgb_out,
+                      unsigned char* mask_u8_out, int* hits_out, int commit, void* ws, size_t ws_bytes, int flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (win_check(c, wins, B, H, W, true, commit != 0)) return 1;
+  if (!ws) return fail(c, "null pointer argument: workspace");
+  if (!aligned_to(ws, 256)) return fail(c, "workspace must be 256-byte aligned");
+  if (!aligned_to(rgb_out, 4) || !aligned_to(mask_u8_out, 4) || !aligned_to(hits_out, 4)) return fail(c, "rgb_out / mask_u8_out / hits_out must be 4-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
+  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  const size_t plane = pad256((size_t)B * H * W * 4), rgbw = pad256((size_t)B * H * W * 3), mw = pad256((size_t)B * H * W),
+               hw = pad256((size_t)B * 4 * sizeof(int));
+  if (ws_bytes < rgbw + mw + hw + 6 * plane) return fail(c, "workspace too small: %zu bytes", ws_bytes);
+  unsigned char* rgb = rgb_out ? rgb_out : (unsigned char*)ws;
+  unsigned char* m8 = mask_u8_out ? mask_u8_out : (unsigned char*)ws + rgbw;
+  int* hits = hits_out ? hits_out : (int*)((char*)ws + rgbw + mw);
+  char* fws = (char*)ws + rgbw + mw + hw;
+  const size_t fws_bytes = ws_bytes - (rgbw + mw + hw);
+  float* image = (float*)(fws + fws_bytes - 4 * plane);      // where se_inference_u8io keeps them
+  float* sketch = (float*)(fws + fws_bytes - plane);
+  if (!aligned_to(image, 16)) return fail(c, "workspace_bytes must be a multiple of 16");
+  const hipStream_t st = (hipStream_t)stream;
+  set_profiler(&c->prof);
+  const se_window* d = win_put(c, st, wins, B);
+  if (!d) return 1;
+  HIPCHK(c, launch_window_gather(d, c->lut8, image, sketch, B, H, W, st));
+  if (inference_u8_locked(c, stream, image, sketch, rgb, m8, fws, fws_bytes, B, H, W, flags, 4)) return 1;
+  set_profiler(&c->prof);
+  HIPCHK(c, launch_window_border(d, m8, hits, B, H, W, st));
+  if (commit) HIPCHK(c, launch_window_paste(d, rgb, m8, B, H, W, st));
+  return 0;
 }
 
 // ---- measurement support (bench.py): per-kernel HIP-event timing ---------------------------------

@@ -7,6 +7,8 @@
 
 #include <vector>
 
+struct se_window;   // include/sketchedit_hip.h
+
 namespace se {
 
 // ---------------------------------------------------------------------------------------------
@@ -15,7 +17,7 @@ namespace se {
 // ---------------------------------------------------------------------------------------------
 enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL_WINO_N192, PL_WINO_N96, PL_WINO_UP96, PL_SMALL_CONV, PL_PACK, PL_COLREDUCE,
                  PL_ATT_PREP, PL_ATT_SCORE, PL_ATT_SOFTMAX, PL_ATT_BOXSUM, PL_ATT_PV, PL_LAYOUT,
-                 PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_COUNT };
+                 PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_WINDOW_GATHER, PL_WINDOW_BORDER, PL_WINDOW_PASTE, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -364,5 +366,18 @@ hipError_t launch_resample_v(const unsigned char* in, const int* d_bounds, const
                              int W, int C, const ResizeOut& o, hipStream_t st);
 // largest tap count the kernels take (48 KiB of LDS per block): a bicubic downscale by more than ~2000x is refused
 constexpr int RESAMPLE_MAX_KSIZE = 8191;
+
+// ---------------------------------------------------------------------------------------------
+// Window edits of a resident frame (se_window.hip).  d_wins = B se_window records in DEVICE memory (the ctx's table).
+// ---------------------------------------------------------------------------------------------
+// each frame's H x W window -> image (B,3,H,W) = lut[v], sketch (B,1,H,W) = (v > 0); either output may be NULL; W % 4 == 0,
+// outputs 16-byte aligned
+hipError_t launch_window_gather(const se_window* d_wins, const float* lut, float* image, float* sketch, int B, int H, int W,
+                                hipStream_t st);
+// m8 (B,H,W) -> hits (B,4): pixels >= 128 on the window's top / bottom / left / right edge, 0 for an edge of the frame itself
+hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8, int* hits, int B, int H, int W, hipStream_t st);
+// frame[y0 + y, x0 + x, :] = rgb[b, y, x, :] where m8[b, y, x] > 0; rgb (B,H,W,3) and m8 (B,H,W) 4-byte aligned, W % 4 == 0
+hipError_t launch_window_paste(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, int B, int H, int W,
+                               hipStream_t st);
 
 }  // namespace se

@@ -1,0 +1,170 @@
+// Window edits of a resident frame: the three memory-bound helpers around the forward when it runs on an
+// H x W window of a larger uint8 frame that stays on the device.  B requests per launch, each with its own frame; a request
+// is one se_window record (include/sketchedit_hip.h) of a device table the ctx owns (se_api.hip win_put).
+//
+//  gather: the window of each frame -> that request's slot of the forward's fp32 NCHW inputs, through the ctx's
+//          dequantisation table (bit-identical to se_dequantize_u8 on a contiguous crop), and the window's sketch as (v > 0);
+//  border: from the forward's uint8 mask, the pixels >= 128 on each one-pixel edge of the window (4 counts per request; an
+//          edge that is the frame's own edge counts 0) -- "did the edit reach the window's border";
+//  paste:  frame[y0 + y, x0 + x, :] = rgb[b, y, x, :] where mask_u8[b, y, x] > 0; every other byte of the frame is untouched.
+//
+// A window row starts at byte 3 (y Wi + x0) of the frame: any alignment.  gather reads it with aligned dword loads and a
+// byte shift; a dword that would reach outside the row's own bytes (the first and the last of a row) is assembled from byte
+// loads of the row's bytes only, so nothing outside the window is ever read.  paste writes whole dwords only where four
+// neighbouring pixels are all selected and the address allows it, single bytes otherwise: it never rewrites a byte it does
+// not own, so concurrent lanes (and windows of other requests on the same frame, which the host requires to be disjoint)
+// do not race.
+#include "../../include/sketchedit_hip.h"
+#include "se_device.h"
+#include "se_kernels.h"
+
+#include <cstdint>
+
+namespace se {
+
+namespace {
+
+// the dword at the 4-byte aligned address p, of which only the bytes inside [lo, hi) are read (the others are 0)
+__device__ __forceinline__ unsigned load_dword_within(const unsigned char* p, const unsigned char* lo, const unsigned char* hi) {
+  if (p >= lo && p + 4 <= hi) return *(const unsigned*)p;
+  unsigned v = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (p + i >= lo && p + i < hi) v |= (unsigned)p[i] << (8 * i);
+  return v;
+}
+
+// One lane = 4 consecutive pixels of one window row: 12 frame bytes + 4 sketch bytes in, four float4 stores out.
+__global__ void __launch_bounds__(256) window_gather_kernel(const se_window* __restrict__ wins, const float* __restrict__ lut,
+                                                            float* __restrict__ image, float* __restrict__ sketch, int B, int H,
+                                                            int W) {
+  __shared__ float T[256];
+  T[threadIdx.x] = lut[threadIdx.x];
+  __syncthreads();
+  const int W4 = W >> 2;
+  const long q = (long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (long)B * H * W4) return;
+  const int x = (int)(q % W4) * 4;
+  const long by = q / W4;
+  const int y = (int)(by % H), b = (int)(by / H);
+  const se_window w = wins[b];
+  const size_t HW = (size_t)H * W, in = (size_t)y * W + x;
+  if (image) {
+    const unsigned char* row = w.frame_u8 + ((size_t)(w.y0 + y) * w.Wi + w.x0) * 3;       // the window row's bytes: [row, row + 3 W)
+    const unsigned char* a = row + 3 * x;
+    const unsigned char* a0 = (const unsigned char*)((uintptr_t)a & ~(uintptr_t)3);
+    const int sh = (int)((uintptr_t)a & 3) * 8;
+    unsigned d[4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) d[i] = load_dword_within(a0 + 4 * i, row, row + 3 * W);
+    d[3] = sh ? load_dword_within(a0 + 12, row, row + 3 * W) : 0u;
+    unsigned char v[12];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const unsigned u = sh ? (d[i] >> sh) | (d[i + 1] << (32 - sh)) : d[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[4 * i + e] = (u >> (8 * e)) & 255u;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      *(float4*)(image + ((size_t)b * 3 + c) * HW + in) = make_float4(T[v[c]], T[v[3 + c]], T[v[6 + c]], T[v[9 + c]]);
+  }
+  if (sketch) {
+    const unsigned char* s = w.sketch_u8 + in;
+    unsigned u;
+    if (((uintptr_t)w.sketch_u8 & 3) == 0) u = *(const unsigned*)s;       // (W % 4 == 0: every group of a 4-aligned sketch is)
+    else u = (unsigned)s[0] | ((unsigned)s[1] << 8) | ((unsigned)s[2] << 16) | ((unsigned)s[3] << 24);
+    *(float4*)(sketch + (size_t)b * HW + in) =
+        make_float4((u & 0xffu) ? 1.f : 0.f, (u & 0xff00u) ? 1.f : 0.f, (u & 0xff0000u) ? 1.f : 0.f, (u & 0xff000000u) ? 1.f : 0.f);
+  }
+}
+
+// One wave per (side, request): the lanes walk the edge 64 pixels at a time, a shuffle reduction adds their counts and lane 0
+// stores the total (a plain vector store: every count is written on every call, nothing to zero beforehand).
+// side 0 top, 1 bottom, 2 left, 3 right.
+__global__ void __launch_bounds__(64) window_border_kernel(const se_window* __restrict__ wins, const unsigned char* __restrict__ m8,
+                                                           int* __restrict__ hits, int H, int W) {
+  const int side = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  const se_window w = wins[b];
+  const bool on_frame_edge = side == 0 ? w.y0 == 0 : side == 1 ? w.y0 + H == w.Hi : side == 2 ? w.x0 == 0 : w.x0 + W == w.Wi;
+  int n = 0;
+  if (!on_frame_edge) {
+    const unsigned char* m = m8 + (size_t)b * H * W;
+    const int len = side < 2 ? W : H;
+    const size_t first = side == 1 ? (size_t)(H - 1) * W : side == 3 ? (size_t)(W - 1) : 0;
+    const size_t step = side < 2 ? 1 : (size_t)W;
+    for (int i = lane; i < len; i += 64) n += m[first + i * step] >= 128 ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
+  if (lane == 0) hits[b * 4 + side] = n;
+}
+
+// One lane = 4 consecutive pixels of one window row.
+__global__ void __launch_bounds__(256) window_paste_kernel(const se_window* __restrict__ wins, const unsigned char* __restrict__ rgb,
+                                                           const unsigned char* __restrict__ m8, int B, int H, int W) {
+  const int W4 = W >> 2;
+  const long q = (long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (long)B * H * W4) return;
+  const int x = (int)(q % W4) * 4;
+  const long by = q / W4;
+  const int y = (int)(by % H), b = (int)(by / H);
+  const size_t pix = ((size_t)b * H + y) * W + x;
+  const unsigned mk = *(const unsigned*)(m8 + pix);
+  if (!mk) return;
+  const se_window w = wins[b];
+  unsigned char* dst = w.frame_u8 + ((size_t)(w.y0 + y) * w.Wi + w.x0 + x) * 3;
+  const unsigned* src = (const unsigned*)(rgb + pix * 3);
+  const unsigned s0 = src[0], s1 = src[1], s2 = src[2];
+  const bool all4 = (mk & 0xffu) && (mk & 0xff00u) && (mk & 0xff0000u) && (mk & 0xff000000u);
+  if (all4 && ((uintptr_t)dst & 3) == 0) {
+    unsigned* d = (unsigned*)dst;
+    d[0] = s0; d[1] = s1; d[2] = s2;
+    return;
+  }
+  const unsigned s[3] = {s0, s1, s2};
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    if ((mk >> (8 * p)) & 255u) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int j = 3 * p + c;
+        dst[j] = (unsigned char)((s[j >> 2] >> (8 * (j & 3))) & 255u);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t launch_window_gather(const se_window* d_wins, const float* lut, float* image, float* sketch, int B, int H, int W,
+                                hipStream_t st) {
+  const long nq = (long)B * H * W / 4;
+  // bytes: the window's uint8 image and sketch read once, the fp32 planes written once
+  set_launch_cost(0.0, (double)B * H * W * ((image ? 3.0 + 12.0 : 0.0) + (sketch ? 1.0 + 4.0 : 0.0)), "window_gather");
+  set_launch_grid((nq + 255) / 256);
+  ProfScope ps_(st, PL_WINDOW_GATHER);
+  hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_wins, lut, image, sketch, B, H, W);
+  return hipGetLastError();
+}
+
+hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8, int* hits, int B, int H, int W, hipStream_t st) {
+  set_launch_cost(0.0, (double)B * (2.0 * W + 2.0 * H + 16.0), "window_border");
+  set_launch_grid(4L * B);
+  ProfScope ps_(st, PL_WINDOW_BORDER);
+  hipLaunchKernelGGL(window_border_kernel, dim3(4, (unsigned)B), dim3(64), 0, st, d_wins, m8, hits, H, W);
+  return hipGetLastError();
+}
+
+hipError_t launch_window_paste(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, int B, int H, int W,
+                               hipStream_t st) {
+  const long nq = (long)B * H * W / 4;
+  // bytes: an upper bound (every pixel selected): mask and rgb read, the frame's window written
+  set_launch_cost(0.0, (double)B * H * W * 7.0, "window_paste");
+  set_launch_grid((nq + 255) / 256);
+  ProfScope ps_(st, PL_WINDOW_PASTE);
+  hipLaunchKernelGGL(window_paste_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_wins, rgb, m8, B, H, W);
+  return hipGetLastError();
+}
+
+}  // namespace se

@@ -28,6 +28,10 @@ KERNEL_LABELS = {
     # the demo's per-request resizes (se_resize.hip)
     "(anonymous namespace)::resample_h_kernel": "resize_h", "(anonymous namespace)::resample_v_kernel": "resize_v",
     "resample_h_kernel": "resize_h", "resample_v_kernel": "resize_v",
+    # window edits of a resident frame (se_window.hip)
+    "(anonymous namespace)::window_gather_kernel": "window_gather", "(anonymous namespace)::window_border_kernel": "window_border",
+    "(anonymous namespace)::window_paste_kernel": "window_paste",
+    "window_gather_kernel": "window_gather", "window_border_kernel": "window_border", "window_paste_kernel": "window_paste",
 }
 
 

@@ -87,6 +87,189 @@ def process_image(model, img, mask, low_latency=None, device_io=False):
     return _to_image(generated, size_raw)
 
 
+def sketch_bbox(sketch):
+    """Tight box of `sketch > 0` of a 2-D uint8 array as (y0, x0, y1, x1), half open; None for an empty sketch."""
+    rows = np.flatnonzero(np.any(sketch > 0, axis=1))
+    if rows.size == 0:
+        return None
+    cols = np.flatnonzero(np.any(sketch[rows[0]:rows[-1] + 1] > 0, axis=0))
+    return int(rows[0]), int(cols[0]), int(rows[-1]) + 1, int(cols[-1]) + 1
+
+
+def choose_window(bbox, frame_hw, margin=0.5, bucket=64, min_side=256):
+    """The window a sketch is edited through (pure host arithmetic).  `bbox` = (y0, x0, y1, x1), half open, the
+    tight box of `sketch > 0` (sketch_bbox); `frame_hw` = (Hi, Wi).  Per axis the side is the box's extent plus
+    ceil(margin * max(box height, box width)) on both ends, raised to `min_side` (and to the forward's minimum, 16), rounded
+    UP to a multiple of `bucket` and capped at the frame's extent floored to a multiple of 8; the window is centred on the
+    box and shifted to lie inside the frame.  -> (y0, x0, h, w), or None for an empty sketch (bbox None or empty).  A frame
+    under the forward's minimum raises ValueError, as _to_tensors does.
+    The defaults are a policy, not a measurement: context of half the edit's size around it, the reference's 256 x 256
+    training size as the floor, and buckets so that windows of different requests share sizes and batch."""
+    Hi, Wi = int(frame_hw[0]), int(frame_hw[1])
+    if Hi // 8 * 8 < 16 or Wi // 8 * 8 < 16:
+        raise ValueError("image too small: %dx%d" % (Wi, Hi))
+    if bucket < 8 or bucket % 8:
+        raise ValueError("bucket must be a positive multiple of 8: %r" % (bucket,))
+    if margin < 0:
+        raise ValueError("margin must not be negative: %r" % (margin,))
+    if bbox is None:
+        return None
+    by0, bx0, by1, bx1 = (int(v) for v in bbox)
+    by0, bx0, by1, bx1 = max(by0, 0), max(bx0, 0), min(by1, Hi), min(bx1, Wi)
+    if by1 <= by0 or bx1 <= bx0:
+        return None
+    pad = int(np.ceil(margin * max(by1 - by0, bx1 - bx0)))
+
+    def axis(lo, hi, extent):
+        side = max(hi - lo + 2 * pad, int(min_side), 16)
+        side = min(-(-side // bucket) * bucket, extent // 8 * 8)
+        start = lo - (side - (hi - lo)) // 2              # centred (a box larger than the window: its centre part)
+        return min(max(start, 0), extent - side), side
+
+    y0, h = axis(by0, by1, Hi)
+    x0, w = axis(bx0, bx1, Wi)
+    return y0, x0, h, w
+
+
+class _ModelBackend:
+    """The device side of an editing session: an EditLine2Model's engine and torch for the copies.  (A seam: the host
+    logic of EditSession and of the window batcher is tested against a scripted stand-in.)"""
+
+    def __init__(self, model):
+        if not (hasattr(model, "engine") and hasattr(model, "edit_window_u8")):
+            raise ValueError("an editing session needs an EditLine2Model (its library engine runs the window steps)")
+        self.model = model
+
+    def _device(self):
+        import torch
+        return torch.device("cuda", self.model.engine().device)
+
+    def upload(self, a):
+        from . import _lib
+        return _lib.upload_u8(a, self._device())
+
+    def run(self, frames, origins, sketches, h, w, commit, low_latency):
+        """-> (rgb, mask_u8, counts): the device results and the border counts on the host (a synchronisation)"""
+        rgb, m8, hits = self.model.edit_window_u8(frames, origins, sketches, h, w, commit=commit, low_latency=low_latency)
+        return rgb, m8, hits.cpu().tolist()
+
+    def paste(self, frames, origins, rgb, m8):
+        self.model.engine().window_paste_u8(frames, origins, rgb, m8)
+
+    def select(self, t, idx):
+        """rows `idx` of a batch result as a contiguous batch"""
+        return t if list(idx) == list(range(t.shape[0])) else t[list(idx)].contiguous()
+
+    def crop(self, frame, y0, x0, h, w):
+        return frame[y0:y0 + h, x0:x0 + w].contiguous().cpu().numpy()
+
+    def download(self, frame):
+        return frame.cpu().numpy()
+
+
+def _sketch_array(sketch):
+    """A request's sketch as a 2-D uint8 array: a PIL 'L' image or an array."""
+    if hasattr(sketch, "mode"):
+        if sketch.mode != "L":
+            raise ValueError("a window edit takes an 'L' sketch (got mode %r)" % sketch.mode)
+        sketch = np.asarray(sketch)
+    sketch = np.asarray(sketch)
+    if sketch.ndim != 2 or sketch.dtype != np.uint8:
+        raise ValueError("a window edit takes a 2-D uint8 sketch")
+    return sketch
+
+
+class EditSession:
+    """A frame that stays on the device and is edited in place through windows (INTEGRATION.md "Editing
+    sessions").  `image`: a PIL image or an (H,W,3) uint8 array; uploaded once.  Every `edit` runs the forward on a window
+    around the sketch only -- its result is DEFINED as the model's inference on that crop, pasted where the uint8 mask is
+    > 0 -- so its time follows the edit, not the frame; pixels the edit does not select keep their bytes, and only the
+    window's sketch and the window's result cross the bus.  The frame on the device is the session's state: the next edit
+    sees this one's result.  Edits of one session are serialised; do not mix `edit` with a BatchingServer(window=True)
+    that was handed the same session."""
+
+    def __init__(self, model, image, backend=None):
+        if hasattr(image, "convert"):
+            image = np.asarray(image.convert("RGB"))
+        image = np.asarray(image)
+        if image.ndim != 3 or image.shape[2] != 3 or image.dtype != np.uint8:
+            raise ValueError("a session's frame is an (H,W,3) uint8 RGB image")
+        Hi, Wi = image.shape[:2]
+        if Hi // 8 * 8 < 16 or Wi // 8 * 8 < 16:
+            raise ValueError("image too small: %dx%d" % (Wi, Hi))
+        self.model = model
+        self.backend = backend if backend is not None else _ModelBackend(model)
+        self.frame_hw = (Hi, Wi)
+        self._frame = self.backend.upload(image)
+        self._lock = threading.Lock()
+
+    def _request(self, sketch):
+        """-> (sketch array, bbox) of a full-size sketch; refusals of the window path"""
+        sk = _sketch_array(sketch)
+        if sk.shape != self.frame_hw:
+            raise ValueError("sketch is %dx%d, the frame %dx%d: a sketch of another size takes the whole-frame path "
+                             "(serve.process_image)" % (sk.shape[1], sk.shape[0], self.frame_hw[1], self.frame_hw[0]))
+        bbox = sketch_bbox(sk)
+        if bbox is None:
+            raise ValueError("empty sketch: nothing to edit")
+        return sk, bbox
+
+    def _check_window(self, window):
+        y0, x0, h, w = (int(v) for v in window)
+        Hi, Wi = self.frame_hw
+        if h < 16 or w < 16 or h % 8 or w % 8 or y0 < 0 or x0 < 0 or y0 + h > Hi or x0 + w > Wi:
+            raise ValueError("window %r: sides are multiples of 8, >= 16, and the window lies inside the %dx%d frame" % (window, Wi, Hi))
+        return y0, x0, h, w
+
+    def _grown(self, bbox, window, margin):
+        """The next larger automatic window: the margin doubles until the window changes.  -> (window, margin), or None when
+        the window already is the floored frame (it cannot grow)."""
+        Hi, Wi = self.frame_hw
+        if (window[2], window[3]) == (Hi // 8 * 8, Wi // 8 * 8):
+            return None
+        while True:
+            margin *= 2
+            nxt = choose_window(bbox, self.frame_hw, margin=margin)
+            if nxt != window:
+                return nxt, margin
+
+    def edit(self, sketch, window=None, max_grow=2, low_latency=None):
+        """One edit.  `sketch`: the FULL-SIZE sketch (PIL 'L' / 2-D uint8 array, the frame's size).  The window is
+        choose_window of the sketch's box, or `window` = (y0, x0, h, w) as given (then it never grows).  The forward runs on
+        the window without committing; if its mask reaches an edge of the window (border counts, a side on the frame's own
+        edge counts 0) and the window can still grow, the margin doubles and the edit is rerun on the larger window, at most
+        `max_grow` times; then the result is pasted.  -> (patch, (x0, y0), info): `patch` (h,w,3) uint8 = the frame's window
+        after the paste (the only download), its position, and info = dict(window=(y0, x0, h, w), counts=[top, bottom, left,
+        right], reruns=n, margin=m)."""
+        sk, bbox = self._request(sketch)
+        margin = 0.5
+        fixed = window is not None
+        win = self._check_window(window) if fixed else choose_window(bbox, self.frame_hw, margin=margin)
+        reruns = 0
+        be = self.backend
+        with self._lock:
+            while True:
+                y0, x0, h, w = win
+                nxt = None if fixed or reruns >= max_grow else self._grown(bbox, win, margin)
+                # a run whose counts cannot change anything commits at once: no round trip between forward and paste
+                commit = nxt is None
+                crop = be.upload(sk[y0:y0 + h, x0:x0 + w])
+                rgb, m8, counts = be.run([self._frame], [(y0, x0)], [crop], h, w, commit, low_latency)
+                if commit or not any(counts[0]):
+                    break
+                win, margin = nxt
+                reruns += 1
+            if not commit:
+                be.paste([self._frame], [(y0, x0)], rgb, m8)
+            patch = be.crop(self._frame, y0, x0, h, w)
+        return patch, (x0, y0), dict(window=win, counts=list(counts[0]), reruns=reruns, margin=margin)
+
+    def frame(self):
+        """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""
+        with self._lock:
+            return self.backend.download(self._frame)
+
+
 def create_models_for_gpus(opt, gpu_ids=None):
     """One EditLine2Model per GPU of this node (weights replicated, one se_ctx / stream / workspace each): the worker set
     of a multi-GPU BatchingServer.  `gpu_ids` defaults to every visible device."""
@@ -123,9 +306,18 @@ class BatchingServer:
     uploads them, resizes and normalises each request into its slot of the group's batch on the device
     (Engine.prepare_u8), runs one forward with fused output quantisation for the group and resizes each result back to its
     raw size on the device (Engine.resize_u8).  Byte-identical to the host steps; a request whose sketch mode the device
-    path does not take is prepared on the host and joins the same group."""
+    path does not take is prepared on the host and joins the same group.
 
-    def __init__(self, model=None, max_batch=32, max_wait_s=0.005, models=None, mode_policy="pinned", device_io=False):
+    window=True (one EditLine2Model): the server batches edits of editing sessions instead -- `submit(session, sketch)` ->
+    what `EditSession.edit` returns.  The group key is the WINDOW size (choose_window's buckets), so sessions whose frames
+    differ in size share a forward; the mode policy is the same, by window size and `max_batch`.  A group is one gather,
+    one forward, one border and one paste launch (Engine.edit_window_u8 / window_paste_u8).  Growing is per request: a
+    request whose mask reaches its window's border is not pasted but queued again under its larger window's size (at most
+    `max_grow` times); a group never holds two requests of one session (the second waits for the next group: it must
+    see the first's result)."""
+
+    def __init__(self, model=None, max_batch=32, max_wait_s=0.005, models=None, mode_policy="pinned", device_io=False,
+                 window=False, max_grow=2):
         if mode_policy not in ("pinned", "by_size"):
             raise ValueError(mode_policy)
         self.mode_policy = mode_policy
@@ -135,6 +327,10 @@ class BatchingServer:
             raise ValueError("BatchingServer needs a model (or a list of models, one per GPU)")
         if self.device_io and not all(hasattr(m, "engine") and hasattr(m, "inference_u8") for m in self.models):
             raise ValueError("device_io=True needs EditLine2Model workers (their library engine runs the request steps)")
+        self.window, self.max_grow = bool(window), int(max_grow)
+        if self.window and (self.device_io or len(self.models) != 1):
+            raise ValueError("window=True serves the sessions of ONE model (a session's frame lives on that model's GPU) and "
+                             "has no device_io variant")
         self.model = self.models[0]
         self._has_knob = [_accepts_low_latency(m) for m in self.models]
         self.max_batch, self.max_wait_s = max_batch, max_wait_s
@@ -149,9 +345,19 @@ class BatchingServer:
         for t in self._workers:
             t.start()
 
+    def _submit_window(self, session, sketch):
+        """key ("window", 3, h, w); request = dict(session, sketch, bbox, window, margin, reruns)"""
+        if session.model is not self.model:
+            raise ValueError("the session belongs to another model than this server's")
+        sk, bbox = session._request(sketch)
+        win = choose_window(bbox, session.frame_hw)
+        return ("window", 3, win[2], win[3]), dict(session=session, sketch=sk, bbox=bbox, window=win, margin=0.5, reruns=0), None
+
     def submit(self, img, mask):
-        arrays = _device_inputs(img, mask) if self.device_io else None
-        if arrays is not None:
+        arrays = _device_inputs(img, mask) if self.device_io and not self.window else None
+        if self.window:
+            key, req, size_raw = self._submit_window(img, mask)
+        elif arrays is not None:
             h_raw, w_raw = arrays[0].shape[:2]
             key, req, size_raw = (1, 3, h_raw // 8 * 8, w_raw // 8 * 8), arrays, (w_raw, h_raw)
         else:
@@ -194,18 +400,73 @@ class BatchingServer:
                 try:
                     deadline = head[4] + self.max_wait_s
                     while True:
-                        n = sum(1 for q in self._queue if q[0] == shape)
+                        n = len(self._candidates(shape))
                         left = deadline - time.monotonic()
                         if n >= self.max_batch or left <= 0 or self._stop:
                             break
                         self._lock.wait(left)
-                    group = [q for q in self._queue if q[0] == shape][:self.max_batch]
+                    group = self._candidates(shape)[:self.max_batch]
                     taken = {id(q) for q in group}    # (list.remove would compare the tensors inside the tuples)
                     self._queue = [q for q in self._queue if id(q) not in taken]
                 finally:
                     self._collecting.discard(shape)
                     self._lock.notify_all()           # requests of this size that did not fit may be collected now
                 return group
+
+    def _candidates(self, shape):
+        """Queued requests of one working size, oldest first.  Window mode: only a session's OLDEST queued request, whatever its
+        size, is eligible -- a session's edits run in the order they were submitted, one per group."""
+        if not self.window:
+            return [q for q in self._queue if q[0] == shape]
+        seen, out = set(), []
+        for q in self._queue:
+            if id(q[1]["session"]) not in seen:
+                seen.add(id(q[1]["session"]))
+                if q[0] == shape:
+                    out.append(q)
+        return out
+
+    def _run_window(self, k, group):
+        """One group of window edits of one window size.  -> one entry per request: its result, or None for a request that
+        was queued again under a larger window."""
+        reqs = [q[1] for q in group]
+        be = reqs[0]["session"].backend
+        _, _, h, w = group[0][0]
+        low_latency = self._mode(group[0][0]) if self._has_knob[k] else None
+        grown = [None if r["reruns"] >= self.max_grow else r["session"]._grown(r["bbox"], r["window"], r["margin"]) for r in reqs]
+        commit = all(g is None for g in grown)            # no request can grow: the counts decide nothing
+        frames = [r["session"]._frame for r in reqs]
+        origins = [r["window"][:2] for r in reqs]
+        locks = sorted({id(r["session"]): r["session"]._lock for r in reqs}.items())
+        for _, lk in locks:
+            lk.acquire()
+        try:
+            crops = [be.upload(r["sketch"][y0:y0 + h, x0:x0 + w]) for r, (y0, x0) in zip(reqs, origins)]
+            rgb, m8, counts = be.run(frames, origins, crops, h, w, commit, low_latency)
+            stay = [i for i in range(len(reqs)) if grown[i] is None or not any(counts[i])]
+            if not commit and stay:
+                be.paste([frames[i] for i in stay], [origins[i] for i in stay], be.select(rgb, stay), be.select(m8, stay))
+            outs = [None] * len(reqs)
+            for i in stay:
+                r = reqs[i]
+                y0, x0 = origins[i]
+                outs[i] = (be.crop(frames[i], y0, x0, h, w), (x0, y0),
+                           dict(window=r["window"], counts=list(counts[i]), reruns=r["reruns"], margin=r["margin"]))
+        finally:
+            for _, lk in locks:
+                lk.release()
+        again = []
+        for i, q in enumerate(group):
+            if outs[i] is None:
+                r = dict(reqs[i])
+                r["window"], r["margin"] = grown[i]
+                r["reruns"] += 1
+                again.append((("window", 3, r["window"][2], r["window"][3]), r, None, q[3], q[4]))
+        if again:
+            with self._lock:
+                self._queue = again + self._queue     # in front: they are older than what arrived since, and their sessions' next edits wait for them
+                self._lock.notify_all()
+        return outs
 
     def _mode(self, shape):
         """Execution mode of a group of requests of working size `shape` (1,3,H,W) -- see the class docstring."""
@@ -255,8 +516,13 @@ class BatchingServer:
                 return
             if not group:                 # another worker took the requests this one was waiting with
                 continue
+            ran = len(group)
             try:
-                if self.device_io:
+                if self.window:
+                    outs = self._run_window(k, group)
+                    done = [(q, out) for q, out in zip(group, outs) if out is not None]     # the others were queued again
+                    group, outs = [q for q, _ in done], [out for _, out in done]
+                elif self.device_io:
                     outs = self._run_device(k, group)
                 else:
                     x = torch.cat([q[1][0] for q in group], 0)
@@ -265,7 +531,7 @@ class BatchingServer:
                         generated, _ = self._forward(k, x, m)
                     outs = [_to_image(generated[i:i + 1], q[2]) for i, q in enumerate(group)]
                 with self._lock:
-                    self.batches.append(len(group))
+                    self.batches.append(ran)
                     self.batches_by_model[k] += 1
                 for q, out in zip(group, outs):
                     q[3]["out"] = out

@@ -4,6 +4,15 @@ around the forward, device_io=False) and with the steps on the device (device_io
 input read once, output written once) from se_profile_report over one device-path request.  Prints one JSON line.
 
     python tools/serve_probe.py [--reps N] [--out FILE]
+
+--window: the editing-session leg instead.  One process, B=1, low-latency mode, a 1921x1081 frame with a sketch
+whose default window is 512x512; wall time per request ending in the download, median / min / max over --reps:
+  (a) whole_frame_device_io: serve.process_image(device_io=True) on the whole frame,
+  (b) whole_512_device_io:   the same whole-frame path on a 512x512 request (the window's crop),
+  (c) edit_session:          serve.EditSession.edit (the frame resident, only the window's sketch up and the patch down),
+plus se_profile_report's per-kernel times of one session edit.
+
+    python tools/serve_probe.py --window [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -40,13 +49,61 @@ def wall_ms(fn, reps):
         fn()                               # ends in a device-to-host copy: the request is complete
         ts.append((time.perf_counter() - t0) * 1e3)
     ts.sort()
-    return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3))
+    return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+
+
+def window_leg(model, reps):
+    """(a), (b), (c) of the module docstring"""
+    import numpy as np
+    from PIL import Image
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    sk = np.zeros((h, w), np.uint8)
+    sk[400:640, 800:1040] = ((rng.rand(240, 240) < 0.01) * 255).astype(np.uint8)      # 240 + 2 * 120 = 480 -> the 512 bucket
+    sk[400, 800] = sk[639, 1039] = 255
+    win = serve.choose_window(serve.sketch_bbox(sk), (h, w))
+    assert win[2:] == (512, 512), win
+    y0, x0 = win[:2]
+    img, skim = Image.fromarray(frame), Image.fromarray(sk)
+    img512 = Image.fromarray(np.ascontiguousarray(frame[y0:y0 + 512, x0:x0 + 512]))
+    sk512 = Image.fromarray(np.ascontiguousarray(sk[y0:y0 + 512, x0:x0 + 512]))
+    session = serve.EditSession(model, frame)
+    legs = dict(whole_frame_device_io=lambda: serve.process_image(model, img, skim, low_latency=True, device_io=True),
+                whole_512_device_io=lambda: serve.process_image(model, img512, sk512, low_latency=True, device_io=True),
+                edit_session=lambda: session.edit(sk, max_grow=0, low_latency=True))
+    legs["edit_session_default_grow"] = lambda: session.edit(sk, low_latency=True)     # max_grow = 2: counts read before the paste
+    # three rounds over the legs, each leg timed back to back after its own warm-up (wall_ms): the first small request
+    # after a 1080p one pays for the switch, which is not what a leg is about; the rounds show the run-to-run spread
+    rounds = [{k: wall_ms(fn, reps) for k, fn in legs.items()} for _ in range(3)]
+    out = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out[k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                      max=max(r[k]["max"] for r in rounds))
+    info = session.edit(sk, low_latency=True)[2]
+    eng = model.engine()
+    eng.profile(True)
+    session.edit(sk, max_grow=0, low_latency=True)
+    rep = eng.profile_report()
+    eng.profile(False)
+    kernels = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+    eng.profile(True)
+    legs["whole_512_device_io"]()
+    rep = eng.profile_report()
+    eng.profile(False)
+    whole512 = round(sum(k["total_ms"] for k in rep["kernels"]), 3)
+    return dict(tool="serve_probe --window", B=1, reps=reps, mode="low_latency", frame=[w, h], window=list(win),
+                ms=out, default_edit_info=dict(counts=info["counts"], reruns=info["reruns"], window=list(info["window"])),
+                edit_kernels_profiled=kernels, edit_kernels_total_ms=round(sum(k["ms"] for k in kernels.values()), 3), whole_512_kernels_total_ms=whole512)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--window", action="store_true", help="the editing-session leg (see the module docstring)")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -55,6 +112,13 @@ def main():
     from sketchedit_amd import serve
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     model = make_model(tempfile.mkdtemp())
+    if args.window:
+        line = json.dumps(window_leg(model, args.reps))
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     eng = model.engine()
     rng = np.random.RandomState(0)
     cases = []
