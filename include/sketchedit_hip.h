@@ -216,6 +216,31 @@ int se_edit_window_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, i
                       unsigned char* mask_u8_out, int* hits_out, int commit, void* workspace, size_t workspace_bytes, int flags);
 size_t se_edit_window_u8_workspace_bytes(se_ctx* ctx, int B, int H, int W);
 
+/* ---- window edits at a working size ------------------------------------------------------------------------
+ * The hs x ws window of the frame (any sizes >= 16, inside the frame) is resampled into the forward's inputs at the working
+ * size H x W (multiples of 8, >= 16), the forward runs there, and its result AND its mask are resampled back to hs x ws and
+ * pasted where the resampled mask byte is > 0.  Every resample is Pillow's BICUBIC `Image.resize` bit for bit (se_resize_u8),
+ * so a scaled window edit is DEFINED as: se_prepare_u8 of the contiguous crop and of the window's sketch -> the forward of
+ * se_inference_u8 -> se_resize_u8 of rgb and of mask_u8 to hs x ws -> the paste rule of se_window_paste_u8; the border counts
+ * are taken on the working-size mask, a side counting 0 where the hs x ws window lies on the frame's own edge.  The working
+ * size is the caller's policy (serve.choose_working_size); no claim about visual quality is attached to it.  All requests of
+ * a call share (hs, ws, H, W); se_window.sketch_u8 is the window's sketch at frame scale, (hs, ws).  With (H, W) == (hs, ws)
+ * every entry below is its unscaled counterpart above, byte for byte.  Violations (a window outside its frame, hs / ws < 16,
+ * H / W not multiples of 8 or < 16, a resize the kernels' tap limit refuses, overlapping windows where the call writes)
+ * return non-zero before anything is enqueued; se_last_error names the argument and the frame is untouched. */
+/* the gather end: no contiguous crop is made, and no byte outside a window's own rows is read */
+int se_window_gather_resize_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W,
+                               float* image_out, float* sketch_out);
+/* the paste end: rgb (B,H,W,3), mask_u8 (B,H,W) at the working size, 4-byte aligned */
+int se_window_paste_resize_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W,
+                              const unsigned char* rgb, const unsigned char* mask_u8);
+/* gather -> forward -> border -> paste if commit != 0, as one call without a host synchronisation, as se_edit_window_u8.
+ * rgb_out (B,H,W,3), mask_u8_out (B,H,W): the forward's outputs AT THE WORKING SIZE; hits_out (B,4); each may be NULL. */
+int se_edit_window_scaled_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W,
+                             unsigned char* rgb_out, unsigned char* mask_u8_out, int* hits_out, int commit, void* workspace,
+                             size_t workspace_bytes, int flags);
+size_t se_edit_window_scaled_u8_workspace_bytes(se_ctx* ctx, int B, int hs, int ws, int H, int W);
+
 /* Host only (no HIP call, no ctx): the coefficient table the resize uses for one axis.  Returns ksize, the taps per output
  * (-1: bad arguments); when bounds (2*out ints: first input index, tap count) and k (cap >= out*ksize ints, fixed point
  * with 22 fractional bits, rows zero padded to ksize) are given, fills them.  Lets a test compare the tables with Pillow's. */

@@ -36,7 +36,8 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
            "se_gated_conv2d_ex", "se_attention", "se_attention_ex", "se_quantize_u8", "se_dequantize_u8", "se_inference_u8io", "se_profile_enable",
            "se_profile_report", "se_debug_set_option", "se_debug_get_option", "se_debug_reset_options",
            "se_resize_u8", "se_prepare_u8", "se_edit_u8", "se_edit_u8_workspace_bytes", "se_resample_coeffs",
-           "se_window_gather_u8", "se_window_border_u8", "se_window_paste_u8", "se_edit_window_u8", "se_edit_window_u8_workspace_bytes"]
+           "se_window_gather_u8", "se_window_border_u8", "se_window_paste_u8", "se_edit_window_u8", "se_edit_window_u8_workspace_bytes",
+           "se_window_gather_resize_u8", "se_window_paste_resize_u8", "se_edit_window_scaled_u8", "se_edit_window_scaled_u8_workspace_bytes"]
 
 
 class SketchEditHipError(RuntimeError):
@@ -174,6 +175,14 @@ def load_library():
         lib.se_edit_window_u8.restype = ci
         lib.se_edit_window_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
         lib.se_edit_window_u8_workspace_bytes.restype = sz
+        lib.se_window_gather_resize_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, ci, c_f, c_f]
+        lib.se_window_gather_resize_u8.restype = ci
+        lib.se_window_paste_resize_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, ci, vp, vp]
+        lib.se_window_paste_resize_u8.restype = ci
+        lib.se_edit_window_scaled_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, sz, ci]
+        lib.se_edit_window_scaled_u8.restype = ci
+        lib.se_edit_window_scaled_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci, ci]
+        lib.se_edit_window_scaled_u8_workspace_bytes.restype = sz
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -670,6 +679,61 @@ class Engine:
         if self.lib.se_edit_window_u8(self.h, self._stream(), wins, B, H, W, _ptr(rgb), _ptr(m8), _ptr(hits), 1 if commit else 0,
                                       _ptr(ws), ws.numel(), flags):
             self._err("se_edit_window_u8")
+        return rgb, m8, hits
+
+    # ---- the same at a working size: window (hs, ws) in the frame, forward at (H, W) --------------------------
+    def window_gather_resize_u8(self, frames, origins, sketches, window_hw, H, W):
+        """se_window_gather_resize_u8: the hs x ws window at origins[i] of every frame and its (hs, ws) sketch, resampled
+        (Pillow's BICUBIC, bit for bit) into the forward's inputs at H x W -> (image (B,3,H,W), sketch (B,1,H,W)) fp32:
+        prepare_u8 of the contiguous crops, without the crops."""
+        import torch
+        hs, ws = (int(v) for v in window_hw)
+        wins = self._windows(frames, origins, sketches)
+        for sk in sketches:
+            if tuple(sk.shape) != (hs, ws):
+                raise SketchEditHipError("window_gather_resize_u8: a sketch is the window's (hs,ws) uint8 plane")
+        B, dev = len(frames), frames[0].device
+        image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        sketch = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        if self.lib.se_window_gather_resize_u8(self.h, self._stream(), wins, B, hs, ws, H, W, _ptr(image), _ptr(sketch)):
+            self._err("se_window_gather_resize_u8")
+        return image, sketch
+
+    def window_paste_resize_u8(self, frames, origins, window_hw, rgb, mask_u8):
+        """se_window_paste_resize_u8, in place: rgb (B,H,W,3) and mask_u8 (B,H,W) at the working size are resampled to the
+        hs x ws windows (BICUBIC, both) and frames[i][y0 + y, x0 + x] takes the resampled colour where the resampled mask
+        byte is > 0.  Overlapping windows of one frame in one call are refused."""
+        _check_dev_u8(rgb, mask_u8)
+        hs, ws = (int(v) for v in window_hw)
+        B, H, W = mask_u8.shape
+        if tuple(rgb.shape) != (B, H, W, 3) or len(frames) != B:
+            raise SketchEditHipError("window_paste_resize_u8: expected rgb (B,H,W,3), mask_u8 (B,H,W) and one frame per request")
+        wins = self._windows(frames, origins)
+        if self.lib.se_window_paste_resize_u8(self.h, self._stream(), wins, B, hs, ws, H, W, _ptr(rgb), _ptr(mask_u8)):
+            self._err("se_window_paste_resize_u8")
+
+    def edit_window_scaled_u8(self, frames, origins, sketches, window_hw, H, W, flags, commit=True, low_latency=None):
+        """se_edit_window_scaled_u8: the window edit with the forward at the working size H x W, ONE library call without a
+        host synchronisation.  -> (rgb (B,H,W,3) uint8, mask_u8 (B,H,W) uint8, hits (B,4) int32) on the device, rgb and
+        mask_u8 AT THE WORKING SIZE.  low_latency: None = by the size of the forward, (B, H, W)."""
+        import torch
+        hs, ws = (int(v) for v in window_hw)
+        wins = self._windows(frames, origins, sketches)
+        for sk in sketches:
+            if tuple(sk.shape) != (hs, ws):
+                raise SketchEditHipError("edit_window_scaled_u8: a sketch is the window's (hs,ws) uint8 plane")
+        B, dev = len(frames), frames[0].device
+        need = self.lib.se_edit_window_scaled_u8_workspace_bytes(self.h, B, hs, ws, H, W)
+        if need == 0:
+            self._err("se_edit_window_scaled_u8_workspace_bytes")
+        ws_t = self._workspace_bytes(need)
+        rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        m8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        hits = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
+        if self.lib.se_edit_window_scaled_u8(self.h, self._stream(), wins, B, hs, ws, H, W, _ptr(rgb), _ptr(m8), _ptr(hits),
+                                             1 if commit else 0, _ptr(ws_t), ws_t.numel(), flags):
+            self._err("se_edit_window_scaled_u8")
         return rgb, m8, hits
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):

@@ -1661,20 +1661,31 @@ int se_edit_u8(se_ctx* c, void* stream, const unsigned char* image_u8, const uns
 // ---- editing sessions: window edits of a resident frame (se_window.hip) ------------------------------
 namespace {
 
-// every argument check of the window calls, on the host, before anything is enqueued
-int win_check(se_ctx* c, const se_window* wins, int B, int H, int W, bool need_sketch, bool writes) {
+// every argument check of the window calls, on the host, before anything is enqueued.  H x W = the size the forward runs at,
+// hs x ws = the window's extent in the frame (the same unless the edit runs at a working size)
+int win_check(se_ctx* c, const se_window* wins, int B, int H, int W, int hs, int ws, bool need_sketch, bool writes) {
   if (check_dims(c, B, H, W)) return 1;
+  if (hs < 16 || ws < 16) return fail(c, "bad window hs=%d ws=%d (a window is at least 16 x 16 frame pixels)", hs, ws);
+  if (hs != H || ws != W) {
+    if (hs > 65535) return fail(c, "bad window hs=%d (a resampled window has at most 65535 rows)", hs);
+    const int io[4][2] = {{ws, W}, {hs, H}, {W, ws}, {H, hs}};       // a tap count the resize kernels refuse
+    for (const auto& a : io)
+      if (resample_ksize(a[0], a[1], SE_RESAMPLE_BICUBIC) > RESAMPLE_MAX_KSIZE)
+        return fail(c, "window hs=%d ws=%d at H=%d W=%d: the resize %d -> %d needs more taps per output than the kernels take (%d)",
+                    hs, ws, H, W, a[0], a[1], RESAMPLE_MAX_KSIZE);
+  }
   if (!wins) return fail(c, "null pointer argument: wins");
-  if (B > 65535 || (long long)B * H * W / 1024 >= (1ll << 31)) return fail(c, "window: B=%d %dx%d is more than one launch takes", B, H, W);
+  if (B > 65535 || (long long)B * H * W / 1024 >= (1ll << 31) || (long long)B * hs * ws / 1024 >= (1ll << 31))
+    return fail(c, "window: B=%d %dx%d (window %dx%d) is more than one launch takes", B, H, W, hs, ws);
   for (int i = 0; i < B; ++i) {
     const se_window& w = wins[i];
     if (!w.frame_u8) return fail(c, "wins[%d].frame_u8 is null", i);
     if (need_sketch && !w.sketch_u8) return fail(c, "wins[%d].sketch_u8 is null", i);
     if (w.Hi < 1 || w.Wi < 1) return fail(c, "wins[%d]: bad frame size Hi=%d Wi=%d", i, w.Hi, w.Wi);
-    if (w.y0 < 0 || (long long)w.y0 + H > w.Hi)
-      return fail(c, "wins[%d].y0=%d: rows [%d, %lld) of the window lie outside the frame (Hi=%d)", i, w.y0, w.y0, (long long)w.y0 + H, w.Hi);
-    if (w.x0 < 0 || (long long)w.x0 + W > w.Wi)
-      return fail(c, "wins[%d].x0=%d: columns [%d, %lld) of the window lie outside the frame (Wi=%d)", i, w.x0, w.x0, (long long)w.x0 + W, w.Wi);
+    if (w.y0 < 0 || (long long)w.y0 + hs > w.Hi)
+      return fail(c, "wins[%d].y0=%d: rows [%d, %lld) of the window lie outside the frame (Hi=%d)", i, w.y0, w.y0, (long long)w.y0 + hs, w.Hi);
+    if (w.x0 < 0 || (long long)w.x0 + ws > w.Wi)
+      return fail(c, "wins[%d].x0=%d: columns [%d, %lld) of the window lie outside the frame (Wi=%d)", i, w.x0, w.x0, (long long)w.x0 + ws, w.Wi);
   }
   if (!writes) return 0;
   // the paste of one launch runs concurrently for all requests: their windows must not share a byte
@@ -1685,7 +1696,7 @@ int win_check(se_ctx* c, const se_window* wins, int B, int H, int W, bool need_s
       if (a1 <= b0 || b1 <= a0) continue;                 // frames apart in memory
       if (a0 != b0 || a.Wi != b.Wi || a.Hi != b.Hi)
         return fail(c, "wins[%d] and wins[%d]: frames overlap in memory without being the same frame", i, j);
-      if (a.y0 < b.y0 + H && b.y0 < a.y0 + H && a.x0 < b.x0 + W && b.x0 < a.x0 + W)
+      if (a.y0 < b.y0 + hs && b.y0 < a.y0 + hs && a.x0 < b.x0 + ws && b.x0 < a.x0 + ws)
         return fail(c, "wins[%d] and wins[%d] name overlapping windows of one frame", i, j);
     }
   return 0;
@@ -1741,12 +1752,117 @@ bool aligned_to(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1
 
 size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+// ---- window edits at a working size: the window resampled into the forward's inputs, the result resampled
+// back with the paste rule as the last pass's epilogue.  Both ends use the resize's tables (and so its one-stream order).
+
+// n coefficient tables (BICUBIC) at once.  A lookup that inserts may move the table vector, so everything is looked up a
+// second time: the n most recently used entries are not evicted (n <= 2 here, the cache holds 64).
+int rs_tables_n(se_ctx* c, int n, const int (*in_out)[2], const se_ctx::ResampleTable** out) {
+  for (int pass = 0; pass < 2; ++pass)
+    for (int i = 0; i < n; ++i)
+      if (!(out[i] = rs_table(c, in_out[i][0], in_out[i][1], SE_RESAMPLE_BICUBIC))) return 1;
+  return 0;
+}
+
+// pitch in pixels of the paste end's intermediates: rows start dword aligned
+int paste_pitch(int ws) { return (ws + 3) & ~3; }
+// intermediates of the two ends.  gather: (B,hs,W,3) uint8, reused for the sketch's (B,hs,W); paste: (B,H,P,3) and (B,H,P)
+size_t gather_mid_bytes(int B, int hs, int W) { return pad256((size_t)B * hs * W * 3); }
+size_t paste_mid_bytes(int B, int H, int ws) { return pad256((size_t)B * H * paste_pitch(ws) * 3) + pad256((size_t)B * H * paste_pitch(ws)); }
+
+// the hs x ws windows -> the forward's fp32 inputs at H x W (not both equal).  The horizontal pass always runs: where ws == W
+// its table is the identity (one tap of weight 1), which copies the window's rows as Pillow's skipped pass would.
+int gather_resize_locked(se_ctx* c, hipStream_t st, const se_window* d, int B, int hs, int ws, int H, int W, float* image,
+                         float* sketch, unsigned char* mid) {
+  const bool need_v = hs != H;
+  const int io[2][2] = {{ws, W}, {hs, H}};
+  const se_ctx::ResampleTable* t[2] = {nullptr, nullptr};
+  if (rs_tables_n(c, need_v ? 2 : 1, io, t)) return 1;
+  for (int C = 3; C >= 1; C -= 2) {
+    float* out = C == 3 ? image : sketch;
+    if (!out) continue;
+    ResizeOut o{C == 3 ? RESIZE_OUT_IMAGE_F32 : RESIZE_OUT_SKETCH_F32, nullptr, out, c->lut8, H, W};
+    ResizeOut oh = o;
+    if (need_v) { oh.mode = RESIZE_OUT_U8; oh.u8 = mid; oh.H = hs; }
+    HIPCHK(c, launch_window_resample_h(d, t[0]->dev, t[0]->dev + 2 * (size_t)W, t[0]->host.data(), t[0]->ksize, B, hs, ws, W, C, oh, st));
+    if (need_v) HIPCHK(c, launch_resample_v(mid, t[1]->dev, t[1]->dev + 2 * (size_t)H, t[1]->ksize, B, hs, H, W, C, o, st));
+  }
+  return 0;
+}
+
+// rgb (B,H,W,3), m8 (B,H,W) -> resampled to hs x ws and pasted into the windows (not both sizes equal).  The vertical pass
+// always runs (it carries the paste): where hs == H its table is the identity.
+int paste_resize_locked(se_ctx* c, hipStream_t st, const se_window* d, int B, int hs, int ws, int H, int W, const unsigned char* rgb,
+                        const unsigned char* m8, unsigned char* mid) {
+  const bool need_h = ws != W;
+  const int io[2][2] = {{H, hs}, {W, ws}};
+  const se_ctx::ResampleTable* t[2] = {nullptr, nullptr};
+  if (rs_tables_n(c, need_h ? 2 : 1, io, t)) return 1;
+  int P = W;
+  if (need_h) {
+    P = paste_pitch(ws);
+    unsigned char* mid_rgb = mid;
+    unsigned char* mid_m = mid + pad256((size_t)B * H * P * 3);
+    const int* dk = t[1]->dev;
+    ResizeOut o{RESIZE_OUT_U8, mid_rgb, nullptr, nullptr, H, P};      // (o.W is the row pitch of what the pass writes)
+    HIPCHK(c, launch_resample_h(rgb, dk, dk + 2 * (size_t)ws, t[1]->host.data(), t[1]->ksize, B, H, W, ws, 3, o, st));
+    o.u8 = mid_m;
+    HIPCHK(c, launch_resample_h(m8, dk, dk + 2 * (size_t)ws, t[1]->host.data(), t[1]->ksize, B, H, W, ws, 1, o, st));
+    rgb = mid_rgb; m8 = mid_m;
+  }
+  HIPCHK(c, launch_window_paste_v(d, rgb, m8, t[0]->dev, t[0]->dev + 2 * (size_t)hs, t[0]->ksize, B, H, hs, P, ws, st));
+  return 0;
+}
+
+// [uint8 result | uint8 mask | counts | intermediates of the resample ends (scaled only) | the workspace of se_inference_u8io:
+// arenas, masks, fp32 image and sketch at its end].  hs x ws == H x W: the window edit at the frame's own resolution.
+int edit_window_locked(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W, unsigned char* rgb_out,
+                       unsigned char* mask_u8_out, int* hits_out, int commit, void* wsp, size_t ws_bytes, int flags) {
+  const bool scaled = hs != H || ws != W;
+  if (win_check(c, wins, B, H, W, hs, ws, true, commit != 0)) return 1;
+  if (!wsp) return fail(c, "null pointer argument: workspace");
+  if (!aligned_to(wsp, 256)) return fail(c, "workspace must be 256-byte aligned");
+  if (!aligned_to(rgb_out, 4) || !aligned_to(mask_u8_out, 4) || !aligned_to(hits_out, 4)) return fail(c, "rgb_out / mask_u8_out / hits_out must be 4-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
+  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  const size_t plane = pad256((size_t)B * H * W * 4), rgbw = pad256((size_t)B * H * W * 3), mw = pad256((size_t)B * H * W),
+               hw = pad256((size_t)B * 4 * sizeof(int)),
+               midw = scaled ? std::max(gather_mid_bytes(B, hs, W), paste_mid_bytes(B, H, ws)) : 0;
+  if (ws_bytes < rgbw + mw + hw + midw + 6 * plane) return fail(c, "workspace too small: %zu bytes", ws_bytes);
+  unsigned char* rgb = rgb_out ? rgb_out : (unsigned char*)wsp;
+  unsigned char* m8 = mask_u8_out ? mask_u8_out : (unsigned char*)wsp + rgbw;
+  int* hits = hits_out ? hits_out : (int*)((char*)wsp + rgbw + mw);
+  unsigned char* mid = (unsigned char*)wsp + rgbw + mw + hw;
+  char* fws = (char*)wsp + rgbw + mw + hw + midw;
+  const size_t fws_bytes = ws_bytes - (rgbw + mw + hw + midw);
+  float* image = (float*)(fws + fws_bytes - 4 * plane);      // where se_inference_u8io keeps them
+  float* sketch = (float*)(fws + fws_bytes - plane);
+  if (!aligned_to(image, 16)) return fail(c, "workspace_bytes must be a multiple of 16");
+  const hipStream_t st = (hipStream_t)stream;
+  if (scaled && rs_enter(c, st)) return 1;
+  set_profiler(&c->prof);
+  const se_window* d = win_put(c, st, wins, B);
+  if (!d) return 1;
+  if (scaled) {
+    if (gather_resize_locked(c, st, d, B, hs, ws, H, W, image, sketch, mid)) return 1;
+  } else {
+    HIPCHK(c, launch_window_gather(d, c->lut8, image, sketch, B, H, W, st));
+  }
+  if (inference_u8_locked(c, stream, image, sketch, rgb, m8, fws, fws_bytes, B, H, W, flags, 4)) return 1;
+  set_profiler(&c->prof);
+  HIPCHK(c, launch_window_border(d, m8, hits, B, H, W, hs, ws, st));
+  if (commit && scaled) return paste_resize_locked(c, st, d, B, hs, ws, H, W, rgb, m8, mid);
+  if (commit) HIPCHK(c, launch_window_paste(d, rgb, m8, B, H, W, st));
+  return 0;
+}
+
 }  // namespace
 
 int se_window_gather_u8(se_ctx* c, void* stream, const se_window* wins, int B, int H, int W, float* image_out, float* sketch_out) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (win_check(c, wins, B, H, W, sketch_out != nullptr, false)) return 1;
+  if (win_check(c, wins, B, H, W, H, W, sketch_out != nullptr, false)) return 1;
   if (!aligned_to(image_out, 16) || !aligned_to(sketch_out, 16)) return fail(c, "image_out / sketch_out must be 16-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));
   set_profiler(&c->prof);
@@ -1760,14 +1876,14 @@ int se_window_border_u8(se_ctx* c, void* stream, const se_window* wins, int B, i
                         int* hits_out) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (win_check(c, wins, B, H, W, false, false)) return 1;
+  if (win_check(c, wins, B, H, W, H, W, false, false)) return 1;
   if (!mask_u8 || !hits_out) return fail(c, "null pointer argument: mask_u8 / hits_out");
   if (!aligned_to(hits_out, 4)) return fail(c, "hits_out must be 4-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));
   set_profiler(&c->prof);
   const se_window* d = win_put(c, (hipStream_t)stream, wins, B);
   if (!d) return 1;
-  HIPCHK(c, launch_window_border(d, mask_u8, hits_out, B, H, W, (hipStream_t)stream));
+  HIPCHK(c, launch_window_border(d, mask_u8, hits_out, B, H, W, H, W, (hipStream_t)stream));
   return 0;
 }
 
@@ -1775,7 +1891,7 @@ int se_window_paste_u8(se_ctx* c, void* stream, const se_window* wins, int B, in
                        const unsigned char* mask_u8) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (win_check(c, wins, B, H, W, false, true)) return 1;
+  if (win_check(c, wins, B, H, W, H, W, false, true)) return 1;
   if (!rgb || !mask_u8) return fail(c, "null pointer argument: rgb / mask_u8");
   if (!aligned_to(rgb, 4) || !aligned_to(mask_u8, 4)) return fail(c, "rgb / mask_u8 must be 4-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));
@@ -1794,39 +1910,77 @@ size_t se_edit_window_u8_workspace_bytes(se_ctx* c, int B, int H, int W) {
   return fwd + pad256((size_t)B * H * W * 3) + pad256((size_t)B * H * W) + pad256((size_t)B * 4 * sizeof(int));
 }
 
-// [uint8 result | uint8 mask | counts | the workspace of se_inference_u8io: arenas, masks, fp32 image and sketch at its end]
 int se_edit_window_u8(se_ctx* c, void* stream, const se_window* wins, int B, int H, int W, unsigned char* rgb_out,
                       unsigned char* mask_u8_out, int* hits_out, int commit, void* ws, size_t ws_bytes, int flags) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (win_check(c, wins, B, H, W, true, commit != 0)) return 1;
-  if (!ws) return fail(c, "null pointer argument: workspace");
-  if (!aligned_to(ws, 256)) return fail(c, "workspace must be 256-byte aligned");
-  if (!aligned_to(rgb_out, 4) || !aligned_to(mask_u8_out, 4) || !aligned_to(hits_out, 4)) return fail(c, "rgb_out / mask_u8_out / hits_out must be 4-byte aligned");
+  return edit_window_locked(c, stream, wins, B, H, W, H, W, rgb_out, mask_u8_out, hits_out, commit, ws, ws_bytes, flags);
+}
+
+// ---- the same at a working size ---------------------------------------------------------------
+int se_window_gather_resize_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W, float* image_out,
+                               float* sketch_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (win_check(c, wins, B, H, W, hs, ws, sketch_out != nullptr, false)) return 1;
+  if (!aligned_to(image_out, 16) || !aligned_to(sketch_out, 16)) return fail(c, "image_out / sketch_out must be 16-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
-  const size_t plane = pad256((size_t)B * H * W * 4), rgbw = pad256((size_t)B * H * W * 3), mw = pad256((size_t)B * H * W),
-               hw = pad256((size_t)B * 4 * sizeof(int));
-  if (ws_bytes < rgbw + mw + hw + 6 * plane) return fail(c, "workspace too small: %zu bytes", ws_bytes);
-  unsigned char* rgb = rgb_out ? rgb_out : (unsigned char*)ws;
-  unsigned char* m8 = mask_u8_out ? mask_u8_out : (unsigned char*)ws + rgbw;
-  int* hits = hits_out ? hits_out : (int*)((char*)ws + rgbw + mw);
-  char* fws = (char*)ws + rgbw + mw + hw;
-  const size_t fws_bytes = ws_bytes - (rgbw + mw + hw);
-  float* image = (float*)(fws + fws_bytes - 4 * plane);      // where se_inference_u8io keeps them
-  float* sketch = (float*)(fws + fws_bytes - plane);
-  if (!aligned_to(image, 16)) return fail(c, "workspace_bytes must be a multiple of 16");
   const hipStream_t st = (hipStream_t)stream;
+  const bool scaled = hs != H || ws != W;
+  unsigned char* mid = nullptr;
+  if (scaled) {
+    if (rs_enter(c, st)) return 1;
+    if (hs != H && !(mid = rs_scratch(c, gather_mid_bytes(B, hs, W)))) return 1;
+  }
   set_profiler(&c->prof);
   const se_window* d = win_put(c, st, wins, B);
   if (!d) return 1;
-  HIPCHK(c, launch_window_gather(d, c->lut8, image, sketch, B, H, W, st));
-  if (inference_u8_locked(c, stream, image, sketch, rgb, m8, fws, fws_bytes, B, H, W, flags, 4)) return 1;
-  set_profiler(&c->prof);
-  HIPCHK(c, launch_window_border(d, m8, hits, B, H, W, st));
-  if (commit) HIPCHK(c, launch_window_paste(d, rgb, m8, B, H, W, st));
+  if (scaled) return gather_resize_locked(c, st, d, B, hs, ws, H, W, image_out, sketch_out, mid);
+  HIPCHK(c, launch_window_gather(d, c->lut8, image_out, sketch_out, B, H, W, st));
   return 0;
+}
+
+int se_window_paste_resize_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W,
+                              const unsigned char* rgb, const unsigned char* mask_u8) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (win_check(c, wins, B, H, W, hs, ws, false, true)) return 1;
+  if (!rgb || !mask_u8) return fail(c, "null pointer argument: rgb / mask_u8");
+  if (!aligned_to(rgb, 4) || !aligned_to(mask_u8, 4)) return fail(c, "rgb / mask_u8 must be 4-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = (hipStream_t)stream;
+  const bool scaled = hs != H || ws != W;
+  unsigned char* mid = nullptr;
+  if (scaled) {
+    if (rs_enter(c, st)) return 1;
+    if (ws != W && !(mid = rs_scratch(c, paste_mid_bytes(B, H, ws)))) return 1;
+  }
+  set_profiler(&c->prof);
+  const se_window* d = win_put(c, st, wins, B);
+  if (!d) return 1;
+  if (scaled) return paste_resize_locked(c, st, d, B, hs, ws, H, W, rgb, mask_u8, mid);
+  HIPCHK(c, launch_window_paste(d, rgb, mask_u8, B, H, W, st));
+  return 0;
+}
+
+size_t se_edit_window_scaled_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws, int H, int W) {
+  if (!c) return 0;
+  const size_t base = se_edit_window_u8_workspace_bytes(c, B, H, W);
+  if (!base) return 0;
+  if (hs < 16 || ws < 16) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    fail(c, "bad window hs=%d ws=%d (a window is at least 16 x 16 frame pixels)", hs, ws);
+    return 0;
+  }
+  return base + ((hs != H || ws != W) ? std::max(gather_mid_bytes(B, hs, W), paste_mid_bytes(B, H, ws)) : 0);
+}
+
+int se_edit_window_scaled_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W,
+                             unsigned char* rgb_out, unsigned char* mask_u8_out, int* hits_out, int commit, void* workspace,
+                             size_t workspace_bytes, int flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return edit_window_locked(c, stream, wins, B, hs, ws, H, W, rgb_out, mask_u8_out, hits_out, commit, workspace, workspace_bytes, flags);
 }
 
 // ---- measurement support (bench.py): per-kernel HIP-event timing ---------------------------------

@@ -17,7 +17,8 @@ namespace se {
 // ---------------------------------------------------------------------------------------------
 enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL_WINO_N192, PL_WINO_N96, PL_WINO_UP96, PL_SMALL_CONV, PL_PACK, PL_COLREDUCE,
                  PL_ATT_PREP, PL_ATT_SCORE, PL_ATT_SOFTMAX, PL_ATT_BOXSUM, PL_ATT_PV, PL_LAYOUT,
-                 PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_WINDOW_GATHER, PL_WINDOW_BORDER, PL_WINDOW_PASTE, PL_COUNT };
+                 PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_WINDOW_GATHER, PL_WINDOW_BORDER, PL_WINDOW_PASTE,
+                 PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -364,6 +365,16 @@ hipError_t launch_resample_h(const unsigned char* in, const int* d_bounds, const
 // vertical pass: (B, Hin, W, C) -> (B, Hout, W, C)
 hipError_t launch_resample_v(const unsigned char* in, const int* d_bounds, const int* d_kk, int ksize, int B, int Hin, int Hout,
                              int W, int C, const ResizeOut& o, hipStream_t st);
+// the ends of a scaled window edit; d_wins = B se_window records in DEVICE memory, as below.
+// gather end: the horizontal pass with its rows taken from the hs x ws windows of the frames (C == 3) or from the requests'
+// contiguous (hs, ws) window sketches (C == 1) -> (B, hs, Wout, C) as `o` says; reads no byte outside a window's own rows
+hipError_t launch_window_resample_h(const se_window* d_wins, const int* d_bounds, const int* d_kk, const int* h_bounds, int ksize,
+                                    int B, int hs, int ws, int Wout, int C, const ResizeOut& o, hipStream_t st);
+// paste end: the vertical pass Hin -> hs of rgb (B,Hin,P,3) and m8 (B,Hin,P) (row pitch P pixels, P % 4 == 0, P >= ws, both
+// 4-byte aligned) with the paste rule as its epilogue: frame[y0 + y, x0 + x, :] = the resampled colour where the resampled
+// mask byte is > 0, every other byte of the frame untouched
+hipError_t launch_window_paste_v(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, const int* d_bounds,
+                                 const int* d_kk, int ksize, int B, int Hin, int hs, int P, int ws, hipStream_t st);
 // largest tap count the kernels take (48 KiB of LDS per block): a bicubic downscale by more than ~2000x is refused
 constexpr int RESAMPLE_MAX_KSIZE = 8191;
 
@@ -374,8 +385,10 @@ constexpr int RESAMPLE_MAX_KSIZE = 8191;
 // outputs 16-byte aligned
 hipError_t launch_window_gather(const se_window* d_wins, const float* lut, float* image, float* sketch, int B, int H, int W,
                                 hipStream_t st);
-// m8 (B,H,W) -> hits (B,4): pixels >= 128 on the window's top / bottom / left / right edge, 0 for an edge of the frame itself
-hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8, int* hits, int B, int H, int W, hipStream_t st);
+// m8 (B,H,W) -> hits (B,4): pixels >= 128 on the mask's top / bottom / left / right edge, 0 for a side on which the hs x ws
+// frame-space window lies on the frame's own edge (hs x ws == H x W unless the edit runs at a working size)
+hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8, int* hits, int B, int H, int W, int hs, int ws,
+                                hipStream_t st);
 // frame[y0 + y, x0 + x, :] = rgb[b, y, x, :] where m8[b, y, x] > 0; rgb (B,H,W,3) and m8 (B,H,W) 4-byte aligned, W % 4 == 0
 hipError_t launch_window_paste(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, int B, int H, int W,
                                hipStream_t st);

@@ -14,7 +14,11 @@
 // ctx's dequantisation table (the one se_dequantize_u8 uses, bit-identical to (v/255 - 0.5)/0.5) and the sketch as
 // (v > 0) in {0, 1}.
 //
-// Both kernels are memory-bound (a few int multiply-adds per byte).  The coefficients of a block's outputs are staged
+// A window edit at a working size uses the same passes with two fused ends: window_resample_h_kernel is the
+// horizontal pass with its rows taken from the frames' windows (no crop copy), window_paste_v_kernel the vertical pass of the
+// way back whose epilogue is the paste rule of se_window.hip (no full-size result is ever written).
+//
+// The kernels are memory-bound (a few int multiply-adds per byte).  The coefficients of a block's outputs are staged
 // in LDS; the vertical pass treats an output row as a flat byte string (every channel of a row shares the row's weights)
 // and moves 16 bytes per lane with the widest loads the alignment allows; the horizontal pass stages the input span of
 // its rows in LDS with dword loads where its LDS budget allows it, and reads global memory directly otherwise.
@@ -133,12 +137,31 @@ __device__ __forceinline__ void store_px(const ResizeOut& o, int b, int y, int x
     o.f32[(((size_t)b * C + c) * o.H + y) * o.W + x] = v ? 1.f : 0.f;
 }
 
-// Horizontal pass: in (B, Hrows, Win, C) -> (B, Hrows, Wout, C).  A block = TX output columns x TY rows, one output pixel
-// per thread.  LDS: [TX * ksize] weights, [TX] (first tap, tap count), then (staged) TY rows of `span` input bytes.
+// Where the horizontal pass finds its input rows.  Contiguous: the (B, Hrows, Win, C) array.  Window: row r of
+// request b is a row of that request's WINDOW -- C == 3: the frame's bytes from 3 ((y0 + r) Wi + x0), any alignment, pitch
+// 3 Wi; C == 1: the window's own contiguous (hs, ws) sketch.  The pass touches a row's bytes [first tap, last tap] only
+// (columns of the window), so nothing outside the window is read.
+struct ContiguousRows {
+  const unsigned char* in;
+  size_t plane, pitch;
+  __device__ __forceinline__ const unsigned char* row(int b, int y) const { return in + b * plane + (size_t)y * pitch; }
+};
 template <int C>
-__global__ void __launch_bounds__(256) resample_h_kernel(const unsigned char* __restrict__ in, const int* __restrict__ bounds,
-                                                         const int* __restrict__ kk, int ksize, int Hrows, int Win, int Wout,
-                                                         int TX, int TY, int span, ResizeOut o) {
+struct WindowRows {
+  const se_window* wins;
+  int ws;
+  __device__ __forceinline__ const unsigned char* row(int b, int y) const {
+    const se_window w = wins[b];
+    if (C == 3) return w.frame_u8 + ((size_t)(w.y0 + y) * w.Wi + w.x0) * 3;
+    return w.sketch_u8 + (size_t)y * ws;
+  }
+};
+
+// Horizontal pass: Hrows rows of Win pixels per request -> (B, Hrows, Wout, C).  A block = TX output columns x TY rows, one
+// output pixel per thread.  LDS: [TX * ksize] weights, [TX] (first tap, tap count), then (staged) TY rows of `span` input bytes.
+template <int C, class Rows>
+__device__ __forceinline__ void resample_h_body(const Rows in, const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
+                                                int Hrows, int Wout, int TX, int TY, int span, const ResizeOut& o) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int* coef = (int*)smem;
   int2* bnd = (int2*)(smem + ((TX * ksize * 4 + 15) & ~15));
@@ -150,13 +173,13 @@ __global__ void __launch_bounds__(256) resample_h_kernel(const unsigned char* __
   for (int i = tid; i < nx; i += nthr) bnd[i] = make_int2(bounds[2 * (x0 + i)], bounds[2 * (x0 + i) + 1]);
   // the block's input columns [p0, p1): first tap of its first output to the last tap of its last (both monotone in x)
   const int p0 = bounds[2 * x0], p1 = bounds[2 * (x0 + nx - 1)] + bounds[2 * (x0 + nx - 1) + 1];
-  const size_t plane = (size_t)Hrows * Win * C;
   if (span) {
-    // row r's bytes [p0 C, p1 C) land at rows[r * span + lead + j], lead = the address's offset within its dword, so that
-    // the dwords wholly inside the range are copied with dword loads and LDS writes; the partial ones byte by byte
+    // row r's bytes [p0 C, p1 C) land at rows[r * span + lead + j], lead = the address's offset within its dword (per row:
+    // rows of a window differ), so that the dwords wholly inside the range are copied with dword loads and LDS writes; the
+    // partial ones byte by byte
     const int nb = (p1 - p0) * C;
     for (int r = 0; r < TY && y0 + r < Hrows; ++r) {
-      const unsigned char* g = in + b * plane + (size_t)(y0 + r) * Win * C + (size_t)p0 * C;
+      const unsigned char* g = in.row(b, y0 + r) + (size_t)p0 * C;
       const int lead = (int)((uintptr_t)g & 3);
       unsigned char* l = rows + r * span;
       const int head = lead ? min(4 - lead, nb) : 0;      // bytes before the first whole dword
@@ -178,10 +201,10 @@ __global__ void __launch_bounds__(256) resample_h_kernel(const unsigned char* __
   const int2 bd = bnd[tx];
   const unsigned char* src;
   if (span) {
-    const unsigned char* g = in + b * plane + (size_t)y * Win * C + (size_t)p0 * C;
+    const unsigned char* g = in.row(b, y) + (size_t)p0 * C;
     src = rows + ty * span + (int)((uintptr_t)g & 3) + (bd.x - p0) * C;
   } else {
-    src = in + b * plane + ((size_t)y * Win + bd.x) * C;
+    src = in.row(b, y) + (size_t)bd.x * C;
   }
   const int* k = coef + tx * ksize;
   int acc[C];
@@ -194,6 +217,22 @@ __global__ void __launch_bounds__(256) resample_h_kernel(const unsigned char* __
   }
 #pragma unroll
   for (int c = 0; c < C; ++c) store_px(o, b, y, xx, c, C, clip8(acc[c]));
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) resample_h_kernel(const unsigned char* __restrict__ in, const int* __restrict__ bounds,
+                                                         const int* __restrict__ kk, int ksize, int Hrows, int Win, int Wout,
+                                                         int TX, int TY, int span, ResizeOut o) {
+  resample_h_body<C>(ContiguousRows{in, (size_t)Hrows * Win * C, (size_t)Win * C}, bounds, kk, ksize, Hrows, Wout, TX, TY, span, o);
+}
+
+// The gather end of a scaled window edit: the same pass with its rows taken straight from the frames (C == 3) or from the
+// requests' window sketches (C == 1) -- no contiguous crop is ever made.
+template <int C>
+__global__ void __launch_bounds__(256) window_resample_h_kernel(const se_window* __restrict__ wins, const int* __restrict__ bounds,
+                                                                const int* __restrict__ kk, int ksize, int hs, int ws, int Wout,
+                                                                int TX, int TY, int span, ResizeOut o) {
+  resample_h_body<C>(WindowRows<C>{wins, ws}, bounds, kk, ksize, hs, Wout, TX, TY, span, o);
 }
 
 // Vertical pass: in (B, Hin, RB bytes) -> (B, Hout, RB), RB = W * C; every byte of an output row takes the row's weights.
@@ -264,12 +303,79 @@ __global__ void __launch_bounds__(256) resample_v_kernel(const unsigned char* __
   }
 }
 
+// The paste end of a scaled window edit: the vertical pass of the resize back to the frame-space window, whose epilogue is
+// the paste rule of se_window.hip.  rgb (B, Hin, P, 3) and m8 (B, Hin, P): the working-size result after the horizontal pass,
+// P = the row pitch in pixels, a multiple of 4 >= ws (columns >= ws are never used).  One lane = 4 consecutive pixels of row
+// yy of the hs x ws window: the mask's column first -- four pixels that all resample to 0 are left without reading a colour
+// byte -- then the twelve colour bytes.  frame[y0 + yy, x0 + x, :] is written only where the resampled mask byte is > 0:
+// whole dwords where all four pixels are selected and the address allows it, single bytes otherwise, so a lane never
+// rewrites a byte it does not own (concurrent lanes and disjoint windows of other requests on the frame do not race).
+__global__ void __launch_bounds__(64) window_paste_v_kernel(const se_window* __restrict__ wins, const unsigned char* __restrict__ rgb,
+                                                            const unsigned char* __restrict__ m8, const int* __restrict__ bounds,
+                                                            const int* __restrict__ kk, int ksize, int Hin, int P, int ws) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int* coef = (int*)smem;
+  const int yy = blockIdx.y, b = blockIdx.z;
+  const int ymin = bounds[2 * yy], n = bounds[2 * yy + 1];
+  for (int i = threadIdx.x; i < n; i += blockDim.x) coef[i] = kk[(size_t)yy * ksize + i];
+  __syncthreads();
+  const int x = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (x >= ws) return;
+  const size_t first = ((size_t)b * Hin + ymin) * P + x;      // the lane's first tap, in pixels
+  int am[4] = {kRoundOne, kRoundOne, kRoundOne, kRoundOne};
+  for (int t = 0; t < n; ++t) {
+    const unsigned d = *(const unsigned*)(m8 + first + (size_t)t * P);
+    const int w = coef[t];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) am[e] += (int)((d >> (8 * e)) & 255u) * w;
+  }
+  bool sel[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) sel[p] = x + p < ws && clip8(am[p]) > 0;
+  if (!(sel[0] || sel[1] || sel[2] || sel[3])) return;
+  int acc[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) acc[e] = kRoundOne;
+  const unsigned char* src = rgb + first * 3;
+  for (int t = 0; t < n; ++t) {
+    const unsigned* s = (const unsigned*)(src + (size_t)t * P * 3);
+    const unsigned d[3] = {s[0], s[1], s[2]};
+    const int w = coef[t];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) acc[e] += (int)((d[e >> 2] >> (8 * (e & 3))) & 255u) * w;
+  }
+  const se_window w = wins[b];
+  unsigned char* dst = w.frame_u8 + ((size_t)(w.y0 + yy) * w.Wi + w.x0 + x) * 3;
+  if (sel[0] && sel[1] && sel[2] && sel[3] && ((uintptr_t)dst & 3) == 0) {
+    unsigned* d = (unsigned*)dst;
+    d[0] = pack4(acc[0], acc[1], acc[2], acc[3]);
+    d[1] = pack4(acc[4], acc[5], acc[6], acc[7]);
+    d[2] = pack4(acc[8], acc[9], acc[10], acc[11]);
+    return;
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    if (sel[p]) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dst[3 * p + c] = clip8(acc[3 * p + c]);
+    }
+  }
+}
+
 bool aligned(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }
 
 }  // namespace
 
-hipError_t launch_resample_h(const unsigned char* in, const int* d_bounds, const int* d_kk, const int* h_bounds, int ksize,
-                             int B, int Hrows, int Win, int Wout, int C, const ResizeOut& o, hipStream_t st) {
+namespace {
+
+// the block shape of a horizontal pass: TX outputs x TY rows, `span` staged bytes per row (0: rows read from global memory)
+struct HShape {
+  int TX, TY, span;
+  size_t lds;
+  dim3 grid;
+};
+
+bool resample_h_shape(const int* h_bounds, int ksize, int B, int Hrows, int Wout, int C, HShape* s) {
   int TX = 64;
   while (TX > 1 && TX / 2 >= Wout) TX /= 2;
   auto coef_lds = [ksize](int tx) { return ((tx * ksize * 4 + 15) & ~15) + ((tx * 8 + 15) & ~15); };
@@ -283,17 +389,53 @@ hipError_t launch_resample_h(const unsigned char* in, const int* d_bounds, const
   }
   int span = (span_max + 3 + 15) & ~15;
   if (coef_bytes + TY * span > kLdsBudget) span = 0;       // rows read from global memory directly
-  if (coef_bytes > kLdsBudget) return hipErrorInvalidValue;    // (the caller refuses such tap counts first)
-  const size_t lds = coef_bytes + (size_t)TY * span;
-  const dim3 grid((unsigned)((Wout + TX - 1) / TX), (unsigned)((Hrows + TY - 1) / TY), (unsigned)B);
+  if (coef_bytes > kLdsBudget) return false;                 // (the caller refuses such tap counts first)
+  s->TX = TX; s->TY = TY; s->span = span;
+  s->lds = coef_bytes + (size_t)TY * span;
+  s->grid = dim3((unsigned)((Wout + TX - 1) / TX), (unsigned)((Hrows + TY - 1) / TY), (unsigned)B);
+  return true;
+}
+
+}  // namespace
+
+hipError_t launch_resample_h(const unsigned char* in, const int* d_bounds, const int* d_kk, const int* h_bounds, int ksize,
+                             int B, int Hrows, int Win, int Wout, int C, const ResizeOut& o, hipStream_t st) {
+  HShape s;
+  if (!resample_h_shape(h_bounds, ksize, B, Hrows, Wout, C, &s)) return hipErrorInvalidValue;
   // bytes: every input byte read once, every output element written once (fp32 outputs: 4 bytes)
   set_launch_cost(0.0, (double)B * Hrows * C * (Win + (o.mode == RESIZE_OUT_U8 ? 1.0 : 4.0) * Wout), "resize_h");
-  set_launch_grid((long)grid.x * grid.y * grid.z);
+  set_launch_grid((long)s.grid.x * s.grid.y * s.grid.z);
   ProfScope ps_(st, PL_RESIZE_H);
   if (C == 3)
-    hipLaunchKernelGGL(resample_h_kernel<3>, grid, dim3(TX * TY), lds, st, in, d_bounds, d_kk, ksize, Hrows, Win, Wout, TX, TY, span, o);
+    hipLaunchKernelGGL(resample_h_kernel<3>, s.grid, dim3(s.TX * s.TY), s.lds, st, in, d_bounds, d_kk, ksize, Hrows, Win, Wout, s.TX, s.TY, s.span, o);
   else
-    hipLaunchKernelGGL(resample_h_kernel<1>, grid, dim3(TX * TY), lds, st, in, d_bounds, d_kk, ksize, Hrows, Win, Wout, TX, TY, span, o);
+    hipLaunchKernelGGL(resample_h_kernel<1>, s.grid, dim3(s.TX * s.TY), s.lds, st, in, d_bounds, d_kk, ksize, Hrows, Win, Wout, s.TX, s.TY, s.span, o);
+  return hipGetLastError();
+}
+
+hipError_t launch_window_resample_h(const se_window* d_wins, const int* d_bounds, const int* d_kk, const int* h_bounds, int ksize,
+                                    int B, int hs, int ws, int Wout, int C, const ResizeOut& o, hipStream_t st) {
+  HShape s;
+  if (!resample_h_shape(h_bounds, ksize, B, hs, Wout, C, &s)) return hipErrorInvalidValue;
+  set_launch_cost(0.0, (double)B * hs * C * (ws + (o.mode == RESIZE_OUT_U8 ? 1.0 : 4.0) * Wout), "window_resample_h");
+  set_launch_grid((long)s.grid.x * s.grid.y * s.grid.z);
+  ProfScope ps_(st, PL_WINDOW_RESAMPLE_H);
+  if (C == 3)
+    hipLaunchKernelGGL(window_resample_h_kernel<3>, s.grid, dim3(s.TX * s.TY), s.lds, st, d_wins, d_bounds, d_kk, ksize, hs, ws, Wout, s.TX, s.TY, s.span, o);
+  else
+    hipLaunchKernelGGL(window_resample_h_kernel<1>, s.grid, dim3(s.TX * s.TY), s.lds, st, d_wins, d_bounds, d_kk, ksize, hs, ws, Wout, s.TX, s.TY, s.span, o);
+  return hipGetLastError();
+}
+
+hipError_t launch_window_paste_v(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, const int* d_bounds,
+                                 const int* d_kk, int ksize, int B, int Hin, int hs, int P, int ws, hipStream_t st) {
+  if (((ksize * 4 + 15) & ~15) > kLdsBudget || (P & 3) || P < ws || !aligned(rgb, 4) || !aligned(m8, 4)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((ws + 4 * 64 - 1) / (4 * 64)), (unsigned)hs, (unsigned)B);
+  // bytes: an upper bound (every pixel selected): the taps of mask and colour read, the frame's window written
+  set_launch_cost(0.0, (double)B * ws * 4.0 * Hin + (double)B * hs * ws * 3.0, "window_paste_v");
+  set_launch_grid((long)grid.x * grid.y * grid.z);
+  ProfScope ps_(st, PL_WINDOW_PASTE_V);
+  hipLaunchKernelGGL(window_paste_v_kernel, grid, dim3(64), (size_t)((ksize * 4 + 15) & ~15), st, d_wins, rgb, m8, d_bounds, d_kk, ksize, Hin, P, ws);
   return hipGetLastError();
 }
 

@@ -81,12 +81,13 @@ __global__ void __launch_bounds__(256) window_gather_kernel(const se_window* __r
 
 // One wave per (side, request): the lanes walk the edge 64 pixels at a time, a shuffle reduction adds their counts and lane 0
 // stores the total (a plain vector store: every count is written on every call, nothing to zero beforehand).
-// side 0 top, 1 bottom, 2 left, 3 right.
+// side 0 top, 1 bottom, 2 left, 3 right.  The mask is H x W; the window it stands for covers hs x ws frame pixels (the same
+// unless the edit ran at a working size), and that extent decides which sides lie on the frame's own edge.
 __global__ void __launch_bounds__(64) window_border_kernel(const se_window* __restrict__ wins, const unsigned char* __restrict__ m8,
-                                                           int* __restrict__ hits, int H, int W) {
+                                                           int* __restrict__ hits, int H, int W, int hs, int ws) {
   const int side = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
   const se_window w = wins[b];
-  const bool on_frame_edge = side == 0 ? w.y0 == 0 : side == 1 ? w.y0 + H == w.Hi : side == 2 ? w.x0 == 0 : w.x0 + W == w.Wi;
+  const bool on_frame_edge = side == 0 ? w.y0 == 0 : side == 1 ? w.y0 + hs == w.Hi : side == 2 ? w.x0 == 0 : w.x0 + ws == w.Wi;
   int n = 0;
   if (!on_frame_edge) {
     const unsigned char* m = m8 + (size_t)b * H * W;
@@ -148,11 +149,12 @@ hipError_t launch_window_gather(const se_window* d_wins, const float* lut, float
   return hipGetLastError();
 }
 
-hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8, int* hits, int B, int H, int W, hipStream_t st) {
+hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8, int* hits, int B, int H, int W, int hs, int ws,
+                                hipStream_t st) {
   set_launch_cost(0.0, (double)B * (2.0 * W + 2.0 * H + 16.0), "window_border");
   set_launch_grid(4L * B);
   ProfScope ps_(st, PL_WINDOW_BORDER);
-  hipLaunchKernelGGL(window_border_kernel, dim3(4, (unsigned)B), dim3(64), 0, st, d_wins, m8, hits, H, W);
+  hipLaunchKernelGGL(window_border_kernel, dim3(4, (unsigned)B), dim3(64), 0, st, d_wins, m8, hits, H, W, hs, ws);
   return hipGetLastError();
 }
 

@@ -25,6 +25,9 @@ KERNEL_LABELS = {
     "small_conv_kernel": "small_conv", "pack_": "pack", "colreduce": "colreduce", "vecbias_kernel": "colreduce",
     "nchw_to_nhwc": "layout", "nhwc_to_nchw": "layout", "nhwc16_to_nchw": "layout", "quantize_u8_kernel": "layout",
     "dequant_u8_kernel": "layout",
+    # the ends of a window edit at a working size (se_resize.hip; before the plain resize names: first matching prefix wins)
+    "(anonymous namespace)::window_resample_h_kernel": "window_resample_h", "(anonymous namespace)::window_paste_v_kernel": "window_paste_v",
+    "window_resample_h_kernel": "window_resample_h", "window_paste_v_kernel": "window_paste_v",
     # the demo's per-request resizes (se_resize.hip)
     "(anonymous namespace)::resample_h_kernel": "resize_h", "(anonymous namespace)::resample_v_kernel": "resize_v",
     "resample_h_kernel": "resize_h", "resample_v_kernel": "resize_v",

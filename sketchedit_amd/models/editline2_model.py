@@ -130,18 +130,26 @@ class EditLine2Model(torch.nn.Module):
                                                                low_latency))
         return rgb[0] if single else rgb
 
-    def edit_window_u8(self, frames, origins, sketches, H, W, commit=True, low_latency=None):
+    def edit_window_u8(self, frames, origins, sketches, H, W, commit=True, low_latency=None, work_hw=None):
         """A window edit of resident frames (no reference counterpart; DESIGN.md 6d, serve.EditSession is the caller-facing
         form): frames[i] (Hi,Wi,3) uint8 ON THE DEVICE, edited in place; origins[i] = (y0, x0) of the H x W window;
         sketches[i] the window's (H,W) uint8 sketch (array or tensor; uploaded here).  The result is this model's inference
         on the contiguous crop, pasted where its uint8 mask is > 0 (commit).  -> (rgb (B,H,W,3), mask_u8 (B,H,W), hits (B,4)
-        int32) on the device.  `low_latency` as in forward, by the size of the forward: B windows of H x W."""
+        int32) on the device.  `low_latency` as in forward, by the size of the forward: B windows of H x W.
+        work_hw = (Hw, Ww): the forward runs at that working size instead -- the window (any H, W >= 16) is
+        resampled into it and the result and its mask are resampled back before the paste, all Pillow's BICUBIC bit for
+        bit; rgb and mask_u8 are then returned at the working size, and the mode follows B forwards of Hw x Ww."""
         if self.training:
             raise NotImplementedError("call model.eval() first: only the eval branch of generate_fake exists here")
         dev = torch.device("cuda", self.opt.gpu_ids[0])
         sks = [_lib.upload_u8(s, dev) for s in sketches]
+        flags = _lib.flags_from_opt(self.opt)
         with torch.no_grad():
-            return self.engine().edit_window_u8(frames, origins, sks, H, W, _lib.flags_from_opt(self.opt), commit=commit,
+            if work_hw is not None:
+                Hw, Ww = (int(v) for v in work_hw)
+                return self.engine().edit_window_scaled_u8(frames, origins, sks, (H, W), Hw, Ww, flags, commit=commit,
+                                                           low_latency=self._mode_for(len(frames), Hw, Ww, low_latency))
+            return self.engine().edit_window_u8(frames, origins, sks, H, W, flags, commit=commit,
                                                 low_latency=self._mode_for(len(frames), H, W, low_latency))
 
     def forward(self, data, mode, low_latency=None):

@@ -131,6 +131,26 @@ def choose_window(bbox, frame_hw, margin=0.5, bucket=64, min_side=256):
     return y0, x0, h, w
 
 
+def choose_working_size(window_hw, max_side):
+    """The working size (H, W) the forward of a window edit runs at (pure host arithmetic).  `window_hw` =
+    (hs, ws), the window's extent in the frame, each >= 16.  If max(hs, ws) <= max_side the window is only floored to
+    multiples of 8; otherwise both sides are scaled by max_side / max(hs, ws), floored to multiples of 8 and kept at
+    least 16 -- the aspect ratio is preserved up to that flooring.  Never upscales.
+    `max_side` is a policy, not a measurement: it bounds an edit's cost whatever the sketch's extent.  The reference demo
+    resamples every request to at most 640 on a side (demo.py `max_size = 640`), which is the obvious value to offer;
+    nothing here measures what it does to the result."""
+    hs, ws = int(window_hw[0]), int(window_hw[1])
+    max_side = int(max_side)
+    if hs < 16 or ws < 16:
+        raise ValueError("window too small: %dx%d" % (ws, hs))
+    if max_side < 16:
+        raise ValueError("max_side must be at least 16: %r" % (max_side,))
+    long_side = max(hs, ws)
+    if long_side <= max_side:
+        return hs // 8 * 8, ws // 8 * 8
+    return max(hs * max_side // long_side // 8 * 8, 16), max(ws * max_side // long_side // 8 * 8, 16)
+
+
 class _ModelBackend:
     """The device side of an editing session: an EditLine2Model's engine and torch for the copies.  (A seam: the host
     logic of EditSession and of the window batcher is tested against a scripted stand-in.)"""
@@ -155,6 +175,15 @@ class _ModelBackend:
 
     def paste(self, frames, origins, rgb, m8):
         self.model.engine().window_paste_u8(frames, origins, rgb, m8)
+
+    def run_scaled(self, frames, origins, sketches, window_hw, work_hw, commit, low_latency):
+        """`run` with the forward at the working size `work_hw`: rgb and mask_u8 come back at that size"""
+        rgb, m8, hits = self.model.edit_window_u8(frames, origins, sketches, window_hw[0], window_hw[1], commit=commit,
+                                                  low_latency=low_latency, work_hw=work_hw)
+        return rgb, m8, hits.cpu().tolist()
+
+    def paste_scaled(self, frames, origins, window_hw, rgb, m8):
+        self.model.engine().window_paste_resize_u8(frames, origins, window_hw, rgb, m8)
 
     def select(self, t, idx):
         """rows `idx` of a batch result as a contiguous batch"""
@@ -214,10 +243,11 @@ class EditSession:
             raise ValueError("empty sketch: nothing to edit")
         return sk, bbox
 
-    def _check_window(self, window):
+    def _check_window(self, window, scaled=False):
+        """`scaled`: the forward runs at a working size, so the window's own sides need not be multiples of 8"""
         y0, x0, h, w = (int(v) for v in window)
         Hi, Wi = self.frame_hw
-        if h < 16 or w < 16 or h % 8 or w % 8 or y0 < 0 or x0 < 0 or y0 + h > Hi or x0 + w > Wi:
+        if h < 16 or w < 16 or (not scaled and (h % 8 or w % 8)) or y0 < 0 or x0 < 0 or y0 + h > Hi or x0 + w > Wi:
             raise ValueError("window %r: sides are multiples of 8, >= 16, and the window lies inside the %dx%d frame" % (window, Wi, Hi))
         return y0, x0, h, w
 
@@ -233,18 +263,25 @@ class EditSession:
             if nxt != window:
                 return nxt, margin
 
-    def edit(self, sketch, window=None, max_grow=2, low_latency=None):
+    def edit(self, sketch, window=None, max_grow=2, low_latency=None, max_side=None):
         """One edit.  `sketch`: the FULL-SIZE sketch (PIL 'L' / 2-D uint8 array, the frame's size).  The window is
         choose_window of the sketch's box, or `window` = (y0, x0, h, w) as given (then it never grows).  The forward runs on
         the window without committing; if its mask reaches an edge of the window (border counts, a side on the frame's own
         edge counts 0) and the window can still grow, the margin doubles and the edit is rerun on the larger window, at most
         `max_grow` times; then the result is pasted.  -> (patch, (x0, y0), info): `patch` (h,w,3) uint8 = the frame's window
         after the paste (the only download), its position, and info = dict(window=(y0, x0, h, w), counts=[top, bottom, left,
-        right], reruns=n, margin=m)."""
+        right], reruns=n, margin=m).
+        `max_side` (None: everything above, at the frame's own resolution): the forward runs at
+        choose_working_size(window, max_side) -- the window is resampled into it, the result and its mask are resampled
+        back and pasted where the resampled mask is > 0 -- so an edit's cost is bounded by `max_side` whatever the
+        sketch's extent.  The window is chosen and grown in frame space as before and the working size follows it; the
+        counts are those of the working-size mask; a given `window` then needs no multiple-of-8 sides; info gains
+        work=(H, W).  Still only the window's sketch goes up and only the window comes down."""
         sk, bbox = self._request(sketch)
         margin = 0.5
         fixed = window is not None
-        win = self._check_window(window) if fixed else choose_window(bbox, self.frame_hw, margin=margin)
+        scaled = max_side is not None
+        win = self._check_window(window, scaled) if fixed else choose_window(bbox, self.frame_hw, margin=margin)
         reruns = 0
         be = self.backend
         with self._lock:
@@ -254,15 +291,24 @@ class EditSession:
                 # a run whose counts cannot change anything commits at once: no round trip between forward and paste
                 commit = nxt is None
                 crop = be.upload(sk[y0:y0 + h, x0:x0 + w])
-                rgb, m8, counts = be.run([self._frame], [(y0, x0)], [crop], h, w, commit, low_latency)
+                if scaled:
+                    work = choose_working_size((h, w), max_side)
+                    rgb, m8, counts = be.run_scaled([self._frame], [(y0, x0)], [crop], (h, w), work, commit, low_latency)
+                else:
+                    rgb, m8, counts = be.run([self._frame], [(y0, x0)], [crop], h, w, commit, low_latency)
                 if commit or not any(counts[0]):
                     break
                 win, margin = nxt
                 reruns += 1
-            if not commit:
+            if not commit and scaled:
+                be.paste_scaled([self._frame], [(y0, x0)], (h, w), rgb, m8)
+            elif not commit:
                 be.paste([self._frame], [(y0, x0)], rgb, m8)
             patch = be.crop(self._frame, y0, x0, h, w)
-        return patch, (x0, y0), dict(window=win, counts=list(counts[0]), reruns=reruns, margin=margin)
+        info = dict(window=win, counts=list(counts[0]), reruns=reruns, margin=margin)
+        if scaled:
+            info["work"] = work
+        return patch, (x0, y0), info
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""
@@ -314,10 +360,12 @@ class BatchingServer:
     one forward, one border and one paste launch (Engine.edit_window_u8 / window_paste_u8).  Growing is per request: a
     request whose mask reaches its window's border is not pasted but queued again under its larger window's size (at most
     `max_grow` times); a group never holds two requests of one session (the second waits for the next group: it must
-    see the first's result)."""
+    see the first's result).  `max_side` (with window=True): every edit runs at
+    choose_working_size(window, max_side), as EditSession.edit(max_side=...) does; the group key is then
+    (hs, ws, H, W) and the mode policy goes by the working size, the size of the forward."""
 
     def __init__(self, model=None, max_batch=32, max_wait_s=0.005, models=None, mode_policy="pinned", device_io=False,
-                 window=False, max_grow=2):
+                 window=False, max_grow=2, max_side=None):
         if mode_policy not in ("pinned", "by_size"):
             raise ValueError(mode_policy)
         self.mode_policy = mode_policy
@@ -331,6 +379,9 @@ class BatchingServer:
         if self.window and (self.device_io or len(self.models) != 1):
             raise ValueError("window=True serves the sessions of ONE model (a session's frame lives on that model's GPU) and "
                              "has no device_io variant")
+        if max_side is not None and not self.window:
+            raise ValueError("max_side is the working-size cap of window edits: it needs window=True")
+        self.max_side = None if max_side is None else int(max_side)
         self.model = self.models[0]
         self._has_knob = [_accepts_low_latency(m) for m in self.models]
         self.max_batch, self.max_wait_s = max_batch, max_wait_s
@@ -345,13 +396,18 @@ class BatchingServer:
         for t in self._workers:
             t.start()
 
+    def _window_key(self, win):
+        """group key of a window: ("window", 3, h, w), with max_side ("window", 3, hs, ws, H, W) -- the forward's size last"""
+        key = ("window", 3, win[2], win[3])
+        return key if self.max_side is None else key + choose_working_size(win[2:], self.max_side)
+
     def _submit_window(self, session, sketch):
-        """key ("window", 3, h, w); request = dict(session, sketch, bbox, window, margin, reruns)"""
+        """key: _window_key; request = dict(session, sketch, bbox, window, margin, reruns)"""
         if session.model is not self.model:
             raise ValueError("the session belongs to another model than this server's")
         sk, bbox = session._request(sketch)
         win = choose_window(bbox, session.frame_hw)
-        return ("window", 3, win[2], win[3]), dict(session=session, sketch=sk, bbox=bbox, window=win, margin=0.5, reruns=0), None
+        return self._window_key(win), dict(session=session, sketch=sk, bbox=bbox, window=win, margin=0.5, reruns=0), None
 
     def submit(self, img, mask):
         arrays = _device_inputs(img, mask) if self.device_io and not self.window else None
@@ -431,7 +487,8 @@ class BatchingServer:
         was queued again under a larger window."""
         reqs = [q[1] for q in group]
         be = reqs[0]["session"].backend
-        _, _, h, w = group[0][0]
+        h, w = group[0][0][2:4]
+        work = group[0][0][4:6] if self.max_side is not None else None
         low_latency = self._mode(group[0][0]) if self._has_knob[k] else None
         grown = [None if r["reruns"] >= self.max_grow else r["session"]._grown(r["bbox"], r["window"], r["margin"]) for r in reqs]
         commit = all(g is None for g in grown)            # no request can grow: the counts decide nothing
@@ -442,16 +499,23 @@ class BatchingServer:
             lk.acquire()
         try:
             crops = [be.upload(r["sketch"][y0:y0 + h, x0:x0 + w]) for r, (y0, x0) in zip(reqs, origins)]
-            rgb, m8, counts = be.run(frames, origins, crops, h, w, commit, low_latency)
+            if work is not None:
+                rgb, m8, counts = be.run_scaled(frames, origins, crops, (h, w), work, commit, low_latency)
+            else:
+                rgb, m8, counts = be.run(frames, origins, crops, h, w, commit, low_latency)
             stay = [i for i in range(len(reqs)) if grown[i] is None or not any(counts[i])]
-            if not commit and stay:
+            if not commit and stay and work is not None:
+                be.paste_scaled([frames[i] for i in stay], [origins[i] for i in stay], (h, w), be.select(rgb, stay), be.select(m8, stay))
+            elif not commit and stay:
                 be.paste([frames[i] for i in stay], [origins[i] for i in stay], be.select(rgb, stay), be.select(m8, stay))
             outs = [None] * len(reqs)
             for i in stay:
                 r = reqs[i]
                 y0, x0 = origins[i]
-                outs[i] = (be.crop(frames[i], y0, x0, h, w), (x0, y0),
-                           dict(window=r["window"], counts=list(counts[i]), reruns=r["reruns"], margin=r["margin"]))
+                info = dict(window=r["window"], counts=list(counts[i]), reruns=r["reruns"], margin=r["margin"])
+                if work is not None:
+                    info["work"] = tuple(work)
+                outs[i] = (be.crop(frames[i], y0, x0, h, w), (x0, y0), info)
         finally:
             for _, lk in locks:
                 lk.release()
@@ -461,7 +525,7 @@ class BatchingServer:
                 r = dict(reqs[i])
                 r["window"], r["margin"] = grown[i]
                 r["reruns"] += 1
-                again.append((("window", 3, r["window"][2], r["window"][3]), r, None, q[3], q[4]))
+                again.append((self._window_key(r["window"]), r, None, q[3], q[4]))
         if again:
             with self._lock:
                 self._queue = again + self._queue     # in front: they are older than what arrived since, and their sessions' next edits wait for them
@@ -469,11 +533,12 @@ class BatchingServer:
         return outs
 
     def _mode(self, shape):
-        """Execution mode of a group of requests of working size `shape` (1,3,H,W) -- see the class docstring."""
+        """Execution mode of a group of requests of working size `shape` (1,3,H,W) -- see the class docstring.  (A group key
+        ends in the size its forward runs at: the window's, or the working size of a scaled window edit.)"""
         if self.mode_policy == "by_size":
             return None
         from ._lib import Engine
-        return Engine.is_low_latency(self.max_batch, shape[2], shape[3])
+        return Engine.is_low_latency(self.max_batch, shape[-2], shape[-1])
 
     def _run_device(self, k, group):
         """device_io: every request prepared into its slot of one (B,3,H,W) / (B,1,H,W) pair on the device, one forward with

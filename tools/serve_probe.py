@@ -13,6 +13,22 @@ whose default window is 512x512; wall time per request ending in the download, m
 plus se_profile_report's per-kernel times of one session edit.
 
     python tools/serve_probe.py --window [--reps N] [--out FILE]
+
+--window-scaled: window edits at a working size, same protocol (one process, B=1, low-latency mode, wall time per
+request ending in the download, own warm-up per leg, median of three rounds' medians).  A 1921x1081 frame and a sketch whose
+native window is the floored frame, 1080x1920:
+  (a) edit_native:        EditSession.edit(max_grow=0): one forward at 1080x1920,
+  (b) edit_scaled:        EditSession.edit(max_grow=0, max_side=640): the fused ends around a forward at 360x640,
+  (c) chained_entries:    the same request handled with the existing entries chained from Python: the session's own parsing of
+                          the sketch (box, window, working size), then a crop copy, prepare_u8, inference_u8, two resize_u8 and
+                          window_paste_u8 at the frame's resolution -- what (b) would cost without the fused ends,
+  (d) edit_scaled_default_grow: edit(max_side=640) with the default grow loop (this window is the floored frame: it cannot grow),
+  (e) edit_512_scale_1:   edit(max_grow=0) on the 512x512 sketch of --window (the unscaled path, which this must not slow),
+and the grow loop where it does grow, on that 512x512 sketch: edit_512_default_grow (three forwards, the last at 1080x1216) and
+edit_512_default_grow_scaled (the same with max_side=640); plus se_profile_report's per-kernel times of one (b) request.
+(b) and (c) are checked to leave the same frame.
+
+    python tools/serve_probe.py --window-scaled [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -99,11 +115,92 @@ def window_leg(model, reps):
                 edit_kernels_profiled=kernels, edit_kernels_total_ms=round(sum(k["ms"] for k in kernels.values()), 3), whole_512_kernels_total_ms=whole512)
 
 
+def big_sketch(rng, h=1081, w=1921):
+    """a sketch whose default window is the floored 1921x1081 frame"""
+    import numpy as np
+    sk = np.zeros((h, w), np.uint8)
+    sk[200:880, 300:1620] = ((rng.rand(680, 1320) < 0.01) * 255).astype(np.uint8)
+    sk[200, 300] = sk[879, 1619] = 255
+    return sk
+
+
+def rounds_of(legs, reps):
+    """three rounds over the legs, each leg timed back to back after its own warm-up -> per leg the median of the rounds'
+    medians, the rounds' medians (their spread is the run-to-run noise), min and max"""
+    rounds = [{k: wall_ms(fn, reps) for k, fn in legs.items()} for _ in range(3)]
+    out = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out[k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                      max=max(r[k]["max"] for r in rounds))
+    return out
+
+
+def window_scaled_leg(model, reps, max_side=640):
+    """(a) - (e) of the module docstring"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import _lib, serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    sk512 = np.zeros((h, w), np.uint8)
+    sk512[400:640, 800:1040] = ((rng.rand(240, 240) < 0.01) * 255).astype(np.uint8)
+    sk512[400, 800] = sk512[639, 1039] = 255
+    assert serve.choose_window(serve.sketch_bbox(sk512), (h, w))[2:] == (512, 512)
+    sk = big_sketch(rng)
+    y0, x0, hs, ws = win = serve.choose_window(serve.sketch_bbox(sk), (h, w))
+    assert (hs, ws) == (h // 8 * 8, w // 8 * 8), win
+    H, W = work = serve.choose_working_size((hs, ws), max_side)
+    eng = model.engine()
+    flags = _lib.flags_from_opt(model.opt)
+    session = serve.EditSession(model, frame)
+    chained_frame = _lib.upload_u8(frame, torch.device("cuda", eng.device))
+
+    def chained():
+        f = chained_frame
+        _, bbox = session._request(sk)                 # the host side of a request, as edit() does it
+        assert serve.choose_window(bbox, (h, w)) == win and serve.choose_working_size((hs, ws), max_side) == work
+        crop = f[y0:y0 + hs, x0:x0 + ws].contiguous()
+        sku = _lib.upload_u8(sk[y0:y0 + hs, x0:x0 + ws], f.device)
+        image, s = eng.prepare_u8(crop, sku, H, W)
+        rgb, m8 = eng.inference_u8(image, s, flags, low_latency=True)
+        eng.window_paste_u8([f], [(y0, x0)], eng.resize_u8(rgb, (hs, ws)), eng.resize_u8(m8, (hs, ws)))
+        return f[y0:y0 + hs, x0:x0 + ws].contiguous().cpu().numpy()
+
+    # (b) and (c) compute the same thing: one request each on a fresh frame
+    check = serve.EditSession(model, frame)
+    same = bool(np.array_equal(check.edit(sk, max_grow=0, low_latency=True, max_side=max_side)[0], chained()))
+    chained_frame.copy_(_lib.upload_u8(frame, chained_frame.device))
+    legs = dict(edit_native=lambda: session.edit(sk, max_grow=0, low_latency=True),
+                edit_scaled=lambda: session.edit(sk, max_grow=0, low_latency=True, max_side=max_side),
+                chained_entries=chained,
+                edit_scaled_default_grow=lambda: session.edit(sk, low_latency=True, max_side=max_side),
+                edit_512_scale_1=lambda: session.edit(sk512, max_grow=0, low_latency=True),
+                edit_512_default_grow=lambda: session.edit(sk512, low_latency=True),
+                edit_512_default_grow_scaled=lambda: session.edit(sk512, low_latency=True, max_side=max_side))
+    out = rounds_of(legs, reps)
+    info = session.edit(sk, low_latency=True, max_side=max_side)[2]
+    info512 = session.edit(sk512, low_latency=True, max_side=max_side)[2]
+    eng.profile(True)
+    session.edit(sk, max_grow=0, low_latency=True, max_side=max_side)
+    rep = eng.profile_report()
+    eng.profile(False)
+    kernels = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4), bytes=int(k["bytes"])) for k in rep["kernels"]}
+    return dict(tool="serve_probe --window-scaled", B=1, reps=reps, mode="low_latency", frame=[w, h], window=list(win), work=list(work),
+                max_side=max_side, ms=out, scaled_equals_chained=same,
+                speedup_native_over_scaled=round(out["edit_native"]["median"] / out["edit_scaled"]["median"], 2),
+                default_edit_info=dict(counts=info["counts"], reruns=info["reruns"], window=list(info["window"]), work=list(info["work"])),
+                default_edit_512_info=dict(counts=info512["counts"], reruns=info512["reruns"], window=list(info512["window"]), work=list(info512["work"])),
+                scaled_edit_kernels_profiled=kernels, scaled_edit_kernels_total_ms=round(sum(k["ms"] for k in kernels.values()), 3))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--window", action="store_true", help="the editing-session leg (see the module docstring)")
+    ap.add_argument("--window-scaled", action="store_true", help="window edits at a working size (see the module docstring)")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -112,8 +209,8 @@ def main():
     from sketchedit_amd import serve
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     model = make_model(tempfile.mkdtemp())
-    if args.window:
-        line = json.dumps(window_leg(model, args.reps))
+    if args.window or args.window_scaled:
+        line = json.dumps(window_scaled_leg(model, args.reps) if args.window_scaled else window_leg(model, args.reps))
         print(line)
         if args.out:
             with open(args.out, "w") as f:
