@@ -241,6 +241,22 @@ int se_edit_window_scaled_u8(se_ctx* ctx, void* stream, const se_window* wins, i
                              size_t workspace_bytes, int flags);
 size_t se_edit_window_scaled_u8_workspace_bytes(se_ctx* ctx, int B, int hs, int ws, int H, int W);
 
+/* ---- the undo journal of an editing session ---------------------------------------------------------------
+ * A paste changes only bytes inside its window's hs x ws rectangle of the frame, so the rectangle's bytes before the paste
+ * are all it takes to undo it.  se_window_save_u8 copies the rectangle of every request into that request's SLOT; enqueued in
+ * front of a committing se_edit_window_u8 / se_edit_window_scaled_u8 (or of the paste of an uncommitted run) on the same
+ * stream, the slot holds the pre-image.  se_window_swap_u8 EXCHANGES rectangle and slot: after the paste it restores the
+ * frame byte for byte (undo) and leaves the edit's result in the slot; the same call again puts it back (redo).
+ * A slot is hs rows of round_up(3 ws, 16) bytes in device memory, 16-byte aligned: se_window_saved_bytes(hs, ws) bytes (host
+ * only, no ctx, no HIP call; 0 if hs or ws < 16).  A row's padding bytes are unspecified.  slots is a HOST array of B device
+ * pointers; se_window.sketch_u8 is not used.  hs, ws >= 16, any values; every window inside its frame.  No byte outside a
+ * window's rows is read and none outside the rectangle is written.  Violations (a window outside its frame, hs / ws < 16, a
+ * NULL or misaligned slot, slots that overlap each other or a frame, for swap overlapping windows as se_window_paste_u8
+ * refuses them) return non-zero before anything is enqueued; se_last_error names the argument, frames and slots untouched. */
+size_t se_window_saved_bytes(int hs, int ws);
+int se_window_save_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int hs, int ws, unsigned char* const* slots);
+int se_window_swap_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int hs, int ws, unsigned char* const* slots);
+
 /* Host only (no HIP call, no ctx): the coefficient table the resize uses for one axis.  Returns ksize, the taps per output
  * (-1: bad arguments); when bounds (2*out ints: first input index, tap count) and k (cap >= out*ksize ints, fixed point
  * with 22 fractional bits, rows zero padded to ksize) are given, fills them.  Lets a test compare the tables with Pillow's. */

@@ -37,7 +37,8 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
            "se_profile_report", "se_debug_set_option", "se_debug_get_option", "se_debug_reset_options",
            "se_resize_u8", "se_prepare_u8", "se_edit_u8", "se_edit_u8_workspace_bytes", "se_resample_coeffs",
            "se_window_gather_u8", "se_window_border_u8", "se_window_paste_u8", "se_edit_window_u8", "se_edit_window_u8_workspace_bytes",
-           "se_window_gather_resize_u8", "se_window_paste_resize_u8", "se_edit_window_scaled_u8", "se_edit_window_scaled_u8_workspace_bytes"]
+           "se_window_gather_resize_u8", "se_window_paste_resize_u8", "se_edit_window_scaled_u8", "se_edit_window_scaled_u8_workspace_bytes",
+           "se_window_saved_bytes", "se_window_save_u8", "se_window_swap_u8"]
 
 
 class SketchEditHipError(RuntimeError):
@@ -183,6 +184,12 @@ def load_library():
         lib.se_edit_window_scaled_u8.restype = ci
         lib.se_edit_window_scaled_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci, ci]
         lib.se_edit_window_scaled_u8_workspace_bytes.restype = sz
+        lib.se_window_saved_bytes.argtypes = [ci, ci]
+        lib.se_window_saved_bytes.restype = sz
+        lib.se_window_save_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ctypes.POINTER(vp)]
+        lib.se_window_save_u8.restype = ci
+        lib.se_window_swap_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ctypes.POINTER(vp)]
+        lib.se_window_swap_u8.restype = ci
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -735,6 +742,42 @@ class Engine:
                                              1 if commit else 0, _ptr(ws_t), ws_t.numel(), flags):
             self._err("se_edit_window_scaled_u8")
         return rgb, m8, hits
+
+    # ---- the undo journal of a session ------------------------------------------------------------------------
+    @staticmethod
+    def window_saved_bytes(hs, ws):
+        """se_window_saved_bytes: the bytes of one journal slot, hs rows of round_up(3 ws, 16); 0 if hs or ws < 16 (host only)"""
+        return int(load_library().se_window_saved_bytes(int(hs), int(ws)))
+
+    def _journal(self, fn, name, frames, origins, window_hw, slots):
+        hs, ws = (int(v) for v in window_hw)
+        wins = self._windows(frames, origins)
+        need = self.window_saved_bytes(hs, ws)
+        if len(slots) != len(frames):
+            raise SketchEditHipError("%s: one slot per request" % name)
+        for t in slots:
+            _check_dev_u8(t)
+            if need and t.numel() < need:
+                raise SketchEditHipError("%s: a slot holds window_saved_bytes(hs, ws) = %d bytes" % (name, need))
+        ptrs = (ctypes.c_void_p * len(slots))(*[t.data_ptr() for t in slots])
+        if fn(self.h, self._stream(), wins, len(frames), hs, ws, ptrs):
+            self._err(name)
+
+    def window_save_u8(self, frames, origins, window_hw):
+        """se_window_save_u8: the hs x ws rectangle at origins[i] of every frame -> a new slot per request, (hs, pitch) uint8
+        with pitch = round_up(3 ws, 16) (a row's first 3 ws bytes are the crop's row).  One launch.  -> [slot tensors]"""
+        import torch
+        hs, ws = (int(v) for v in window_hw)
+        n = self.window_saved_bytes(hs, ws)                   # (0: a window the library refuses; it says why)
+        slots = [torch.empty(n, dtype=torch.uint8, device=f.device).view(hs, n // hs) if n else
+                 torch.empty(16, dtype=torch.uint8, device=f.device) for f in frames]
+        self._journal(self.lib.se_window_save_u8, "se_window_save_u8", frames, origins, (hs, ws), slots)
+        return slots
+
+    def window_swap_u8(self, frames, origins, window_hw, slots):
+        """se_window_swap_u8, in place: the hs x ws rectangle at origins[i] of frames[i] <-> slots[i] (as window_save_u8 made
+        it).  Overlapping windows of one frame in one call are refused."""
+        self._journal(self.lib.se_window_swap_u8, "se_window_swap_u8", frames, origins, window_hw, slots)
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):
         """Inference into ONE (B,4,H,W) buffer `out`: planes 0-2 composed, plane 3 the soft mask -- the unit the

@@ -1661,6 +1661,36 @@ int se_edit_u8(se_ctx* c, void* stream, const unsigned char* image_u8, const uns
 // ---- editing sessions: window edits of a resident frame (se_window.hip) ------------------------------
 namespace {
 
+// the records of a call: frames given, sizes sane, every hs x ws window inside its frame
+int win_check_records(se_ctx* c, const se_window* wins, int B, int hs, int ws, bool need_sketch) {
+  for (int i = 0; i < B; ++i) {
+    const se_window& w = wins[i];
+    if (!w.frame_u8) return fail(c, "wins[%d].frame_u8 is null", i);
+    if (need_sketch && !w.sketch_u8) return fail(c, "wins[%d].sketch_u8 is null", i);
+    if (w.Hi < 1 || w.Wi < 1) return fail(c, "wins[%d]: bad frame size Hi=%d Wi=%d", i, w.Hi, w.Wi);
+    if (w.y0 < 0 || (long long)w.y0 + hs > w.Hi)
+      return fail(c, "wins[%d].y0=%d: rows [%d, %lld) of the window lie outside the frame (Hi=%d)", i, w.y0, w.y0, (long long)w.y0 + hs, w.Hi);
+    if (w.x0 < 0 || (long long)w.x0 + ws > w.Wi)
+      return fail(c, "wins[%d].x0=%d: columns [%d, %lld) of the window lie outside the frame (Wi=%d)", i, w.x0, w.x0, (long long)w.x0 + ws, w.Wi);
+  }
+  return 0;
+}
+
+// a launch that writes the frames runs concurrently for all requests: their windows must not share a byte
+int win_check_disjoint(se_ctx* c, const se_window* wins, int B, int hs, int ws) {
+  for (int i = 0; i < B; ++i)
+    for (int j = i + 1; j < B; ++j) {
+      const se_window &a = wins[i], &b = wins[j];
+      const uintptr_t a0 = (uintptr_t)a.frame_u8, a1 = a0 + (size_t)a.Hi * a.Wi * 3, b0 = (uintptr_t)b.frame_u8, b1 = b0 + (size_t)b.Hi * b.Wi * 3;
+      if (a1 <= b0 || b1 <= a0) continue;                 // frames apart in memory
+      if (a0 != b0 || a.Wi != b.Wi || a.Hi != b.Hi)
+        return fail(c, "wins[%d] and wins[%d]: frames overlap in memory without being the same frame", i, j);
+      if (a.y0 < b.y0 + hs && b.y0 < a.y0 + hs && a.x0 < b.x0 + ws && b.x0 < a.x0 + ws)
+        return fail(c, "wins[%d] and wins[%d] name overlapping windows of one frame", i, j);
+    }
+  return 0;
+}
+
 // every argument check of the window calls, on the host, before anything is enqueued.  H x W = the size the forward runs at,
 // hs x ws = the window's extent in the frame (the same unless the edit runs at a working size)
 int win_check(se_ctx* c, const se_window* wins, int B, int H, int W, int hs, int ws, bool need_sketch, bool writes) {
@@ -1677,29 +1707,8 @@ int win_check(se_ctx* c, const se_window* wins, int B, int H, int W, int hs, int
   if (!wins) return fail(c, "null pointer argument: wins");
   if (B > 65535 || (long long)B * H * W / 1024 >= (1ll << 31) || (long long)B * hs * ws / 1024 >= (1ll << 31))
     return fail(c, "window: B=%d %dx%d (window %dx%d) is more than one launch takes", B, H, W, hs, ws);
-  for (int i = 0; i < B; ++i) {
-    const se_window& w = wins[i];
-    if (!w.frame_u8) return fail(c, "wins[%d].frame_u8 is null", i);
-    if (need_sketch && !w.sketch_u8) return fail(c, "wins[%d].sketch_u8 is null", i);
-    if (w.Hi < 1 || w.Wi < 1) return fail(c, "wins[%d]: bad frame size Hi=%d Wi=%d", i, w.Hi, w.Wi);
-    if (w.y0 < 0 || (long long)w.y0 + hs > w.Hi)
-      return fail(c, "wins[%d].y0=%d: rows [%d, %lld) of the window lie outside the frame (Hi=%d)", i, w.y0, w.y0, (long long)w.y0 + hs, w.Hi);
-    if (w.x0 < 0 || (long long)w.x0 + ws > w.Wi)
-      return fail(c, "wins[%d].x0=%d: columns [%d, %lld) of the window lie outside the frame (Wi=%d)", i, w.x0, w.x0, (long long)w.x0 + ws, w.Wi);
-  }
-  if (!writes) return 0;
-  // the paste of one launch runs concurrently for all requests: their windows must not share a byte
-  for (int i = 0; i < B; ++i)
-    for (int j = i + 1; j < B; ++j) {
-      const se_window &a = wins[i], &b = wins[j];
-      const uintptr_t a0 = (uintptr_t)a.frame_u8, a1 = a0 + (size_t)a.Hi * a.Wi * 3, b0 = (uintptr_t)b.frame_u8, b1 = b0 + (size_t)b.Hi * b.Wi * 3;
-      if (a1 <= b0 || b1 <= a0) continue;                 // frames apart in memory
-      if (a0 != b0 || a.Wi != b.Wi || a.Hi != b.Hi)
-        return fail(c, "wins[%d] and wins[%d]: frames overlap in memory without being the same frame", i, j);
-      if (a.y0 < b.y0 + hs && b.y0 < a.y0 + hs && a.x0 < b.x0 + ws && b.x0 < a.x0 + ws)
-        return fail(c, "wins[%d] and wins[%d] name overlapping windows of one frame", i, j);
-    }
-  return 0;
+  if (win_check_records(c, wins, B, hs, ws, need_sketch)) return 1;
+  return writes ? win_check_disjoint(c, wins, B, hs, ws) : 0;
 }
 
 // the records of one call -> the next B slots of the ctx's ring, copied to the device on `st`; returns the device address
@@ -1981,6 +1990,60 @@ int se_edit_window_scaled_u8(se_ctx* c, void* stream, const se_window* wins, int
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
   return edit_window_locked(c, stream, wins, B, hs, ws, H, W, rgb_out, mask_u8_out, hits_out, commit, workspace, workspace_bytes, flags);
+}
+
+// ---- the undo journal of a session ---------------------------------------------------------------
+size_t se_window_saved_bytes(int hs, int ws) {
+  if (hs < 16 || ws < 16) return 0;
+  return (size_t)hs * (((size_t)3 * ws + 15) & ~(size_t)15);
+}
+
+namespace {
+
+// save (the windows -> their slots) or swap (windows <-> slots): every check on the host, then ONE launch.  The slot pointers
+// travel with the records: 2 B consecutive entries of the ctx's ring (win_put takes them as one group), the second B carrying
+// a slot in frame_u8.
+int window_journal_call(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, unsigned char* const* slots, bool swap) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (B < 1) return fail(c, "bad B=%d", B);
+  if (hs < 16 || ws < 16) return fail(c, "bad window hs=%d ws=%d (a window is at least 16 x 16 frame pixels)", hs, ws);
+  if (!wins) return fail(c, "null pointer argument: wins");
+  if (!slots) return fail(c, "null pointer argument: slots");
+  if (B > 32767 || (long long)B * hs * ws / 1024 >= (1ll << 31))
+    return fail(c, "window: B=%d (window %dx%d) is more than one launch takes", B, hs, ws);
+  if (win_check_records(c, wins, B, hs, ws, false)) return 1;
+  const size_t bytes = se_window_saved_bytes(hs, ws);
+  for (int i = 0; i < B; ++i) {
+    if (!slots[i]) return fail(c, "slots[%d] is null", i);
+    if (!aligned_to(slots[i], 16)) return fail(c, "slots[%d] must be 16-byte aligned", i);
+    const uintptr_t s0 = (uintptr_t)slots[i], s1 = s0 + bytes;
+    for (int j = 0; j < B; ++j) {
+      const uintptr_t f0 = (uintptr_t)wins[j].frame_u8, f1 = f0 + (size_t)wins[j].Hi * wins[j].Wi * 3;
+      if (s0 < f1 && f0 < s1) return fail(c, "slots[%d] overlaps the frame of wins[%d]", i, j);
+      const uintptr_t t0 = (uintptr_t)slots[j];
+      if (j > i && s0 < t0 + bytes && t0 < s1) return fail(c, "slots[%d] and slots[%d] overlap", i, j);
+    }
+  }
+  if (swap && win_check_disjoint(c, wins, B, hs, ws)) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  std::vector<se_window> recs(wins, wins + B);
+  for (int i = 0; i < B; ++i) recs.push_back(se_window{slots[i], nullptr, 0, 0, 0, 0});
+  const se_window* d = win_put(c, (hipStream_t)stream, recs.data(), 2 * B);
+  if (!d) return 1;
+  HIPCHK(c, launch_window_journal(d, B, hs, ws, swap, (hipStream_t)stream));
+  return 0;
+}
+
+}  // namespace
+
+int se_window_save_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, unsigned char* const* slots) {
+  return window_journal_call(c, stream, wins, B, hs, ws, slots, false);
+}
+
+int se_window_swap_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, unsigned char* const* slots) {
+  return window_journal_call(c, stream, wins, B, hs, ws, slots, true);
 }
 
 // ---- measurement support (bench.py): per-kernel HIP-event timing ---------------------------------

@@ -18,7 +18,7 @@ namespace se {
 enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL_WINO_N192, PL_WINO_N96, PL_WINO_UP96, PL_SMALL_CONV, PL_PACK, PL_COLREDUCE,
                  PL_ATT_PREP, PL_ATT_SCORE, PL_ATT_SOFTMAX, PL_ATT_BOXSUM, PL_ATT_PV, PL_LAYOUT,
                  PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_WINDOW_GATHER, PL_WINDOW_BORDER, PL_WINDOW_PASTE,
-                 PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_COUNT };
+                 PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -392,5 +392,9 @@ hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8
 // frame[y0 + y, x0 + x, :] = rgb[b, y, x, :] where m8[b, y, x] > 0; rgb (B,H,W,3) and m8 (B,H,W) 4-byte aligned, W % 4 == 0
 hipError_t launch_window_paste(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, int B, int H, int W,
                                hipStream_t st);
+// the undo journal.  d_wins = 2 B records: the requests, then B records whose frame_u8 is the request's slot
+// (hs rows of round_up(3 ws, 16) bytes, 16-byte aligned).  save: the hs x ws rectangle -> the slot; swap: rectangle <-> slot.
+// Any hs, ws; no byte outside a window's rows is read, none outside the rectangle written.
+hipError_t launch_window_journal(const se_window* d_wins, int B, int hs, int ws, bool swap, hipStream_t st);
 
 }  // namespace se

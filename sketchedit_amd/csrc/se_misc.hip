@@ -106,7 +106,7 @@ const char* prof_label_name(int l) {
   static const char* n[PL_COUNT] = {"gconv_n192", "gconv_n96", "gconv_n48", "gconv_n24", "wino_n192", "wino_n96", "wino_up96", "small_conv", "pack",
                                     "colreduce", "att_prep", "att_score", "att_softmax", "att_boxsum", "att_pv", "layout",
                                     "att_stream_stats", "att_stream_out", "resize_h", "resize_v", "window_gather", "window_border",
-                                    "window_paste", "window_resample_h", "window_paste_v"};
+                                    "window_paste", "window_resample_h", "window_paste_v", "window_save", "window_swap"};
   return (l >= 0 && l < PL_COUNT) ? n[l] : "?";
 }
 

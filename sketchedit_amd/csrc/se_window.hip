@@ -14,6 +14,16 @@
 // neighbouring pixels are all selected and the address allows it, single bytes otherwise: it never rewrites a byte it does
 // not own, so concurrent lanes (and windows of other requests on the same frame, which the host requires to be disjoint)
 // do not race.
+//
+// The undo journal of a session adds two copies between a window and a journal slot -- hs rows of
+// pitch = round_up(3 ws, 16) bytes, 16-byte aligned, so the slot side moves as aligned 16-byte vectors:
+//
+//  save: the window's hs x ws rectangle of each frame -> that request's slot (the bytes before a paste);
+//  swap: the rectangle <-> the slot (undo, and redo: the same exchange again).
+//
+// One lane owns one 16-byte chunk of a slot row and the (up to) 16 frame bytes that belong in it.  It reads them as gather
+// does and, in swap, writes them back by the ownership rule above: aligned dwords that lie inside its own bytes, single bytes
+// in front of and behind them.  No lane writes a byte another lane owns, and none outside the rectangle.
 #include "../../include/sketchedit_hip.h"
 #include "se_device.h"
 #include "se_kernels.h"
@@ -32,6 +42,75 @@ __device__ __forceinline__ unsigned load_dword_within(const unsigned char* p, co
   for (int i = 0; i < 4; ++i)
     if (p + i >= lo && p + i < hi) v |= (unsigned)p[i] << (8 * i);
   return v;
+}
+
+// the 16 bytes at `a` (any alignment), of which only those inside [lo, hi) are read (the others are 0): aligned dwords and a
+// byte shift
+__device__ __forceinline__ uint4 load16_within(const unsigned char* a, const unsigned char* lo, const unsigned char* hi) {
+  const unsigned char* a0 = (const unsigned char*)((uintptr_t)a & ~(uintptr_t)3);
+  const int sh = (int)((uintptr_t)a & 3) * 8;
+  unsigned d[5], u[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) d[i] = load_dword_within(a0 + 4 * i, lo, hi);
+  d[4] = sh ? load_dword_within(a0 + 16, lo, hi) : 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) u[i] = sh ? (d[i] >> sh) | (d[i + 1] << (32 - sh)) : d[i];
+  return make_uint4(u[0], u[1], u[2], u[3]);
+}
+
+// the first n (1..16) bytes of s -> [a, a + n), any alignment, and not one byte more: the aligned dwords that lie inside the
+// span whole, single bytes at its head and tail
+__device__ __forceinline__ void store_owned(unsigned char* a, int n, uint4 s) {
+  const int mis = (int)((uintptr_t)a & 3);
+  if (n == 16 && ((uintptr_t)a & 15) == 0) {
+    *(uint4*)a = s;
+    return;
+  }
+  unsigned char* a0 = a - mis;
+  const unsigned v[5] = {s.x, s.y, s.z, s.w, 0u};
+  const int sl = mis * 8;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    // the dword at a0 + 4 k holds the bytes 4 k - mis .. 4 k - mis + 3 of s
+    const unsigned f = sl ? (v[k] << sl) | (k > 0 ? v[k - 1] >> (32 - sl) : 0u) : v[k];
+    const int off = 4 * k - mis;
+    if (off >= 0 && off + 4 <= n) {
+      *(unsigned*)(a0 + 4 * k) = f;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (off + e >= 0 && off + e < n) a0[4 * k + e] = (unsigned char)((f >> (8 * e)) & 255u);
+    }
+  }
+}
+
+// One lane = one 16-byte chunk of one slot row.  wins holds 2 B records: wins[B + b].frame_u8 is request b's slot.
+template <bool SWAP>
+__device__ __forceinline__ void window_journal(const se_window* __restrict__ wins, int B, int hs, int ws) {
+  const int pitch = (3 * ws + 15) & ~15, chunks = pitch >> 4;
+  const long q = (long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (long)B * hs * chunks) return;
+  const int j = (int)(q % chunks);
+  const long by = q / chunks;
+  const int y = (int)(by % hs), b = (int)(by / hs);
+  const se_window w = wins[b];
+  unsigned char* row = w.frame_u8 + ((size_t)(w.y0 + y) * w.Wi + w.x0) * 3;       // the window row's bytes: [row, row + 3 ws)
+  unsigned char* a = row + 16 * j;
+  uint4* s = (uint4*)(wins[B + b].frame_u8 + (size_t)y * pitch) + j;
+  const uint4 f = load16_within(a, row, row + 3 * ws);
+  if (SWAP) {
+    const uint4 old = *s;
+    store_owned(a, min(16, 3 * ws - 16 * j), old);
+  }
+  *s = f;
+}
+
+__global__ void __launch_bounds__(256) window_save_kernel(const se_window* __restrict__ wins, int B, int hs, int ws) {
+  window_journal<false>(wins, B, hs, ws);
+}
+
+__global__ void __launch_bounds__(256) window_swap_kernel(const se_window* __restrict__ wins, int B, int hs, int ws) {
+  window_journal<true>(wins, B, hs, ws);
 }
 
 // One lane = 4 consecutive pixels of one window row: 12 frame bytes + 4 sketch bytes in, four float4 stores out.
@@ -166,6 +245,17 @@ hipError_t launch_window_paste(const se_window* d_wins, const unsigned char* rgb
   set_launch_grid((nq + 255) / 256);
   ProfScope ps_(st, PL_WINDOW_PASTE);
   hipLaunchKernelGGL(window_paste_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_wins, rgb, m8, B, H, W);
+  return hipGetLastError();
+}
+
+hipError_t launch_window_journal(const se_window* d_wins, int B, int hs, int ws, bool swap, hipStream_t st) {
+  const long nq = (long)B * hs * ((3 * ws + 15) / 16);
+  // bytes: save reads the rectangle and writes the slot's rows; swap reads and writes both
+  set_launch_cost(0.0, (double)B * hs * (3.0 * ws + (double)((3 * ws + 15) & ~15)) * (swap ? 2.0 : 1.0), swap ? "window_swap" : "window_save");
+  set_launch_grid((nq + 255) / 256);
+  ProfScope ps_(st, swap ? PL_WINDOW_SWAP : PL_WINDOW_SAVE);
+  if (swap) hipLaunchKernelGGL(window_swap_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_wins, B, hs, ws);
+  else hipLaunchKernelGGL(window_save_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_wins, B, hs, ws);
   return hipGetLastError();
 }
 

@@ -152,6 +152,15 @@ class EditLine2Model(torch.nn.Module):
             return self.engine().edit_window_u8(frames, origins, sks, H, W, flags, commit=commit,
                                                 low_latency=self._mode_for(len(frames), H, W, low_latency))
 
+    def window_save_u8(self, frames, origins, window_hw):
+        """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
+        slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""
+        return self.engine().window_save_u8(frames, origins, window_hw)
+
+    def window_swap_u8(self, frames, origins, window_hw, slots):
+        """Undo / redo: exchanges each frame's rectangle with its slot, in place."""
+        self.engine().window_swap_u8(frames, origins, window_hw, slots)
+
     def forward(self, data, mode, low_latency=None):
         """`low_latency` (no reference counterpart): None = by this call's own size, True / False = pinned.  Results are
         bit-identical across batch compositions only WITHIN one mode (include/sketchedit_hip.h), so callers whose batch size

@@ -151,6 +151,13 @@ def choose_working_size(window_hw, max_side):
     return max(hs * max_side // long_side // 8 * 8, 16), max(ws * max_side // long_side // 8 * 8, 16)
 
 
+def window_saved_bytes(hs, ws):
+    """Bytes of one undo-journal slot of an hs x ws window: hs rows of 3 ws bytes rounded up to 16; 0 for a
+    window under 16 x 16.  The library's se_window_saved_bytes in host arithmetic (the host tests compare the two)."""
+    hs, ws = int(hs), int(ws)
+    return 0 if hs < 16 or ws < 16 else hs * ((3 * ws + 15) // 16 * 16)
+
+
 class _ModelBackend:
     """The device side of an editing session: an EditLine2Model's engine and torch for the copies.  (A seam: the host
     logic of EditSession and of the window batcher is tested against a scripted stand-in.)"""
@@ -185,6 +192,14 @@ class _ModelBackend:
     def paste_scaled(self, frames, origins, window_hw, rgb, m8):
         self.model.engine().window_paste_resize_u8(frames, origins, window_hw, rgb, m8)
 
+    def save(self, frames, origins, window_hw):
+        """the windows' rectangles -> one new journal slot each, on the stream the edit follows on"""
+        return self.model.window_save_u8(frames, origins, window_hw)
+
+    def swap(self, frames, origins, window_hw, slots):
+        """rectangles <-> slots: undo, and redo"""
+        self.model.window_swap_u8(frames, origins, window_hw, slots)
+
     def select(self, t, idx):
         """rows `idx` of a batch result as a contiguous batch"""
         return t if list(idx) == list(range(t.shape[0])) else t[list(idx)].contiguous()
@@ -215,9 +230,15 @@ class EditSession:
     > 0 -- so its time follows the edit, not the frame; pixels the edit does not select keep their bytes, and only the
     window's sketch and the window's result cross the bus.  The frame on the device is the session's state: the next edit
     sees this one's result.  Edits of one session are serialised; do not mix `edit` with a BatchingServer(window=True)
-    that was handed the same session."""
+    that was handed the same session.
+    `history` (0: no journal, the session as above): the number of edits `undo` can take back.  Before a
+    committed paste the window's rectangle of the frame is copied into a journal slot on the device; `undo` exchanges
+    rectangle and slot, `redo` exchanges them again -- the whole frame is byte-identical to what it was.  `history_bytes`
+    caps the bytes of all slots (window_saved_bytes each, undo and redo together); over either cap the OLDEST undo entry is
+    dropped; an edit whose own slot exceeds `history_bytes` is committed without a journal entry and clears the history
+    (info["undoable"] = False).  A new edit drops the redo entries."""
 
-    def __init__(self, model, image, backend=None):
+    def __init__(self, model, image, backend=None, history=0, history_bytes=None):
         if hasattr(image, "convert"):
             image = np.asarray(image.convert("RGB"))
         image = np.asarray(image)
@@ -231,6 +252,70 @@ class EditSession:
         self.frame_hw = (Hi, Wi)
         self._frame = self.backend.upload(image)
         self._lock = threading.Lock()
+        if int(history) < 0 or (history_bytes is not None and int(history_bytes) < 0):
+            raise ValueError("history and history_bytes must not be negative")
+        self.history = int(history)
+        self.history_bytes = None if history_bytes is None else int(history_bytes)
+        self._undo, self._redo = [], []          # entries (window, slot, bytes); the next to undo / redo is the last
+
+    # ---- the undo journal; the helpers below run with the session's lock held ---------------------------------
+    def _journals(self, h, w):
+        """whether a committed edit of an h x w window gets a journal entry"""
+        return self.history > 0 and (self.history_bytes is None or window_saved_bytes(h, w) <= self.history_bytes)
+
+    def _bytes_used(self):
+        return sum(e[2] for e in self._undo) + sum(e[2] for e in self._redo)
+
+    def _record(self, window, slot):
+        """A paste into `window` was committed; `slot` holds the rectangle's bytes from before it (None: the edit was not
+        journalled).  -> undoable"""
+        self._redo.clear()
+        if slot is None:
+            self._undo.clear()                   # an older entry could no longer restore a state the frame was in
+            return False
+        self._undo.append((tuple(window), slot, window_saved_bytes(window[2], window[3])))
+        while len(self._undo) > self.history or (self.history_bytes is not None and self._bytes_used() > self.history_bytes):
+            self._undo.pop(0)
+        return True
+
+    def _exchanged(self, src, dst):
+        """the entry `src` ends in was exchanged with the frame: it moves to `dst`; -> what undo / redo return"""
+        dst.append(src.pop())
+        y0, x0, h, w = dst[-1][0]
+        info = dict(window=dst[-1][0], undo_depth=len(self._undo), redo_depth=len(self._redo))
+        return self.backend.crop(self._frame, y0, x0, h, w), (x0, y0), info
+
+    def _exchange(self, src, dst, what):
+        with self._lock:
+            if not src:
+                raise IndexError("nothing to " + what)
+            (y0, x0, h, w), slot, _ = src[-1]
+            self.backend.swap([self._frame], [(y0, x0)], (h, w), [slot])
+            return self._exchanged(src, dst)
+
+    def undo(self):
+        """Takes the last edit back: the frame is byte-identical to what it was before it.  -> (patch, (x0, y0), info) in
+        `edit`'s shape: the window after the exchange (the only download), info = dict(window, undo_depth, redo_depth).
+        IndexError when there is nothing to undo."""
+        return self._exchange(self._undo, self._redo, "undo")
+
+    def redo(self):
+        """Puts the last undone edit back, byte for byte.  Returns as `undo`; IndexError when there is nothing to redo."""
+        return self._exchange(self._redo, self._undo, "redo")
+
+    @property
+    def can_undo(self):
+        return bool(self._undo)
+
+    @property
+    def can_redo(self):
+        return bool(self._redo)
+
+    @property
+    def history_bytes_used(self):
+        """bytes of the journal slots held, undo and redo together"""
+        with self._lock:
+            return self._bytes_used()
 
     def _request(self, sketch):
         """-> (sketch array, bbox) of a full-size sketch; refusals of the window path"""
@@ -276,7 +361,9 @@ class EditSession:
         back and pasted where the resampled mask is > 0 -- so an edit's cost is bounded by `max_side` whatever the
         sketch's extent.  The window is chosen and grown in frame space as before and the working size follows it; the
         counts are those of the working-size mask; a given `window` then needs no multiple-of-8 sides; info gains
-        work=(H, W).  Still only the window's sketch goes up and only the window comes down."""
+        work=(H, W).  Still only the window's sketch goes up and only the window comes down.
+        With history on, the window that is finally committed is journalled (one save in front of its paste) and info
+        gains undoable."""
         sk, bbox = self._request(sketch)
         margin = 0.5
         fixed = window is not None
@@ -291,6 +378,7 @@ class EditSession:
                 # a run whose counts cannot change anything commits at once: no round trip between forward and paste
                 commit = nxt is None
                 crop = be.upload(sk[y0:y0 + h, x0:x0 + w])
+                slot = be.save([self._frame], [(y0, x0)], (h, w))[0] if commit and self._journals(h, w) else None
                 if scaled:
                     work = choose_working_size((h, w), max_side)
                     rgb, m8, counts = be.run_scaled([self._frame], [(y0, x0)], [crop], (h, w), work, commit, low_latency)
@@ -300,14 +388,19 @@ class EditSession:
                     break
                 win, margin = nxt
                 reruns += 1
+            if not commit and self._journals(h, w):
+                slot = be.save([self._frame], [(y0, x0)], (h, w))[0]
             if not commit and scaled:
                 be.paste_scaled([self._frame], [(y0, x0)], (h, w), rgb, m8)
             elif not commit:
                 be.paste([self._frame], [(y0, x0)], rgb, m8)
+            undoable = self._record(win, slot) if self.history > 0 else None
             patch = be.crop(self._frame, y0, x0, h, w)
         info = dict(window=win, counts=list(counts[0]), reruns=reruns, margin=margin)
         if scaled:
             info["work"] = work
+        if undoable is not None:
+            info["undoable"] = undoable
         return patch, (x0, y0), info
 
     def frame(self):
@@ -362,7 +455,11 @@ class BatchingServer:
     `max_grow` times); a group never holds two requests of one session (the second waits for the next group: it must
     see the first's result).  `max_side` (with window=True): every edit runs at
     choose_working_size(window, max_side), as EditSession.edit(max_side=...) does; the group key is then
-    (hs, ws, H, W) and the mode policy goes by the working size, the size of the forward."""
+    (hs, ws, H, W) and the mode policy goes by the working size, the size of the forward.
+    Sessions bring their own `history`: the saves of a group's journalled requests are ONE launch, in front of
+    the run when the group commits in the call, else in front of the paste for the requests that stay.  `undo(session)` /
+    `redo(session)` block and return like `submit`; they are queued like an edit of that session, so an undo submitted after
+    two edits undoes the second; undo / redo requests of different sessions share a group, one swap launch per window size."""
 
     def __init__(self, model=None, max_batch=32, max_wait_s=0.005, models=None, mode_policy="pinned", device_io=False,
                  window=False, max_grow=2, max_side=None):
@@ -409,6 +506,20 @@ class BatchingServer:
         win = choose_window(bbox, session.frame_hw)
         return self._window_key(win), dict(session=session, sketch=sk, bbox=bbox, window=win, margin=0.5, reruns=0), None
 
+    def _submit_history(self, session, op):
+        if not self.window:
+            raise ValueError("undo / redo are requests of editing sessions: they need window=True")
+        if session.model is not self.model:
+            raise ValueError("the session belongs to another model than this server's")
+        return self._enqueue(("history",), dict(session=session, op=op), None)
+
+    def undo(self, session):
+        """`session.undo()` in the session's queue order -> what it returns"""
+        return self._submit_history(session, "undo")
+
+    def redo(self, session):
+        return self._submit_history(session, "redo")
+
     def submit(self, img, mask):
         arrays = _device_inputs(img, mask) if self.device_io and not self.window else None
         if self.window:
@@ -419,6 +530,9 @@ class BatchingServer:
         else:
             x, m, size_raw = _to_tensors(img, mask)
             key, req = tuple(x.shape), (x, m)
+        return self._enqueue(key, req, size_raw)
+
+    def _enqueue(self, key, req, size_raw):
         slot = {"done": threading.Event(), "out": None, "err": None}
         with self._lock:
             if self._stop:
@@ -494,16 +608,26 @@ class BatchingServer:
         commit = all(g is None for g in grown)            # no request can grow: the counts decide nothing
         frames = [r["session"]._frame for r in reqs]
         origins = [r["window"][:2] for r in reqs]
+        journalled = [i for i, r in enumerate(reqs) if r["session"]._journals(h, w)]
+        slots = {}
+
+        def save(idx):                                    # one launch for the group's journalled requests
+            if idx:
+                slots.update(zip(idx, be.save([frames[i] for i in idx], [origins[i] for i in idx], (h, w))))
         locks = sorted({id(r["session"]): r["session"]._lock for r in reqs}.items())
         for _, lk in locks:
             lk.acquire()
         try:
             crops = [be.upload(r["sketch"][y0:y0 + h, x0:x0 + w]) for r, (y0, x0) in zip(reqs, origins)]
+            if commit:
+                save(journalled)
             if work is not None:
                 rgb, m8, counts = be.run_scaled(frames, origins, crops, (h, w), work, commit, low_latency)
             else:
                 rgb, m8, counts = be.run(frames, origins, crops, h, w, commit, low_latency)
             stay = [i for i in range(len(reqs)) if grown[i] is None or not any(counts[i])]
+            if not commit:
+                save([i for i in stay if i in journalled])          # (a request that is queued again journals nothing yet)
             if not commit and stay and work is not None:
                 be.paste_scaled([frames[i] for i in stay], [origins[i] for i in stay], (h, w), be.select(rgb, stay), be.select(m8, stay))
             elif not commit and stay:
@@ -515,6 +639,8 @@ class BatchingServer:
                 info = dict(window=r["window"], counts=list(counts[i]), reruns=r["reruns"], margin=r["margin"])
                 if work is not None:
                     info["work"] = tuple(work)
+                if r["session"].history > 0:
+                    info["undoable"] = r["session"]._record(r["window"], slots.get(i))
                 outs[i] = (be.crop(frames[i], y0, x0, h, w), (x0, y0), info)
         finally:
             for _, lk in locks:
@@ -530,6 +656,35 @@ class BatchingServer:
             with self._lock:
                 self._queue = again + self._queue     # in front: they are older than what arrived since, and their sessions' next edits wait for them
                 self._lock.notify_all()
+        return outs
+
+    def _run_history(self, group):
+        """One group of undo / redo requests, each of another session (_candidates): one swap launch per window size.  A
+        request with nothing to undo / redo fails alone (IndexError)."""
+        reqs = [q[1] for q in group]
+        be = reqs[0]["session"].backend
+        outs = [None] * len(reqs)
+        locks = sorted({id(r["session"]): r["session"]._lock for r in reqs}.items())
+        for _, lk in locks:
+            lk.acquire()
+        try:
+            stacks, by_size = [], {}
+            for i, r in enumerate(reqs):
+                s = r["session"]
+                stacks.append((s._undo, s._redo) if r["op"] == "undo" else (s._redo, s._undo))
+                if not stacks[i][0]:
+                    group[i][3]["err"] = IndexError("nothing to " + r["op"])
+                    outs[i] = False
+                else:
+                    by_size.setdefault(stacks[i][0][-1][0][2:], []).append(i)
+            for hw, idx in by_size.items():
+                tops = [stacks[i][0][-1] for i in idx]
+                be.swap([reqs[i]["session"]._frame for i in idx], [t[0][:2] for t in tops], hw, [t[1] for t in tops])
+                for i in idx:
+                    outs[i] = reqs[i]["session"]._exchanged(*stacks[i])
+        finally:
+            for _, lk in locks:
+                lk.release()
         return outs
 
     def _mode(self, shape):
@@ -583,7 +738,9 @@ class BatchingServer:
                 continue
             ran = len(group)
             try:
-                if self.window:
+                if self.window and group[0][0] == ("history",):
+                    outs = self._run_history(group)
+                elif self.window:
                     outs = self._run_window(k, group)
                     done = [(q, out) for q, out in zip(group, outs) if out is not None]     # the others were queued again
                     group, outs = [q for q, _ in done], [out for _, out in done]

@@ -29,6 +29,16 @@ edit_512_default_grow_scaled (the same with max_side=640); plus se_profile_repor
 (b) and (c) are checked to leave the same frame.
 
     python tools/serve_probe.py --window-scaled [--reps N] [--out FILE]
+
+--window-history: the undo journal, same protocol.  On the 512x512 sketch of --window:
+  (a) edit_h0:    EditSession(history=0).edit(max_grow=0) -- the session without a journal (the leg that is compared with the
+                  parent commit's build, run with --window-history-parent there: only this leg, no journal call),
+  (b) edit_h8:    the same with history=8 (one window_save launch in front of the committing call),
+  (c) undo_redo:  undo() and redo() alternating on that session, one exchange per request,
+and (d) big_edit_h0 / (e) big_edit_h8 / (f) big_undo_redo: the same three at --window-scaled's input (1080x1920 window,
+max_side=640; the slot is 6.2 MB); plus se_profile_report's window_save / window_swap times and bytes.
+
+    python tools/serve_probe.py --window-history [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -195,12 +205,61 @@ def window_scaled_leg(model, reps, max_side=640):
                 scaled_edit_kernels_profiled=kernels, scaled_edit_kernels_total_ms=round(sum(k["ms"] for k in kernels.values()), 3))
 
 
+def window_history_leg(model, reps, parent=False, max_side=640):
+    """(a) - (f) of the module docstring; parent=True: legs (a) and (d) only, with the calls a build without the journal has"""
+    import numpy as np
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    sk512 = np.zeros((h, w), np.uint8)
+    sk512[400:640, 800:1040] = ((rng.rand(240, 240) < 0.01) * 255).astype(np.uint8)
+    sk512[400, 800] = sk512[639, 1039] = 255
+    assert serve.choose_window(serve.sketch_bbox(sk512), (h, w))[2:] == (512, 512)
+    big = big_sketch(rng)
+    s0 = serve.EditSession(model, frame)
+    legs = dict(edit_h0=lambda: s0.edit(sk512, max_grow=0, low_latency=True),
+                big_edit_h0=lambda: s0.edit(big, max_grow=0, low_latency=True, max_side=max_side))
+    if not parent:
+        s8, b8 = serve.EditSession(model, frame, history=8), serve.EditSession(model, frame, history=8)
+        s8.edit(sk512, max_grow=0, low_latency=True)
+        b8.edit(big, max_grow=0, low_latency=True, max_side=max_side)
+
+        def flip(s):
+            return s.undo() if s.can_undo else s.redo()
+        legs.update(edit_h8=lambda: s8.edit(sk512, max_grow=0, low_latency=True), undo_redo=lambda: flip(u8),
+                    big_edit_h8=lambda: b8.edit(big, max_grow=0, low_latency=True, max_side=max_side),
+                    big_undo_redo=lambda: flip(ub))
+        u8, ub = serve.EditSession(model, frame, history=1), serve.EditSession(model, frame, history=1)
+        u8.edit(sk512, max_grow=0, low_latency=True)
+        ub.edit(big, max_grow=0, low_latency=True, max_side=max_side)
+    out = dict(tool="serve_probe --window-history" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency",
+               frame=[w, h], max_side=max_side, ms=rounds_of(legs, reps))
+    if not parent:
+        eng = model.engine()
+        prof = {}
+        for tag, s, sk, kw in (("512", s8, sk512, {}), ("big", b8, big, dict(max_side=max_side))):
+            eng.profile(True)
+            s.edit(sk, max_grow=0, low_latency=True, **kw)
+            s.undo()
+            rep = eng.profile_report()
+            eng.profile(False)
+            prof[tag] = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4), bytes=int(k["bytes"]))
+                         for k in rep["kernels"] if k["kernel"].startswith("window_")}
+            prof[tag]["all_kernels_ms"] = round(sum(k["total_ms"] for k in rep["kernels"]), 3)
+        out.update(journal_kernels_profiled=prof, slot_bytes={"512": serve.window_saved_bytes(512, 512),
+                                                               "big": serve.window_saved_bytes(1080, 1920)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--window", action="store_true", help="the editing-session leg (see the module docstring)")
     ap.add_argument("--window-scaled", action="store_true", help="window edits at a working size (see the module docstring)")
+    ap.add_argument("--window-history", action="store_true", help="the undo journal (see the module docstring)")
+    ap.add_argument("--window-history-parent", action="store_true", help="the history=0 legs of --window-history only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -209,8 +268,12 @@ def main():
     from sketchedit_amd import serve
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     model = make_model(tempfile.mkdtemp())
-    if args.window or args.window_scaled:
-        line = json.dumps(window_scaled_leg(model, args.reps) if args.window_scaled else window_leg(model, args.reps))
+    if args.window or args.window_scaled or args.window_history or args.window_history_parent:
+        if args.window_history or args.window_history_parent:
+            res = window_history_leg(model, args.reps, parent=args.window_history_parent)
+        else:
+            res = window_scaled_leg(model, args.reps) if args.window_scaled else window_leg(model, args.reps)
+        line = json.dumps(res)
         print(line)
         if args.out:
             with open(args.out, "w") as f:
