@@ -257,6 +257,46 @@ size_t se_window_saved_bytes(int hs, int ws);
 int se_window_save_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int hs, int ws, unsigned char* const* slots);
 int se_window_swap_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int hs, int ws, unsigned char* const* slots);
 
+/* ---- locked regions of an editing session ------------------------------------------------------------------
+ * A LOCK PLANE is a (Hi,Wi) uint8 plane in device memory that belongs to a frame; a non-zero byte means "no edit may change
+ * this pixel".  The lock enters the forward where the mask is made, so that a locked pixel is known context for netG and not
+ * a hole it fills: with lock in {0,1} at the forward's size,
+ *     mask = where(lock, 0, netM(image, sketch));  hard = mask > 0.5;  netG(image, image, hard, hard, sketch);
+ *     composed = fine * mask + image * (1 - mask)          -- composed == image, bit for bit, where locked
+ * (generate_fake, models/editline2_model.py:338-370, with the mask netG is given taken from elsewhere than the threshold of
+ * netM alone).  lock_u8 (B,H,W) uint8, device: NULL, or all zero, gives se_inference / se_inference_u8 bit for bit.
+ * se_inference_locked has every optional output of se_inference; flags as there, GRAPH is ignored. */
+int se_inference_locked(se_ctx* ctx, void* stream, const float* image, const float* sketch, const unsigned char* lock_u8,
+                        float* composed_out, float* mask_out, float* hard_out, float* maskim_out, float* coarse_out,
+                        float* fine_out, void* workspace, size_t workspace_bytes, int B, int H, int W, int flags);
+int se_inference_u8_locked(se_ctx* ctx, void* stream, const float* image, const float* sketch, const unsigned char* lock_u8,
+                           unsigned char* rgb_out, unsigned char* mask_u8_out, void* workspace, size_t workspace_bytes, int B,
+                           int H, int W, int flags);
+/* The window entries with locks.  `locks` is a HOST array of B device pointers: locks[b] = the (Hi,Wi) plane of request b's
+ * frame, or NULL (that request has no lock).  Sizes as in the scaled entries; (H, W) == (hs, ws) is the unscaled edit.
+ * the lock at the working size: lock_out (B,H,W) uint8 in {0,1}, 8-byte aligned.  Unscaled: lock_crop > 0.  Scaled:
+ * Image.resize(lock_crop as 'L', (W, H), BICUBIC) > 0 -- the sketch's filter and test, the image's axis tables; bicubic
+ * ringing can only add locked pixels.  A row starts at byte (y0 + r) Wi + x0 of the plane, any alignment; no byte outside a
+ * window's own rows is read.  A NULL plane gives zeros. */
+int se_window_gather_lock_u8(se_ctx* ctx, void* stream, const se_window* wins, const unsigned char* const* locks, int B, int hs,
+                             int ws, int H, int W, unsigned char* lock_out);
+/* se_window_paste_resize_u8 with the rule  frame[y0 + y, x0 + x, :] = RGB[y, x, :]  WHERE  M[y, x] > 0  AND
+ * locks[b][y0 + y, x0 + x] == 0  (RGB, M: rgb and mask_u8 resampled to hs x ws; the arrays themselves when unscaled).  The
+ * second condition is tested in frame space, so the ringing of a resampled mask cannot reach a locked pixel: a locked pixel's
+ * three bytes never change, at any scale. */
+int se_window_paste_locked_u8(se_ctx* ctx, void* stream, const se_window* wins, const unsigned char* const* locks, int B, int hs,
+                              int ws, int H, int W, const unsigned char* rgb, const unsigned char* mask_u8);
+/* se_edit_window_scaled_u8 with locks: gather, lock gather, the forward of se_inference_u8_locked, border, and the locked
+ * paste if commit != 0.  The border counts are taken on the working-size mask, where locked pixels are 0.  With every entry of
+ * locks NULL, or every plane zero: the frame, rgb_out, mask_u8_out and the counts of se_edit_window_scaled_u8 / _u8, byte for
+ * byte.  Refused before anything is enqueued (frames untouched, se_last_error names the argument): everything the scaled
+ * entries refuse, and -- where the call writes frames -- a lock plane that shares a byte with a frame of the call.
+ * Setting a lock is not an edit: the journal (6f) neither sees nor restores lock planes. */
+int se_edit_window_locked_u8(se_ctx* ctx, void* stream, const se_window* wins, const unsigned char* const* locks, int B, int hs,
+                             int ws, int H, int W, unsigned char* rgb_out, unsigned char* mask_u8_out, int* hits_out, int commit,
+                             void* workspace, size_t workspace_bytes, int flags);
+size_t se_edit_window_locked_u8_workspace_bytes(se_ctx* ctx, int B, int hs, int ws, int H, int W);
+
 /* Host only (no HIP call, no ctx): the coefficient table the resize uses for one axis.  Returns ksize, the taps per output
  * (-1: bad arguments); when bounds (2*out ints: first input index, tap count) and k (cap >= out*ksize ints, fixed point
  * with 22 fractional bits, rows zero padded to ksize) are given, fills them.  Lets a test compare the tables with Pillow's. */

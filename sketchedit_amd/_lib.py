@@ -38,7 +38,9 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
            "se_resize_u8", "se_prepare_u8", "se_edit_u8", "se_edit_u8_workspace_bytes", "se_resample_coeffs",
            "se_window_gather_u8", "se_window_border_u8", "se_window_paste_u8", "se_edit_window_u8", "se_edit_window_u8_workspace_bytes",
            "se_window_gather_resize_u8", "se_window_paste_resize_u8", "se_edit_window_scaled_u8", "se_edit_window_scaled_u8_workspace_bytes",
-           "se_window_saved_bytes", "se_window_save_u8", "se_window_swap_u8"]
+           "se_window_saved_bytes", "se_window_save_u8", "se_window_swap_u8",
+           "se_inference_locked", "se_inference_u8_locked", "se_window_gather_lock_u8", "se_window_paste_locked_u8",
+           "se_edit_window_locked_u8", "se_edit_window_locked_u8_workspace_bytes"]
 
 
 class SketchEditHipError(RuntimeError):
@@ -190,6 +192,18 @@ def load_library():
         lib.se_window_save_u8.restype = ci
         lib.se_window_swap_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ctypes.POINTER(vp)]
         lib.se_window_swap_u8.restype = ci
+        lib.se_inference_locked.argtypes = [vp, vp, c_f, c_f, vp, c_f, c_f, c_f, c_f, c_f, c_f, vp, sz, ci, ci, ci, ci]
+        lib.se_inference_locked.restype = ci
+        lib.se_inference_u8_locked.argtypes = [vp, vp, c_f, c_f, vp, vp, vp, vp, sz, ci, ci, ci, ci]
+        lib.se_inference_u8_locked.restype = ci
+        lib.se_window_gather_lock_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ci, ci, ci, ci, ci, vp]
+        lib.se_window_gather_lock_u8.restype = ci
+        lib.se_window_paste_locked_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ci, ci, ci, ci, ci, vp, vp]
+        lib.se_window_paste_locked_u8.restype = ci
+        lib.se_edit_window_locked_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, sz, ci]
+        lib.se_edit_window_locked_u8.restype = ci
+        lib.se_edit_window_locked_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci, ci]
+        lib.se_edit_window_locked_u8_workspace_bytes.restype = sz
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -435,8 +449,12 @@ class Engine:
         return (FLAG_LOW_LATENCY if self.is_low_latency(B, H, W, low_latency) else 0) | (FLAG_GRAPH if graph else 0) | \
             (FLAG_BF16 if self.precision == "bf16" else 0) | (FLAG_CONSERVATIVE if self.conservative else 0)
 
-    def inference(self, image, sketch, flags, visualize=False, out=None, low_latency=None, graph=False):
+    def inference(self, image, sketch, flags, visualize=False, out=None, low_latency=None, graph=False, lock=None):
         """-> dict(composed, mask[, hard, maskim, coarse, fine]).  `out` may hold preallocated composed/mask.
+
+        lock: a (B,H,W) uint8 tensor on the device, non-zero = locked -- the soft mask is 0 there before the
+        threshold, so netG sees those pixels as known context and composed keeps the image's bits (se_inference_locked;
+        graph=True is ignored with a lock).
 
         low_latency: None = by size (small calls), True / False = forced.  graph=True replays the forward from a
         captured hipGraph: that needs stable pointers, so the inputs are copied into buffers this Engine keeps per
@@ -444,6 +462,9 @@ class Engine:
         same shape."""
         import torch
         _check_dev(image, sketch)
+        if lock is not None:
+            self._check_lock(lock, image)
+            graph = False
         if graph and out is not None:
             raise SketchEditHipError("graph=True replays into buffers the Engine keeps per shape: `out=` cannot be honoured "
                                      "(copy from the returned tensors, or call without graph=True)")
@@ -468,10 +489,23 @@ class Engine:
             with self._graph_lock:
                 return self._inference_graph(image, sketch, flags, visualize, ws, B, H, W, new_outputs)
         r = new_outputs(out)
-        self._call_inference(image, sketch, r, ws, B, H, W, flags, self._stream())
+        self._call_inference(image, sketch, r, ws, B, H, W, flags, self._stream(), lock)
         return r
 
-    def _call_inference(self, image, sketch, r, ws, B, H, W, flags, stream):
+    @staticmethod
+    def _check_lock(lock, image):
+        _check_dev_u8(lock)
+        B, _, H, W = image.shape
+        if tuple(lock.shape) != (B, H, W):
+            raise SketchEditHipError("lock: expected a (B,H,W) uint8 plane of the images' size")
+
+    def _call_inference(self, image, sketch, r, ws, B, H, W, flags, stream, lock=None):
+        if lock is not None:
+            if self.lib.se_inference_locked(self.h, stream, _ptr(image), _ptr(sketch), _ptr(lock), _ptr(r["composed"]),
+                                            _ptr(r["mask"]), _ptr(r.get("hard")), _ptr(r.get("maskim")), _ptr(r.get("coarse")),
+                                            _ptr(r.get("fine")), _ptr(ws), ws.numel(), B, H, W, flags):
+                self._err("se_inference_locked")
+            return
         if self.lib.se_inference(self.h, stream, _ptr(image), _ptr(sketch), _ptr(r["composed"]), _ptr(r["mask"]),
                                  _ptr(r.get("hard")), _ptr(r.get("maskim")), _ptr(r.get("coarse")), _ptr(r.get("fine")),
                                  _ptr(ws), ws.numel(), B, H, W, flags):
@@ -499,18 +533,24 @@ class Engine:
         cur.wait_stream(gs)
         return r
 
-    def inference_u8(self, image, sketch, flags, low_latency=None):
+    def inference_u8(self, image, sketch, flags, low_latency=None, lock=None):
         """The forward with test.py:25-27's quantisation fused into its last kernel -> (rgb (B,H,W,3) uint8, mask (B,H,W)
-        uint8): what test.py writes to disk, without an fp32 output tensor or a separate pass."""
+        uint8): what test.py writes to disk, without an fp32 output tensor or a separate pass.  lock: as `inference`."""
         import torch
         _check_dev(image, sketch)
+        if lock is not None:
+            self._check_lock(lock, image)
         B, _, H, W = image.shape
         ws = self.workspace(B, H, W)
         rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=image.device)
         m8 = torch.empty((B, H, W), dtype=torch.uint8, device=image.device)
         flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
-        if self.lib.se_inference_u8(self.h, self._stream(), _ptr(image), _ptr(sketch), _ptr(rgb), _ptr(m8), _ptr(ws),
-                                    ws.numel(), B, H, W, flags):
+        if lock is not None:
+            if self.lib.se_inference_u8_locked(self.h, self._stream(), _ptr(image), _ptr(sketch), _ptr(lock), _ptr(rgb), _ptr(m8),
+                                               _ptr(ws), ws.numel(), B, H, W, flags):
+                self._err("se_inference_u8_locked")
+        elif self.lib.se_inference_u8(self.h, self._stream(), _ptr(image), _ptr(sketch), _ptr(rgb), _ptr(m8), _ptr(ws),
+                                      ws.numel(), B, H, W, flags):
             self._err("se_inference_u8")
         return rgb, m8
 
@@ -778,6 +818,67 @@ class Engine:
         """se_window_swap_u8, in place: the hs x ws rectangle at origins[i] of frames[i] <-> slots[i] (as window_save_u8 made
         it).  Overlapping windows of one frame in one call are refused."""
         self._journal(self.lib.se_window_swap_u8, "se_window_swap_u8", frames, origins, window_hw, slots)
+
+    # ---- locked regions of a session (DESIGN.md 6g): locks[i] = the (Hi,Wi) uint8 plane of frames[i] on the device, or None --
+    @staticmethod
+    def _locks(locks, frames):
+        if len(locks) != len(frames):
+            raise SketchEditHipError("locked window call: one lock plane (or None) per request")
+        for t, f in zip(locks, frames):
+            if t is not None:
+                _check_dev_u8(t)
+                if tuple(t.shape) != tuple(f.shape[:2]):
+                    raise SketchEditHipError("locked window call: a lock plane is the frame's (Hi,Wi) uint8 plane")
+        return (ctypes.c_void_p * len(locks))(*[None if t is None else t.data_ptr() for t in locks])
+
+    def window_gather_lock_u8(self, frames, origins, locks, window_hw, H, W):
+        """se_window_gather_lock_u8: the hs x ws window at origins[i] of every lock plane -> (B,H,W) uint8 in {0,1} at the
+        working size H x W: `crop > 0` when unscaled, else Pillow's BICUBIC resize of the crop, `> 0`.  None -> zeros."""
+        import torch
+        hs, ws = (int(v) for v in window_hw)
+        wins = self._windows(frames, origins)
+        ptrs = self._locks(locks, frames)
+        out = torch.empty((len(frames), H, W), dtype=torch.uint8, device=frames[0].device)
+        if self.lib.se_window_gather_lock_u8(self.h, self._stream(), wins, ptrs, len(frames), hs, ws, H, W, _ptr(out)):
+            self._err("se_window_gather_lock_u8")
+        return out
+
+    def window_paste_locked_u8(self, frames, origins, locks, window_hw, rgb, mask_u8):
+        """se_window_paste_locked_u8, in place: window_paste_resize_u8 (window_paste_u8 when the sizes agree) that leaves
+        every pixel whose byte of its frame's lock plane is non-zero untouched, whatever the mask says."""
+        _check_dev_u8(rgb, mask_u8)
+        hs, ws = (int(v) for v in window_hw)
+        B, H, W = mask_u8.shape
+        if tuple(rgb.shape) != (B, H, W, 3) or len(frames) != B:
+            raise SketchEditHipError("window_paste_locked_u8: expected rgb (B,H,W,3), mask_u8 (B,H,W) and one frame per request")
+        wins = self._windows(frames, origins)
+        ptrs = self._locks(locks, frames)
+        if self.lib.se_window_paste_locked_u8(self.h, self._stream(), wins, ptrs, B, hs, ws, H, W, _ptr(rgb), _ptr(mask_u8)):
+            self._err("se_window_paste_locked_u8")
+
+    def edit_window_locked_u8(self, frames, origins, sketches, locks, window_hw, H, W, flags, commit=True, low_latency=None):
+        """se_edit_window_locked_u8: edit_window_scaled_u8 (edit_window_u8 when (H, W) == window_hw) in which no edit changes
+        a locked pixel: the lock enters the forward (inference_u8(lock=)) and the paste.  -> (rgb, mask_u8, hits) as there."""
+        import torch
+        hs, ws = (int(v) for v in window_hw)
+        wins = self._windows(frames, origins, sketches)
+        ptrs = self._locks(locks, frames)
+        for sk in sketches:
+            if tuple(sk.shape) != (hs, ws):
+                raise SketchEditHipError("edit_window_locked_u8: a sketch is the window's (hs,ws) uint8 plane")
+        B, dev = len(frames), frames[0].device
+        need = self.lib.se_edit_window_locked_u8_workspace_bytes(self.h, B, hs, ws, H, W)
+        if need == 0:
+            self._err("se_edit_window_locked_u8_workspace_bytes")
+        ws_t = self._workspace_bytes(need)
+        rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        m8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        hits = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
+        if self.lib.se_edit_window_locked_u8(self.h, self._stream(), wins, ptrs, B, hs, ws, H, W, _ptr(rgb), _ptr(m8), _ptr(hits),
+                                             1 if commit else 0, _ptr(ws_t), ws_t.numel(), flags):
+            self._err("se_edit_window_locked_u8")
+        return rgb, m8, hits
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):
         """Inference into ONE (B,4,H,W) buffer `out`: planes 0-2 composed, plane 3 the soft mask -- the unit the

@@ -714,7 +714,8 @@ Act decoder(Plan& P, const std::string& p, Act& in, const float* src1 = nullptr,
 }
 
 int small(Plan& P, const char* name, Act& in, int mode, float* out_nchw, float* hard, const float* img,
-          const float* mask, float* xnow, float* composed, int no_mask_coarse, long packed_bs = 0) {
+          const float* mask, float* xnow, float* composed, int no_mask_coarse, long packed_bs = 0,
+          const unsigned char* lock = nullptr) {
   if (P.rc) return P.rc;
   se_ctx* c = P.c;
   if (!c->dry) {
@@ -727,6 +728,7 @@ int small(Plan& P, const char* name, Act& in, int mode, float* out_nchw, float* 
     sp.mode = mode; sp.out_nchw = out_nchw; sp.hard = hard; sp.img = img; sp.mask = mask; sp.xnow = xnow;
     sp.composed = composed; sp.no_mask_coarse = no_mask_coarse;
     if (mode == 3) { sp.rgb8 = c->rgb8; sp.m8 = c->m8; }
+    if (mode == 0) sp.lock = lock;
     if (packed_bs) {      // SE_FLAG_PACKED_OUT: soft mask and composite live in one (B,4,H,W) buffer
       if (mode == 0) sp.out_bs = packed_bs;
       if (mode == 3) { sp.mask_bs = packed_bs; sp.comp_bs = packed_bs; }
@@ -740,9 +742,9 @@ int small(Plan& P, const char* name, Act& in, int mode, float* out_nchw, float* 
   return 0;
 }
 
-// MDGenerator.forward, editline2_g.py:59-94
+// MDGenerator.forward, editline2_g.py:59-94.  lock (B,H,W) uint8 or null: the mask is 0 where it is non-zero
 int plan_netM(se_ctx* c, const float* image, const float* sketch, float* mask_out, float* hard_out, float* maskim_out,
-              int B, int H, int W, long packed_bs = 0) {
+              int B, int H, int W, long packed_bs = 0, const unsigned char* lock = nullptr) {
   Plan P(c, c->M, B);
   c->cur_net = SE_NET_M;
   Act in = P.alloc(H, W, 4);
@@ -756,7 +758,7 @@ int plan_netM(se_ctx* c, const float* image, const float* sketch, float* mask_ou
     small(P, "conv17", d, 1, maskim_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
   }
   Act d = decoder(P, "conv_mask_", x10);
-  small(P, "conv_mask_17", d, 0, mask_out, hard_out, nullptr, nullptr, nullptr, nullptr, 0, packed_bs);
+  small(P, "conv_mask_17", d, 0, mask_out, hard_out, nullptr, nullptr, nullptr, nullptr, 0, packed_bs, lock);
   return P.rc;
 }
 
@@ -1400,7 +1402,7 @@ namespace {
 // netM -> threshold -> netG -> composite, enqueued on `stream` (and, in low-latency mode, the ctx's side stream)
 int enqueue_inference(se_ctx* c, void* stream, const float* image, const float* sketch, float* composed_out, float* mask_out,
                       float* hard_out, float* maskim_out, float* coarse_out, float* fine_out, void* ws, size_t ws_bytes,
-                      int B, int H, int W, int flags) {
+                      int B, int H, int W, int flags, const unsigned char* lock8 = nullptr) {
   // the hard mask lives at the end of the workspace for the whole call
   const size_t plane = ((size_t)B * H * W * 4 + 255) & ~(size_t)255;
   float* hard_all = hard_out ? hard_out : (float*)((char*)ws + ws_bytes - plane);
@@ -1419,7 +1421,8 @@ int enqueue_inference(se_ctx* c, void* stream, const float* image, const float* 
     const float *img = image + b0 * 3 * HW, *sk = sketch + b0 * HW;
     float *hard = hard_all + b0 * HW, *mk = mask_out + b0 * mask_bs;
     begin_call(c, stream, flags);
-    int rc = plan_netM(c, img, sk, mk, hard, maskim_out ? maskim_out + b0 * 3 * HW : nullptr, bb, H, W, packed_bs);     // editline2_model.py:339,346-347
+    int rc = plan_netM(c, img, sk, mk, hard, maskim_out ? maskim_out + b0 * 3 * HW : nullptr, bb, H, W, packed_bs,     // editline2_model.py:339,346-347
+                       lock8 ? lock8 + b0 * HW : nullptr);
     if (rc) return rc;
     if (carve(c, pk, ws, ws_bytes, plane)) return 1;
     // netG(inputs, inputs, mask_inpaint, mask_inpaint, line)  :366-368 ; composite with the soft mask :132
@@ -1484,13 +1487,30 @@ int se_inference(se_ctx* c, void* stream, const float* image, const float* sketc
   return 0;
 }
 
+// se_inference with a lock plane: the soft mask is 0 where lock_u8 is non-zero, before the threshold
+int se_inference_locked(se_ctx* c, void* stream, const float* image, const float* sketch, const unsigned char* lock_u8,
+                        float* composed_out, float* mask_out, float* hard_out, float* maskim_out, float* coarse_out, float* fine_out,
+                        void* ws, size_t ws_bytes, int B, int H, int W, int flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (check_dims(c, B, H, W)) return 1;
+  if (!image || !sketch || !composed_out || (!mask_out && !(flags & SE_FLAG_PACKED_OUT)) || !ws) return fail(c, "null pointer argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
+  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  return enqueue_inference(c, stream, image, sketch, composed_out, mask_out, hard_out, maskim_out, coarse_out, fine_out, ws,
+                           ws_bytes, B, H, W, flags & ~SE_FLAG_GRAPH, lock_u8);
+}
+
 // The forward with the output quantisation of test.py:25-27 fused into its last kernel: the composite and the soft mask
 // leave the device as uint8 only (a quarter of the fp32 bytes, no separate pass); the soft mask needed between netM and
 // the final composite lives in the workspace.
 namespace {
 // `tail_planes` fp32 (B,H,W) planes at the end of the workspace are the caller's; the soft and hard masks sit in front of them
+// (`_locked` = the ctx's mutex is held; lock8 = the (B,H,W) lock plane of DESIGN.md 6g, or null)
 int inference_u8_locked(se_ctx* c, void* stream, const float* image, const float* sketch, unsigned char* rgb_out,
-                        unsigned char* mask_u8_out, void* ws, size_t ws_bytes, int B, int H, int W, int flags, int tail_planes) {
+                        unsigned char* mask_u8_out, void* ws, size_t ws_bytes, int B, int H, int W, int flags, int tail_planes,
+                        const unsigned char* lock8 = nullptr) {
   flags &= ~(SE_FLAG_GRAPH | SE_FLAG_PACKED_OUT);
   const size_t plane = ((size_t)B * H * W * 4 + 255) & ~(size_t)255;
   const size_t tail = (2 + (size_t)tail_planes) * plane;
@@ -1507,7 +1527,7 @@ int inference_u8_locked(se_ctx* c, void* stream, const float* image, const float
     const float *img = image + b0 * 3 * HW, *sk = sketch + b0 * HW;
     float *hard = hard_all + b0 * HW, *soft = soft_all + b0 * HW;
     begin_call(c, stream, flags);
-    int rc = plan_netM(c, img, sk, soft, hard, nullptr, bb, H, W);
+    int rc = plan_netM(c, img, sk, soft, hard, nullptr, bb, H, W, 0, lock8 ? lock8 + b0 * HW : nullptr);
     if (rc) return rc;
     if (carve(c, pk, ws, ws_bytes, tail)) return 1;
     c->rgb8 = rgb_out + b0 * 3 * HW; c->m8 = mask_u8_out ? mask_u8_out + b0 * HW : nullptr;
@@ -1528,6 +1548,18 @@ int se_inference_u8(se_ctx* c, void* stream, const float* image, const float* sk
   c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
   c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
   return inference_u8_locked(c, stream, image, sketch, rgb_out, mask_u8_out, ws, ws_bytes, B, H, W, flags, 0);
+}
+
+int se_inference_u8_locked(se_ctx* c, void* stream, const float* image, const float* sketch, const unsigned char* lock_u8,
+                           unsigned char* rgb_out, unsigned char* mask_u8_out, void* ws, size_t ws_bytes, int B, int H, int W, int flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (check_dims(c, B, H, W)) return 1;
+  if (!image || !sketch || !rgb_out || !ws) return fail(c, "null pointer argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
+  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  return inference_u8_locked(c, stream, image, sketch, rgb_out, mask_u8_out, ws, ws_bytes, B, H, W, flags, 0, lock_u8);
 }
 
 // data/testimage_dataset.py:89-111 on the device (table lookup; see se_create)
@@ -1802,7 +1834,7 @@ int gather_resize_locked(se_ctx* c, hipStream_t st, const se_window* d, int B, i
 // rgb (B,H,W,3), m8 (B,H,W) -> resampled to hs x ws and pasted into the windows (not both sizes equal).  The vertical pass
 // always runs (it carries the paste): where hs == H its table is the identity.
 int paste_resize_locked(se_ctx* c, hipStream_t st, const se_window* d, int B, int hs, int ws, int H, int W, const unsigned char* rgb,
-                        const unsigned char* m8, unsigned char* mid) {
+                        const unsigned char* m8, unsigned char* mid, bool locked = false) {
   const bool need_h = ws != W;
   const int io[2][2] = {{H, hs}, {W, ws}};
   const se_ctx::ResampleTable* t[2] = {nullptr, nullptr};
@@ -1819,16 +1851,72 @@ int paste_resize_locked(se_ctx* c, hipStream_t st, const se_window* d, int B, in
     HIPCHK(c, launch_resample_h(m8, dk, dk + 2 * (size_t)ws, t[1]->host.data(), t[1]->ksize, B, H, W, ws, 1, o, st));
     rgb = mid_rgb; m8 = mid_m;
   }
-  HIPCHK(c, launch_window_paste_v(d, rgb, m8, t[0]->dev, t[0]->dev + 2 * (size_t)hs, t[0]->ksize, B, H, hs, P, ws, st));
+  HIPCHK(c, launch_window_paste_v(d, rgb, m8, t[0]->dev, t[0]->dev + 2 * (size_t)hs, t[0]->ksize, B, H, hs, P, ws, st, locked));
   return 0;
 }
 
-// [uint8 result | uint8 mask | counts | intermediates of the resample ends (scaled only) | the workspace of se_inference_u8io:
-// arenas, masks, fp32 image and sketch at its end].  hs x ws == H x W: the window edit at the frame's own resolution.
+// ---- locked regions: locks = a HOST array of B device pointers, request b's (Hi,Wi) uint8 lock plane or null
+
+bool any_lock(const unsigned char* const* locks, int B) {
+  for (int i = 0; locks && i < B; ++i)
+    if (locks[i]) return true;
+  return false;
+}
+
+// a call that writes frames: no lock plane may share a byte with one of them (the paste reads the plane while it writes)
+int win_check_locks(se_ctx* c, const se_window* wins, const unsigned char* const* locks, int B) {
+  for (int i = 0; i < B; ++i) {
+    if (!locks[i]) continue;
+    const uintptr_t l0 = (uintptr_t)locks[i], l1 = l0 + (size_t)wins[i].Hi * wins[i].Wi;
+    for (int j = 0; j < B; ++j) {
+      const uintptr_t f0 = (uintptr_t)wins[j].frame_u8, f1 = f0 + (size_t)wins[j].Hi * wins[j].Wi * 3;
+      if (l0 < f1 && f0 < l1) return fail(c, "locks[%d] overlaps the frame of wins[%d]", i, j);
+    }
+  }
+  return 0;
+}
+
+// the records of a locked call: the requests, then B records whose frame_u8 is the request's lock plane (as the journal's
+// slots travel); one group of the ctx's ring
+const se_window* win_put_locks(se_ctx* c, hipStream_t st, const se_window* wins, const unsigned char* const* locks, int B) {
+  std::vector<se_window> recs(wins, wins + B);
+  for (int i = 0; i < B; ++i) recs.push_back(se_window{const_cast<unsigned char*>(locks[i]), nullptr, 0, 0, 0, 0});
+  return win_put(c, st, recs.data(), 2 * B);
+}
+
+size_t lock_mid_bytes(int B, int hs, int W) { return pad256((size_t)B * hs * W); }
+
+// the hs x ws windows of the lock planes -> lock_out (B,H,W) in {0, 1} at the working size; d = the 2 B records.  Unscaled: one
+// gather launch.  Scaled: the sketch's resample -- BICUBIC, then > 0 -- over the plane's rows, with the axis tables the image
+// uses; mid = (B,hs,W) bytes where hs != H.
+int lock_gather_locked(se_ctx* c, hipStream_t st, const se_window* d, int B, int hs, int ws, int H, int W, unsigned char* lock_out,
+                       unsigned char* mid) {
+  if (hs == H && ws == W) {
+    HIPCHK(c, launch_window_lock_gather(d, lock_out, B, H, W, st));
+    return 0;
+  }
+  const bool need_v = hs != H;
+  const int io[2][2] = {{ws, W}, {hs, H}};
+  const se_ctx::ResampleTable* t[2] = {nullptr, nullptr};
+  if (rs_tables_n(c, need_v ? 2 : 1, io, t)) return 1;
+  ResizeOut o{RESIZE_OUT_LOCK_U8, lock_out, nullptr, nullptr, H, W};
+  ResizeOut oh = o;
+  if (need_v) { oh.mode = RESIZE_OUT_U8; oh.u8 = mid; oh.H = hs; }
+  HIPCHK(c, launch_window_lock_resample_h(d, t[0]->dev, t[0]->dev + 2 * (size_t)W, t[0]->host.data(), t[0]->ksize, B, hs, ws, W, oh, st));
+  if (need_v) HIPCHK(c, launch_resample_v(mid, t[1]->dev, t[1]->dev + 2 * (size_t)H, t[1]->ksize, B, hs, H, W, 1, o, st));
+  return 0;
+}
+
+// [uint8 result | uint8 mask | counts | working-size lock plane (a call with a lock only) | intermediates of the resample ends
+// (scaled only) | the workspace of se_inference_u8io: arenas, masks, fp32 image and sketch at its end].  hs x ws == H x W: the
+// window edit at the frame's own resolution.  locks null, or all its entries null: the edit without locks.
 int edit_window_locked(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W, unsigned char* rgb_out,
-                       unsigned char* mask_u8_out, int* hits_out, int commit, void* wsp, size_t ws_bytes, int flags) {
+                       unsigned char* mask_u8_out, int* hits_out, int commit, void* wsp, size_t ws_bytes, int flags,
+                       const unsigned char* const* locks = nullptr) {
   const bool scaled = hs != H || ws != W;
   if (win_check(c, wins, B, H, W, hs, ws, true, commit != 0)) return 1;
+  const bool locked = any_lock(locks, B);
+  if (locked && commit && win_check_locks(c, wins, locks, B)) return 1;
   if (!wsp) return fail(c, "null pointer argument: workspace");
   if (!aligned_to(wsp, 256)) return fail(c, "workspace must be 256-byte aligned");
   if (!aligned_to(rgb_out, 4) || !aligned_to(mask_u8_out, 4) || !aligned_to(hits_out, 4)) return fail(c, "rgb_out / mask_u8_out / hits_out must be 4-byte aligned");
@@ -1837,31 +1925,34 @@ int edit_window_locked(se_ctx* c, void* stream, const se_window* wins, int B, in
   c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
   const size_t plane = pad256((size_t)B * H * W * 4), rgbw = pad256((size_t)B * H * W * 3), mw = pad256((size_t)B * H * W),
                hw = pad256((size_t)B * 4 * sizeof(int)),
-               midw = scaled ? std::max(gather_mid_bytes(B, hs, W), paste_mid_bytes(B, H, ws)) : 0;
-  if (ws_bytes < rgbw + mw + hw + midw + 6 * plane) return fail(c, "workspace too small: %zu bytes", ws_bytes);
+               midw = scaled ? std::max(gather_mid_bytes(B, hs, W), paste_mid_bytes(B, H, ws)) : 0, lockw = locked ? mw : 0;
+  if (ws_bytes < rgbw + mw + hw + lockw + midw + 6 * plane) return fail(c, "workspace too small: %zu bytes", ws_bytes);
   unsigned char* rgb = rgb_out ? rgb_out : (unsigned char*)wsp;
   unsigned char* m8 = mask_u8_out ? mask_u8_out : (unsigned char*)wsp + rgbw;
   int* hits = hits_out ? hits_out : (int*)((char*)wsp + rgbw + mw);
-  unsigned char* mid = (unsigned char*)wsp + rgbw + mw + hw;
-  char* fws = (char*)wsp + rgbw + mw + hw + midw;
-  const size_t fws_bytes = ws_bytes - (rgbw + mw + hw + midw);
+  unsigned char* lock8 = locked ? (unsigned char*)wsp + rgbw + mw + hw : nullptr;
+  unsigned char* mid = (unsigned char*)wsp + rgbw + mw + hw + lockw;
+  char* fws = (char*)wsp + rgbw + mw + hw + lockw + midw;
+  const size_t fws_bytes = ws_bytes - (rgbw + mw + hw + lockw + midw);
   float* image = (float*)(fws + fws_bytes - 4 * plane);      // where se_inference_u8io keeps them
   float* sketch = (float*)(fws + fws_bytes - plane);
   if (!aligned_to(image, 16)) return fail(c, "workspace_bytes must be a multiple of 16");
   const hipStream_t st = (hipStream_t)stream;
   if (scaled && rs_enter(c, st)) return 1;
   set_profiler(&c->prof);
-  const se_window* d = win_put(c, st, wins, B);
+  const se_window* d = locked ? win_put_locks(c, st, wins, locks, B) : win_put(c, st, wins, B);
   if (!d) return 1;
   if (scaled) {
     if (gather_resize_locked(c, st, d, B, hs, ws, H, W, image, sketch, mid)) return 1;
   } else {
     HIPCHK(c, launch_window_gather(d, c->lut8, image, sketch, B, H, W, st));
   }
-  if (inference_u8_locked(c, stream, image, sketch, rgb, m8, fws, fws_bytes, B, H, W, flags, 4)) return 1;
+  if (locked && lock_gather_locked(c, st, d, B, hs, ws, H, W, lock8, mid)) return 1;
+  if (inference_u8_locked(c, stream, image, sketch, rgb, m8, fws, fws_bytes, B, H, W, flags, 4, lock8)) return 1;
   set_profiler(&c->prof);
   HIPCHK(c, launch_window_border(d, m8, hits, B, H, W, hs, ws, st));
-  if (commit && scaled) return paste_resize_locked(c, st, d, B, hs, ws, H, W, rgb, m8, mid);
+  if (commit && scaled) return paste_resize_locked(c, st, d, B, hs, ws, H, W, rgb, m8, mid, locked);
+  // (unscaled: m8 is 0 at a locked pixel, so the rule's second condition is implied and the paste need not read the planes)
   if (commit) HIPCHK(c, launch_window_paste(d, rgb, m8, B, H, W, st));
   return 0;
 }
@@ -1990,6 +2081,67 @@ int se_edit_window_scaled_u8(se_ctx* c, void* stream, const se_window* wins, int
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
   return edit_window_locked(c, stream, wins, B, hs, ws, H, W, rgb_out, mask_u8_out, hits_out, commit, workspace, workspace_bytes, flags);
+}
+
+// ---- locked regions --------------------------------------------------------------------------------
+int se_window_gather_lock_u8(se_ctx* c, void* stream, const se_window* wins, const unsigned char* const* locks, int B, int hs, int ws,
+                             int H, int W, unsigned char* lock_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (win_check(c, wins, B, H, W, hs, ws, false, false)) return 1;
+  if (!locks || !lock_out) return fail(c, "null pointer argument: locks / lock_out");
+  if (!aligned_to(lock_out, 8)) return fail(c, "lock_out must be 8-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = (hipStream_t)stream;
+  unsigned char* mid = nullptr;
+  if (hs != H || ws != W) {
+    if (rs_enter(c, st)) return 1;
+    if (hs != H && !(mid = rs_scratch(c, lock_mid_bytes(B, hs, W)))) return 1;
+  }
+  set_profiler(&c->prof);
+  const se_window* d = win_put_locks(c, st, wins, locks, B);
+  if (!d) return 1;
+  return lock_gather_locked(c, st, d, B, hs, ws, H, W, lock_out, mid);
+}
+
+int se_window_paste_locked_u8(se_ctx* c, void* stream, const se_window* wins, const unsigned char* const* locks, int B, int hs, int ws,
+                              int H, int W, const unsigned char* rgb, const unsigned char* mask_u8) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (win_check(c, wins, B, H, W, hs, ws, false, true)) return 1;
+  if (!locks) return fail(c, "null pointer argument: locks");
+  if (!rgb || !mask_u8) return fail(c, "null pointer argument: rgb / mask_u8");
+  if (!aligned_to(rgb, 4) || !aligned_to(mask_u8, 4)) return fail(c, "rgb / mask_u8 must be 4-byte aligned");
+  if (win_check_locks(c, wins, locks, B)) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = (hipStream_t)stream;
+  const bool scaled = hs != H || ws != W;
+  unsigned char* mid = nullptr;
+  if (scaled) {
+    if (rs_enter(c, st)) return 1;
+    if (ws != W && !(mid = rs_scratch(c, paste_mid_bytes(B, H, ws)))) return 1;
+  }
+  set_profiler(&c->prof);
+  const se_window* d = win_put_locks(c, st, wins, locks, B);
+  if (!d) return 1;
+  if (scaled) return paste_resize_locked(c, st, d, B, hs, ws, H, W, rgb, mask_u8, mid, true);
+  HIPCHK(c, launch_window_paste(d, rgb, mask_u8, B, H, W, st, true));
+  return 0;
+}
+
+size_t se_edit_window_locked_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws, int H, int W) {
+  const size_t base = se_edit_window_scaled_u8_workspace_bytes(c, B, hs, ws, H, W);
+  return base ? base + pad256((size_t)B * H * W) : 0;
+}
+
+int se_edit_window_locked_u8(se_ctx* c, void* stream, const se_window* wins, const unsigned char* const* locks, int B, int hs, int ws,
+                             int H, int W, unsigned char* rgb_out, unsigned char* mask_u8_out, int* hits_out, int commit,
+                             void* workspace, size_t workspace_bytes, int flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!locks) return fail(c, "null pointer argument: locks");
+  return edit_window_locked(c, stream, wins, B, hs, ws, H, W, rgb_out, mask_u8_out, hits_out, commit, workspace, workspace_bytes,
+                            flags, locks);
 }
 
 // ---- the undo journal of a session ---------------------------------------------------------------

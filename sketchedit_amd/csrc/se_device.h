@@ -240,6 +240,33 @@ DEVFN void frag_offsets(int lane, int& off0, int& off1) {
   off1 = (lane & 15) * 128 + (((4 + (lane >> 4)) ^ swz) << 4);
 }
 
+// ---- bytes at any alignment, read inside a span only (the window kernels: se_window.hip, se_resize.hip) ---------------
+// the dword at the 4-byte aligned address p, of which only the bytes inside [lo, hi) are read (the others are 0)
+DEVFN unsigned load_dword_within(const unsigned char* p, const unsigned char* lo, const unsigned char* hi) {
+  if (p >= lo && p + 4 <= hi) return *(const unsigned*)p;
+  unsigned v = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (p + i >= lo && p + i < hi) v |= (unsigned)p[i] << (8 * i);
+  return v;
+}
+// the 4 bytes at `a` (any alignment), of which only those inside [lo, hi) are read (the others are 0): two aligned dwords
+// and a byte shift
+DEVFN unsigned load4_within(const unsigned char* a, const unsigned char* lo, const unsigned char* hi) {
+  const unsigned char* a0 = (const unsigned char*)((size_t)a & ~(size_t)3);
+  const int sh = (int)((size_t)a & 3) * 8;
+  const unsigned d0 = load_dword_within(a0, lo, hi);
+  if (!sh) return d0;
+  return (d0 >> sh) | (load_dword_within(a0 + 4, lo, hi) << (32 - sh));
+}
+// the bytes of `sel` (one per pixel, 4 pixels) whose byte of `lk` is non-zero, cleared
+DEVFN unsigned clear_locked(unsigned sel, unsigned lk) {
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+    if ((lk >> (8 * p)) & 255u) sel &= ~(255u << (8 * p));
+  return sel;
+}
+
 // ---- host: launch profiler scope -------------------------------------------------------------------
 struct ProfScope {
   hipStream_t st;

@@ -18,7 +18,8 @@ namespace se {
 enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL_WINO_N192, PL_WINO_N96, PL_WINO_UP96, PL_SMALL_CONV, PL_PACK, PL_COLREDUCE,
                  PL_ATT_PREP, PL_ATT_SCORE, PL_ATT_SOFTMAX, PL_ATT_BOXSUM, PL_ATT_PV, PL_LAYOUT,
                  PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_WINDOW_GATHER, PL_WINDOW_BORDER, PL_WINDOW_PASTE,
-                 PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_COUNT };
+                 PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
+                 PL_WINDOW_PASTE_V_LOCKED, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -266,6 +267,8 @@ struct SmallConvParams {
   // mode 3: the output quantisation of test.py:25-27 fused into this last kernel (either may be null)
   unsigned char* rgb8; // (B,H,W,3) uint8 = trunc((composed + 1) / 2 * 255)
   unsigned char* m8;   // (B,H,W)   uint8 = trunc(soft mask * 255)
+  // mode 0: (B,H,W) uint8 lock plane of an editing session (may be null): the mask is 0 where it is non-zero
+  const unsigned char* lock;
 };
 hipError_t launch_small_conv(const SmallConvParams& p, hipStream_t st);
 
@@ -350,8 +353,9 @@ int att_stream_xt_tail();
 // ---------------------------------------------------------------------------------------------
 int resample_ksize(int in, int out, int filter);            // taps per output (the table's row length), -1 for bad arguments
 int resample_coeffs(int in, int out, int filter, int* bounds, int* kk);     // host only; returns ksize
-enum { RESIZE_OUT_U8 = 0, RESIZE_OUT_IMAGE_F32 = 1, RESIZE_OUT_SKETCH_F32 = 2 };
-// what the LAST pass writes: uint8 (B,H,W,C); or the forward's fp32 NCHW inputs -- (B,C,H,W) = lut[v], or (v > 0)
+enum { RESIZE_OUT_U8 = 0, RESIZE_OUT_IMAGE_F32 = 1, RESIZE_OUT_SKETCH_F32 = 2, RESIZE_OUT_LOCK_U8 = 3 };
+// what the LAST pass writes: uint8 (B,H,W,C); or the forward's fp32 NCHW inputs -- (B,C,H,W) = lut[v], or (v > 0); or, for a
+// lock plane (C == 1), uint8 (B,H,W) = (v > 0) in {0, 1}
 struct ResizeOut {
   int mode;
   unsigned char* u8;
@@ -373,8 +377,14 @@ hipError_t launch_window_resample_h(const se_window* d_wins, const int* d_bounds
 // paste end: the vertical pass Hin -> hs of rgb (B,Hin,P,3) and m8 (B,Hin,P) (row pitch P pixels, P % 4 == 0, P >= ws, both
 // 4-byte aligned) with the paste rule as its epilogue: frame[y0 + y, x0 + x, :] = the resampled colour where the resampled
 // mask byte is > 0, every other byte of the frame untouched
+// locked: d_wins = 2 B records, wins[B + b].frame_u8 = request b's (Hi,Wi) lock plane or null; a pixel whose
+// byte of the plane at its frame position is non-zero is not written, whatever the resampled mask says
 hipError_t launch_window_paste_v(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, const int* d_bounds,
-                                 const int* d_kk, int ksize, int B, int Hin, int hs, int P, int ws, hipStream_t st);
+                                 const int* d_kk, int ksize, int B, int Hin, int hs, int P, int ws, hipStream_t st, bool locked = false);
+// the gather end for lock planes: d_wins = 2 B records as above; the horizontal pass over the planes' hs x ws windows ->
+// (B, hs, Wout) as `o` says (zeros for a null plane); reads no byte outside a window's own rows
+hipError_t launch_window_lock_resample_h(const se_window* d_wins, const int* d_bounds, const int* d_kk, const int* h_bounds, int ksize,
+                                         int B, int hs, int ws, int Wout, const ResizeOut& o, hipStream_t st);
 // largest tap count the kernels take (48 KiB of LDS per block): a bicubic downscale by more than ~2000x is refused
 constexpr int RESAMPLE_MAX_KSIZE = 8191;
 
@@ -390,8 +400,13 @@ hipError_t launch_window_gather(const se_window* d_wins, const float* lut, float
 hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8, int* hits, int B, int H, int W, int hs, int ws,
                                 hipStream_t st);
 // frame[y0 + y, x0 + x, :] = rgb[b, y, x, :] where m8[b, y, x] > 0; rgb (B,H,W,3) and m8 (B,H,W) 4-byte aligned, W % 4 == 0
+// locked: d_wins = 2 B records, wins[B + b].frame_u8 = request b's (Hi,Wi) lock plane or null, and the rule
+// gains `and lock[y0 + y, x0 + x] == 0`
 hipError_t launch_window_paste(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, int B, int H, int W,
-                               hipStream_t st);
+                               hipStream_t st, bool locked = false);
+// d_wins = 2 B records as above: each plane's H x W window -> out (B,H,W) uint8 = (v > 0) in {0, 1}, zeros for a null plane;
+// W % 8 == 0, out 8-byte aligned; no byte outside a window's rows is read
+hipError_t launch_window_lock_gather(const se_window* d_wins, unsigned char* out, int B, int H, int W, hipStream_t st);
 // the undo journal.  d_wins = 2 B records: the requests, then B records whose frame_u8 is the request's slot
 // (hs rows of round_up(3 ws, 16) bytes, 16-byte aligned).  save: the hs x ws rectangle -> the slot; swap: rectangle <-> slot.
 // Any hs, ws; no byte outside a window's rows is read, none outside the rectangle written.

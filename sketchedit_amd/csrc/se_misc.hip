@@ -106,7 +106,8 @@ const char* prof_label_name(int l) {
   static const char* n[PL_COUNT] = {"gconv_n192", "gconv_n96", "gconv_n48", "gconv_n24", "wino_n192", "wino_n96", "wino_up96", "small_conv", "pack",
                                     "colreduce", "att_prep", "att_score", "att_softmax", "att_boxsum", "att_pv", "layout",
                                     "att_stream_stats", "att_stream_out", "resize_h", "resize_v", "window_gather", "window_border",
-                                    "window_paste", "window_resample_h", "window_paste_v", "window_save", "window_swap"};
+                                    "window_paste", "window_resample_h", "window_paste_v", "window_save", "window_swap", "window_lock_gather",
+                                    "window_paste_locked", "window_paste_v_locked"};
   return (l >= 0 && l < PL_COUNT) ? n[l] : "?";
 }
 
@@ -249,7 +250,8 @@ __global__ __launch_bounds__(256) void small_conv_kernel(const SmallConvParams p
       continue;
     }
     if (p.mode == 0) {
-      const float m = sigmoidf_(a1[0]);
+      // a locked pixel is outside the mask: known context for netG, and composed == image there
+      const float m = (p.lock && p.lock[idx]) ? 0.f : sigmoidf_(a1[0]);
       p.out_nchw[p.out_bs ? (long)b * p.out_bs + rem : idx] = m;
       if (p.hard) p.hard[idx] = m > 0.5f ? 1.f : 0.f;
       continue;
@@ -306,6 +308,7 @@ hipError_t launch_small_conv(const SmallConvParams& p0, hipStream_t st) {
     const long cs = p0.mode == 4 ? p0.cout : (p0.mode == 0 ? 1 : 3);
     if (p0.out_nchw) p.out_nchw = p0.out_nchw + (size_t)b0 * (p0.out_bs ? p0.out_bs : cs * HW);
     if (p0.hard) p.hard = p0.hard + (size_t)b0 * HW;
+    if (p0.lock) p.lock = p0.lock + (size_t)b0 * HW;
     if (p0.img) p.img = p0.img + (size_t)b0 * 3 * HW;
     if (p0.mask) p.mask = p0.mask + (size_t)b0 * (p0.mask_bs ? p0.mask_bs : HW);
     if (p0.xnow) p.xnow = (float*)((char*)p0.xnow + (size_t)b0 * HW * 16);

@@ -16,7 +16,9 @@
 //
 // A window edit at a working size uses the same passes with two fused ends: window_resample_h_kernel is the
 // horizontal pass with its rows taken from the frames' windows (no crop copy), window_paste_v_kernel the vertical pass of the
-// way back whose epilogue is the paste rule of se_window.hip (no full-size result is ever written).
+// way back whose epilogue is the paste rule of se_window.hip (no full-size result is ever written).  A session's lock plane
+//  takes the same two ends: window_lock_resample_h_kernel reads its rows from the planes' windows and the last
+// pass writes (v > 0) as bytes (RESIZE_OUT_LOCK_U8); window_paste_v_locked_kernel tests the plane in frame space.
 //
 // The kernels are memory-bound (a few int multiply-adds per byte).  The coefficients of a block's outputs are staged
 // in LDS; the vertical pass treats an output row as a flat byte string (every channel of a row shares the row's weights)
@@ -133,6 +135,8 @@ __device__ __forceinline__ void store_px(const ResizeOut& o, int b, int y, int x
     o.u8[(((size_t)b * o.H + y) * o.W + x) * C + c] = v;
   else if (o.mode == RESIZE_OUT_IMAGE_F32)
     o.f32[(((size_t)b * C + c) * o.H + y) * o.W + x] = o.lut[v];
+  else if (o.mode == RESIZE_OUT_LOCK_U8)
+    o.u8[((size_t)b * o.H + y) * o.W + x] = v ? 1 : 0;
   else
     o.f32[(((size_t)b * C + c) * o.H + y) * o.W + x] = v ? 1.f : 0.f;
 }
@@ -154,6 +158,17 @@ struct WindowRows {
     const se_window w = wins[b];
     if (C == 3) return w.frame_u8 + ((size_t)(w.y0 + y) * w.Wi + w.x0) * 3;
     return w.sketch_u8 + (size_t)y * ws;
+  }
+};
+
+// Lock plane (C == 1): wins holds 2 B records, wins[B + b].frame_u8 = request b's (Hi, Wi) plane; row r of the
+// window starts at byte (y0 + r) Wi + x0, any alignment, pitch Wi.
+struct LockRows {
+  const se_window* wins;
+  int B;
+  __device__ __forceinline__ const unsigned char* row(int b, int y) const {
+    const se_window w = wins[b];
+    return wins[B + b].frame_u8 + (size_t)(w.y0 + y) * w.Wi + w.x0;
   }
 };
 
@@ -235,6 +250,18 @@ __global__ void __launch_bounds__(256) window_resample_h_kernel(const se_window*
   resample_h_body<C>(WindowRows<C>{wins, ws}, bounds, kk, ksize, hs, Wout, TX, TY, span, o);
 }
 
+// The gather end for the lock planes: the same pass over LockRows.  A request without a plane (null) gets zeros.
+__global__ void __launch_bounds__(256) window_lock_resample_h_kernel(const se_window* __restrict__ wins, int B,
+                                                                     const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                                     int ksize, int hs, int Wout, int TX, int TY, int span, ResizeOut o) {
+  if (!wins[B + blockIdx.z].frame_u8) {          // block-uniform
+    const int xx = blockIdx.x * TX + threadIdx.x % TX, y = blockIdx.y * TY + threadIdx.x / TX;
+    if (xx < Wout && y < hs) store_px(o, blockIdx.z, y, xx, 0, 1, 0);
+    return;
+  }
+  resample_h_body<1>(LockRows{wins, B}, bounds, kk, ksize, hs, Wout, TX, TY, span, o);
+}
+
 // Vertical pass: in (B, Hin, RB bytes) -> (B, Hout, RB), RB = W * C; every byte of an output row takes the row's weights.
 // One block = 256 lanes x 16 bytes of one output row; V = bytes per load (16, 4 or 1: what the alignment of `in`, RB and,
 // for uint8 output, `o.u8` allows).
@@ -310,9 +337,12 @@ __global__ void __launch_bounds__(256) resample_v_kernel(const unsigned char* __
 // byte -- then the twelve colour bytes.  frame[y0 + yy, x0 + x, :] is written only where the resampled mask byte is > 0:
 // whole dwords where all four pixels are selected and the address allows it, single bytes otherwise, so a lane never
 // rewrites a byte it does not own (concurrent lanes and disjoint windows of other requests on the frame do not race).
-__global__ void __launch_bounds__(64) window_paste_v_kernel(const se_window* __restrict__ wins, const unsigned char* __restrict__ rgb,
-                                                            const unsigned char* __restrict__ m8, const int* __restrict__ bounds,
-                                                            const int* __restrict__ kk, int ksize, int Hin, int P, int ws) {
+// LOCKED: wins holds 2 B records, wins[B + b].frame_u8 = request b's lock plane or null; a pixel whose byte of
+// the plane, at its FRAME position, is non-zero leaves the selection -- after the mask's early exit, before the colour reads.
+template <bool LOCKED>
+__device__ __forceinline__ void window_paste_v(const se_window* __restrict__ wins, int B, const unsigned char* __restrict__ rgb,
+                                               const unsigned char* __restrict__ m8, const int* __restrict__ bounds,
+                                               const int* __restrict__ kk, int ksize, int Hin, int P, int ws) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int* coef = (int*)smem;
   const int yy = blockIdx.y, b = blockIdx.z;
@@ -333,6 +363,17 @@ __global__ void __launch_bounds__(64) window_paste_v_kernel(const se_window* __r
 #pragma unroll
   for (int p = 0; p < 4; ++p) sel[p] = x + p < ws && clip8(am[p]) > 0;
   if (!(sel[0] || sel[1] || sel[2] || sel[3])) return;
+  if (LOCKED) {
+    const unsigned char* plane = wins[B + b].frame_u8;
+    if (plane) {
+      const se_window w = wins[b];
+      const unsigned char* row = plane + (size_t)(w.y0 + yy) * w.Wi + w.x0;      // the window row's lock bytes: [row, row + ws)
+      const unsigned lk = load4_within(row + x, row, row + ws);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) sel[p] = sel[p] && !((lk >> (8 * p)) & 255u);
+      if (!(sel[0] || sel[1] || sel[2] || sel[3])) return;
+    }
+  }
   int acc[12];
 #pragma unroll
   for (int e = 0; e < 12; ++e) acc[e] = kRoundOne;
@@ -360,6 +401,19 @@ __global__ void __launch_bounds__(64) window_paste_v_kernel(const se_window* __r
       for (int c = 0; c < 3; ++c) dst[3 * p + c] = clip8(acc[3 * p + c]);
     }
   }
+}
+
+__global__ void __launch_bounds__(64) window_paste_v_kernel(const se_window* __restrict__ wins, const unsigned char* __restrict__ rgb,
+                                                            const unsigned char* __restrict__ m8, const int* __restrict__ bounds,
+                                                            const int* __restrict__ kk, int ksize, int Hin, int P, int ws) {
+  window_paste_v<false>(wins, 0, rgb, m8, bounds, kk, ksize, Hin, P, ws);
+}
+
+__global__ void __launch_bounds__(64) window_paste_v_locked_kernel(const se_window* __restrict__ wins, int B,
+                                                                   const unsigned char* __restrict__ rgb,
+                                                                   const unsigned char* __restrict__ m8, const int* __restrict__ bounds,
+                                                                   const int* __restrict__ kk, int ksize, int Hin, int P, int ws) {
+  window_paste_v<true>(wins, B, rgb, m8, bounds, kk, ksize, Hin, P, ws);
 }
 
 bool aligned(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }
@@ -427,15 +481,28 @@ hipError_t launch_window_resample_h(const se_window* d_wins, const int* d_bounds
   return hipGetLastError();
 }
 
+hipError_t launch_window_lock_resample_h(const se_window* d_wins, const int* d_bounds, const int* d_kk, const int* h_bounds, int ksize,
+                                         int B, int hs, int ws, int Wout, const ResizeOut& o, hipStream_t st) {
+  HShape s;
+  if (!resample_h_shape(h_bounds, ksize, B, hs, Wout, 1, &s)) return hipErrorInvalidValue;
+  set_launch_cost(0.0, (double)B * hs * (ws + Wout), "window_lock_gather");
+  set_launch_grid((long)s.grid.x * s.grid.y * s.grid.z);
+  ProfScope ps_(st, PL_WINDOW_LOCK_GATHER);
+  hipLaunchKernelGGL(window_lock_resample_h_kernel, s.grid, dim3(s.TX * s.TY), s.lds, st, d_wins, B, d_bounds, d_kk, ksize, hs, Wout, s.TX, s.TY, s.span, o);
+  return hipGetLastError();
+}
+
 hipError_t launch_window_paste_v(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, const int* d_bounds,
-                                 const int* d_kk, int ksize, int B, int Hin, int hs, int P, int ws, hipStream_t st) {
+                                 const int* d_kk, int ksize, int B, int Hin, int hs, int P, int ws, hipStream_t st, bool locked) {
   if (((ksize * 4 + 15) & ~15) > kLdsBudget || (P & 3) || P < ws || !aligned(rgb, 4) || !aligned(m8, 4)) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((ws + 4 * 64 - 1) / (4 * 64)), (unsigned)hs, (unsigned)B);
   // bytes: an upper bound (every pixel selected): the taps of mask and colour read, the frame's window written
-  set_launch_cost(0.0, (double)B * ws * 4.0 * Hin + (double)B * hs * ws * 3.0, "window_paste_v");
+  set_launch_cost(0.0, (double)B * ws * 4.0 * Hin + (double)B * hs * ws * (locked ? 4.0 : 3.0), locked ? "window_paste_v_locked" : "window_paste_v");
   set_launch_grid((long)grid.x * grid.y * grid.z);
-  ProfScope ps_(st, PL_WINDOW_PASTE_V);
-  hipLaunchKernelGGL(window_paste_v_kernel, grid, dim3(64), (size_t)((ksize * 4 + 15) & ~15), st, d_wins, rgb, m8, d_bounds, d_kk, ksize, Hin, P, ws);
+  ProfScope ps_(st, locked ? PL_WINDOW_PASTE_V_LOCKED : PL_WINDOW_PASTE_V);
+  const size_t lds = (size_t)((ksize * 4 + 15) & ~15);
+  if (locked) hipLaunchKernelGGL(window_paste_v_locked_kernel, grid, dim3(64), lds, st, d_wins, B, rgb, m8, d_bounds, d_kk, ksize, Hin, P, ws);
+  else hipLaunchKernelGGL(window_paste_v_kernel, grid, dim3(64), lds, st, d_wins, rgb, m8, d_bounds, d_kk, ksize, Hin, P, ws);
   return hipGetLastError();
 }
 

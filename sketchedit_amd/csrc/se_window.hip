@@ -24,6 +24,14 @@
 // One lane owns one 16-byte chunk of a slot row and the (up to) 16 frame bytes that belong in it.  It reads them as gather
 // does and, in swap, writes them back by the ownership rule above: aligned dwords that lie inside its own bytes, single bytes
 // in front of and behind them.  No lane writes a byte another lane owns, and none outside the rectangle.
+//
+// Locked regions: a frame may own a (Hi, Wi) uint8 LOCK PLANE, non-zero = locked.  Its pointers travel
+// like the journal's slots: wins holds 2 B records and wins[B + b].frame_u8 is request b's plane, or null.
+//
+//  lock gather:  the window of each plane -> that request's slot of a contiguous (B,H,W) plane of {0, 1} (null: zeros), which
+//                the mask predictor's last kernel takes; a row starts at byte (y0 + r) Wi + x0 and is read as gather reads;
+//  locked paste: paste, with `and lock[y0 + y, x0 + x] == 0` added to the rule -- the four lock bytes of a lane's pixels are
+//                read the same way and those pixels leave the selection before it decides between dwords and bytes.
 #include "../../include/sketchedit_hip.h"
 #include "se_device.h"
 #include "se_kernels.h"
@@ -33,16 +41,6 @@
 namespace se {
 
 namespace {
-
-// the dword at the 4-byte aligned address p, of which only the bytes inside [lo, hi) are read (the others are 0)
-__device__ __forceinline__ unsigned load_dword_within(const unsigned char* p, const unsigned char* lo, const unsigned char* hi) {
-  if (p >= lo && p + 4 <= hi) return *(const unsigned*)p;
-  unsigned v = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (p + i >= lo && p + i < hi) v |= (unsigned)p[i] << (8 * i);
-  return v;
-}
 
 // the 16 bytes at `a` (any alignment), of which only those inside [lo, hi) are read (the others are 0): aligned dwords and a
 // byte shift
@@ -180,9 +178,40 @@ __global__ void __launch_bounds__(64) window_border_kernel(const se_window* __re
   if (lane == 0) hits[b * 4 + side] = n;
 }
 
-// One lane = 4 consecutive pixels of one window row.
-__global__ void __launch_bounds__(256) window_paste_kernel(const se_window* __restrict__ wins, const unsigned char* __restrict__ rgb,
-                                                           const unsigned char* __restrict__ m8, int B, int H, int W) {
+// One lane = 16 consecutive bytes of one window row of a lock plane (W % 8 == 0: the last lane of a row may hold 8), written
+// as two 8-byte stores (out is 8-byte aligned and so is every chunk).  wins holds 2 B records (see above).
+__global__ void __launch_bounds__(256) window_lock_gather_kernel(const se_window* __restrict__ wins, unsigned char* __restrict__ out,
+                                                                 int B, int H, int W) {
+  const int chunks = (W + 15) >> 4;
+  const long q = (long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (long)B * H * chunks) return;
+  const int j = (int)(q % chunks);
+  const long by = q / chunks;
+  const int y = (int)(by % H), b = (int)(by / H);
+  const se_window w = wins[b];
+  const unsigned char* plane = wins[B + b].frame_u8;
+  uint4 f = make_uint4(0u, 0u, 0u, 0u);
+  if (plane) {
+    const unsigned char* row = plane + (size_t)(w.y0 + y) * w.Wi + w.x0;       // the window row's bytes: [row, row + W)
+    f = load16_within(row + 16 * j, row, row + W);
+  }
+  unsigned d[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    unsigned u = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) u |= ((d[i] >> (8 * e)) & 255u) ? 1u << (8 * e) : 0u;
+    d[i] = u;
+  }
+  uint2* o = (uint2*)(out + ((size_t)b * H + y) * W + 16 * j);
+  o[0] = make_uint2(d[0], d[1]);
+  if (16 * j + 8 < W) o[1] = make_uint2(d[2], d[3]);
+}
+
+// One lane = 4 consecutive pixels of one window row.  LOCKED: wins holds 2 B records (see above).
+template <bool LOCKED>
+__device__ __forceinline__ void window_paste(const se_window* __restrict__ wins, const unsigned char* __restrict__ rgb,
+                                             const unsigned char* __restrict__ m8, int B, int H, int W) {
   const int W4 = W >> 2;
   const long q = (long)blockIdx.x * 256 + threadIdx.x;
   if (q >= (long)B * H * W4) return;
@@ -190,9 +219,17 @@ __global__ void __launch_bounds__(256) window_paste_kernel(const se_window* __re
   const long by = q / W4;
   const int y = (int)(by % H), b = (int)(by / H);
   const size_t pix = ((size_t)b * H + y) * W + x;
-  const unsigned mk = *(const unsigned*)(m8 + pix);
+  unsigned mk = *(const unsigned*)(m8 + pix);
   if (!mk) return;
   const se_window w = wins[b];
+  if (LOCKED) {
+    const unsigned char* plane = wins[B + b].frame_u8;
+    if (plane) {
+      const unsigned char* row = plane + (size_t)(w.y0 + y) * w.Wi + w.x0;     // the window row's lock bytes: [row, row + W)
+      mk = clear_locked(mk, load4_within(row + x, row, row + W));
+      if (!mk) return;
+    }
+  }
   unsigned char* dst = w.frame_u8 + ((size_t)(w.y0 + y) * w.Wi + w.x0 + x) * 3;
   const unsigned* src = (const unsigned*)(rgb + pix * 3);
   const unsigned s0 = src[0], s1 = src[1], s2 = src[2];
@@ -213,6 +250,16 @@ __global__ void __launch_bounds__(256) window_paste_kernel(const se_window* __re
       }
     }
   }
+}
+
+__global__ void __launch_bounds__(256) window_paste_kernel(const se_window* __restrict__ wins, const unsigned char* __restrict__ rgb,
+                                                           const unsigned char* __restrict__ m8, int B, int H, int W) {
+  window_paste<false>(wins, rgb, m8, B, H, W);
+}
+
+__global__ void __launch_bounds__(256) window_paste_locked_kernel(const se_window* __restrict__ wins, const unsigned char* __restrict__ rgb,
+                                                                  const unsigned char* __restrict__ m8, int B, int H, int W) {
+  window_paste<true>(wins, rgb, m8, B, H, W);
 }
 
 }  // namespace
@@ -238,13 +285,23 @@ hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8
 }
 
 hipError_t launch_window_paste(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, int B, int H, int W,
-                               hipStream_t st) {
+                               hipStream_t st, bool locked) {
   const long nq = (long)B * H * W / 4;
-  // bytes: an upper bound (every pixel selected): mask and rgb read, the frame's window written
-  set_launch_cost(0.0, (double)B * H * W * 7.0, "window_paste");
+  // bytes: an upper bound (every pixel selected): mask (and lock) and rgb read, the frame's window written
+  set_launch_cost(0.0, (double)B * H * W * (locked ? 8.0 : 7.0), locked ? "window_paste_locked" : "window_paste");
   set_launch_grid((nq + 255) / 256);
-  ProfScope ps_(st, PL_WINDOW_PASTE);
-  hipLaunchKernelGGL(window_paste_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_wins, rgb, m8, B, H, W);
+  ProfScope ps_(st, locked ? PL_WINDOW_PASTE_LOCKED : PL_WINDOW_PASTE);
+  if (locked) hipLaunchKernelGGL(window_paste_locked_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_wins, rgb, m8, B, H, W);
+  else hipLaunchKernelGGL(window_paste_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_wins, rgb, m8, B, H, W);
+  return hipGetLastError();
+}
+
+hipError_t launch_window_lock_gather(const se_window* d_wins, unsigned char* out, int B, int H, int W, hipStream_t st) {
+  const long nq = (long)B * H * ((W + 15) / 16);
+  set_launch_cost(0.0, (double)B * H * W * 2.0, "window_lock_gather");
+  set_launch_grid((nq + 255) / 256);
+  ProfScope ps_(st, PL_WINDOW_LOCK_GATHER);
+  hipLaunchKernelGGL(window_lock_gather_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_wins, out, B, H, W);
   return hipGetLastError();
 }
 

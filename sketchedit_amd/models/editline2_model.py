@@ -130,7 +130,7 @@ class EditLine2Model(torch.nn.Module):
                                                                low_latency))
         return rgb[0] if single else rgb
 
-    def edit_window_u8(self, frames, origins, sketches, H, W, commit=True, low_latency=None, work_hw=None):
+    def edit_window_u8(self, frames, origins, sketches, H, W, commit=True, low_latency=None, work_hw=None, locks=None):
         """A window edit of resident frames (no reference counterpart; DESIGN.md 6d, serve.EditSession is the caller-facing
         form): frames[i] (Hi,Wi,3) uint8 ON THE DEVICE, edited in place; origins[i] = (y0, x0) of the H x W window;
         sketches[i] the window's (H,W) uint8 sketch (array or tensor; uploaded here).  The result is this model's inference
@@ -138,13 +138,19 @@ class EditLine2Model(torch.nn.Module):
         int32) on the device.  `low_latency` as in forward, by the size of the forward: B windows of H x W.
         work_hw = (Hw, Ww): the forward runs at that working size instead -- the window (any H, W >= 16) is
         resampled into it and the result and its mask are resampled back before the paste, all Pillow's BICUBIC bit for
-        bit; rgb and mask_u8 are then returned at the working size, and the mode follows B forwards of Hw x Ww."""
+        bit; rgb and mask_u8 are then returned at the working size, and the mode follows B forwards of Hw x Ww.
+        locks: one (Hi,Wi) uint8 lock plane ON THE DEVICE per frame, or None for a frame without one -- no
+        edit changes a pixel whose byte is non-zero; the lock enters the forward where the mask is made, and the paste."""
         if self.training:
             raise NotImplementedError("call model.eval() first: only the eval branch of generate_fake exists here")
         dev = torch.device("cuda", self.opt.gpu_ids[0])
         sks = [_lib.upload_u8(s, dev) for s in sketches]
         flags = _lib.flags_from_opt(self.opt)
         with torch.no_grad():
+            if locks is not None and any(t is not None for t in locks):
+                Hw, Ww = (int(v) for v in work_hw) if work_hw is not None else (H, W)
+                return self.engine().edit_window_locked_u8(frames, origins, sks, locks, (H, W), Hw, Ww, flags, commit=commit,
+                                                           low_latency=self._mode_for(len(frames), Hw, Ww, low_latency))
             if work_hw is not None:
                 Hw, Ww = (int(v) for v in work_hw)
                 return self.engine().edit_window_scaled_u8(frames, origins, sks, (H, W), Hw, Ww, flags, commit=commit,

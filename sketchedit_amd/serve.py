@@ -192,6 +192,16 @@ class _ModelBackend:
     def paste_scaled(self, frames, origins, window_hw, rgb, m8):
         self.model.engine().window_paste_resize_u8(frames, origins, window_hw, rgb, m8)
 
+    def run_locked(self, frames, origins, sketches, locks, window_hw, work_hw, commit, low_latency):
+        """`run` (work_hw None) or `run_scaled` for a group in which at least one request's frame has a lock plane (DESIGN.md
+        6g): locks[i] = that plane on the device, or None"""
+        rgb, m8, hits = self.model.edit_window_u8(frames, origins, sketches, window_hw[0], window_hw[1], commit=commit,
+                                                  low_latency=low_latency, work_hw=work_hw, locks=locks)
+        return rgb, m8, hits.cpu().tolist()
+
+    def paste_locked(self, frames, origins, locks, window_hw, rgb, m8):
+        self.model.engine().window_paste_locked_u8(frames, origins, locks, window_hw, rgb, m8)
+
     def save(self, frames, origins, window_hw):
         """the windows' rectangles -> one new journal slot each, on the stream the edit follows on"""
         return self.model.window_save_u8(frames, origins, window_hw)
@@ -236,7 +246,10 @@ class EditSession:
     rectangle and slot, `redo` exchanges them again -- the whole frame is byte-identical to what it was.  `history_bytes`
     caps the bytes of all slots (window_saved_bytes each, undo and redo together); over either cap the OLDEST undo entry is
     dropped; an edit whose own slot exceeds `history_bytes` is committed without a journal entry and clears the history
-    (info["undoable"] = False).  A new edit drops the redo entries."""
+    (info["undoable"] = False).  A new edit drops the redo entries.
+    `set_lock` gives the frame a lock plane: pixels no later edit may change.  The lock enters the forward
+    where the mask is made -- a locked pixel is known context for the generator, not a hole it fills -- and the paste; it
+    is the session's state like the frame, but not an edit: `undo` does not touch it."""
 
     def __init__(self, model, image, backend=None, history=0, history_bytes=None):
         if hasattr(image, "convert"):
@@ -257,6 +270,35 @@ class EditSession:
         self.history = int(history)
         self.history_bytes = None if history_bytes is None else int(history_bytes)
         self._undo, self._redo = [], []          # entries (window, slot, bytes); the next to undo / redo is the last
+        self._lock_plane = None                  # the (Hi,Wi) uint8 lock plane on the device (0 / 255), or None
+
+    # ---- locked regions -----------------------------------------------------------------------------------------
+    def set_lock(self, mask):
+        """`mask`: (Hi,Wi), a uint8 or bool array or a PIL 'L' image, non-zero = locked; uploaded once (as 0 / 255) and kept
+        on the device until the next set_lock.  None frees it.  Every later edit leaves the locked pixels' bytes as they
+        are.  Not an edit: nothing is journalled, and `undo` does not bring an earlier lock back."""
+        if mask is not None:
+            if hasattr(mask, "mode"):
+                if mask.mode != "L":
+                    raise ValueError("a lock is an 'L' image (got mode %r)" % mask.mode)
+                mask = np.asarray(mask)
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 and mask.dtype != np.bool_:
+                raise TypeError("a lock is a uint8 or bool array (got %s)" % mask.dtype)
+            if mask.shape != self.frame_hw:
+                raise ValueError("a lock is the frame's (%d,%d) plane (got %r)" % (self.frame_hw + (mask.shape,)))
+            mask = np.where(mask != 0, np.uint8(255), np.uint8(0))
+        with self._lock:
+            self._lock_plane = None if mask is None else self.backend.upload(mask)
+
+    def lock(self):
+        """The lock plane as an (Hi,Wi) uint8 array of 0 / 255 (a download), or None."""
+        with self._lock:
+            return None if self._lock_plane is None else self.backend.download(self._lock_plane)
+
+    @property
+    def locked(self):
+        return self._lock_plane is not None
 
     # ---- the undo journal (DESIGN.md 6f); the helpers below run with the session's lock held ---------------------------------
     def _journals(self, h, w):
@@ -363,7 +405,9 @@ class EditSession:
         counts are those of the working-size mask; a given `window` then needs no multiple-of-8 sides; info gains
         work=(H, W).  Still only the window's sketch goes up and only the window comes down.
         With history on, the window that is finally committed is journalled (one save in front of its paste) and info
-        gains undoable."""
+        gains undoable.  With a lock plane (set_lock) info gains locked = True (a session without one reports what it
+        always did: read it as info.get("locked", False)) -- every run of the edit, committed or not, at either scale, used
+        the plane, and the grow loop saw a mask that is 0 on locked pixels."""
         sk, bbox = self._request(sketch)
         margin = 0.5
         fixed = window is not None
@@ -372,6 +416,7 @@ class EditSession:
         reruns = 0
         be = self.backend
         with self._lock:
+            lk = self._lock_plane
             while True:
                 y0, x0, h, w = win
                 nxt = None if fixed or reruns >= max_grow else self._grown(bbox, win, margin)
@@ -379,8 +424,10 @@ class EditSession:
                 commit = nxt is None
                 crop = be.upload(sk[y0:y0 + h, x0:x0 + w])
                 slot = be.save([self._frame], [(y0, x0)], (h, w))[0] if commit and self._journals(h, w) else None
-                if scaled:
-                    work = choose_working_size((h, w), max_side)
+                work = choose_working_size((h, w), max_side) if scaled else None
+                if lk is not None:
+                    rgb, m8, counts = be.run_locked([self._frame], [(y0, x0)], [crop], [lk], (h, w), work, commit, low_latency)
+                elif scaled:
                     rgb, m8, counts = be.run_scaled([self._frame], [(y0, x0)], [crop], (h, w), work, commit, low_latency)
                 else:
                     rgb, m8, counts = be.run([self._frame], [(y0, x0)], [crop], h, w, commit, low_latency)
@@ -390,13 +437,17 @@ class EditSession:
                 reruns += 1
             if not commit and self._journals(h, w):
                 slot = be.save([self._frame], [(y0, x0)], (h, w))[0]
-            if not commit and scaled:
+            if not commit and lk is not None:
+                be.paste_locked([self._frame], [(y0, x0)], [lk], (h, w), rgb, m8)
+            elif not commit and scaled:
                 be.paste_scaled([self._frame], [(y0, x0)], (h, w), rgb, m8)
             elif not commit:
                 be.paste([self._frame], [(y0, x0)], rgb, m8)
             undoable = self._record(win, slot) if self.history > 0 else None
             patch = be.crop(self._frame, y0, x0, h, w)
         info = dict(window=win, counts=list(counts[0]), reruns=reruns, margin=margin)
+        if lk is not None:
+            info["locked"] = True
         if scaled:
             info["work"] = work
         if undoable is not None:
@@ -459,7 +510,10 @@ class BatchingServer:
     Sessions bring their own `history`: the saves of a group's journalled requests are ONE launch, in front of
     the run when the group commits in the call, else in front of the paste for the requests that stay.  `undo(session)` /
     `redo(session)` block and return like `submit`; they are queued like an edit of that session, so an undo submitted after
-    two edits undoes the second; undo / redo requests of different sessions share a group, one swap launch per window size."""
+    two edits undoes the second; undo / redo requests of different sessions share a group, one swap launch per window size.
+    Sessions bring their own lock planes too; the group keys do not know about them.  A group with at least one
+    locked session runs the locked entry, with no plane for the others (whose results are what they get alone); a group
+    with none runs the entries above."""
 
     def __init__(self, model=None, max_batch=32, max_wait_s=0.005, models=None, mode_policy="pinned", device_io=False,
                  window=False, max_grow=2, max_side=None):
@@ -610,6 +664,8 @@ class BatchingServer:
         origins = [r["window"][:2] for r in reqs]
         journalled = [i for i, r in enumerate(reqs) if r["session"]._journals(h, w)]
         slots = {}
+        lks = [r["session"]._lock_plane for r in reqs]
+        locked = any(t is not None for t in lks)
 
         def save(idx):                                    # one launch for the group's journalled requests
             if idx:
@@ -621,14 +677,19 @@ class BatchingServer:
             crops = [be.upload(r["sketch"][y0:y0 + h, x0:x0 + w]) for r, (y0, x0) in zip(reqs, origins)]
             if commit:
                 save(journalled)
-            if work is not None:
+            if locked:
+                rgb, m8, counts = be.run_locked(frames, origins, crops, lks, (h, w), work, commit, low_latency)
+            elif work is not None:
                 rgb, m8, counts = be.run_scaled(frames, origins, crops, (h, w), work, commit, low_latency)
             else:
                 rgb, m8, counts = be.run(frames, origins, crops, h, w, commit, low_latency)
             stay = [i for i in range(len(reqs)) if grown[i] is None or not any(counts[i])]
             if not commit:
                 save([i for i in stay if i in journalled])          # (a request that is queued again journals nothing yet)
-            if not commit and stay and work is not None:
+            if not commit and stay and locked:
+                be.paste_locked([frames[i] for i in stay], [origins[i] for i in stay], [lks[i] for i in stay], (h, w),
+                                be.select(rgb, stay), be.select(m8, stay))
+            elif not commit and stay and work is not None:
                 be.paste_scaled([frames[i] for i in stay], [origins[i] for i in stay], (h, w), be.select(rgb, stay), be.select(m8, stay))
             elif not commit and stay:
                 be.paste([frames[i] for i in stay], [origins[i] for i in stay], be.select(rgb, stay), be.select(m8, stay))
@@ -637,6 +698,8 @@ class BatchingServer:
                 r = reqs[i]
                 y0, x0 = origins[i]
                 info = dict(window=r["window"], counts=list(counts[i]), reruns=r["reruns"], margin=r["margin"])
+                if lks[i] is not None:
+                    info["locked"] = True
                 if work is not None:
                     info["work"] = tuple(work)
                 if r["session"].history > 0:

@@ -39,6 +39,15 @@ and (d) big_edit_h0 / (e) big_edit_h8 / (f) big_undo_redo: the same three at --w
 max_side=640; the slot is 6.2 MB); plus se_profile_report's window_save / window_swap times and bytes.
 
     python tools/serve_probe.py --window-history [--reps N] [--out FILE]
+
+--window-lock: locked regions, same protocol.  On the 512x512 sketch of --window:
+  (a) edit_unlocked: EditSession.edit(max_grow=0) of a session without a lock (the leg that is compared with the parent
+                     commit's build, run with --window-lock-parent there: the unlocked legs only, no lock call),
+  (b) edit_locked:   the same after set_lock of a plane that locks the left half of the 512x512 window,
+and (c) big_edit_unlocked / (d) big_edit_locked: the same two at --window-scaled's input (1080x1920 window, max_side=640, the
+left half of the window locked); plus se_profile_report's window_* kernel times and bytes of one (b) and one (d) request.
+
+    python tools/serve_probe.py --window-lock [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -252,6 +261,52 @@ def window_history_leg(model, reps, parent=False, max_side=640):
     return out
 
 
+def window_lock_leg(model, reps, parent=False, max_side=640):
+    """(a) - (d) of the module docstring; parent=True: legs (a) and (c) only, with the calls a build without locks has"""
+    import numpy as np
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    sk512 = np.zeros((h, w), np.uint8)
+    sk512[400:640, 800:1040] = ((rng.rand(240, 240) < 0.01) * 255).astype(np.uint8)
+    sk512[400, 800] = sk512[639, 1039] = 255
+    win512 = serve.choose_window(serve.sketch_bbox(sk512), (h, w))
+    assert win512[2:] == (512, 512)
+    big = big_sketch(rng)
+    winbig = serve.choose_window(serve.sketch_bbox(big), (h, w))
+    s0 = serve.EditSession(model, frame)
+    legs = dict(edit_unlocked=lambda: s0.edit(sk512, max_grow=0, low_latency=True),
+                big_edit_unlocked=lambda: s0.edit(big, max_grow=0, low_latency=True, max_side=max_side))
+    if not parent:
+        def half(win):
+            lk = np.zeros((h, w), np.uint8)
+            lk[win[0]:win[0] + win[2], win[1]:win[1] + win[3] // 2] = 255
+            return lk
+        sl, bl = serve.EditSession(model, frame), serve.EditSession(model, frame)
+        sl.set_lock(half(win512))
+        bl.set_lock(half(winbig))
+        legs.update(edit_locked=lambda: sl.edit(sk512, max_grow=0, low_latency=True),
+                    big_edit_locked=lambda: bl.edit(big, max_grow=0, low_latency=True, max_side=max_side))
+    out = dict(tool="serve_probe --window-lock" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency",
+               frame=[w, h], max_side=max_side, ms=rounds_of(legs, reps))
+    if not parent:
+        eng = model.engine()
+        prof = {}
+        for tag, s, sk, kw in (("512", sl, sk512, {}), ("big", bl, big, dict(max_side=max_side))):
+            eng.profile(True)
+            s.edit(sk, max_grow=0, low_latency=True, **kw)
+            rep = eng.profile_report()
+            eng.profile(False)
+            prof[tag] = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4), bytes=int(k["bytes"]))
+                         for k in rep["kernels"] if k["kernel"].startswith("window_")}
+            prof[tag]["all_kernels_ms"] = round(sum(k["total_ms"] for k in rep["kernels"]), 3)
+            locked = s.lock() > 0
+            prof[tag]["locked_pixels_unchanged"] = bool(np.array_equal(s.frame()[locked], frame[locked]))
+        out.update(lock_kernels_profiled=prof)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -260,6 +315,8 @@ def main():
     ap.add_argument("--window-scaled", action="store_true", help="window edits at a working size (see the module docstring)")
     ap.add_argument("--window-history", action="store_true", help="the undo journal (see the module docstring)")
     ap.add_argument("--window-history-parent", action="store_true", help="the history=0 legs of --window-history only")
+    ap.add_argument("--window-lock", action="store_true", help="locked regions (see the module docstring)")
+    ap.add_argument("--window-lock-parent", action="store_true", help="the unlocked legs of --window-lock only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -268,8 +325,10 @@ def main():
     from sketchedit_amd import serve
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     model = make_model(tempfile.mkdtemp())
-    if args.window or args.window_scaled or args.window_history or args.window_history_parent:
-        if args.window_history or args.window_history_parent:
+    if args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent:
+        if args.window_lock or args.window_lock_parent:
+            res = window_lock_leg(model, args.reps, parent=args.window_lock_parent)
+        elif args.window_history or args.window_history_parent:
             res = window_history_leg(model, args.reps, parent=args.window_history_parent)
         else:
             res = window_scaled_leg(model, args.reps) if args.window_scaled else window_leg(model, args.reps)
