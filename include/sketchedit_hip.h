@@ -316,7 +316,15 @@ int se_profile_report(se_ctx* ctx, char* buf, size_t cap);
  * changes an entry for every later call of the process (name with or without the "SE_" prefix; returns 0, or 1 for an
  * unknown name), se_debug_get_option reads one, se_debug_reset_options restores the environment / built-in values.
  * "SE_TEST_OFFSET_LIMIT" (settable only here) lowers the byte range the 32-bit-offset kernels may address, so that a
- * test reaches the large-batch passes of the forwards with a few small images. */
+ * test reaches the large-batch passes of the forwards with a few small images.
+ * "SE_TEST_POISON" (settable only here; 0, the default: off, nothing is added to any call) with a value v in 1..255 (any other value is off) fills every
+ * scratch region with the byte v when it is handed out and before its first producer is enqueued, on that producer's stream:
+ * every block of the workspace arenas of the forwards, the scratch the per-op entry points allocate, every region a call
+ * carves out of the workspace outside the arenas (the hard / soft masks, the fp32 inputs of the uint8 entries, the rgb /
+ * mask / counts / lock regions of the window entries where the caller passed NULL, the resample intermediates) and the
+ * ctx-owned resize intermediate at each use -- not the weight images, not the window record ring.  A result that changes
+ * with v depends on a byte nobody wrote (tests/test_gpu_poison.py).  While it is set, a call with SE_FLAG_GRAPH runs
+ * uncaptured and enters nothing into the graph cache. */
 int se_debug_set_option(const char* name, int value);
 int se_debug_get_option(const char* name, int* value);
 void se_debug_reset_options(void);

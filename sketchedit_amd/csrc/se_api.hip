@@ -208,6 +208,25 @@ long long addr_limit() {
   return v > 0 ? (long long)v : (1ll << 31);
 }
 
+// SE_TEST_POISON (se_debug_set_option only; 0, the default: nothing happens, no call is added).  A value v in 1..255: every
+// scratch region is filled with the byte v when it is handed out, on the stream its first producer will be enqueued on -- so a
+// kernel that reads a byte nobody wrote (pad channels and columns, guard bands, ragged tiles) reads v, whatever the memory held
+// before (tests/test_gpu_poison.py: 0xFF is a NaN in every float type, 0x47 / 0xC7 are large finite values of either sign).
+// Regions: every arena block (Plan::alloc_raw), the scratch of the per-op entry points, every region a call carves out of the
+// workspace outside the arenas, the resize intermediate at each use.  Not the weight images, not the window record ring.
+// While it is set, an SE_FLAG_GRAPH call runs uncaptured and enters nothing into the graph cache (se_inference).
+// (A value outside 1..255 is off, like 0: 256 must not turn into a fill with zeros, the one byte the aid exists to avoid.)
+int poison_byte() {
+  const int v = opt(OPT_TEST_POISON);
+  return v >= 1 && v <= 255 ? v : 0;
+}
+int poison(se_ctx* c, void* p, size_t bytes, hipStream_t st) {
+  const int v = poison_byte();
+  if (!v || !p || !bytes) return 0;
+  HIPCHK(c, hipMemsetAsync(p, v, bytes, st));
+  return 0;
+}
+
 // ---- narrow layers in raw-tile form (se_rtile.hip): returns 0 and sets *done when the layer was launched there ------
 int try_rtile(se_ctx* c, const Layer& L, bool bf, const float* src0, int C0, const float* src1, float* dst, int B, int Hin, int Win,
               int Ho, int Wo, int pad, bool* done) {
@@ -618,6 +637,14 @@ struct Plan {
   float* alloc_raw(size_t nfloats) {
     float* p = ar->alloc(nfloats);
     if (!p && !rc) rc = fail(c, "workspace too small (need more than %zu bytes)", ar->cap);
+    // SE_TEST_POISON: the whole block (its 256-byte rounding included) is filled on c->st, the stream of the branch being
+    // planned, where the block's first producer is enqueued next.  The fill is ordered after every earlier user of the bytes:
+    // a block is reused within one arena, and an arena is used in the order of one stream -- the main arena on the main stream,
+    // the side arena between side_begin() and side_end() on the side stream, which starts behind the fork event, i.e. behind
+    // everything the main stream did with side-arena blocks before (the style input, `vec`, a previous plan's joined side
+    // branch).  A block both branches read (xnow, vec, pm) is released only after join(), and nothing is allocated from the
+    // side arena between a side_end() and the next side_begin() except before the first fork, when that arena is still unused.
+    if (p && !rc && !c->dry && poison(c, p, (nfloats * 4 + 255) & ~(size_t)255, c->st)) rc = 1;
     return p;
   }
   Act alloc(int H, int W, int C) {
@@ -1157,6 +1184,7 @@ int resize_locked(se_ctx* c, hipStream_t st, const unsigned char* in, int B, int
     if (need_v) {
       unsigned char* mid = rs_scratch(c, (size_t)B * Hin * Wout * C);
       if (!mid) return 1;
+      if (poison(c, mid, (size_t)B * Hin * Wout * C, st)) return 1;
       oh.mode = RESIZE_OUT_U8; oh.u8 = mid; oh.H = Hin;
       src = mid;
     }
@@ -1414,6 +1442,7 @@ int enqueue_inference(se_ctx* c, void* stream, const float* image, const float* 
   // a batch beyond the kernels' 32-bit byte offsets runs as passes over image ranges (pass_size)
   const int nb = pass_size(c, B, H, W, flags);
   if (!nb) return 1;
+  if (!hard_out && poison(c, hard_all, plane, (hipStream_t)stream)) return 1;
   for (int b0 = 0; b0 < B; b0 += nb) {
     const int bb = std::min(nb, B - b0);
     const se_ctx::Peaks pk = plan_peaks(c, 3, bb, H, W, flags, maskim_out != nullptr);
@@ -1444,7 +1473,8 @@ int se_inference(se_ctx* c, void* stream, const float* image, const float* sketc
   HIPCHK(c, hipSetDevice(c->device));
   c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
   c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
-  if (!(flags & SE_FLAG_GRAPH) || c->prof.on)
+  // (SE_TEST_POISON set: uncaptured, and nothing enters the graph cache -- the fills belong to the test aid, not to a graph)
+  if (!(flags & SE_FLAG_GRAPH) || c->prof.on || poison_byte() != 0)
     return enqueue_inference(c, stream, image, sketch, composed_out, mask_out, hard_out, maskim_out, coarse_out, fine_out, ws,
                              ws_bytes, B, H, W, flags);
   // SE_FLAG_GRAPH: the forward for these exact arguments (every pointer is baked into the kernel nodes) is captured
@@ -1520,6 +1550,7 @@ int inference_u8_locked(se_ctx* c, void* stream, const float* image, const float
   const size_t HW = (size_t)H * W;
   const int nb = pass_size(c, B, H, W, flags);       // passes over image ranges beyond the kernels' 32-bit byte offsets
   if (!nb) return 1;
+  if (poison(c, soft_all, 2 * plane, (hipStream_t)stream)) return 1;      // (the caller's tail planes are the caller's to fill)
   for (int b0 = 0; b0 < B; b0 += nb) {
     const int bb = std::min(nb, B - b0);
     const se_ctx::Peaks pk = plan_peaks(c, 3, bb, H, W, flags, false);
@@ -1591,6 +1622,7 @@ int se_inference_u8io(se_ctx* c, void* stream, const unsigned char* image_u8, co
   float* image = (float*)((char*)ws + ws_bytes - 4 * plane);      // (B,3,H,W) contiguous: 3 B H W floats <= 3 planes
   float* sketch = (float*)((char*)ws + ws_bytes - plane);
   set_profiler(&c->prof);
+  if (poison(c, image, 4 * plane, (hipStream_t)stream)) return 1;
   HIPCHK(c, launch_dequantize_u8(image_u8, sketch_u8, c->lut8, image, sketch, B, H, W, (hipStream_t)stream));
   return inference_u8_locked(c, stream, image, sketch, rgb_out, mask_u8_out, ws, ws_bytes, B, H, W, flags, 4);
 }
@@ -1684,6 +1716,7 @@ int se_edit_u8(se_ctx* c, void* stream, const unsigned char* image_u8, const uns
   float* image = (float*)(fws + fws_bytes - 4 * plane);      // where se_inference_u8io keeps them
   float* sketch = (float*)(fws + fws_bytes - plane);
   const hipStream_t st = (hipStream_t)stream;
+  if (poison(c, rgb_work, rgbw, st) || poison(c, image, 4 * plane, st)) return 1;
   if (prepare_locked(c, st, image_u8, B, Hi, Wi, sketch_u8, Hs, Ws, image, sketch, H, W)) return 1;
   if (inference_u8_locked(c, stream, image, sketch, rgb_work, nullptr, fws, fws_bytes, B, H, W, flags, 4)) return 1;
   ResizeOut o{RESIZE_OUT_U8, rgb_out, nullptr, nullptr, 0, 0};
@@ -1825,6 +1858,7 @@ int gather_resize_locked(se_ctx* c, hipStream_t st, const se_window* d, int B, i
     ResizeOut o{C == 3 ? RESIZE_OUT_IMAGE_F32 : RESIZE_OUT_SKETCH_F32, nullptr, out, c->lut8, H, W};
     ResizeOut oh = o;
     if (need_v) { oh.mode = RESIZE_OUT_U8; oh.u8 = mid; oh.H = hs; }
+    if (need_v && poison(c, mid, gather_mid_bytes(B, hs, W), st)) return 1;      // (each pass: the sketch's reuses the image's)
     HIPCHK(c, launch_window_resample_h(d, t[0]->dev, t[0]->dev + 2 * (size_t)W, t[0]->host.data(), t[0]->ksize, B, hs, ws, W, C, oh, st));
     if (need_v) HIPCHK(c, launch_resample_v(mid, t[1]->dev, t[1]->dev + 2 * (size_t)H, t[1]->ksize, B, hs, H, W, C, o, st));
   }
@@ -1842,6 +1876,7 @@ int paste_resize_locked(se_ctx* c, hipStream_t st, const se_window* d, int B, in
   int P = W;
   if (need_h) {
     P = paste_pitch(ws);
+    if (poison(c, mid, paste_mid_bytes(B, H, ws), st)) return 1;
     unsigned char* mid_rgb = mid;
     unsigned char* mid_m = mid + pad256((size_t)B * H * P * 3);
     const int* dk = t[1]->dev;
@@ -1902,6 +1937,7 @@ int lock_gather_locked(se_ctx* c, hipStream_t st, const se_window* d, int B, int
   ResizeOut o{RESIZE_OUT_LOCK_U8, lock_out, nullptr, nullptr, H, W};
   ResizeOut oh = o;
   if (need_v) { oh.mode = RESIZE_OUT_U8; oh.u8 = mid; oh.H = hs; }
+  if (need_v && poison(c, mid, lock_mid_bytes(B, hs, W), st)) return 1;
   HIPCHK(c, launch_window_lock_resample_h(d, t[0]->dev, t[0]->dev + 2 * (size_t)W, t[0]->host.data(), t[0]->ksize, B, hs, ws, W, oh, st));
   if (need_v) HIPCHK(c, launch_resample_v(mid, t[1]->dev, t[1]->dev + 2 * (size_t)H, t[1]->ksize, B, hs, H, W, 1, o, st));
   return 0;
@@ -1940,6 +1976,11 @@ int edit_window_locked(se_ctx* c, void* stream, const se_window* wins, int B, in
   const hipStream_t st = (hipStream_t)stream;
   if (scaled && rs_enter(c, st)) return 1;
   set_profiler(&c->prof);
+  // SE_TEST_POISON: the regions in front of the forward's part that the caller left to the workspace, and the fp32 inputs
+  // (`mid` is filled where it is used: gather_resize_locked, lock_gather_locked, paste_resize_locked)
+  if ((!rgb_out && poison(c, rgb, rgbw, st)) || (!mask_u8_out && poison(c, m8, mw, st)) || (!hits_out && poison(c, hits, hw, st)) ||
+      poison(c, lock8, lockw, st) || poison(c, image, 4 * plane, st))
+    return 1;
   const se_window* d = locked ? win_put_locks(c, st, wins, locks, B) : win_put(c, st, wins, B);
   if (!d) return 1;
   if (scaled) {
@@ -2302,11 +2343,13 @@ int se_gated_conv2d_ex(se_ctx* c, void* stream, const float* x, const float* x1,
     }
   } drain{c};
   HIPCHK(c, xin.alloc((size_t)B * H * W * Cp * 4));
+  if (poison(c, xin, (size_t)B * H * W * Cp * 4, c->st)) return 1;
   int rc = (bf ? launch_nchw_to_nhwc16 : launch_nchw_to_nhwc)(x, xin, B, Cin, Cp, H, W, c->st) != hipSuccess;
   if (!rc && x1) {
     // second source of the virtual concat (editline_g.py:166-167,211): a tensor (B,Cin1,H,W) or a per-image vector (B,Cin1)
     const size_t n1 = x1_is_vector ? (size_t)B * Cin1 : (size_t)B * H * W * Cin1;
     HIPCHK(c, x1in.alloc(n1 * 4));
+    if (poison(c, x1in, n1 * 4, c->st)) return 1;
     if (x1_is_vector && !bf) rc = hipMemcpyAsync(x1in, x1, n1 * 4, hipMemcpyDeviceToDevice, c->st) != hipSuccess;
     else if (x1_is_vector) rc = launch_nchw_to_nhwc16(x1, x1in, B, Cin1, Cin1, 1, 1, c->st) != hipSuccess;
     else rc = (bf ? launch_nchw_to_nhwc16 : launch_nchw_to_nhwc)(x1, x1in, B, Cin1, Cin1, H, W, c->st) != hipSuccess;
@@ -2322,8 +2365,10 @@ int se_gated_conv2d_ex(se_ctx* c, void* stream, const float* x, const float* x1,
     const ConvShape sh = conv_shape(L.def, H, W);
     const int Gs = bf ? (Cout / 2 + 7) & ~7 : Cout / 2;
     HIPCHK(c, yout.alloc((size_t)B * sh.Ho * sh.Wo * Gs * 4));
+    if (poison(c, yout, (size_t)B * sh.Ho * sh.Wo * Gs * 4, c->st)) return 1;
     if (x1in && x1_is_vector) {               // scratch of the folded vector source (the forwards take it from the workspace)
       HIPCHK(c, vb_test.alloc((size_t)B * 9 * 192 * 4));
+      if (poison(c, vb_test, (size_t)B * 9 * 192 * 4, c->st)) return 1;
       c->vbias_ws = vb_test;
       c->vec32 = bf ? x1 : nullptr;           // bf16 mode: the caller's fp32 vector (x1in is its bf16 rounding)
     }
@@ -2359,6 +2404,7 @@ int se_attention_ex(se_ctx* c, void* stream, const float* x, const float* mask_f
   const size_t bytes = ((size_t)B * h * w * 96 * 3 + rr + (size_t)B * Rp * (7 + 4 * 96) + 64 * 96 * B + 2 * (size_t)B * R + 9 * (size_t)(w / 2 + 72) + (size_t)B * (768 + (h / 2) * 384)) * 4 + (1 << 16);
   char* ws = nullptr;
   HIPCHK(c, hipMalloc(&ws, bytes));
+  if (poison(c, ws, bytes, c->st)) { (void)hipStreamSynchronize(c->st); (void)hipFree(ws); return 1; }      // (what no block covers, too)
   c->arena.reset(ws, bytes, false);
   c->arena2.reset(nullptr, 0, false);
   Plan P(c, c->G, B);

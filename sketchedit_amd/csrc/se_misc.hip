@@ -31,7 +31,7 @@ struct OptTable {
 #undef X
     };
     for (int i = 0; i < OPT_COUNT; ++i) {
-      const char* e = i == OPT_TEST_OFFSET_LIMIT ? nullptr : getenv(names[i]);      // (the test aid is not an environment switch)
+      const char* e = (i == OPT_TEST_OFFSET_LIMIT || i == OPT_TEST_POISON) ? nullptr : getenv(names[i]);      // (the test aids are not environment switches)
       dflt[i] = e ? atoi(e) : builtin[i];
       v[i].store(dflt[i], std::memory_order_relaxed);
     }

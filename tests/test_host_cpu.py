@@ -497,11 +497,14 @@ def test_developer_switches_are_a_table_read_once():
     try:                                                  # every mutation inside try / finally: nothing leaks into later tests
         _lib.set_option("SE_WINOGRAD_F43", 2)
         _lib.set_option("SE_TEST_OFFSET_LIMIT", 12345)
+        _lib.set_option("SE_TEST_POISON", 0xC7)
         assert _lib.get_option("SE_WINOGRAD_F43") == 2 and _lib.get_option("SE_TEST_OFFSET_LIMIT") == 12345
+        assert _lib.get_option("SE_TEST_POISON") == 0xC7
         os.environ["SE_WINOGRAD_F43"] = "0"              # the environment is not consulted again
         assert _lib.get_option("SE_WINOGRAD_F43") == 2
         _lib.reset_options()
         assert _lib.get_option("SE_WINOGRAD_F43") == base_f43 and _lib.get_option("SE_TEST_OFFSET_LIMIT") == 0
+        assert _lib.get_option("SE_TEST_POISON") == 0
     finally:
         _lib.reset_options()
         if saved_env is None:
@@ -516,13 +519,13 @@ def test_developer_switches_are_a_table_read_once():
                     "SE_LL_STAGES", "SE_RCONV16_TILE", "SE_WINOUP_TILES", "SE_WINO48_TILES", "SE_ATT_PV_PT"):
         with pytest.raises(_lib.SketchEditHipError):
             _lib.get_option(retired)                      # A/B-only variants, retired with their kernels
-    # a fresh process takes its initial values from the environment -- except the test aid, which only the call can set
+    # a fresh process takes its initial values from the environment -- except the test aids, which only the call can set
     code = ("from sketchedit_amd import _lib; print(_lib.get_option('SE_WINOGRAD_F43'), _lib.get_option('SE_ATT_E16'), "
-            "_lib.get_option('SE_TEST_OFFSET_LIMIT'))")
-    env = dict(os.environ, SE_WINOGRAD_F43="2", SE_ATT_E16="0", SE_TEST_OFFSET_LIMIT="777")
+            "_lib.get_option('SE_TEST_OFFSET_LIMIT'), _lib.get_option('SE_TEST_POISON'))")
+    env = dict(os.environ, SE_WINOGRAD_F43="2", SE_ATT_E16="0", SE_TEST_OFFSET_LIMIT="777", SE_TEST_POISON="255")
     out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.split() == ["2", "0", "0"]
+    assert out.stdout.split() == ["2", "0", "0", "0"]
 
 
 def test_dataset_u8_mode_carries_the_decoders_arrays(tmp_path):
