@@ -354,6 +354,53 @@ int se_attention(se_ctx* ctx, void* stream, const float* x, const float* mask_fu
 int se_attention_ex(se_ctx* ctx, void* stream, const float* x, const float* mask_full, float* out, float* similar_out,
                     int B, int h, int w, int exec_flags);
 
+/* The kernels between the convolutions, through the launchers the forwards call (tests/test_gpu_glue.py).  Any B, H, W >= 1.
+ *
+ * Input packing, the first kernel of netM / netG.  net_id SE_NET_M (editline2_g.py:62): x = image (B,3,H,W), guide = sketch
+ * (B,1,H,W), the others ignored; packed_out (B,H,W,4) fp32 = [image(3), sketch].  net_id SE_NET_G (editline_g.py:120-135):
+ * x, x2 (B,3,H,W), mask, mask2, guide (B,1,H,W); packed_out (B,H,W,8) fp32 = [x (1 - mask) (3), guide, mask, 0, 0, 0], the
+ * coarse encoder's input; style_out (B,H,W,8) fp32 = [x2 mask2 (3), guide, mask2, 0, 0, 0], or with SE_FLAG_JOINT_TRAIN_INP
+ * in `flags` (B,H,W,4) fp32 = [x2 mask2 (3), mask2]; with SE_FLAG_NO_MASK_CC the three colour channels are x2 itself.
+ * With SE_FLAG_BF16 in exec_flags every buffer is instead ONE 16-byte granule per pixel, (B,H,W,8) bf16, the fp32 values
+ * above rounded to nearest even in the same channel order, the remaining half-words zero.  The kernels write the caller's
+ * buffers directly (device memory, 16-byte aligned): the layout is the contract with the first conv. */
+int se_pack_inputs(se_ctx* ctx, void* stream, int net_id, const float* x, const float* x2, const float* mask, const float* mask2,
+                   const float* guide, void* packed_out, void* style_out, int B, int H, int W, int flags, int exec_flags);
+/* The column reduce over pixels (the pooled style vector, editline_g.py:159-165, and the key norm of the attention): x
+ * (B,C,H,W) fp32 -> out (B,C) fp32; op 0: max, 1: mean, 2: 1 / sqrt(sum x^2 + 1e-8).  Deterministic: the same input gives the
+ * same bits.  SE_FLAG_BF16: x is rounded to bf16 on the way in (the sums stay fp32).  out_bf16 (B,C) bf16, may be NULL: the
+ * result rounded to nearest even, as conv11 reads the style vector in bf16 mode.  Refused (non-zero return, nothing enqueued):
+ * C > 256, C % 4 != 0, with SE_FLAG_BF16 C % 8 != 0. */
+int se_column_reduce(se_ctx* ctx, void* stream, const float* x, float* out, unsigned short* out_bf16, int B, int C, int H, int W,
+                     int op, int exec_flags);
+/* The last kernel of every decoder: the 3x3 conv 12 -> cout with its fused epilogue.  x (B,12,H,W) device, w (cout,12,3,3)
+ * and b (cout) HOST; with SE_FLAG_BF16 x and w are rounded to bf16 on the way in.  With a = conv(x) + b:
+ *   mode 0 (cout 1)  m = lock ? 0 : sigmoid(a) -> out (B,1,H,W);  hard (B,1,H,W) = (m > 0.5);  lock (B,H,W) uint8, non-zero =
+ *                    locked (editline2_g.py:94, editline2_model.py:346-347)
+ *   mode 1 (cout 3)  tanh(a) -> out (B,3,H,W)
+ *   mode 2 (cout 3)  t = tanh(a) -> out;  xnow = t mask + (img (1 - mask)) (1 - mask), or t with no_mask_coarse
+ *                    (editline_g.py:124,179-180): (B,H,W,4) fp32 with a zero fourth channel, or with SE_FLAG_BF16 one
+ *                    16-byte granule per pixel, (B,H,W,8) bf16, channels 3-7 zero
+ *   mode 3 (cout 3)  t = tanh(a) -> out;  v = t mask + img (1 - mask) -> composed (B,3,H,W) (editline2_model.py:132);
+ *                    rgb8 (B,H,W,3) uint8 = trunc((v + 1) * 0.5 * 255), m8 (B,H,W) uint8 = trunc(mask * 255) (test.py:25-27)
+ * img (B,3,H,W), mask (B,1,H,W).  Every pointer but those a mode needs (0: out; 2: img, mask, xnow; 3: img and mask where
+ * composed, rgb8 or m8 is given) may be NULL.  packed != 0 gives the strides of SE_FLAG_PACKED_OUT: one (B,4,H,W) buffer, the
+ * composite in planes 0-2 and the soft mask in plane 3 -- mode 0 then takes `out`, mode 3 `mask` and `composed`, with a batch
+ * stride of 4 H W floats, each pointing at its plane of image 0. */
+typedef struct se_output_conv_io {
+  float* out;
+  float* hard;
+  const unsigned char* lock;
+  const float* img;
+  const float* mask;
+  void* xnow;
+  float* composed;
+  unsigned char* rgb8;
+  unsigned char* m8;
+} se_output_conv_io;
+int se_output_conv(se_ctx* ctx, void* stream, const float* x, const float* w_host, const float* b_host, int B, int H, int W,
+                   int cout, int mode, const se_output_conv_io* io, int no_mask_coarse, int packed, int exec_flags);
+
 #ifdef __cplusplus
 }
 #endif

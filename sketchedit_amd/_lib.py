@@ -40,7 +40,8 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
            "se_window_gather_resize_u8", "se_window_paste_resize_u8", "se_edit_window_scaled_u8", "se_edit_window_scaled_u8_workspace_bytes",
            "se_window_saved_bytes", "se_window_save_u8", "se_window_swap_u8",
            "se_inference_locked", "se_inference_u8_locked", "se_window_gather_lock_u8", "se_window_paste_locked_u8",
-           "se_edit_window_locked_u8", "se_edit_window_locked_u8_workspace_bytes"]
+           "se_edit_window_locked_u8", "se_edit_window_locked_u8_workspace_bytes",
+           "se_pack_inputs", "se_column_reduce", "se_output_conv"]
 
 
 class SketchEditHipError(RuntimeError):
@@ -57,6 +58,11 @@ class Window(ctypes.Structure):
     pointers) and where the window lies in the frame"""
     _fields_ = [("frame_u8", ctypes.c_void_p), ("sketch_u8", ctypes.c_void_p), ("Hi", ctypes.c_int), ("Wi", ctypes.c_int),
                 ("y0", ctypes.c_int), ("x0", ctypes.c_int)]
+
+
+class OutputConvIO(ctypes.Structure):
+    """se_output_conv_io (include/sketchedit_hip.h): the optional tensors of the output conv's epilogue, device pointers or NULL"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("out", "hard", "lock", "img", "mask", "xnow", "composed", "rgb8", "m8")]
 
 
 def build_library(force=False, verbose=False, extra_flags=()):
@@ -204,6 +210,12 @@ def load_library():
         lib.se_edit_window_locked_u8.restype = ci
         lib.se_edit_window_locked_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci, ci]
         lib.se_edit_window_locked_u8_workspace_bytes.restype = sz
+        lib.se_pack_inputs.argtypes = [vp, vp, ci, c_f, c_f, c_f, c_f, c_f, vp, vp, ci, ci, ci, ci, ci]
+        lib.se_pack_inputs.restype = ci
+        lib.se_column_reduce.argtypes = [vp, vp, c_f, c_f, vp, ci, ci, ci, ci, ci, ci]
+        lib.se_column_reduce.restype = ci
+        lib.se_output_conv.argtypes = [vp, vp, c_f, c_f, c_f, ci, ci, ci, ci, ci, ctypes.POINTER(OutputConvIO), ci, ci, ci]
+        lib.se_output_conv.restype = ci
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -931,6 +943,66 @@ class Engine:
                                        (FLAG_LOW_LATENCY if low_latency else 0) | (FLAG_BF16 if bf16 else 0)):
             self._err("se_gated_conv2d_ex")
         return y
+
+    def pack_inputs(self, net, x, guide, x2=None, mask=None, mask2=None, flags=0, bf16=False):
+        """se_pack_inputs: the first kernel of netM (net 'M': x = image, guide = sketch -> packed) or netG (net 'G' ->
+        (coarse input, style input)), as the first conv reads them: fp32 (B,H,W,4 or 8), or with bf16 a (B,H,W,8) int16 tensor
+        holding the bf16 bit patterns of one 16-byte granule per pixel."""
+        import torch
+        _check_dev(x, guide, x2, mask, mask2)
+        B, _, H, W = x.shape
+        dev = x.device
+
+        def buf(ch):
+            return torch.empty((B, H, W, 8), dtype=torch.int16, device=dev) if bf16 else \
+                torch.empty((B, H, W, ch), dtype=torch.float32, device=dev)
+        joint = bool(flags & FLAG_JOINT_TRAIN_INP)
+        packed = buf(4 if net == "M" else 8)
+        style = None if net == "M" else buf(4 if joint else 8)
+        if self.lib.se_pack_inputs(self.h, self._stream(), SE_NET_M if net == "M" else SE_NET_G, _ptr(x), _ptr(x2), _ptr(mask),
+                                   _ptr(mask2), _ptr(guide), _ptr(packed), _ptr(style), B, H, W, flags & 31,
+                                   FLAG_BF16 if bf16 else 0):
+            self._err("se_pack_inputs")
+        return packed if net == "M" else (packed, style)
+
+    def column_reduce(self, x, op, bf16=False):
+        """se_column_reduce: x (B,C,H,W) -> (B,C) fp32; op 'max', 'mean' or 'rsqrt' (1 / sqrt(sum x^2 + 1e-8)).  With bf16 ->
+        (fp32 result, its bf16 copy as an int16 tensor of bit patterns)."""
+        import torch
+        _check_dev(x)
+        B, C, H, W = x.shape
+        out = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        out16 = torch.empty((B, C), dtype=torch.int16, device=x.device) if bf16 else None
+        if self.lib.se_column_reduce(self.h, self._stream(), _ptr(x), _ptr(out), _ptr(out16), B, C, H, W,
+                                     {"max": 0, "mean": 1, "rsqrt": 2}[op], FLAG_BF16 if bf16 else 0):
+            self._err("se_column_reduce")
+        return (out, out16) if bf16 else out
+
+    def output_conv(self, x, w, b, mode, bf16=False, no_mask_coarse=False, packed=None, **io):
+        """se_output_conv: the 3x3 conv 12 -> cout with the epilogue of `mode` (0 sigmoid + threshold + lock, 1 tanh, 2 tanh +
+        stage-2 input, 3 tanh + composite + uint8 outputs).  io: the tensors of se_output_conv_io by name (device tensors the
+        caller allocated; absent = NULL).  packed: a (B,4,H,W) fp32 buffer -- mode 0 writes the soft mask into its plane 3, mode
+        3 reads the mask there and writes the composite into planes 0-2 (`out` / `mask` / `composed` must then be absent)."""
+        _check_dev(x, packed)
+        w = np.ascontiguousarray(w, np.float32)
+        b = np.ascontiguousarray(b, np.float32)
+        B, _, H, W = x.shape
+        assert x.shape[1] == 12 and w.shape[1:] == (12, 3, 3) and b.shape == (w.shape[0],)
+        ptrs = {k: (None if t is None else t.data_ptr()) for k, t in io.items()}
+        if packed is not None:
+            assert tuple(packed.shape) == (B, 4, H, W)
+            plane3 = packed.data_ptr() + 3 * H * W * 4
+            if mode == 0:
+                assert "out" not in ptrs
+                ptrs["out"] = plane3
+            if mode == 3:
+                assert "mask" not in ptrs and "composed" not in ptrs
+                ptrs["mask"], ptrs["composed"] = plane3, packed.data_ptr()
+        rec = OutputConvIO(**ptrs)
+        if self.lib.se_output_conv(self.h, self._stream(), _ptr(x), w.ctypes.data_as(ctypes.c_void_p),
+                                   b.ctypes.data_as(ctypes.c_void_p), B, H, W, w.shape[0], int(mode), ctypes.byref(rec),
+                                   int(bool(no_mask_coarse)), int(packed is not None), FLAG_BF16 if bf16 else 0):
+            self._err("se_output_conv")
 
     def quantize_u8(self, composed, mask):
         """test.py:25-27 on the device: ((composed+1)/2*255) -> uint8 (B,H,W,3) RGB, (mask*255) -> uint8 (B,H,W)."""

@@ -2423,4 +2423,103 @@ int se_attention(se_ctx* c, void* stream, const float* x, const float* mask_full
   return se_attention_ex(c, stream, x, mask_full, out, similar_out, B, h, w, 0);
 }
 
+// ---- the kernels between the convolutions: input packing, pooling, output conv (tests/test_gpu_glue.py) ----
+int se_pack_inputs(se_ctx* c, void* stream, int net_id, const float* x, const float* x2, const float* mask, const float* mask2,
+                   const float* guide, void* packed_out, void* style_out, int B, int H, int W, int flags, int exec_flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (B < 1 || H < 1 || W < 1) return fail(c, "pack: bad shape B=%d H=%d W=%d", B, H, W);
+  if (net_id != SE_NET_M && net_id != SE_NET_G) return fail(c, "pack: net_id must be SE_NET_G or SE_NET_M");
+  if (!x || !guide || !packed_out || (net_id == SE_NET_G && (!x2 || !mask || !mask2 || !style_out))) return fail(c, "null pointer argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  begin_call(c, stream, exec_flags & SE_FLAG_BF16);
+  // no scratch: the kernels write the caller's buffers directly, as they write the first conv's input in the forwards
+  if (net_id == SE_NET_M) {      // plan_netM
+    HIPCHK(c, (c->bf16 ? launch_pack_m16 : launch_pack_m)(x, guide, (float*)packed_out, B, H, W, c->st));
+  } else {                       // plan_netG
+    HIPCHK(c, (c->bf16 ? launch_pack_g16 : launch_pack_g)(x, x2, mask, mask2, guide, (float*)packed_out, (float*)style_out, B, H, W,
+                                                          (flags & SE_FLAG_NO_MASK_CC) ? 1 : 0,
+                                                          (flags & SE_FLAG_JOINT_TRAIN_INP) ? 1 : 0, c->st));
+  }
+  return 0;
+}
+
+int se_column_reduce(se_ctx* c, void* stream, const float* x, float* out, unsigned short* out_bf16, int B, int C, int H, int W,
+                     int op, int exec_flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!x || !out) return fail(c, "null pointer argument");
+  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(c, "column reduce: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+  if (op < 0 || op > 2) return fail(c, "column reduce: op must be 0 (max), 1 (mean) or 2 (rsqrt of the sum of squares)");
+  const bool bf = (exec_flags & SE_FLAG_BF16) != 0;
+  // what launch_colreduce refuses, before anything is allocated or enqueued
+  if (C > 256 || C % (bf ? 8 : 4))
+    return fail(c, "column reduce: C = %d must be a multiple of %d and at most 256", C, bf ? 8 : 4);
+  if ((double)B * H * W * C * (bf ? 2 : 4) >= 2147483648.0) return fail(c, "column reduce: B H W C beyond the 32-bit byte range");
+  HIPCHK(c, hipSetDevice(c->device));
+  begin_call(c, stream, exec_flags & SE_FLAG_BF16);
+  DevBuf xin, part;
+  struct Drain {      // the launches on c->st read the scratch: every return drains the stream before it is freed
+    se_ctx* c;
+    ~Drain() { (void)hipStreamSynchronize(c->st); }
+  } drain{c};
+  const size_t xbytes = (size_t)B * H * W * C * (bf ? 2 : 4), pbytes = (size_t)B * COLREDUCE_SPLITS * C * 4;
+  HIPCHK(c, xin.alloc(xbytes));
+  HIPCHK(c, part.alloc(pbytes));
+  if (poison(c, xin, xbytes, c->st) || poison(c, part, pbytes, c->st)) return 1;
+  HIPCHK(c, (bf ? launch_nchw_to_nhwc16 : launch_nchw_to_nhwc)(x, xin, B, C, C, H, W, c->st));
+  HIPCHK(c, launch_colreduce(xin, part, out, B, H * W, C, op, c->st, bf ? 1 : 0, (float*)out_bf16));
+  return 0;
+}
+
+int se_output_conv(se_ctx* c, void* stream, const float* x, const float* w_host, const float* b_host, int B, int H, int W, int cout,
+                   int mode, const se_output_conv_io* io, int no_mask_coarse, int packed, int exec_flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!x || !w_host || !b_host || !io) return fail(c, "null pointer argument");
+  if (B < 1 || H < 1 || W < 1) return fail(c, "output conv: bad shape B=%d H=%d W=%d", B, H, W);
+  if (mode < 0 || mode > 3) return fail(c, "output conv: mode must be 0..3");
+  if (cout != (mode == 0 ? 1 : 3)) return fail(c, "output conv: mode %d has %d output channels", mode, mode == 0 ? 1 : 3);
+  // the pointers the kernel dereferences without a test
+  if (mode == 0 && !io->out) return fail(c, "output conv: mode 0 writes `out`");
+  if (mode == 2 && (!io->img || !io->mask || !io->xnow)) return fail(c, "output conv: mode 2 needs img, mask and xnow");
+  if (mode == 3 && (io->composed || io->rgb8 || io->m8) && (!io->img || !io->mask))
+    return fail(c, "output conv: the composite of mode 3 needs img and mask");
+  HIPCHK(c, hipSetDevice(c->device));
+  begin_call(c, stream, exec_flags & SE_FLAG_BF16);
+  const bool bf = c->bf16;
+  Layer L;
+  L.def = LayerDef{"test", 12, cout, 3, 1, 1, ACT_NONE, 0};
+  L.w.assign(w_host, w_host + (size_t)cout * 12 * 9);
+  L.b.assign(b_host, b_host + cout);
+  std::vector<int> chans(12);
+  std::iota(chans.begin(), chans.end(), 0);
+  if (pack_layer_images(L, chans, c->err)) return 1;
+  DevBuf xin;
+  struct Drain {      // the launches on c->st read xin and the layer's images: every return drains the stream before they are freed
+    se_ctx* c;
+    ~Drain() { (void)hipStreamSynchronize(c->st); }
+  } drain{c};
+  const int Cp = bf ? 16 : 12;
+  const size_t xbytes = (size_t)B * H * W * Cp * (bf ? 2 : 4);
+  HIPCHK(c, xin.alloc(xbytes));
+  if (poison(c, xin, xbytes, c->st)) return 1;
+  HIPCHK(c, (bf ? launch_nchw_to_nhwc16 : launch_nchw_to_nhwc)(x, xin, B, 12, Cp, H, W, c->st));
+  SmallConvParams sp;      // filled as small() fills it
+  memset(&sp, 0, sizeof sp);
+  sp.x = xin; sp.w = L.direct[bf].w; sp.b = L.d_b; sp.B = B; sp.H = H; sp.W = W; sp.cout = cout;
+  sp.bf16 = bf ? 1 : 0;
+  sp.mode = mode; sp.out_nchw = io->out; sp.hard = io->hard; sp.img = io->img; sp.mask = io->mask; sp.xnow = (float*)io->xnow;
+  sp.composed = io->composed; sp.no_mask_coarse = no_mask_coarse ? 1 : 0;
+  if (mode == 3) { sp.rgb8 = io->rgb8; sp.m8 = io->m8; }
+  if (mode == 0) sp.lock = io->lock;
+  if (packed) {
+    const long packed_bs = 4l * H * W;
+    if (mode == 0) sp.out_bs = packed_bs;
+    if (mode == 3) { sp.mask_bs = packed_bs; sp.comp_bs = packed_bs; }
+  }
+  HIPCHK(c, launch_small_conv(sp, c->st));
+  return 0;
+}
+
 }  // extern "C"

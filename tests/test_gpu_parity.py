@@ -68,6 +68,22 @@ def test_op_gated_conv_golden(eng, golden_dir, case):
     assert _md(y, g["op." + name]) < TOL_OP
 
 
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("cout", [1, 3])
+def test_op_raw_conv_four_row_strips(eng, cout, bf16):
+    """The raw 12 -> {1,3} conv of the two golden cases above (12 x 16: 2-row strips) at 1 x 1037 x 252, where
+    launch_small_conv takes the 4-row strips (B ceil(H / 4) W = 65520 > 65280) and the last strip has ONE row; against the
+    float64 conv of the same inputs (bf16 mode: of x and w rounded to bf16)."""
+    B, H, W = 1, 1037, 252
+    w = synth.uniform(7, "raw4.w%d" % cout, (cout, 12, 3, 3), -0.5, 0.5)
+    b = synth.uniform(7, "raw4.b%d" % cout, (cout,), -0.5, 0.5)
+    x = synth.uniform(7, "raw4.x", (B, 12, H, W), -1, 1)
+    y = eng.gated_conv2d(_cuda(x), w, b, act=None, bf16=bf16)
+    rnd = (lambda a: torch.from_numpy(a).to(torch.bfloat16).double()) if bf16 else (lambda a: torch.from_numpy(a).double())
+    ref = torch.nn.functional.conv2d(rnd(x), rnd(w), torch.from_numpy(b).double(), padding=1)
+    assert tuple(y.shape) == (B, cout, H, W) and _md(y, ref) < TOL_OP
+
+
 def test_op_deconv_golden(eng, golden_dir):
     g = _load(golden_dir, "ops.npz")
     w = synth.uniform(7, "deconv.w", (16, 8, 3, 3), -0.5, 0.5)

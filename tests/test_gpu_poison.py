@@ -572,6 +572,66 @@ def test_window_save_and_swap(eng, seopt, window_hw):
     _four(seopt, call)
 
 
+# ---- the kernels between the convolutions (shapes of tests/test_gpu_glue.py) -------------------------------------------------
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("net", ["M", "G", "G-joint"])
+def test_pack_inputs(eng, seopt, net, bf16):
+    from test_gpu_glue import _pack_case
+    x, x2, mask, mask2, guide = (_cuda(a) for a in _pack_case(5, 7))
+
+    def call(v):
+        if net == "M":
+            return {"packed": eng.pack_inputs("M", x, guide, bf16=bf16)}
+        coarse, style = eng.pack_inputs("G", x, guide, x2, mask, mask2, flags=16 if net == "G-joint" else 0, bf16=bf16)
+        return {"coarse": coarse, "style": style}
+    _four(seopt, call)
+
+
+# (C, H, W): an HW < 128 pool (most splits empty), the 40 x 72 input's, a granule count that does not divide 256 at a size
+# that reaches the four-loads-in-flight loop
+POOLS = [(96, 4, 4), (96, 10, 18), (104, 82, 100)]
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("op", ["max", "mean", "rsqrt"])
+@pytest.mark.parametrize("case", POOLS, ids=lambda c: "c%d-%dx%d" % c)
+def test_column_reduce(eng, seopt, case, op, bf16):
+    C, H, W = case
+    x = _cuda(synth.uniform(71, "pool%s" % (case,), (3, C, H, W), -1, 1))
+
+    def call(v):
+        r = eng.column_reduce(x, op, bf16=bf16)
+        return {"out": r[0], "out16": r[1]} if bf16 else {"out": r}
+    _four(seopt, call)
+
+
+# 2-row strips, and a 4-row-strip launch whose last strip has one row
+OUTPUT_CONVS = [(3, 5, 7), (2, 12, 16), (1, 1037, 252)]
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("shape", OUTPUT_CONVS, ids=lambda s: "%dx%dx%d" % s)
+def test_output_conv(eng, seopt, shape, bf16):
+    B, H, W = shape
+    a = 1.5 / np.sqrt(108.0)
+    w1, w3 = synth.uniform(73, "oc.w1", (1, 12, 3, 3), -a, a), synth.uniform(73, "oc.w3", (3, 12, 3, 3), -a, a)
+    b1, b3 = np.float32([0.3]), np.float32([-1.0, 0.1, 1.0])
+    x = _cuda(synth.uniform(73, "oc.x%s" % (shape,), (B, 12, H, W), -4, 4))
+    img = _cuda(synth.uniform(73, "oc.img%s" % (shape,), (B, 3, H, W), -1, 1))
+    mask = _cuda(synth.uniform(73, "oc.mask%s" % (shape,), (B, 1, H, W), 0, 1))
+    lock = _u8(synth.uniform(73, "oc.lock%s" % (shape,), (B, H, W), 0, 1) < 0.3)
+
+    def call(v):
+        r = {"mask": _empty(v, (B, 1, H, W)), "hard": _empty(v, (B, 1, H, W)), "coarse": _empty(v, (B, 3, H, W)),
+             "xnow": _empty(v, (B, H, W, 8), torch.int16) if bf16 else _empty(v, (B, H, W, 4)), "fine": _empty(v, (B, 3, H, W)),
+             "composed": _empty(v, (B, 3, H, W)), "rgb8": _empty(v, (B, H, W, 3), torch.uint8), "m8": _empty(v, (B, H, W), torch.uint8)}
+        eng.output_conv(x, w1, b1, 0, bf16=bf16, out=r["mask"], hard=r["hard"], lock=lock)
+        eng.output_conv(x, w3, b3, 2, bf16=bf16, out=r["coarse"], img=img, mask=mask, xnow=r["xnow"])
+        eng.output_conv(x, w3, b3, 3, bf16=bf16, out=r["fine"], img=img, mask=mask, composed=r["composed"], rgb8=r["rgb8"], m8=r["m8"])
+        return r
+    _four(seopt, call)
+
+
 # ---- guard conditions: the harness cannot pass vacuously --------------------------------------------------------------------
 def test_poisoned_forward_still_runs(eng, seopt):
     """with the option on, the forward still launches its kernels (the profiler counts them) and leaves the graph cache alone"""
