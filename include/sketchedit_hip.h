@@ -297,6 +297,17 @@ int se_edit_window_locked_u8(se_ctx* ctx, void* stream, const se_window* wins, c
                              void* workspace, size_t workspace_bytes, int flags);
 size_t se_edit_window_locked_u8_workspace_bytes(se_ctx* ctx, int B, int hs, int ws, int H, int W);
 
+/* ---- region edits of an editing session ---------------------------------------------------------------------
+ * Where a full-size sketch is drawn: sketch_u8 is an (Hi,Wi) uint8 plane in device memory (its base may have any alignment),
+ * cut into tile x tile squares, tile in {16, 32, 64}; the last row / column of squares is ragged where tile does not divide
+ * Hi / Wi.  tiles_out (ceil(Hi / tile), ceil(Wi / tile), 5) int32, device, 4-byte aligned: one record [count, y0, x0, y1, x1]
+ * per square -- the number of its pixels > 0 and their tight half-open box in FRAME coordinates; five zeros for an empty
+ * square.  EVERY record is written (the buffer need not be zeroed) and no byte outside the plane's Hi Wi bytes is read, even
+ * inside the same allocation.  Deterministic: one wave per square, shuffle reductions, plain stores, no atomics.  One launch,
+ * no workspace (SE_TEST_POISON has nothing to fill).  Refused before anything is enqueued (non-zero return, se_last_error
+ * names the argument, tiles_out untouched): Hi or Wi < 16, another tile, a NULL pointer, a misaligned tiles_out. */
+int se_sketch_tiles_u8(se_ctx* ctx, void* stream, const unsigned char* sketch_u8, int Hi, int Wi, int tile, int* tiles_out);
+
 /* Host only (no HIP call, no ctx): the coefficient table the resize uses for one axis.  Returns ksize, the taps per output
  * (-1: bad arguments); when bounds (2*out ints: first input index, tap count) and k (cap >= out*ksize ints, fixed point
  * with 22 fractional bits, rows zero padded to ksize) are given, fills them.  Lets a test compare the tables with Pillow's. */

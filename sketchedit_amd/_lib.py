@@ -40,7 +40,7 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
            "se_window_gather_resize_u8", "se_window_paste_resize_u8", "se_edit_window_scaled_u8", "se_edit_window_scaled_u8_workspace_bytes",
            "se_window_saved_bytes", "se_window_save_u8", "se_window_swap_u8",
            "se_inference_locked", "se_inference_u8_locked", "se_window_gather_lock_u8", "se_window_paste_locked_u8",
-           "se_edit_window_locked_u8", "se_edit_window_locked_u8_workspace_bytes",
+           "se_edit_window_locked_u8", "se_edit_window_locked_u8_workspace_bytes", "se_sketch_tiles_u8",
            "se_pack_inputs", "se_column_reduce", "se_output_conv"]
 
 
@@ -210,6 +210,8 @@ def load_library():
         lib.se_edit_window_locked_u8.restype = ci
         lib.se_edit_window_locked_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci, ci]
         lib.se_edit_window_locked_u8_workspace_bytes.restype = sz
+        lib.se_sketch_tiles_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+        lib.se_sketch_tiles_u8.restype = ci
         lib.se_pack_inputs.argtypes = [vp, vp, ci, c_f, c_f, c_f, c_f, c_f, vp, vp, ci, ci, ci, ci, ci]
         lib.se_pack_inputs.restype = ci
         lib.se_column_reduce.argtypes = [vp, vp, c_f, c_f, vp, ci, ci, ci, ci, ci, ci]
@@ -891,6 +893,24 @@ class Engine:
                                              1 if commit else 0, _ptr(ws_t), ws_t.numel(), flags):
             self._err("se_edit_window_locked_u8")
         return rgb, m8, hits
+
+    # ---- region edits ------------------------------------------------------------------------------------------
+    def sketch_tiles_u8(self, sketch_u8, tile, out=None):
+        """se_sketch_tiles_u8: an (Hi,Wi) uint8 plane on the device (any alignment of its base) -> (ceil(Hi / tile),
+        ceil(Wi / tile), 5) int32 on the device, [count, y0, x0, y1, x1] per tile x tile square: the pixels > 0 in it and
+        their tight half-open box in frame coordinates, five zeros for an empty square.  tile in {16, 32, 64}.  `out`: a
+        tensor of that shape to write into (every record is written)."""
+        import torch
+        _check_dev_u8(sketch_u8)
+        if sketch_u8.dim() != 2:
+            raise SketchEditHipError("sketch_tiles_u8: a sketch is an (Hi,Wi) uint8 plane")
+        Hi, Wi = sketch_u8.shape
+        tile = int(tile)
+        if out is None and tile > 0:
+            out = torch.empty((-(-Hi // tile), -(-Wi // tile), 5), dtype=torch.int32, device=sketch_u8.device)
+        if self.lib.se_sketch_tiles_u8(self.h, self._stream(), _ptr(sketch_u8), Hi, Wi, tile, _ptr(out)):
+            self._err("se_sketch_tiles_u8")
+        return out
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):
         """Inference into ONE (B,4,H,W) buffer `out`: planes 0-2 composed, plane 3 the soft mask -- the unit the

@@ -2239,6 +2239,24 @@ int se_window_swap_u8(se_ctx* c, void* stream, const se_window* wins, int B, int
   return window_journal_call(c, stream, wins, B, hs, ws, slots, true);
 }
 
+// ---- region edits: where a full-size sketch is drawn, per tile ----------------------------------------
+// Every check on the host, then ONE launch that writes the caller's records directly: no workspace, nothing for SE_TEST_POISON
+// to fill.
+int se_sketch_tiles_u8(se_ctx* c, void* stream, const unsigned char* sketch_u8, int Hi, int Wi, int tile, int* tiles_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (Hi < 16 || Wi < 16) return fail(c, "bad Hi=%d Wi=%d (a sketch plane is at least 16 x 16)", Hi, Wi);
+  if (tile != 16 && tile != 32 && tile != 64) return fail(c, "bad tile=%d (16, 32 or 64)", tile);
+  if (!sketch_u8 || !tiles_out) return fail(c, "null pointer argument: sketch_u8 / tiles_out");
+  if (!aligned_to(tiles_out, 4)) return fail(c, "tiles_out must be 4-byte aligned");
+  if ((long long)((Hi + tile - 1) / tile) * ((Wi + tile - 1) / tile) > (1ll << 30))
+    return fail(c, "sketch tiles: Hi=%d Wi=%d at tile=%d is more than one launch takes", Hi, Wi, tile);
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  HIPCHK(c, launch_sketch_tiles(sketch_u8, Hi, Wi, tile, tiles_out, (hipStream_t)stream));
+  return 0;
+}
+
 // ---- measurement support (bench.py): per-kernel HIP-event timing ---------------------------------
 int se_profile_enable(se_ctx* c, int on) {
   if (!c) return 1;

@@ -32,6 +32,13 @@
 //                the mask predictor's last kernel takes; a row starts at byte (y0 + r) Wi + x0 and is read as gather reads;
 //  locked paste: paste, with `and lock[y0 + y, x0 + x] == 0` added to the rule -- the four lock bytes of a lane's pixels are
 //                read the same way and those pixels leave the selection before it decides between dwords and bytes.
+//
+// Region edits: one more helper, in front of the forwards, that finds where a full-size sketch is drawn.
+//
+//  sketch tiles: the (Hi, Wi) sketch plane cut into tile x tile squares (the last row / column of squares ragged) -> one record
+//                [count, y0, x0, y1, x1] per square: the pixels > 0 in it and their tight half-open box in frame coordinates,
+//                five zeros for an empty square.  The plane's base and pitch have any alignment: a row's part of a square is
+//                read as gather reads a window row, so no byte outside the plane is read.
 #include "../../include/sketchedit_hip.h"
 #include "se_device.h"
 #include "se_kernels.h"
@@ -262,7 +269,75 @@ __global__ void __launch_bounds__(256) window_paste_locked_kernel(const se_windo
   window_paste<true>(wins, rgb, m8, B, H, W);
 }
 
+// One wave per tile x tile square (TILE 16 / 32 / 64), four squares per workgroup.  A lane owns 4 consecutive bytes of a row of
+// the square, TILE / 4 lanes a row, and the wave walks the square 256 bytes at a time; the bytes come from load4_within bounded
+// by the square's own part of the row, so a byte past the row's end (or the plane's) is never read and counts as 0.  Five
+// shuffle reductions (a sum, two minima, two maxima) and lane 0 stores the record with plain vector stores: every record is
+// written on every call, the empty ones as zeros, and the same plane gives the same bits.
+template <int TILE>
+__global__ void __launch_bounds__(256) sketch_tiles_kernel(const unsigned char* __restrict__ plane, int Hi, int Wi, int ntx, long ntiles,
+                                                           int* __restrict__ out) {
+  constexpr int C = TILE / 4, R = 64 / C;       // lanes per row, rows per step
+  const int lane = threadIdx.x & 63;
+  const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= ntiles) return;                      // (wave-uniform; the kernel has no barrier)
+  const int ty = (int)(t / ntx), tx = (int)(t % ntx);
+  const int xt = tx * TILE, xe = min(xt + TILE, Wi);
+  const int x = xt + 4 * (lane % C);
+  int n = 0, y0 = 0x7fffffff, x0 = 0x7fffffff, y1 = -1, x1 = -1;
+  if (x < xe) {
+#pragma unroll 4
+    for (int r = lane / C; r < TILE; r += R) {
+      const int y = ty * TILE + r;
+      if (y >= Hi) break;
+      const unsigned char* row = plane + (size_t)y * Wi;
+      const unsigned u = load4_within(row + x, row + xt, row + xe);
+      if (!u) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if ((u >> (8 * e)) & 255u) {
+          ++n;
+          x0 = min(x0, x + e);
+          x1 = max(x1, x + e);
+        }
+      }
+      y0 = min(y0, y);
+      y1 = max(y1, y);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n += __shfl_down(n, o, 64);
+    y0 = min(y0, __shfl_down(y0, o, 64));
+    x0 = min(x0, __shfl_down(x0, o, 64));
+    y1 = max(y1, __shfl_down(y1, o, 64));
+    x1 = max(x1, __shfl_down(x1, o, 64));
+  }
+  if (lane == 0) {
+    int* rec = out + t * 5;
+    rec[0] = n;
+    rec[1] = n ? y0 : 0;
+    rec[2] = n ? x0 : 0;
+    rec[3] = n ? y1 + 1 : 0;
+    rec[4] = n ? x1 + 1 : 0;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_sketch_tiles(const unsigned char* plane, int Hi, int Wi, int tile, int* tiles_out, hipStream_t st) {
+  const int ntx = (Wi + tile - 1) / tile;
+  const long ntiles = (long)((Hi + tile - 1) / tile) * ntx;
+  const dim3 grid((unsigned)((ntiles + 3) / 4));
+  // bytes: the plane read once, the records written once
+  set_launch_cost(0.0, (double)Hi * Wi + 20.0 * ntiles, "sketch_tiles");
+  set_launch_grid((ntiles + 3) / 4);
+  ProfScope ps_(st, PL_SKETCH_TILES);
+  if (tile == 16) hipLaunchKernelGGL(sketch_tiles_kernel<16>, grid, dim3(256), 0, st, plane, Hi, Wi, ntx, ntiles, tiles_out);
+  else if (tile == 32) hipLaunchKernelGGL(sketch_tiles_kernel<32>, grid, dim3(256), 0, st, plane, Hi, Wi, ntx, ntiles, tiles_out);
+  else hipLaunchKernelGGL(sketch_tiles_kernel<64>, grid, dim3(256), 0, st, plane, Hi, Wi, ntx, ntiles, tiles_out);
+  return hipGetLastError();
+}
 
 hipError_t launch_window_gather(const se_window* d_wins, const float* lut, float* image, float* sketch, int B, int H, int W,
                                 hipStream_t st) {

@@ -38,6 +38,8 @@ KERNEL_LABELS = {
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",
+    # region edits: the tile pass over a full-size sketch (se_window.hip)
+    "(anonymous namespace)::sketch_tiles_kernel": "sketch_tiles", "sketch_tiles_kernel": "sketch_tiles",
 }
 
 

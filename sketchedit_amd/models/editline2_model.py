@@ -167,6 +167,11 @@ class EditLine2Model(torch.nn.Module):
         """Undo / redo: exchanges each frame's rectangle with its slot, in place."""
         self.engine().window_swap_u8(frames, origins, window_hw, slots)
 
+    def sketch_tiles_u8(self, sketch_u8, tile):
+        """Where a full-size sketch is drawn: the (Hi,Wi) uint8 plane ON THE DEVICE -> (ceil(Hi / tile),
+        ceil(Wi / tile), 5) int32 there, [count, y0, x0, y1, x1] per tile (Engine.sketch_tiles_u8)."""
+        return self.engine().sketch_tiles_u8(sketch_u8, tile)
+
     def forward(self, data, mode, low_latency=None):
         """`low_latency` (no reference counterpart): None = by this call's own size, True / False = pinned.  Results are
         bit-identical across batch compositions only WITHIN one mode (include/sketchedit_hip.h), so callers whose batch size

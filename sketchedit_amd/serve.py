@@ -158,6 +158,72 @@ def window_saved_bytes(hs, ws):
     return 0 if hs < 16 or ws < 16 else hs * ((3 * ws + 15) // 16 * 16)
 
 
+def _windows_intersect(a, b):
+    return a[0] < b[0] + b[2] and b[0] < a[0] + a[2] and a[1] < b[1] + b[3] and b[1] < a[1] + a[3]
+
+
+def merge_regions(boxes, frame_hw, margin=0.5, bucket=64, min_side=256):
+    """The merge rule of a region edit (pure host arithmetic): every box (y0, x0, y1, x1) gets its
+    choose_window; while any two windows intersect, the lowest-indexed intersecting pair -- with the components kept sorted by
+    their boxes, so the result is a function of the SET of boxes, not of the order they came in -- becomes one component with
+    the union box and a new window.  Each merge leaves one component fewer, so the loop ends.  -> [(box, window)], windows
+    pairwise disjoint, sorted by window (y0, x0)."""
+    comps = sorted({tuple(int(v) for v in b) for b in boxes})
+    while True:
+        wins = [choose_window(b, frame_hw, margin, bucket, min_side) for b in comps]
+        pair = next(((i, j) for i in range(len(comps)) for j in range(i + 1, len(comps)) if _windows_intersect(wins[i], wins[j])), None)
+        if pair is None:
+            return sorted(zip(comps, wins), key=lambda r: r[1][:2])
+        a, b = comps[pair[0]], comps[pair[1]]
+        union = (min(a[0], b[0]), min(a[1], b[1]), max(a[2], b[2]), max(a[3], b[3]))
+        comps = sorted(set(c for k, c in enumerate(comps) if k not in pair) | {union})
+
+
+def split_regions(tiles, tile, frame_hw, margin=0.5, bucket=64, min_side=256):
+    """The windows a sketch of several separate strokes is edited through (pure host arithmetic).  `tiles`: the
+    (ceil(Hi / tile), ceil(Wi / tile), 5) grid of [count, y0, x0, y1, x1] records of the sketch (se_sketch_tiles_u8).  The
+    8-connected components of the non-empty tiles are the strokes, each with the union of its tiles' tight boxes; they get
+    windows by merge_regions.  -> [(box, window)] sorted by window (y0, x0), [] for an all-empty grid.  One component gives
+    exactly choose_window(sketch_bbox(sketch)): a single-blob sketch gets the window `EditSession.edit` gives it.
+    `tile` and the three policy arguments are a policy, not a measurement: choose_window's defaults, and a tile fine enough
+    that strokes a window apart are never one component."""
+    tiles = np.asarray(tiles)
+    nty, ntx = -(-int(frame_hw[0]) // int(tile)), -(-int(frame_hw[1]) // int(tile))
+    if tiles.shape != (nty, ntx, 5):
+        raise ValueError("tiles is %r, a %dx%d frame at tile %d has (%d, %d, 5)" % (tiles.shape, frame_hw[1], frame_hw[0], tile, nty, ntx))
+    full = tiles[..., 0] > 0
+    label = np.full((nty, ntx), -1, np.int64)
+    boxes = []
+    for ty, tx in zip(*np.nonzero(full)):                 # raster order: a component is numbered by its first tile
+        if label[ty, tx] >= 0:
+            continue
+        label[ty, tx] = len(boxes)
+        stack, members = [(ty, tx)], []
+        while stack:
+            y, x = stack.pop()
+            members.append(tiles[y, x, 1:])
+            for v in range(max(y - 1, 0), min(y + 2, nty)):
+                for u in range(max(x - 1, 0), min(x + 2, ntx)):
+                    if full[v, u] and label[v, u] < 0:
+                        label[v, u] = len(boxes)
+                        stack.append((v, u))
+        m = np.stack(members)
+        boxes.append((int(m[:, 0].min()), int(m[:, 1].min()), int(m[:, 2].max()), int(m[:, 3].max())))
+    return merge_regions(boxes, frame_hw, margin, bucket, min_side)
+
+
+def _by_size(windows):
+    """{(h, w): [indices into `windows`]}, sizes in the order they first appear"""
+    out = {}
+    for i, w in enumerate(windows):
+        out.setdefault((w[2], w[3]), []).append(i)
+    return out
+
+
+class _Regions(tuple):
+    """the windows of a region edit's journal entry (its slots are a list in the same order)"""
+
+
 class _ModelBackend:
     """The device side of an editing session: an EditLine2Model's engine and torch for the copies.  (A seam: the host
     logic of EditSession and of the window batcher is tested against a scripted stand-in.)"""
@@ -209,6 +275,14 @@ class _ModelBackend:
     def swap(self, frames, origins, window_hw, slots):
         """rectangles <-> slots: undo, and redo"""
         self.model.window_swap_u8(frames, origins, window_hw, slots)
+
+    def tiles(self, sketch, tile):
+        """the tile records of a full-size sketch that is on the device, on the host (a synchronisation)"""
+        return self.model.sketch_tiles_u8(sketch, tile).cpu().numpy()
+
+    def window_of(self, plane, y0, x0, h, w):
+        """a window of a plane that is on the device, as a contiguous plane there"""
+        return plane[y0:y0 + h, x0:x0 + w].contiguous()
 
     def select(self, t, idx):
         """rows `idx` of a batch result as a contiguous batch"""
@@ -315,10 +389,32 @@ class EditSession:
         if slot is None:
             self._undo.clear()                   # an older entry could no longer restore a state the frame was in
             return False
-        self._undo.append((tuple(window), slot, window_saved_bytes(window[2], window[3])))
+        self._push((tuple(window), slot, window_saved_bytes(window[2], window[3])))
+        return True
+
+    def _push(self, entry):
+        self._undo.append(entry)
         while len(self._undo) > self.history or (self.history_bytes is not None and self._bytes_used() > self.history_bytes):
             self._undo.pop(0)
+
+    def _record_regions(self, windows, slots):
+        """`_record` for a region edit: ONE entry with all its windows and their slots (None: not journalled)"""
+        self._redo.clear()
+        if slots is None:
+            self._undo.clear()
+            return False
+        self._push((_Regions(windows), list(slots), sum(window_saved_bytes(w[2], w[3]) for w in windows)))
         return True
+
+    def _exchange_regions(self, src, dst):
+        """the region entry `src` ends in <-> the frame, one swap call per window size (the journal's calls take rectangles of
+        one size); -> what undo / redo return for it: lists in edit_regions' shape"""
+        wins, slots, _ = src[-1]
+        for hw, idx in _by_size(wins).items():
+            self.backend.swap([self._frame] * len(idx), [wins[i][:2] for i in idx], hw, [slots[i] for i in idx])
+        dst.append(src.pop())
+        info = dict(windows=list(wins), undo_depth=len(self._undo), redo_depth=len(self._redo))
+        return [self.backend.crop(self._frame, *w) for w in wins], [(w[1], w[0]) for w in wins], info
 
     def _exchanged(self, src, dst):
         """the entry `src` ends in was exchanged with the frame: it moves to `dst`; -> what undo / redo return"""
@@ -331,6 +427,8 @@ class EditSession:
         with self._lock:
             if not src:
                 raise IndexError("nothing to " + what)
+            if isinstance(src[-1][0], _Regions):
+                return self._exchange_regions(src, dst)
             (y0, x0, h, w), slot, _ = src[-1]
             self.backend.swap([self._frame], [(y0, x0)], (h, w), [slot])
             return self._exchanged(src, dst)
@@ -338,7 +436,8 @@ class EditSession:
     def undo(self):
         """Takes the last edit back: the frame is byte-identical to what it was before it.  -> (patch, (x0, y0), info) in
         `edit`'s shape: the window after the exchange (the only download), info = dict(window, undo_depth, redo_depth).
-        IndexError when there is nothing to undo."""
+        A region edit (edit_regions) is one step: all its windows are exchanged and the three are lists in ITS shape, with
+        info = dict(windows, undo_depth, redo_depth).  IndexError when there is nothing to undo."""
         return self._exchange(self._undo, self._redo, "undo")
 
     def redo(self):
@@ -359,12 +458,16 @@ class EditSession:
         with self._lock:
             return self._bytes_used()
 
-    def _request(self, sketch):
-        """-> (sketch array, bbox) of a full-size sketch; refusals of the window path"""
+    def _full_size(self, sketch):
         sk = _sketch_array(sketch)
         if sk.shape != self.frame_hw:
             raise ValueError("sketch is %dx%d, the frame %dx%d: a sketch of another size takes the whole-frame path "
                              "(serve.process_image)" % (sk.shape[1], sk.shape[0], self.frame_hw[1], self.frame_hw[0]))
+        return sk
+
+    def _request(self, sketch):
+        """-> (sketch array, bbox) of a full-size sketch; refusals of the window path"""
+        sk = self._full_size(sketch)
         bbox = sketch_bbox(sk)
         if bbox is None:
             raise ValueError("empty sketch: nothing to edit")
@@ -453,6 +556,69 @@ class EditSession:
         if undoable is not None:
             info["undoable"] = undoable
         return patch, (x0, y0), info
+
+    def edit_regions(self, sketch, low_latency=None, max_side=None, tile=32, margin=0.5, bucket=64, min_side=256):
+        """One edit of SEPARATE strokes through separate windows, so that two small strokes in opposite
+        corners cost two small windows, not the frame.  `sketch` as in `edit`.  The full sketch goes up once; the library's
+        tile pass (se_sketch_tiles_u8; `tile` in 16 / 32 / 64) finds where it is drawn and its grid comes down -- the one
+        synchronisation before the forwards; split_regions(grid, tile, frame, margin, bucket, min_side) gives pairwise
+        disjoint windows w_k.  The frame after the call is DEFINED as the frame after
+            edit(sketch, window=w_k, max_grow=0, low_latency=..., max_side=...)   for every k, in any order,
+        byte for byte, all in one pinned execution mode: each region's sketch is the full sketch cropped to its window (on
+        the device), a neighbouring stroke's pixels inside it included.  The windows are grouped by size and each group is
+        ONE committing call with B = the group's size on this frame (the locked entry with the session's plane for every
+        request if there is one, else the scaled entry if `max_side` is set).  No window grows; the border counts are
+        reported so that a caller can edit again.  One sketch blob gives the window `edit` starts from.
+        -> (patches, origins, info): the windows after the paste (the downloads), their (x0, y0), and info = dict(windows,
+        boxes, counts=[[top, bottom, left, right], ...], groups=the number of forwards), plus locked / work (one working
+        size per window) / undoable where `edit` reports them.  An empty sketch or one of another size raises ValueError.
+        With history on the call is ONE undo step: every window's rectangle is saved in front of its group's commit and the
+        entry holds all slots; if they exceed `history_bytes` together the edit commits unjournalled and clears the history."""
+        sk = self._full_size(sketch)
+        scaled = max_side is not None
+        be = self.backend
+        with self._lock:
+            lk = self._lock_plane
+            plane = be.upload(sk)
+            regions = split_regions(be.tiles(plane, tile), tile, self.frame_hw, margin, bucket, min_side)
+            if not regions:
+                raise ValueError("empty sketch: nothing to edit")
+            wins = [w for _, w in regions]
+            journal = self.history > 0 and (self.history_bytes is None or
+                                            sum(window_saved_bytes(w[2], w[3]) for w in wins) <= self.history_bytes)
+            counts, slots, works = [None] * len(wins), [None] * len(wins), [None] * len(wins)
+            groups = _by_size(wins)
+            try:
+                for (h, w), idx in groups.items():
+                    frames, origins = [self._frame] * len(idx), [wins[i][:2] for i in idx]
+                    crops = [be.window_of(plane, *wins[i]) for i in idx]
+                    if journal:
+                        for i, slot in zip(idx, be.save(frames, origins, (h, w))):
+                            slots[i] = slot
+                    work = choose_working_size((h, w), max_side) if scaled else None
+                    if lk is not None:
+                        _, _, hits = be.run_locked(frames, origins, crops, [lk] * len(idx), (h, w), work, True, low_latency)
+                    elif scaled:
+                        _, _, hits = be.run_scaled(frames, origins, crops, (h, w), work, True, low_latency)
+                    else:
+                        _, _, hits = be.run(frames, origins, crops, h, w, True, low_latency)
+                    for i, c in zip(idx, hits):
+                        counts[i], works[i] = list(c), work
+            except Exception:
+                if any(c is not None for c in counts):    # some groups are in the frame: no entry restores a state it was in
+                    self._undo.clear()
+                    self._redo.clear()
+                raise
+            undoable = self._record_regions(wins, slots if journal else None) if self.history > 0 else None
+            patches = [be.crop(self._frame, *w) for w in wins]
+        info = dict(windows=wins, boxes=[b for b, _ in regions], counts=counts, groups=len(groups))
+        if lk is not None:
+            info["locked"] = True
+        if scaled:
+            info["work"] = works
+        if undoable is not None:
+            info["undoable"] = undoable
+        return patches, [(w[1], w[0]) for w in wins], info
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""
@@ -738,6 +904,8 @@ class BatchingServer:
                 if not stacks[i][0]:
                     group[i][3]["err"] = IndexError("nothing to " + r["op"])
                     outs[i] = False
+                elif isinstance(stacks[i][0][-1][0], _Regions):      # a region edit's entry: the session's own exchange
+                    outs[i] = s._exchange_regions(*stacks[i])
                 else:
                     by_size.setdefault(stacks[i][0][-1][0][2:], []).append(i)
             for hw, idx in by_size.items():

@@ -48,6 +48,17 @@ and (c) big_edit_unlocked / (d) big_edit_locked: the same two at --window-scaled
 left half of the window locked); plus se_profile_report's window_* kernel times and bytes of one (b) and one (d) request.
 
     python tools/serve_probe.py --window-lock [--reps N] [--out FILE]
+
+--regions: region edits, same protocol.  A 1921x1081 frame and a sketch of two 40-pixel strokes near opposite
+corners, whose single window is the floored frame:
+  (a) edit_one_window: EditSession.edit(max_grow=0): one forward at 1080x1920 (the leg that is compared with the parent
+                       commit's build, run with --regions-parent there: only this leg, no region call),
+  (b) edit_regions:    EditSession.edit_regions: the tile pass, then ONE forward with B = 2 on two 256x256 windows,
+  (c) tiles_device / tiles_host: the tiles step alone -- the sketch's upload, se_sketch_tiles_u8 and the grid's download --
+                       against serve.sketch_bbox plus a vectorised numpy tile pass on the host;
+plus se_profile_report's per-kernel times of one (b) request.
+
+    python tools/serve_probe.py --regions [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -307,6 +318,64 @@ def window_lock_leg(model, reps, parent=False, max_side=640):
     return out
 
 
+def host_tiles(sk, tile):
+    """the tile records of serve.split_regions from a host array, vectorised numpy (what a host-only policy would run)"""
+    import numpy as np
+    Hi, Wi = sk.shape
+    nty, ntx = -(-Hi // tile), -(-Wi // tile)
+    p = np.zeros((nty * tile, ntx * tile), bool)
+    p[:Hi, :Wi] = sk > 0
+    b = p.reshape(nty, tile, ntx, tile)
+    n = b.sum((1, 3), dtype=np.int32)
+    rows, cols = b.any(3), b.any(1)                            # (nty, tile, ntx), (nty, ntx, tile)
+    oy, ox = (np.arange(nty) * tile)[:, None], (np.arange(ntx) * tile)[None, :]
+    rec = np.stack([n, oy + rows.argmax(1), ox + cols.argmax(2), oy + tile - rows[:, ::-1].argmax(1), ox + tile - cols[:, :, ::-1].argmax(2)], -1)
+    return np.where(n[..., None] > 0, rec, 0).astype(np.int32)
+
+
+def regions_leg(model, reps, parent=False, tile=32):
+    """(a) - (c) of the module docstring; parent=True: leg (a) only, with the calls a build without region edits has"""
+    import numpy as np
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    sk = np.zeros((h, w), np.uint8)
+    sk[30:70, 30:70] = ((rng.rand(40, 40) < 0.2) * 255).astype(np.uint8)
+    sk[1000:1040, 1850:1890] = ((rng.rand(40, 40) < 0.2) * 255).astype(np.uint8)
+    sk[30, 30] = sk[69, 69] = sk[1000, 1850] = sk[1039, 1889] = 255
+    win = serve.choose_window(serve.sketch_bbox(sk), (h, w))
+    assert win == (0, 0, 1080, 1920), win
+    s1 = serve.EditSession(model, frame)
+    legs = dict(edit_one_window=lambda: s1.edit(sk, max_grow=0, low_latency=True))
+    out = dict(tool="serve_probe --regions" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               one_window=list(win))
+    if not parent:
+        s2 = serve.EditSession(model, frame)
+        be = s2.backend
+
+        def tiles_device():
+            return be.tiles(be.upload(sk), tile)
+
+        def tiles_host():
+            return serve.sketch_bbox(sk), host_tiles(sk, tile)
+        assert np.array_equal(tiles_device(), tiles_host()[1])
+        legs.update(edit_regions=lambda: s2.edit_regions(sk, low_latency=True, tile=tile), tiles_device=tiles_device, tiles_host=tiles_host)
+    out["ms"] = rounds_of(legs, reps)
+    if not parent:
+        info = s2.edit_regions(sk, low_latency=True, tile=tile)[2]
+        eng = model.engine()
+        eng.profile(True)
+        s2.edit_regions(sk, low_latency=True, tile=tile)
+        rep = eng.profile_report()
+        eng.profile(False)
+        kernels = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        out.update(tile=tile, windows=[list(v) for v in info["windows"]], groups=info["groups"], counts=info["counts"],
+                   speedup_one_window_over_regions=round(out["ms"]["edit_one_window"]["median"] / out["ms"]["edit_regions"]["median"], 2),
+                   regions_kernels_profiled=kernels, regions_kernels_total_ms=round(sum(k["ms"] for k in kernels.values()), 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -317,6 +386,8 @@ def main():
     ap.add_argument("--window-history-parent", action="store_true", help="the history=0 legs of --window-history only")
     ap.add_argument("--window-lock", action="store_true", help="locked regions (see the module docstring)")
     ap.add_argument("--window-lock-parent", action="store_true", help="the unlocked legs of --window-lock only")
+    ap.add_argument("--regions", action="store_true", help="region edits (see the module docstring)")
+    ap.add_argument("--regions-parent", action="store_true", help="the single-window leg of --regions only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -325,8 +396,11 @@ def main():
     from sketchedit_amd import serve
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     model = make_model(tempfile.mkdtemp())
-    if args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent:
-        if args.window_lock or args.window_lock_parent:
+    if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
+            or args.regions or args.regions_parent):
+        if args.regions or args.regions_parent:
+            res = regions_leg(model, args.reps, parent=args.regions_parent)
+        elif args.window_lock or args.window_lock_parent:
             res = window_lock_leg(model, args.reps, parent=args.window_lock_parent)
         elif args.window_history or args.window_history_parent:
             res = window_history_leg(model, args.reps, parent=args.window_history_parent)
