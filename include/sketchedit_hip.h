@@ -308,6 +308,28 @@ size_t se_edit_window_locked_u8_workspace_bytes(se_ctx* ctx, int B, int hs, int 
  * names the argument, tiles_out untouched): Hi or Wi < 16, another tile, a NULL pointer, a misaligned tiles_out. */
 int se_sketch_tiles_u8(se_ctx* ctx, void* stream, const unsigned char* sketch_u8, int Hi, int Wi, int tile, int* tiles_out);
 
+/* ---- strokes as polylines ------------------------------------------------------------------------------------
+ * The windows' sketches rasterised on the device from a few segments, so that no full-size sketch plane exists anywhere.  A new
+ * operation with an integer-only definition, in quarter pixels: the centre of frame pixel (y, x) is P = (4 x + 2, 4 y + 2); a
+ * SEGMENT is five int32 [ax, ay, bx, by, r] with 0 <= ax, bx <= 4 Wi, 0 <= ay, by <= 4 Hi, 3 <= r <= 512 and Hi, Wi <= 8192.
+ * With d = B - A, e = P - A, f = P - B, t = e.d, dd = d.d, cr = ex dy - ey dx, the segment COVERS the pixel iff, in this order,
+ *     t <= 0: e.e <= r r        (a zero-length segment, a dot, always lands here)
+ *     t >= dd: f.f <= r r
+ *     otherwise: cr cr <= r r dd
+ * -- every intermediate fits int64 (cr cr <= 2^62).  sketch_out[b, y, x] = 255 if any segment first .. first + count - 1 of
+ * request b covers frame pixel (y0 + y, x0 + x), else 0.
+ * wins: a HOST array of B records of which only Hi, Wi, y0, x0 are used; segs: (N,5) int32 in DEVICE memory, 4-byte aligned;
+ * ranges: a HOST array (B,2) of [first, count] (ranges may overlap: requests share segments; count 0 gives zeros); sketch_out
+ * (B,hs,ws) uint8, device, ANY alignment, hs, ws >= 16 of any value -- slice b has the shape se_window.sketch_u8 takes.  EVERY
+ * byte of sketch_out is written on every call (it need not be zeroed) and none outside it; one launch, plain stores, no atomics,
+ * no workspace (SE_TEST_POISON has nothing to fill).  The limits on a segment's values are the caller's to keep, the segments
+ * being on the device: the kernel clamps what it loads to them, so other values give other pixels, never an access outside
+ * segs or sketch_out.  Refused before anything is enqueued (non-zero return, se_last_error names the argument, sketch_out
+ * untouched): a NULL pointer, B < 1, hs or ws < 16, a window outside its frame, Hi or Wi > 8192, N < 0 or a range outside
+ * [0, N], a misaligned segs, segs overlapping sketch_out. */
+int se_sketch_strokes_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int hs, int ws, const int* segs, int N,
+                         const int* ranges, unsigned char* sketch_out);
+
 /* Host only (no HIP call, no ctx): the coefficient table the resize uses for one axis.  Returns ksize, the taps per output
  * (-1: bad arguments); when bounds (2*out ints: first input index, tap count) and k (cap >= out*ksize ints, fixed point
  * with 22 fractional bits, rows zero padded to ksize) are given, fills them.  Lets a test compare the tables with Pillow's. */

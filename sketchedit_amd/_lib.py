@@ -41,6 +41,7 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
            "se_window_saved_bytes", "se_window_save_u8", "se_window_swap_u8",
            "se_inference_locked", "se_inference_u8_locked", "se_window_gather_lock_u8", "se_window_paste_locked_u8",
            "se_edit_window_locked_u8", "se_edit_window_locked_u8_workspace_bytes", "se_sketch_tiles_u8",
+           "se_sketch_strokes_u8",
            "se_pack_inputs", "se_column_reduce", "se_output_conv"]
 
 
@@ -212,6 +213,8 @@ def load_library():
         lib.se_edit_window_locked_u8_workspace_bytes.restype = sz
         lib.se_sketch_tiles_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
         lib.se_sketch_tiles_u8.restype = ci
+        lib.se_sketch_strokes_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, ci, vp, vp]
+        lib.se_sketch_strokes_u8.restype = ci
         lib.se_pack_inputs.argtypes = [vp, vp, ci, c_f, c_f, c_f, c_f, c_f, vp, vp, ci, ci, ci, ci, ci]
         lib.se_pack_inputs.restype = ci
         lib.se_column_reduce.argtypes = [vp, vp, c_f, c_f, vp, ci, ci, ci, ci, ci, ci]
@@ -910,6 +913,38 @@ class Engine:
             out = torch.empty((-(-Hi // tile), -(-Wi // tile), 5), dtype=torch.int32, device=sketch_u8.device)
         if self.lib.se_sketch_tiles_u8(self.h, self._stream(), _ptr(sketch_u8), Hi, Wi, tile, _ptr(out)):
             self._err("se_sketch_tiles_u8")
+        return out
+
+    # ---- strokes as polylines -----------------------------------------------------------------------------------
+    def sketch_strokes_u8(self, segs, frame_hws, origins, window_hw, ranges=None, out=None):
+        """se_sketch_strokes_u8: `segs` (N,5) int32 on the device, [ax, ay, bx, by, r] in quarter pixels of the frame ->
+        (B,hs,ws) uint8 on the device: the sketch of the (hs, ws) window at origins[i] = (y0, x0) of a frame of
+        frame_hws[i] = (Hi, Wi), 255 where a segment of ranges[i] = (first, count) (None: all N) covers the pixel's centre by
+        the integer rule of the header, 0 elsewhere.  Slice i is contiguous: what the window entries take as sketches[i].
+        `out`: a contiguous uint8 tensor of B hs ws elements to write into (every byte is written)."""
+        import torch
+        if not (isinstance(segs, torch.Tensor) and segs.is_cuda and segs.dtype == torch.int32 and segs.is_contiguous()
+                and segs.dim() == 2 and segs.shape[1] == 5):
+            raise SketchEditHipError("sketch_strokes_u8: segments are an (N,5) contiguous int32 CUDA(HIP) tensor")
+        hs, ws = (int(v) for v in window_hw)
+        B, N = len(origins), segs.shape[0]
+        if B < 1 or len(frame_hws) != B or (ranges is not None and len(ranges) != B):
+            raise SketchEditHipError("sketch_strokes_u8: one frame size, one origin (and one range) per request")
+        wins = (Window * B)()
+        for i, ((Hi, Wi), (y0, x0)) in enumerate(zip(frame_hws, origins)):
+            wins[i] = Window(None, None, int(Hi), int(Wi), int(y0), int(x0))
+        flat = [int(v) for r in (ranges if ranges is not None else [(0, N)] * B) for v in r]
+        if len(flat) != 2 * B:
+            raise SketchEditHipError("sketch_strokes_u8: a range is (first, count)")
+        rng = (ctypes.c_int * (2 * B))(*flat)
+        if out is None and hs > 0 and ws > 0:
+            out = torch.empty((B, hs, ws), dtype=torch.uint8, device=segs.device)
+        if out is not None:
+            _check_dev_u8(out)
+            if out.numel() != B * hs * ws:
+                raise SketchEditHipError("sketch_strokes_u8: out holds B hs ws bytes")
+        if self.lib.se_sketch_strokes_u8(self.h, self._stream(), wins, B, hs, ws, _ptr(segs), N, rng, _ptr(out)):
+            self._err("se_sketch_strokes_u8")
         return out
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):

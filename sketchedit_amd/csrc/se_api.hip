@@ -2257,6 +2257,46 @@ int se_sketch_tiles_u8(se_ctx* c, void* stream, const unsigned char* sketch_u8, 
   return 0;
 }
 
+// ---- strokes as polylines: the windows' sketches rasterised from segments ----------------------------
+// Every check on the host, then the records (with the ranges behind them, as the journal's slots travel) and ONE launch that
+// writes the caller's sketches directly: no workspace, nothing for SE_TEST_POISON to fill.
+int se_sketch_strokes_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, const int* segs, int N, const int* ranges,
+                         unsigned char* sketch_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (B < 1 || B > 32767) return fail(c, "bad B=%d (1 .. 32767 requests per call)", B);
+  if (hs < 16 || ws < 16) return fail(c, "bad window hs=%d ws=%d (a window is at least 16 x 16 frame pixels)", hs, ws);
+  if (N < 0) return fail(c, "bad N=%d", N);
+  if (!wins || !segs || !ranges || !sketch_out) return fail(c, "null pointer argument: wins / segs / ranges / sketch_out");
+  if (!aligned_to(segs, 4)) return fail(c, "segs must be 4-byte aligned");
+  std::vector<se_window> recs(2 * (size_t)B, se_window{nullptr, nullptr, 0, 0, 0, 0});
+  long nseg_sum = 0;
+  for (int i = 0; i < B; ++i) {
+    const se_window& w = wins[i];
+    if (w.Hi < 1 || w.Wi < 1 || w.Hi > 8192 || w.Wi > 8192)
+      return fail(c, "wins[%d]: bad frame size Hi=%d Wi=%d (1 .. 8192: the range the rule's 64-bit arithmetic is stated for)", i, w.Hi, w.Wi);
+    if (w.y0 < 0 || (long long)w.y0 + hs > w.Hi)
+      return fail(c, "wins[%d].y0=%d: rows [%d, %lld) of the window lie outside the frame (Hi=%d)", i, w.y0, w.y0, (long long)w.y0 + hs, w.Hi);
+    if (w.x0 < 0 || (long long)w.x0 + ws > w.Wi)
+      return fail(c, "wins[%d].x0=%d: columns [%d, %lld) of the window lie outside the frame (Wi=%d)", i, w.x0, w.x0, (long long)w.x0 + ws, w.Wi);
+    const int first = ranges[2 * i], count = ranges[2 * i + 1];
+    if (first < 0 || count < 0 || (long long)first + count > N)
+      return fail(c, "ranges[%d] = [first %d, count %d] lies outside the %d segments", i, first, count, N);
+    recs[i].Hi = w.Hi; recs[i].Wi = w.Wi; recs[i].y0 = w.y0; recs[i].x0 = w.x0;
+    recs[B + i].Hi = first; recs[B + i].Wi = count;
+    nseg_sum += count;
+  }
+  const uintptr_t s0 = (uintptr_t)segs, s1 = s0 + (size_t)N * 5 * sizeof(int), o0 = (uintptr_t)sketch_out, o1 = o0 + (size_t)B * hs * ws;
+  if (s0 < o1 && o0 < s1) return fail(c, "segs overlaps sketch_out");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  const hipStream_t st = (hipStream_t)stream;
+  const se_window* d = win_put(c, st, recs.data(), 2 * B);
+  if (!d) return 1;
+  HIPCHK(c, launch_sketch_strokes(d, B, hs, ws, segs, nseg_sum, sketch_out, st));
+  return 0;
+}
+
 // ---- measurement support (bench.py): per-kernel HIP-event timing ---------------------------------
 int se_profile_enable(se_ctx* c, int on) {
   if (!c) return 1;

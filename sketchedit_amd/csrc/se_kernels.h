@@ -19,7 +19,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_ATT_PREP, PL_ATT_SCORE, PL_ATT_SOFTMAX, PL_ATT_BOXSUM, PL_ATT_PV, PL_LAYOUT,
                  PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_WINDOW_GATHER, PL_WINDOW_BORDER, PL_WINDOW_PASTE,
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
-                 PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_COUNT };
+                 PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -416,5 +416,11 @@ hipError_t launch_window_journal(const se_window* d_wins, int B, int hs, int ws,
 // (ceil(Hi / tile), ceil(Wi / tile), 5) int32 = [count of pixels > 0, y0, x0, y1, x1] (the tight half-open box in frame
 // coordinates; five zeros for an empty square).  Every record is written; no byte outside the plane is read.
 hipError_t launch_sketch_tiles(const unsigned char* plane, int Hi, int Wi, int tile, int* tiles_out, hipStream_t st);
+// strokes as polylines: segs (N,5) int32 [ax, ay, bx, by, r] in quarter pixels of the frame -> sketch_out (B,hs,ws)
+// uint8, any alignment: 255 where a segment of request b's range covers the pixel's centre, else 0.  d_wins = 2 B records, the
+// second B carrying the ranges (Hi = first, Wi = count).  Every byte of sketch_out is written, none outside it; any int32 in
+// segs is safe (clamped to the rule's limits).  nseg_sum = the ranges' counts added up (the profiler's byte estimate).
+hipError_t launch_sketch_strokes(const se_window* d_wins, int B, int hs, int ws, const int* segs, long nseg_sum, unsigned char* sketch_out,
+                                 hipStream_t st);
 
 }  // namespace se

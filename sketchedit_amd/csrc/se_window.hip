@@ -39,6 +39,13 @@
 //                [count, y0, x0, y1, x1] per square: the pixels > 0 in it and their tight half-open box in frame coordinates,
 //                five zeros for an empty square.  The plane's base and pitch have any alignment: a row's part of a square is
 //                read as gather reads a window row, so no byte outside the plane is read.
+//
+// Strokes as polylines: the windows' sketches need not come from a full-size plane at all.
+//
+//  sketch strokes: (N,5) int32 segments [ax, ay, bx, by, r] in quarter pixels of the frame -> the (hs, ws) sketch of each
+//                  request's window, 255 where a segment of the request's range covers the pixel's centre and 0 elsewhere, by
+//                  the integer rule of 6i.  wins holds 2 B records: wins[B + b].Hi / .Wi are request b's first segment and
+//                  its segment count.  Every byte of the output is written, by the paste's ownership rule; none outside it.
 #include "../../include/sketchedit_hip.h"
 #include "se_device.h"
 #include "se_kernels.h"
@@ -323,7 +330,95 @@ __global__ void __launch_bounds__(256) sketch_tiles_kernel(const unsigned char* 
   }
 }
 
+// One workgroup = one 64 x 16 pixel tile of one request's window; one lane = 4 consecutive pixels of one row.  The request's
+// segments are walked in chunks of 256, one per lane: a lane keeps its segment if the segment's box grown by r meets the box
+// of the tile's pixel centres, the kept ones are compacted into LDS (a ballot and a prefix count per wave, the waves' totals
+// through LDS) together with what the test needs of them, and every lane tests its pixels against those only.  A range of
+// any length is so many chunks; an empty one writes zeros.
+// What is loaded is clamped to the limits the rule is stated for (coordinates to [0, 4 * 8192], r to [0, 512]) -- a no-op on
+// valid segments -- so that every intermediate fits int64 whatever the buffer holds: |e|, |d| <= 2^15 + 62 per axis (a lane's
+// pixels may lie up to 3 columns / 15 rows past the window), hence |t|, |cr| < 2^31.01, cr^2 < 2^62.02, r^2 dd <= 2^49.
+// The store is window_paste's: a dword where all four bytes are the lane's and the address is aligned, single bytes otherwise.
+__global__ void __launch_bounds__(256) sketch_strokes_kernel(const se_window* __restrict__ wins, int B, int hs, int ws,
+                                                             const int* __restrict__ segs, unsigned char* __restrict__ out) {
+  constexpr int CHUNK = 256, LIM = 4 * 8192, RMAX = 512;
+  __shared__ int s_ax[CHUNK], s_ay[CHUNK], s_dx[CHUNK], s_dy[CHUNK], s_r2[CHUNK];
+  __shared__ long long s_dd[CHUNK], s_r2dd[CHUNK];
+  __shared__ int s_wave_n[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.z;
+  const se_window w = wins[b];
+  const int first = wins[B + b].Hi, count = wins[B + b].Wi;
+  const int tx0 = blockIdx.x * 64, ty0 = blockIdx.y * 16;                       // the tile, in window pixels
+  const int tx1 = min(tx0 + 64, ws), ty1 = min(ty0 + 16, hs);
+  // the box of the tile's pixel centres, in quarter pixels of the frame
+  const int cx0 = 4 * (w.x0 + tx0) + 2, cx1 = 4 * (w.x0 + tx1 - 1) + 2, cy0 = 4 * (w.y0 + ty0) + 2, cy1 = 4 * (w.y0 + ty1 - 1) + 2;
+  const int x = tx0 + 4 * (tid & 15), y = ty0 + (tid >> 4);
+  const int n = y < hs ? max(0, min(4, ws - x)) : 0;                           // the lane's pixels inside the window
+  const long long px = 4 * (w.x0 + x) + 2, py = 4 * (w.y0 + y) + 2;
+  unsigned cov = 0;                                                             // bit p: pixel x + p is covered
+  for (int base = 0; base < count; base += CHUNK) {                            // (block-uniform: every lane meets the barriers)
+    bool keep = false;
+    int ax = 0, ay = 0, bx = 0, by = 0, r = 0;
+    if (base + tid < count) {
+      const int* s = segs + 5 * ((size_t)first + base + tid);
+      ax = min(max(s[0], 0), LIM); ay = min(max(s[1], 0), LIM);
+      bx = min(max(s[2], 0), LIM); by = min(max(s[3], 0), LIM);
+      r = min(max(s[4], 0), RMAX);
+      keep = min(ax, bx) - r <= cx1 && max(ax, bx) + r >= cx0 && min(ay, by) - r <= cy1 && max(ay, by) + r >= cy0;
+    }
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) s_wave_n[wave] = __popcll(m);
+    __syncthreads();                              // the totals are there, and the previous chunk's tests are over
+    int at = __popcll(m & ((1ull << lane) - 1ull)), kept = 0;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      at += v < wave ? s_wave_n[v] : 0;
+      kept += s_wave_n[v];
+    }
+    if (keep) {
+      const int dx = bx - ax, dy = by - ay;
+      const long long dd = (long long)dx * dx + (long long)dy * dy;
+      s_ax[at] = ax; s_ay[at] = ay; s_dx[at] = dx; s_dy[at] = dy; s_r2[at] = r * r;
+      s_dd[at] = dd; s_r2dd[at] = (long long)(r * r) * dd;
+    }
+    __syncthreads();
+    if (n > 0) {
+      for (int i = 0; i < kept && cov != 15u; ++i) {
+        const long long dx = s_dx[i], dy = s_dy[i], r2 = s_r2[i], dd = s_dd[i], r2dd = s_r2dd[i];
+        const long long ex0 = px - s_ax[i], ey = py - s_ay[i], fy = ey - dy;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const long long ex = ex0 + 4 * p, fx = ex - dx;
+          const long long t = ex * dx + ey * dy, cr = ex * dy - ey * dx;
+          const bool c = t <= 0 ? ex * ex + ey * ey <= r2 : t >= dd ? fx * fx + fy * fy <= r2 : cr * cr <= r2dd;
+          cov |= c ? 1u << p : 0u;
+        }
+      }
+    }
+  }
+  if (n > 0) {
+    unsigned char* a = out + ((size_t)b * hs + y) * ws + x;
+    const unsigned v = ((cov & 1u) ? 0xffu : 0u) | ((cov & 2u) ? 0xff00u : 0u) | ((cov & 4u) ? 0xff0000u : 0u) | ((cov & 8u) ? 0xff000000u : 0u);
+    if (n == 4 && ((uintptr_t)a & 3) == 0) {
+      *(unsigned*)a = v;
+    } else {
+      for (int e = 0; e < n; ++e) a[e] = (unsigned char)((v >> (8 * e)) & 255u);
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t launch_sketch_strokes(const se_window* d_wins, int B, int hs, int ws, const int* segs, long nseg_sum, unsigned char* sketch_out,
+                                 hipStream_t st) {
+  const dim3 grid((unsigned)((ws + 63) / 64), (unsigned)((hs + 15) / 16), (unsigned)B);
+  // bytes: every tile reads its request's segments (an upper bound: the L2 serves most of it), the sketches written once
+  set_launch_cost(0.0, (double)B * hs * ws + 20.0 * (double)nseg_sum * grid.x * grid.y, "sketch_strokes");
+  set_launch_grid((long)grid.x * grid.y * grid.z);
+  ProfScope ps_(st, PL_SKETCH_STROKES);
+  hipLaunchKernelGGL(sketch_strokes_kernel, grid, dim3(256), 0, st, d_wins, B, hs, ws, segs, sketch_out);
+  return hipGetLastError();
+}
 
 hipError_t launch_sketch_tiles(const unsigned char* plane, int Hi, int Wi, int tile, int* tiles_out, hipStream_t st) {
   const int ntx = (Wi + tile - 1) / tile;

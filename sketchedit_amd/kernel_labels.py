@@ -40,6 +40,8 @@ KERNEL_LABELS = {
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",
     # region edits: the tile pass over a full-size sketch (se_window.hip)
     "(anonymous namespace)::sketch_tiles_kernel": "sketch_tiles", "sketch_tiles_kernel": "sketch_tiles",
+    # strokes as polylines: the rasteriser of the windows' sketches (se_window.hip)
+    "(anonymous namespace)::sketch_strokes_kernel": "sketch_strokes", "sketch_strokes_kernel": "sketch_strokes",
 }
 
 

@@ -172,6 +172,11 @@ class EditLine2Model(torch.nn.Module):
         ceil(Wi / tile), 5) int32 there, [count, y0, x0, y1, x1] per tile (Engine.sketch_tiles_u8)."""
         return self.engine().sketch_tiles_u8(sketch_u8, tile)
 
+    def sketch_strokes_u8(self, segs, frame_hws, origins, window_hw, ranges=None):
+        """The windows' sketches from segments: `segs` (N,5) int32 ON THE DEVICE -> (B,hs,ws) uint8 there, one
+        slice per window at origins[i] of a frame of frame_hws[i] (Engine.sketch_strokes_u8)."""
+        return self.engine().sketch_strokes_u8(segs, frame_hws, origins, window_hw, ranges=ranges)
+
     def forward(self, data, mode, low_latency=None):
         """`low_latency` (no reference counterpart): None = by this call's own size, True / False = pinned.  Results are
         bit-identical across batch compositions only WITHIN one mode (include/sketchedit_hip.h), so callers whose batch size

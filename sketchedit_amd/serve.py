@@ -212,6 +212,59 @@ def split_regions(tiles, tile, frame_hw, margin=0.5, bucket=64, min_side=256):
     return merge_regions(boxes, frame_hw, margin, bucket, min_side)
 
 
+STROKE_Q = 4                # quarter pixels: the unit of a segment's coordinates and radius
+STROKE_R_MIN, STROKE_R_MAX = 3, 512
+STROKE_MAX_EXTENT = 8192
+
+
+def stroke_segments(strokes, frame_hw):
+    """Strokes as a drawing front end has them -> the segments the rasteriser takes (pure host arithmetic).
+    `strokes`: [(points, width_px)], points = [(x, y)] floats in pixels of the frame (pixel (y, x) covers [x, x + 1) x [y, y + 1):
+    its centre is (x + 0.5, y + 0.5)), width_px the brush's diameter.  Coordinates are rounded to quarter pixels (half up) and
+    clamped to the frame's rectangle [0, 4 Wi] x [0, 4 Hi]; r = round(2 width_px), the radius in quarter pixels, must lie in
+    [3, 512] -- a brush of 1.5 to 256 pixels.  n points give n - 1 segments, one point a dot (a segment of length zero).
+    -> (segs, ranges): an (N,5) int32 array of [ax, ay, bx, by, r] and each stroke's (first, count).  ValueError for no
+    strokes, a stroke without points, a value that is not finite, a width outside the range, a frame over 8192 on a side."""
+    Hi, Wi = int(frame_hw[0]), int(frame_hw[1])
+    if not (1 <= Hi <= STROKE_MAX_EXTENT and 1 <= Wi <= STROKE_MAX_EXTENT):
+        raise ValueError("strokes are rasterised on frames of at most %d pixels on a side (got %dx%d)" % (STROKE_MAX_EXTENT, Wi, Hi))
+    strokes = list(strokes)
+    if not strokes:
+        raise ValueError("no strokes: nothing to edit")
+    segs, ranges = [], []
+    for k, (points, width) in enumerate(strokes):
+        pts = np.asarray(points, np.float64)
+        if pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 1:
+            raise ValueError("stroke %d: points are a non-empty list of (x, y)" % k)
+        if not (np.isfinite(pts).all() and np.isfinite(width)):
+            raise ValueError("stroke %d: coordinates and width must be finite" % k)
+        r = int(np.floor(2.0 * float(width) + 0.5))
+        if not STROKE_R_MIN <= r <= STROKE_R_MAX:
+            raise ValueError("stroke %d: width %r gives a radius of %d quarter pixels, outside [%d, %d]" % (k, width, r, STROKE_R_MIN, STROKE_R_MAX))
+        q = np.floor(STROKE_Q * pts + 0.5)
+        qx = np.clip(q[:, 0], 0, STROKE_Q * Wi).astype(np.int64)
+        qy = np.clip(q[:, 1], 0, STROKE_Q * Hi).astype(np.int64)
+        ends = [(0, 0)] if len(pts) == 1 else [(i, i + 1) for i in range(len(pts) - 1)]
+        ranges.append((len(segs), len(ends)))
+        segs.extend([qx[i], qy[i], qx[j], qy[j], r] for i, j in ends)
+    return np.asarray(segs, np.int32).reshape(-1, 5), ranges
+
+
+def stroke_box(segs, frame_hw):
+    """The box of a stroke's segments (pure host arithmetic): (y0, x0, y1, x1), half open, in pixels -- per axis
+    [ceil((min - r - 2) / 4), floor((max + r - 2) / 4) + 1) over the segments' end points, clipped to the frame.  A pixel a
+    segment covers has its centre 4 x + 2 within r of the segment, so the box holds every covered pixel; with r >= 3 and the
+    end points inside the frame's rectangle it is never empty (a centre lies within 2 of every point of [0, 4 W])."""
+    s = np.asarray(segs, np.int64).reshape(-1, 5)
+    if s.shape[0] < 1:
+        raise ValueError("a stroke has at least one segment")
+    Hi, Wi = int(frame_hw[0]), int(frame_hw[1])
+    r = s[:, 4]
+    lo = lambda a, b: int(-((-(np.minimum(a, b) - r - 2).min()) // STROKE_Q))
+    hi = lambda a, b: int((np.maximum(a, b) + r - 2).max() // STROKE_Q) + 1
+    return (max(lo(s[:, 1], s[:, 3]), 0), max(lo(s[:, 0], s[:, 2]), 0), min(hi(s[:, 1], s[:, 3]), Hi), min(hi(s[:, 0], s[:, 2]), Wi))
+
+
 def _by_size(windows):
     """{(h, w): [indices into `windows`]}, sizes in the order they first appear"""
     out = {}
@@ -275,6 +328,12 @@ class _ModelBackend:
     def swap(self, frames, origins, window_hw, slots):
         """rectangles <-> slots: undo, and redo"""
         self.model.window_swap_u8(frames, origins, window_hw, slots)
+
+    def strokes(self, segs, frame_hw, windows):
+        """the (h, w) sketches of `windows` (all of one size) of a frame of `frame_hw`, rasterised there from `segs` -- the
+        (N,5) int32 segments, on the device -- in ONE call; -> one contiguous plane per window"""
+        out = self.model.sketch_strokes_u8(segs, [frame_hw] * len(windows), [w[:2] for w in windows], windows[0][2:])
+        return [out[i] for i in range(len(windows))]
 
     def tiles(self, sketch, tile):
         """the tile records of a full-size sketch that is on the device, on the host (a synchronisation)"""
@@ -575,42 +634,49 @@ class EditSession:
         With history on the call is ONE undo step: every window's rectangle is saved in front of its group's commit and the
         entry holds all slots; if they exceed `history_bytes` together the edit commits unjournalled and clears the history."""
         sk = self._full_size(sketch)
-        scaled = max_side is not None
         be = self.backend
         with self._lock:
-            lk = self._lock_plane
             plane = be.upload(sk)
             regions = split_regions(be.tiles(plane, tile), tile, self.frame_hw, margin, bucket, min_side)
             if not regions:
                 raise ValueError("empty sketch: nothing to edit")
-            wins = [w for _, w in regions]
-            journal = self.history > 0 and (self.history_bytes is None or
-                                            sum(window_saved_bytes(w[2], w[3]) for w in wins) <= self.history_bytes)
-            counts, slots, works = [None] * len(wins), [None] * len(wins), [None] * len(wins)
-            groups = _by_size(wins)
-            try:
-                for (h, w), idx in groups.items():
-                    frames, origins = [self._frame] * len(idx), [wins[i][:2] for i in idx]
-                    crops = [be.window_of(plane, *wins[i]) for i in idx]
-                    if journal:
-                        for i, slot in zip(idx, be.save(frames, origins, (h, w))):
-                            slots[i] = slot
-                    work = choose_working_size((h, w), max_side) if scaled else None
-                    if lk is not None:
-                        _, _, hits = be.run_locked(frames, origins, crops, [lk] * len(idx), (h, w), work, True, low_latency)
-                    elif scaled:
-                        _, _, hits = be.run_scaled(frames, origins, crops, (h, w), work, True, low_latency)
-                    else:
-                        _, _, hits = be.run(frames, origins, crops, h, w, True, low_latency)
-                    for i, c in zip(idx, hits):
-                        counts[i], works[i] = list(c), work
-            except Exception:
-                if any(c is not None for c in counts):    # some groups are in the frame: no entry restores a state it was in
-                    self._undo.clear()
-                    self._redo.clear()
-                raise
-            undoable = self._record_regions(wins, slots if journal else None) if self.history > 0 else None
-            patches = [be.crop(self._frame, *w) for w in wins]
+            return self._edit_windows(regions, lambda wins: [be.window_of(plane, *w) for w in wins], low_latency, max_side)
+
+    def _edit_windows(self, regions, crops_of, low_latency, max_side):
+        """The committing part of edit_regions and edit_strokes, with the session's lock held: `regions` = [(box, window)],
+        windows pairwise disjoint; crops_of(windows of one size) -> their sketches on the device.  Groups the windows by size;
+        per group the crops, the journal's saves and ONE committing call.  -> what the two return."""
+        be = self.backend
+        scaled = max_side is not None
+        lk = self._lock_plane
+        wins = [w for _, w in regions]
+        journal = self.history > 0 and (self.history_bytes is None or
+                                        sum(window_saved_bytes(w[2], w[3]) for w in wins) <= self.history_bytes)
+        counts, slots, works = [None] * len(wins), [None] * len(wins), [None] * len(wins)
+        groups = _by_size(wins)
+        try:
+            for (h, w), idx in groups.items():
+                frames, origins = [self._frame] * len(idx), [wins[i][:2] for i in idx]
+                crops = crops_of([wins[i] for i in idx])
+                if journal:
+                    for i, slot in zip(idx, be.save(frames, origins, (h, w))):
+                        slots[i] = slot
+                work = choose_working_size((h, w), max_side) if scaled else None
+                if lk is not None:
+                    _, _, hits = be.run_locked(frames, origins, crops, [lk] * len(idx), (h, w), work, True, low_latency)
+                elif scaled:
+                    _, _, hits = be.run_scaled(frames, origins, crops, (h, w), work, True, low_latency)
+                else:
+                    _, _, hits = be.run(frames, origins, crops, h, w, True, low_latency)
+                for i, c in zip(idx, hits):
+                    counts[i], works[i] = list(c), work
+        except Exception:
+            if any(c is not None for c in counts):    # some groups are in the frame: no entry restores a state it was in
+                self._undo.clear()
+                self._redo.clear()
+            raise
+        undoable = self._record_regions(wins, slots if journal else None) if self.history > 0 else None
+        patches = [be.crop(self._frame, *w) for w in wins]
         info = dict(windows=wins, boxes=[b for b, _ in regions], counts=counts, groups=len(groups))
         if lk is not None:
             info["locked"] = True
@@ -619,6 +685,24 @@ class EditSession:
         if undoable is not None:
             info["undoable"] = undoable
         return patches, [(w[1], w[0]) for w in wins], info
+
+    def edit_strokes(self, strokes, low_latency=None, max_side=None, margin=0.5, bucket=64, min_side=256):
+        """One edit of strokes given as POLYLINES: `strokes` = [(points, width_px)] as stroke_segments takes
+        them.  No full-size sketch exists anywhere: the host knows each stroke's box in closed form (stroke_box), merge_regions
+        turns the boxes into pairwise disjoint windows exactly as edit_regions' are made, and the windows' sketches are
+        rasterised on the device from the segments (se_sketch_strokes_u8, one call per window size) -- the segments are the
+        only upload and the border counts the only download in front of the forwards.  A window's sketch holds every segment
+        of the call that reaches into it, a neighbouring stroke's too.  The frame after the call is DEFINED as the frame after
+            edit(S, window=w_k, max_grow=0, low_latency=..., max_side=...)   for every k, in any order,
+        byte for byte in one pinned execution mode, S being the full-size 0 / 255 sketch the integer rule of 6i gives for
+        the segments.  Everything else -- groups, lock, working size, history (ONE undo step), the return value -- is
+        edit_regions'.  ValueError for no strokes or one stroke_segments refuses."""
+        segs, ranges = stroke_segments(strokes, self.frame_hw)
+        regions = merge_regions([stroke_box(segs[f:f + n], self.frame_hw) for f, n in ranges], self.frame_hw, margin, bucket, min_side)
+        be = self.backend
+        with self._lock:
+            dsegs = be.upload(segs)
+            return self._edit_windows(regions, lambda wins: be.strokes(dsegs, self.frame_hw, wins), low_latency, max_side)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""

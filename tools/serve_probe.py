@@ -59,6 +59,17 @@ corners, whose single window is the floored frame:
 plus se_profile_report's per-kernel times of one (b) request.
 
     python tools/serve_probe.py --regions [--reps N] [--out FILE]
+
+--strokes: strokes as polylines, same protocol.  The frame of --regions and its two 40-pixel strokes stated as
+polylines (a 3-pixel brush, 20 points each, the same boxes and so the same two 256x256 windows):
+  (a) edit_regions: EditSession.edit_regions of the full-size sketch the rule draws for the polylines (the leg that is compared
+                    with the parent commit's build, run with --strokes-parent there: only this leg, no stroke call),
+  (b) edit_strokes: EditSession.edit_strokes of the polylines: the segments' upload, ONE rasteriser call, ONE forward with B = 2,
+  (c) raster_device / raster_host: the two windows' sketches alone -- the segments' upload and se_sketch_strokes_u8 (with a
+                    synchronisation, which the edit does not need) -- against the numpy rule on the strokes' boxes;
+plus se_profile_report's per-kernel times of one (b) request.
+
+    python tools/serve_probe.py --strokes [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -376,6 +387,92 @@ def regions_leg(model, reps, parent=False, tile=32):
     return out
 
 
+def probe_strokes():
+    """the two strokes of --regions as polylines: zigzags inside [31.5, 68.5]^2 and [1001.5, 1038.5] x [1851.5, 1888.5] at a
+    3-pixel brush, so that their boxes are the 40-pixel boxes of --regions"""
+    out = []
+    for y0, x0 in ((30, 30), (1000, 1850)):
+        pts = [(x0 + 1.5 + 37.0 * (i % 2 if i % 4 < 2 else 1 - i % 2) * 0.6 + 37.0 * 0.4 * i / 19.0, y0 + 1.5 + 37.0 * i / 19.0) for i in range(20)]
+        pts[0], pts[-1] = (x0 + 1.5, y0 + 1.5), (x0 + 38.5, y0 + 38.5)
+        out.append((pts, 3.0))
+    return out
+
+
+def host_segments(strokes):
+    """serve.stroke_segments without the checks and the clamp (the probe's strokes need neither): also runs on a build without it"""
+    import numpy as np
+    segs = []
+    for pts, width in strokes:
+        q = np.floor(4.0 * np.asarray(pts, np.float64) + 0.5).astype(np.int64)
+        r = int(np.floor(2.0 * width + 0.5))
+        segs += [[q[i, 0], q[i, 1], q[i + 1, 0], q[i + 1, 1], r] for i in range(len(q) - 1)]
+    return np.asarray(segs, np.int32)
+
+
+def host_raster(segs, hw):
+    """the rule of DESIGN.md 6i in numpy int64, each segment over its own box only (what a host-only front end would run)"""
+    import numpy as np
+    sk = np.zeros(hw, np.uint8)
+    for ax, ay, bx, by, r in np.asarray(segs, np.int64):
+        y0, y1 = max((min(ay, by) - r - 2 + 3) // 4, 0), min((max(ay, by) + r - 2) // 4 + 1, hw[0])
+        x0, x1 = max((min(ax, bx) - r - 2 + 3) // 4, 0), min((max(ax, bx) + r - 2) // 4 + 1, hw[1])
+        px, py = (4 * np.arange(x0, x1) + 2)[None, :], (4 * np.arange(y0, y1) + 2)[:, None]
+        dx, dy, ex, ey = bx - ax, by - ay, px - ax, py - ay
+        t, dd, cr = ex * dx + ey * dy, dx * dx + dy * dy, ex * dy - ey * dx
+        hit = np.where(t <= 0, ex * ex + ey * ey <= r * r, np.where(t >= dd, (ex - dx) ** 2 + (ey - dy) ** 2 <= r * r, cr * cr <= r * r * dd))
+        sk[y0:y1, x0:x1][hit] = 255
+    return sk
+
+
+def strokes_leg(model, reps, parent=False, tile=32):
+    """(a) - (c) of the module docstring; parent=True: leg (a) only, with the calls a build without stroke edits has"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    strokes = probe_strokes()
+    segs = host_segments(strokes)
+    sk = host_raster(segs, (h, w))
+    s1 = serve.EditSession(model, frame)
+    legs = dict(edit_regions=lambda: s1.edit_regions(sk, low_latency=True, tile=tile))
+    out = dict(tool="serve_probe --strokes" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               segments=int(len(segs)), sketch_pixels=int((sk > 0).sum()))
+    if not parent:
+        assert np.array_equal(serve.stroke_segments(strokes, (h, w))[0], segs)
+        s2 = serve.EditSession(model, frame)
+        be = s2.backend
+        wins = s1.edit_regions(sk, low_latency=True, tile=tile)[2]["windows"]
+
+        def raster_device():
+            crops = be.strokes(be.upload(segs), (h, w), wins)
+            torch.cuda.synchronize()
+            return crops
+        whole = be.strokes(be.upload(segs), (h, w), [(0, 0, h, w)])[0].cpu().numpy()
+        assert np.array_equal(whole, sk)                     # the device's whole-frame raster is the numpy rule's
+        legs.update(edit_strokes=lambda: s2.edit_strokes(strokes, low_latency=True), raster_device=raster_device,
+                    raster_host=lambda: host_raster(segs, (h, w)))
+    out["ms"] = rounds_of(legs, reps)
+    info = s1.edit_regions(sk, low_latency=True, tile=tile)[2]
+    out.update(regions_windows=[list(v) for v in info["windows"]])
+    if not parent:
+        s3, s4 = serve.EditSession(model, frame), serve.EditSession(model, frame)
+        s3.edit_regions(sk, low_latency=True, tile=tile)
+        info = s4.edit_strokes(strokes, low_latency=True)[2]
+        eng = model.engine()
+        eng.profile(True)
+        s2.edit_strokes(strokes, low_latency=True)
+        rep = eng.profile_report()
+        eng.profile(False)
+        kernels = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        out.update(windows=[list(v) for v in info["windows"]], groups=info["groups"], counts=info["counts"],
+                   frames_identical=bool(np.array_equal(s3.frame(), s4.frame())),
+                   regions_minus_strokes_ms=round(out["ms"]["edit_regions"]["median"] - out["ms"]["edit_strokes"]["median"], 3),
+                   strokes_kernels_profiled=kernels, strokes_kernels_total_ms=round(sum(k["ms"] for k in kernels.values()), 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -388,6 +485,8 @@ def main():
     ap.add_argument("--window-lock-parent", action="store_true", help="the unlocked legs of --window-lock only")
     ap.add_argument("--regions", action="store_true", help="region edits (see the module docstring)")
     ap.add_argument("--regions-parent", action="store_true", help="the single-window leg of --regions only")
+    ap.add_argument("--strokes", action="store_true", help="strokes as polylines (see the module docstring)")
+    ap.add_argument("--strokes-parent", action="store_true", help="the edit_regions leg of --strokes only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -397,8 +496,10 @@ def main():
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     model = make_model(tempfile.mkdtemp())
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
-            or args.regions or args.regions_parent):
-        if args.regions or args.regions_parent:
+            or args.regions or args.regions_parent or args.strokes or args.strokes_parent):
+        if args.strokes or args.strokes_parent:
+            res = strokes_leg(model, args.reps, parent=args.strokes_parent)
+        elif args.regions or args.regions_parent:
             res = regions_leg(model, args.reps, parent=args.regions_parent)
         elif args.window_lock or args.window_lock_parent:
             res = window_lock_leg(model, args.reps, parent=args.window_lock_parent)
