@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_png.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -43,6 +43,8 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
            "se_edit_window_locked_u8", "se_edit_window_locked_u8_workspace_bytes", "se_sketch_tiles_u8",
            "se_sketch_strokes_u8",
            "se_pack_inputs", "se_column_reduce", "se_output_conv"]
+# every symbol declared in include/sketchedit_png.h (the PNG entries of the editing sessions)
+PNG_SYMBOLS = ["se_png_bound", "se_png_encode_u8", "se_png_encode_u8_workspace_bytes"]
 
 
 class SketchEditHipError(RuntimeError):
@@ -73,7 +75,8 @@ def build_library(force=False, verbose=False, extra_flags=()):
     an exclusive file lock, so concurrent builders (ranks, test workers) do not write the same objects."""
     import fcntl
     from concurrent.futures import ThreadPoolExecutor
-    hdrs = [os.path.join(CSRC, "se_kernels.h"), os.path.join(CSRC, "se_device.h"), os.path.join(CSRC, "se_pack.h"), os.path.join(_HERE, "..", "include", "sketchedit_hip.h")]
+    hdrs = [os.path.join(CSRC, "se_kernels.h"), os.path.join(CSRC, "se_device.h"), os.path.join(CSRC, "se_pack.h"), os.path.join(_HERE, "..", "include", "sketchedit_hip.h"),
+            os.path.join(_HERE, "..", "include", "sketchedit_png.h")]
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
@@ -221,6 +224,12 @@ def load_library():
         lib.se_column_reduce.restype = ci
         lib.se_output_conv.argtypes = [vp, vp, c_f, c_f, c_f, ci, ci, ci, ci, ci, ctypes.POINTER(OutputConvIO), ci, ci, ci]
         lib.se_output_conv.restype = ci
+        lib.se_png_bound.argtypes = [ci, ci]
+        lib.se_png_bound.restype = sz
+        lib.se_png_encode_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, vp, sz, vp, vp, sz]
+        lib.se_png_encode_u8.restype = ci
+        lib.se_png_encode_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
+        lib.se_png_encode_u8_workspace_bytes.restype = sz
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -946,6 +955,38 @@ class Engine:
         if self.lib.se_sketch_strokes_u8(self.h, self._stream(), wins, B, hs, ws, _ptr(segs), N, rng, _ptr(out)):
             self._err("se_sketch_strokes_u8")
         return out
+
+    # ---- patches as PNG ------------------------------------------------------------------------------------------
+    @staticmethod
+    def png_bound(hs, ws):
+        """se_png_bound: the most bytes the zlib stream of an hs x ws rectangle can take; 0 for a side outside [16, 8192]
+        (host only)"""
+        return int(load_library().se_png_bound(int(hs), int(ws)))
+
+    def png_encode_u8(self, frames, origins, window_hw, out=None):
+        """se_png_encode_u8: the (hs, ws) rectangle at origins[i] = (y0, x0) of every frame (Hi,Wi,3) uint8 on the device -> the
+        zlib stream of its PNG (include/sketchedit_png.h; serve.png_from_zlib makes the file), encoded on the device.
+        -> (out (B, cap) uint8, sizes (B,) int64), both on the device: out[i, :sizes[i]] is image i's stream, and no byte
+        behind it is written.  `out`: a contiguous uint8 tensor of B rows of cap >= png_bound(hs, ws) bytes to write into."""
+        import torch
+        hs, ws = (int(v) for v in window_hw)
+        wins = self._windows(frames, origins)
+        B, dev = len(frames), frames[0].device
+        bound = self.png_bound(hs, ws)
+        if out is None:
+            out = torch.empty((B, max(bound, 1)), dtype=torch.uint8, device=dev)
+        _check_dev_u8(out)
+        if out.dim() != 2 or out.shape[0] != B:
+            raise SketchEditHipError("png_encode_u8: `out` is a (B, cap) uint8 tensor")
+        sizes = torch.empty((B,), dtype=torch.int64, device=dev)
+        need = self.lib.se_png_encode_u8_workspace_bytes(self.h, B, hs, ws)
+        if need == 0:
+            self._err("se_png_encode_u8_workspace_bytes")
+        ws_t = self._workspace_bytes(need)
+        if self.lib.se_png_encode_u8(self.h, self._stream(), wins, B, hs, ws, _ptr(out), out.shape[1], _ptr(sizes), _ptr(ws_t),
+                                     ws_t.numel()):
+            self._err("se_png_encode_u8")
+        return out, sizes
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):
         """Inference into ONE (B,4,H,W) buffer `out`: planes 0-2 composed, plane 3 the soft mask -- the unit the

@@ -7,6 +7,7 @@
 // and the plans restate the forward methods (editline_g.py:119-221, editline2_g.py:59-94,
 // editline2_model.py:128-133,338-370).
 #include "../../include/sketchedit_hip.h"
+#include "../../include/sketchedit_png.h"
 #include "se_kernels.h"
 #include "se_pack.h"
 
@@ -2294,6 +2295,85 @@ int se_sketch_strokes_u8(se_ctx* c, void* stream, const se_window* wins, int B, 
   const se_window* d = win_put(c, st, recs.data(), 2 * B);
   if (!d) return 1;
   HIPCHK(c, launch_sketch_strokes(d, B, hs, ws, segs, nseg_sum, sketch_out, st));
+  return 0;
+}
+
+// ---- the device PNG encoder (include/sketchedit_png.h): a window of a frame -> the zlib stream of its PNG --
+// Every check on the host, then the records and three launches.  The workspace is handed out by the main arena, block by block,
+// as a forward's activations are: SE_TEST_POISON fills each block on the stream before its producer is enqueued.
+size_t se_png_bound(int hs, int ws) {
+  if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) return 0;
+  const size_t row = 1 + 3 * (size_t)ws;
+  const int full = hs / 32, rest = hs % 32;
+  return 2 + (size_t)full * png_stripe_bound(32 * row) + (rest ? png_stripe_bound((size_t)rest * row) : 0) + 9;
+}
+
+namespace {
+
+struct PngLayout { size_t ftype, sizes, parts, slots; };      // bytes of the four blocks, each a multiple of 256
+PngLayout png_layout(int B, int hs, int ws) {
+  const size_t q = (size_t)B * png_stripes(hs);
+  return PngLayout{pad256((size_t)B * hs), pad256(q * 4), pad256(q * 8), pad256(q * png_slot_bytes(ws))};
+}
+
+}  // namespace
+
+size_t se_png_encode_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws) {
+  if (!c) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (B < 1 || B > 65535) { fail(c, "bad B=%d (1 .. 65535 images per call)", B); return 0; }
+  if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) { fail(c, "bad rectangle hs=%d ws=%d (sides are 16 .. 8192)", hs, ws); return 0; }
+  const PngLayout L = png_layout(B, hs, ws);
+  return L.ftype + L.sizes + L.parts + L.slots;
+}
+
+int se_png_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, unsigned char* out, size_t cap,
+                     unsigned long long* sizes_out, void* workspace, size_t workspace_bytes) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (B < 1 || B > 65535) return fail(c, "bad B=%d (1 .. 65535 images per call)", B);
+  if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) return fail(c, "bad rectangle hs=%d ws=%d (sides are 16 .. 8192)", hs, ws);
+  if (!wins) return fail(c, "null pointer argument: wins");
+  if (!out) return fail(c, "null pointer argument: out");
+  if (!sizes_out) return fail(c, "null pointer argument: sizes_out");
+  if (!workspace) return fail(c, "null pointer argument: workspace");
+  if (win_check_records(c, wins, B, hs, ws, false)) return 1;
+  const size_t bound = se_png_bound(hs, ws);
+  if (cap < bound) return fail(c, "cap=%zu is less than se_png_bound(%d, %d) = %zu", cap, hs, ws, bound);
+  if (cap > ((size_t)1 << 40) / (size_t)B) return fail(c, "cap=%zu: B cap is more than one call takes", cap);
+  const PngLayout L = png_layout(B, hs, ws);
+  const size_t need = L.ftype + L.sizes + L.parts + L.slots;
+  if (workspace_bytes < need) return fail(c, "workspace too small: %zu bytes, need %zu", workspace_bytes, need);
+  if (!aligned_to(workspace, 256)) return fail(c, "workspace must be 256-byte aligned");
+  if (!aligned_to(sizes_out, 8)) return fail(c, "sizes_out must be 8-byte aligned");
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)B * cap, w0 = (uintptr_t)workspace, w1 = w0 + need;
+  const uintptr_t z0 = (uintptr_t)sizes_out, z1 = z0 + (size_t)B * sizeof(unsigned long long);
+  for (int i = 0; i < B; ++i) {
+    const uintptr_t f0 = (uintptr_t)wins[i].frame_u8, f1 = f0 + (size_t)wins[i].Hi * wins[i].Wi * 3;
+    if (o0 < f1 && f0 < o1) return fail(c, "out overlaps the frame of wins[%d]", i);
+    if (z0 < f1 && f0 < z1) return fail(c, "sizes_out overlaps the frame of wins[%d]", i);
+    if (w0 < f1 && f0 < w1) return fail(c, "workspace overlaps the frame of wins[%d]", i);
+  }
+  if (o0 < w1 && w0 < o1) return fail(c, "out overlaps the workspace");
+  if (o0 < z1 && z0 < o1) return fail(c, "out overlaps sizes_out");
+  if (z0 < w1 && w0 < z1) return fail(c, "sizes_out overlaps the workspace");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  const hipStream_t st = (hipStream_t)stream;
+  c->arena.reset((char*)workspace, need, false);
+  c->arena2.reset(nullptr, 0, false);
+  void* blk[4];
+  const size_t bytes[4] = {L.ftype, L.sizes, L.parts, L.slots};
+  for (int i = 0; i < 4; ++i) {
+    blk[i] = c->arena.alloc(bytes[i] / 4);
+    if (!blk[i]) return fail(c, "workspace arena exhausted");
+    if (poison(c, blk[i], bytes[i], st)) return 1;
+  }
+  const se_window* d = win_put(c, st, wins, B);
+  if (!d) return 1;
+  HIPCHK(c, launch_png_rows(d, B, hs, ws, (unsigned char*)blk[0], st));
+  HIPCHK(c, launch_png_stripes(d, B, hs, ws, (const unsigned char*)blk[0], (unsigned*)blk[1], (unsigned*)blk[2], (unsigned char*)blk[3], st));
+  HIPCHK(c, launch_png_finish(B, hs, ws, (const unsigned*)blk[1], (const unsigned*)blk[2], (const unsigned char*)blk[3], out, cap, sizes_out, st));
   return 0;
 }
 

@@ -19,7 +19,8 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_ATT_PREP, PL_ATT_SCORE, PL_ATT_SOFTMAX, PL_ATT_BOXSUM, PL_ATT_PV, PL_LAYOUT,
                  PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_WINDOW_GATHER, PL_WINDOW_BORDER, PL_WINDOW_PASTE,
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
-                 PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_COUNT };
+                 PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
+                 PL_PNG_FINISH, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -422,5 +423,17 @@ hipError_t launch_sketch_tiles(const unsigned char* plane, int Hi, int Wi, int t
 // segs is safe (clamped to the rule's limits).  nseg_sum = the ranges' counts added up (the profiler's byte estimate).
 hipError_t launch_sketch_strokes(const se_window* d_wins, int B, int hs, int ws, const int* segs, long nseg_sum, unsigned char* sketch_out,
                                  hipStream_t st);
+// the device PNG encoder (include/sketchedit_png.h): the hs x ws rectangles of d_wins (B records) -> their zlib
+// streams.  rows: ftype (B,hs) uint8, each row's filter type.  stripes: one workgroup per stripe of 32 rows -> its deflate blocks
+// in its slot of png_slot_bytes(ws) bytes (16-byte aligned), its size in sizes (B,S) and its Adler parts in parts (B,S,2), S =
+// png_stripes(hs).  finish: the streams, concatenated, at out + b cap (any alignment) and their lengths in sizes_out (B).
+int png_stripes(int hs);
+size_t png_stripe_bound(size_t n);
+size_t png_slot_bytes(int ws);
+hipError_t launch_png_rows(const se_window* d_wins, int B, int hs, int ws, unsigned char* ftype, hipStream_t st);
+hipError_t launch_png_stripes(const se_window* d_wins, int B, int hs, int ws, const unsigned char* ftype, unsigned* sizes, unsigned* parts,
+                              unsigned char* slots, hipStream_t st);
+hipError_t launch_png_finish(int B, int hs, int ws, const unsigned* sizes, const unsigned* parts, const unsigned char* slots, unsigned char* out,
+                             size_t cap, unsigned long long* sizes_out, hipStream_t st);
 
 }  // namespace se

@@ -107,7 +107,8 @@ const char* prof_label_name(int l) {
                                     "colreduce", "att_prep", "att_score", "att_softmax", "att_boxsum", "att_pv", "layout",
                                     "att_stream_stats", "att_stream_out", "resize_h", "resize_v", "window_gather", "window_border",
                                     "window_paste", "window_resample_h", "window_paste_v", "window_save", "window_swap", "window_lock_gather",
-                                    "window_paste_locked", "window_paste_v_locked", "sketch_tiles", "sketch_strokes"};
+                                    "window_paste_locked", "window_paste_v_locked", "sketch_tiles", "sketch_strokes", "png_rows", "png_stripes",
+                                    "png_finish"};
   return (l >= 0 && l < PL_COUNT) ? n[l] : "?";
 }
 

@@ -42,6 +42,10 @@ KERNEL_LABELS = {
     "(anonymous namespace)::sketch_tiles_kernel": "sketch_tiles", "sketch_tiles_kernel": "sketch_tiles",
     # strokes as polylines: the rasteriser of the windows' sketches (se_window.hip)
     "(anonymous namespace)::sketch_strokes_kernel": "sketch_strokes", "sketch_strokes_kernel": "sketch_strokes",
+    # the device PNG encoder of the editing sessions (se_png.hip)
+    "(anonymous namespace)::png_rows_kernel": "png_rows", "(anonymous namespace)::png_stripe_kernel": "png_stripes",
+    "(anonymous namespace)::png_finish_kernel": "png_finish",
+    "png_rows_kernel": "png_rows", "png_stripe_kernel": "png_stripes", "png_finish_kernel": "png_finish",
 }
 
 

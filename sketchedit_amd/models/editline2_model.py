@@ -177,6 +177,11 @@ class EditLine2Model(torch.nn.Module):
         slice per window at origins[i] of a frame of frame_hws[i] (Engine.sketch_strokes_u8)."""
         return self.engine().sketch_strokes_u8(segs, frame_hws, origins, window_hw, ranges=ranges)
 
+    def png_encode_u8(self, frames, origins, window_hw):
+        """Patches as PNG: the (hs, ws) rectangle at origins[i] of every resident frame -> the zlib stream of its
+        PNG, encoded ON THE DEVICE; -> (out (B, cap) uint8, sizes (B,) int64) there (Engine.png_encode_u8)."""
+        return self.engine().png_encode_u8(frames, origins, window_hw)
+
     def forward(self, data, mode, low_latency=None):
         """`low_latency` (no reference counterpart): None = by this call's own size, True / False = pinned.  Results are
         bit-identical across batch compositions only WITHIN one mode (include/sketchedit_hip.h), so callers whose batch size

@@ -265,6 +265,23 @@ def stroke_box(segs, frame_hw):
     return (max(lo(s[:, 1], s[:, 3]), 0), max(lo(s[:, 0], s[:, 2]), 0), min(hi(s[:, 1], s[:, 3]), Hi), min(hi(s[:, 0], s[:, 2]), Wi))
 
 
+def png_from_zlib(stream, h, w):
+    """The PNG file around a zlib stream of filtered 8-bit RGB rows: signature, IHDR, ONE IDAT holding
+    `stream` as it is, IEND -- the chunk framing and its CRCs are the host's part of a patch that was encoded on the device."""
+    import struct
+    from .png_worker import _SIG, _chunk
+    return _SIG + _chunk(b"IHDR", struct.pack(">IIBBBBB", int(w), int(h), 8, 2, 0, 0, 0)) + _chunk(b"IDAT", bytes(stream)) + _chunk(b"IEND", b"")
+
+
+PNG_SIDE_MIN, PNG_SIDE_MAX = 16, 8192       # the sides of a rectangle the device encoder takes (include/sketchedit_png.h)
+
+
+def _check_encode(encode):
+    if encode not in (None, "png"):
+        raise ValueError("encode is None (raw (h,w,3) arrays) or 'png' (got %r)" % (encode,))
+    return encode
+
+
 def _by_size(windows):
     """{(h, w): [indices into `windows`]}, sizes in the order they first appear"""
     out = {}
@@ -349,6 +366,16 @@ class _ModelBackend:
 
     def crop(self, frame, y0, x0, h, w):
         return frame[y0:y0 + h, x0:x0 + w].contiguous().cpu().numpy()
+
+    def crop_png(self, frames, windows):
+        """the windows (y0, x0, h, w) of `frames` as PNG files, encoded on the device: one encoder call per
+        window size; the streams' sizes come down first (the synchronisation), then exactly that many bytes of each"""
+        out = [None] * len(windows)
+        for (h, w), idx in _by_size(windows).items():
+            buf, sizes = self.model.png_encode_u8([frames[i] for i in idx], [windows[i][:2] for i in idx], (h, w))
+            for k, (i, n) in enumerate(zip(idx, sizes.cpu().tolist())):
+                out[i] = png_from_zlib(buf[k, :n].cpu().numpy().tobytes(), h, w)
+        return out
 
     def download(self, frame):
         return frame.cpu().numpy()
@@ -552,7 +579,7 @@ class EditSession:
             if nxt != window:
                 return nxt, margin
 
-    def edit(self, sketch, window=None, max_grow=2, low_latency=None, max_side=None):
+    def edit(self, sketch, window=None, max_grow=2, low_latency=None, max_side=None, encode=None):
         """One edit.  `sketch`: the FULL-SIZE sketch (PIL 'L' / 2-D uint8 array, the frame's size).  The window is
         choose_window of the sketch's box, or `window` = (y0, x0, h, w) as given (then it never grows).  The forward runs on
         the window without committing; if its mask reaches an edge of the window (border counts, a side on the frame's own
@@ -569,7 +596,11 @@ class EditSession:
         With history on, the window that is finally committed is journalled (one save in front of its paste) and info
         gains undoable.  With a lock plane (set_lock) info gains locked = True (a session without one reports what it
         always did: read it as info.get("locked", False)) -- every run of the edit, committed or not, at either scale, used
-        the plane, and the grow loop saw a mask that is 0 on locked pixels."""
+        the plane, and the grow loop saw a mask that is 0 on locked pixels.
+        `encode` (None: everything above): "png" returns `patch` as the bytes of a PNG file of the same window,
+        encoded on the device -- what comes down is the compressed stream, not the pixels; the frame, the journal and info
+        are what they are without it."""
+        _check_encode(encode)
         sk, bbox = self._request(sketch)
         margin = 0.5
         fixed = window is not None
@@ -606,7 +637,7 @@ class EditSession:
             elif not commit:
                 be.paste([self._frame], [(y0, x0)], rgb, m8)
             undoable = self._record(win, slot) if self.history > 0 else None
-            patch = be.crop(self._frame, y0, x0, h, w)
+            patch = be.crop(self._frame, y0, x0, h, w) if encode is None else be.crop_png([self._frame], [(y0, x0, h, w)])[0]
         info = dict(window=win, counts=list(counts[0]), reruns=reruns, margin=margin)
         if lk is not None:
             info["locked"] = True
@@ -616,7 +647,7 @@ class EditSession:
             info["undoable"] = undoable
         return patch, (x0, y0), info
 
-    def edit_regions(self, sketch, low_latency=None, max_side=None, tile=32, margin=0.5, bucket=64, min_side=256):
+    def edit_regions(self, sketch, low_latency=None, max_side=None, tile=32, margin=0.5, bucket=64, min_side=256, encode=None):
         """One edit of SEPARATE strokes through separate windows, so that two small strokes in opposite
         corners cost two small windows, not the frame.  `sketch` as in `edit`.  The full sketch goes up once; the library's
         tile pass (se_sketch_tiles_u8; `tile` in 16 / 32 / 64) finds where it is drawn and its grid comes down -- the one
@@ -632,7 +663,9 @@ class EditSession:
         boxes, counts=[[top, bottom, left, right], ...], groups=the number of forwards), plus locked / work (one working
         size per window) / undoable where `edit` reports them.  An empty sketch or one of another size raises ValueError.
         With history on the call is ONE undo step: every window's rectangle is saved in front of its group's commit and the
-        entry holds all slots; if they exceed `history_bytes` together the edit commits unjournalled and clears the history."""
+        entry holds all slots; if they exceed `history_bytes` together the edit commits unjournalled and clears the history.
+        `encode` as in `edit`: "png" returns the patches as PNG files, encoded on the device (one backend call for all)."""
+        _check_encode(encode)
         sk = self._full_size(sketch)
         be = self.backend
         with self._lock:
@@ -640,9 +673,9 @@ class EditSession:
             regions = split_regions(be.tiles(plane, tile), tile, self.frame_hw, margin, bucket, min_side)
             if not regions:
                 raise ValueError("empty sketch: nothing to edit")
-            return self._edit_windows(regions, lambda wins: [be.window_of(plane, *w) for w in wins], low_latency, max_side)
+            return self._edit_windows(regions, lambda wins: [be.window_of(plane, *w) for w in wins], low_latency, max_side, encode)
 
-    def _edit_windows(self, regions, crops_of, low_latency, max_side):
+    def _edit_windows(self, regions, crops_of, low_latency, max_side, encode=None):
         """The committing part of edit_regions and edit_strokes, with the session's lock held: `regions` = [(box, window)],
         windows pairwise disjoint; crops_of(windows of one size) -> their sketches on the device.  Groups the windows by size;
         per group the crops, the journal's saves and ONE committing call.  -> what the two return."""
@@ -676,7 +709,7 @@ class EditSession:
                 self._redo.clear()
             raise
         undoable = self._record_regions(wins, slots if journal else None) if self.history > 0 else None
-        patches = [be.crop(self._frame, *w) for w in wins]
+        patches = [be.crop(self._frame, *w) for w in wins] if encode is None else be.crop_png([self._frame] * len(wins), wins)
         info = dict(windows=wins, boxes=[b for b, _ in regions], counts=counts, groups=len(groups))
         if lk is not None:
             info["locked"] = True
@@ -686,7 +719,7 @@ class EditSession:
             info["undoable"] = undoable
         return patches, [(w[1], w[0]) for w in wins], info
 
-    def edit_strokes(self, strokes, low_latency=None, max_side=None, margin=0.5, bucket=64, min_side=256):
+    def edit_strokes(self, strokes, low_latency=None, max_side=None, margin=0.5, bucket=64, min_side=256, encode=None):
         """One edit of strokes given as POLYLINES: `strokes` = [(points, width_px)] as stroke_segments takes
         them.  No full-size sketch exists anywhere: the host knows each stroke's box in closed form (stroke_box), merge_regions
         turns the boxes into pairwise disjoint windows exactly as edit_regions' are made, and the windows' sketches are
@@ -696,18 +729,30 @@ class EditSession:
             edit(S, window=w_k, max_grow=0, low_latency=..., max_side=...)   for every k, in any order,
         byte for byte in one pinned execution mode, S being the full-size 0 / 255 sketch the integer rule of 6i gives for
         the segments.  Everything else -- groups, lock, working size, history (ONE undo step), the return value -- is
-        edit_regions'.  ValueError for no strokes or one stroke_segments refuses."""
+        edit_regions', `encode` too.  ValueError for no strokes or one stroke_segments refuses."""
+        _check_encode(encode)
         segs, ranges = stroke_segments(strokes, self.frame_hw)
         regions = merge_regions([stroke_box(segs[f:f + n], self.frame_hw) for f, n in ranges], self.frame_hw, margin, bucket, min_side)
         be = self.backend
         with self._lock:
             dsegs = be.upload(segs)
-            return self._edit_windows(regions, lambda wins: be.strokes(dsegs, self.frame_hw, wins), low_latency, max_side)
+            return self._edit_windows(regions, lambda wins: be.strokes(dsegs, self.frame_hw, wins), low_latency, max_side, encode)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""
         with self._lock:
             return self.backend.download(self._frame)
+
+    def frame_png(self, rect=None):
+        """The frame, or its rectangle `rect` = (y0, x0, h, w), as the bytes of a PNG file encoded on the device (DESIGN.md
+        6j): only the compressed stream comes down.  The sides lie in [16, 8192] and the rectangle inside the frame."""
+        Hi, Wi = self.frame_hw
+        y0, x0, h, w = (0, 0, Hi, Wi) if rect is None else (int(v) for v in rect)
+        if not (PNG_SIDE_MIN <= h <= PNG_SIDE_MAX and PNG_SIDE_MIN <= w <= PNG_SIDE_MAX) or y0 < 0 or x0 < 0 or y0 + h > Hi or x0 + w > Wi:
+            raise ValueError("rectangle %r: sides are %d .. %d and the rectangle lies inside the %dx%d frame"
+                             % ((y0, x0, h, w), PNG_SIDE_MIN, PNG_SIDE_MAX, Wi, Hi))
+        with self._lock:
+            return self.backend.crop_png([self._frame], [(y0, x0, h, w)])[0]
 
 
 def create_models_for_gpus(opt, gpu_ids=None):

@@ -70,6 +70,17 @@ polylines (a 3-pixel brush, 20 points each, the same boxes and so the same two 2
 plus se_profile_report's per-kernel times of one (b) request.
 
     python tools/serve_probe.py --strokes [--reps N] [--out FILE]
+
+--png: patches as PNG, encoded on the device, same protocol.  A 1921x1081 frame of smooth content with a little
+noise (a flat or a noise frame would flatter one encoder or the other), one edit through a fixed 512x512 window per request:
+  (a) edit_then_host_png: EditSession.edit, then png_worker.png_bytes_fast of the patch on the host (the leg that is compared
+                          with the parent commit's build, run with --png-parent there: only this leg, no encoder call),
+  (b) edit_png:           EditSession.edit(encode="png"),
+  (c) encode_device / encode_host: the encoders alone -- se_png_encode_u8 of the window with the download of its stream, against
+                          the download of the window's pixels and png_bytes_fast of them;
+plus the bytes each request downloads, both files' sizes, and se_profile_report's per-kernel times of one (b) request.
+
+    python tools/serve_probe.py --png [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -473,6 +484,51 @@ def strokes_leg(model, reps, parent=False, tile=32):
     return out
 
 
+def png_leg(model, reps, parent=False, side=512):
+    """(a) - (c) of the module docstring; parent=True: leg (a) only, with the calls a build without the encoder has"""
+    import io
+    import numpy as np
+    from PIL import Image
+    from sketchedit_amd import png_worker, serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = np.stack([96 + 64 * np.sin(xx / 97.0) + 48 * np.cos(yy / 61.0), 128 + 90 * np.sin((xx + yy) / 143.0),
+                     110 + 70 * np.cos(xx / 53.0) * np.sin(yy / 77.0)], axis=2)
+    frame = np.clip(base + rng.randint(-2, 3, (h, w, 3)), 0, 255).astype(np.uint8)
+    win = (283, 705, side, side)
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    s1 = serve.EditSession(model, frame)
+    edit = lambda s, **kw: s.edit(sk, window=win, max_grow=0, low_latency=True, **kw)      # noqa: E731
+    legs = dict(edit_then_host_png=lambda: png_worker.png_bytes_fast(edit(s1)[0]))
+    out = dict(tool="serve_probe --png" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               window=list(win), raw_bytes_downloaded=side * side * 3)
+    if not parent:
+        s2 = serve.EditSession(model, frame)
+        be = s2.backend
+        legs.update(edit_png=lambda: edit(s2, encode="png"), encode_device=lambda: be.crop_png([s2._frame], [win]),
+                    encode_host=lambda: png_worker.png_bytes_fast(be.crop(s2._frame, *win)))
+    out["ms"] = rounds_of(legs, reps)
+    patch = edit(s1)[0]
+    out.update(host_png_bytes=len(png_worker.png_bytes_fast(patch)))
+    if not parent:
+        s3, s4 = serve.EditSession(model, frame), serve.EditSession(model, frame)
+        raw, png = edit(s3)[0], edit(s4, encode="png")[0]
+        eng = model.engine()
+        eng.profile(True)
+        edit(s2, encode="png")
+        rep = eng.profile_report()
+        eng.profile(False)
+        kernels = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"] if k["kernel"].startswith("png_")}
+        framing = len(serve.png_from_zlib(b"", side, side))
+        out.update(device_png_bytes=len(png), png_bytes_downloaded=len(png) - framing, png_kernels_profiled=kernels,
+                   decodes_to_the_raw_patch=bool(np.array_equal(np.asarray(Image.open(io.BytesIO(png))), raw)),
+                   frames_identical=bool(np.array_equal(s3.frame(), s4.frame())),
+                   host_minus_device_request_ms=round(out["ms"]["edit_then_host_png"]["median"] - out["ms"]["edit_png"]["median"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -487,6 +543,8 @@ def main():
     ap.add_argument("--regions-parent", action="store_true", help="the single-window leg of --regions only")
     ap.add_argument("--strokes", action="store_true", help="strokes as polylines (see the module docstring)")
     ap.add_argument("--strokes-parent", action="store_true", help="the edit_regions leg of --strokes only")
+    ap.add_argument("--png", action="store_true", help="patches as PNG, encoded on the device (see the module docstring)")
+    ap.add_argument("--png-parent", action="store_true", help="the edit + host encoder leg of --png only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -496,8 +554,10 @@ def main():
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     model = make_model(tempfile.mkdtemp())
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
-            or args.regions or args.regions_parent or args.strokes or args.strokes_parent):
-        if args.strokes or args.strokes_parent:
+            or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent):
+        if args.png or args.png_parent:
+            res = png_leg(model, args.reps, parent=args.png_parent)
+        elif args.strokes or args.strokes_parent:
             res = strokes_leg(model, args.reps, parent=args.strokes_parent)
         elif args.regions or args.regions_parent:
             res = regions_leg(model, args.reps, parent=args.regions_parent)
