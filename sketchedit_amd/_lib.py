@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_png.hip", "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -45,6 +45,8 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
            "se_pack_inputs", "se_column_reduce", "se_output_conv"]
 # every symbol declared in include/sketchedit_png.h (the PNG entries of the editing sessions)
 PNG_SYMBOLS = ["se_png_bound", "se_png_encode_u8", "se_png_encode_u8_workspace_bytes"]
+# every symbol declared in include/sketchedit_jpg.h (the JPEG entries of the editing sessions)
+JPG_SYMBOLS = ["se_jpg_bound", "se_jpg_encode_u8", "se_jpg_encode_u8_workspace_bytes"]
 
 
 class SketchEditHipError(RuntimeError):
@@ -76,7 +78,7 @@ def build_library(force=False, verbose=False, extra_flags=()):
     import fcntl
     from concurrent.futures import ThreadPoolExecutor
     hdrs = [os.path.join(CSRC, "se_kernels.h"), os.path.join(CSRC, "se_device.h"), os.path.join(CSRC, "se_pack.h"), os.path.join(_HERE, "..", "include", "sketchedit_hip.h"),
-            os.path.join(_HERE, "..", "include", "sketchedit_png.h")]
+            os.path.join(_HERE, "..", "include", "sketchedit_png.h"), os.path.join(_HERE, "..", "include", "sketchedit_jpg.h")]
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
@@ -230,6 +232,12 @@ def load_library():
         lib.se_png_encode_u8.restype = ci
         lib.se_png_encode_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
         lib.se_png_encode_u8_workspace_bytes.restype = sz
+        lib.se_jpg_bound.argtypes = [ci, ci]
+        lib.se_jpg_bound.restype = sz
+        lib.se_jpg_encode_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, vp, sz, vp, vp, sz]
+        lib.se_jpg_encode_u8.restype = ci
+        lib.se_jpg_encode_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
+        lib.se_jpg_encode_u8_workspace_bytes.restype = sz
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -986,6 +994,39 @@ class Engine:
         if self.lib.se_png_encode_u8(self.h, self._stream(), wins, B, hs, ws, _ptr(out), out.shape[1], _ptr(sizes), _ptr(ws_t),
                                      ws_t.numel()):
             self._err("se_png_encode_u8")
+        return out, sizes
+
+    # ---- patches as JPEG -----------------------------------------------------------------------------------------
+    @staticmethod
+    def jpg_bound(hs, ws):
+        """se_jpg_bound: the most bytes the entropy-coded segment of an hs x ws rectangle can take; 0 for a side outside
+        [16, 8192] (host only)"""
+        return int(load_library().se_jpg_bound(int(hs), int(ws)))
+
+    def jpg_encode_u8(self, frames, origins, window_hw, quality=90, out=None):
+        """se_jpg_encode_u8: the (hs, ws) rectangle at origins[i] = (y0, x0) of every frame (Hi,Wi,3) uint8 on the device -> the
+        entropy-coded segment of its baseline JPEG at `quality` 1 .. 100 (include/sketchedit_jpg.h; serve.jpg_from_scan makes
+        the file), encoded on the device.  -> (out (B, cap) uint8, sizes (B,) int64), both on the device: out[i, :sizes[i]] is
+        image i's segment, and no byte behind it is written.  `out`: a contiguous uint8 tensor of B rows of cap >=
+        jpg_bound(hs, ws) bytes to write into."""
+        import torch
+        hs, ws = (int(v) for v in window_hw)
+        wins = self._windows(frames, origins)
+        B, dev = len(frames), frames[0].device
+        bound = self.jpg_bound(hs, ws)
+        if out is None:
+            out = torch.empty((B, max(bound, 1)), dtype=torch.uint8, device=dev)
+        _check_dev_u8(out)
+        if out.dim() != 2 or out.shape[0] != B:
+            raise SketchEditHipError("jpg_encode_u8: `out` is a (B, cap) uint8 tensor")
+        sizes = torch.empty((B,), dtype=torch.int64, device=dev)
+        need = self.lib.se_jpg_encode_u8_workspace_bytes(self.h, B, hs, ws)
+        if need == 0:
+            self._err("se_jpg_encode_u8_workspace_bytes")
+        ws_t = self._workspace_bytes(need)
+        if self.lib.se_jpg_encode_u8(self.h, self._stream(), wins, B, hs, ws, int(quality), _ptr(out), out.shape[1], _ptr(sizes),
+                                     _ptr(ws_t), ws_t.numel()):
+            self._err("se_jpg_encode_u8")
         return out, sizes
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):

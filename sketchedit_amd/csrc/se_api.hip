@@ -8,6 +8,7 @@
 // editline2_model.py:128-133,338-370).
 #include "../../include/sketchedit_hip.h"
 #include "../../include/sketchedit_png.h"
+#include "../../include/sketchedit_jpg.h"
 #include "se_kernels.h"
 #include "se_pack.h"
 
@@ -2374,6 +2375,84 @@ int se_png_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int 
   HIPCHK(c, launch_png_rows(d, B, hs, ws, (unsigned char*)blk[0], st));
   HIPCHK(c, launch_png_stripes(d, B, hs, ws, (const unsigned char*)blk[0], (unsigned*)blk[1], (unsigned*)blk[2], (unsigned char*)blk[3], st));
   HIPCHK(c, launch_png_finish(B, hs, ws, (const unsigned*)blk[1], (const unsigned*)blk[2], (const unsigned char*)blk[3], out, cap, sizes_out, st));
+  return 0;
+}
+
+// ---- the device JPEG encoder (include/sketchedit_jpg.h): a window of a frame -> the entropy-coded segment --
+// As the PNG encoder above: every check on the host, then the records and three launches; the workspace's blocks come from the
+// main arena, so SE_TEST_POISON fills each on the stream before its producer is enqueued.
+size_t se_jpg_bound(int hs, int ws) {
+  if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) return 0;
+  return (size_t)jpg_rows(hs) * jpg_row_bound(ws);
+}
+
+namespace {
+
+struct JpgLayout { size_t coef, sizes, slots; };              // bytes of the three blocks, each a multiple of 256
+JpgLayout jpg_layout(int B, int hs, int ws) {
+  const size_t q = (size_t)B * jpg_rows(hs);
+  return JpgLayout{pad256(q * jpg_row_blocks(ws) * 128), pad256(q * 4), pad256(q * jpg_slot_bytes(ws))};
+}
+
+}  // namespace
+
+size_t se_jpg_encode_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws) {
+  if (!c) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (B < 1 || B > 65535) { fail(c, "bad B=%d (1 .. 65535 images per call)", B); return 0; }
+  if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) { fail(c, "bad rectangle hs=%d ws=%d (sides are 16 .. 8192)", hs, ws); return 0; }
+  const JpgLayout L = jpg_layout(B, hs, ws);
+  return L.coef + L.sizes + L.slots;
+}
+
+int se_jpg_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int quality, unsigned char* out, size_t cap,
+                     unsigned long long* sizes_out, void* workspace, size_t workspace_bytes) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (B < 1 || B > 65535) return fail(c, "bad B=%d (1 .. 65535 images per call)", B);
+  if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) return fail(c, "bad rectangle hs=%d ws=%d (sides are 16 .. 8192)", hs, ws);
+  if (quality < 1 || quality > 100) return fail(c, "bad quality=%d (1 .. 100)", quality);
+  if (!wins) return fail(c, "null pointer argument: wins");
+  if (!out) return fail(c, "null pointer argument: out");
+  if (!sizes_out) return fail(c, "null pointer argument: sizes_out");
+  if (!workspace) return fail(c, "null pointer argument: workspace");
+  if (win_check_records(c, wins, B, hs, ws, false)) return 1;
+  const size_t bound = se_jpg_bound(hs, ws);
+  if (cap < bound) return fail(c, "cap=%zu is less than se_jpg_bound(%d, %d) = %zu", cap, hs, ws, bound);
+  if (cap > ((size_t)1 << 40) / (size_t)B) return fail(c, "cap=%zu: B cap is more than one call takes", cap);
+  const JpgLayout L = jpg_layout(B, hs, ws);
+  const size_t need = L.coef + L.sizes + L.slots;
+  if (workspace_bytes < need) return fail(c, "workspace too small: %zu bytes, need %zu", workspace_bytes, need);
+  if (!aligned_to(workspace, 256)) return fail(c, "workspace must be 256-byte aligned");
+  if (!aligned_to(sizes_out, 8)) return fail(c, "sizes_out must be 8-byte aligned");
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)B * cap, w0 = (uintptr_t)workspace, w1 = w0 + need;
+  const uintptr_t z0 = (uintptr_t)sizes_out, z1 = z0 + (size_t)B * sizeof(unsigned long long);
+  for (int i = 0; i < B; ++i) {
+    const uintptr_t f0 = (uintptr_t)wins[i].frame_u8, f1 = f0 + (size_t)wins[i].Hi * wins[i].Wi * 3;
+    if (o0 < f1 && f0 < o1) return fail(c, "out overlaps the frame of wins[%d]", i);
+    if (z0 < f1 && f0 < z1) return fail(c, "sizes_out overlaps the frame of wins[%d]", i);
+    if (w0 < f1 && f0 < w1) return fail(c, "workspace overlaps the frame of wins[%d]", i);
+  }
+  if (o0 < w1 && w0 < o1) return fail(c, "out overlaps the workspace");
+  if (o0 < z1 && z0 < o1) return fail(c, "out overlaps sizes_out");
+  if (z0 < w1 && w0 < z1) return fail(c, "sizes_out overlaps the workspace");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  const hipStream_t st = (hipStream_t)stream;
+  c->arena.reset((char*)workspace, need, false);
+  c->arena2.reset(nullptr, 0, false);
+  void* blk[3];
+  const size_t bytes[3] = {L.coef, L.sizes, L.slots};
+  for (int i = 0; i < 3; ++i) {
+    blk[i] = c->arena.alloc(bytes[i] / 4);
+    if (!blk[i]) return fail(c, "workspace arena exhausted");
+    if (poison(c, blk[i], bytes[i], st)) return 1;
+  }
+  const se_window* d = win_put(c, st, wins, B);
+  if (!d) return 1;
+  HIPCHK(c, launch_jpg_blocks(d, B, hs, ws, quality, (short*)blk[0], st));
+  HIPCHK(c, launch_jpg_rows(B, hs, ws, (const short*)blk[0], (unsigned*)blk[1], (unsigned char*)blk[2], st));
+  HIPCHK(c, launch_jpg_finish(B, hs, ws, (const unsigned*)blk[1], (const unsigned char*)blk[2], out, cap, sizes_out, st));
   return 0;
 }
 

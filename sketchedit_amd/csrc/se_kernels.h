@@ -20,7 +20,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_WINDOW_GATHER, PL_WINDOW_BORDER, PL_WINDOW_PASTE,
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
-                 PL_PNG_FINISH, PL_COUNT };
+                 PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -435,5 +435,18 @@ hipError_t launch_png_stripes(const se_window* d_wins, int B, int hs, int ws, co
                               unsigned char* slots, hipStream_t st);
 hipError_t launch_png_finish(int B, int hs, int ws, const unsigned* sizes, const unsigned* parts, const unsigned char* slots, unsigned char* out,
                              size_t cap, unsigned long long* sizes_out, hipStream_t st);
+// the device JPEG encoder (include/sketchedit_jpg.h): the hs x ws rectangles of d_wins (B records) -> their
+// entropy-coded segments.  blocks: coef (B,R,n,64) int16, the quantised coefficients in zigzag order, R = jpg_rows(hs) rows of
+// n = jpg_row_blocks(ws) blocks (Y, Cb, Cr per MCU).  rows: one workgroup per row -> its restart interval, stuffed, with its
+// marker, in its slot of jpg_slot_bytes(ws) bytes (16-byte aligned) and its size in sizes (B,R).  finish: the rows, concatenated,
+// at out + b cap (any alignment) and their lengths in sizes_out (B).
+int jpg_rows(int hs);
+int jpg_row_blocks(int ws);
+size_t jpg_row_bound(int ws);
+size_t jpg_slot_bytes(int ws);
+hipError_t launch_jpg_blocks(const se_window* d_wins, int B, int hs, int ws, int quality, short* coef, hipStream_t st);
+hipError_t launch_jpg_rows(int B, int hs, int ws, const short* coef, unsigned* sizes, unsigned char* slots, hipStream_t st);
+hipError_t launch_jpg_finish(int B, int hs, int ws, const unsigned* sizes, const unsigned char* slots, unsigned char* out, size_t cap,
+                             unsigned long long* sizes_out, hipStream_t st);
 
 }  // namespace se

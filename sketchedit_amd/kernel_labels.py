@@ -46,6 +46,10 @@ KERNEL_LABELS = {
     "(anonymous namespace)::png_rows_kernel": "png_rows", "(anonymous namespace)::png_stripe_kernel": "png_stripes",
     "(anonymous namespace)::png_finish_kernel": "png_finish",
     "png_rows_kernel": "png_rows", "png_stripe_kernel": "png_stripes", "png_finish_kernel": "png_finish",
+    # the device JPEG encoder of the editing sessions (se_jpg.hip)
+    "(anonymous namespace)::jpg_blocks_kernel": "jpg_blocks", "(anonymous namespace)::jpg_rows_kernel": "jpg_rows",
+    "(anonymous namespace)::jpg_finish_kernel": "jpg_finish",
+    "jpg_blocks_kernel": "jpg_blocks", "jpg_rows_kernel": "jpg_rows", "jpg_finish_kernel": "jpg_finish",
 }
 
 

@@ -182,6 +182,12 @@ class EditLine2Model(torch.nn.Module):
         PNG, encoded ON THE DEVICE; -> (out (B, cap) uint8, sizes (B,) int64) there (Engine.png_encode_u8)."""
         return self.engine().png_encode_u8(frames, origins, window_hw)
 
+    def jpg_encode_u8(self, frames, origins, window_hw, quality=90):
+        """Patches as JPEG: the (hs, ws) rectangle at origins[i] of every resident frame -> the entropy-coded
+        segment of its baseline JPEG, encoded ON THE DEVICE; -> (out (B, cap) uint8, sizes (B,) int64) there
+        (Engine.jpg_encode_u8)."""
+        return self.engine().jpg_encode_u8(frames, origins, window_hw, quality=quality)
+
     def forward(self, data, mode, low_latency=None):
         """`low_latency` (no reference counterpart): None = by this call's own size, True / False = pinned.  Results are
         bit-identical across batch compositions only WITHIN one mode (include/sketchedit_hip.h), so callers whose batch size

@@ -276,10 +276,73 @@ def png_from_zlib(stream, h, w):
 PNG_SIDE_MIN, PNG_SIDE_MAX = 16, 8192       # the sides of a rectangle the device encoder takes (include/sketchedit_png.h)
 
 
+# ---- the file around a device-encoded JPEG segment (include/sketchedit_jpg.h) ---------------------------------------
+# Annex K's quantisation tables in zigzag order, and its Huffman tables as a DHT segment carries them (counts per length, symbols)
+JPG_BASE_LUMA = (16, 11, 12, 14, 12, 10, 16, 14, 13, 14, 18, 17, 16, 19, 24, 40, 26, 24, 22, 22, 24, 49, 35, 37, 29, 40, 58, 51, 61, 60,
+                 57, 51, 56, 55, 64, 72, 92, 78, 64, 68, 87, 69, 55, 56, 80, 109, 81, 87, 95, 98, 103, 104, 103, 62, 77, 113, 121, 112,
+                 100, 120, 92, 101, 103, 99)
+JPG_BASE_CHROMA = (17, 18, 18, 24, 21, 24, 47, 26, 26, 47, 99, 66, 56, 66, 99) + (99,) * 49
+JPG_DHT = (
+    (0x00, (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x10, (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125),
+     (1, 2, 3, 0, 4, 17, 5, 18, 33, 49, 65, 6, 19, 81, 97, 7, 34, 113, 20, 50, 129, 145, 161, 8, 35, 66, 177, 193, 21, 82, 209, 240, 36, 51,
+      98, 114, 130, 9, 10, 22, 23, 24, 25, 26, 37, 38, 39, 40, 41, 42, 52, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74, 83, 84, 85,
+      86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 131, 132, 133, 134, 135, 136, 137,
+      138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185,
+      186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 225, 226, 227, 228, 229, 230, 231, 232,
+      233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250)),
+    (0x01, (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x11, (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119),
+     (0, 1, 2, 3, 17, 4, 5, 33, 49, 6, 18, 65, 81, 7, 97, 113, 19, 34, 50, 129, 8, 20, 66, 145, 161, 177, 193, 9, 35, 51, 82, 240, 21, 98,
+      114, 209, 10, 22, 36, 52, 225, 37, 241, 23, 24, 25, 26, 38, 39, 40, 41, 42, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74, 83,
+      84, 85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 130, 131, 132, 133, 134, 135,
+      136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183,
+      184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 226, 227, 228, 229, 230, 231,
+      232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250)),
+)
+JPG_QUALITY = 90                             # encode="jpg"
+
+
+def jpg_quant_table(base, quality):
+    """Annex K's table `base` under libjpeg's quality scaling, in zigzag order (rule 4 of include/sketchedit_jpg.h)"""
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise ValueError("quality is 1 .. 100 (got %r)" % (quality,))
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return [min(max((b * scale + 50) // 100, 1), 255) for b in base]
+
+
+def jpg_from_scan(scan, h, w, quality):
+    """The baseline JPEG file around an entropy-coded segment of an h x w rectangle at `quality`: SOI, a JFIF APP0,
+    two DQT, SOF0 (three components, 4:4:4), the four Annex K DHT, DRI (one restart interval per row of MCUs), SOS, `scan` as it
+    is, EOI -- the headers are the host's part of a patch that was encoded on the device."""
+    h, w = int(h), int(w)
+
+    def seg(marker, payload):
+        return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + bytes(payload)
+    out = [b"\xff\xd8", seg(0xE0, b"JFIF\0\x01\x01\0\0\x01\0\x01\0\0"),
+           seg(0xDB, [0] + jpg_quant_table(JPG_BASE_LUMA, quality)), seg(0xDB, [1] + jpg_quant_table(JPG_BASE_CHROMA, quality)),
+           seg(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([3, 1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1]))]
+    out += [seg(0xC4, (tc_th,) + counts + symbols) for tc_th, counts, symbols in JPG_DHT]
+    out += [seg(0xDD, (-(-w // 8)).to_bytes(2, "big")), seg(0xDA, [3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]), bytes(scan), b"\xff\xd9"]
+    return b"".join(out)
+
+
 def _check_encode(encode):
-    if encode not in (None, "png"):
-        raise ValueError("encode is None (raw (h,w,3) arrays) or 'png' (got %r)" % (encode,))
-    return encode
+    """-> None, "png" or ("jpg", quality)"""
+    if encode is None or (isinstance(encode, str) and encode == "png"):
+        return encode
+    if isinstance(encode, str) and encode == "jpg":
+        return ("jpg", JPG_QUALITY)
+    if (isinstance(encode, tuple) and len(encode) == 2 and isinstance(encode[0], str) and encode[0] == "jpg" and isinstance(encode[1], int)
+            and not isinstance(encode[1], bool) and 1 <= encode[1] <= 100):
+        return ("jpg", int(encode[1]))
+    raise ValueError("encode is None (raw (h,w,3) arrays), 'png', 'jpg' (quality %d) or ('jpg', quality 1 .. 100) (got %r)" % (JPG_QUALITY, encode))
+
+
+def _encoded(be, encode, frames, windows):
+    """the windows of `frames` as files, by a checked `encode` that is not None: one backend call"""
+    return be.crop_png(frames, windows) if encode == "png" else be.crop_jpg(frames, windows, encode[1])
 
 
 def _by_size(windows):
@@ -375,6 +438,16 @@ class _ModelBackend:
             buf, sizes = self.model.png_encode_u8([frames[i] for i in idx], [windows[i][:2] for i in idx], (h, w))
             for k, (i, n) in enumerate(zip(idx, sizes.cpu().tolist())):
                 out[i] = png_from_zlib(buf[k, :n].cpu().numpy().tobytes(), h, w)
+        return out
+
+    def crop_jpg(self, frames, windows, quality):
+        """the windows (y0, x0, h, w) of `frames` as baseline JPEG files at `quality`, encoded on the device: one
+        encoder call per window size; the segments' sizes come down first (the synchronisation), then exactly that many bytes"""
+        out = [None] * len(windows)
+        for (h, w), idx in _by_size(windows).items():
+            buf, sizes = self.model.jpg_encode_u8([frames[i] for i in idx], [windows[i][:2] for i in idx], (h, w), quality)
+            for k, (i, n) in enumerate(zip(idx, sizes.cpu().tolist())):
+                out[i] = jpg_from_scan(buf[k, :n].cpu().numpy().tobytes(), h, w, quality)
         return out
 
     def download(self, frame):
@@ -599,8 +672,9 @@ class EditSession:
         the plane, and the grow loop saw a mask that is 0 on locked pixels.
         `encode` (None: everything above): "png" returns `patch` as the bytes of a PNG file of the same window,
         encoded on the device -- what comes down is the compressed stream, not the pixels; the frame, the journal and info
-        are what they are without it."""
-        _check_encode(encode)
+        are what they are without it.  "jpg" (quality 90) or ("jpg", Q), Q = 1 .. 100, returns it as a baseline JPEG file
+        instead: a lossy preview several times smaller; the frame itself stays byte-exact."""
+        encode = _check_encode(encode)
         sk, bbox = self._request(sketch)
         margin = 0.5
         fixed = window is not None
@@ -637,7 +711,7 @@ class EditSession:
             elif not commit:
                 be.paste([self._frame], [(y0, x0)], rgb, m8)
             undoable = self._record(win, slot) if self.history > 0 else None
-            patch = be.crop(self._frame, y0, x0, h, w) if encode is None else be.crop_png([self._frame], [(y0, x0, h, w)])[0]
+            patch = be.crop(self._frame, y0, x0, h, w) if encode is None else _encoded(be, encode, [self._frame], [(y0, x0, h, w)])[0]
         info = dict(window=win, counts=list(counts[0]), reruns=reruns, margin=margin)
         if lk is not None:
             info["locked"] = True
@@ -664,8 +738,9 @@ class EditSession:
         size per window) / undoable where `edit` reports them.  An empty sketch or one of another size raises ValueError.
         With history on the call is ONE undo step: every window's rectangle is saved in front of its group's commit and the
         entry holds all slots; if they exceed `history_bytes` together the edit commits unjournalled and clears the history.
-        `encode` as in `edit`: "png" returns the patches as PNG files, encoded on the device (one backend call for all)."""
-        _check_encode(encode)
+        `encode` as in `edit`: "png", "jpg" or ("jpg", Q) returns the patches as files, encoded on the device (one backend call
+        for all)."""
+        encode = _check_encode(encode)
         sk = self._full_size(sketch)
         be = self.backend
         with self._lock:
@@ -709,7 +784,7 @@ class EditSession:
                 self._redo.clear()
             raise
         undoable = self._record_regions(wins, slots if journal else None) if self.history > 0 else None
-        patches = [be.crop(self._frame, *w) for w in wins] if encode is None else be.crop_png([self._frame] * len(wins), wins)
+        patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, [self._frame] * len(wins), wins)
         info = dict(windows=wins, boxes=[b for b, _ in regions], counts=counts, groups=len(groups))
         if lk is not None:
             info["locked"] = True
@@ -730,7 +805,7 @@ class EditSession:
         byte for byte in one pinned execution mode, S being the full-size 0 / 255 sketch the integer rule of 6i gives for
         the segments.  Everything else -- groups, lock, working size, history (ONE undo step), the return value -- is
         edit_regions', `encode` too.  ValueError for no strokes or one stroke_segments refuses."""
-        _check_encode(encode)
+        encode = _check_encode(encode)
         segs, ranges = stroke_segments(strokes, self.frame_hw)
         regions = merge_regions([stroke_box(segs[f:f + n], self.frame_hw) for f, n in ranges], self.frame_hw, margin, bucket, min_side)
         be = self.backend
@@ -743,16 +818,31 @@ class EditSession:
         with self._lock:
             return self.backend.download(self._frame)
 
-    def frame_png(self, rect=None):
-        """The frame, or its rectangle `rect` = (y0, x0, h, w), as the bytes of a PNG file encoded on the device (DESIGN.md
-        6j): only the compressed stream comes down.  The sides lie in [16, 8192] and the rectangle inside the frame."""
+    def _rect(self, rect):
+        """frame_png's and frame_jpg's rectangle, checked: (y0, x0, h, w), the whole frame for None"""
         Hi, Wi = self.frame_hw
         y0, x0, h, w = (0, 0, Hi, Wi) if rect is None else (int(v) for v in rect)
         if not (PNG_SIDE_MIN <= h <= PNG_SIDE_MAX and PNG_SIDE_MIN <= w <= PNG_SIDE_MAX) or y0 < 0 or x0 < 0 or y0 + h > Hi or x0 + w > Wi:
             raise ValueError("rectangle %r: sides are %d .. %d and the rectangle lies inside the %dx%d frame"
                              % ((y0, x0, h, w), PNG_SIDE_MIN, PNG_SIDE_MAX, Wi, Hi))
+        return (y0, x0, h, w)
+
+    def frame_png(self, rect=None):
+        """The frame, or its rectangle `rect` = (y0, x0, h, w), as the bytes of a PNG file encoded on the device (DESIGN.md
+        6j): only the compressed stream comes down.  The sides lie in [16, 8192] and the rectangle inside the frame."""
         with self._lock:
-            return self.backend.crop_png([self._frame], [(y0, x0, h, w)])[0]
+            return self.backend.crop_png([self._frame], [self._rect(rect)])[0]
+
+    def frame_jpg(self, rect=None, quality=90):
+        """The frame, or its rectangle `rect` = (y0, x0, h, w), as the bytes of a baseline JPEG file at `quality` 1 .. 100,
+        encoded on the device: a lossy preview, several times smaller than frame_png's file; the resident frame
+        is not touched.  The sides lie in [16, 8192] and the rectangle inside the frame."""
+        q = int(quality)
+        if not 1 <= q <= 100:
+            raise ValueError("quality is 1 .. 100 (got %r)" % (quality,))
+        win = self._rect(rect)
+        with self._lock:
+            return self.backend.crop_jpg([self._frame], [win], q)[0]
 
 
 def create_models_for_gpus(opt, gpu_ids=None):

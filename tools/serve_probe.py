@@ -81,6 +81,17 @@ noise (a flat or a noise frame would flatter one encoder or the other), one edit
 plus the bytes each request downloads, both files' sizes, and se_profile_report's per-kernel times of one (b) request.
 
     python tools/serve_probe.py --png [--reps N] [--out FILE]
+
+--jpg: patches as baseline JPEG at quality 90, encoded on the device, the same frame, window and protocol:
+  (a) edit_then_host_jpg: EditSession.edit, then Pillow's encoder (quality 90, 4:4:4, standard tables) on the patch on the host
+                          (the leg that is compared with the parent commit's build, run with --jpg-parent there: only this leg),
+  (b) edit_jpg:           EditSession.edit(encode="jpg"),
+  (c) encode_device / encode_host: the encoders alone -- se_jpg_encode_u8 of the window with the download of its segment, against
+                          the download of the window's pixels and Pillow's encoder on them;
+plus the bytes each request downloads, both files' sizes, the PNG's size for the same patch, the PSNR of both decoded files
+against the raw patch, and se_profile_report's per-kernel times of one (b) request.
+
+    python tools/serve_probe.py --jpg [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -529,6 +540,60 @@ def png_leg(model, reps, parent=False, side=512):
     return out
 
 
+def jpg_leg(model, reps, parent=False, side=512, quality=90):
+    """(a) - (c) of the module docstring; parent=True: leg (a) only, with the calls a build without the encoder has"""
+    import io
+    import numpy as np
+    from PIL import Image
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = np.stack([96 + 64 * np.sin(xx / 97.0) + 48 * np.cos(yy / 61.0), 128 + 90 * np.sin((xx + yy) / 143.0),
+                     110 + 70 * np.cos(xx / 53.0) * np.sin(yy / 77.0)], axis=2)
+    frame = np.clip(base + rng.randint(-2, 3, (h, w, 3)), 0, 255).astype(np.uint8)
+    win = (283, 705, side, side)
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+
+    def host_jpg(a):
+        f = io.BytesIO()
+        Image.fromarray(a).save(f, format="JPEG", quality=quality, subsampling=0, optimize=False)
+        return f.getvalue()
+
+    def psnr(data, a):
+        d = np.asarray(Image.open(io.BytesIO(data))).astype(np.float64) - a
+        return round(float(10 * np.log10(255.0 ** 2 / np.mean(d ** 2))), 3)
+    s1 = serve.EditSession(model, frame)
+    edit = lambda s, **kw: s.edit(sk, window=win, max_grow=0, low_latency=True, **kw)      # noqa: E731
+    legs = dict(edit_then_host_jpg=lambda: host_jpg(edit(s1)[0]))
+    out = dict(tool="serve_probe --jpg" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               window=list(win), quality=quality, raw_bytes_downloaded=side * side * 3)
+    if not parent:
+        s2 = serve.EditSession(model, frame)
+        be = s2.backend
+        legs.update(edit_jpg=lambda: edit(s2, encode=("jpg", quality)), encode_device=lambda: be.crop_jpg([s2._frame], [win], quality),
+                    encode_host=lambda: host_jpg(be.crop(s2._frame, *win)))
+    out["ms"] = rounds_of(legs, reps)
+    patch = edit(s1)[0]
+    out.update(host_jpg_bytes=len(host_jpg(patch)), host_jpg_psnr=psnr(host_jpg(patch), patch))
+    if not parent:
+        s3, s4 = serve.EditSession(model, frame), serve.EditSession(model, frame)
+        raw, jpg = edit(s3)[0], edit(s4, encode=("jpg", quality))[0]
+        eng = model.engine()
+        eng.profile(True)
+        edit(s2, encode=("jpg", quality))
+        rep = eng.profile_report()
+        eng.profile(False)
+        kernels = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"] if k["kernel"].startswith("jpg_")}
+        headers = len(serve.jpg_from_scan(b"", side, side, quality))
+        out.update(device_jpg_bytes=len(jpg), jpg_bytes_downloaded=len(jpg) - headers, jpg_kernels_profiled=kernels,
+                   device_png_bytes=len(be.crop_png([s4._frame], [win])[0]), device_jpg_psnr=psnr(jpg, raw),
+                   frames_identical=bool(np.array_equal(s3.frame(), s4.frame())),
+                   host_minus_device_request_ms=round(out["ms"]["edit_then_host_jpg"]["median"] - out["ms"]["edit_jpg"]["median"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -545,6 +610,8 @@ def main():
     ap.add_argument("--strokes-parent", action="store_true", help="the edit_regions leg of --strokes only")
     ap.add_argument("--png", action="store_true", help="patches as PNG, encoded on the device (see the module docstring)")
     ap.add_argument("--png-parent", action="store_true", help="the edit + host encoder leg of --png only")
+    ap.add_argument("--jpg", action="store_true", help="patches as JPEG, encoded on the device (see the module docstring)")
+    ap.add_argument("--jpg-parent", action="store_true", help="the edit + host encoder leg of --jpg only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -554,8 +621,11 @@ def main():
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     model = make_model(tempfile.mkdtemp())
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
-            or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent):
-        if args.png or args.png_parent:
+            or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
+            or args.jpg or args.jpg_parent):
+        if args.jpg or args.jpg_parent:
+            res = jpg_leg(model, args.reps, parent=args.jpg_parent)
+        elif args.png or args.png_parent:
             res = png_leg(model, args.reps, parent=args.png_parent)
         elif args.strokes or args.strokes_parent:
             res = strokes_leg(model, args.reps, parent=args.strokes_parent)
