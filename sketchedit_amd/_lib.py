@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_png.hip", "se_jpg.hip", "se_jpg2.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -47,6 +47,11 @@ SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_we
 PNG_SYMBOLS = ["se_png_bound", "se_png_encode_u8", "se_png_encode_u8_workspace_bytes"]
 # every symbol declared in include/sketchedit_jpg.h (the JPEG entries of the editing sessions)
 JPG_SYMBOLS = ["se_jpg_bound", "se_jpg_encode_u8", "se_jpg_encode_u8_workspace_bytes"]
+# every symbol declared in include/sketchedit_jpg2.h (4:2:0 sampling and per-image Huffman tables)
+JPG2_SYMBOLS = ["se_jpg2_bound", "se_jpg2_encode_u8", "se_jpg2_encode_u8_workspace_bytes", "se_jpg2_code_i16",
+                "se_jpg2_code_i16_workspace_bytes"]
+SE_JPG_420, SE_JPG_OPTIMIZE = 1, 2            # the flags of include/sketchedit_jpg2.h
+JPG_TABLE_RECORD_BYTES = 1088                 # one image's four tables as se_jpg2_encode_u8 leaves them
 
 
 class SketchEditHipError(RuntimeError):
@@ -78,7 +83,8 @@ def build_library(force=False, verbose=False, extra_flags=()):
     import fcntl
     from concurrent.futures import ThreadPoolExecutor
     hdrs = [os.path.join(CSRC, "se_kernels.h"), os.path.join(CSRC, "se_device.h"), os.path.join(CSRC, "se_pack.h"), os.path.join(_HERE, "..", "include", "sketchedit_hip.h"),
-            os.path.join(_HERE, "..", "include", "sketchedit_png.h"), os.path.join(_HERE, "..", "include", "sketchedit_jpg.h")]
+            os.path.join(_HERE, "..", "include", "sketchedit_png.h"), os.path.join(_HERE, "..", "include", "sketchedit_jpg.h"),
+            os.path.join(_HERE, "..", "include", "sketchedit_jpg2.h"), os.path.join(CSRC, "se_jpg_tables.h")]
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
@@ -238,6 +244,16 @@ def load_library():
         lib.se_jpg_encode_u8.restype = ci
         lib.se_jpg_encode_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
         lib.se_jpg_encode_u8_workspace_bytes.restype = sz
+        lib.se_jpg2_bound.argtypes = [ci, ci, ci]
+        lib.se_jpg2_bound.restype = sz
+        lib.se_jpg2_encode_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, ci, vp, sz, vp, vp, vp, sz]
+        lib.se_jpg2_encode_u8.restype = ci
+        lib.se_jpg2_encode_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
+        lib.se_jpg2_encode_u8_workspace_bytes.restype = sz
+        lib.se_jpg2_code_i16.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, sz, vp, vp, vp, sz]
+        lib.se_jpg2_code_i16.restype = ci
+        lib.se_jpg2_code_i16_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
+        lib.se_jpg2_code_i16_workspace_bytes.restype = sz
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -1028,6 +1044,80 @@ class Engine:
                                      _ptr(ws_t), ws_t.numel()):
             self._err("se_jpg_encode_u8")
         return out, sizes
+
+    # ---- patches as JPEG, 4:2:0 and per-image Huffman tables ----------------------------------------------------------
+    @staticmethod
+    def jpg2_flags(subsampling="444", optimize=False):
+        """("444" | "420", a bool) -> the flags of include/sketchedit_jpg2.h"""
+        if not (isinstance(subsampling, str) and subsampling in ("444", "420")):
+            raise SketchEditHipError("subsampling is '444' or '420' (got %r)" % (subsampling,))
+        if not isinstance(optimize, bool):
+            raise SketchEditHipError("optimize is a bool (got %r)" % (optimize,))
+        return (SE_JPG_420 if subsampling == "420" else 0) | (SE_JPG_OPTIMIZE if optimize else 0)
+
+    @staticmethod
+    def jpg2_bound(hs, ws, flags=0):
+        """se_jpg2_bound: the most bytes the segment of an hs x ws rectangle can take under `flags`; 0 for a side outside
+        [16, 8192] or flags outside 0 .. 3 (host only)"""
+        return int(load_library().se_jpg2_bound(int(hs), int(ws), int(flags)))
+
+    def _jpg2_outputs(self, B, cap_min, flags, dev, out, tables, what):
+        import torch
+        if out is None:
+            out = torch.empty((B, max(cap_min, 1)), dtype=torch.uint8, device=dev)
+        _check_dev_u8(out)
+        if out.dim() != 2 or out.shape[0] != B:
+            raise SketchEditHipError("%s: `out` is a (B, cap) uint8 tensor" % what)
+        if flags & SE_JPG_OPTIMIZE:
+            if tables is None:
+                tables = torch.empty((B, JPG_TABLE_RECORD_BYTES), dtype=torch.uint8, device=dev)
+            _check_dev_u8(tables)
+            if tuple(tables.shape) != (B, JPG_TABLE_RECORD_BYTES):
+                raise SketchEditHipError("%s: `tables` is a (B, %d) uint8 tensor" % (what, JPG_TABLE_RECORD_BYTES))
+        else:
+            tables = None
+        return out, torch.empty((B,), dtype=torch.int64, device=dev), tables
+
+    def jpg2_encode_u8(self, frames, origins, window_hw, quality=90, subsampling="444", optimize=False, out=None, tables=None):
+        """se_jpg2_encode_u8: jpg_encode_u8 with chroma at half resolution (subsampling="420") and/or four Huffman tables made
+        for each image (optimize=True; include/sketchedit_jpg2.h).  -> (out (B, cap) uint8, sizes (B,) int64, tables (B, 1088)
+        uint8 or None without `optimize`), all on the device; serve.jpg_from_scan makes the file from a segment and its table
+        record.  `out`: B rows of cap >= jpg2_bound(hs, ws, flags) bytes to write into; `tables`: the (B, 1088) tensor to
+        write the records into."""
+        hs, ws = (int(v) for v in window_hw)
+        flags = self.jpg2_flags(subsampling, optimize)
+        wins = self._windows(frames, origins)
+        B, dev = len(frames), frames[0].device
+        out, sizes, tables = self._jpg2_outputs(B, self.jpg2_bound(hs, ws, flags), flags, dev, out, tables, "jpg2_encode_u8")
+        need = self.lib.se_jpg2_encode_u8_workspace_bytes(self.h, B, hs, ws, flags)
+        if need == 0:
+            self._err("se_jpg2_encode_u8_workspace_bytes")
+        ws_t = self._workspace_bytes(need)
+        if self.lib.se_jpg2_encode_u8(self.h, self._stream(), wins, B, hs, ws, int(quality), flags, _ptr(out), out.shape[1], _ptr(sizes),
+                                      _ptr(tables) if tables is not None else None, _ptr(ws_t), ws_t.numel()):
+            self._err("se_jpg2_encode_u8")
+        return out, sizes, tables
+
+    def jpg2_code_i16(self, coef, subsampling="444", optimize=False, out=None, tables=None):
+        """se_jpg2_code_i16: the stages behind the DCT on their own.  coef (B, R, nblk, 64) int16 on the device, the quantised
+        coefficients in zigzag order and the stream's block order -> (out, sizes, tables) as jpg2_encode_u8.  Any int16 is
+        taken: AC coefficients and DC differences are clamped to what the tables have codes for."""
+        import torch
+        flags = self.jpg2_flags(subsampling, optimize)
+        if not (isinstance(coef, torch.Tensor) and coef.is_cuda and coef.dtype == torch.int16 and coef.is_contiguous() and coef.dim() == 4
+                and coef.shape[3] == 64):
+            raise SketchEditHipError("jpg2_code_i16: coef is a contiguous (B, R, nblk, 64) int16 tensor on the device")
+        B, R, nblk = (int(v) for v in coef.shape[:3])
+        need = self.lib.se_jpg2_code_i16_workspace_bytes(self.h, B, R, nblk, flags)
+        if need == 0:
+            self._err("se_jpg2_code_i16_workspace_bytes")
+        bits = 1665 if flags & SE_JPG_OPTIMIZE else 1660
+        out, sizes, tables = self._jpg2_outputs(B, R * (2 * ((bits * nblk + 7) // 8) + 2), flags, coef.device, out, tables, "jpg2_code_i16")
+        ws_t = self._workspace_bytes(need)
+        if self.lib.se_jpg2_code_i16(self.h, self._stream(), _ptr(coef), B, R, nblk, flags, _ptr(out), out.shape[1], _ptr(sizes),
+                                     _ptr(tables) if tables is not None else None, _ptr(ws_t), ws_t.numel()):
+            self._err("se_jpg2_code_i16")
+        return out, sizes, tables
 
     def inference_packed(self, image, sketch, flags, out, low_latency=None):
         """Inference into ONE (B,4,H,W) buffer `out`: planes 0-2 composed, plane 3 the soft mask -- the unit the

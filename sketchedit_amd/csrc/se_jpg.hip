@@ -28,6 +28,7 @@
 // stores only, no inline assembly.
 #include "../../include/sketchedit_jpg.h"
 #include "se_device.h"
+#include "se_jpg_tables.h"
 #include "se_kernels.h"
 
 #include <cstdint>
@@ -40,51 +41,6 @@ constexpr int JPG_T = 1024;                     // lanes of a row's workgroup
 constexpr int JPG_TILE = JPG_T / 64;            // blocks of a tile: a wave each
 constexpr int JPG_BLOCK_BITS = 22 + 63 * 26;    // the most bits of one block
 constexpr int JPG_STAGE = (31 + JPG_TILE * JPG_BLOCK_BITS + 31) / 32 + 2;      // words of the stage: 31 carried bits + a tile, and two more
-
-// rule 3's table, A[u][x]
-__device__ const short JPG_A[64] = {2896, 2896, 2896, 2896, 2896, 2896, 2896, 2896, 4017, 3406, 2276, 799, -799, -2276, -3406, -4017,
-                                    3784, 1567, -1567, -3784, -3784, -1567, 1567, 3784, 3406, -799, -4017, -2276, 2276, 4017, 799, -3406,
-                                    2896, -2896, -2896, 2896, 2896, -2896, -2896, 2896, 2276, -4017, 799, 3406, -3406, -799, 4017, -2276,
-                                    1567, -3784, 3784, -1567, -1567, 3784, -3784, 1567, 799, -2276, 3406, -4017, 4017, -3406, 2276, -799};
-// the zigzag index of the coefficient at natural index v * 8 + u
-__device__ const unsigned char JPG_ZZ_OF[64] = {0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43,
-                                                9, 11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60,
-                                                21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
-// Annex K's quantisation tables (K.1, K.2) in zigzag order
-__device__ const unsigned char JPG_BASE[2][64] = {
-    {16, 11, 12, 14, 12, 10, 16, 14, 13, 14, 18, 17, 16, 19, 24, 40, 26, 24, 22, 22, 24, 49, 35, 37, 29, 40, 58, 51, 61, 60, 57, 51,
-     56, 55, 64, 72, 92, 78, 64, 68, 87, 69, 55, 56, 80, 109, 81, 87, 95, 98, 103, 104, 103, 62, 77, 113, 121, 112, 100, 120, 92, 101, 103, 99},
-    {17, 18, 18, 24, 21, 24, 47, 26, 26, 47, 99, 66, 56, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-// Annex K's Huffman tables (K.3 - K.6) as a DHT segment carries them: codes per length 1 .. 16, then the symbols in code order
-__device__ const unsigned char JPG_DC_COUNTS[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
-__device__ const unsigned char JPG_AC_COUNTS[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
-__device__ const unsigned char JPG_AC_SYMBOLS[2][162] = {
-    {1, 2, 3, 0, 4, 17, 5, 18, 33, 49, 65, 6, 19, 81, 97, 7, 34, 113, 20, 50, 129, 145, 161, 8, 35, 66, 177, 193, 21, 82, 209, 240,
-     36, 51, 98, 114, 130, 9, 10, 22, 23, 24, 25, 26, 37, 38, 39, 40, 41, 42, 52, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72,
-     73, 74, 83, 84, 85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 131,
-     132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170,
-     178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216,
-     217, 218, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250},
-    {0, 1, 2, 3, 17, 4, 5, 33, 49, 6, 18, 65, 81, 7, 97, 113, 19, 34, 50, 129, 8, 20, 66, 145, 161, 177, 193, 9, 35, 51, 82, 240,
-     21, 98, 114, 209, 10, 22, 36, 52, 225, 37, 241, 23, 24, 25, 26, 38, 39, 40, 41, 42, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70,
-     71, 72, 73, 74, 83, 84, 85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121,
-     122, 130, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167,
-     168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213,
-     214, 215, 216, 217, 218, 226, 227, 228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250}};
-
-// the k-th symbol (in code order) of a table with these counts -> (code << 5) | length, the canonical code of Annex C
-__device__ __forceinline__ unsigned canonical(const unsigned char* counts, int k) {
-  unsigned code = 0u;
-  int first = 0;
-  for (int len = 1; len <= 16; ++len) {
-    const int n = counts[len - 1];
-    if (k < first + n) return ((code + (unsigned)(k - first)) << 5) | (unsigned)len;
-    code = (code + (unsigned)n) << 1;
-    first += n;
-  }
-  return 0u;
-}
 
 __global__ void __launch_bounds__(256) jpg_blocks_kernel(const se_window* __restrict__ wins, int hs, int ws, int nbx, int scale,
                                                          short* __restrict__ coef) {
@@ -347,6 +303,16 @@ hipError_t launch_jpg_finish(int B, int hs, int ws, const unsigned* sizes, const
   set_launch_grid((long)R * B);
   ProfScope ps_(st, PL_JPG_FINISH);
   hipLaunchKernelGGL(jpg_finish_kernel, dim3((unsigned)R, (unsigned)B), dim3(256), 0, st, R, sizes, slots, jpg_slot_bytes(ws), out, cap, sizes_out);
+  return hipGetLastError();
+}
+
+// the same kernel for rows of any geometry (se_jpg2.hip): R rows an image, slots of slot_bytes (16-byte aligned), nblk blocks a row
+hipError_t launch_jpg_finish_rows(int B, int R, int nblk, size_t slot_bytes, const unsigned* sizes, const unsigned char* slots,
+                                  unsigned char* out, size_t cap, unsigned long long* sizes_out, hipStream_t st) {
+  set_launch_cost(0.0, (double)B * R * nblk * 64.0 * 2.0, "jpg_finish");
+  set_launch_grid((long)R * B);
+  ProfScope ps_(st, PL_JPG_FINISH);
+  hipLaunchKernelGGL(jpg_finish_kernel, dim3((unsigned)R, (unsigned)B), dim3(256), 0, st, R, sizes, slots, slot_bytes, out, cap, sizes_out);
   return hipGetLastError();
 }
 

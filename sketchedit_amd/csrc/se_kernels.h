@@ -20,7 +20,8 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_ATT_STREAM_STATS, PL_ATT_STREAM_OUT, PL_RESIZE_H, PL_RESIZE_V, PL_WINDOW_GATHER, PL_WINDOW_BORDER, PL_WINDOW_PASTE,
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
-                 PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_COUNT };
+                 PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
+                 PL_JPG2_ROWS, PL_COUNT };
 const char* prof_label_name(int l);
 struct Profiler {
   struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
@@ -448,5 +449,21 @@ hipError_t launch_jpg_blocks(const se_window* d_wins, int B, int hs, int ws, int
 hipError_t launch_jpg_rows(int B, int hs, int ws, const short* coef, unsigned* sizes, unsigned char* slots, hipStream_t st);
 hipError_t launch_jpg_finish(int B, int hs, int ws, const unsigned* sizes, const unsigned char* slots, unsigned char* out, size_t cap,
                              unsigned long long* sizes_out, hipStream_t st);
+// the same with 4:2:0 sampling and per-image Huffman tables (include/sketchedit_jpg2.h; flags = SE_JPG_420 |
+// SE_JPG_OPTIMIZE).  A row of MCUs is 16 pixel rows of 6 blocks an MCU under SE_JPG_420 (blocks420: coef (B,R,mcus,6,64)).  hist:
+// one partial histogram of 4 x 256 counters per row, hist (B,R,4,256).  tables: per image the codes (B,4,256), (code << 5) |
+// length per symbol, and the record of 4 x 272 bytes at tables_out + 1088 b (4-byte aligned).  rows: as above, the tables from
+// `codes` or, where that is null, Annex K's.  finish: launch_jpg_finish_rows, the kernel of launch_jpg_finish for any geometry.
+int jpg2_rows(int hs, int flags);
+int jpg2_row_blocks(int ws, int flags);
+size_t jpg2_row_bound(int nblk, int flags);
+size_t jpg2_slot_bytes(int nblk, int flags);
+hipError_t launch_jpg2_blocks420(const se_window* d_wins, int B, int hs, int ws, int quality, short* coef, hipStream_t st);
+hipError_t launch_jpg2_hist(int B, int R, int nblk, int flags, const short* coef, unsigned* hist, hipStream_t st);
+hipError_t launch_jpg2_tables(int B, int R, const unsigned* hist, unsigned* codes, unsigned char* tables_out, hipStream_t st);
+hipError_t launch_jpg2_rows(int B, int R, int nblk, int flags, const short* coef, const unsigned* codes, unsigned* sizes,
+                            unsigned char* slots, hipStream_t st);
+hipError_t launch_jpg_finish_rows(int B, int R, int nblk, size_t slot_bytes, const unsigned* sizes, const unsigned char* slots,
+                                  unsigned char* out, size_t cap, unsigned long long* sizes_out, hipStream_t st);
 
 }  // namespace se

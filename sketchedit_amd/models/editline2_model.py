@@ -188,6 +188,12 @@ class EditLine2Model(torch.nn.Module):
         (Engine.jpg_encode_u8)."""
         return self.engine().jpg_encode_u8(frames, origins, window_hw, quality=quality)
 
+    def jpg2_encode_u8(self, frames, origins, window_hw, quality=90, subsampling="444", optimize=False):
+        """Patches as JPEG with chroma at half resolution (subsampling="420") and/or four Huffman tables made for each image
+        (optimize=True), encoded ON THE DEVICE; -> (out (B, cap) uint8, sizes (B,) int64, tables (B, 1088) uint8
+        or None) there (Engine.jpg2_encode_u8)."""
+        return self.engine().jpg2_encode_u8(frames, origins, window_hw, quality=quality, subsampling=subsampling, optimize=optimize)
+
     def forward(self, data, mode, low_latency=None):
         """`low_latency` (no reference counterpart): None = by this call's own size, True / False = pinned.  Results are
         bit-identical across batch compositions only WITHIN one mode (include/sketchedit_hip.h), so callers whose batch size

@@ -312,37 +312,76 @@ def jpg_quant_table(base, quality):
     return [min(max((b * scale + 50) // 100, 1), 255) for b in base]
 
 
-def jpg_from_scan(scan, h, w, quality):
-    """The baseline JPEG file around an entropy-coded segment of an h x w rectangle at `quality`: SOI, a JFIF APP0,
-    two DQT, SOF0 (three components, 4:4:4), the four Annex K DHT, DRI (one restart interval per row of MCUs), SOS, `scan` as it
-    is, EOI -- the headers are the host's part of a patch that was encoded on the device."""
+JPG_SUBSAMPLINGS = ("444", "420")
+JPG_TABLE_BYTES = 272                        # one table of a device record: 16 counts of codes per length, 256 symbols (zero-padded)
+
+
+def _check_subsampling(subsampling):
+    if not (isinstance(subsampling, str) and subsampling in JPG_SUBSAMPLINGS):
+        raise ValueError("subsampling is '444' or '420' (got %r)" % (subsampling,))
+    return subsampling
+
+
+def jpg_dht_from_record(tables):
+    """A device table record (include/sketchedit_jpg2.h rule 5e: 4 x 272 bytes, DC lum, AC lum, DC chr, AC chr) -> the four
+    (class/id, counts, symbols) of its DHT segments, with the true symbol counts, not the padding"""
+    tables = bytes(tables)
+    if len(tables) != 4 * JPG_TABLE_BYTES:
+        raise ValueError("a table record is %d bytes (got %d)" % (4 * JPG_TABLE_BYTES, len(tables)))
+    out = []
+    for k, tc_th in enumerate((0x00, 0x10, 0x01, 0x11)):
+        part = tables[k * JPG_TABLE_BYTES:(k + 1) * JPG_TABLE_BYTES]
+        n = sum(part[:16])
+        if not 1 <= n <= 256:
+            raise ValueError("table %d of the record has %d symbols" % (k, n))
+        out.append((tc_th, tuple(part[:16]), tuple(part[16:16 + n])))
+    return out
+
+
+def jpg_from_scan(scan, h, w, quality, subsampling="444", tables=None):
+    """The baseline JPEG file around an entropy-coded segment of an h x w rectangle at `quality`: SOI, a JFIF
+    APP0, two DQT, SOF0 (three components; Y's sampling factors 0x22 for subsampling="420"), four DHT (Annex K's, or those of
+    `tables`, the device's record of an image coded with its own tables), DRI (one restart interval per row of MCUs), SOS, `scan`
+    as it is, EOI -- the headers are the host's part of a patch that was encoded on the device."""
     h, w = int(h), int(w)
+    mcu = 16 if _check_subsampling(subsampling) == "420" else 8
+    dht = JPG_DHT if tables is None else jpg_dht_from_record(tables)
 
     def seg(marker, payload):
         return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + bytes(payload)
     out = [b"\xff\xd8", seg(0xE0, b"JFIF\0\x01\x01\0\0\x01\0\x01\0\0"),
            seg(0xDB, [0] + jpg_quant_table(JPG_BASE_LUMA, quality)), seg(0xDB, [1] + jpg_quant_table(JPG_BASE_CHROMA, quality)),
-           seg(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([3, 1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1]))]
-    out += [seg(0xC4, (tc_th,) + counts + symbols) for tc_th, counts, symbols in JPG_DHT]
-    out += [seg(0xDD, (-(-w // 8)).to_bytes(2, "big")), seg(0xDA, [3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]), bytes(scan), b"\xff\xd9"]
+           seg(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([3, 1, 0x22 if mcu == 16 else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1]))]
+    out += [seg(0xC4, (tc_th,) + counts + symbols) for tc_th, counts, symbols in dht]
+    out += [seg(0xDD, (-(-w // mcu)).to_bytes(2, "big")), seg(0xDA, [3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]), bytes(scan), b"\xff\xd9"]
     return b"".join(out)
 
 
 def _check_encode(encode):
-    """-> None, "png" or ("jpg", quality)"""
+    """-> None, "png", ("jpg", quality) or ("jpg", quality, subsampling, optimize)"""
     if encode is None or (isinstance(encode, str) and encode == "png"):
         return encode
     if isinstance(encode, str) and encode == "jpg":
         return ("jpg", JPG_QUALITY)
-    if (isinstance(encode, tuple) and len(encode) == 2 and isinstance(encode[0], str) and encode[0] == "jpg" and isinstance(encode[1], int)
-            and not isinstance(encode[1], bool) and 1 <= encode[1] <= 100):
-        return ("jpg", int(encode[1]))
-    raise ValueError("encode is None (raw (h,w,3) arrays), 'png', 'jpg' (quality %d) or ('jpg', quality 1 .. 100) (got %r)" % (JPG_QUALITY, encode))
+    if (isinstance(encode, tuple) and 2 <= len(encode) <= 4 and isinstance(encode[0], str) and encode[0] == "jpg" and isinstance(encode[1], int)
+            and not isinstance(encode[1], bool) and 1 <= encode[1] <= 100
+            and (len(encode) < 3 or (isinstance(encode[2], str) and encode[2] in JPG_SUBSAMPLINGS))
+            and (len(encode) < 4 or isinstance(encode[3], bool))):
+        sub, opt = encode[2] if len(encode) > 2 else "444", encode[3] if len(encode) > 3 else False
+        if sub == "444" and not opt:             # the defaults spelled out: the call the backends have always received
+            return ("jpg", int(encode[1]))
+        return ("jpg", int(encode[1]), sub, opt)
+    raise ValueError("encode is None (raw (h,w,3) arrays), 'png', 'jpg' (quality %d), ('jpg', quality 1 .. 100), ('jpg', quality, '444' | '420') "
+                     "or ('jpg', quality, '444' | '420', a bool: per-image Huffman tables) (got %r)" % (JPG_QUALITY, encode))
 
 
 def _encoded(be, encode, frames, windows):
     """the windows of `frames` as files, by a checked `encode` that is not None: one backend call"""
-    return be.crop_png(frames, windows) if encode == "png" else be.crop_jpg(frames, windows, encode[1])
+    if encode == "png":
+        return be.crop_png(frames, windows)
+    if len(encode) == 2:                         # (the call the backends have always received)
+        return be.crop_jpg(frames, windows, encode[1])
+    return be.crop_jpg(frames, windows, encode[1], subsampling=encode[2], optimize=encode[3])
 
 
 def _by_size(windows):
@@ -440,14 +479,26 @@ class _ModelBackend:
                 out[i] = png_from_zlib(buf[k, :n].cpu().numpy().tobytes(), h, w)
         return out
 
-    def crop_jpg(self, frames, windows, quality):
+    def crop_jpg(self, frames, windows, quality, subsampling="444", optimize=False):
         """the windows (y0, x0, h, w) of `frames` as baseline JPEG files at `quality`, encoded on the device: one
-        encoder call per window size; the segments' sizes come down first (the synchronisation), then exactly that many bytes"""
+        encoder call per window size; the segments' sizes come down first (the synchronisation), then exactly that many bytes.
+        subsampling="420" and/or optimize=True (four Huffman tables per image, which come down with the sizes) take the
+        encoder of DESIGN.md 6l; the defaults take 6k's, as before."""
         out = [None] * len(windows)
+        if _check_subsampling(subsampling) == "444" and optimize is False:
+            for (h, w), idx in _by_size(windows).items():
+                buf, sizes = self.model.jpg_encode_u8([frames[i] for i in idx], [windows[i][:2] for i in idx], (h, w), quality)
+                for k, (i, n) in enumerate(zip(idx, sizes.cpu().tolist())):
+                    out[i] = jpg_from_scan(buf[k, :n].cpu().numpy().tobytes(), h, w, quality)
+            return out
         for (h, w), idx in _by_size(windows).items():
-            buf, sizes = self.model.jpg_encode_u8([frames[i] for i in idx], [windows[i][:2] for i in idx], (h, w), quality)
-            for k, (i, n) in enumerate(zip(idx, sizes.cpu().tolist())):
-                out[i] = jpg_from_scan(buf[k, :n].cpu().numpy().tobytes(), h, w, quality)
+            buf, sizes, tables = self.model.jpg2_encode_u8([frames[i] for i in idx], [windows[i][:2] for i in idx], (h, w), quality,
+                                                           subsampling=subsampling, optimize=optimize)
+            sizes = sizes.cpu().tolist()
+            tables = tables.cpu().numpy() if tables is not None else None
+            for k, (i, n) in enumerate(zip(idx, sizes)):
+                out[i] = jpg_from_scan(buf[k, :n].cpu().numpy().tobytes(), h, w, quality, subsampling,
+                                       tables[k].tobytes() if tables is not None else None)
         return out
 
     def download(self, frame):
@@ -673,7 +724,9 @@ class EditSession:
         `encode` (None: everything above): "png" returns `patch` as the bytes of a PNG file of the same window,
         encoded on the device -- what comes down is the compressed stream, not the pixels; the frame, the journal and info
         are what they are without it.  "jpg" (quality 90) or ("jpg", Q), Q = 1 .. 100, returns it as a baseline JPEG file
-        instead: a lossy preview several times smaller; the frame itself stays byte-exact."""
+        instead: a lossy preview several times smaller; the frame itself stays byte-exact.  ("jpg", Q, "420")
+        stores chroma at half resolution and ("jpg", Q, "444" | "420", True) codes with four Huffman tables made for the patch
+        (DESIGN.md 6l): smaller files for the same decoder."""
         encode = _check_encode(encode)
         sk, bbox = self._request(sketch)
         margin = 0.5
@@ -833,16 +886,23 @@ class EditSession:
         with self._lock:
             return self.backend.crop_png([self._frame], [self._rect(rect)])[0]
 
-    def frame_jpg(self, rect=None, quality=90):
+    def frame_jpg(self, rect=None, quality=90, subsampling="444", optimize=False):
         """The frame, or its rectangle `rect` = (y0, x0, h, w), as the bytes of a baseline JPEG file at `quality` 1 .. 100,
         encoded on the device: a lossy preview, several times smaller than frame_png's file; the resident frame
-        is not touched.  The sides lie in [16, 8192] and the rectangle inside the frame."""
+        is not touched.  The sides lie in [16, 8192] and the rectangle inside the frame.  subsampling="420" stores chroma at
+        half resolution and optimize=True codes with four Huffman tables made for this image: smaller files,
+        the same decoder."""
         q = int(quality)
         if not 1 <= q <= 100:
             raise ValueError("quality is 1 .. 100 (got %r)" % (quality,))
+        _check_subsampling(subsampling)
+        if not isinstance(optimize, bool):
+            raise ValueError("optimize is a bool (got %r)" % (optimize,))
         win = self._rect(rect)
         with self._lock:
-            return self.backend.crop_jpg([self._frame], [win], q)[0]
+            if subsampling == "444" and not optimize:
+                return self.backend.crop_jpg([self._frame], [win], q)[0]
+            return self.backend.crop_jpg([self._frame], [win], q, subsampling=subsampling, optimize=optimize)[0]
 
 
 def create_models_for_gpus(opt, gpu_ids=None):

@@ -92,6 +92,14 @@ plus the bytes each request downloads, both files' sizes, the PNG's size for the
 against the raw patch, and se_profile_report's per-kernel times of one (b) request.
 
     python tools/serve_probe.py --jpg [--reps N] [--out FILE]
+
+--jpg2: the JPEG forms of DESIGN.md 6l next to 6k's in one build, the same frame, window, quality and protocol: EditSession.edit
+with encode=("jpg", 90) (edit_jpg: the leg that is compared with the parent commit's --jpg run, whose leg (b) it is),
+("jpg", 90, "420"), ("jpg", 90, "444", True) and ("jpg", 90, "420", True); plus each form's file size, the bytes its request
+downloads (the segment and, with per-image tables, the 1088-byte record), its PSNR against the raw patch, that Pillow decodes
+the two 4:2:0 files to the same pixels, and se_profile_report's per-kernel times of one request of each form.
+
+    python tools/serve_probe.py --jpg2 [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -594,6 +602,62 @@ def jpg_leg(model, reps, parent=False, side=512, quality=90):
     return out
 
 
+def jpg2_leg(model, reps, side=512, quality=90):
+    """the four forms of the module docstring"""
+    import io
+    import numpy as np
+    from PIL import Image
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = np.stack([96 + 64 * np.sin(xx / 97.0) + 48 * np.cos(yy / 61.0), 128 + 90 * np.sin((xx + yy) / 143.0),
+                     110 + 70 * np.cos(xx / 53.0) * np.sin(yy / 77.0)], axis=2)
+    frame = np.clip(base + rng.randint(-2, 3, (h, w, 3)), 0, 255).astype(np.uint8)
+    win = (283, 705, side, side)
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    forms = dict(edit_jpg=("jpg", quality), edit_jpg_420=("jpg", quality, "420"), edit_jpg_444_opt=("jpg", quality, "444", True),
+                 edit_jpg_420_opt=("jpg", quality, "420", True))
+
+    def pixels(data):
+        return np.asarray(Image.open(io.BytesIO(data))).astype(np.float64)
+
+    def scan_bytes(data):
+        """the bytes between the SOS segment and EOI: what the device wrote"""
+        i = 2
+        while data[i + 1] != 0xDA:
+            i += 2 + ((data[i + 2] << 8) | data[i + 3])
+        return len(data) - (i + 2 + ((data[i + 2] << 8) | data[i + 3])) - 2
+    edit = lambda s, **kw: s.edit(sk, window=win, max_grow=0, low_latency=True, **kw)      # noqa: E731
+    sessions = {k: serve.EditSession(model, frame) for k in forms}
+    out = dict(tool="serve_probe --jpg2", B=1, reps=reps, mode="low_latency", frame=[w, h], window=list(win), quality=quality,
+               raw_bytes_downloaded=side * side * 3)
+    out["ms"] = rounds_of({k: (lambda k=k: edit(sessions[k], encode=forms[k])) for k in forms}, reps)
+    raw = edit(serve.EditSession(model, frame))[0]
+    eng = model.engine()
+    files = {}
+    for k, form in forms.items():
+        s = serve.EditSession(model, frame)
+        files[k] = edit(s, encode=form)[0]
+        eng.profile(True)
+        edit(sessions[k], encode=form)
+        rep = eng.profile_report()
+        eng.profile(False)
+        kernels = {r["kernel"]: dict(launches=r["launches"], ms=round(r["total_ms"], 4)) for r in rep["kernels"] if r["kernel"].startswith("jpg")}
+        out[k] = dict(file_bytes=len(files[k]), bytes_downloaded=scan_bytes(files[k]) + (1088 if len(form) > 3 and form[3] else 0),
+                      kernels_profiled=kernels, kernels_total_ms=round(sum(v["ms"] for v in kernels.values()), 4),
+                      psnr=round(float(10 * np.log10(255.0 ** 2 / np.mean((pixels(files[k]) - raw) ** 2))), 3),
+                      ratio_to_edit_jpg=round(len(files[k]) / len(files["edit_jpg"]), 4),
+                      frame_identical=bool(np.array_equal(s.frame(), sessions["edit_jpg"].frame())))
+    out.update(decoded_420_equal_with_and_without_tables=bool(np.array_equal(pixels(files["edit_jpg_420"]), pixels(files["edit_jpg_420_opt"]))),
+               decoded_444_equal_with_and_without_tables=bool(np.array_equal(pixels(files["edit_jpg"]), pixels(files["edit_jpg_444_opt"]))),
+               table_record_bytes_downloaded=1088)
+    for k in forms:
+        out[k]["minus_edit_jpg_ms"] = round(out["ms"][k]["median"] - out["ms"]["edit_jpg"]["median"], 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -612,6 +676,7 @@ def main():
     ap.add_argument("--png-parent", action="store_true", help="the edit + host encoder leg of --png only")
     ap.add_argument("--jpg", action="store_true", help="patches as JPEG, encoded on the device (see the module docstring)")
     ap.add_argument("--jpg-parent", action="store_true", help="the edit + host encoder leg of --jpg only")
+    ap.add_argument("--jpg2", action="store_true", help="JPEG patches in 4:2:0 and with per-image Huffman tables (see the module docstring)")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -622,8 +687,10 @@ def main():
     model = make_model(tempfile.mkdtemp())
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
-            or args.jpg or args.jpg_parent):
-        if args.jpg or args.jpg_parent:
+            or args.jpg or args.jpg_parent or args.jpg2):
+        if args.jpg2:
+            res = jpg2_leg(model, args.reps)
+        elif args.jpg or args.jpg_parent:
             res = jpg_leg(model, args.reps, parent=args.jpg_parent)
         elif args.png or args.png_parent:
             res = png_leg(model, args.reps, parent=args.png_parent)
