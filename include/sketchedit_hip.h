@@ -339,7 +339,9 @@ int se_resample_coeffs(int in, int out, int filter, int* bounds, int* k, size_t 
  * se_profile_enable(ctx, 1): wrap every kernel launch of subsequent forwards in a pair of HIP events
  * recorded on the launch stream; se_profile_report synchronises the device and writes a JSON array
  *   [{"kernel": name, "launches": n, "total_ms": t, "flops": algorithmic FLOPs, "bytes": ...}, ...]
- * aggregated per kernel.  se_profile_enable(ctx, 0) switches it off and drops the records. */
+ * aggregated per kernel ("kernels"), the same per layer ("layers"), and every launch on its own in launch order
+ * ("launches": [{"form": the kernel form the dispatcher chose, "kernel", "layer", "workgroups"}, ...] -- what the tests
+ * read to know which kernel ran).  se_profile_enable(ctx, 0) switches it off and drops the records. */
 int se_profile_enable(se_ctx* ctx, int on);
 int se_profile_report(se_ctx* ctx, char* buf, size_t cap);
 

@@ -4,6 +4,7 @@ This is the thin layer a maintainer of the reference would add:
 device tensors, this module passes their raw pointers + the current HIP stream to the library.
 There is NO fallback: if the library is missing or fails, an exception is raised.
 """
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -1138,10 +1139,23 @@ class Engine:
 
     def profile_report(self):
         import json
-        buf = ctypes.create_string_buffer(1 << 18)
+        buf = ctypes.create_string_buffer(1 << 19)      # (a full event pool: 1024 records of "launches", ~130 bytes each)
         if self.lib.se_profile_report(self.h, buf, len(buf)):
             self._err("se_profile_report")
         return json.loads(buf.value.decode())
+
+    @contextlib.contextmanager
+    def launch_forms(self):
+        """Test aid: records which kernel form every launch of the body took.  Turns the profiler on (which clears earlier
+        records); on exit -- also when the body raises -- turns it off again.  Yields a list that holds, after the body, one
+        (form, layer) tuple per launch in launch order (se_profile_report's "launches"; DESIGN.md 3.1f names the forms)."""
+        forms = []
+        self.profile(True)
+        try:
+            yield forms
+            forms.extend((r["form"], r["layer"]) for r in self.profile_report()["launches"])
+        finally:
+            self.profile(False)
 
     # ---- per-op entry points (unit tests) --------------------------------------------------------
     def gated_conv2d(self, x, w, b, stride=1, rate=1, act="elu", upsample=False, x1=None, low_latency=False, bf16=False):

@@ -237,9 +237,12 @@ int try_rtile(se_ctx* c, const Layer& L, bool bf, const float* src0, int C0, con
   const LayerDef& d = L.def;
   if (!opt(OPT_RTILE) || src1 || d.stride != 1 || d.rate != 1 || (L.cfg != GC_N48 && L.cfg != GC_N24)) return 0;
   {
-    // low-latency mode: only when the tiles still cover the CUs (the small-grid gather-GEMM splits rows over blockIdx.y)
+    // low-latency mode: only when the tiles still cover the CUs (the small-grid gather-GEMM splits rows over blockIdx.y).
+    // Counted PER IMAGE like the Winograd grids of run_gconv: the kernel a layer runs depends on the image size and the
+    // mode only, never on the batch (with B in the count a 128x128 image took the raw-tile kernel at B = 2 and the
+    // gather-GEMM at B = 1, and its bits differed between the two calls)
     const int TR0 = rtile_rows(bf);
-    const long tiles = (long)B * ((Hin + TR0 - 1) / TR0) * ((Win + 15) / 16) * (d.up ? 4 : 1);
+    const long tiles = (long)((Hin + TR0 - 1) / TR0) * ((Win + 15) / 16) * (d.up ? 4 : 1);
     if (c->low_latency && tiles < opt(OPT_RTILE_LL_MIN)) return 0;
   }
   const int es = bf ? 2 : 4, gran = bf ? 8 : 4;
@@ -2685,6 +2688,16 @@ int se_profile_report(se_ctx* c, char* buf, size_t cap) {
     char t[384];
     snprintf(t, sizeof t, "%s{\"layer\": \"%s\", \"launches\": %ld, \"total_ms\": %.6f, \"flops\": %.6e, \"flops_executed\": %.6e}",
              first ? "" : ", ", k.c_str(), cnt[k], agg[k].first, agg[k].second, aggx[k]);
+    s += t;
+    first = false;
+  }
+  s += "], \"launches\": [";
+  // every record in launch order, with the kernel form the dispatcher chose (Profiler::Rec::form): what the tests read
+  first = true;
+  for (auto& r : c->prof.recs) {
+    char t[256];
+    snprintf(t, sizeof t, "%s{\"form\": \"%s\", \"kernel\": \"%s\", \"layer\": \"%s\", \"workgroups\": %ld}", first ? "" : ", ",
+             r.form ? r.form : "?", prof_label_name(r.label), r.name ? r.name : "", r.blocks);
     s += t;
     first = false;
   }

@@ -1317,7 +1317,7 @@ static hipError_t launch_attention_v2_t(const AttParams& p0, hipStream_t st) {
       }
       set_launch_cost(alg_flops, alg_bytes, nullptr, 2.0 * (double)grid.x * grid.y * grid.z * (PT * 64.0) * (NT * 16.0) * 384.0);
       set_launch_grid((long)grid.x * grid.y * grid.z);
-      ProfScope ps_(st, PL_ATT_SCORE);
+      ProfScope ps_(st, PL_ATT_SCORE, p.sym ? "att_pair_sym" : "att_pair_all");
       hipLaunchKernelGGL((att2_pair_kernel<NT, PT, BF16>), grid, dim3(256), LDS, st, p);
     } else {          // one or a few small images: 128 queries x 32 keys per workgroup, 4x the workgroups (same k order: same bits)
       constexpr int NT = 2, PT = 2;
@@ -1335,7 +1335,7 @@ static hipError_t launch_attention_v2_t(const AttParams& p0, hipStream_t st) {
       }
       set_launch_cost(alg_flops, alg_bytes, nullptr, 2.0 * (double)grid.x * grid.y * grid.z * (PT * 64.0) * (NT * 16.0) * 384.0);
       set_launch_grid((long)grid.x * grid.y * grid.z);
-      ProfScope ps_(st, PL_ATT_SCORE);
+      ProfScope ps_(st, PL_ATT_SCORE, p.sym ? "att_pair_sym" : "att_pair_all");
       hipLaunchKernelGGL((att2_pair_kernel<NT, PT, BF16>), grid, dim3(256), LDS, st, p);
     }
   }
@@ -1360,9 +1360,10 @@ static hipError_t launch_attention_v2_t(const AttParams& p0, hipStream_t st) {
   } while (0)
     {
       const long rows = tile_order_count(p.B, p.hs, p.ws);
-      ProfScope ps_(st, PL_ATT_SOFTMAX);
+      const bool st_lds = lds_form && stats_lds && (p.e16 || p.Rp > 1024);
+      ProfScope ps_(st, PL_ATT_SOFTMAX, st_lds ? "att_stats_lds" : "att_stats_r3");
       const dim3 grid((unsigned)((rows + 3) / 4));
-      if (lds_form && stats_lds && (p.e16 || p.Rp > 1024)) {      // (R <= 1024: the register kernel is as fast, 44 vs 46 us)
+      if (st_lds) {      // (R <= 1024: the register kernel is as fast, 44 vs 46 us)
         if (p.e16) { if (p.wc <= 64) SE_LAUNCH_STATS_LDS(true, 10); else SE_LAUNCH_STATS_LDS(true, 14); }
         else { if (p.wc <= 64) SE_LAUNCH_STATS_LDS(false, 20); else SE_LAUNCH_STATS_LDS(false, 26); }
       } else if (p.Rp <= 64 * 16) hipLaunchKernelGGL((att2_stats_kernel<16, BF16>), grid, dim3(256), 0, st, p);
@@ -1371,7 +1372,7 @@ static hipError_t launch_attention_v2_t(const AttParams& p0, hipStream_t st) {
     }
     {
       const long rows = tile_order_count(p.B, p.hc, p.wc);
-      ProfScope ps_(st, PL_ATT_BOXSUM);
+      ProfScope ps_(st, PL_ATT_BOXSUM, lds_form ? "att_ptilde_lds" : "att_ptilde_r3");
       const dim3 grid((unsigned)((rows + 3) / 4));
       if (lds_form) {
         bool done = false;
@@ -1390,7 +1391,7 @@ static hipError_t launch_attention_v2_t(const AttParams& p0, hipStream_t st) {
   } else {
     {
       const long rows = tile_order_count(p.B, p.hs, p.ws);
-      ProfScope ps_(st, PL_ATT_SOFTMAX);
+      ProfScope ps_(st, PL_ATT_SOFTMAX, p.Rp <= 64 * 64 ? "att_softmax_reg" : "att_softmax_wide");
       const dim3 grid((unsigned)((rows + 3) / 4));
       if (p.Rp <= 64 * 16) hipLaunchKernelGGL((att2_softmax_reg_kernel<16, BF16>), grid, dim3(256), 0, st, p);
       else if (p.Rp <= 64 * 64) hipLaunchKernelGGL((att2_softmax_reg_kernel<64, BF16>), grid, dim3(256), 0, st, p);

@@ -271,7 +271,7 @@ DEVFN unsigned clear_locked(unsigned sel, unsigned lk) {
 struct ProfScope {
   hipStream_t st;
   int idx = -1;
-  ProfScope(hipStream_t s, int label);
+  ProfScope(hipStream_t s, int label, const char* form = nullptr);      // form: a static string (nullptr: the label's name)
   ~ProfScope();
 };
 

@@ -285,7 +285,7 @@ __global__ __launch_bounds__(256, WPS) void gconv_kernel(const GConvParams p) {
 }
 
 template <int NT, int PT, bool MIXED, int WPS, bool FAST, bool SPLIT, bool BF16>
-static hipError_t launch_gconv_f(const GConvParams& p, hipStream_t st, int label) {
+static hipError_t launch_gconv_f(const GConvParams& p, hipStream_t st, int label, const char* form) {
   constexpr int PIX = PT * 64;
   constexpr int LDS = 2 * (PIX * 128 + NT * 16 * 128);
   static_assert(PIX * 8 <= 2 * PIX * 128, "row table aliases the X buffers");
@@ -297,7 +297,7 @@ static hipError_t launch_gconv_f(const GConvParams& p, hipStream_t st, int label
   const int grid = p.up2 ? class_tile_grid(tiles) : tiles;
   const int groups = SPLIT ? p.np_full / (NT * 16) : 1;
   set_launch_grid((long)grid * groups);
-  ProfScope ps_(st, label);
+  ProfScope ps_(st, label, form);
   hipLaunchKernelGGL((gconv_kernel<NT, PT, MIXED, WPS, FAST, SPLIT, BF16>), dim3(grid, groups), dim3(256), LDS, st, p);
   return hipGetLastError();
 }
@@ -308,35 +308,47 @@ static bool fast_eligible(const GConvParams& p) {
          (long long)p.B * p.Hin * p.Win * p.C0 * (p.bf16 ? 2 : 4) < (1ll << 31);
 }
 template <int NT, int PT, bool MIXED, int WPS, bool SPLIT = false>
-static hipError_t launch_gconv_t(const GConvParams& p, hipStream_t st, int label) {
+static hipError_t launch_gconv_t(const GConvParams& p, hipStream_t st, int label, const char* form) {
   if (p.bf16)
-    return fast_eligible(p) ? launch_gconv_f<NT, PT, MIXED, WPS, true, SPLIT, true>(p, st, label)
-                            : launch_gconv_f<NT, PT, MIXED, WPS, false, SPLIT, true>(p, st, label);
-  return fast_eligible(p) ? launch_gconv_f<NT, PT, MIXED, WPS, true, SPLIT, false>(p, st, label)
-                          : launch_gconv_f<NT, PT, MIXED, WPS, false, SPLIT, false>(p, st, label);
+    return fast_eligible(p) ? launch_gconv_f<NT, PT, MIXED, WPS, true, SPLIT, true>(p, st, label, form)
+                            : launch_gconv_f<NT, PT, MIXED, WPS, false, SPLIT, true>(p, st, label, form);
+  return fast_eligible(p) ? launch_gconv_f<NT, PT, MIXED, WPS, true, SPLIT, false>(p, st, label, form)
+                          : launch_gconv_f<NT, PT, MIXED, WPS, false, SPLIT, false>(p, st, label, form);
 }
 
 // (A 3-stage LDS ring for the narrow MIXED shapes -- two chunks of DMA in flight, exact vmcnt waits -- was measured
 // and is slower: 66 KiB of LDS leave two instead of three workgroups per CU, N48 2.91 -> 3.38 ms.)
 // Tile shapes (chosen by sweeps).  Shapes with LDS <= 80 KiB and <= 256 registers run two workgroups
 // per CU, so the staging code, LDS-read latency and epilogue of one overlap the MFMAs of the other.
+// the form name of a launch (Profiler::Rec::form): gconv_n<rows>[_small][_up2][_2src][_bf16]
+static const char* gconv_form(int cfg, const GConvParams& p) {
+#define SE_GF(n) n, n "_bf16", n "_2src", n "_2src_bf16", n "_up2", n "_up2_bf16", n "_up2_2src", n "_up2_2src_bf16"
+#define SE_GS(n) { SE_GF(n), SE_GF(n "_small") }
+  static const char* const names[4][16] = {SE_GS("gconv_n192"), SE_GS("gconv_n96"), SE_GS("gconv_n48"), SE_GS("gconv_n24")};
+#undef SE_GS
+#undef SE_GF
+  if (cfg < 0 || cfg > 3) return nullptr;
+  return names[cfg][(p.small_grid ? 8 : 0) | (p.up2 ? 4 : 0) | (p.C0g != p.CG ? 2 : 0) | (p.bf16 ? 1 : 0)];
+}
+
 hipError_t launch_gconv(int cfg, const GConvParams& p, hipStream_t st) {
+  const char* form = gconv_form(cfg, p);
   if (p.small_grid) {
     // low-latency shapes: 64-pixel tiles; the wide layers also split their rows over blockIdx.y (one feature tile + its
     // gate tile per workgroup): 6x / 3x more workgroups, each a sixth / third as long
     switch (cfg) {
-      case GC_N192: return launch_gconv_t<2, 1, false, 4, true>(p, st, PL_GCONV_N192);
-      case GC_N96: return launch_gconv_t<2, 1, false, 4, true>(p, st, PL_GCONV_N96);
-      case GC_N48: return launch_gconv_t<3, 1, true, 4>(p, st, PL_GCONV_N48);
-      case GC_N24: return launch_gconv_t<2, 1, true, 4>(p, st, PL_GCONV_N24);
+      case GC_N192: return launch_gconv_t<2, 1, false, 4, true>(p, st, PL_GCONV_N192, form);
+      case GC_N96: return launch_gconv_t<2, 1, false, 4, true>(p, st, PL_GCONV_N96, form);
+      case GC_N48: return launch_gconv_t<3, 1, true, 4>(p, st, PL_GCONV_N48, form);
+      case GC_N24: return launch_gconv_t<2, 1, true, 4>(p, st, PL_GCONV_N24, form);
     }
     return hipErrorInvalidValue;
   }
   switch (cfg) {
-    case GC_N192: return launch_gconv_t<12, 2, false, 2>(p, st, PL_GCONV_N192);
-    case GC_N96: return launch_gconv_t<6, 3, false, 2>(p, st, PL_GCONV_N96);
-    case GC_N48: return launch_gconv_t<3, 2, true, 2>(p, st, PL_GCONV_N48);
-    case GC_N24: return launch_gconv_t<2, 2, true, 2>(p, st, PL_GCONV_N24);
+    case GC_N192: return launch_gconv_t<12, 2, false, 2>(p, st, PL_GCONV_N192, form);
+    case GC_N96: return launch_gconv_t<6, 3, false, 2>(p, st, PL_GCONV_N96, form);
+    case GC_N48: return launch_gconv_t<3, 2, true, 2>(p, st, PL_GCONV_N48, form);
+    case GC_N24: return launch_gconv_t<2, 2, true, 2>(p, st, PL_GCONV_N24, form);
   }
   return hipErrorInvalidValue;
 }

@@ -23,8 +23,10 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
                  PL_JPG2_ROWS, PL_COUNT };
 const char* prof_label_name(int l);
+// Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
+// know which kernel the dispatcher chose; the label's name where the launcher has one form only
 struct Profiler {
-  struct Rec { int label; const char* name; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
+  struct Rec { int label; const char* name; const char* form; double flops; double exec_flops; double bytes; long blocks; hipEvent_t a, b; };
   std::vector<Rec> recs;
   std::vector<hipEvent_t> pool;   // pre-created events (se_profile_enable), handed out two per launch
   size_t used = 0;

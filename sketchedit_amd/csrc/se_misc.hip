@@ -113,7 +113,7 @@ const char* prof_label_name(int l) {
   return (l >= 0 && l < PL_COUNT) ? n[l] : "?";
 }
 
-ProfScope::ProfScope(hipStream_t s, int label) : st(s) {
+ProfScope::ProfScope(hipStream_t s, int label, const char* form) : st(s) {
   Profiler* p = g_prof;
   const double fl = g_next_flops, by = g_next_bytes, ex = g_next_exec;
   const char* nm = g_next_name;
@@ -123,7 +123,7 @@ ProfScope::ProfScope(hipStream_t s, int label) : st(s) {
   g_next_name = nullptr;
   if (!p || !p->on) return;
   Profiler::Rec r;
-  r.label = label; r.name = nm; r.flops = fl; r.exec_flops = ex; r.bytes = by; r.blocks = nb;
+  r.label = label; r.name = nm; r.form = form ? form : prof_label_name(label); r.flops = fl; r.exec_flops = ex; r.bytes = by; r.blocks = nb;
   // events come from a pool created at se_profile_enable(): creating them here cost ~10 us of host time per launch,
   // let the GPU run dry between kernels and inflated the measured durations of short kernels
   if (p->used + 2 > p->pool.size()) return;
@@ -704,7 +704,7 @@ __global__ __launch_bounds__(768) void vecbias_kernel(const float* __restrict__ 
 }
 hipError_t launch_vecbias(const float* wv, const float* vec, float* T, int B, int C1, hipStream_t st, int round_vec) {
   if (C1 % 8) return hipErrorInvalidValue;
-  ProfScope ps_(st, PL_COLREDUCE);
+  ProfScope ps_(st, PL_COLREDUCE, "vecbias");
   hipLaunchKernelGGL(vecbias_kernel, dim3(B, 2), dim3(768), 0, st, wv, vec, T, C1, round_vec);
   return hipGetLastError();
 }

@@ -236,7 +236,7 @@ hipError_t launch_rconv16(const RConvParams& p, hipStream_t st) {
   if (e != hipSuccess) return e;
   const int grid = p.B * p.d * (p.dual ? p.d / 2 : p.d) * p.ty * p.tx;
   set_launch_grid(grid);
-  ProfScope ps_(st, PL_GCONV_N192);
+  ProfScope ps_(st, PL_GCONV_N192, p.dual ? "rconv16_dual" : "rconv16");
   hipLaunchKernelGGL(rconv16b_kernel, dim3(grid), dim3(256), LDS, st, p);
   return hipGetLastError();
 }

@@ -202,7 +202,7 @@ static hipError_t launch_rconv96_t(const RConv96Params& p, hipStream_t st) {
   const int tiles = p.B * p.ty * p.tx;
   const int grid = UP ? class_tile_grid(tiles) : tiles;
   set_launch_grid(grid);
-  ProfScope ps_(st, PL_GCONV_N96);
+  ProfScope ps_(st, PL_GCONV_N96, UP ? "rconv96_up" : STRIDE == 2 ? "rconv96_s2" : CG == 3 ? "rconv96_c24" : "rconv96");
   hipLaunchKernelGGL((rconv96_kernel<CG, P, KW, UP, STRIDE>), dim3(grid), dim3(256), LDS, st, p);
   return hipGetLastError();
 }

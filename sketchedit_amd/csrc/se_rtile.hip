@@ -545,7 +545,7 @@ static hipError_t launch_rtile_dense5w(const RTileParams& p, hipStream_t st) {
   if (e != hipSuccess) return e;
   const int tiles = p.B * p.ty * p.tx;
   set_launch_grid(tiles);
-  ProfScope ps_(st, PL_GCONV_N48);
+  ProfScope ps_(st, PL_GCONV_N48, "rtile_dense5w");
   hipLaunchKernelGGL((rtile_dense5w_kernel<CD>), dim3(tiles), dim3(256), LDS, st, p);
   return hipGetLastError();
 }
@@ -558,7 +558,7 @@ static hipError_t launch_rtile_dense5(const RTileParams& p, hipStream_t st) {
   if (e != hipSuccess) return e;
   const int tiles = p.B * p.ty * p.tx;
   set_launch_grid(tiles);
-  ProfScope ps_(st, PL_GCONV_N48);
+  ProfScope ps_(st, PL_GCONV_N48, "rtile_dense5");
   hipLaunchKernelGGL((rtile_dense5_kernel<CD>), dim3(tiles), dim3(256), LDS, st, p);
   return hipGetLastError();
 }
@@ -573,7 +573,7 @@ static hipError_t launch_rtile_t(const RTileParams& p, hipStream_t st, int label
   const int tiles = p.B * p.ty * p.tx;
   const int grid = p.up2 ? class_tile_grid(tiles) : tiles;
   set_launch_grid(grid);
-  ProfScope ps_(st, label);
+  ProfScope ps_(st, label, D4 ? "rtile_bf16_d4" : BF16 ? (p.up2 ? "rtile_bf16_up2" : "rtile_bf16") : (p.up2 ? "rtile_up2" : "rtile"));
   hipLaunchKernelGGL((rtile_kernel<NT, PT, BF16, D4>), dim3(grid), dim3(256), lds, st, p);
   return hipGetLastError();
 }

@@ -482,7 +482,7 @@ hipError_t launch_rtilew(const RTileParams& p, hipStream_t st) {
   const int cus = cu_count();
   const int grid = nblk < cus ? nblk : cus;      // persistent: one workgroup per CU (147 KB of LDS), each walks nblk / grid blocks
   set_launch_grid(grid);
-  ProfScope ps_(st, PL_GCONV_N24);
+  ProfScope ps_(st, PL_GCONV_N24, "rtilew");
   hipLaunchKernelGGL(rtilew_kernel, dim3(grid), dim3(512), LDS, st, p);
   return hipGetLastError();
 }
@@ -497,7 +497,7 @@ hipError_t launch_rtilew2(const RTileParams& p, hipStream_t st) {
   const int cus = cu_count();
   const int grid = nblk < cus ? nblk : cus;
   set_launch_grid(grid);
-  ProfScope ps_(st, PL_GCONV_N24);
+  ProfScope ps_(st, PL_GCONV_N24, "rtilew2");
   hipLaunchKernelGGL(rtilew2_kernel, dim3(grid), dim3(512), LDS, st, p);
   return hipGetLastError();
 }

@@ -447,7 +447,7 @@ static hipError_t launch_wino24_t(const WinoParams& p, hipStream_t st) {
   }
   const int grid = (p.total_tiles + 31) / 32;
   set_launch_grid(grid);
-  ProfScope ps_(st, PL_WINO_N192);
+  ProfScope ps_(st, PL_WINO_N192, CIN48 ? "wino24_c48" : NCHK == 6 ? "wino24_2src" : "wino24");
   hipLaunchKernelGGL((wino24_kernel<NCHK, CIN48>), dim3(grid), dim3(512), LDS, st, p);
   return hipGetLastError();
 }

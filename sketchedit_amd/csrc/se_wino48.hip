@@ -400,7 +400,7 @@ static hipError_t launch_wino48_t(const WinoParams& p, hipStream_t st) {
   }
   const int grid = (p.total_tiles + TILES - 1) / TILES;
   set_launch_grid(grid);
-  ProfScope ps_(st, PL_WINO_N96);
+  ProfScope ps_(st, PL_WINO_N96, CIN == 24 ? "wino48_c24" : "wino48");
   hipLaunchKernelGGL((wino48_kernel<TILES, CIN>), dim3(grid), dim3(TILES * 4), LDS, st, p);
   return hipGetLastError();
 }

@@ -289,7 +289,7 @@ hipError_t launch_winoup(const WinoParams& p, hipStream_t st) {
   }
   const int grid = class_tile_grid((p.total_tiles + TILES - 1) / TILES);
   set_launch_grid(grid);
-  ProfScope ps_(st, PL_WINO_UP96);
+  ProfScope ps_(st, PL_WINO_UP96, "winoup");
   hipLaunchKernelGGL(winoup_kernel<TILES>, dim3(grid), dim3(TILES * 4), LDS, st, p);
   return hipGetLastError();
 }

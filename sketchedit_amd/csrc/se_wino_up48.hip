@@ -304,7 +304,7 @@ hipError_t launch_winoup48(const WinoParams& p, hipStream_t st) {
   }
   const int grid = class_tile_grid((p.total_tiles + TILES - 1) / TILES);
   set_launch_grid(grid);
-  ProfScope ps_(st, PL_GCONV_N48);
+  ProfScope ps_(st, PL_GCONV_N48, "winoup48");
   hipLaunchKernelGGL(winoup48_kernel, dim3(grid), dim3(TILES * 4), LDS, st, p);
   return hipGetLastError();
 }

@@ -1,4 +1,5 @@
-"""Shared by the GPU parity tests: the composite the oracle gives FOR THE HARD MASK THE GPU PIPELINE USED.
+"""Shared by the GPU parity tests: the one-spacing rule of a bf16 layer (layer_close), and the composite the oracle gives FOR
+THE HARD MASK THE GPU PIPELINE USED.
 
 `mask_inpaint = (mask > 0.5)` (reference models/editline2_model.py:347) turns fp32 noise on a logit that sits on the
 threshold into a different INPUT of netG.  Instead of skipping the composite comparison when a pixel flipped (a guard
@@ -23,3 +24,18 @@ def composed_for_hard_mask(O, WG, img, sk, ref_mask, ref_hard, ref_composed, gpu
     with torch.no_grad():
         _, fine = O.netG_forward(WG, img, img, gpu_hard, gpu_hard, sk, **netg_kw)
     return fine * ref_mask + img * (1 - ref_mask), flips
+
+
+def layer_close(y, ref):
+    """One bf16 layer (same bf16 inputs and weights, fp32 accumulation, ONE rounding of the result) against its reference: the
+    two can differ by the accumulation order only, i.e. by at most one bf16 spacing of the result (2^-8 .. 2^-7 of |y|) where
+    a value sits on a rounding boundary -- |d| <= 2^-7 |y| + 1e-6 on EVERY element -- and rarely: mean |d| < 2e-4
+    (tests/test_gpu_bf16.py, "Tolerances")."""
+    y = (y.detach().cpu().numpy() if hasattr(y, "detach") else np.asarray(y)).astype(np.float64)
+    ref = (ref.detach().cpu().numpy() if hasattr(ref, "detach") else np.asarray(ref)).astype(np.float64)
+    assert y.shape == ref.shape
+    bad = np.abs(y - ref) > (2.0 ** -7) * np.abs(ref) + 1e-6
+    assert not bad.any(), "%d of %d values off by more than one bf16 spacing, worst %.3e" % (
+        bad.sum(), bad.size, np.abs(y - ref).max())
+    # and the roundings are unbiased / rare: the mean difference is far below one spacing
+    assert np.abs(y - ref).mean() < 2e-4 * max(1.0, np.abs(ref).mean())

@@ -24,6 +24,8 @@ import pytest
 import torch
 
 from sketchedit_amd import synth
+from forms_util import conv_as
+from parity_util import layer_close as _layer_close
 
 pytestmark = pytest.mark.gpu
 
@@ -39,16 +41,6 @@ def _cuda(a):
 
 def _np(a):
     return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-
-
-def _layer_close(y, ref):
-    y, ref = _np(y).astype(np.float64), _np(ref).astype(np.float64)
-    assert y.shape == ref.shape
-    bad = np.abs(y - ref) > (2.0 ** -7) * np.abs(ref) + 1e-6
-    assert not bad.any(), "%d of %d values off by more than one bf16 spacing, worst %.3e" % (
-        bad.sum(), bad.size, np.abs(y - ref).max())
-    # and the roundings are unbiased / rare: the mean difference is far below one spacing
-    assert np.abs(y - ref).mean() < 2e-4 * max(1.0, np.abs(ref).mean())
 
 
 @pytest.fixture(scope="module")
@@ -105,7 +97,8 @@ def test_op_rconv16_raw_tile_bf16(eng, case):
     w = synth.uniform(41, "rc.w%s" % (case,), (192, 96, 3, 3), -a, a)
     b = synth.uniform(41, "rc.b%s" % (case,), (192,), -0.3, 0.3)
     x = synth.uniform(41, "rc.x%s" % (case,), (2, 96, H, W), -1, 1)
-    y = eng.gated_conv2d(_cuda(x), w, b, stride=1, rate=d, act=act, bf16=True)
+    form = "rconv16" if H // d >= 12 and W // d >= 12 else "rconv16_dual"
+    y = conv_as(eng, form, _cuda(x), w, b, stride=1, rate=d, act=act, bf16=True)
     _layer_close(y, O.gated_conv(torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), 1, d, act, BF))
 
 
@@ -123,7 +116,8 @@ def test_op_rconv96_raw_tile_bf16(eng, case):
     w = synth.uniform(43, "r96.w%s" % (case,), (96, cin, 3, 3), -a, a)
     b = synth.uniform(43, "r96.b%s" % (case,), (96,), -0.3, 0.3)
     x = synth.uniform(43, "r96.x%s" % (case,), (2, cin, H, W), -1, 1)
-    y = eng.gated_conv2d(_cuda(x), w, b, stride=1, rate=1, act=act, upsample=up, bf16=True)
+    form = "rconv96_up" if up else "rconv96" if cin == 48 else "rconv96_c24"
+    y = conv_as(eng, form, _cuda(x), w, b, stride=1, rate=1, act=act, upsample=up, bf16=True)
     tw, tb, tx = torch.from_numpy(w), torch.from_numpy(b), torch.from_numpy(x)
     if up:
         ref = O.gated_deconv(tx, tw, tb, BF)       # pre-summed sub-pixel weights are rounded once (see above)
@@ -134,6 +128,9 @@ def test_op_rconv96_raw_tile_bf16(eng, case):
 
 @pytest.mark.parametrize("kind", ["tensor", "vector"])
 def test_op_two_source_conv_bf16(eng, kind):
+    """conv11 / allconv11 in bf16 mode at 14x18: the tensor source through the gather-GEMM's two-source gather, the vector
+    source folded into a bias table (launch_vecbias with the vector rounded to bf16) in front of the raw-tile kernel on the
+    first source alone (se_rconv16.hip; h, w >= 12)."""
     from oracle import sketchedit_oracle as O
     H, W = 14, 18
     a = 1.5 / np.sqrt(192 * 9)
@@ -146,7 +143,8 @@ def test_op_two_source_conv_bf16(eng, kind):
     else:
         x1 = synth.uniform(37, "b16two.v", (2, 96), -1, 1)
         cat = np.concatenate([x, np.broadcast_to(x1[:, :, None, None], (2, 96, H, W))], 1)
-    y = eng.gated_conv2d(_cuda(x), w, b, x1=_cuda(x1), bf16=True)
+    form = "gconv_n192_2src_bf16" if kind == "tensor" else ["vecbias", "rconv16"]
+    y = conv_as(eng, form, _cuda(x), w, b, x1=_cuda(x1), bf16=True)
     _layer_close(y, O.gated_conv(torch.from_numpy(cat), torch.from_numpy(w), torch.from_numpy(b), 1, 1, "elu", BF))
 
 

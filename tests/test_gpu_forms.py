@@ -1,0 +1,177 @@
+"""Every kernel form of a gated convolution on its own: the dispatcher (run_gconv / run_gconv16 / try_rtile,
+sketchedit_amd/csrc/se_api.hip) must choose the form the table says (tests/forms_util.py FORMS), and that form
+must compute the layer -- against a float64 reference of the same operation on the CPU, every element compared.
+
+A row whose dispatch condition is narrowed by mistake fails here on the form's NAME (Engine.launch_forms()), where a value
+comparison alone would go on passing on the fallback gather-GEMM; a widened condition fails at the row of the neighbour that
+must take over.  The whole-forward tests at the end assert that production launches no conv form without a row, and that the
+choice depends on image size and mode only, never on the batch.
+"""
+import numpy as np
+import pytest
+import torch
+
+from sketchedit_amd import synth
+import forms_util as FU
+from parity_util import layer_close
+
+pytestmark = pytest.mark.gpu
+
+FLAGS = 1 | 2 | 16
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from sketchedit_amd._lib import Engine
+    e = Engine(0)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def eng_w():
+    from sketchedit_amd._lib import Engine
+    e = Engine(0)
+    e.load_state_dict("M", synth.make_state_dict("M", 0))
+    e.load_state_dict("G", synth.make_state_dict("G", 0))
+    assert e.weights_ready()
+    yield e
+    e.close()
+
+
+def _check_values(r, y, ref):
+    got = y.detach().cpu().numpy().astype(np.float64)
+    want = ref.numpy()
+    assert got.shape == want.shape, (got.shape, want.shape)
+    md = float(np.abs(got - want).max())
+    print("%s: max-abs %.3e" % (FU.row_id(r), md))
+    if not r.mode.startswith("bf16") or r.act is None:
+        assert md < FU.TOL_OP
+    elif r.up:
+        assert md < FU.TOL_BF16_DECONV
+    else:
+        layer_close(got, want)
+
+
+def _run_row(eng, r, shape, seopt, expect=None):
+    for name, v in r.switches.items():
+        seopt.set(name, v)
+    x, x1, w, b = FU.make_inputs(r, shape)
+    y, launches = FU.run(eng, r, x, x1, w, b)
+    # (a) dispatch: the conv launches are exactly the expected form (where folded: vecbias, then the form)
+    want = list(r.pre) + [r.form] if expect is None else expect
+    assert FU.conv_launches(launches) == want, (FU.row_id(r, shape), launches)
+    # (b) values
+    _check_values(r, y, FU.reference(r, x, x1, w, b))
+
+
+CASES = FU.cases()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[FU.row_id(r, s) for r, s in CASES])
+def test_form_dispatch_and_values(eng, case, seopt):
+    r, shape = case
+    _run_row(eng, r, shape, seopt)
+
+
+@pytest.mark.parametrize("t", FU.LL_THRESHOLDS, ids=[FU.row_id(t.row) for t in FU.LL_THRESHOLDS])
+def test_low_latency_threshold(eng, t, seopt):
+    """Low-latency mode: with the threshold switch at the workgroup (tile) count per image of the shape the Winograd / raw-tile
+    form runs, one above it the small-grid gather-GEMM; both against the reference."""
+    r = t.row._replace(mode="bf16-lowlat" if t.row.mode == "bf16" else "lowlat")
+    shape = r.shapes[-1]
+    seopt.set(t.switch, t.count)
+    _run_row(eng, r, shape, seopt)
+    seopt.set(t.switch, t.count + 1)
+    _run_row(eng, r, shape, seopt, expect=[t.below])
+
+
+@pytest.mark.parametrize("B", [1, 2, 3])
+def test_low_latency_choice_ignores_the_batch(eng, B, seopt):
+    """The thresholds count workgroups PER IMAGE (se_api.hip, run_gconv): 24 -> 24 at 18x34 is 9 raw tiles per image whatever
+    the batch, so SE_RTILE_LL_MIN = 9 runs rtilew2 and 10 the small-grid gather-GEMM at every B (try_rtile once counted B x 9)."""
+    r = FU.row("rtilew2", 24, 24, [(18, 34)], mode="lowlat")
+    x, x1, w, b = FU.make_inputs(r, (18, 34), B=B)
+    ref = FU.reference(r, x, x1, w, b)
+    for limit, form in ((9, "rtilew2"), (10, "gconv_n24_small")):
+        seopt.set("SE_RTILE_LL_MIN", limit)
+        y, launches = FU.run(eng, r, x, x1, w, b)
+        assert FU.conv_launches(launches) == [form], (B, limit, launches)
+        _check_values(r, y, ref)
+
+
+def test_launch_forms_turns_the_profiler_off_when_the_body_raises(eng):
+    r = FU.row("rtilew2", 24, 24, [(2, 2)])
+    x, x1, w, b = FU.make_inputs(r, (2, 2))
+    with pytest.raises(RuntimeError):
+        with eng.launch_forms() as launches:
+            raise RuntimeError("body")
+    assert launches == []
+    eng.gated_conv2d(torch.from_numpy(x).cuda(), w, b)                   # profiler off: nothing recorded
+    assert eng.profile_report()["launches"] == []
+    _, launches = FU.run(eng, r, x, x1, w, b)                             # ... and a later scope starts from no records
+    assert FU.conv_launches(launches) == ["rtilew2"]
+
+
+# ---- the forward runs nothing without a per-op row ----------------------------------------------------------------------------
+MODES = ["default", "lowlat", "conservative", "bf16"]
+
+
+def _forward_launches(eng_w, B, H, W, mode):
+    img, sk = synth.make_inputs(B, H, W, seed=1234)
+    ci, cs = torch.from_numpy(img).cuda(), torch.from_numpy(sk).cuda()
+    eng_w.set_precision("bf16" if mode == "bf16" else "f32")
+    eng_w.set_conservative(mode == "conservative")
+    try:
+        with eng_w.launch_forms() as launches:
+            r = eng_w.inference(ci, cs, FLAGS, low_latency=(mode == "lowlat"))
+        assert torch.isfinite(r["composed"]).all()
+    finally:
+        eng_w.set_precision("f32")
+        eng_w.set_conservative(False)
+    return [(layer, form) for form, layer in launches]
+
+
+def _netM_part(seq):
+    """The records of netM: the forward runs netM first, and the two nets share layer names (conv1 ... conv17) -- netG starts at
+    the second conv1 or at the first layer only it has."""
+    seen_conv1 = False
+    for i, (layer, _) in enumerate(seq):
+        if layer.startswith(("wconv", "xconv", "pmconv", "allconv")) or (layer == "conv1" and seen_conv1):
+            return seq[:i]
+        seen_conv1 = seen_conv1 or layer == "conv1"
+    return seq
+
+
+def _check_forward(seq, mode):
+    known = FU.known_forms()
+    convs = [(layer, form) for layer, form in seq if form.startswith(FU.CONV_PREFIXES)]
+    assert len(convs) > 50                                                # (not vacuous: netM and netG have some seventy convs)
+    missing = sorted({form for _, form in convs} - known)
+    assert not missing, "conv forms without a row in forms_util.FORMS: %s" % missing
+    if mode == "conservative":
+        netm = _netM_part(seq)
+        assert any(layer.startswith("conv_mask_") for layer, _ in netm) and any(form == "wino" for _, form in netm)
+        bad = [(layer, form) for layer, form in netm if form.startswith("wino24")]
+        assert not bad, bad
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("size", [(64, 64), (40, 72)], ids=lambda s: "%dx%d" % s)
+def test_forward_forms_have_rows_and_ignore_the_batch(eng_w, size, mode):
+    """Every conv form a forward launches has a row in FORMS; the (layer, form) sequence of B = 3 is that of B = 1 (the kernel a
+    layer runs depends on image size and mode only, se_api.hip run_gconv); SE_FLAG_CONSERVATIVE keeps netM off wino24."""
+    H, W = size
+    one = _forward_launches(eng_w, 1, H, W, mode)
+    three = _forward_launches(eng_w, 3, H, W, mode)
+    _check_forward(one, mode)
+    assert three == one
+    if mode == "conservative" and W % 16 == 0:      # (the flag has something to select: the default mode runs netM's 96 -> 192
+        #                                                layers on wino24 where the quarter-resolution width is a multiple of 4)
+        dflt = _forward_launches(eng_w, 1, H, W, "default")
+        assert any(form.startswith("wino24") for _, form in _netM_part(dflt))
+
+
+@pytest.mark.parametrize("mode", ["default", "bf16"])
+def test_forward_forms_have_rows_256(eng_w, mode):
+    _check_forward(_forward_launches(eng_w, 1, 256, 256, mode), mode)

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from sketchedit_amd import synth
+from forms_util import conv_as
 from parity_util import composed_for_hard_mask
 
 pytestmark = pytest.mark.gpu
@@ -132,7 +133,7 @@ def test_op_winograd_path_vs_oracle(eng, case, seopt):
     w = synth.uniform(13, "wino.w%s" % (case,), (192, 96, 3, 3), -a, a)
     b = synth.uniform(13, "wino.b%s" % (case,), (192,), -0.3, 0.3)
     x = synth.uniform(13, "wino.x%s" % (case,), (3, 96, H, W), -1, 1)
-    y = eng.gated_conv2d(_cuda(x), w, b, stride=1, rate=d, act=act)
+    y = conv_as(eng, "wino", _cuda(x), w, b, stride=1, rate=d, act=act)
     ref = O.gated_conv(torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), 1, d, act)
     assert _md(y, ref) < TOL_OP
 
@@ -154,16 +155,16 @@ def test_op_winograd_f43_path_vs_oracle(eng, case, seopt):
     b = synth.uniform(17, "w24.b%s" % (case,), (192,), -0.3, 0.3)
     x = synth.uniform(17, "w24.x%s" % (case,), (3, 96, H, W), -1, 1)
     seopt.set("SE_WINOGRAD_F43", "1")
-    y = eng.gated_conv2d(_cuda(x), w, b, stride=1, rate=d, act=act)
+    y = conv_as(eng, "wino24", _cuda(x), w, b, stride=1, rate=d, act=act)
     seopt.set("SE_WINOGRAD_F43", "0")
-    y22 = eng.gated_conv2d(_cuda(x), w, b, stride=1, rate=d, act=act)
+    y22 = conv_as(eng, "wino", _cuda(x), w, b, stride=1, rate=d, act=act)
     ref = O.gated_conv(torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), 1, d, act)
     assert _md(y, ref) < TOL_OP and _md(y22, ref) < TOL_OP
     assert _md(y, y22) < 2e-5
     # larger activations (|x| up to 8: the range the F(4,3) constants amplify): relative bound
     x8 = x * 8.0
     seopt.set("SE_WINOGRAD_F43", "1")
-    y8 = eng.gated_conv2d(_cuda(x8), w, b, stride=1, rate=d, act=act)
+    y8 = conv_as(eng, "wino24", _cuda(x8), w, b, stride=1, rate=d, act=act)
     ref8 = O.gated_conv(torch.from_numpy(x8), torch.from_numpy(w), torch.from_numpy(b), 1, d, act)
     assert _md(y8, ref8) < TOL_OP * max(1.0, float(ref8.abs().max()))
 
@@ -180,9 +181,9 @@ def test_op_winograd_f43_48_channel_source_vs_oracle(eng, size, seopt):
     x = synth.uniform(19, "w24c48.x%s" % (size,), (3, 48, H, W), -1, 1)
     ref = O.gated_conv(torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), 1, 1, "elu")
     seopt.set("SE_WINOGRAD_F43", "1")
-    y = eng.gated_conv2d(_cuda(x), w, b)
+    y = conv_as(eng, "wino24_c48", _cuda(x), w, b)
     seopt.set("SE_WINOGRAD_F43", "0")
-    yd = eng.gated_conv2d(_cuda(x), w, b)
+    yd = conv_as(eng, "gconv_n192", _cuda(x), w, b)
     assert _md(y, ref) < TOL_OP and _md(yd, ref) < TOL_OP
     assert _md(y, yd) < 2e-5 and _md(y, yd) > 0.0          # (two different kernels ran)
 
@@ -205,11 +206,11 @@ def test_op_conv24_winograd_along_x_vs_oracle(eng, case, seopt):
     x = synth.uniform(23, "c24.x%s" % (case,), (2, 24, H, W), -1, 1)
     ref = O.gated_conv(torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), 1, 1, act)
     seopt.set("SE_RTILE_WX", "2")              # default: two-dimensional F(2x2,3x3) where the height is even too
-    y2 = eng.gated_conv2d(_cuda(x), w, b, act=act)
+    y2 = conv_as(eng, "rtilew2" if H % 2 == 0 else "rtilew", _cuda(x), w, b, act=act)
     seopt.set("SE_RTILE_WX", "1")              # F(2,3) along x only
-    y = eng.gated_conv2d(_cuda(x), w, b, act=act)
+    y = conv_as(eng, "rtilew", _cuda(x), w, b, act=act)
     seopt.set("SE_RTILE_WX", "0")              # direct raw-tile kernel
-    yd = eng.gated_conv2d(_cuda(x), w, b, act=act)
+    yd = conv_as(eng, "rtile", _cuda(x), w, b, act=act)
     assert tuple(y.shape) == (2, 12, H, W)
     assert _md(y, ref) < TOL_OP and _md(yd, ref) < TOL_OP and _md(y2, ref) < TOL_OP
     assert 0.0 < _md(y, yd) < 2e-5                      # (different kernels ran)
@@ -231,7 +232,7 @@ def test_op_winograd48_path_vs_oracle(eng, case):
     w = synth.uniform(17, "wino48.w%s" % (case,), (96, 48, 3, 3), -a, a)
     b = synth.uniform(17, "wino48.b%s" % (case,), (96,), -0.3, 0.3)
     x = synth.uniform(17, "wino48.x%s" % (case,), (3, 48, H, W), -1, 1)
-    y = eng.gated_conv2d(_cuda(x), w, b, stride=1, rate=d, act=act)
+    y = conv_as(eng, "wino48", _cuda(x), w, b, stride=1, rate=d, act=act)
     ref = O.gated_conv(torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), 1, d, act)
     assert _md(y, ref) < TOL_OP
 
@@ -248,11 +249,11 @@ def test_op_winograd24_to_96_path_vs_oracle(eng, case, seopt):
     w = synth.uniform(18, "wino24c.w%s" % (case,), (96, 24, 3, 3), -a, a)
     b = synth.uniform(18, "wino24c.b%s" % (case,), (96,), -0.3, 0.3)
     x = synth.uniform(18, "wino24c.x%s" % (case,), (3, 24, H, W), -1, 1)
-    y = eng.gated_conv2d(_cuda(x), w, b, stride=1, rate=d, act=act)
+    y = conv_as(eng, "wino48_c24", _cuda(x), w, b, stride=1, rate=d, act=act)
     ref = O.gated_conv(torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), 1, d, act)
     assert _md(y, ref) < TOL_OP
     seopt.set("SE_WINOGRAD48", 0)
-    yd = eng.gated_conv2d(_cuda(x), w, b, stride=1, rate=d, act=act)
+    yd = conv_as(eng, "gconv_n96", _cuda(x), w, b, stride=1, rate=d, act=act)
     assert _md(yd, ref) < TOL_OP
     if H % (2 * d) == 0 and W % (2 * d) == 0:
         assert 0.0 < _md(y, yd) < 2e-5                  # (different kernels ran)
@@ -273,7 +274,7 @@ def test_op_winograd_upsample_path_vs_oracle(eng, case, cin):
     w = synth.uniform(19, "winoup%d.w%s" % (cin, case), (cin, cin, 3, 3), -a, a)
     b = synth.uniform(19, "winoup%d.b%s" % (cin, case), (cin,), -0.3, 0.3)
     x = synth.uniform(19, "winoup%d.x%s" % (cin, case), (3, cin, H, W), -1, 1)
-    y = eng.gated_conv2d(_cuda(x), w, b, upsample=True, act=act)
+    y = conv_as(eng, "winoup" if cin == 96 else "winoup48", _cuda(x), w, b, upsample=True, act=act)
     xu = torch.from_numpy(x).repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)      # utils.py:47
     ref = O.gated_conv(xu, torch.from_numpy(w), torch.from_numpy(b), 1, 1, act)
     assert tuple(y.shape) == (3, cin // 2, 2 * H, 2 * W)
@@ -288,8 +289,10 @@ TWO_SRC = [("tensor", 16, 16, 1), ("vector", 16, 24, 1), ("vector", 10, 14, 1), 
 def test_op_two_source_conv_vs_oracle(eng, case, ll):
     """conv11 / allconv11 (editline_g.py:166-167,211): 3x3 conv over the virtual concat cat([x, x1]), x1 a tensor
     (patch-match branch) or the pooled style vector broadcast over the image (zero padded at the borders like a
-    tensor).  Even sizes take wino_kernel<6> (se_wino.hip), the 22x18 case and the low-latency mode the direct
-    kernel's two-source gather."""
+    tensor).  Default mode: every size here is even, so the tensor cases take the two-source Winograd kernels -- 16x16 the
+    hybrid wino24_kernel<6> (w % 4 == 0), 22x18 wino_kernel<6> -- and the vector cases the folded form (launch_vecbias, then the
+    single-source wino24 / wino kernel); the direct kernel's two-source gather runs in the low-latency mode only (its
+    default-mode form, odd sizes, is a row of tests/forms_util.py)."""
     from oracle import sketchedit_oracle as O
     kind, H, W, d = case
     a = 1.5 / np.sqrt(192 * 9)
@@ -302,7 +305,9 @@ def test_op_two_source_conv_vs_oracle(eng, case, ll):
     else:
         x1 = synth.uniform(23, "two.v%s" % (case,), (3, 96), -1, 1)
         cat = np.concatenate([x, np.broadcast_to(x1[:, :, None, None], (3, 96, H, W))], 1)
-    y = eng.gated_conv2d(_cuda(x), w, b, stride=1, rate=d, x1=_cuda(x1), low_latency=ll)
+    wino = "wino24" if W % 4 == 0 else "wino"
+    form = "gconv_n192_small_2src" if ll else wino + "_2src" if kind == "tensor" else ["vecbias", wino]
+    y = conv_as(eng, form, _cuda(x), w, b, stride=1, rate=d, x1=_cuda(x1), low_latency=ll)
     ref = O.gated_conv(torch.from_numpy(cat), torch.from_numpy(w), torch.from_numpy(b), 1, d, "elu")
     assert _md(y, ref) < TOL_OP
 
@@ -321,9 +326,9 @@ def test_op_two_source_winograd_forms_vs_oracle(eng, size, seopt):
     x1 = synth.uniform(29, "two24.y%s" % (size,), (3, 96, H, W), -1, 1)
     ref = O.gated_conv(torch.from_numpy(np.concatenate([x, x1], 1)), torch.from_numpy(w), torch.from_numpy(b), 1, 1, "elu")
     seopt.set("SE_WINOGRAD_F43", "1")
-    y24 = eng.gated_conv2d(_cuda(x), w, b, x1=_cuda(x1))
+    y24 = conv_as(eng, "wino24_2src", _cuda(x), w, b, x1=_cuda(x1))
     seopt.set("SE_WINOGRAD_F43", "0")
-    y22 = eng.gated_conv2d(_cuda(x), w, b, x1=_cuda(x1))
+    y22 = conv_as(eng, "wino_2src", _cuda(x), w, b, x1=_cuda(x1))
     assert _md(y24, ref) < TOL_OP and _md(y22, ref) < TOL_OP
     assert _md(y24, y22) < 2e-5
 
@@ -362,31 +367,33 @@ def test_op_vector_source_folded_into_bias(eng, size, seopt):
     cat = np.concatenate([x, np.broadcast_to(v[:, :, None, None], (3, 96, H, W))], 1)
     ref = O.gated_conv(torch.from_numpy(cat), torch.from_numpy(w), torch.from_numpy(b), 1, 1, "elu")
     seopt.set("SE_VECBIAS", "1")
-    folded = eng.gated_conv2d(_cuda(x), w, b, x1=_cuda(v))
+    folded = conv_as(eng, ["vecbias", "wino24"], _cuda(x), w, b, x1=_cuda(v))      # (every width here is a multiple of 4)
     seopt.set("SE_VECBIAS", "0")
-    two = eng.gated_conv2d(_cuda(x), w, b, x1=_cuda(v))
+    two = conv_as(eng, "wino_2src", _cuda(x), w, b, x1=_cuda(v))
     assert _md(folded, ref) < TOL_OP and _md(two, ref) < TOL_OP
     assert _md(folded, two) < 1e-5
 
 
 @pytest.mark.parametrize("case", [(5, 22, 18), (3, 22, 18), (4, 22, 18), (5, 8, 16), (3, 40, 33), (4, 16, 48), (5, 9, 70)], ids=lambda c: "c%d-%dx%d" % c)
 def test_op_first_layer_dense_k_vs_oracle(eng, case, seopt):
-    """The 5x5 first layers whose stored input carries padding channels (5 of NHWC8, 3 of NHWC4) in the dense-K raw-tile form
-    (se_rtile.hip rtile_dense5_kernel: k = tap * cin + channel, dword-granular staging): exact, ragged and single-tile
-    sizes, image borders on every side; against the oracle and against the channel-padded form (SE_RTILE_DENSE=0)."""
+    """The 5x5 first layers whose stored input carries padding channels (5 of NHWC8, 3 of NHWC4) in the dense-K raw-tile forms
+    (se_rtile.hip: k = tap * cin + channel, dword-granular staging) -- at the even widths rtile_dense5w_kernel, its F(2,5)
+    form along x, which is what production runs; at the odd widths (40x33) the direct rtile_dense5_kernel --: exact, ragged
+    and single-tile sizes, image borders on every side; against the oracle and against the channel-padded form
+    (SE_RTILE_DENSE=0).  The direct kernel at even widths: test_op_first_layer_winograd_along_x_vs_oracle (SE_RTILE_D5W=0)."""
     from oracle import sketchedit_oracle as O
     cin, H, W = case
     a = 1.5 / np.sqrt(cin * 25)
     w = synth.uniform(47, "d5.w%s" % (case,), (48, cin, 5, 5), -a, a)
     b = synth.uniform(47, "d5.b%s" % (case,), (48,), -0.3, 0.3)
     x = synth.uniform(47, "d5.x%s" % (case,), (3, cin, H, W), -1, 1)
-    y = eng.gated_conv2d(_cuda(x), w, b)
+    y = conv_as(eng, "rtile_dense5w" if W % 2 == 0 else "rtile_dense5", _cuda(x), w, b)
     ref = O.gated_conv(torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), 1, 1, "elu")
     assert _md(y, ref) < TOL_OP
     seopt.set("SE_RTILE_DENSE", "0")
     # the switch takes effect from the next call on (se_debug_set_option): the channel-padded form sums in another order, so
     # the two results agree to rounding but are not the same bits (odd widths: both calls run the direct dense / padded forms)
-    y2 = eng.gated_conv2d(_cuda(x), w, b)
+    y2 = conv_as(eng, "rtile", _cuda(x), w, b)
     assert _md(y2, ref) < TOL_OP
     assert _md(y, y2) < TOL_OP
     if H * W >= 64:
@@ -407,28 +414,28 @@ def test_op_first_layer_winograd_along_x_vs_oracle(eng, case, seopt):
     x = synth.uniform(59, "d5w.x%s" % (case,), (2, cin, H, W), -1, 1)
     ref = O.gated_conv(torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), 1, 1, "elu")
     seopt.set("SE_RTILE_D5W", "1")
-    y = eng.gated_conv2d(_cuda(x), w, b)
+    y = conv_as(eng, "rtile_dense5w", _cuda(x), w, b)
     seopt.set("SE_RTILE_D5W", "0")
-    yd = eng.gated_conv2d(_cuda(x), w, b)
+    yd = conv_as(eng, "rtile_dense5", _cuda(x), w, b)
     assert _md(y, ref) < TOL_OP and _md(yd, ref) < TOL_OP
     assert 0.0 < _md(y, yd) < 3e-5                      # (two different kernels ran)
     seopt.set("SE_RTILE_D5W", "1")
-    y8 = eng.gated_conv2d(_cuda(x * 8.0), w, b)
+    y8 = conv_as(eng, "rtile_dense5w", _cuda(x * 8.0), w, b)
     ref8 = O.gated_conv(torch.from_numpy(x * 8.0), torch.from_numpy(w), torch.from_numpy(b), 1, 1, "elu")
     assert _md(y8, ref8) < TOL_OP * max(1.0, float(ref8.abs().max()))
 
 
 def test_op_first_layer_dense_k_oversized_batch_keeps_the_kernel_form(eng, seopt):
     """a batch whose first-layer input exceeds the kernel's 32-bit byte offsets runs as sub-launches of the SAME
-    dense-K kernel (not the channel-padded one, which sums in another order): forced here with a small byte limit
-    (SE_TEST_OFFSET_LIMIT), the result is bit-identical to the single launch."""
+    dense-K kernel (at this even width its F(2,5) form, rtile_dense5w; not the channel-padded one, which sums in another order):
+    forced here with a small byte limit (SE_TEST_OFFSET_LIMIT), the result is bit-identical to the single launch."""
     a = 1.5 / np.sqrt(5 * 25)
     w = synth.uniform(61, "dk.w", (48, 5, 5, 5), -a, a)
     b = synth.uniform(61, "dk.b", (48,), -0.3, 0.3)
     x = synth.uniform(61, "dk.x", (5, 5, 24, 40), -1, 1)
-    y1 = eng.gated_conv2d(_cuda(x), w, b)
+    y1 = conv_as(eng, "rtile_dense5w", _cuda(x), w, b)
     seopt.set("SE_TEST_OFFSET_LIMIT", str(2 * 24 * 40 * 8 * 4 + 1))      # two images (stored NHWC8) per sub-launch: 2 + 2 + 1
-    y2 = eng.gated_conv2d(_cuda(x), w, b)
+    y2 = conv_as(eng, ["rtile_dense5w"] * 3, _cuda(x), w, b)
     assert torch.equal(y1, y2)
 
 
