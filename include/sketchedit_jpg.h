@@ -56,7 +56,8 @@ size_t se_jpg_bound(int hs, int ws);
  * one slot of the row bound's size per row); SE_TEST_POISON fills it.  Three launches, no host synchronisation.  Refused before
  * anything is enqueued (non-zero return, se_last_error names the argument, out untouched): a NULL pointer, B < 1 (or > 65535), a
  * side outside [16, 8192], a quality outside [1, 100], a window outside its frame, cap < se_jpg_bound(hs, ws), a short or
- * misaligned workspace, a misaligned sizes_out, out overlapping a frame, the workspace or sizes_out. */
+ * misaligned workspace, a misaligned sizes_out, out overlapping a frame, the workspace or sizes_out.  The call is
+ * se_jpg2_encode_u8 (sketchedit_jpg2.h) with flags = 0 and no tables_out: the same checks, workspace and launches. */
 int se_jpg_encode_u8(se_ctx* ctx, void* stream, const se_window* wins, int B, int hs, int ws, int quality, unsigned char* out,
                      size_t cap, unsigned long long* sizes_out, void* workspace, size_t workspace_bytes);
 size_t se_jpg_encode_u8_workspace_bytes(se_ctx* ctx, int B, int hs, int ws);

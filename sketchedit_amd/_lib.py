@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_png.hip", "se_jpg.hip", "se_jpg2.hip", "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -1025,26 +1025,9 @@ class Engine:
         entropy-coded segment of its baseline JPEG at `quality` 1 .. 100 (include/sketchedit_jpg.h; serve.jpg_from_scan makes
         the file), encoded on the device.  -> (out (B, cap) uint8, sizes (B,) int64), both on the device: out[i, :sizes[i]] is
         image i's segment, and no byte behind it is written.  `out`: a contiguous uint8 tensor of B rows of cap >=
-        jpg_bound(hs, ws) bytes to write into."""
-        import torch
-        hs, ws = (int(v) for v in window_hw)
-        wins = self._windows(frames, origins)
-        B, dev = len(frames), frames[0].device
-        bound = self.jpg_bound(hs, ws)
-        if out is None:
-            out = torch.empty((B, max(bound, 1)), dtype=torch.uint8, device=dev)
-        _check_dev_u8(out)
-        if out.dim() != 2 or out.shape[0] != B:
-            raise SketchEditHipError("jpg_encode_u8: `out` is a (B, cap) uint8 tensor")
-        sizes = torch.empty((B,), dtype=torch.int64, device=dev)
-        need = self.lib.se_jpg_encode_u8_workspace_bytes(self.h, B, hs, ws)
-        if need == 0:
-            self._err("se_jpg_encode_u8_workspace_bytes")
-        ws_t = self._workspace_bytes(need)
-        if self.lib.se_jpg_encode_u8(self.h, self._stream(), wins, B, hs, ws, int(quality), _ptr(out), out.shape[1], _ptr(sizes),
-                                     _ptr(ws_t), ws_t.numel()):
-            self._err("se_jpg_encode_u8")
-        return out, sizes
+        jpg_bound(hs, ws) bytes to write into.  It is jpg2_encode_u8 with its defaults: one encoder, se_jpg2_encode_u8 without
+        flags, which is what se_jpg_encode_u8 runs."""
+        return self.jpg2_encode_u8(frames, origins, window_hw, quality=quality, out=out)[:2]
 
     # ---- patches as JPEG, 4:2:0 and per-image Huffman tables (DESIGN.md 6l) ----------------------------------------------------------
     @staticmethod

@@ -2382,90 +2382,16 @@ int se_png_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int 
   return 0;
 }
 
-// ---- the device JPEG encoder (include/sketchedit_jpg.h): a window of a frame -> the entropy-coded segment --
-// As the PNG encoder above: every check on the host, then the records and three launches; the workspace's blocks come from the
-// main arena, so SE_TEST_POISON fills each on the stream before its producer is enqueued.
-size_t se_jpg_bound(int hs, int ws) {
-  if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) return 0;
-  return (size_t)jpg_rows(hs) * jpg_row_bound(ws);
-}
+// ---- the device JPEG encoder (DESIGN.md sections 6k and 6l, include/sketchedit_jpg.h and sketchedit_jpg2.h): a window of a frame
+// -> the entropy-coded segment.  As the PNG encoder above: every check on the host, then the records and the launches; the
+// workspace's blocks come from the main arena, so SE_TEST_POISON fills each on the stream before its producer is enqueued.
+// se_jpg_encode_u8 is se_jpg2_encode_u8 without flags: three launches (blocks, rows, finish).  se_jpg2_code_i16 shares the stages
+// behind the DCT (jpg2_code): with SE_JPG_OPTIMIZE the histogram and the tables in front of the rows, five launches from pixels.
+size_t se_jpg_bound(int hs, int ws) { return se_jpg2_bound(hs, ws, 0); }
 
-namespace {
-
-struct JpgLayout { size_t coef, sizes, slots; };              // bytes of the three blocks, each a multiple of 256
-JpgLayout jpg_layout(int B, int hs, int ws) {
-  const size_t q = (size_t)B * jpg_rows(hs);
-  return JpgLayout{pad256(q * jpg_row_blocks(ws) * 128), pad256(q * 4), pad256(q * jpg_slot_bytes(ws))};
-}
-
-}  // namespace
-
-size_t se_jpg_encode_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws) {
-  if (!c) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (B < 1 || B > 65535) { fail(c, "bad B=%d (1 .. 65535 images per call)", B); return 0; }
-  if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) { fail(c, "bad rectangle hs=%d ws=%d (sides are 16 .. 8192)", hs, ws); return 0; }
-  const JpgLayout L = jpg_layout(B, hs, ws);
-  return L.coef + L.sizes + L.slots;
-}
-
-int se_jpg_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int quality, unsigned char* out, size_t cap,
-                     unsigned long long* sizes_out, void* workspace, size_t workspace_bytes) {
-  if (!c) return 1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (B < 1 || B > 65535) return fail(c, "bad B=%d (1 .. 65535 images per call)", B);
-  if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) return fail(c, "bad rectangle hs=%d ws=%d (sides are 16 .. 8192)", hs, ws);
-  if (quality < 1 || quality > 100) return fail(c, "bad quality=%d (1 .. 100)", quality);
-  if (!wins) return fail(c, "null pointer argument: wins");
-  if (!out) return fail(c, "null pointer argument: out");
-  if (!sizes_out) return fail(c, "null pointer argument: sizes_out");
-  if (!workspace) return fail(c, "null pointer argument: workspace");
-  if (win_check_records(c, wins, B, hs, ws, false)) return 1;
-  const size_t bound = se_jpg_bound(hs, ws);
-  if (cap < bound) return fail(c, "cap=%zu is less than se_jpg_bound(%d, %d) = %zu", cap, hs, ws, bound);
-  if (cap > ((size_t)1 << 40) / (size_t)B) return fail(c, "cap=%zu: B cap is more than one call takes", cap);
-  const JpgLayout L = jpg_layout(B, hs, ws);
-  const size_t need = L.coef + L.sizes + L.slots;
-  if (workspace_bytes < need) return fail(c, "workspace too small: %zu bytes, need %zu", workspace_bytes, need);
-  if (!aligned_to(workspace, 256)) return fail(c, "workspace must be 256-byte aligned");
-  if (!aligned_to(sizes_out, 8)) return fail(c, "sizes_out must be 8-byte aligned");
-  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)B * cap, w0 = (uintptr_t)workspace, w1 = w0 + need;
-  const uintptr_t z0 = (uintptr_t)sizes_out, z1 = z0 + (size_t)B * sizeof(unsigned long long);
-  for (int i = 0; i < B; ++i) {
-    const uintptr_t f0 = (uintptr_t)wins[i].frame_u8, f1 = f0 + (size_t)wins[i].Hi * wins[i].Wi * 3;
-    if (o0 < f1 && f0 < o1) return fail(c, "out overlaps the frame of wins[%d]", i);
-    if (z0 < f1 && f0 < z1) return fail(c, "sizes_out overlaps the frame of wins[%d]", i);
-    if (w0 < f1 && f0 < w1) return fail(c, "workspace overlaps the frame of wins[%d]", i);
-  }
-  if (o0 < w1 && w0 < o1) return fail(c, "out overlaps the workspace");
-  if (o0 < z1 && z0 < o1) return fail(c, "out overlaps sizes_out");
-  if (z0 < w1 && w0 < z1) return fail(c, "sizes_out overlaps the workspace");
-  HIPCHK(c, hipSetDevice(c->device));
-  set_profiler(&c->prof);
-  const hipStream_t st = (hipStream_t)stream;
-  c->arena.reset((char*)workspace, need, false);
-  c->arena2.reset(nullptr, 0, false);
-  void* blk[3];
-  const size_t bytes[3] = {L.coef, L.sizes, L.slots};
-  for (int i = 0; i < 3; ++i) {
-    blk[i] = c->arena.alloc(bytes[i] / 4);
-    if (!blk[i]) return fail(c, "workspace arena exhausted");
-    if (poison(c, blk[i], bytes[i], st)) return 1;
-  }
-  const se_window* d = win_put(c, st, wins, B);
-  if (!d) return 1;
-  HIPCHK(c, launch_jpg_blocks(d, B, hs, ws, quality, (short*)blk[0], st));
-  HIPCHK(c, launch_jpg_rows(B, hs, ws, (const short*)blk[0], (unsigned*)blk[1], (unsigned char*)blk[2], st));
-  HIPCHK(c, launch_jpg_finish(B, hs, ws, (const unsigned*)blk[1], (const unsigned char*)blk[2], out, cap, sizes_out, st));
-  return 0;
-}
-
-// ---- the same with 4:2:0 sampling and per-image Huffman tables (include/sketchedit_jpg2.h) ----------------
-// se_jpg_encode_u8 above is untouched.  Both entries here share the stages behind the DCT (jpg2_code): with SE_JPG_OPTIMIZE the
-// histogram and the tables in front of the rows, five launches from pixels, three without.
 size_t se_jpg2_bound(int hs, int ws, int flags) {
   if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192 || flags < 0 || flags > 3) return 0;
-  return (size_t)jpg2_rows(hs, flags) * jpg2_row_bound(jpg2_row_blocks(ws, flags), flags);
+  return (size_t)jpg_rows(hs, flags) * jpg_row_bound(jpg_row_blocks(ws, flags), flags);
 }
 
 namespace {
@@ -2474,7 +2400,7 @@ struct Jpg2Layout { size_t coef, sizes, slots, hist, codes; };             // by
 Jpg2Layout jpg2_layout(int B, int R, int nblk, int flags, bool with_coef) {
   const size_t q = (size_t)B * R;
   const bool opt_ = (flags & SE_JPG_OPTIMIZE) != 0;
-  return Jpg2Layout{with_coef ? pad256(q * nblk * 128) : 0, pad256(q * 4), pad256(q * jpg2_slot_bytes(nblk, flags)), opt_ ? pad256(q * 4096) : 0,
+  return Jpg2Layout{with_coef ? pad256(q * nblk * 128) : 0, pad256(q * 4), pad256(q * jpg_slot_bytes(nblk, flags)), opt_ ? pad256(q * 4096) : 0,
                     opt_ ? pad256((size_t)B * 4096) : 0};
 }
 size_t jpg2_need(const Jpg2Layout& L) { return L.coef + L.sizes + L.slots + L.hist + L.codes; }
@@ -2535,27 +2461,22 @@ int jpg2_code(se_ctx* c, int B, int R, int nblk, int flags, const short* coef, v
     HIPCHK(c, launch_jpg2_tables(B, R, (const unsigned*)blk[3], (unsigned*)blk[4], tables_out, st));
     codes = (const unsigned*)blk[4];
   }
-  HIPCHK(c, launch_jpg2_rows(B, R, nblk, flags, coef, codes, (unsigned*)blk[1], (unsigned char*)blk[2], st));
-  HIPCHK(c, launch_jpg_finish_rows(B, R, nblk, jpg2_slot_bytes(nblk, flags), (const unsigned*)blk[1], (const unsigned char*)blk[2], out, cap,
-                                   sizes_out, st));
+  HIPCHK(c, launch_jpg_rows(B, R, nblk, flags, coef, codes, (unsigned*)blk[1], (unsigned char*)blk[2], st));
+  HIPCHK(c, launch_jpg_finish(B, R, nblk, jpg_slot_bytes(nblk, flags), (const unsigned*)blk[1], (const unsigned char*)blk[2], out, cap, sizes_out,
+                              st));
   return 0;
 }
 
-}  // namespace
-
-size_t se_jpg2_encode_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws, int flags) {
-  if (!c) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
+// the encoder from pixels, for both headers' entries; the caller holds c->mu (a plain mutex: no public entry calls another)
+size_t jpg2_encode_workspace_bytes(se_ctx* c, int B, int hs, int ws, int flags) {
   if (B < 1 || B > 65535) { fail(c, "bad B=%d (1 .. 65535 images per call)", B); return 0; }
   if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) { fail(c, "bad rectangle hs=%d ws=%d (sides are 16 .. 8192)", hs, ws); return 0; }
   if (flags < 0 || flags > 3) { fail(c, "bad flags=%d (SE_JPG_420 | SE_JPG_OPTIMIZE: 0 .. 3)", flags); return 0; }
-  return jpg2_need(jpg2_layout(B, jpg2_rows(hs, flags), jpg2_row_blocks(ws, flags), flags, true));
+  return jpg2_need(jpg2_layout(B, jpg_rows(hs, flags), jpg_row_blocks(ws, flags), flags, true));
 }
 
-int se_jpg2_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int quality, int flags, unsigned char* out,
-                      size_t cap, unsigned long long* sizes_out, unsigned char* tables_out, void* workspace, size_t workspace_bytes) {
-  if (!c) return 1;
-  std::lock_guard<std::mutex> lk(c->mu);
+int jpg2_encode(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int quality, int flags, unsigned char* out, size_t cap,
+                unsigned long long* sizes_out, unsigned char* tables_out, void* workspace, size_t workspace_bytes) {
   if (B < 1 || B > 65535) return fail(c, "bad B=%d (1 .. 65535 images per call)", B);
   if (hs < 16 || ws < 16 || hs > 8192 || ws > 8192) return fail(c, "bad rectangle hs=%d ws=%d (sides are 16 .. 8192)", hs, ws);
   if (quality < 1 || quality > 100) return fail(c, "bad quality=%d (1 .. 100)", quality);
@@ -2566,7 +2487,7 @@ int se_jpg2_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int
   if ((flags & SE_JPG_OPTIMIZE) && !tables_out) return fail(c, "null pointer argument: tables_out (SE_JPG_OPTIMIZE)");
   if (!workspace) return fail(c, "null pointer argument: workspace");
   if (win_check_records(c, wins, B, hs, ws, false)) return 1;
-  const int R = jpg2_rows(hs, flags), nblk = jpg2_row_blocks(ws, flags);
+  const int R = jpg_rows(hs, flags), nblk = jpg_row_blocks(ws, flags);
   const Jpg2Layout L = jpg2_layout(B, R, nblk, flags, true);
   std::vector<Span> srcs;
   for (int i = 0; i < B; ++i)
@@ -2587,6 +2508,34 @@ int se_jpg2_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int
     HIPCHK(c, launch_jpg_blocks(d, B, hs, ws, quality, (short*)blk[0], st));
   }
   return jpg2_code(c, B, R, nblk, flags, (const short*)blk[0], blk, out, cap, sizes_out, tables_out, st);
+}
+
+}  // namespace
+
+size_t se_jpg_encode_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws) {
+  if (!c) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return jpg2_encode_workspace_bytes(c, B, hs, ws, 0);
+}
+
+int se_jpg_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int quality, unsigned char* out, size_t cap,
+                     unsigned long long* sizes_out, void* workspace, size_t workspace_bytes) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return jpg2_encode(c, stream, wins, B, hs, ws, quality, 0, out, cap, sizes_out, nullptr, workspace, workspace_bytes);
+}
+
+size_t se_jpg2_encode_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws, int flags) {
+  if (!c) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return jpg2_encode_workspace_bytes(c, B, hs, ws, flags);
+}
+
+int se_jpg2_encode_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int quality, int flags, unsigned char* out,
+                      size_t cap, unsigned long long* sizes_out, unsigned char* tables_out, void* workspace, size_t workspace_bytes) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return jpg2_encode(c, stream, wins, B, hs, ws, quality, flags, out, cap, sizes_out, tables_out, workspace, workspace_bytes);
 }
 
 namespace {
@@ -2622,7 +2571,7 @@ int se_jpg2_code_i16(se_ctx* c, void* stream, const short* coef, int B, int R, i
   if (!aligned_to(coef, 2)) return fail(c, "coef must be 2-byte aligned");
   const Jpg2Layout L = jpg2_layout(B, R, nblk, flags, false);
   const std::vector<Span> srcs = {{(uintptr_t)coef, (uintptr_t)coef + (size_t)B * R * nblk * 128, nullptr}};
-  if (jpg2_check(c, B, flags, out, cap, (size_t)R * jpg2_row_bound(nblk, flags), sizes_out, tables_out, workspace, workspace_bytes, jpg2_need(L),
+  if (jpg2_check(c, B, flags, out, cap, (size_t)R * jpg_row_bound(nblk, flags), sizes_out, tables_out, workspace, workspace_bytes, jpg2_need(L),
                  srcs, "coef"))
     return 1;
   HIPCHK(c, hipSetDevice(c->device));

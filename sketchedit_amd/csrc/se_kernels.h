@@ -21,7 +21,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
-                 PL_JPG2_ROWS, PL_COUNT };
+                 PL_COUNT };
 const char* prof_label_name(int l);
 // Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
 // know which kernel the dispatcher chose; the label's name where the launcher has one form only
@@ -438,34 +438,26 @@ hipError_t launch_png_stripes(const se_window* d_wins, int B, int hs, int ws, co
                               unsigned char* slots, hipStream_t st);
 hipError_t launch_png_finish(int B, int hs, int ws, const unsigned* sizes, const unsigned* parts, const unsigned char* slots, unsigned char* out,
                              size_t cap, unsigned long long* sizes_out, hipStream_t st);
-// the device JPEG encoder (include/sketchedit_jpg.h): the hs x ws rectangles of d_wins (B records) -> their
-// entropy-coded segments.  blocks: coef (B,R,n,64) int16, the quantised coefficients in zigzag order, R = jpg_rows(hs) rows of
-// n = jpg_row_blocks(ws) blocks (Y, Cb, Cr per MCU).  rows: one workgroup per row -> its restart interval, stuffed, with its
-// marker, in its slot of jpg_slot_bytes(ws) bytes (16-byte aligned) and its size in sizes (B,R).  finish: the rows, concatenated,
-// at out + b cap (any alignment) and their lengths in sizes_out (B).
-int jpg_rows(int hs);
-int jpg_row_blocks(int ws);
-size_t jpg_row_bound(int ws);
-size_t jpg_slot_bytes(int ws);
+// the device JPEG encoder (include/sketchedit_jpg.h and sketchedit_jpg2.h; flags = SE_JPG_420 |
+// SE_JPG_OPTIMIZE): the hs x ws rectangles of d_wins (B records) -> their entropy-coded segments.  blocks: coef (B,R,n,64) int16,
+// the quantised coefficients in zigzag order, R = jpg_rows(hs, flags) rows of n = jpg_row_blocks(ws, flags) blocks (Y, Cb, Cr per
+// MCU of 8 pixel rows; blocks420, under SE_JPG_420: 4 Y, Cb, Cr per MCU of 16).  hist (SE_JPG_OPTIMIZE): one partial histogram of
+// 4 x 256 counters per row, hist (B,R,4,256).  tables: per image the codes (B,4,256), (code << 5) | length per symbol, and the
+// record of 4 x 272 bytes at tables_out + 1088 b (4-byte aligned).  rows: one workgroup per row -> its restart interval, stuffed,
+// with its marker, in its slot of jpg_slot_bytes(n, flags) bytes (16-byte aligned) and its size in sizes (B,R); the tables from
+// `codes` or, where that is null, Annex K's.  finish: the rows, concatenated, at out + b cap (any alignment) and their lengths in
+// sizes_out (B).
+int jpg_rows(int hs, int flags);
+int jpg_row_blocks(int ws, int flags);
+size_t jpg_row_bound(int nblk, int flags);
+size_t jpg_slot_bytes(int nblk, int flags);
 hipError_t launch_jpg_blocks(const se_window* d_wins, int B, int hs, int ws, int quality, short* coef, hipStream_t st);
-hipError_t launch_jpg_rows(int B, int hs, int ws, const short* coef, unsigned* sizes, unsigned char* slots, hipStream_t st);
-hipError_t launch_jpg_finish(int B, int hs, int ws, const unsigned* sizes, const unsigned char* slots, unsigned char* out, size_t cap,
-                             unsigned long long* sizes_out, hipStream_t st);
-// the same with 4:2:0 sampling and per-image Huffman tables (include/sketchedit_jpg2.h; flags = SE_JPG_420 |
-// SE_JPG_OPTIMIZE).  A row of MCUs is 16 pixel rows of 6 blocks an MCU under SE_JPG_420 (blocks420: coef (B,R,mcus,6,64)).  hist:
-// one partial histogram of 4 x 256 counters per row, hist (B,R,4,256).  tables: per image the codes (B,4,256), (code << 5) |
-// length per symbol, and the record of 4 x 272 bytes at tables_out + 1088 b (4-byte aligned).  rows: as above, the tables from
-// `codes` or, where that is null, Annex K's.  finish: launch_jpg_finish_rows, the kernel of launch_jpg_finish for any geometry.
-int jpg2_rows(int hs, int flags);
-int jpg2_row_blocks(int ws, int flags);
-size_t jpg2_row_bound(int nblk, int flags);
-size_t jpg2_slot_bytes(int nblk, int flags);
 hipError_t launch_jpg2_blocks420(const se_window* d_wins, int B, int hs, int ws, int quality, short* coef, hipStream_t st);
 hipError_t launch_jpg2_hist(int B, int R, int nblk, int flags, const short* coef, unsigned* hist, hipStream_t st);
 hipError_t launch_jpg2_tables(int B, int R, const unsigned* hist, unsigned* codes, unsigned char* tables_out, hipStream_t st);
-hipError_t launch_jpg2_rows(int B, int R, int nblk, int flags, const short* coef, const unsigned* codes, unsigned* sizes,
-                            unsigned char* slots, hipStream_t st);
-hipError_t launch_jpg_finish_rows(int B, int R, int nblk, size_t slot_bytes, const unsigned* sizes, const unsigned char* slots,
-                                  unsigned char* out, size_t cap, unsigned long long* sizes_out, hipStream_t st);
+hipError_t launch_jpg_rows(int B, int R, int nblk, int flags, const short* coef, const unsigned* codes, unsigned* sizes,
+                           unsigned char* slots, hipStream_t st);
+hipError_t launch_jpg_finish(int B, int R, int nblk, size_t slot_bytes, const unsigned* sizes, const unsigned char* slots,
+                             unsigned char* out, size_t cap, unsigned long long* sizes_out, hipStream_t st);
 
 }  // namespace se

@@ -50,7 +50,8 @@ KERNEL_LABELS = {
     "(anonymous namespace)::jpg_blocks_kernel": "jpg_blocks", "(anonymous namespace)::jpg_rows_kernel": "jpg_rows",
     "(anonymous namespace)::jpg_finish_kernel": "jpg_finish",
     "jpg_blocks_kernel": "jpg_blocks", "jpg_rows_kernel": "jpg_rows", "jpg_finish_kernel": "jpg_finish",
-    # the same with 4:2:0 sampling and per-image Huffman tables (se_jpg2.hip)
+    # its kernels for 4:2:0 sampling and per-image Huffman tables (se_jpg.hip).  No kernel is named jpg2_rows_kernel any more (the one
+    # row kernel is jpg_rows_kernel); the entries stay for the committed traces that name it
     "(anonymous namespace)::jpg2_blocks420_kernel": "jpg2_blocks420", "(anonymous namespace)::jpg2_hist_kernel": "jpg2_hist",
     "(anonymous namespace)::jpg2_tables_kernel": "jpg2_tables", "(anonymous namespace)::jpg2_rows_kernel": "jpg2_rows",
     "jpg2_blocks420_kernel": "jpg2_blocks420", "jpg2_hist_kernel": "jpg2_hist", "jpg2_tables_kernel": "jpg2_tables",

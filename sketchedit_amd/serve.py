@@ -482,15 +482,10 @@ class _ModelBackend:
     def crop_jpg(self, frames, windows, quality, subsampling="444", optimize=False):
         """the windows (y0, x0, h, w) of `frames` as baseline JPEG files at `quality`, encoded on the device: one
         encoder call per window size; the segments' sizes come down first (the synchronisation), then exactly that many bytes.
-        subsampling="420" and/or optimize=True (four Huffman tables per image, which come down with the sizes) take the
-        encoder of DESIGN.md 6l; the defaults take 6k's, as before."""
+        subsampling="420" and/or optimize=True (four Huffman tables per image, which come down with the sizes) are the
+        forms of DESIGN.md 6l."""
         out = [None] * len(windows)
-        if _check_subsampling(subsampling) == "444" and optimize is False:
-            for (h, w), idx in _by_size(windows).items():
-                buf, sizes = self.model.jpg_encode_u8([frames[i] for i in idx], [windows[i][:2] for i in idx], (h, w), quality)
-                for k, (i, n) in enumerate(zip(idx, sizes.cpu().tolist())):
-                    out[i] = jpg_from_scan(buf[k, :n].cpu().numpy().tobytes(), h, w, quality)
-            return out
+        _check_subsampling(subsampling)
         for (h, w), idx in _by_size(windows).items():
             buf, sizes, tables = self.model.jpg2_encode_u8([frames[i] for i in idx], [windows[i][:2] for i in idx], (h, w), quality,
                                                            subsampling=subsampling, optimize=optimize)

@@ -3,7 +3,8 @@
 (tests/jpg_stream_util.py) over them and checks what each is there for; tests/test_gpu_jpg.py runs the kernels over the same.
 Each is a few KB: the statement is plain Python.
 
-The row kernel (se_jpg.hip) walks a row of MCUs in tiles of 16 blocks, a wave per block.  A row of ws pixels has 3 ceil(ws / 8)
+The row kernel (se_jpg.hip, jpg_rows_kernel: the one row kernel of every form of the encoder) walks a row of MCUs in tiles of 16
+blocks, a wave per block.  A row of ws pixels has 3 ceil(ws / 8)
 blocks, so every ws > 40 spans more than one tile; the wide case is 100 pixels = 13 MCUs = 39 blocks = two tiles and 7 blocks of a
 third, and no tile boundary but the first falls between two MCUs."""
 import numpy as np

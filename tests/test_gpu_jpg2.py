@@ -149,6 +149,8 @@ def test_code_i16_takes_a_batch(model):
 
 
 def test_flags_0_is_se_jpg_encode_u8(model):
+    """se_jpg_encode_u8 forwards to the flags-0 case, so what the name stood for is checked against 6k's own statement
+    (jpg_stream_util, not jpg2_stream_util as everywhere else in this file): both entries write its bytes"""
     eng = model.engine()
     for name, frames, reqs, hw, quality in jpg_cases.cases():
         dev = [torch.from_numpy(f).cuda() for f in frames]
@@ -156,8 +158,12 @@ def test_flags_0_is_se_jpg_encode_u8(model):
         old, osz = eng.jpg_encode_u8(*args, quality=quality)
         got = _encode(eng, frames, reqs, hw, quality, 0)
         assert U2.jpg2_bound(hw[0], hw[1], 0) == U.jpg_bound(*hw) == eng.jpg2_bound(hw[0], hw[1], 0) == eng.jpg_bound(*hw)
-        for b, n in enumerate(osz.cpu().tolist()):
-            assert got[b] == (old[b, :n].cpu().numpy().tobytes(), None), (name, b)
+        osz = osz.cpu().tolist()
+        assert len(got) == len(osz) == len(reqs)
+        for b, r in enumerate(reqs):
+            want = U.jpg_scan(jpg_cases.rectangle(frames, r, hw), quality)
+            assert got[b] == (want, None), (name, b, len(got[b][0]), len(want))
+            assert osz[b] == len(want) and old[b, :osz[b]].cpu().numpy().tobytes() == want, (name, b, osz[b], len(want))
 
 
 def test_every_alignment_of_out(model):
