@@ -716,20 +716,64 @@ class Engine:
             wins[i] = Window(f.data_ptr(), sk.data_ptr() if sk is not None else None, f.shape[0], f.shape[1], int(y0), int(x0))
         return wins
 
-    def window_gather_u8(self, frames, origins, sketches, H, W):
-        """se_window_gather_u8: the H x W window at origins[i] = (y0, x0) of every frame and its sketch -> the forward's inputs
-        (image (B,3,H,W), sketch (B,1,H,W)) fp32, bit-identical to dequantize_u8 of the contiguous crops.  One launch."""
+    def _window_args(self, name, frames, origins, sketches, window_hw, H, W, locks):
+        """What a window step's C entry takes after the stream, as (head, sizes): head = the records and (a locked entry:
+        `locks` not None) the lock pointers; sizes = B, the window's (hs, ws) (an entry with `window_hw`; None: the window is
+        (H, W)) and (H, W).  A step that reads sketches has them checked against the window's size."""
+        hs, ws = (H, W) if window_hw is None else (int(v) for v in window_hw)
+        head = [self._windows(frames, origins, sketches)]
+        if locks is not None:
+            head.append(self._locks(locks, frames))
+        for sk in () if sketches is None else sketches:
+            if tuple(sk.shape) != (hs, ws):
+                raise SketchEditHipError("%s: a sketch is the window's %s uint8 plane"
+                                         % (name, "(H,W)" if window_hw is None else "(hs,ws)"))
+        return head, [len(frames)] + ([] if window_hw is None else [hs, ws]) + [H, W]
+
+    def _window_gather(self, fn, name, frames, origins, sketches, window_hw, H, W):
+        """the one body of window_gather_u8 and window_gather_resize_u8: `fn` = the entry's C function, `name` its name"""
         import torch
-        wins = self._windows(frames, origins, sketches)
-        for sk in sketches:
-            if tuple(sk.shape) != (H, W):
-                raise SketchEditHipError("window_gather_u8: a sketch is the window's (H,W) uint8 plane")
+        head, sizes = self._window_args(name, frames, origins, sketches, window_hw, H, W, None)
         B, dev = len(frames), frames[0].device
         image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
         sketch = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        if self.lib.se_window_gather_u8(self.h, self._stream(), wins, B, H, W, _ptr(image), _ptr(sketch)):
-            self._err("se_window_gather_u8")
+        if fn(self.h, self._stream(), *head, *sizes, _ptr(image), _ptr(sketch)):
+            self._err("se_" + name)
         return image, sketch
+
+    def _window_paste(self, fn, name, frames, origins, window_hw, rgb, mask_u8, locks):
+        """the one body of the three pastes; `locks` None for the two entries that take none"""
+        _check_dev_u8(rgb, mask_u8)
+        B, H, W = mask_u8.shape
+        if tuple(rgb.shape) != (B, H, W, 3) or len(frames) != B:
+            raise SketchEditHipError("%s: expected rgb (B,H,W,3), mask_u8 (B,H,W) and one frame per request" % name)
+        head, sizes = self._window_args(name, frames, origins, None, window_hw, H, W, locks)
+        if fn(self.h, self._stream(), *head, *sizes, _ptr(rgb), _ptr(mask_u8)):
+            self._err("se_" + name)
+
+    def _edit_window(self, fns, name, frames, origins, sketches, window_hw, H, W, locks, flags, commit, low_latency):
+        """the one body of the three edit_window*_u8: `fns` = (the entry's C function, its workspace query) -- each entry
+        keeps its own pair, their workspaces differ"""
+        import torch
+        fn, workspace_bytes = fns
+        head, sizes = self._window_args(name, frames, origins, sketches, window_hw, H, W, locks)
+        B, dev = len(frames), frames[0].device
+        need = workspace_bytes(self.h, *sizes)
+        if need == 0:
+            self._err("se_%s_workspace_bytes" % name)
+        ws = self._workspace_bytes(need)
+        rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        m8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        hits = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
+        if fn(self.h, self._stream(), *head, *sizes, _ptr(rgb), _ptr(m8), _ptr(hits), 1 if commit else 0, _ptr(ws), ws.numel(), flags):
+            self._err("se_" + name)
+        return rgb, m8, hits
+
+    def window_gather_u8(self, frames, origins, sketches, H, W):
+        """se_window_gather_u8: the H x W window at origins[i] = (y0, x0) of every frame and its sketch -> the forward's inputs
+        (image (B,3,H,W), sketch (B,1,H,W)) fp32, bit-identical to dequantize_u8 of the contiguous crops.  One launch."""
+        return self._window_gather(self.lib.se_window_gather_u8, "window_gather_u8", frames, origins, sketches, None, H, W)
 
     def window_border_u8(self, frames, origins, mask_u8):
         """se_window_border_u8: mask_u8 (B,H,W) uint8 -> (B,4) int32 on the device: pixels >= 128 on the top / bottom / left /
@@ -748,91 +792,36 @@ class Engine:
     def window_paste_u8(self, frames, origins, rgb, mask_u8):
         """se_window_paste_u8, in place: frames[i][y0 + y, x0 + x] = rgb[i, y, x] where mask_u8[i, y, x] > 0; rgb (B,H,W,3),
         mask_u8 (B,H,W) uint8 on the device.  Overlapping windows of one frame in one call are refused."""
-        _check_dev_u8(rgb, mask_u8)
-        B, H, W = mask_u8.shape
-        if tuple(rgb.shape) != (B, H, W, 3) or len(frames) != B:
-            raise SketchEditHipError("window_paste_u8: expected rgb (B,H,W,3), mask_u8 (B,H,W) and one frame per request")
-        wins = self._windows(frames, origins)
-        if self.lib.se_window_paste_u8(self.h, self._stream(), wins, B, H, W, _ptr(rgb), _ptr(mask_u8)):
-            self._err("se_window_paste_u8")
+        self._window_paste(self.lib.se_window_paste_u8, "window_paste_u8", frames, origins, None, rgb, mask_u8, None)
 
     def edit_window_u8(self, frames, origins, sketches, H, W, flags, commit=True, low_latency=None):
         """se_edit_window_u8: gather, the forward with fused quantisation, the border counts and (commit) the paste into the
         frames, as ONE library call without a host synchronisation.  -> (rgb (B,H,W,3) uint8, mask_u8 (B,H,W) uint8,
         hits (B,4) int32), on the device.  low_latency: None = by the size of the forward, (B, H, W) of the WINDOW."""
-        import torch
-        wins = self._windows(frames, origins, sketches)
-        for sk in sketches:
-            if tuple(sk.shape) != (H, W):
-                raise SketchEditHipError("edit_window_u8: a sketch is the window's (H,W) uint8 plane")
-        B, dev = len(frames), frames[0].device
-        need = self.lib.se_edit_window_u8_workspace_bytes(self.h, B, H, W)
-        if need == 0:
-            self._err("se_edit_window_u8_workspace_bytes")
-        ws = self._workspace_bytes(need)
-        rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
-        m8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-        hits = torch.empty((B, 4), dtype=torch.int32, device=dev)
-        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
-        if self.lib.se_edit_window_u8(self.h, self._stream(), wins, B, H, W, _ptr(rgb), _ptr(m8), _ptr(hits), 1 if commit else 0,
-                                      _ptr(ws), ws.numel(), flags):
-            self._err("se_edit_window_u8")
-        return rgb, m8, hits
+        return self._edit_window((self.lib.se_edit_window_u8, self.lib.se_edit_window_u8_workspace_bytes), "edit_window_u8",
+                                 frames, origins, sketches, None, H, W, None, flags, commit, low_latency)
 
     # ---- the same at a working size (DESIGN.md 6e): window (hs, ws) in the frame, forward at (H, W) --------------------------
     def window_gather_resize_u8(self, frames, origins, sketches, window_hw, H, W):
         """se_window_gather_resize_u8: the hs x ws window at origins[i] of every frame and its (hs, ws) sketch, resampled
         (Pillow's BICUBIC, bit for bit) into the forward's inputs at H x W -> (image (B,3,H,W), sketch (B,1,H,W)) fp32:
         prepare_u8 of the contiguous crops, without the crops."""
-        import torch
-        hs, ws = (int(v) for v in window_hw)
-        wins = self._windows(frames, origins, sketches)
-        for sk in sketches:
-            if tuple(sk.shape) != (hs, ws):
-                raise SketchEditHipError("window_gather_resize_u8: a sketch is the window's (hs,ws) uint8 plane")
-        B, dev = len(frames), frames[0].device
-        image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        sketch = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        if self.lib.se_window_gather_resize_u8(self.h, self._stream(), wins, B, hs, ws, H, W, _ptr(image), _ptr(sketch)):
-            self._err("se_window_gather_resize_u8")
-        return image, sketch
+        return self._window_gather(self.lib.se_window_gather_resize_u8, "window_gather_resize_u8", frames, origins, sketches,
+                                   window_hw, H, W)
 
     def window_paste_resize_u8(self, frames, origins, window_hw, rgb, mask_u8):
         """se_window_paste_resize_u8, in place: rgb (B,H,W,3) and mask_u8 (B,H,W) at the working size are resampled to the
         hs x ws windows (BICUBIC, both) and frames[i][y0 + y, x0 + x] takes the resampled colour where the resampled mask
         byte is > 0.  Overlapping windows of one frame in one call are refused."""
-        _check_dev_u8(rgb, mask_u8)
-        hs, ws = (int(v) for v in window_hw)
-        B, H, W = mask_u8.shape
-        if tuple(rgb.shape) != (B, H, W, 3) or len(frames) != B:
-            raise SketchEditHipError("window_paste_resize_u8: expected rgb (B,H,W,3), mask_u8 (B,H,W) and one frame per request")
-        wins = self._windows(frames, origins)
-        if self.lib.se_window_paste_resize_u8(self.h, self._stream(), wins, B, hs, ws, H, W, _ptr(rgb), _ptr(mask_u8)):
-            self._err("se_window_paste_resize_u8")
+        self._window_paste(self.lib.se_window_paste_resize_u8, "window_paste_resize_u8", frames, origins, window_hw, rgb, mask_u8,
+                           None)
 
     def edit_window_scaled_u8(self, frames, origins, sketches, window_hw, H, W, flags, commit=True, low_latency=None):
         """se_edit_window_scaled_u8: the window edit with the forward at the working size H x W, ONE library call without a
         host synchronisation.  -> (rgb (B,H,W,3) uint8, mask_u8 (B,H,W) uint8, hits (B,4) int32) on the device, rgb and
         mask_u8 AT THE WORKING SIZE.  low_latency: None = by the size of the forward, (B, H, W)."""
-        import torch
-        hs, ws = (int(v) for v in window_hw)
-        wins = self._windows(frames, origins, sketches)
-        for sk in sketches:
-            if tuple(sk.shape) != (hs, ws):
-                raise SketchEditHipError("edit_window_scaled_u8: a sketch is the window's (hs,ws) uint8 plane")
-        B, dev = len(frames), frames[0].device
-        need = self.lib.se_edit_window_scaled_u8_workspace_bytes(self.h, B, hs, ws, H, W)
-        if need == 0:
-            self._err("se_edit_window_scaled_u8_workspace_bytes")
-        ws_t = self._workspace_bytes(need)
-        rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
-        m8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-        hits = torch.empty((B, 4), dtype=torch.int32, device=dev)
-        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
-        if self.lib.se_edit_window_scaled_u8(self.h, self._stream(), wins, B, hs, ws, H, W, _ptr(rgb), _ptr(m8), _ptr(hits),
-                                             1 if commit else 0, _ptr(ws_t), ws_t.numel(), flags):
-            self._err("se_edit_window_scaled_u8")
-        return rgb, m8, hits
+        return self._edit_window((self.lib.se_edit_window_scaled_u8, self.lib.se_edit_window_scaled_u8_workspace_bytes),
+                                 "edit_window_scaled_u8", frames, origins, sketches, window_hw, H, W, None, flags, commit, low_latency)
 
     # ---- the undo journal of a session (DESIGN.md 6f) ------------------------------------------------------------------------
     @staticmethod
@@ -897,39 +886,14 @@ class Engine:
     def window_paste_locked_u8(self, frames, origins, locks, window_hw, rgb, mask_u8):
         """se_window_paste_locked_u8, in place: window_paste_resize_u8 (window_paste_u8 when the sizes agree) that leaves
         every pixel whose byte of its frame's lock plane is non-zero untouched, whatever the mask says."""
-        _check_dev_u8(rgb, mask_u8)
-        hs, ws = (int(v) for v in window_hw)
-        B, H, W = mask_u8.shape
-        if tuple(rgb.shape) != (B, H, W, 3) or len(frames) != B:
-            raise SketchEditHipError("window_paste_locked_u8: expected rgb (B,H,W,3), mask_u8 (B,H,W) and one frame per request")
-        wins = self._windows(frames, origins)
-        ptrs = self._locks(locks, frames)
-        if self.lib.se_window_paste_locked_u8(self.h, self._stream(), wins, ptrs, B, hs, ws, H, W, _ptr(rgb), _ptr(mask_u8)):
-            self._err("se_window_paste_locked_u8")
+        self._window_paste(self.lib.se_window_paste_locked_u8, "window_paste_locked_u8", frames, origins, window_hw, rgb, mask_u8,
+                           locks)
 
     def edit_window_locked_u8(self, frames, origins, sketches, locks, window_hw, H, W, flags, commit=True, low_latency=None):
         """se_edit_window_locked_u8: edit_window_scaled_u8 (edit_window_u8 when (H, W) == window_hw) in which no edit changes
         a locked pixel: the lock enters the forward (inference_u8(lock=)) and the paste.  -> (rgb, mask_u8, hits) as there."""
-        import torch
-        hs, ws = (int(v) for v in window_hw)
-        wins = self._windows(frames, origins, sketches)
-        ptrs = self._locks(locks, frames)
-        for sk in sketches:
-            if tuple(sk.shape) != (hs, ws):
-                raise SketchEditHipError("edit_window_locked_u8: a sketch is the window's (hs,ws) uint8 plane")
-        B, dev = len(frames), frames[0].device
-        need = self.lib.se_edit_window_locked_u8_workspace_bytes(self.h, B, hs, ws, H, W)
-        if need == 0:
-            self._err("se_edit_window_locked_u8_workspace_bytes")
-        ws_t = self._workspace_bytes(need)
-        rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
-        m8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-        hits = torch.empty((B, 4), dtype=torch.int32, device=dev)
-        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
-        if self.lib.se_edit_window_locked_u8(self.h, self._stream(), wins, ptrs, B, hs, ws, H, W, _ptr(rgb), _ptr(m8), _ptr(hits),
-                                             1 if commit else 0, _ptr(ws_t), ws_t.numel(), flags):
-            self._err("se_edit_window_locked_u8")
-        return rgb, m8, hits
+        return self._edit_window((self.lib.se_edit_window_locked_u8, self.lib.se_edit_window_locked_u8_workspace_bytes),
+                                 "edit_window_locked_u8", frames, origins, sketches, window_hw, H, W, locks, flags, commit, low_latency)
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------
     def sketch_tiles_u8(self, sketch_u8, tile, out=None):

@@ -1067,6 +1067,14 @@ void begin_call(se_ctx* c, void* stream, int flags) {
   set_profiler(&c->prof);
 }
 
+// what every entry that plans a forward does once its arguments are checked (the mutex is held)
+int forward_enter(se_ctx* c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
+  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  return 0;
+}
+
 // A captured forward may still be executing on the stream it was last launched on: destroying an in-flight hipGraphExec
 // is not safe on every ROCm version, so that stream is drained first (eviction and weight reloads are rare events).
 void destroy_graph(se_ctx::GraphEntry& g) {
@@ -1376,9 +1384,7 @@ int se_netM_forward_ex(se_ctx* c, void* stream, const float* image, const float*
   std::lock_guard<std::mutex> lk(c->mu);
   if (check_dims(c, B, H, W)) return 1;
   if (!image || !sketch || !mask_out || !ws) return fail(c, "null pointer argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  if (forward_enter(c)) return 1;
   exec_flags &= SE_FLAG_LOW_LATENCY | SE_FLAG_BF16 | SE_FLAG_CONSERVATIVE;
   const int nb = pass_size(c, B, H, W, exec_flags);
   if (!nb) return 1;
@@ -1406,9 +1412,7 @@ int se_netG_forward_taps(se_ctx* c, void* stream, const float* x, const float* x
   std::lock_guard<std::mutex> lk(c->mu);
   if (check_dims(c, B, H, W)) return 1;
   if (!x || !x2 || !mask || !mask2 || !guide || !fine_out || !ws) return fail(c, "null pointer argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  if (forward_enter(c)) return 1;
   const int nb = pass_size(c, B, H, W, flags);
   if (!nb) return 1;
   if (taps && nb < B) return fail(c, "se_netG_forward_taps: %d images do not fit one pass (%d)", B, nb);
@@ -1476,9 +1480,7 @@ int se_inference(se_ctx* c, void* stream, const float* image, const float* sketc
   std::lock_guard<std::mutex> lk(c->mu);
   if (check_dims(c, B, H, W)) return 1;
   if (!image || !sketch || !composed_out || (!mask_out && !(flags & SE_FLAG_PACKED_OUT)) || !ws) return fail(c, "null pointer argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  if (forward_enter(c)) return 1;
   // (SE_TEST_POISON set: uncaptured, and nothing enters the graph cache -- the fills belong to the test aid, not to a graph)
   if (!(flags & SE_FLAG_GRAPH) || c->prof.on || poison_byte() != 0)
     return enqueue_inference(c, stream, image, sketch, composed_out, mask_out, hard_out, maskim_out, coarse_out, fine_out, ws,
@@ -1531,9 +1533,7 @@ int se_inference_locked(se_ctx* c, void* stream, const float* image, const float
   std::lock_guard<std::mutex> lk(c->mu);
   if (check_dims(c, B, H, W)) return 1;
   if (!image || !sketch || !composed_out || (!mask_out && !(flags & SE_FLAG_PACKED_OUT)) || !ws) return fail(c, "null pointer argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  if (forward_enter(c)) return 1;
   return enqueue_inference(c, stream, image, sketch, composed_out, mask_out, hard_out, maskim_out, coarse_out, fine_out, ws,
                            ws_bytes, B, H, W, flags & ~SE_FLAG_GRAPH, lock_u8);
 }
@@ -1577,14 +1577,7 @@ int inference_u8_locked(se_ctx* c, void* stream, const float* image, const float
 
 int se_inference_u8(se_ctx* c, void* stream, const float* image, const float* sketch, unsigned char* rgb_out,
                     unsigned char* mask_u8_out, void* ws, size_t ws_bytes, int B, int H, int W, int flags) {
-  if (!c) return 1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (check_dims(c, B, H, W)) return 1;
-  if (!image || !sketch || !rgb_out || !ws) return fail(c, "null pointer argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
-  return inference_u8_locked(c, stream, image, sketch, rgb_out, mask_u8_out, ws, ws_bytes, B, H, W, flags, 0);
+  return se_inference_u8_locked(c, stream, image, sketch, nullptr, rgb_out, mask_u8_out, ws, ws_bytes, B, H, W, flags);      // (locks there)
 }
 
 int se_inference_u8_locked(se_ctx* c, void* stream, const float* image, const float* sketch, const unsigned char* lock_u8,
@@ -1593,9 +1586,7 @@ int se_inference_u8_locked(se_ctx* c, void* stream, const float* image, const fl
   std::lock_guard<std::mutex> lk(c->mu);
   if (check_dims(c, B, H, W)) return 1;
   if (!image || !sketch || !rgb_out || !ws) return fail(c, "null pointer argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  if (forward_enter(c)) return 1;
   return inference_u8_locked(c, stream, image, sketch, rgb_out, mask_u8_out, ws, ws_bytes, B, H, W, flags, 0, lock_u8);
 }
 
@@ -1620,9 +1611,7 @@ int se_inference_u8io(se_ctx* c, void* stream, const unsigned char* image_u8, co
   std::lock_guard<std::mutex> lk(c->mu);
   if (check_dims(c, B, H, W)) return 1;
   if (!image_u8 || !sketch_u8 || !rgb_out || !ws) return fail(c, "null pointer argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  if (forward_enter(c)) return 1;
   const size_t plane = ((size_t)B * H * W * 4 + 255) & ~(size_t)255;
   if (ws_bytes < 6 * plane) return fail(c, "workspace too small: %zu bytes", ws_bytes);
   float* image = (float*)((char*)ws + ws_bytes - 4 * plane);      // (B,3,H,W) contiguous: 3 B H W floats <= 3 planes
@@ -1711,9 +1700,7 @@ int se_edit_u8(se_ctx* c, void* stream, const unsigned char* image_u8, const uns
   if (edit_dims(c, B, Hi, Wi, &H, &W)) return 1;
   if (check_dims(c, B, H, W)) return 1;
   if (!image_u8 || !sketch_u8 || !rgb_out || !ws) return fail(c, "null pointer argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  if (forward_enter(c)) return 1;
   const size_t plane = ((size_t)B * H * W * 4 + 255) & ~(size_t)255, rgbw = ((size_t)B * H * W * 3 + 255) & ~(size_t)255;
   if (ws_bytes < rgbw + 6 * plane) return fail(c, "workspace too small: %zu bytes", ws_bytes);
   unsigned char* rgb_work = (unsigned char*)ws;
@@ -1962,9 +1949,7 @@ int edit_window_locked(se_ctx* c, void* stream, const se_window* wins, int B, in
   if (!wsp) return fail(c, "null pointer argument: workspace");
   if (!aligned_to(wsp, 256)) return fail(c, "workspace must be 256-byte aligned");
   if (!aligned_to(rgb_out, 4) || !aligned_to(mask_u8_out, 4) || !aligned_to(hits_out, 4)) return fail(c, "rgb_out / mask_u8_out / hits_out must be 4-byte aligned");
-  HIPCHK(c, hipSetDevice(c->device));
-  c->serial = c->prof.on;      // profiler on: default mode planned on one stream (Plan::forked)
-  c->fork2 = opt(OPT_FORK_DEFAULT) != 0;
+  if (forward_enter(c)) return 1;
   const size_t plane = pad256((size_t)B * H * W * 4), rgbw = pad256((size_t)B * H * W * 3), mw = pad256((size_t)B * H * W),
                hw = pad256((size_t)B * 4 * sizeof(int)),
                midw = scaled ? std::max(gather_mid_bytes(B, hs, W), paste_mid_bytes(B, H, ws)) : 0, lockw = locked ? mw : 0;
@@ -2004,19 +1989,58 @@ int edit_window_locked(se_ctx* c, void* stream, const se_window* wins, int B, in
   return 0;
 }
 
+// the gather step alone: se_window_gather_u8 (hs x ws == H x W) and se_window_gather_resize_u8
+int window_gather_locked(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W, float* image_out,
+                         float* sketch_out) {
+  if (win_check(c, wins, B, H, W, hs, ws, sketch_out != nullptr, false)) return 1;
+  if (!aligned_to(image_out, 16) || !aligned_to(sketch_out, 16)) return fail(c, "image_out / sketch_out must be 16-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = (hipStream_t)stream;
+  const bool scaled = hs != H || ws != W;
+  unsigned char* mid = nullptr;
+  if (scaled) {
+    if (rs_enter(c, st)) return 1;
+    if (hs != H && !(mid = rs_scratch(c, gather_mid_bytes(B, hs, W)))) return 1;
+  }
+  set_profiler(&c->prof);
+  const se_window* d = win_put(c, st, wins, B);
+  if (!d) return 1;
+  if (scaled) return gather_resize_locked(c, st, d, B, hs, ws, H, W, image_out, sketch_out, mid);
+  HIPCHK(c, launch_window_gather(d, c->lut8, image_out, sketch_out, B, H, W, st));
+  return 0;
+}
+
+// the paste step alone, for the three paste entries.  `locked`: se_window_paste_locked_u8 -- the 2 B records and the locked
+// kernels whatever `locks` holds; the other two pass locks = null and never take either
+int window_paste_locked(se_ctx* c, void* stream, const se_window* wins, const unsigned char* const* locks, bool locked, int B, int hs,
+                        int ws, int H, int W, const unsigned char* rgb, const unsigned char* mask_u8) {
+  if (win_check(c, wins, B, H, W, hs, ws, false, true)) return 1;
+  if (locked && !locks) return fail(c, "null pointer argument: locks");
+  if (!rgb || !mask_u8) return fail(c, "null pointer argument: rgb / mask_u8");
+  if (!aligned_to(rgb, 4) || !aligned_to(mask_u8, 4)) return fail(c, "rgb / mask_u8 must be 4-byte aligned");
+  if (locked && win_check_locks(c, wins, locks, B)) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = (hipStream_t)stream;
+  const bool scaled = hs != H || ws != W;
+  unsigned char* mid = nullptr;
+  if (scaled) {
+    if (rs_enter(c, st)) return 1;
+    if (ws != W && !(mid = rs_scratch(c, paste_mid_bytes(B, H, ws)))) return 1;
+  }
+  set_profiler(&c->prof);
+  const se_window* d = locked ? win_put_locks(c, st, wins, locks, B) : win_put(c, st, wins, B);
+  if (!d) return 1;
+  if (scaled) return paste_resize_locked(c, st, d, B, hs, ws, H, W, rgb, mask_u8, mid, locked);
+  HIPCHK(c, launch_window_paste(d, rgb, mask_u8, B, H, W, st, locked));
+  return 0;
+}
+
 }  // namespace
 
 int se_window_gather_u8(se_ctx* c, void* stream, const se_window* wins, int B, int H, int W, float* image_out, float* sketch_out) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (win_check(c, wins, B, H, W, H, W, sketch_out != nullptr, false)) return 1;
-  if (!aligned_to(image_out, 16) || !aligned_to(sketch_out, 16)) return fail(c, "image_out / sketch_out must be 16-byte aligned");
-  HIPCHK(c, hipSetDevice(c->device));
-  set_profiler(&c->prof);
-  const se_window* d = win_put(c, (hipStream_t)stream, wins, B);
-  if (!d) return 1;
-  HIPCHK(c, launch_window_gather(d, c->lut8, image_out, sketch_out, B, H, W, (hipStream_t)stream));
-  return 0;
+  return window_gather_locked(c, stream, wins, B, H, W, H, W, image_out, sketch_out);
 }
 
 int se_window_border_u8(se_ctx* c, void* stream, const se_window* wins, int B, int H, int W, const unsigned char* mask_u8,
@@ -2038,15 +2062,7 @@ int se_window_paste_u8(se_ctx* c, void* stream, const se_window* wins, int B, in
                        const unsigned char* mask_u8) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (win_check(c, wins, B, H, W, H, W, false, true)) return 1;
-  if (!rgb || !mask_u8) return fail(c, "null pointer argument: rgb / mask_u8");
-  if (!aligned_to(rgb, 4) || !aligned_to(mask_u8, 4)) return fail(c, "rgb / mask_u8 must be 4-byte aligned");
-  HIPCHK(c, hipSetDevice(c->device));
-  set_profiler(&c->prof);
-  const se_window* d = win_put(c, (hipStream_t)stream, wins, B);
-  if (!d) return 1;
-  HIPCHK(c, launch_window_paste(d, rgb, mask_u8, B, H, W, (hipStream_t)stream));
-  return 0;
+  return window_paste_locked(c, stream, wins, nullptr, false, B, H, W, H, W, rgb, mask_u8);
 }
 
 // the uint8 result, the uint8 mask and the border counts in front of the forward's part (used where the caller passes NULL)
@@ -2069,45 +2085,14 @@ int se_window_gather_resize_u8(se_ctx* c, void* stream, const se_window* wins, i
                                float* sketch_out) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (win_check(c, wins, B, H, W, hs, ws, sketch_out != nullptr, false)) return 1;
-  if (!aligned_to(image_out, 16) || !aligned_to(sketch_out, 16)) return fail(c, "image_out / sketch_out must be 16-byte aligned");
-  HIPCHK(c, hipSetDevice(c->device));
-  const hipStream_t st = (hipStream_t)stream;
-  const bool scaled = hs != H || ws != W;
-  unsigned char* mid = nullptr;
-  if (scaled) {
-    if (rs_enter(c, st)) return 1;
-    if (hs != H && !(mid = rs_scratch(c, gather_mid_bytes(B, hs, W)))) return 1;
-  }
-  set_profiler(&c->prof);
-  const se_window* d = win_put(c, st, wins, B);
-  if (!d) return 1;
-  if (scaled) return gather_resize_locked(c, st, d, B, hs, ws, H, W, image_out, sketch_out, mid);
-  HIPCHK(c, launch_window_gather(d, c->lut8, image_out, sketch_out, B, H, W, st));
-  return 0;
+  return window_gather_locked(c, stream, wins, B, hs, ws, H, W, image_out, sketch_out);
 }
 
 int se_window_paste_resize_u8(se_ctx* c, void* stream, const se_window* wins, int B, int hs, int ws, int H, int W,
                               const unsigned char* rgb, const unsigned char* mask_u8) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (win_check(c, wins, B, H, W, hs, ws, false, true)) return 1;
-  if (!rgb || !mask_u8) return fail(c, "null pointer argument: rgb / mask_u8");
-  if (!aligned_to(rgb, 4) || !aligned_to(mask_u8, 4)) return fail(c, "rgb / mask_u8 must be 4-byte aligned");
-  HIPCHK(c, hipSetDevice(c->device));
-  const hipStream_t st = (hipStream_t)stream;
-  const bool scaled = hs != H || ws != W;
-  unsigned char* mid = nullptr;
-  if (scaled) {
-    if (rs_enter(c, st)) return 1;
-    if (ws != W && !(mid = rs_scratch(c, paste_mid_bytes(B, H, ws)))) return 1;
-  }
-  set_profiler(&c->prof);
-  const se_window* d = win_put(c, st, wins, B);
-  if (!d) return 1;
-  if (scaled) return paste_resize_locked(c, st, d, B, hs, ws, H, W, rgb, mask_u8, mid);
-  HIPCHK(c, launch_window_paste(d, rgb, mask_u8, B, H, W, st));
-  return 0;
+  return window_paste_locked(c, stream, wins, nullptr, false, B, hs, ws, H, W, rgb, mask_u8);
 }
 
 size_t se_edit_window_scaled_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws, int H, int W) {
@@ -2155,25 +2140,7 @@ int se_window_paste_locked_u8(se_ctx* c, void* stream, const se_window* wins, co
                               int H, int W, const unsigned char* rgb, const unsigned char* mask_u8) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (win_check(c, wins, B, H, W, hs, ws, false, true)) return 1;
-  if (!locks) return fail(c, "null pointer argument: locks");
-  if (!rgb || !mask_u8) return fail(c, "null pointer argument: rgb / mask_u8");
-  if (!aligned_to(rgb, 4) || !aligned_to(mask_u8, 4)) return fail(c, "rgb / mask_u8 must be 4-byte aligned");
-  if (win_check_locks(c, wins, locks, B)) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  const hipStream_t st = (hipStream_t)stream;
-  const bool scaled = hs != H || ws != W;
-  unsigned char* mid = nullptr;
-  if (scaled) {
-    if (rs_enter(c, st)) return 1;
-    if (ws != W && !(mid = rs_scratch(c, paste_mid_bytes(B, H, ws)))) return 1;
-  }
-  set_profiler(&c->prof);
-  const se_window* d = win_put_locks(c, st, wins, locks, B);
-  if (!d) return 1;
-  if (scaled) return paste_resize_locked(c, st, d, B, hs, ws, H, W, rgb, mask_u8, mid, true);
-  HIPCHK(c, launch_window_paste(d, rgb, mask_u8, B, H, W, st, true));
-  return 0;
+  return window_paste_locked(c, stream, wins, locks, true, B, hs, ws, H, W, rgb, mask_u8);
 }
 
 size_t se_edit_window_locked_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws, int H, int W) {

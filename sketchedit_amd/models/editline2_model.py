@@ -145,18 +145,16 @@ class EditLine2Model(torch.nn.Module):
             raise NotImplementedError("call model.eval() first: only the eval branch of generate_fake exists here")
         dev = torch.device("cuda", self.opt.gpu_ids[0])
         sks = [_lib.upload_u8(s, dev) for s in sketches]
-        flags = _lib.flags_from_opt(self.opt)
+        Hw, Ww = (int(v) for v in work_hw) if work_hw is not None else (H, W)      # the size of the forward
+        args = (Hw, Ww, _lib.flags_from_opt(self.opt))
         with torch.no_grad():
+            eng = self.engine()
+            kw = dict(commit=commit, low_latency=self._mode_for(len(frames), Hw, Ww, low_latency))
             if locks is not None and any(t is not None for t in locks):
-                Hw, Ww = (int(v) for v in work_hw) if work_hw is not None else (H, W)
-                return self.engine().edit_window_locked_u8(frames, origins, sks, locks, (H, W), Hw, Ww, flags, commit=commit,
-                                                           low_latency=self._mode_for(len(frames), Hw, Ww, low_latency))
+                return eng.edit_window_locked_u8(frames, origins, sks, locks, (H, W), *args, **kw)
             if work_hw is not None:
-                Hw, Ww = (int(v) for v in work_hw)
-                return self.engine().edit_window_scaled_u8(frames, origins, sks, (H, W), Hw, Ww, flags, commit=commit,
-                                                           low_latency=self._mode_for(len(frames), Hw, Ww, low_latency))
-            return self.engine().edit_window_u8(frames, origins, sks, H, W, flags, commit=commit,
-                                                low_latency=self._mode_for(len(frames), H, W, low_latency))
+                return eng.edit_window_scaled_u8(frames, origins, sks, (H, W), *args, **kw)
+            return eng.edit_window_u8(frames, origins, sks, *args, **kw)
 
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new

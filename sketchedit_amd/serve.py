@@ -396,6 +396,38 @@ class _Regions(tuple):
     """the windows of a region edit's journal entry (its slots are a list in the same order)"""
 
 
+def _run_windows(be, frames, origins, crops, window_hw, work, locks, commit, low_latency):
+    """The one choice of the backend entry a window edit takes: `locks` = a plane or None per request
+    (None: no request of the call has one) -> run_locked; else `work` = the working size (None: no max_side; it is not
+    compared with the window) -> run_scaled; else run.  -> what the entry returns."""
+    if locks is not None:
+        return be.run_locked(frames, origins, crops, locks, window_hw, work, commit, low_latency)
+    if work is not None:
+        return be.run_scaled(frames, origins, crops, window_hw, work, commit, low_latency)
+    return be.run(frames, origins, crops, window_hw[0], window_hw[1], commit, low_latency)
+
+
+def _paste_windows(be, frames, origins, window_hw, work, locks, rgb, m8):
+    """the paste that belongs to an uncommitted `_run_windows` of the same `work` and `locks`"""
+    if locks is not None:
+        be.paste_locked(frames, origins, locks, window_hw, rgb, m8)
+    elif work is not None:
+        be.paste_scaled(frames, origins, window_hw, rgb, m8)
+    else:
+        be.paste(frames, origins, rgb, m8)
+
+
+def _edit_info(info, locked, work, undoable):
+    """an edit's `info` with what only some sessions report: locked (a lock plane), work (max_side), undoable (history)"""
+    if locked:
+        info["locked"] = True
+    if work is not None:
+        info["work"] = work
+    if undoable is not None:
+        info["undoable"] = undoable
+    return info
+
+
 class _ModelBackend:
     """The device side of an editing session: an EditLine2Model's engine and torch for the copies.  (A seam: the host
     logic of EditSession and of the window batcher is tested against a scripted stand-in.)"""
@@ -731,7 +763,7 @@ class EditSession:
         reruns = 0
         be = self.backend
         with self._lock:
-            lk = self._lock_plane
+            planes = None if self._lock_plane is None else [self._lock_plane]
             while True:
                 y0, x0, h, w = win
                 nxt = None if fixed or reruns >= max_grow else self._grown(bbox, win, margin)
@@ -740,34 +772,19 @@ class EditSession:
                 crop = be.upload(sk[y0:y0 + h, x0:x0 + w])
                 slot = be.save([self._frame], [(y0, x0)], (h, w))[0] if commit and self._journals(h, w) else None
                 work = choose_working_size((h, w), max_side) if scaled else None
-                if lk is not None:
-                    rgb, m8, counts = be.run_locked([self._frame], [(y0, x0)], [crop], [lk], (h, w), work, commit, low_latency)
-                elif scaled:
-                    rgb, m8, counts = be.run_scaled([self._frame], [(y0, x0)], [crop], (h, w), work, commit, low_latency)
-                else:
-                    rgb, m8, counts = be.run([self._frame], [(y0, x0)], [crop], h, w, commit, low_latency)
+                rgb, m8, counts = _run_windows(be, [self._frame], [(y0, x0)], [crop], (h, w), work, planes, commit, low_latency)
                 if commit or not any(counts[0]):
                     break
                 win, margin = nxt
                 reruns += 1
             if not commit and self._journals(h, w):
                 slot = be.save([self._frame], [(y0, x0)], (h, w))[0]
-            if not commit and lk is not None:
-                be.paste_locked([self._frame], [(y0, x0)], [lk], (h, w), rgb, m8)
-            elif not commit and scaled:
-                be.paste_scaled([self._frame], [(y0, x0)], (h, w), rgb, m8)
-            elif not commit:
-                be.paste([self._frame], [(y0, x0)], rgb, m8)
+            if not commit:
+                _paste_windows(be, [self._frame], [(y0, x0)], (h, w), work, planes, rgb, m8)
             undoable = self._record(win, slot) if self.history > 0 else None
             patch = be.crop(self._frame, y0, x0, h, w) if encode is None else _encoded(be, encode, [self._frame], [(y0, x0, h, w)])[0]
         info = dict(window=win, counts=list(counts[0]), reruns=reruns, margin=margin)
-        if lk is not None:
-            info["locked"] = True
-        if scaled:
-            info["work"] = work
-        if undoable is not None:
-            info["undoable"] = undoable
-        return patch, (x0, y0), info
+        return patch, (x0, y0), _edit_info(info, planes is not None, work, undoable)
 
     def edit_regions(self, sketch, low_latency=None, max_side=None, tile=32, margin=0.5, bucket=64, min_side=256, encode=None):
         """One edit of SEPARATE strokes through separate windows, so that two small strokes in opposite
@@ -818,12 +835,8 @@ class EditSession:
                     for i, slot in zip(idx, be.save(frames, origins, (h, w))):
                         slots[i] = slot
                 work = choose_working_size((h, w), max_side) if scaled else None
-                if lk is not None:
-                    _, _, hits = be.run_locked(frames, origins, crops, [lk] * len(idx), (h, w), work, True, low_latency)
-                elif scaled:
-                    _, _, hits = be.run_scaled(frames, origins, crops, (h, w), work, True, low_latency)
-                else:
-                    _, _, hits = be.run(frames, origins, crops, h, w, True, low_latency)
+                planes = None if lk is None else [lk] * len(idx)
+                _, _, hits = _run_windows(be, frames, origins, crops, (h, w), work, planes, True, low_latency)
                 for i, c in zip(idx, hits):
                     counts[i], works[i] = list(c), work
         except Exception:
@@ -834,13 +847,7 @@ class EditSession:
         undoable = self._record_regions(wins, slots if journal else None) if self.history > 0 else None
         patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, [self._frame] * len(wins), wins)
         info = dict(windows=wins, boxes=[b for b, _ in regions], counts=counts, groups=len(groups))
-        if lk is not None:
-            info["locked"] = True
-        if scaled:
-            info["work"] = works
-        if undoable is not None:
-            info["undoable"] = undoable
-        return patches, [(w[1], w[0]) for w in wins], info
+        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, lk is not None, works if scaled else None, undoable)
 
     def edit_strokes(self, strokes, low_latency=None, max_side=None, margin=0.5, bucket=64, min_side=256, encode=None):
         """One edit of strokes given as POLYLINES: `strokes` = [(points, width_px)] as stroke_segments takes
@@ -1105,7 +1112,7 @@ class BatchingServer:
         journalled = [i for i, r in enumerate(reqs) if r["session"]._journals(h, w)]
         slots = {}
         lks = [r["session"]._lock_plane for r in reqs]
-        locked = any(t is not None for t in lks)
+        locked = any(t is not None for t in lks)          # (then the whole list travels, its Nones included)
 
         def save(idx):                                    # one launch for the group's journalled requests
             if idx:
@@ -1117,33 +1124,20 @@ class BatchingServer:
             crops = [be.upload(r["sketch"][y0:y0 + h, x0:x0 + w]) for r, (y0, x0) in zip(reqs, origins)]
             if commit:
                 save(journalled)
-            if locked:
-                rgb, m8, counts = be.run_locked(frames, origins, crops, lks, (h, w), work, commit, low_latency)
-            elif work is not None:
-                rgb, m8, counts = be.run_scaled(frames, origins, crops, (h, w), work, commit, low_latency)
-            else:
-                rgb, m8, counts = be.run(frames, origins, crops, h, w, commit, low_latency)
+            rgb, m8, counts = _run_windows(be, frames, origins, crops, (h, w), work, lks if locked else None, commit, low_latency)
             stay = [i for i in range(len(reqs)) if grown[i] is None or not any(counts[i])]
             if not commit:
                 save([i for i in stay if i in journalled])          # (a request that is queued again journals nothing yet)
-            if not commit and stay and locked:
-                be.paste_locked([frames[i] for i in stay], [origins[i] for i in stay], [lks[i] for i in stay], (h, w),
-                                be.select(rgb, stay), be.select(m8, stay))
-            elif not commit and stay and work is not None:
-                be.paste_scaled([frames[i] for i in stay], [origins[i] for i in stay], (h, w), be.select(rgb, stay), be.select(m8, stay))
-            elif not commit and stay:
-                be.paste([frames[i] for i in stay], [origins[i] for i in stay], be.select(rgb, stay), be.select(m8, stay))
+            if not commit and stay:
+                _paste_windows(be, [frames[i] for i in stay], [origins[i] for i in stay], (h, w), work,
+                               [lks[i] for i in stay] if locked else None, be.select(rgb, stay), be.select(m8, stay))
             outs = [None] * len(reqs)
             for i in stay:
                 r = reqs[i]
                 y0, x0 = origins[i]
                 info = dict(window=r["window"], counts=list(counts[i]), reruns=r["reruns"], margin=r["margin"])
-                if lks[i] is not None:
-                    info["locked"] = True
-                if work is not None:
-                    info["work"] = tuple(work)
-                if r["session"].history > 0:
-                    info["undoable"] = r["session"]._record(r["window"], slots.get(i))
+                undoable = r["session"]._record(r["window"], slots.get(i)) if r["session"].history > 0 else None
+                _edit_info(info, lks[i] is not None, None if work is None else tuple(work), undoable)
                 outs[i] = (be.crop(frames[i], y0, x0, h, w), (x0, y0), info)
         finally:
             for _, lk in locks:

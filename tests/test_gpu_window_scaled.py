@@ -325,6 +325,53 @@ def test_scale_one_is_the_unscaled_edit(model):
     assert _same_bits(ia, ib) and _same_bits(sa, sb)
 
 
+def test_step_entries_agree_at_scale_one(model):
+    """The step entries alone, no forward: at (hs, ws) == (H, W) the gathers of 6d and 6e return the same bits, and the
+    pastes of 6d, 6e and 6g (no plane at all; an all-zero plane for one frame and none for the other) leave the same bytes,
+    those of the numpy rule.  B = 3: two disjoint windows of a 97 x 131 frame (a width that is no multiple of 4, odd
+    origins) and one window of a 64 x 80 frame."""
+    eng = model.engine()
+    rng = np.random.RandomState(21)
+    fs = [_frame(rng, 131, 97), _frame(rng, 80, 64)]
+    for H, W in ((16, 24), (40, 48)):
+        origins = [(1, 1), (H + 3, W + 3), (5, 3)]
+        which = [0, 0, 1]                                          # the frame of each request
+
+        def frames():
+            fts = [_cuda(f) for f in fs]
+            return fts, [fts[k] for k in which]
+
+        sks = [_cuda(_sketch(rng, H, W, 0.2)) for _ in which]
+        ia, sa = eng.window_gather_u8(frames()[1], origins, sks, H, W)
+        ib, sb = eng.window_gather_resize_u8(frames()[1], origins, sks, (H, W), H, W)
+        assert _same_bits(ia, ib), (H, W)
+        assert _same_bits(sa, sb), (H, W)
+
+        rgb = rng.randint(0, 256, (3, H, W, 3), dtype=np.uint8)
+        m8 = rng.choice(np.array([0, 1, 255], np.uint8), size=(3, H, W))
+        assert all((m8 == v).any() for v in (0, 1, 255))
+        want = [f.copy() for f in fs]
+        for i, (k, (y0, x0)) in enumerate(zip(which, origins)):
+            want[k], _ = _paste_rule(want[k], y0, x0, rgb[i], m8[i])
+        zero = torch.zeros((97, 131), dtype=torch.uint8, device="cuda")
+        pastes = {
+            "paste": lambda fr: eng.window_paste_u8(fr, origins, _cuda(rgb), _cuda(m8)),
+            "paste_resize": lambda fr: eng.window_paste_resize_u8(fr, origins, (H, W), _cuda(rgb), _cuda(m8)),
+            "paste_locked, no plane": lambda fr: eng.window_paste_locked_u8(fr, origins, [None] * 3, (H, W), _cuda(rgb), _cuda(m8)),
+            "paste_locked, zero plane": lambda fr: eng.window_paste_locked_u8(fr, origins, [zero, zero, None], (H, W), _cuda(rgb), _cuda(m8)),
+        }
+        first = None
+        for name, paste in pastes.items():
+            fts, per_request = frames()
+            paste(per_request)
+            got = [t.cpu().numpy() for t in fts]
+            first = first or got
+            for k in range(2):
+                assert np.array_equal(got[k], first[k]), (name, (H, W), k)          # the entries agree ...
+                assert np.array_equal(got[k], want[k]), (name, (H, W), k)           # ... on the rule's bytes
+        assert not np.array_equal(want[0], fs[0]) and not np.array_equal(want[1], fs[1])
+
+
 def _stroke(rng, hw, box, p=0.02):
     sk = np.zeros(hw, np.uint8)
     y0, x0, y1, x1 = box
