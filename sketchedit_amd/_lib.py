@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_feather.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -53,6 +53,9 @@ JPG2_SYMBOLS = ["se_jpg2_bound", "se_jpg2_encode_u8", "se_jpg2_encode_u8_workspa
                 "se_jpg2_code_i16_workspace_bytes"]
 SE_JPG_420, SE_JPG_OPTIMIZE = 1, 2            # the flags of include/sketchedit_jpg2.h
 JPG_TABLE_RECORD_BYTES = 1088                 # one image's four tables as se_jpg2_encode_u8 leaves them
+# every symbol declared in include/sketchedit_feather.h (the feathered paste of the editing sessions)
+FEATHER_SYMBOLS = ["se_window_paste_feather_u8"]
+FEATHER_MAX_RADIUS = 16                       # SE_FEATHER_MAX_RADIUS
 
 
 class SketchEditHipError(RuntimeError):
@@ -85,7 +88,8 @@ def build_library(force=False, verbose=False, extra_flags=()):
     from concurrent.futures import ThreadPoolExecutor
     hdrs = [os.path.join(CSRC, "se_kernels.h"), os.path.join(CSRC, "se_device.h"), os.path.join(CSRC, "se_pack.h"), os.path.join(_HERE, "..", "include", "sketchedit_hip.h"),
             os.path.join(_HERE, "..", "include", "sketchedit_png.h"), os.path.join(_HERE, "..", "include", "sketchedit_jpg.h"),
-            os.path.join(_HERE, "..", "include", "sketchedit_jpg2.h"), os.path.join(CSRC, "se_jpg_tables.h")]
+            os.path.join(_HERE, "..", "include", "sketchedit_jpg2.h"), os.path.join(_HERE, "..", "include", "sketchedit_feather.h"),
+            os.path.join(CSRC, "se_jpg_tables.h")]
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
@@ -255,6 +259,8 @@ def load_library():
         lib.se_jpg2_code_i16.restype = ci
         lib.se_jpg2_code_i16_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
         lib.se_jpg2_code_i16_workspace_bytes.restype = sz
+        lib.se_window_paste_feather_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ci, ci, ci, ci, vp, vp]
+        lib.se_window_paste_feather_u8.restype = ci
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -894,6 +900,25 @@ class Engine:
         a locked pixel: the lock enters the forward (inference_u8(lock=)) and the paste.  -> (rgb, mask_u8, hits) as there."""
         return self._edit_window((self.lib.se_edit_window_locked_u8, self.lib.se_edit_window_locked_u8_workspace_bytes),
                                  "edit_window_locked_u8", frames, origins, sketches, window_hw, H, W, locks, flags, commit, low_latency)
+
+    # ---- the feathered paste (DESIGN.md 6m) -------------------------------------------------------------------------------------
+    def window_paste_feather_u8(self, frames, origins, locks, window_hw, radius, rgb, m8):
+        """se_window_paste_feather_u8, in place: rgb (B,hs,ws,3) and m8 (B,hs,ws) uint8 on the device AT THE WINDOW'S SIZE
+        window_hw = (hs, ws) (any sides >= 16) are blended into frames[i] at origins[i] = (y0, x0) by the rule of
+        include/sketchedit_feather.h: a selected pixel (m8 > 0, not locked) takes c / n of rgb and (n - c) / n of the frame,
+        c = the selected pixels in the (2 radius + 1)^2 box around it; radius 0 .. 16, 0 = window_paste_locked_u8.  locks:
+        one (Hi,Wi) uint8 plane or None per request, or None for none.  One launch; overlapping windows of one frame are
+        refused."""
+        _check_dev_u8(rgb, m8)
+        hs, ws = (int(v) for v in window_hw)
+        B = len(frames)
+        if tuple(m8.shape) != (B, hs, ws) or tuple(rgb.shape) != (B, hs, ws, 3):
+            raise SketchEditHipError("window_paste_feather_u8: expected rgb (B,hs,ws,3), m8 (B,hs,ws) at the window's size and one "
+                                     "frame per request")
+        wins = self._windows(frames, origins)
+        ptrs = None if locks is None else self._locks(locks, frames)
+        if self.lib.se_window_paste_feather_u8(self.h, self._stream(), wins, ptrs, B, hs, ws, int(radius), _ptr(rgb), _ptr(m8)):
+            self._err("se_window_paste_feather_u8")
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------
     def sketch_tiles_u8(self, sketch_u8, tile, out=None):

@@ -10,6 +10,7 @@
 #include "../../include/sketchedit_png.h"
 #include "../../include/sketchedit_jpg.h"
 #include "../../include/sketchedit_jpg2.h"
+#include "../../include/sketchedit_feather.h"
 #include "se_kernels.h"
 #include "se_pack.h"
 
@@ -2156,6 +2157,34 @@ int se_edit_window_locked_u8(se_ctx* c, void* stream, const se_window* wins, con
   if (!locks) return fail(c, "null pointer argument: locks");
   return edit_window_locked(c, stream, wins, B, hs, ws, H, W, rgb_out, mask_u8_out, hits_out, commit, workspace, workspace_bytes,
                             flags, locks);
+}
+
+// ---- the feathered paste (include/sketchedit_feather.h) -----------------------------------------------------
+// Every check on the host, then ONE launch that reads the caller's arrays and writes the frames: no workspace, nothing for
+// SE_TEST_POISON to fill.  The window's sides take any value >= 16 (no forward runs here, so win_check's multiples of 8 do not
+// apply); the records, the windows' disjointness and the lock planes are checked as the locked paste checks them.
+int se_window_paste_feather_u8(se_ctx* c, void* stream, const se_window* wins, const unsigned char* const* locks, int B, int hs, int ws,
+                               int radius, const unsigned char* rgb, const unsigned char* mask_u8) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (B < 1 || B > 65535) return fail(c, "bad B=%d (1 .. 65535 requests per call)", B);
+  if (hs < 16 || ws < 16) return fail(c, "bad window hs=%d ws=%d (a window is at least 16 x 16 frame pixels)", hs, ws);
+  if (radius < 0 || radius > SE_FEATHER_MAX_RADIUS) return fail(c, "bad radius=%d (0 .. %d)", radius, SE_FEATHER_MAX_RADIUS);
+  if (!wins) return fail(c, "null pointer argument: wins");
+  if (!rgb || !mask_u8) return fail(c, "null pointer argument: rgb / mask_u8");
+  if ((hs + 15) / 16 > 65535 || (long long)B * hs * ws / 1024 >= (1ll << 31))
+    return fail(c, "window: B=%d window %dx%d is more than one launch takes", B, hs, ws);
+  if (win_check_records(c, wins, B, hs, ws, false) || win_check_disjoint(c, wins, B, hs, ws)) return 1;
+  const std::vector<const unsigned char*> none((size_t)B, nullptr);
+  if (!locks) locks = none.data();
+  if (win_check_locks(c, wins, locks, B)) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = (hipStream_t)stream;
+  set_profiler(&c->prof);
+  const se_window* d = win_put_locks(c, st, wins, locks, B);
+  if (!d) return 1;
+  HIPCHK(c, launch_window_paste_feather(d, rgb, mask_u8, B, hs, ws, radius, st));
+  return 0;
 }
 
 // ---- the undo journal of a session ---------------------------------------------------------------

@@ -21,7 +21,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
-                 PL_COUNT };
+                 PL_WINDOW_PASTE_FEATHER, PL_COUNT };
 const char* prof_label_name(int l);
 // Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
 // know which kernel the dispatcher chose; the label's name where the launcher has one form only
@@ -409,6 +409,11 @@ hipError_t launch_window_border(const se_window* d_wins, const unsigned char* m8
 // gains `and lock[y0 + y, x0 + x] == 0`
 hipError_t launch_window_paste(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, int B, int H, int W,
                                hipStream_t st, bool locked = false);
+// the feathered paste (include/sketchedit_feather.h; se_feather.hip): d_wins = 2 B records as for the locked paste;
+// rgb (B,hs,ws,3) and m8 (B,hs,ws) at the window's size, any hs, ws >= 16 and any alignment; radius 0 .. 16.  Only bytes of
+// selected pixels are written; no byte outside a window's own rows is read.
+hipError_t launch_window_paste_feather(const se_window* d_wins, const unsigned char* rgb, const unsigned char* m8, int B, int hs, int ws,
+                                       int radius, hipStream_t st);
 // d_wins = 2 B records as above: each plane's H x W window -> out (B,H,W) uint8 = (v > 0) in {0, 1}, zeros for a null plane;
 // W % 8 == 0, out 8-byte aligned; no byte outside a window's rows is read
 hipError_t launch_window_lock_gather(const se_window* d_wins, unsigned char* out, int B, int H, int W, hipStream_t st);

@@ -35,6 +35,8 @@ KERNEL_LABELS = {
     "(anonymous namespace)::window_gather_kernel": "window_gather", "(anonymous namespace)::window_border_kernel": "window_border",
     "(anonymous namespace)::window_paste_kernel": "window_paste",
     "window_gather_kernel": "window_gather", "window_border_kernel": "window_border", "window_paste_kernel": "window_paste",
+    # the feathered paste of a session (se_feather.hip)
+    "(anonymous namespace)::window_paste_feather_kernel": "window_paste_feather", "window_paste_feather_kernel": "window_paste_feather",
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",

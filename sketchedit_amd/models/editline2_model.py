@@ -156,6 +156,18 @@ class EditLine2Model(torch.nn.Module):
                 return eng.edit_window_scaled_u8(frames, origins, sks, (H, W), *args, **kw)
             return eng.edit_window_u8(frames, origins, sks, *args, **kw)
 
+    def window_paste_feather_u8(self, frames, origins, locks, window_hw, radius, rgb, m8):
+        """The feathered paste that belongs to an uncommitted edit_window_u8: rgb (B,H,W,3) and m8 (B,H,W) as
+        it returned them -- at a working size they are first resized to the window's (hs, ws) with Pillow's BICUBIC
+        (Engine.resize_u8), the arrays the paste of 6e is defined on -- are blended into the frames with radius 0 .. 16
+        (Engine.window_paste_feather_u8).  locks: a plane or None per request, or None."""
+        hs, ws = (int(v) for v in window_hw)
+        with torch.no_grad():
+            eng = self.engine()
+            if tuple(m8.shape[1:3]) != (hs, ws):
+                rgb, m8 = eng.resize_u8(rgb, (hs, ws)), eng.resize_u8(m8, (hs, ws))
+            eng.window_paste_feather_u8(frames, origins, locks, (hs, ws), radius, rgb, m8)
+
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
         slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""

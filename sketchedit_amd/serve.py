@@ -375,6 +375,19 @@ def _check_encode(encode):
                      "or ('jpg', quality, '444' | '420', a bool: per-image Huffman tables) (got %r)" % (JPG_QUALITY, encode))
 
 
+FEATHER_MAX_RADIUS = 16                      # the largest radius of the feathered paste (include/sketchedit_feather.h)
+
+
+def _check_feather(feather):
+    """-> None (the hard paste: None or 0) or the radius 1 .. 16 of the feathered paste"""
+    if feather is None:
+        return None
+    if not isinstance(feather, int) or isinstance(feather, bool) or not 0 <= feather <= FEATHER_MAX_RADIUS:
+        raise ValueError("feather is None or an int 0 .. %d, the radius of the paste's soft edge in frame pixels (got %r)"
+                         % (FEATHER_MAX_RADIUS, feather))
+    return int(feather) or None
+
+
 def _encoded(be, encode, frames, windows):
     """the windows of `frames` as files, by a checked `encode` that is not None: one backend call"""
     if encode == "png":
@@ -417,8 +430,11 @@ def _paste_windows(be, frames, origins, window_hw, work, locks, rgb, m8):
         be.paste(frames, origins, rgb, m8)
 
 
-def _edit_info(info, locked, work, undoable):
-    """an edit's `info` with what only some sessions report: locked (a lock plane), work (max_side), undoable (history)"""
+def _edit_info(info, locked, work, undoable, feather=None):
+    """an edit's `info` with what only some sessions report: locked (a lock plane), work (max_side), undoable (history),
+    feather (a feathered paste)"""
+    if feather is not None:
+        info["feather"] = feather
     if locked:
         info["locked"] = True
     if work is not None:
@@ -471,6 +487,12 @@ class _ModelBackend:
 
     def paste_locked(self, frames, origins, locks, window_hw, rgb, m8):
         self.model.engine().window_paste_locked_u8(frames, origins, locks, window_hw, rgb, m8)
+
+    def paste_feather(self, frames, origins, locks, window_hw, radius, rgb, m8):
+        """the feathered paste of an uncommitted run's results: rgb and m8 as `run` / `run_scaled` /
+        `run_locked` returned them (resized to the window here when they are at a working size), locks a plane or None per
+        request, or None"""
+        self.model.window_paste_feather_u8(frames, origins, locks, window_hw, radius, rgb, m8)
 
     def save(self, frames, origins, window_hw):
         """the windows' rectangles -> one new journal slot each, on the stream the edit follows on"""
@@ -730,7 +752,7 @@ class EditSession:
             if nxt != window:
                 return nxt, margin
 
-    def edit(self, sketch, window=None, max_grow=2, low_latency=None, max_side=None, encode=None):
+    def edit(self, sketch, window=None, max_grow=2, low_latency=None, max_side=None, encode=None, feather=None):
         """One edit.  `sketch`: the FULL-SIZE sketch (PIL 'L' / 2-D uint8 array, the frame's size).  The window is
         choose_window of the sketch's box, or `window` = (y0, x0, h, w) as given (then it never grows).  The forward runs on
         the window without committing; if its mask reaches an edge of the window (border counts, a side on the frame's own
@@ -753,8 +775,15 @@ class EditSession:
         are what they are without it.  "jpg" (quality 90) or ("jpg", Q), Q = 1 .. 100, returns it as a baseline JPEG file
         instead: a lossy preview several times smaller; the frame itself stays byte-exact.  ("jpg", Q, "420")
         stores chroma at half resolution and ("jpg", Q, "444" | "420", True) codes with four Huffman tables made for the patch
-        (DESIGN.md 6l): smaller files for the same decoder."""
+        (DESIGN.md 6l): smaller files for the same decoder.
+        `feather` (None or 0: everything above): the radius r = 1 .. 16, in frame pixels, of a soft edge.  No
+        run commits; the final window's result -- resized to the window when `max_side` is set -- enters the frame through
+        the feathered paste: a selected pixel (mask > 0, not locked) takes c / n of the result and (n - c) / n of the frame,
+        c = the selected pixels in the (2r + 1)^2 box around it, so exactly the pixels the hard paste writes change, the
+        interior of the mask takes the result itself and its rim fades into the frame.  A policy without a quality claim,
+        like `max_side`; info gains feather=r."""
         encode = _check_encode(encode)
+        feather = _check_feather(feather)
         sk, bbox = self._request(sketch)
         margin = 0.5
         fixed = window is not None
@@ -768,25 +797,30 @@ class EditSession:
                 y0, x0, h, w = win
                 nxt = None if fixed or reruns >= max_grow else self._grown(bbox, win, margin)
                 # a run whose counts cannot change anything commits at once: no round trip between forward and paste
-                commit = nxt is None
+                # (a feathered paste is a call of its own: no run commits)
+                last = nxt is None
+                commit = last and feather is None
                 crop = be.upload(sk[y0:y0 + h, x0:x0 + w])
                 slot = be.save([self._frame], [(y0, x0)], (h, w))[0] if commit and self._journals(h, w) else None
                 work = choose_working_size((h, w), max_side) if scaled else None
                 rgb, m8, counts = _run_windows(be, [self._frame], [(y0, x0)], [crop], (h, w), work, planes, commit, low_latency)
-                if commit or not any(counts[0]):
+                if last or not any(counts[0]):
                     break
                 win, margin = nxt
                 reruns += 1
             if not commit and self._journals(h, w):
                 slot = be.save([self._frame], [(y0, x0)], (h, w))[0]
-            if not commit:
+            if feather is not None:
+                be.paste_feather([self._frame], [(y0, x0)], planes, (h, w), feather, rgb, m8)
+            elif not commit:
                 _paste_windows(be, [self._frame], [(y0, x0)], (h, w), work, planes, rgb, m8)
             undoable = self._record(win, slot) if self.history > 0 else None
             patch = be.crop(self._frame, y0, x0, h, w) if encode is None else _encoded(be, encode, [self._frame], [(y0, x0, h, w)])[0]
         info = dict(window=win, counts=list(counts[0]), reruns=reruns, margin=margin)
-        return patch, (x0, y0), _edit_info(info, planes is not None, work, undoable)
+        return patch, (x0, y0), _edit_info(info, planes is not None, work, undoable, feather)
 
-    def edit_regions(self, sketch, low_latency=None, max_side=None, tile=32, margin=0.5, bucket=64, min_side=256, encode=None):
+    def edit_regions(self, sketch, low_latency=None, max_side=None, tile=32, margin=0.5, bucket=64, min_side=256, encode=None,
+                     feather=None):
         """One edit of SEPARATE strokes through separate windows, so that two small strokes in opposite
         corners cost two small windows, not the frame.  `sketch` as in `edit`.  The full sketch goes up once; the library's
         tile pass (se_sketch_tiles_u8; `tile` in 16 / 32 / 64) finds where it is drawn and its grid comes down -- the one
@@ -804,8 +838,10 @@ class EditSession:
         With history on the call is ONE undo step: every window's rectangle is saved in front of its group's commit and the
         entry holds all slots; if they exceed `history_bytes` together the edit commits unjournalled and clears the history.
         `encode` as in `edit`: "png", "jpg" or ("jpg", Q) returns the patches as files, encoded on the device (one backend call
-        for all)."""
+        for all).  `feather` as in `edit`: every group runs uncommitted and is pasted with ONE feathered paste,
+        behind the group's saves; the definition above holds with feather=... in each edit."""
         encode = _check_encode(encode)
+        feather = _check_feather(feather)
         sk = self._full_size(sketch)
         be = self.backend
         with self._lock:
@@ -813,12 +849,14 @@ class EditSession:
             regions = split_regions(be.tiles(plane, tile), tile, self.frame_hw, margin, bucket, min_side)
             if not regions:
                 raise ValueError("empty sketch: nothing to edit")
-            return self._edit_windows(regions, lambda wins: [be.window_of(plane, *w) for w in wins], low_latency, max_side, encode)
+            return self._edit_windows(regions, lambda wins: [be.window_of(plane, *w) for w in wins], low_latency, max_side, encode,
+                                      feather)
 
-    def _edit_windows(self, regions, crops_of, low_latency, max_side, encode=None):
+    def _edit_windows(self, regions, crops_of, low_latency, max_side, encode=None, feather=None):
         """The committing part of edit_regions and edit_strokes, with the session's lock held: `regions` = [(box, window)],
         windows pairwise disjoint; crops_of(windows of one size) -> their sketches on the device.  Groups the windows by size;
-        per group the crops, the journal's saves and ONE committing call.  -> what the two return."""
+        per group the crops, the journal's saves and ONE committing call -- with `feather` the uncommitted call, the saves
+        and ONE feathered paste.  -> what the two return."""
         be = self.backend
         scaled = max_side is not None
         lk = self._lock_plane
@@ -831,12 +869,17 @@ class EditSession:
             for (h, w), idx in groups.items():
                 frames, origins = [self._frame] * len(idx), [wins[i][:2] for i in idx]
                 crops = crops_of([wins[i] for i in idx])
+                work = choose_working_size((h, w), max_side) if scaled else None
+                planes = None if lk is None else [lk] * len(idx)
+                if feather is not None:
+                    rgb, m8, hits = _run_windows(be, frames, origins, crops, (h, w), work, planes, False, low_latency)
                 if journal:
                     for i, slot in zip(idx, be.save(frames, origins, (h, w))):
                         slots[i] = slot
-                work = choose_working_size((h, w), max_side) if scaled else None
-                planes = None if lk is None else [lk] * len(idx)
-                _, _, hits = _run_windows(be, frames, origins, crops, (h, w), work, planes, True, low_latency)
+                if feather is not None:
+                    be.paste_feather(frames, origins, planes, (h, w), feather, rgb, m8)
+                else:
+                    _, _, hits = _run_windows(be, frames, origins, crops, (h, w), work, planes, True, low_latency)
                 for i, c in zip(idx, hits):
                     counts[i], works[i] = list(c), work
         except Exception:
@@ -847,9 +890,9 @@ class EditSession:
         undoable = self._record_regions(wins, slots if journal else None) if self.history > 0 else None
         patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, [self._frame] * len(wins), wins)
         info = dict(windows=wins, boxes=[b for b, _ in regions], counts=counts, groups=len(groups))
-        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, lk is not None, works if scaled else None, undoable)
+        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, lk is not None, works if scaled else None, undoable, feather)
 
-    def edit_strokes(self, strokes, low_latency=None, max_side=None, margin=0.5, bucket=64, min_side=256, encode=None):
+    def edit_strokes(self, strokes, low_latency=None, max_side=None, margin=0.5, bucket=64, min_side=256, encode=None, feather=None):
         """One edit of strokes given as POLYLINES: `strokes` = [(points, width_px)] as stroke_segments takes
         them.  No full-size sketch exists anywhere: the host knows each stroke's box in closed form (stroke_box), merge_regions
         turns the boxes into pairwise disjoint windows exactly as edit_regions' are made, and the windows' sketches are
@@ -859,14 +902,16 @@ class EditSession:
             edit(S, window=w_k, max_grow=0, low_latency=..., max_side=...)   for every k, in any order,
         byte for byte in one pinned execution mode, S being the full-size 0 / 255 sketch the integer rule of 6i gives for
         the segments.  Everything else -- groups, lock, working size, history (ONE undo step), the return value -- is
-        edit_regions', `encode` too.  ValueError for no strokes or one stroke_segments refuses."""
+        edit_regions', `encode` and `feather` too.  ValueError for no strokes or one stroke_segments refuses."""
         encode = _check_encode(encode)
+        feather = _check_feather(feather)
         segs, ranges = stroke_segments(strokes, self.frame_hw)
         regions = merge_regions([stroke_box(segs[f:f + n], self.frame_hw) for f, n in ranges], self.frame_hw, margin, bucket, min_side)
         be = self.backend
         with self._lock:
             dsegs = be.upload(segs)
-            return self._edit_windows(regions, lambda wins: be.strokes(dsegs, self.frame_hw, wins), low_latency, max_side, encode)
+            return self._edit_windows(regions, lambda wins: be.strokes(dsegs, self.frame_hw, wins), low_latency, max_side, encode,
+                                      feather)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""
@@ -960,10 +1005,13 @@ class BatchingServer:
     two edits undoes the second; undo / redo requests of different sessions share a group, one swap launch per window size.
     Sessions bring their own lock planes too; the group keys do not know about them.  A group with at least one
     locked session runs the locked entry, with no plane for the others (whose results are what they get alone); a group
-    with none runs the entries above."""
+    with none runs the entries above.
+    `feather` (with window=True): server-wide like `max_side`, the radius of EditSession.edit(feather=...).  A
+    group always runs uncommitted; the requests that stay are pasted with ONE feathered paste launch, behind the one save
+    launch.  The group key does not change."""
 
     def __init__(self, model=None, max_batch=32, max_wait_s=0.005, models=None, mode_policy="pinned", device_io=False,
-                 window=False, max_grow=2, max_side=None):
+                 window=False, max_grow=2, max_side=None, feather=None):
         if mode_policy not in ("pinned", "by_size"):
             raise ValueError(mode_policy)
         self.mode_policy = mode_policy
@@ -980,6 +1028,9 @@ class BatchingServer:
         if max_side is not None and not self.window:
             raise ValueError("max_side is the working-size cap of window edits: it needs window=True")
         self.max_side = None if max_side is None else int(max_side)
+        self.feather = _check_feather(feather)
+        if self.feather is not None and not self.window:
+            raise ValueError("feather is the soft edge of window edits' paste: it needs window=True")
         self.model = self.models[0]
         self._has_knob = [_accepts_low_latency(m) for m in self.models]
         self.max_batch, self.max_wait_s = max_batch, max_wait_s
@@ -1106,7 +1157,8 @@ class BatchingServer:
         work = group[0][0][4:6] if self.max_side is not None else None
         low_latency = self._mode(group[0][0]) if self._has_knob[k] else None
         grown = [None if r["reruns"] >= self.max_grow else r["session"]._grown(r["bbox"], r["window"], r["margin"]) for r in reqs]
-        commit = all(g is None for g in grown)            # no request can grow: the counts decide nothing
+        # no request can grow: the counts decide nothing (a feathered paste is a call of its own: no group commits)
+        commit = all(g is None for g in grown) and self.feather is None
         frames = [r["session"]._frame for r in reqs]
         origins = [r["window"][:2] for r in reqs]
         journalled = [i for i, r in enumerate(reqs) if r["session"]._journals(h, w)]
@@ -1128,7 +1180,10 @@ class BatchingServer:
             stay = [i for i in range(len(reqs)) if grown[i] is None or not any(counts[i])]
             if not commit:
                 save([i for i in stay if i in journalled])          # (a request that is queued again journals nothing yet)
-            if not commit and stay:
+            if self.feather is not None and stay:
+                be.paste_feather([frames[i] for i in stay], [origins[i] for i in stay], [lks[i] for i in stay] if locked else None,
+                                 (h, w), self.feather, be.select(rgb, stay), be.select(m8, stay))
+            elif not commit and stay:
                 _paste_windows(be, [frames[i] for i in stay], [origins[i] for i in stay], (h, w), work,
                                [lks[i] for i in stay] if locked else None, be.select(rgb, stay), be.select(m8, stay))
             outs = [None] * len(reqs)
@@ -1137,7 +1192,7 @@ class BatchingServer:
                 y0, x0 = origins[i]
                 info = dict(window=r["window"], counts=list(counts[i]), reruns=r["reruns"], margin=r["margin"])
                 undoable = r["session"]._record(r["window"], slots.get(i)) if r["session"].history > 0 else None
-                _edit_info(info, lks[i] is not None, None if work is None else tuple(work), undoable)
+                _edit_info(info, lks[i] is not None, None if work is None else tuple(work), undoable, self.feather)
                 outs[i] = (be.crop(frames[i], y0, x0, h, w), (x0, y0), info)
         finally:
             for _, lk in locks:

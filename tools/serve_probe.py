@@ -100,6 +100,16 @@ downloads (the segment and, with per-image tables, the 1088-byte record), its PS
 the two 4:2:0 files to the same pixels, and se_profile_report's per-kernel times of one request of each form.
 
     python tools/serve_probe.py --jpg2 [--reps N] [--out FILE]
+
+--feather: the feathered paste: one 512 x 512 window edit of the 1921 x 1081 frame, without and with max_side=640
+(which leaves a 512 x 512 window at its own size: the scaled entry, nothing to resample), and the floored frame's window at
+max_side=640 (360 x 640: the resizes run), the same protocol:
+  (a) edit / edit_max_side / edit_frame_scaled: EditSession.edit(window=..., max_grow=0) without feather (the legs that are compared
+                                          with the parent commit's build, run with --feather-parent there: only these legs),
+  (b) the same three with _feather:       feather=8 -- the uncommitted run, (resampled) two resizes, one feather launch;
+plus se_profile_report's per-kernel times of one (b) request of each kind and that feather=0 leaves the frame of (a).
+
+    python tools/serve_probe.py --feather [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -658,6 +668,52 @@ def jpg2_leg(model, reps, side=512, quality=90):
     return out
 
 
+def feather_leg(model, reps, parent=False, side=512, radius=8, max_side=640):
+    """(a), (b) of the module docstring; parent=True: the legs (a) only, with the calls a build without the feathered paste has"""
+    import numpy as np
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    win = (283, 705, side, side)
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    big = (0, 0, h // 8 * 8, w // 8 * 8)
+    bsk = big_sketch(rng)
+    s1, s2 = serve.EditSession(model, frame), serve.EditSession(model, frame)
+    edit = lambda s, **kw: s.edit(sk, window=win, max_grow=0, low_latency=True, **kw)                            # noqa: E731
+    edit_big = lambda s, **kw: s.edit(bsk, window=big, max_grow=0, low_latency=True, max_side=max_side, **kw)     # noqa: E731
+    s5 = serve.EditSession(model, frame)
+    legs = dict(edit=lambda: edit(s1), edit_max_side=lambda: edit(s5, max_side=max_side), edit_frame_scaled=lambda: edit_big(s2))
+    out = dict(tool="serve_probe --feather" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               window=list(win), scaled_window=list(big), max_side=max_side)
+    if not parent:
+        s3, s4, s6 = serve.EditSession(model, frame), serve.EditSession(model, frame), serve.EditSession(model, frame)
+        legs.update(edit_feather=lambda: edit(s3, feather=radius), edit_max_side_feather=lambda: edit(s6, max_side=max_side, feather=radius),
+                    edit_frame_scaled_feather=lambda: edit_big(s4, feather=radius))
+    out["ms"] = rounds_of(legs, reps)
+    if not parent:
+        eng = model.engine()
+        kernels = {}
+        for name in ("edit_feather", "edit_frame_scaled_feather"):
+            eng.profile(True)
+            legs[name]()
+            rep = eng.profile_report()
+            eng.profile(False)
+            kernels[name] = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]
+                             if k["kernel"].startswith(("window_", "resize_"))}
+        a, b, c = serve.EditSession(model, frame), serve.EditSession(model, frame), serve.EditSession(model, frame)
+        edit(a), edit(b, feather=0), edit(c, feather=radius)
+        fa, fb, fc = a.frame(), b.frame(), c.frame()
+        out.update(radius=radius, work=list(edit_big(s4, feather=radius)[2]["work"]), window_kernels_profiled=kernels,
+                   feather_0_is_the_hard_paste=bool(np.array_equal(fa, fb)),
+                   pixels_changed=dict(hard=int((fa != frame).any(2).sum()), feather=int((fc != frame).any(2).sum()),
+                                       differ=int((fa != fc).any(2).sum())),
+                   feather_minus_hard_ms={k: round(out["ms"][k + "_feather"]["median"] - out["ms"][k]["median"], 3)
+                                          for k in ("edit", "edit_max_side", "edit_frame_scaled")})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -677,6 +733,8 @@ def main():
     ap.add_argument("--jpg", action="store_true", help="patches as JPEG, encoded on the device (see the module docstring)")
     ap.add_argument("--jpg-parent", action="store_true", help="the edit + host encoder leg of --jpg only")
     ap.add_argument("--jpg2", action="store_true", help="JPEG patches in 4:2:0 and with per-image Huffman tables (see the module docstring)")
+    ap.add_argument("--feather", action="store_true", help="the feathered paste (see the module docstring)")
+    ap.add_argument("--feather-parent", action="store_true", help="the legs of --feather without a feathered paste only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -687,8 +745,10 @@ def main():
     model = make_model(tempfile.mkdtemp())
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
-            or args.jpg or args.jpg_parent or args.jpg2):
-        if args.jpg2:
+            or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent):
+        if args.feather or args.feather_parent:
+            res = feather_leg(model, args.reps, parent=args.feather_parent)
+        elif args.jpg2:
             res = jpg2_leg(model, args.reps)
         elif args.jpg or args.jpg_parent:
             res = jpg_leg(model, args.reps, parent=args.jpg_parent)
