@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -56,6 +56,8 @@ JPG_TABLE_RECORD_BYTES = 1088                 # one image's four tables as se_jp
 # every symbol declared in include/sketchedit_feather.h (the feathered paste of the editing sessions)
 FEATHER_SYMBOLS = ["se_window_paste_feather_u8"]
 FEATHER_MAX_RADIUS = 16                       # SE_FEATHER_MAX_RADIUS
+# every symbol declared in include/sketchedit_fill.h (fills of a painted region)
+FILL_SYMBOLS = ["se_fill", "se_fill_window_u8", "se_fill_window_u8_workspace_bytes", "se_fill_keep_u8"]
 
 
 class SketchEditHipError(RuntimeError):
@@ -89,7 +91,7 @@ def build_library(force=False, verbose=False, extra_flags=()):
     hdrs = [os.path.join(CSRC, "se_kernels.h"), os.path.join(CSRC, "se_device.h"), os.path.join(CSRC, "se_pack.h"), os.path.join(_HERE, "..", "include", "sketchedit_hip.h"),
             os.path.join(_HERE, "..", "include", "sketchedit_png.h"), os.path.join(_HERE, "..", "include", "sketchedit_jpg.h"),
             os.path.join(_HERE, "..", "include", "sketchedit_jpg2.h"), os.path.join(_HERE, "..", "include", "sketchedit_feather.h"),
-            os.path.join(CSRC, "se_jpg_tables.h")]
+            os.path.join(_HERE, "..", "include", "sketchedit_fill.h"), os.path.join(CSRC, "se_jpg_tables.h")]
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
@@ -261,6 +263,14 @@ def load_library():
         lib.se_jpg2_code_i16_workspace_bytes.restype = sz
         lib.se_window_paste_feather_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ci, ci, ci, ci, vp, vp]
         lib.se_window_paste_feather_u8.restype = ci
+        lib.se_fill.argtypes = [vp, vp, c_f, c_f, vp, vp, c_f, c_f, c_f, c_f, vp, sz, ci, ci, ci, ci]
+        lib.se_fill.restype = ci
+        lib.se_fill_window_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, sz, ci]
+        lib.se_fill_window_u8.restype = ci
+        lib.se_fill_window_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci, ci]
+        lib.se_fill_window_u8_workspace_bytes.restype = sz
+        lib.se_fill_keep_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci]
+        lib.se_fill_keep_u8.restype = ci
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -919,6 +929,96 @@ class Engine:
         ptrs = None if locks is None else self._locks(locks, frames)
         if self.lib.se_window_paste_feather_u8(self.h, self._stream(), wins, ptrs, B, hs, ws, int(radius), _ptr(rgb), _ptr(m8)):
             self._err("se_window_paste_feather_u8")
+
+    # ---- fills of a painted region (include/sketchedit_fill.h) ------------------------------------------------------
+    def fill(self, image, hole, flags, sketch=None, lock=None, visualize=False, low_latency=None):
+        """se_fill: netG alone on a hole the caller gives.  image (B,3,H,W) fp32, hole (B,H,W) uint8 on the device, non-zero =
+        fill; sketch (B,1,H,W) fp32 or None (zeros); lock (B,H,W) uint8 or None -- a locked pixel is never a hole.
+        -> dict(composed[, coarse, fine, hard]) with hole = fill & ~lock in `hard`: coarse, fine = netG(image, image, hard,
+        hard, sketch) and composed = where(hard, fine, image), bit for bit.  low_latency as `inference`."""
+        import torch
+        _check_dev(image, sketch)
+        B, _, H, W = image.shape
+        for name, t in (("hole", hole), ("lock", lock)):
+            if t is not None or name == "hole":
+                _check_dev_u8(t)
+                if tuple(t.shape) != (B, H, W):
+                    raise SketchEditHipError("%s: expected a (B,H,W) uint8 plane of the images' size" % name)
+        if sketch is not None and tuple(sketch.shape) != (B, 1, H, W):
+            raise SketchEditHipError("sketch: expected a (B,1,H,W) tensor of the images' size")
+        ws = self.workspace(B, H, W)
+        mk = lambda c: torch.empty((B, c, H, W), dtype=torch.float32, device=image.device)     # noqa: E731
+        r = dict(composed=mk(3))
+        if visualize:
+            r.update(coarse=mk(3), fine=mk(3), hard=mk(1))
+        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
+        if self.lib.se_fill(self.h, self._stream(), _ptr(image), _ptr(sketch), _ptr(hole), _ptr(lock), _ptr(r["composed"]),
+                            _ptr(r.get("coarse")), _ptr(r.get("fine")), _ptr(r.get("hard")), _ptr(ws), ws.numel() // 16 * 16, B, H, W, flags):
+            self._err("se_fill")
+        return r
+
+    @staticmethod
+    def _planes(planes, frames, what, required):
+        """the HOST array of a fill call's plane pointers: one (Hi,Wi) uint8 plane per request (or None unless `required`)"""
+        if len(planes) != len(frames):
+            raise SketchEditHipError("fill call: one %s plane per request" % what)
+        for t, f in zip(planes, frames):
+            if t is None and not required:
+                continue
+            _check_dev_u8(t)
+            if tuple(t.shape) != tuple(f.shape[:2]):
+                raise SketchEditHipError("fill call: a %s plane is the frame's (Hi,Wi) uint8 plane" % what)
+        return (ctypes.c_void_p * len(planes))(*[None if t is None else t.data_ptr() for t in planes])
+
+    def fill_window_u8(self, frames, origins, sketches, holes, locks, window_hw, H, W, flags, low_latency=None):
+        """se_fill_window_u8: the fill of the (hs, ws) windows at origins[i] of resident frames with the forward at H x W (equal:
+        the frame's own resolution), ONE library call.  holes[i]: the frame's (Hi,Wi) uint8 fill plane on the device, non-zero
+        = fill; locks: a plane or None per request, or None; sketches: the window's (hs,ws) uint8 sketch or None per request,
+        or None.  Never commits.  -> (rgb (B,H,W,3), mask_u8 (B,H,W)) on the device, mask_u8 255 in the hole: what the pastes
+        take, with the keep planes of fill_keep_u8 in place of the locks."""
+        import torch
+        hs, ws = (int(v) for v in window_hw)
+        B, dev = len(frames), frames[0].device if frames else None
+        wins = self._windows(frames, origins)
+        if sketches is not None:
+            if len(sketches) != B:
+                raise SketchEditHipError("fill_window_u8: one sketch (or None) per request")
+            for i, sk in enumerate(sketches):
+                if sk is None:
+                    continue
+                _check_dev_u8(sk)
+                if tuple(sk.shape) != (hs, ws):
+                    raise SketchEditHipError("fill_window_u8: a sketch is the window's (hs,ws) uint8 plane")
+                wins[i].sketch_u8 = sk.data_ptr()
+        hp = self._planes(holes, frames, "fill", True)
+        lp = None if locks is None else self._planes(locks, frames, "lock", False)
+        need = self.lib.se_fill_window_u8_workspace_bytes(self.h, B, hs, ws, H, W)
+        if need == 0:
+            self._err("se_fill_window_u8_workspace_bytes")
+        wsp = self._workspace_bytes(need)
+        rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        m8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
+        if self.lib.se_fill_window_u8(self.h, self._stream(), wins, hp, lp, B, hs, ws, H, W, _ptr(rgb), _ptr(m8), _ptr(wsp),
+                                      wsp.numel() // 16 * 16, flags):
+            self._err("se_fill_window_u8")
+        return rgb, m8
+
+    def fill_keep_u8(self, frames, origins, holes, locks, window_hw, keeps=None):
+        """se_fill_keep_u8: the keep planes of a fill's paste -- the (hs, ws) rectangle at origins[i] of keeps[i], an (Hi,Wi)
+        uint8 plane on the device, becomes 255 where holes[i] is 0 or locks[i] is non-zero, else 0; no other byte is written.
+        keeps None: new planes, whose bytes outside the rectangle are undefined (the pastes read none of them).  -> keeps"""
+        import torch
+        hs, ws = (int(v) for v in window_hw)
+        wins = self._windows(frames, origins)
+        hp = self._planes(holes, frames, "fill", True)
+        lp = None if locks is None else self._planes(locks, frames, "lock", False)
+        if keeps is None:
+            keeps = [torch.empty(tuple(f.shape[:2]), dtype=torch.uint8, device=f.device) for f in frames]
+        kp = self._planes(keeps, frames, "keep", True)
+        if self.lib.se_fill_keep_u8(self.h, self._stream(), wins, hp, lp, kp, len(frames), hs, ws):
+            self._err("se_fill_keep_u8")
+        return keeps
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------
     def sketch_tiles_u8(self, sketch_u8, tile, out=None):

@@ -11,6 +11,7 @@
 #include "../../include/sketchedit_jpg.h"
 #include "../../include/sketchedit_jpg2.h"
 #include "../../include/sketchedit_feather.h"
+#include "../../include/sketchedit_fill.h"
 #include "se_kernels.h"
 #include "se_pack.h"
 
@@ -2184,6 +2185,183 @@ int se_window_paste_feather_u8(se_ctx* c, void* stream, const se_window* wins, c
   const se_window* d = win_put_locks(c, st, wins, locks, B);
   if (!d) return 1;
   HIPCHK(c, launch_window_paste_feather(d, rgb, mask_u8, B, hs, ws, radius, st));
+  return 0;
+}
+
+// ---- fills of a painted region (include/sketchedit_fill.h) ------------------------------------------------
+// netG alone on a hole the caller gives: hole = fill & ~lock is mask, mask2 AND the composite's soft mask of plan_netG.
+namespace {
+
+// the passes of a netG-only forward (as se_netG_forward_taps plans them): `hole` (B,H,W) fp32 is read as hard and as soft
+// mask; `tail` bytes at the end of the workspace are the caller's.  rgb8 / m8 (either may be null): the fused uint8 outputs.
+int fill_passes(se_ctx* c, void* stream, const float* image, const float* sketch, const float* hole, float* composed_out,
+                float* coarse_out, float* fine_out, unsigned char* rgb8, unsigned char* m8, void* ws, size_t ws_bytes, size_t tail, int B,
+                int H, int W, int flags) {
+  const int nb = pass_size(c, B, H, W, flags);
+  if (!nb) return 1;
+  const size_t HW = (size_t)H * W;
+  for (int b0 = 0; b0 < B; b0 += nb) {
+    const int bb = std::min(nb, B - b0);
+    if (carve(c, plan_peaks(c, 2, bb, H, W, flags, false), ws, ws_bytes, tail)) return 1;
+    begin_call(c, stream, flags);
+    c->rgb8 = rgb8 ? rgb8 + b0 * 3 * HW : nullptr; c->m8 = m8 ? m8 + b0 * HW : nullptr;
+    const float *img = image + b0 * 3 * HW, *h = hole + b0 * HW;
+    const int rc = plan_netG(c, img, img, h, h, sketch + b0 * HW, coarse_out ? coarse_out + b0 * 3 * HW : nullptr,
+                             fine_out ? fine_out + b0 * 3 * HW : nullptr, h, composed_out ? composed_out + b0 * 3 * HW : nullptr, bb, H, W,
+                             flags);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// holes: every entry given
+int fill_check_holes(se_ctx* c, const unsigned char* const* holes, int B) {
+  if (!holes) return fail(c, "null pointer argument: holes");
+  for (int i = 0; i < B; ++i)
+    if (!holes[i]) return fail(c, "holes[%d] is null", i);
+  return 0;
+}
+
+}  // namespace
+
+int se_fill(se_ctx* c, void* stream, const float* image, const float* sketch, const unsigned char* hole_u8, const unsigned char* lock_u8,
+            float* composed_out, float* coarse_out, float* fine_out, float* hard_out, void* ws, size_t ws_bytes, int B, int H, int W,
+            int flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (check_dims(c, B, H, W)) return 1;
+  if (!image) return fail(c, "null pointer argument: image");
+  if (!hole_u8) return fail(c, "null pointer argument: hole_u8");
+  if (!composed_out) return fail(c, "null pointer argument: composed_out");
+  if (!ws) return fail(c, "null pointer argument: workspace");
+  if (!aligned_to(hole_u8, 16) || !aligned_to(lock_u8, 16) || !aligned_to(hard_out, 16)) return fail(c, "hole_u8 / lock_u8 / hard_out must be 16-byte aligned");
+  if (!aligned_to(ws, 256) || (ws_bytes & 15)) return fail(c, "workspace must be 256-byte aligned and workspace_bytes a multiple of 16");
+  if (forward_enter(c)) return 1;
+  flags &= ~(SE_FLAG_GRAPH | SE_FLAG_PACKED_OUT);
+  // the hole plane and the zero sketch of a call without one live at the end of the workspace for the whole call
+  const size_t plane = pad256((size_t)B * H * W * 4), tail = 2 * plane;
+  if (ws_bytes < tail) return fail(c, "workspace too small: %zu bytes", ws_bytes);
+  float* hole = (float*)((char*)ws + ws_bytes - tail);
+  float* zero = sketch ? nullptr : (float*)((char*)ws + ws_bytes - plane);
+  const hipStream_t st = (hipStream_t)stream;
+  set_profiler(&c->prof);
+  if (poison(c, hole, tail, st)) return 1;
+  HIPCHK(c, launch_fill_masks(hole_u8, lock_u8, hole, hard_out, zero, B, H, W, st));
+  return fill_passes(c, stream, image, sketch ? sketch : zero, hole, composed_out, coarse_out, fine_out, nullptr, nullptr, ws, ws_bytes, tail,
+                     B, H, W, flags);
+}
+
+// [uint8 result | uint8 mask | working-size fill plane | working-size lock plane (a call with a lock only) | a zero (hs,ws) sketch (a
+// call with a request without one only) | intermediates of the resample end (scaled only) | the forward's part: the arenas, then
+// the fp32 hole plane, then the fp32 image (3 planes) and sketch -- where se_inference_u8io keeps them]
+size_t se_fill_window_u8_workspace_bytes(se_ctx* c, int B, int hs, int ws, int H, int W) {
+  const size_t base = se_edit_window_locked_u8_workspace_bytes(c, B, hs, ws, H, W);      // (its lock plane and its counts included)
+  return base ? base + pad256((size_t)B * H * W) + pad256((size_t)hs * ws) : 0;
+}
+
+int se_fill_window_u8(se_ctx* c, void* stream, const se_window* wins, const unsigned char* const* holes, const unsigned char* const* locks,
+                      int B, int hs, int ws, int H, int W, unsigned char* rgb_out, unsigned char* mask_u8_out, void* wsp, size_t ws_bytes,
+                      int flags) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  const bool scaled = hs != H || ws != W;
+  if (win_check(c, wins, B, H, W, hs, ws, false, false)) return 1;
+  if (fill_check_holes(c, holes, B)) return 1;
+  if (!wsp) return fail(c, "null pointer argument: workspace");
+  if (!aligned_to(wsp, 256)) return fail(c, "workspace must be 256-byte aligned");
+  if (!aligned_to(rgb_out, 4) || !aligned_to(mask_u8_out, 4)) return fail(c, "rgb_out / mask_u8_out must be 4-byte aligned");
+  if (ws_bytes & 15) return fail(c, "workspace_bytes must be a multiple of 16");
+  const bool locked = any_lock(locks, B);
+  bool bare = false;                                      // a request without a sketch
+  for (int i = 0; i < B; ++i) bare = bare || !wins[i].sketch_u8;
+  if (forward_enter(c)) return 1;
+  flags &= ~(SE_FLAG_GRAPH | SE_FLAG_PACKED_OUT);
+  const size_t plane = pad256((size_t)B * H * W * 4), rgbw = pad256((size_t)B * H * W * 3), mw = pad256((size_t)B * H * W),
+               zw = bare ? pad256((size_t)hs * ws) : 0, midw = scaled ? gather_mid_bytes(B, hs, W) : 0, lockw = locked ? mw : 0;
+  const size_t head = rgbw + mw + mw + lockw + zw + midw, tail = 5 * plane;
+  if (ws_bytes < head + tail) return fail(c, "workspace too small: %zu bytes", ws_bytes);
+  unsigned char* rgb = rgb_out ? rgb_out : (unsigned char*)wsp;
+  unsigned char* m8 = mask_u8_out ? mask_u8_out : (unsigned char*)wsp + rgbw;
+  unsigned char* fill8 = (unsigned char*)wsp + rgbw + mw;
+  unsigned char* lock8 = locked ? fill8 + mw : nullptr;
+  unsigned char* zsk = bare ? fill8 + mw + lockw : nullptr;
+  unsigned char* mid = fill8 + mw + lockw + zw;
+  char* fws = (char*)wsp + head;
+  const size_t fws_bytes = ws_bytes - head;
+  float* hole = (float*)(fws + fws_bytes - tail);
+  float* image = (float*)(fws + fws_bytes - 4 * plane);
+  float* sketch = (float*)(fws + fws_bytes - plane);
+  const hipStream_t st = (hipStream_t)stream;
+  if (scaled && rs_enter(c, st)) return 1;
+  set_profiler(&c->prof);
+  if ((!rgb_out && poison(c, rgb, rgbw, st)) || (!mask_u8_out && poison(c, m8, mw, st)) || poison(c, fill8, mw + lockw, st) ||
+      poison(c, hole, tail, st))
+    return 1;
+  // a request without a sketch reads the zero plane: the gathers at either scale then give it an all-zero sketch
+  if (bare) HIPCHK(c, hipMemsetAsync(zsk, 0, (size_t)hs * ws, st));
+  std::vector<se_window> recs(wins, wins + B);
+  for (se_window& w : recs)
+    if (!w.sketch_u8) w.sketch_u8 = zsk;
+  // one group of records per plane: the requests, then the plane's pointers (the gathers of 6g take them so)
+  const se_window* d = win_put_locks(c, st, recs.data(), holes, B);
+  if (!d) return 1;
+  if (scaled) {
+    if (gather_resize_locked(c, st, d, B, hs, ws, H, W, image, sketch, mid)) return 1;
+  } else {
+    HIPCHK(c, launch_window_gather(d, c->lut8, image, sketch, B, H, W, st));
+  }
+  if (lock_gather_locked(c, st, d, B, hs, ws, H, W, fill8, mid)) return 1;
+  if (locked) {
+    const se_window* dl = win_put_locks(c, st, recs.data(), locks, B);
+    if (!dl) return 1;
+    if (lock_gather_locked(c, st, dl, B, hs, ws, H, W, lock8, mid)) return 1;
+  }
+  HIPCHK(c, launch_fill_masks(fill8, lock8, hole, nullptr, nullptr, B, H, W, st));
+  return fill_passes(c, stream, image, sketch, hole, nullptr, nullptr, nullptr, rgb, m8, fws, fws_bytes, tail, B, H, W, flags);
+}
+
+int se_fill_keep_u8(se_ctx* c, void* stream, const se_window* wins, const unsigned char* const* holes, const unsigned char* const* locks,
+                    unsigned char* const* keeps, int B, int hs, int ws) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (B < 1 || B > 16383) return fail(c, "bad B=%d (1 .. 16383 requests per call)", B);
+  if (hs < 16 || ws < 16) return fail(c, "bad window hs=%d ws=%d (a window is at least 16 x 16 frame pixels)", hs, ws);
+  if (!wins) return fail(c, "null pointer argument: wins");
+  if ((long long)B * hs * ws / 1024 >= (1ll << 31)) return fail(c, "window: B=%d window %dx%d is more than one launch takes", B, hs, ws);
+  if (win_check_records(c, wins, B, hs, ws, false)) return 1;
+  if (fill_check_holes(c, holes, B)) return 1;
+  if (!keeps) return fail(c, "null pointer argument: keeps");
+  for (int i = 0; i < B; ++i)
+    if (!keeps[i]) return fail(c, "keeps[%d] is null", i);
+  auto meets = [](uintptr_t a0, size_t an, uintptr_t b0, size_t bn) { return a0 < b0 + bn && b0 < a0 + an; };
+  for (int i = 0; i < B; ++i) {
+    const uintptr_t k0 = (uintptr_t)keeps[i];
+    const size_t kn = (size_t)wins[i].Hi * wins[i].Wi;
+    for (int j = 0; j < B; ++j) {
+      const size_t pn = (size_t)wins[j].Hi * wins[j].Wi;
+      if (meets(k0, kn, (uintptr_t)wins[j].frame_u8, 3 * pn)) return fail(c, "keeps[%d] overlaps the frame of wins[%d]", i, j);
+      if (meets(k0, kn, (uintptr_t)holes[j], pn)) return fail(c, "keeps[%d] overlaps holes[%d]", i, j);
+      if (locks && locks[j] && meets(k0, kn, (uintptr_t)locks[j], pn)) return fail(c, "keeps[%d] overlaps locks[%d]", i, j);
+      if (j <= i || !meets(k0, kn, (uintptr_t)keeps[j], pn)) continue;
+      // two requests of one keep plane: the same plane, rectangles apart
+      const se_window &a = wins[i], &b = wins[j];
+      if (keeps[i] != keeps[j] || a.Hi != b.Hi || a.Wi != b.Wi)
+        return fail(c, "keeps[%d] and keeps[%d] overlap in memory without being the same plane", i, j);
+      if (a.y0 < b.y0 + hs && b.y0 < a.y0 + hs && a.x0 < b.x0 + ws && b.x0 < a.x0 + ws)
+        return fail(c, "keeps[%d] and keeps[%d]: overlapping rectangles of one keep plane", i, j);
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = (hipStream_t)stream;
+  set_profiler(&c->prof);
+  std::vector<se_window> recs(wins, wins + B);
+  for (int k = 0; k < 3; ++k)
+    for (int i = 0; i < B; ++i)
+      recs.push_back(se_window{k == 0 ? const_cast<unsigned char*>(holes[i]) : k == 1 ? (locks ? const_cast<unsigned char*>(locks[i]) : nullptr) : keeps[i],
+                               nullptr, 0, 0, 0, 0});
+  const se_window* d = win_put(c, st, recs.data(), 4 * B);
+  if (!d) return 1;
+  HIPCHK(c, launch_fill_keep(d, B, hs, ws, st));
   return 0;
 }
 

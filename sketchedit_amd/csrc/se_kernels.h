@@ -21,7 +21,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
-                 PL_WINDOW_PASTE_FEATHER, PL_COUNT };
+                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_COUNT };
 const char* prof_label_name(int l);
 // Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
 // know which kernel the dispatcher chose; the label's name where the launcher has one form only
@@ -431,6 +431,15 @@ hipError_t launch_sketch_tiles(const unsigned char* plane, int Hi, int Wi, int t
 // segs is safe (clamped to the rule's limits).  nseg_sum = the ranges' counts added up (the profiler's byte estimate).
 hipError_t launch_sketch_strokes(const se_window* d_wins, int B, int hs, int ws, const int* segs, long nseg_sum, unsigned char* sketch_out,
                                  hipStream_t st);
+// fills of a painted region (include/sketchedit_fill.h; se_fill.hip).  masks: fill (B,H,W) and lock (B,H,W) or null,
+// uint8, non-zero = set -> hole (B,H,W) fp32 = fill & ~lock in {0, 1}, the same into `hard` and zeros into `zero` where those are
+// not null; every pointer 16-byte aligned, H % 8 == W % 8 == 0; every float of every plane is written.
+hipError_t launch_fill_masks(const unsigned char* fill, const unsigned char* lock, float* hole, float* hard, float* zero, int B, int H,
+                             int W, hipStream_t st);
+// keep: d_wins = 4 B records -- the requests, then B records each whose frame_u8 is the request's (Hi,Wi) fill plane, lock plane
+// or null, keep plane.  The hs x ws rectangle of the keep plane = 255 where fill == 0 or lock != 0, else 0.  Any hs, ws and any
+// alignment; no byte outside the rectangle's rows is read, none outside the rectangle written.
+hipError_t launch_fill_keep(const se_window* d_wins, int B, int hs, int ws, hipStream_t st);
 // the device PNG encoder (include/sketchedit_png.h): the hs x ws rectangles of d_wins (B records) -> their zlib
 // streams.  rows: ftype (B,hs) uint8, each row's filter type.  stripes: one workgroup per stripe of 32 rows -> its deflate blocks
 // in its slot of png_slot_bytes(ws) bytes (16-byte aligned), its size in sizes (B,S) and its Adler parts in parts (B,S,2), S =

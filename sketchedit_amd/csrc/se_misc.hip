@@ -108,7 +108,8 @@ const char* prof_label_name(int l) {
                                     "att_stream_stats", "att_stream_out", "resize_h", "resize_v", "window_gather", "window_border",
                                     "window_paste", "window_resample_h", "window_paste_v", "window_save", "window_swap", "window_lock_gather",
                                     "window_paste_locked", "window_paste_v_locked", "sketch_tiles", "sketch_strokes", "png_rows", "png_stripes",
-                                    "png_finish", "jpg_blocks", "jpg_rows", "jpg_finish", "jpg2_blocks420", "jpg2_hist", "jpg2_tables", "window_paste_feather"};
+                                    "png_finish", "jpg_blocks", "jpg_rows", "jpg_finish", "jpg2_blocks420", "jpg2_hist", "jpg2_tables", "window_paste_feather",
+                                    "fill_masks", "fill_keep"};
   return (l >= 0 && l < PL_COUNT) ? n[l] : "?";
 }
 

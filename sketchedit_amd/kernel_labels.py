@@ -37,6 +37,9 @@ KERNEL_LABELS = {
     "window_gather_kernel": "window_gather", "window_border_kernel": "window_border", "window_paste_kernel": "window_paste",
     # the feathered paste of a session (se_feather.hip)
     "(anonymous namespace)::window_paste_feather_kernel": "window_paste_feather", "window_paste_feather_kernel": "window_paste_feather",
+    # fills of a painted region (se_fill.hip)
+    "(anonymous namespace)::fill_masks_kernel": "fill_masks", "(anonymous namespace)::fill_keep_kernel": "fill_keep",
+    "fill_masks_kernel": "fill_masks", "fill_keep_kernel": "fill_keep",
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",

@@ -168,6 +168,42 @@ class EditLine2Model(torch.nn.Module):
                 rgb, m8 = eng.resize_u8(rgb, (hs, ws)), eng.resize_u8(m8, (hs, ws))
             eng.window_paste_feather_u8(frames, origins, locks, (hs, ws), radius, rgb, m8)
 
+    def fill(self, image, hole, sketch=None, lock=None, visualize=False, low_latency=None):
+        """A fill (no inference entry of the reference; its generate_fake trains netG on such masks, editline2_model.py:338-370;
+        DESIGN.md 6n): netG alone on the hole the caller gives, netM never runs.  image (B,3,H,W) in [-1,1]; hole (B,H,W)
+        uint8, non-zero = fill; sketch (B,1,H,W) in {0,1} or None; lock (B,H,W) uint8 or None, non-zero = never a hole.
+        -> composed, or with visualize dict(composed, coarse, fine, hard) (Engine.fill)."""
+        if self.training:
+            raise NotImplementedError("call model.eval() first: only the eval branch of generate_fake exists here")
+        dev = torch.device("cuda", self.opt.gpu_ids[0])
+        image = image.to(dev).float().contiguous()
+        sketch = None if sketch is None else sketch.to(dev).float().contiguous()
+        hole = _lib.upload_u8(hole, dev)
+        lock = None if lock is None else _lib.upload_u8(lock, dev)
+        with torch.no_grad():
+            r = self.engine().fill(image, hole, _lib.flags_from_opt(self.opt), sketch=sketch, lock=lock, visualize=visualize,
+                                   low_latency=self._mode_for(image.shape[0], image.shape[2], image.shape[3], low_latency))
+        return r if visualize else r["composed"]
+
+    def fill_window_u8(self, frames, origins, sketches, holes, H, W, low_latency=None, work_hw=None, locks=None):
+        """The fill of windows of resident frames (serve.EditSession.fill is the caller-facing form): as
+        edit_window_u8(commit=False) with the hole taken from holes[i], the frame's (Hi,Wi) uint8 fill plane ON THE DEVICE,
+        instead of netM.  sketches[i]: the window's (H,W) uint8 sketch or None; sketches may be None.  -> (rgb, mask_u8) on the
+        device, at the working size with work_hw; nothing is pasted (Engine.fill_window_u8)."""
+        if self.training:
+            raise NotImplementedError("call model.eval() first: only the eval branch of generate_fake exists here")
+        dev = torch.device("cuda", self.opt.gpu_ids[0])
+        sks = None if sketches is None else [None if s is None else _lib.upload_u8(s, dev) for s in sketches]
+        Hw, Ww = (int(v) for v in work_hw) if work_hw is not None else (H, W)
+        with torch.no_grad():
+            return self.engine().fill_window_u8(frames, origins, sks, holes, locks, (H, W), Hw, Ww, _lib.flags_from_opt(self.opt),
+                                                low_latency=self._mode_for(len(frames), Hw, Ww, low_latency))
+
+    def fill_keep_u8(self, frames, origins, holes, locks, window_hw, keeps=None):
+        """The keep planes a fill's paste takes in place of the locks: 255 where holes[i] is 0 or locks[i] is
+        non-zero, over the window's rectangle only (Engine.fill_keep_u8)."""
+        return self.engine().fill_keep_u8(frames, origins, holes, locks, window_hw, keeps=keeps)
+
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
         slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""

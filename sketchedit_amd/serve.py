@@ -494,6 +494,17 @@ class _ModelBackend:
         request, or None"""
         self.model.window_paste_feather_u8(frames, origins, locks, window_hw, radius, rgb, m8)
 
+    def run_fill(self, frames, origins, sketches, holes, locks, window_hw, work_hw, low_latency):
+        """the fill of a group: holes[i] = the frame's fill plane on the device, sketches[i] the window's sketch
+        or None, locks a plane or None per request, or None; never commits and downloads nothing.  -> (rgb, mask_u8), at the
+        working size `work_hw` if that is not None"""
+        return self.model.fill_window_u8(frames, origins, sketches, holes, window_hw[0], window_hw[1], low_latency=low_latency,
+                                         work_hw=work_hw, locks=locks)
+
+    def fill_keep(self, frames, origins, holes, locks, window_hw):
+        """the keep planes of a fill's paste: what paste_locked / paste_feather take in place of the locks"""
+        return self.model.fill_keep_u8(frames, origins, holes, locks, window_hw)
+
     def save(self, frames, origins, window_hw):
         """the windows' rectangles -> one new journal slot each, on the stream the edit follows on"""
         return self.model.window_save_u8(frames, origins, window_hw)
@@ -912,6 +923,96 @@ class EditSession:
             dsegs = be.upload(segs)
             return self._edit_windows(regions, lambda wins: be.strokes(dsegs, self.frame_hw, wins), low_latency, max_side, encode,
                                       feather)
+
+    # ---- fills -----------------------------------------------------------------------------------------------
+    def _fill_plane(self, mask):
+        """a fill's `mask` -> the (Hi,Wi) uint8 array of 0 / 255 that is uploaded; the refusals of set_lock (an empty one is
+        refused by `fill`, which scans it for its box anyway)"""
+        if hasattr(mask, "mode"):
+            if mask.mode != "L":
+                raise ValueError("a fill mask is an 'L' image (got mode %r)" % mask.mode)
+            mask = np.asarray(mask)
+        mask = np.asarray(mask)
+        if mask.dtype != np.uint8 and mask.dtype != np.bool_:
+            raise TypeError("a fill mask is a uint8 or bool array (got %s)" % mask.dtype)
+        if mask.shape != self.frame_hw:
+            raise ValueError("a fill mask is the frame's (%d,%d) plane (got %r)" % (self.frame_hw + (mask.shape,)))
+        return np.where(mask != 0, np.uint8(255), np.uint8(0))
+
+    def _fill_window(self, box, window, margin, max_side):
+        """the window of a fill: `window` as given (checked), or choose_window of `box`, the box of painted region and sketch"""
+        if window is not None:
+            return self._check_window(window, max_side is not None)
+        return choose_window(box, self.frame_hw, margin=margin)
+
+    def _fill(self, fill_plane, crop, win, low_latency, max_side, encode, feather):
+        """The device part of fill and fill_strokes, with the session's lock held: `fill_plane` the frame-sized plane and `crop`
+        the window's sketch (or None), both on the device.  Keep plane, the forward, the journal's save, ONE paste, the
+        patch: no download in between."""
+        be = self.backend
+        scaled = max_side is not None
+        y0, x0, h, w = win
+        frames, origins = [self._frame], [(y0, x0)]
+        planes = None if self._lock_plane is None else [self._lock_plane]
+        work = choose_working_size((h, w), max_side) if scaled else None
+        keep = be.fill_keep(frames, origins, [fill_plane], planes, (h, w))
+        rgb, m8 = be.run_fill(frames, origins, [crop], [fill_plane], planes, (h, w), work, low_latency)
+        slot = be.save(frames, origins, (h, w))[0] if self._journals(h, w) else None
+        if feather is not None:
+            be.paste_feather(frames, origins, keep, (h, w), feather, rgb, m8)
+        else:
+            be.paste_locked(frames, origins, keep, (h, w), rgb, m8)
+        undoable = self._record(win, slot) if self.history > 0 else None
+        patch = be.crop(self._frame, y0, x0, h, w) if encode is None else _encoded(be, encode, frames, [win])[0]
+        return patch, (x0, y0), _edit_info(dict(window=win, fill=True), planes is not None, work, undoable, feather)
+
+    def fill(self, mask, sketch=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None, feather=None):
+        """One fill: "paint over this, fill it in".  `mask`: (Hi,Wi), a uint8 or bool array or a PIL 'L' image,
+        non-zero = fill; uploaded once per call as 0 / 255.  `sketch`: an optional FULL-SIZE sketch that guides the fill, used
+        as given (not masked by the hole).  netG alone runs, on the hole mask & ~lock: there is no mask predictor, no
+        threshold and no grow loop.  The window is choose_window of the box of mask and sketch together at `margin`, or
+        `window` = (y0, x0, h, w) as given.  The result enters the frame where the mask is painted and the lock plane
+        (set_lock) is 0, both tested in frame space: at any scale only painted, unlocked pixels can change.
+        `max_side`, `encode` and `feather` as in `edit`; with history on the call is ONE undo step.
+        -> (patch, (x0, y0), info) in `edit`'s shape, info = dict(window, fill=True) plus work / undoable / locked / feather
+        where `edit` reports them.  ValueError for an all-zero mask, a mask or sketch of another size, a bad window."""
+        encode = _check_encode(encode)
+        feather = _check_feather(feather)
+        plane = self._fill_plane(mask)
+        sk = None if sketch is None else self._full_size(sketch)
+        box = sketch_bbox(plane)
+        if box is None:
+            raise ValueError("empty mask: nothing to fill")
+        by0, bx0, by1, bx1 = box
+        sb = None if sk is None else sketch_bbox(sk)
+        if sb is not None:
+            by0, bx0, by1, bx1 = min(by0, sb[0]), min(bx0, sb[1]), max(by1, sb[2]), max(bx1, sb[3])
+        win = self._fill_window((by0, bx0, by1, bx1), window, margin, max_side)
+        y0, x0, h, w = win
+        be = self.backend
+        with self._lock:
+            return self._fill(be.upload(plane), None if sk is None else be.upload(sk[y0:y0 + h, x0:x0 + w]), win, low_latency, max_side,
+                              encode, feather)
+
+    def fill_strokes(self, strokes, sketch_strokes=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None,
+                     feather=None):
+        """`fill` with the painted region given as POLYLINES with a brush width: `strokes` (and the optional
+        `sketch_strokes` that guide the fill) = [(points, width_px)] as stroke_segments takes them.  Each set is rasterised on
+        the device into a frame-sized plane (se_sketch_strokes_u8 with the whole frame as its one window) -- nothing but the
+        segments is uploaded -- and the call proceeds as `fill` of those planes; the box is stroke_box of all segments.
+        ValueError for no strokes or one stroke_segments refuses."""
+        encode = _check_encode(encode)
+        feather = _check_feather(feather)
+        Hi, Wi = self.frame_hw
+        segs, _ = stroke_segments(strokes, self.frame_hw)
+        sk_segs = None if sketch_strokes is None else stroke_segments(sketch_strokes, self.frame_hw)[0]
+        win = self._fill_window(stroke_box(segs if sk_segs is None else np.concatenate([segs, sk_segs]), self.frame_hw), window, margin,
+                                max_side)
+        be = self.backend
+        with self._lock:
+            plane = be.strokes(be.upload(segs), self.frame_hw, [(0, 0, Hi, Wi)])[0]
+            sk = None if sk_segs is None else be.strokes(be.upload(sk_segs), self.frame_hw, [(0, 0, Hi, Wi)])[0]
+            return self._fill(plane, None if sk is None else be.window_of(sk, *win), win, low_latency, max_side, encode, feather)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""

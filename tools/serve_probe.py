@@ -110,6 +110,16 @@ max_side=640 (360 x 640: the resizes run), the same protocol:
 plus se_profile_report's per-kernel times of one (b) request of each kind and that feather=0 leaves the frame of (a).
 
     python tools/serve_probe.py --feather [--reps N] [--out FILE]
+
+--fill: fills of a painted region, netG alone: the 512 x 512 window of --feather on the 1921 x 1081 frame and the
+floored frame's window at max_side=640, the same protocol, all in one build:
+  (a) edit / edit_frame_scaled: EditSession.edit(window=..., max_grow=0) (the legs that are compared with the parent commit's
+                                build, run with --fill-parent there: only these legs),
+  (b) fill / fill_frame_scaled: EditSession.fill of a painted disc in the same window with the same sketch -- the upload of the
+                                frame-sized mask, the keep launch, the forward without netM, one locked paste;
+plus se_profile_report's per-kernel times of one request of each leg and the pixels each changes.
+
+    python tools/serve_probe.py --fill [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -714,6 +724,51 @@ def feather_leg(model, reps, parent=False, side=512, radius=8, max_side=640):
     return out
 
 
+def fill_leg(model, reps, parent=False, side=512, max_side=640):
+    """(a), (b) of the module docstring; parent=True: the legs (a) only, with the calls a build without fills has"""
+    import numpy as np
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    win = (283, 705, side, side)
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    big = (0, 0, h // 8 * 8, w // 8 * 8)
+    bsk = big_sketch(rng)
+    yy, xx = np.mgrid[0:h, 0:w]
+    disc = ((yy - (win[0] + side // 2)) ** 2 + (xx - (win[1] + side // 2)) ** 2 <= (side // 4) ** 2).astype(np.uint8) * 255
+    big_disc = ((yy - h // 2) ** 2 + (xx - w // 2) ** 2 <= (h // 4) ** 2).astype(np.uint8) * 255
+    s1, s2 = serve.EditSession(model, frame), serve.EditSession(model, frame)
+    legs = dict(edit=lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True),
+                edit_frame_scaled=lambda: s2.edit(bsk, window=big, max_grow=0, low_latency=True, max_side=max_side))
+    out = dict(tool="serve_probe --fill" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               window=list(win), scaled_window=list(big), max_side=max_side)
+    if not parent:
+        s3, s4 = serve.EditSession(model, frame), serve.EditSession(model, frame)
+        legs.update(fill=lambda: s3.fill(disc, sketch=sk, window=win, low_latency=True),
+                    fill_frame_scaled=lambda: s4.fill(big_disc, sketch=bsk, window=big, low_latency=True, max_side=max_side))
+    out["ms"] = rounds_of(legs, reps)
+    if not parent:
+        eng = model.engine()
+        kernels = {}
+        for name in legs:
+            eng.profile(True)
+            legs[name]()
+            rep = eng.profile_report()
+            eng.profile(False)
+            ks = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+            kernels[name] = dict(total_ms=round(sum(k["ms"] for k in ks.values()), 3), launches=sum(k["launches"] for k in ks.values()),
+                                 around_the_forward={n: k for n, k in ks.items() if n.startswith(("window_", "resize_", "fill_"))})
+        out.update(work=list(legs["fill_frame_scaled"]()[2]["work"]), kernels_profiled=kernels,
+                   pixels_painted=dict(fill=int((disc > 0).sum()), fill_frame_scaled=int((big_disc > 0).sum())),
+                   pixels_changed={k: int((s.frame() != frame).any(2).sum()) for k, s in (("edit", s1), ("edit_frame_scaled", s2), ("fill", s3),
+                                                                                          ("fill_frame_scaled", s4))},
+                   fill_minus_edit_ms={k: round(out["ms"][k.replace("edit", "fill")]["median"] - out["ms"][k]["median"], 3)
+                                       for k in ("edit", "edit_frame_scaled")})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -735,6 +790,8 @@ def main():
     ap.add_argument("--jpg2", action="store_true", help="JPEG patches in 4:2:0 and with per-image Huffman tables (see the module docstring)")
     ap.add_argument("--feather", action="store_true", help="the feathered paste (see the module docstring)")
     ap.add_argument("--feather-parent", action="store_true", help="the legs of --feather without a feathered paste only")
+    ap.add_argument("--fill", action="store_true", help="fills of a painted region (see the module docstring)")
+    ap.add_argument("--fill-parent", action="store_true", help="the edit legs of --fill only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -745,8 +802,10 @@ def main():
     model = make_model(tempfile.mkdtemp())
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
-            or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent):
-        if args.feather or args.feather_parent:
+            or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent):
+        if args.fill or args.fill_parent:
+            res = fill_leg(model, args.reps, parent=args.fill_parent)
+        elif args.feather or args.feather_parent:
             res = feather_leg(model, args.reps, parent=args.feather_parent)
         elif args.jpg2:
             res = jpg2_leg(model, args.reps)
