@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -58,6 +58,9 @@ FEATHER_SYMBOLS = ["se_window_paste_feather_u8"]
 FEATHER_MAX_RADIUS = 16                       # SE_FEATHER_MAX_RADIUS
 # every symbol declared in include/sketchedit_fill.h (fills of a painted region)
 FILL_SYMBOLS = ["se_fill", "se_fill_window_u8", "se_fill_window_u8_workspace_bytes", "se_fill_keep_u8"]
+# every symbol declared in include/sketchedit_select.h (selection by colour)
+SELECT_SYMBOLS = ["se_select_similar_u8", "se_select_flood_u8", "se_select_grow_u8"]
+SELECT_MAX_GROW, SELECT_MAX_PASSES = 16, 64   # SE_SELECT_MAX_GROW, SE_SELECT_MAX_PASSES
 
 
 class SketchEditHipError(RuntimeError):
@@ -91,7 +94,8 @@ def build_library(force=False, verbose=False, extra_flags=()):
     hdrs = [os.path.join(CSRC, "se_kernels.h"), os.path.join(CSRC, "se_device.h"), os.path.join(CSRC, "se_pack.h"), os.path.join(_HERE, "..", "include", "sketchedit_hip.h"),
             os.path.join(_HERE, "..", "include", "sketchedit_png.h"), os.path.join(_HERE, "..", "include", "sketchedit_jpg.h"),
             os.path.join(_HERE, "..", "include", "sketchedit_jpg2.h"), os.path.join(_HERE, "..", "include", "sketchedit_feather.h"),
-            os.path.join(_HERE, "..", "include", "sketchedit_fill.h"), os.path.join(CSRC, "se_jpg_tables.h")]
+            os.path.join(_HERE, "..", "include", "sketchedit_fill.h"), os.path.join(_HERE, "..", "include", "sketchedit_select.h"),
+            os.path.join(CSRC, "se_jpg_tables.h")]
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
@@ -271,6 +275,12 @@ def load_library():
         lib.se_fill_window_u8_workspace_bytes.restype = sz
         lib.se_fill_keep_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci]
         lib.se_fill_keep_u8.restype = ci
+        lib.se_select_similar_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+        lib.se_select_similar_u8.restype = ci
+        lib.se_select_flood_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+        lib.se_select_flood_u8.restype = ci
+        lib.se_select_grow_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+        lib.se_select_grow_u8.restype = ci
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -1019,6 +1029,61 @@ class Engine:
         if self.lib.se_fill_keep_u8(self.h, self._stream(), wins, hp, lp, kp, len(frames), hs, ws):
             self._err("se_fill_keep_u8")
         return keeps
+
+    # ---- selection by colour (include/sketchedit_select.h) ----------------------------------------------------------
+    @staticmethod
+    def _state_plane(t, what):
+        _check_dev_u8(t)
+        if t.dim() != 2:
+            raise SketchEditHipError("%s: an (Hi,Wi) uint8 plane on the device" % what)
+        return int(t.shape[0]), int(t.shape[1])
+
+    def select_similar_u8(self, frame, seed, tolerance, contiguous, state=None):
+        """se_select_similar_u8: frame (Hi,Wi,3) uint8 on the device, seed = (y, x) -> the state plane (Hi,Wi) uint8 there: 255 at
+        the seed; elsewhere, where max_c |frame[y, x, c] - frame[seed, c]| <= tolerance, 1 if `contiguous` else 255; 0 for every
+        other pixel.  `state`: a plane of that shape to write into, any alignment (every byte is written)."""
+        import torch
+        _check_dev_u8(frame)
+        if frame.dim() != 3 or frame.shape[2] != 3:
+            raise SketchEditHipError("select_similar_u8: a frame is an (Hi,Wi,3) uint8 tensor")
+        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
+        if state is None:
+            state = torch.empty((Hi, Wi), dtype=torch.uint8, device=frame.device)
+        if self._state_plane(state, "select_similar_u8: state") != (Hi, Wi):
+            raise SketchEditHipError("select_similar_u8: the state plane is the frame's (Hi,Wi) plane")
+        if self.lib.se_select_similar_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, int(seed[0]), int(seed[1]), int(tolerance),
+                                         1 if contiguous else 0, _ptr(state)):
+            self._err("se_select_similar_u8")
+        return state
+
+    def select_flood_u8(self, state, passes=8, changed=None):
+        """se_select_flood_u8: `passes` (1 .. 64) passes over the state plane, in place: a byte of 1 next to a reached byte
+        becomes 255, closed over every 64 x 64 tile.  -> `changed`, (passes,) int32 on the device (`changed`: a tensor of that
+        shape to write into): 1 where that pass stored a byte, else 0.  A 0 says the plane is at its fixed point."""
+        import torch
+        Hi, Wi = self._state_plane(state, "select_flood_u8: state")
+        passes = int(passes)
+        if changed is None and passes > 0:
+            changed = torch.empty((passes,), dtype=torch.int32, device=state.device)
+        if changed is not None and not (isinstance(changed, torch.Tensor) and changed.is_cuda and changed.dtype == torch.int32
+                                        and changed.is_contiguous() and changed.numel() == passes):
+            raise SketchEditHipError("select_flood_u8: changed is a contiguous (passes,) int32 CUDA(HIP) tensor")
+        if self.lib.se_select_flood_u8(self.h, self._stream(), _ptr(state), Hi, Wi, passes, _ptr(changed)):
+            self._err("se_select_flood_u8")
+        return changed
+
+    def select_grow_u8(self, state, grow, out=None):
+        """se_select_grow_u8: the state plane -> a fill plane (Hi,Wi) uint8 on the device (`out`: another plane of that shape,
+        any alignment; every byte is written): 255 where a byte of 255 lies within Chebyshev distance `grow` (0 .. 16), else 0."""
+        import torch
+        Hi, Wi = self._state_plane(state, "select_grow_u8: state")
+        if out is None:
+            out = torch.empty((Hi, Wi), dtype=torch.uint8, device=state.device)
+        if self._state_plane(out, "select_grow_u8: out") != (Hi, Wi):
+            raise SketchEditHipError("select_grow_u8: out is a plane of the state's shape")
+        if self.lib.se_select_grow_u8(self.h, self._stream(), _ptr(state), Hi, Wi, int(grow), _ptr(out)):
+            self._err("se_select_grow_u8")
+        return out
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------
     def sketch_tiles_u8(self, sketch_u8, tile, out=None):

@@ -12,6 +12,7 @@
 #include "../../include/sketchedit_jpg2.h"
 #include "../../include/sketchedit_feather.h"
 #include "../../include/sketchedit_fill.h"
+#include "../../include/sketchedit_select.h"
 #include "se_kernels.h"
 #include "se_pack.h"
 
@@ -2362,6 +2363,75 @@ int se_fill_keep_u8(se_ctx* c, void* stream, const se_window* wins, const unsign
   const se_window* d = win_put(c, st, recs.data(), 4 * B);
   if (!d) return 1;
   HIPCHK(c, launch_fill_keep(d, B, hs, ws, st));
+  return 0;
+}
+
+// ---- selection by colour (include/sketchedit_select.h) ------------------------------------------------------
+// Every check on the host, then launches that write the caller's planes directly: no workspace, nothing for SE_TEST_POISON to
+// fill.
+namespace {
+
+int select_check_plane(se_ctx* c, int Hi, int Wi) {
+  if (Hi < 16 || Wi < 16) return fail(c, "bad Hi=%d Wi=%d (a state plane is at least 16 x 16)", Hi, Wi);
+  // the largest grid of the three kernels: the grow's 64 x 16 tiles
+  if ((long long)Hi * Wi > (1ll << 40) || (long long)((Hi + 15) / 16) * ((Wi + 63) / 64) >= (1ll << 31))
+    return fail(c, "select: Hi=%d Wi=%d is more than one launch takes", Hi, Wi);
+  return 0;
+}
+
+bool select_meets(const void* a, size_t an, const void* b, size_t bn) {
+  return (uintptr_t)a < (uintptr_t)b + bn && (uintptr_t)b < (uintptr_t)a + an;
+}
+
+}  // namespace
+
+int se_select_similar_u8(se_ctx* c, void* stream, const unsigned char* frame_u8, int Hi, int Wi, int seed_y, int seed_x, int tolerance,
+                         int contiguous, unsigned char* state_u8) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (select_check_plane(c, Hi, Wi)) return 1;
+  if (!frame_u8) return fail(c, "null pointer argument: frame_u8");
+  if (!state_u8) return fail(c, "null pointer argument: state_u8");
+  if (seed_y < 0 || seed_y >= Hi || seed_x < 0 || seed_x >= Wi)
+    return fail(c, "seed_y=%d seed_x=%d: the seed lies outside the frame (Hi=%d Wi=%d)", seed_y, seed_x, Hi, Wi);
+  if (tolerance < 0 || tolerance > 255) return fail(c, "bad tolerance=%d (0 .. 255)", tolerance);
+  const size_t n = (size_t)Hi * Wi;
+  if (select_meets(state_u8, n, frame_u8, 3 * n)) return fail(c, "state_u8 overlaps frame_u8");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  HIPCHK(c, launch_select_similar(frame_u8, Hi, Wi, seed_y, seed_x, tolerance, contiguous ? 1 : 0, state_u8, (hipStream_t)stream));
+  return 0;
+}
+
+int se_select_flood_u8(se_ctx* c, void* stream, unsigned char* state_u8, int Hi, int Wi, int passes, unsigned* changed_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (select_check_plane(c, Hi, Wi)) return 1;
+  if (!state_u8) return fail(c, "null pointer argument: state_u8");
+  if (!changed_out) return fail(c, "null pointer argument: changed_out");
+  if (passes < 1 || passes > SE_SELECT_MAX_PASSES) return fail(c, "bad passes=%d (1 .. %d)", passes, SE_SELECT_MAX_PASSES);
+  if (!aligned_to(changed_out, 4)) return fail(c, "changed_out must be 4-byte aligned");
+  if (select_meets(changed_out, (size_t)passes * sizeof(unsigned), state_u8, (size_t)Hi * Wi)) return fail(c, "changed_out overlaps state_u8");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = (hipStream_t)stream;
+  set_profiler(&c->prof);
+  HIPCHK(c, hipMemsetAsync(changed_out, 0, (size_t)passes * sizeof(unsigned), st));
+  for (int p = 0; p < passes; ++p) HIPCHK(c, launch_select_flood(state_u8, Hi, Wi, changed_out + p, st));
+  return 0;
+}
+
+int se_select_grow_u8(se_ctx* c, void* stream, const unsigned char* state_u8, int Hi, int Wi, int grow, unsigned char* plane_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (select_check_plane(c, Hi, Wi)) return 1;
+  if (!state_u8) return fail(c, "null pointer argument: state_u8");
+  if (!plane_out) return fail(c, "null pointer argument: plane_out");
+  if (grow < 0 || grow > SE_SELECT_MAX_GROW) return fail(c, "bad grow=%d (0 .. %d)", grow, SE_SELECT_MAX_GROW);
+  const size_t n = (size_t)Hi * Wi;
+  if (select_meets(plane_out, n, state_u8, n)) return fail(c, "plane_out overlaps state_u8");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  HIPCHK(c, launch_select_grow(state_u8, Hi, Wi, grow, plane_out, (hipStream_t)stream));
   return 0;
 }
 

@@ -21,7 +21,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
-                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_COUNT };
+                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW, PL_COUNT };
 const char* prof_label_name(int l);
 // Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
 // know which kernel the dispatcher chose; the label's name where the launcher has one form only
@@ -440,6 +440,15 @@ hipError_t launch_fill_masks(const unsigned char* fill, const unsigned char* loc
 // or null, keep plane.  The hs x ws rectangle of the keep plane = 255 where fill == 0 or lock != 0, else 0.  Any hs, ws and any
 // alignment; no byte outside the rectangle's rows is read, none outside the rectangle written.
 hipError_t launch_fill_keep(const se_window* d_wins, int B, int hs, int ws, hipStream_t st);
+// selection by colour (include/sketchedit_select.h; se_select.hip), on a state plane (Hi,Wi) uint8: 0 not similar,
+// 1 similar and not reached, 255 reached.  Any Hi, Wi and any alignment; no byte outside a plane or the frame is read or written.
+// similar: every byte of `state` written from the frame (Hi,Wi,3) and the seed's colour, read on the device.
+hipError_t launch_select_similar(const unsigned char* frame, int Hi, int Wi, int seed_y, int seed_x, int tolerance, int contiguous,
+                                 unsigned char* state, hipStream_t st);
+// flood: ONE pass, a wave per 64 x 64 tile; stores 255 to newly reached bytes and 1 to *changed if it stored any (never 0)
+hipError_t launch_select_flood(unsigned char* state, int Hi, int Wi, unsigned* changed, hipStream_t st);
+// grow: out (another buffer) = 255 where a reached byte lies within Chebyshev distance `grow` (0 .. 16), else 0; every byte written
+hipError_t launch_select_grow(const unsigned char* state, int Hi, int Wi, int grow, unsigned char* out, hipStream_t st);
 // the device PNG encoder (include/sketchedit_png.h): the hs x ws rectangles of d_wins (B records) -> their zlib
 // streams.  rows: ftype (B,hs) uint8, each row's filter type.  stripes: one workgroup per stripe of 32 rows -> its deflate blocks
 // in its slot of png_slot_bytes(ws) bytes (16-byte aligned), its size in sizes (B,S) and its Adler parts in parts (B,S,2), S =

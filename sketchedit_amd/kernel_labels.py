@@ -40,6 +40,10 @@ KERNEL_LABELS = {
     # fills of a painted region (se_fill.hip)
     "(anonymous namespace)::fill_masks_kernel": "fill_masks", "(anonymous namespace)::fill_keep_kernel": "fill_keep",
     "fill_masks_kernel": "fill_masks", "fill_keep_kernel": "fill_keep",
+    # selection by colour (se_select.hip)
+    "(anonymous namespace)::select_similar_kernel": "select_similar", "(anonymous namespace)::select_flood_kernel": "select_flood",
+    "(anonymous namespace)::select_grow_kernel": "select_grow",
+    "select_similar_kernel": "select_similar", "select_flood_kernel": "select_flood", "select_grow_kernel": "select_grow",
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",

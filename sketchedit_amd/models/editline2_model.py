@@ -204,6 +204,21 @@ class EditLine2Model(torch.nn.Module):
         non-zero, over the window's rectangle only (Engine.fill_keep_u8)."""
         return self.engine().fill_keep_u8(frames, origins, holes, locks, window_hw, keeps=keeps)
 
+    def select_similar_u8(self, frame, seed, tolerance, contiguous, state=None):
+        """Selection by colour (serve.EditSession.select_similar is the caller-facing form): the state plane of a
+        resident frame and a seed (y, x) -- 255 at the seed, 1 (contiguous) or 255 where a pixel's colour is within
+        `tolerance` of the seed's in every channel, else 0 (Engine.select_similar_u8)."""
+        return self.engine().select_similar_u8(frame, seed, tolerance, contiguous, state=state)
+
+    def select_flood_u8(self, state, passes=8, changed=None):
+        """`passes` flood passes over a state plane, in place -> the (passes,) int32 `changed` words on the device, 0 from the
+        first pass that stored nothing (Engine.select_flood_u8)."""
+        return self.engine().select_flood_u8(state, passes=passes, changed=changed)
+
+    def select_grow_u8(self, state, grow, out=None):
+        """A state plane -> the fill plane: 255 within Chebyshev distance `grow` of a reached byte (Engine.select_grow_u8)."""
+        return self.engine().select_grow_u8(state, grow, out=out)
+
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
         slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""

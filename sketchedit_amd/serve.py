@@ -444,6 +444,37 @@ def _edit_info(info, locked, work, undoable, feather=None):
     return info
 
 
+SELECT_PASSES = 8            # flood passes per library call, and per download of their `changed` words
+SELECT_MAX_GROW = 16         # SE_SELECT_MAX_GROW
+
+
+def tiles_box(tiles):
+    """The tile records of a plane (se_sketch_tiles_u8: [count, y0, x0, y1, x1] per tile) -> (box, count): the tight box
+    (y0, x0, y1, x1), half open, of its pixels > 0 and their number; (None, 0) for an empty plane.  Pure host arithmetic."""
+    t = np.asarray(tiles).reshape(-1, 5)
+    t = t[t[:, 0] > 0]
+    if t.shape[0] == 0:
+        return None, 0
+    return (int(t[:, 1].min()), int(t[:, 2].min()), int(t[:, 3].max()), int(t[:, 4].max())), int(t[:, 0].sum())
+
+
+class Selection:
+    """A selection of an editing session: a frame-sized mask that lives on the device.  `.plane`: the (Hi,Wi)
+    uint8 fill plane there, 255 = selected; `.box` = (y0, x0, y1, x1), half open, its tight box; `.count` its pixels;
+    `.frame_hw` the size of the frame it was made on.  A selection is a mask, not a view of the frame: it stays what it is
+    when the frame changes."""
+
+    def __init__(self, backend, plane, box, count, frame_hw):
+        self._backend = backend
+        self.plane, self.box, self.count, self.frame_hw = plane, tuple(int(v) for v in box), int(count), tuple(frame_hw)
+
+    def mask(self):
+        """the box's crop of the plane as a (y1 - y0, x1 - x0) uint8 array of 0 / 255 on the host (a download of the box only):
+        what a front end outlines"""
+        y0, x0, y1, x1 = self.box
+        return self._backend.crop(self.plane, y0, x0, y1 - y0, x1 - x0)
+
+
 class _ModelBackend:
     """The device side of an editing session: an EditLine2Model's engine and torch for the copies.  (A seam: the host
     logic of EditSession and of the window batcher is tested against a scripted stand-in.)"""
@@ -504,6 +535,23 @@ class _ModelBackend:
     def fill_keep(self, frames, origins, holes, locks, window_hw):
         """the keep planes of a fill's paste: what paste_locked / paste_feather take in place of the locks"""
         return self.model.fill_keep_u8(frames, origins, holes, locks, window_hw)
+
+    def select_similar(self, frame, seed, tolerance, contiguous, grow):
+        """the selection by colour of a resident frame, made on the device: the state plane, if `contiguous`
+        flood calls of SELECT_PASSES passes each until one reports a pass that stored nothing -- each call's `changed` words
+        are ONE download, the only ones in front of the tile records -- then the grow and the records of its plane.
+        -> (plane, box, count): the frame-sized fill plane on the device, its tight box (y0, x0, y1, x1) and its pixels"""
+        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
+        state = self.model.select_similar_u8(frame, seed, tolerance, contiguous)
+        if contiguous:
+            passes = 0
+            while 0 not in self.model.select_flood_u8(state, passes=SELECT_PASSES).cpu().tolist():
+                passes += SELECT_PASSES
+                if passes > Hi * Wi:             # every productive pass reaches a pixel at least
+                    raise RuntimeError("select_similar: %d passes over a %dx%d frame without a fixed point" % (passes, Wi, Hi))
+        plane = self.model.select_grow_u8(state, grow)
+        box, count = tiles_box(self.tiles(plane, 32))
+        return plane, box, count
 
     def save(self, frames, origins, window_hw):
         """the windows' rectangles -> one new journal slot each, on the stream the edit follows on"""
@@ -1013,6 +1061,94 @@ class EditSession:
             plane = be.strokes(be.upload(segs), self.frame_hw, [(0, 0, Hi, Wi)])[0]
             sk = None if sk_segs is None else be.strokes(be.upload(sk_segs), self.frame_hw, [(0, 0, Hi, Wi)])[0]
             return self._fill(plane, None if sk is None else be.window_of(sk, *win), win, low_latency, max_side, encode, feather)
+
+    # ---- selection by colour ------------------------------------------------------------------------------------
+    def _check_select(self, seed, tolerance, grow):
+        """-> (seed, tolerance, grow) as ints; the refusals of a selection, all in front of the first backend call"""
+        def integer(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+        try:
+            sy, sx = seed
+        except (TypeError, ValueError):
+            raise ValueError("seed is (y, x), a pixel of the frame (got %r)" % (seed,))
+        Hi, Wi = self.frame_hw
+        if not (integer(sy) and integer(sx)) or not (0 <= sy < Hi and 0 <= sx < Wi):
+            raise ValueError("seed is (y, x), two ints inside the %dx%d frame (got %r)" % (Wi, Hi, seed))
+        if not integer(tolerance) or not 0 <= tolerance <= 255:
+            raise ValueError("tolerance is an int 0 .. 255, the largest difference in any channel (got %r)" % (tolerance,))
+        if not integer(grow) or not 0 <= grow <= SELECT_MAX_GROW:
+            raise ValueError("grow is an int 0 .. %d, in frame pixels (got %r)" % (SELECT_MAX_GROW, grow))
+        return (int(sy), int(sx)), int(tolerance), int(grow)
+
+    def _check_fill_args(self, box, sketch, window, margin, max_side):
+        """what a fill of a selection refuses before its first backend call: a sketch of another size, a bad window or margin
+        (tried on `box`), a bad max_side.  -> the sketch as an array, or None"""
+        sk = None if sketch is None else self._full_size(sketch)
+        self._fill_window(box, window, margin, max_side)
+        if max_side is not None:
+            choose_working_size((16, 16), max_side)
+        return sk
+
+    def _select(self, seed, tolerance, contiguous, grow):
+        """with the session's lock held: ONE backend call"""
+        plane, box, count = self.backend.select_similar(self._frame, seed, tolerance, bool(contiguous), grow)
+        return Selection(self.backend, plane, box, count, self.frame_hw)
+
+    def _fill_selected(self, selection, sk, window, margin, low_latency, max_side, encode, feather):
+        """with the session's lock held: `_fill` of the selection's plane through the window of its box united with the
+        sketch's"""
+        by0, bx0, by1, bx1 = selection.box
+        sb = None if sk is None else sketch_bbox(sk)
+        if sb is not None:
+            by0, bx0, by1, bx1 = min(by0, sb[0]), min(bx0, sb[1]), max(by1, sb[2]), max(bx1, sb[3])
+        win = self._fill_window((by0, bx0, by1, bx1), window, margin, max_side)
+        y0, x0, h, w = win
+        crop = None if sk is None else self.backend.upload(sk[y0:y0 + h, x0:x0 + w])
+        patch, pos, info = self._fill(selection.plane, crop, win, low_latency, max_side, encode, feather)
+        info["selected"] = selection.count
+        return patch, pos, info
+
+    def select_similar(self, seed, tolerance=16, contiguous=True, grow=0):
+        """"Click on it" (DESIGN.md 6o): the pixels whose colour is within `tolerance` (0 .. 255) of the pixel at `seed` =
+        (y, x) in every channel -- with `contiguous` only those 4-connected to the seed through such pixels (diagonals do not
+        connect) -- and every pixel within `grow` (0 .. 16) pixels of one, to cover an object's soft edge.  Made on the
+        device from the resident frame: nothing frame-sized moves; what comes down are the flood's pass flags and the tile
+        records the box is made of.  The lock plane plays no part: a fill of the selection respects it as every fill does.
+        -> Selection (.box, .count, .plane, .mask()).  Not an edit: nothing is journalled.  ValueError for a seed outside the
+        frame or not two ints, a tolerance or grow outside its range."""
+        seed, tolerance, grow = self._check_select(seed, tolerance, grow)
+        with self._lock:
+            return self._select(seed, tolerance, contiguous, grow)
+
+    def fill_selection(self, selection, sketch=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None, feather=None):
+        """`fill` of a Selection: its plane is on the device already, so only the optional sketch's window goes
+        up.  The window is choose_window of the selection's box united with the sketch's at `margin`, or `window` as given;
+        everything else -- netG alone on selection & ~lock, the paste in frame space, `max_side`, `encode`, `feather`, ONE undo
+        step -- is `fill`'s.  -> what `fill` returns, with info["fill"] = True and info["selected"] = the selection's pixels.
+        ValueError for a selection made on a frame of another size and for what `fill` refuses."""
+        encode = _check_encode(encode)
+        feather = _check_feather(feather)
+        if not isinstance(selection, Selection):
+            raise TypeError("fill_selection takes what select_similar returned (got %s)" % type(selection).__name__)
+        if tuple(selection.frame_hw) != self.frame_hw:
+            raise ValueError("the selection was made on a %dx%d frame, this one is %dx%d"
+                             % (selection.frame_hw[1], selection.frame_hw[0], self.frame_hw[1], self.frame_hw[0]))
+        sk = self._check_fill_args(selection.box, sketch, window, margin, max_side)
+        with self._lock:
+            return self._fill_selected(selection, sk, window, margin, low_latency, max_side, encode, feather)
+
+    def fill_similar(self, seed, tolerance=16, contiguous=True, grow=2, sketch=None, window=None, margin=0.5, low_latency=None,
+                     max_side=None, encode=None, feather=None):
+        """select_similar(seed, tolerance, contiguous, grow) and fill_selection of the result under ONE hold of the session's
+        lock: "click on it, fill it in".  Nothing frame-sized crosses the bus in either direction.
+        -> what fill_selection returns; ONE undo step.  Every ValueError comes before the first backend call."""
+        encode = _check_encode(encode)
+        feather = _check_feather(feather)
+        seed, tolerance, grow = self._check_select(seed, tolerance, grow)
+        sk = self._check_fill_args((seed[0], seed[1], seed[0] + 1, seed[1] + 1), sketch, window, margin, max_side)
+        with self._lock:
+            return self._fill_selected(self._select(seed, tolerance, contiguous, grow), sk, window, margin, low_latency, max_side,
+                                       encode, feather)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""

@@ -120,6 +120,20 @@ floored frame's window at max_side=640, the same protocol, all in one build:
 plus se_profile_report's per-kernel times of one request of each leg and the pixels each changes.
 
     python tools/serve_probe.py --fill [--reps N] [--out FILE]
+
+--select: the selection by colour: a flat-coloured disc of about 50 000 pixels on noise in the 1921 x 1081 frame,
+filled through the 512 x 512 window of --fill, the same protocol, all in one build; the frame is put back (a device copy, not
+timed) in front of every timed call, because a fill changes the colour under the seed:
+  (a) edit:         EditSession.edit(window=..., max_grow=0), the unchanged control (run with --select-parent on the parent
+                    commit's build: only this leg),
+  (b) fill_similar: EditSession.fill_similar(seed, grow=2, window=...) -- state plane, flood passes, grow and tile records on the
+                    device, then the fill; nothing frame-sized crosses the bus,
+  (c) host_route:   session.frame() (the 6 MB download), the flood and the grow on the host (scipy.ndimage where it is installed,
+                    else plain numpy), EditSession.fill(mask, window=...) (the 2 MB upload),
+plus the host route's three parts timed alone, the passes the disc took, that (b) and (c) leave the same frame, and
+se_profile_report's per-kernel times of one (b) request.
+
+    python tools/serve_probe.py --select [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -769,6 +783,131 @@ def fill_leg(model, reps, parent=False, side=512, max_side=640):
     return out
 
 
+def host_select(frame, seed, tolerance, grow):
+    """the selection of DESIGN.md 6o on the host -> (mask (H,W) uint8 of 0 / 255, the route's name)"""
+    import numpy as np
+    sim = np.abs(frame.astype(np.int16) - frame[seed[0], seed[1]].astype(np.int16)).max(axis=2) <= tolerance
+    try:
+        from scipy import ndimage
+        labels, _ = ndimage.label(sim)
+        reached = labels == labels[seed[0], seed[1]]
+        if grow:
+            reached = ndimage.maximum_filter(reached.view(np.uint8), size=2 * grow + 1, mode="constant") > 0
+        return np.where(reached, np.uint8(255), np.uint8(0)), "scipy.ndimage"
+    except ImportError:
+        pass
+    reached = np.zeros(sim.shape, bool)
+    reached[seed[0], seed[1]] = True
+    for step in range(sim.size):
+        near = reached.copy()
+        near[1:] |= reached[:-1]
+        near[:-1] |= reached[1:]
+        near[:, 1:] |= reached[:, :-1]
+        near[:, :-1] |= reached[:, 1:]
+        near &= sim
+        if step and np.array_equal(near, reached):
+            break
+        reached = near | reached
+    out = reached.copy()
+    for _ in range(grow):                      # r steps of the 3 x 3 box = the (2r + 1)^2 box
+        g = out.copy()
+        g[1:] |= out[:-1]
+        g[:-1] |= out[1:]
+        out = g.copy()
+        out[:, 1:] |= g[:, :-1]
+        out[:, :-1] |= g[:, 1:]
+    return np.where(out, np.uint8(255), np.uint8(0)), "numpy"
+
+
+def select_leg(model, reps, parent=False, side=512, tolerance=16, grow=2):
+    """(a), (b), (c) of the module docstring; parent=True: the leg (a) only, with the calls a build without selections has"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    frame[..., 0] = frame[..., 0] % 90                               # no noise pixel is similar to the disc's colour
+    win = (283, 705, side, side)
+    seed = (win[0] + side // 2, win[1] + side // 2)
+    yy, xx = np.mgrid[0:h, 0:w]
+    disc = (yy - seed[0]) ** 2 + (xx - seed[1]) ** 2 <= 126 ** 2
+    frame[disc] = 128
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    dev0 = torch.from_numpy(frame).cuda()
+
+    def fresh(session):
+        def put_back():
+            session._frame.copy_(dev0)
+            torch.cuda.synchronize()
+        return put_back
+
+    def timed(fn, put_back):
+        def rounds():
+            for _ in range(2):                 # warm-up: plans, workspace, code objects
+                put_back()
+                fn()
+            ts = []
+            for _ in range(reps):
+                put_back()
+                t0 = time.perf_counter()
+                fn()                           # ends in a device-to-host copy: the request is complete
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts.sort()
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    s1 = serve.EditSession(model, frame)
+    legs = dict(edit=timed(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True), fresh(s1)))
+    out = dict(tool="serve_probe --select" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               window=list(win), seed=list(seed), tolerance=tolerance, grow=grow, disc_pixels=int(disc.sum()))
+    if not parent:
+        s2, s3 = serve.EditSession(model, frame), serve.EditSession(model, frame)
+
+        def host_route():
+            mask, _ = host_select(s3.frame(), seed, tolerance, grow)
+            return s3.fill(mask, window=win, low_latency=True)
+        legs.update(fill_similar=timed(lambda: s2.fill_similar(seed, tolerance=tolerance, grow=grow, window=win, low_latency=True), fresh(s2)),
+                    host_route=timed(host_route, fresh(s3)))
+        mask, route = host_select(frame, seed, tolerance, grow)
+        parts = dict(frame_download=timed(lambda: s3.frame(), lambda: None), host_select=timed(lambda: host_select(frame, seed, tolerance, grow),
+                                                                                                 lambda: None),
+                     fill_of_the_mask=timed(lambda: s3.fill(mask, window=win, low_latency=True), fresh(s3)),
+                     select_similar=timed(lambda: s2.select_similar(seed, tolerance=tolerance, grow=grow), fresh(s2)))
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    if not parent:
+        out["parts_ms"] = {k: fn() for k, fn in parts.items()}
+        # the passes the disc takes, one launch per call
+        state = model.select_similar_u8(dev0, seed, tolerance, True)
+        passes = 0
+        while model.select_flood_u8(state, passes=1).cpu().tolist()[0]:
+            passes += 1
+        fresh(s2)()
+        fresh(s3)()
+        eng = model.engine()
+        eng.profile(True)
+        _, _, info = s2.fill_similar(seed, tolerance=tolerance, grow=grow, window=win, low_latency=True)
+        rep = eng.profile_report()
+        eng.profile(False)
+        host_route()
+        ks = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        out.update(host_select_route=route, productive_passes=passes, flood_calls_of_8=passes // 8 + 1, selected=info["selected"],
+                   selected_by_the_host=int((mask > 0).sum()), same_frame_as_the_host_route=bool(np.array_equal(s2.frame(), s3.frame())),
+                   pixels_changed=int((s2.frame() != frame).any(2).sum()),
+                   kernels_profiled=dict(total_ms=round(sum(k["ms"] for k in ks.values()), 3), launches=sum(k["launches"] for k in ks.values()),
+                                         around_the_forward={n: k for n, k in ks.items()
+                                                             if n.startswith(("window_", "resize_", "fill_", "select_", "sketch_"))}),
+                   fill_similar_minus_host_route_ms=round(out["ms"]["fill_similar"]["median"] - out["ms"]["host_route"]["median"], 3),
+                   fill_similar_minus_edit_ms=round(out["ms"]["fill_similar"]["median"] - out["ms"]["edit"]["median"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -792,6 +931,8 @@ def main():
     ap.add_argument("--feather-parent", action="store_true", help="the legs of --feather without a feathered paste only")
     ap.add_argument("--fill", action="store_true", help="fills of a painted region (see the module docstring)")
     ap.add_argument("--fill-parent", action="store_true", help="the edit legs of --fill only")
+    ap.add_argument("--select", action="store_true", help="the selection by colour (see the module docstring)")
+    ap.add_argument("--select-parent", action="store_true", help="the edit leg of --select only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -802,8 +943,11 @@ def main():
     model = make_model(tempfile.mkdtemp())
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
-            or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent):
-        if args.fill or args.fill_parent:
+            or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
+            or args.select or args.select_parent):
+        if args.select or args.select_parent:
+            res = select_leg(model, args.reps, parent=args.select_parent)
+        elif args.fill or args.fill_parent:
             res = fill_leg(model, args.reps, parent=args.fill_parent)
         elif args.feather or args.feather_parent:
             res = feather_leg(model, args.reps, parent=args.feather_parent)
