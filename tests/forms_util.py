@@ -197,6 +197,27 @@ LL_THRESHOLDS = [
 ]
 
 
+# The arithmetic family of a form: which Winograd-type transforms lie between the operands and the sum (se_pack.hip and the
+# kernels' header comments).  Everything not named here multiplies the operands as they are ('direct'): the
+# gather-GEMM forms, rtile / rtile_up2 / rtile_dense5 / rtile_bf16*, rconv16*, rconv96*, small_conv.
+FAMILY = {
+    "wino": "f23xf23", "wino_2src": "f23xf23", "wino48": "f23xf23", "wino48_c24": "f23xf23", "rtilew2": "f23xf23",
+    "wino24": "f23xf43", "wino24_2src": "f23xf43", "wino24_c48": "f23xf43",
+    "rtilew": "f23x",
+    "rtile_dense5w": "f25x",
+    "winoup": "subpixel", "winoup48": "subpixel",
+}
+
+
+def family(form):
+    """'direct', 'f23xf23' (F(2,3) x F(2,3)), 'f23xf43' (F(2,3) x F(4,3)), 'f23x' (F(2,3) along x), 'f25x' (F(2,5) along x) or
+    'subpixel' (F(2x2,2x2) on the sub-pixel classes of gen_deconv)."""
+    if form in FAMILY:
+        return FAMILY[form]
+    assert form.startswith(("gconv_", "rtile", "rconv", "small_conv", "vecbias")) and not form.startswith(("rtilew", "rtile_dense5w")), form
+    return "direct"
+
+
 def conv_launches(launches):
     """The conv launches among (form, layer) records, as a list of forms."""
     return [f for f, _ in launches if f.startswith(CONV_PREFIXES)]
