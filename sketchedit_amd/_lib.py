@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -61,6 +61,10 @@ FILL_SYMBOLS = ["se_fill", "se_fill_window_u8", "se_fill_window_u8_workspace_byt
 # every symbol declared in include/sketchedit_select.h (selection by colour)
 SELECT_SYMBOLS = ["se_select_similar_u8", "se_select_flood_u8", "se_select_grow_u8"]
 SELECT_MAX_GROW, SELECT_MAX_PASSES = 16, 64   # SE_SELECT_MAX_GROW, SE_SELECT_MAX_PASSES
+# every symbol declared in include/sketchedit_lasso.h (lasso selections and their algebra)
+LASSO_SYMBOLS = ["se_lasso_fill_u8", "se_plane_combine_u8"]
+LASSO_MAX_EDGES, LASSO_MAX_EXTENT = 65536, 8192   # SE_LASSO_MAX_EDGES, SE_LASSO_MAX_EXTENT
+COMBINE_ADD, COMBINE_SUBTRACT, COMBINE_INTERSECT, COMBINE_XOR, COMBINE_INVERT = range(5)   # SE_COMBINE_*
 
 
 class SketchEditHipError(RuntimeError):
@@ -95,6 +99,7 @@ def build_library(force=False, verbose=False, extra_flags=()):
             os.path.join(_HERE, "..", "include", "sketchedit_png.h"), os.path.join(_HERE, "..", "include", "sketchedit_jpg.h"),
             os.path.join(_HERE, "..", "include", "sketchedit_jpg2.h"), os.path.join(_HERE, "..", "include", "sketchedit_feather.h"),
             os.path.join(_HERE, "..", "include", "sketchedit_fill.h"), os.path.join(_HERE, "..", "include", "sketchedit_select.h"),
+            os.path.join(_HERE, "..", "include", "sketchedit_lasso.h"),
             os.path.join(CSRC, "se_jpg_tables.h")]
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "lib", "obj")
@@ -281,6 +286,10 @@ def load_library():
         lib.se_select_flood_u8.restype = ci
         lib.se_select_grow_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
         lib.se_select_grow_u8.restype = ci
+        lib.se_lasso_fill_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+        lib.se_lasso_fill_u8.restype = ci
+        lib.se_plane_combine_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
+        lib.se_plane_combine_u8.restype = ci
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -1083,6 +1092,43 @@ class Engine:
             raise SketchEditHipError("select_grow_u8: out is a plane of the state's shape")
         if self.lib.se_select_grow_u8(self.h, self._stream(), _ptr(state), Hi, Wi, int(grow), _ptr(out)):
             self._err("se_select_grow_u8")
+        return out
+
+    # ---- lasso selections and their algebra (include/sketchedit_lasso.h) ---------------------------------------------
+    def lasso_fill_u8(self, edges, Hi, Wi, out=None):
+        """se_lasso_fill_u8: `edges` (N,4) int32 on the device, [ax, ay, bx, by] in quarter pixels of an (Hi,Wi) frame, N >= 0 ->
+        the fill plane (Hi,Wi) uint8 there: 255 where an odd number of edges cross the pixel's scanline strictly left of its
+        centre (the even-odd rule of the header), else 0.  `out`: a plane of that shape to write into, any alignment (every byte
+        is written)."""
+        import torch
+        if not (isinstance(edges, torch.Tensor) and edges.is_cuda and edges.dtype == torch.int32 and edges.is_contiguous()
+                and edges.dim() == 2 and edges.shape[1] == 4):
+            raise SketchEditHipError("lasso_fill_u8: edges are an (N,4) contiguous int32 CUDA(HIP) tensor")
+        Hi, Wi, N = int(Hi), int(Wi), int(edges.shape[0])
+        if out is None:
+            if Hi < 1 or Wi < 1:
+                raise SketchEditHipError("lasso_fill_u8: bad Hi=%d Wi=%d" % (Hi, Wi))
+            out = torch.empty((Hi, Wi), dtype=torch.uint8, device=edges.device)
+        if self._state_plane(out, "lasso_fill_u8: out") != (Hi, Wi):
+            raise SketchEditHipError("lasso_fill_u8: out is an (Hi,Wi) plane")
+        if self.lib.se_lasso_fill_u8(self.h, self._stream(), _ptr(edges) if N else None, N, Hi, Wi, _ptr(out)):
+            self._err("se_lasso_fill_u8")
+        return out
+
+    def plane_combine_u8(self, a, b, op, out=None):
+        """se_plane_combine_u8: planes (Hi,Wi) uint8 on the device, non-zero = selected -> `out` (a new plane, or a plane of that
+        shape: `a` itself, `b` itself, or one that shares no byte with them; any alignment), 0 / 255: op COMBINE_ADD a | b,
+        COMBINE_SUBTRACT a & ~b, COMBINE_INTERSECT a & b, COMBINE_XOR a ^ b, COMBINE_INVERT ~a (b is None)."""
+        import torch
+        Hi, Wi = self._state_plane(a, "plane_combine_u8: a")
+        if b is not None and self._state_plane(b, "plane_combine_u8: b") != (Hi, Wi):
+            raise SketchEditHipError("plane_combine_u8: b is a plane of a's shape")
+        if out is None:
+            out = torch.empty((Hi, Wi), dtype=torch.uint8, device=a.device)
+        if self._state_plane(out, "plane_combine_u8: out") != (Hi, Wi):
+            raise SketchEditHipError("plane_combine_u8: out is a plane of a's shape")
+        if self.lib.se_plane_combine_u8(self.h, self._stream(), _ptr(a), _ptr(b), Hi, Wi, int(op), _ptr(out)):
+            self._err("se_plane_combine_u8")
         return out
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 #include "../../include/sketchedit_feather.h"
 #include "../../include/sketchedit_fill.h"
 #include "../../include/sketchedit_select.h"
+#include "../../include/sketchedit_lasso.h"
 #include "se_kernels.h"
 #include "se_pack.h"
 
@@ -2432,6 +2433,52 @@ int se_select_grow_u8(se_ctx* c, void* stream, const unsigned char* state_u8, in
   HIPCHK(c, hipSetDevice(c->device));
   set_profiler(&c->prof);
   HIPCHK(c, launch_select_grow(state_u8, Hi, Wi, grow, plane_out, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- lasso selections and their algebra (include/sketchedit_lasso.h) ---------------------------------------
+// Every check on the host, then ONE launch that writes the caller's plane directly: no workspace, nothing for SE_TEST_POISON to
+// fill.
+namespace {
+
+int lasso_check_plane(se_ctx* c, int Hi, int Wi) {
+  if (Hi < 16 || Wi < 16 || Hi > SE_LASSO_MAX_EXTENT || Wi > SE_LASSO_MAX_EXTENT)
+    return fail(c, "bad Hi=%d Wi=%d (a selection's plane is 16 .. %d on a side)", Hi, Wi, SE_LASSO_MAX_EXTENT);
+  return 0;
+}
+
+}  // namespace
+
+int se_lasso_fill_u8(se_ctx* c, void* stream, const int* edges, int N, int Hi, int Wi, unsigned char* plane_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (lasso_check_plane(c, Hi, Wi)) return 1;
+  if (N < 0 || N > SE_LASSO_MAX_EDGES) return fail(c, "bad N=%d (0 .. %d edges)", N, SE_LASSO_MAX_EDGES);
+  if (!plane_out) return fail(c, "null pointer argument: plane_out");
+  if (!edges && N > 0) return fail(c, "null pointer argument: edges");
+  if (edges && !aligned_to(edges, 4)) return fail(c, "edges must be 4-byte aligned");
+  if (edges && N > 0 && select_meets(edges, (size_t)N * 4 * sizeof(int), plane_out, (size_t)Hi * Wi)) return fail(c, "edges overlaps plane_out");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  HIPCHK(c, launch_lasso_fill(edges, N, Hi, Wi, plane_out, (hipStream_t)stream));
+  return 0;
+}
+
+int se_plane_combine_u8(se_ctx* c, void* stream, const unsigned char* a, const unsigned char* b, int Hi, int Wi, int op, unsigned char* out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (lasso_check_plane(c, Hi, Wi)) return 1;
+  if (op < SE_COMBINE_ADD || op > SE_COMBINE_INVERT) return fail(c, "bad op=%d (0 .. 4)", op);
+  if (!a) return fail(c, "null pointer argument: a");
+  if (!out) return fail(c, "null pointer argument: out");
+  if (op == SE_COMBINE_INVERT && b) return fail(c, "b must be NULL for SE_COMBINE_INVERT");
+  if (op != SE_COMBINE_INVERT && !b) return fail(c, "null pointer argument: b");
+  const size_t n = (size_t)Hi * Wi;
+  if (out != a && select_meets(out, n, a, n)) return fail(c, "out overlaps a (it may be a itself)");
+  if (b && out != b && select_meets(out, n, b, n)) return fail(c, "out overlaps b (it may be b itself)");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  HIPCHK(c, launch_plane_combine(a, b, Hi, Wi, op, out, (hipStream_t)stream));
   return 0;
 }
 

@@ -21,7 +21,8 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
-                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW, PL_COUNT };
+                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW,
+                 PL_LASSO_FILL, PL_PLANE_COMBINE, PL_COUNT };
 const char* prof_label_name(int l);
 // Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
 // know which kernel the dispatcher chose; the label's name where the launcher has one form only
@@ -449,6 +450,12 @@ hipError_t launch_select_similar(const unsigned char* frame, int Hi, int Wi, int
 hipError_t launch_select_flood(unsigned char* state, int Hi, int Wi, unsigned* changed, hipStream_t st);
 // grow: out (another buffer) = 255 where a reached byte lies within Chebyshev distance `grow` (0 .. 16), else 0; every byte written
 hipError_t launch_select_grow(const unsigned char* state, int Hi, int Wi, int grow, unsigned char* out, hipStream_t st);
+// lasso selections and their algebra (include/sketchedit_lasso.h; se_lasso.hip).  Any Hi, Wi >= 16 and any alignment
+// of the planes; no byte outside a plane or the edge buffer is read or written.
+// lasso_fill: every byte of plane_out (Hi,Wi) <- the even-odd fill of the N edges [ax, ay, bx, by] (int32, quarter pixels)
+hipError_t launch_lasso_fill(const int* edges, int N, int Hi, int Wi, unsigned char* plane_out, hipStream_t st);
+// plane_combine: out <- a op b as 0 / 255 (op: SE_COMBINE_*; b null for INVERT); out may be exactly a or exactly b
+hipError_t launch_plane_combine(const unsigned char* a, const unsigned char* b, int Hi, int Wi, int op, unsigned char* out, hipStream_t st);
 // the device PNG encoder (include/sketchedit_png.h): the hs x ws rectangles of d_wins (B records) -> their zlib
 // streams.  rows: ftype (B,hs) uint8, each row's filter type.  stripes: one workgroup per stripe of 32 rows -> its deflate blocks
 // in its slot of png_slot_bytes(ws) bytes (16-byte aligned), its size in sizes (B,S) and its Adler parts in parts (B,S,2), S =

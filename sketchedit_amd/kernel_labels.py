@@ -44,6 +44,9 @@ KERNEL_LABELS = {
     "(anonymous namespace)::select_similar_kernel": "select_similar", "(anonymous namespace)::select_flood_kernel": "select_flood",
     "(anonymous namespace)::select_grow_kernel": "select_grow",
     "select_similar_kernel": "select_similar", "select_flood_kernel": "select_flood", "select_grow_kernel": "select_grow",
+    # lasso selections and their algebra (se_lasso.hip)
+    "(anonymous namespace)::lasso_fill_kernel": "lasso_fill", "(anonymous namespace)::plane_combine_kernel": "plane_combine",
+    "lasso_fill_kernel": "lasso_fill", "plane_combine_kernel": "plane_combine",
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",

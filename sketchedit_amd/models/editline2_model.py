@@ -219,6 +219,16 @@ class EditLine2Model(torch.nn.Module):
         """A state plane -> the fill plane: 255 within Chebyshev distance `grow` of a reached byte (Engine.select_grow_u8)."""
         return self.engine().select_grow_u8(state, grow, out=out)
 
+    def lasso_fill_u8(self, edges, Hi, Wi, out=None):
+        """A lasso selection (serve.EditSession.select_lasso is the caller-facing form): the (N,4) int32 edges of
+        closed rings, in quarter pixels, on the device -> the (Hi,Wi) fill plane of their even-odd interior (Engine.lasso_fill_u8)."""
+        return self.engine().lasso_fill_u8(edges, Hi, Wi, out=out)
+
+    def plane_combine_u8(self, a, b, op, out=None):
+        """Two selection planes -> a op b as 0 / 255; op = _lib.COMBINE_ADD / SUBTRACT / INTERSECT / XOR, or COMBINE_INVERT with
+        b None (Engine.plane_combine_u8)."""
+        return self.engine().plane_combine_u8(a, b, op, out=out)
+
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
         slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""

@@ -265,6 +265,61 @@ def stroke_box(segs, frame_hw):
     return (max(lo(s[:, 1], s[:, 3]), 0), max(lo(s[:, 0], s[:, 2]), 0), min(hi(s[:, 1], s[:, 3]), Hi), min(hi(s[:, 0], s[:, 2]), Wi))
 
 
+LASSO_MAX_EDGES = 65536     # SE_LASSO_MAX_EDGES
+COMBINE_OPS = {"add": 0, "subtract": 1, "intersect": 2, "xor": 3}     # SE_COMBINE_*
+COMBINE_INVERT = 4
+
+
+def lasso_edges(rings, frame_hw):
+    """Outlines as a drawing front end has them -> the edges the lasso's rasteriser takes (pure host arithmetic).
+    `rings`: a list of point lists [(x, y)], floats in pixels of the frame as stroke_segments takes them, at least 3 points
+    each; every ring is closed here (its last point is joined to its first).  Coordinates are rounded to quarter pixels (half up)
+    and clamped to the frame's rectangle [0, 4 Wi] x [0, 4 Hi]: a vertex outside the frame moves to its border.  The interior
+    is even-odd over all rings together: a ring inside a ring is a hole.
+    -> an (N,4) int32 array of [ax, ay, bx, by], one edge per point (horizontal and zero-length edges are kept: they never
+    count).  ValueError for no rings, a ring under 3 points, a value that is not finite, more than 65 536 edges, a frame over
+    8192 on a side."""
+    Hi, Wi = int(frame_hw[0]), int(frame_hw[1])
+    if not (1 <= Hi <= STROKE_MAX_EXTENT and 1 <= Wi <= STROKE_MAX_EXTENT):
+        raise ValueError("a lasso is rasterised on frames of at most %d pixels on a side (got %dx%d)" % (STROKE_MAX_EXTENT, Wi, Hi))
+    rings = list(rings)
+    if not rings:
+        raise ValueError("no rings: nothing to select")
+    edges = []
+    for k, points in enumerate(rings):
+        try:
+            pts = np.asarray(points, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("ring %d: points are a list of (x, y)" % k)
+        if pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 3:
+            raise ValueError("ring %d: an outline is a list of at least 3 points (x, y)" % k)
+        if not np.isfinite(pts).all():
+            raise ValueError("ring %d: coordinates must be finite" % k)
+        q = np.floor(STROKE_Q * pts + 0.5)
+        qx = np.clip(q[:, 0], 0, STROKE_Q * Wi).astype(np.int64)
+        qy = np.clip(q[:, 1], 0, STROKE_Q * Hi).astype(np.int64)
+        edges.append(np.stack([qx, qy, np.roll(qx, -1), np.roll(qy, -1)], axis=1))
+        if sum(e.shape[0] for e in edges) > LASSO_MAX_EDGES:
+            raise ValueError("a lasso has at most %d edges" % LASSO_MAX_EDGES)
+    return np.concatenate(edges).astype(np.int32).reshape(-1, 4)
+
+
+def lasso_box(edges, frame_hw):
+    """A box that holds every pixel a lasso selects (pure host arithmetic): (y0, x0, y1, x1), half open -- rows
+    [ceil((min_y - 2) / 4), floor((max_y - 3) / 4) + 1), columns [floor((min_x - 2) / 4) + 1, floor((max_x - 2) / 4) + 1) over the
+    edges' end points, clipped to the frame -- or None when that is empty (no centre can be selected).  A selected centre has
+    min_y <= py < max_y (an edge spans its scanline) and min_x < px <= max_x (a crossing lies strictly left of it, and for
+    closed rings one lies at or right of it).  A bound, not the tight box."""
+    e = np.asarray(edges, np.int64).reshape(-1, 4)
+    if e.shape[0] < 1:
+        return None
+    Hi, Wi = int(frame_hw[0]), int(frame_hw[1])
+    xs, ys = e[:, [0, 2]], e[:, [1, 3]]
+    y0, y1 = max(int(-((-(ys.min() - 2)) // STROKE_Q)), 0), min(int((ys.max() - 3) // STROKE_Q) + 1, Hi)
+    x0, x1 = max(int((xs.min() - 2) // STROKE_Q) + 1, 0), min(int((xs.max() - 2) // STROKE_Q) + 1, Wi)
+    return (y0, x0, y1, x1) if y0 < y1 and x0 < x1 else None
+
+
 def png_from_zlib(stream, h, w):
     """The PNG file around a zlib stream of filtered 8-bit RGB rows: signature, IHDR, ONE IDAT holding
     `stream` as it is, IEND -- the chunk framing and its CRCs are the host's part of a patch that was encoded on the device."""
@@ -459,18 +514,21 @@ def tiles_box(tiles):
 
 
 class Selection:
-    """A selection of an editing session (DESIGN.md 6o): a frame-sized mask that lives on the device.  `.plane`: the (Hi,Wi)
+    """A selection of an editing session (DESIGN.md 6o, 6p): a frame-sized mask that lives on the device.  `.plane`: the (Hi,Wi)
     uint8 fill plane there, 255 = selected; `.box` = (y0, x0, y1, x1), half open, its tight box; `.count` its pixels;
     `.frame_hw` the size of the frame it was made on.  A selection is a mask, not a view of the frame: it stays what it is
-    when the frame changes."""
+    when the frame changes.  An EMPTY selection (what a subtraction can leave) has `.box` None and `.count` 0; its plane is
+    all zeros."""
 
     def __init__(self, backend, plane, box, count, frame_hw):
         self._backend = backend
-        self.plane, self.box, self.count, self.frame_hw = plane, tuple(int(v) for v in box), int(count), tuple(frame_hw)
+        self.plane, self.box, self.count, self.frame_hw = plane, None if box is None else tuple(int(v) for v in box), int(count), tuple(frame_hw)
 
     def mask(self):
         """the box's crop of the plane as a (y1 - y0, x1 - x0) uint8 array of 0 / 255 on the host (a download of the box only):
-        what a front end outlines"""
+        what a front end outlines; a (0, 0) array, and no download, for an empty selection"""
+        if self.box is None:
+            return np.zeros((0, 0), np.uint8)
         y0, x0, y1, x1 = self.box
         return self._backend.crop(self.plane, y0, x0, y1 - y0, x1 - x0)
 
@@ -552,6 +610,27 @@ class _ModelBackend:
         plane = self.model.select_grow_u8(state, grow)
         box, count = tiles_box(self.tiles(plane, 32))
         return plane, box, count
+
+    def select_lasso(self, edges, frame_hw, grow):
+        """the lasso selection of `edges`, the (N,4) int32 edges on the device: the even-odd fill, the grow when
+        `grow` > 0 (a lasso's plane is a state plane of 6o as it is), the tile records of the result -- the one download.
+        -> (plane, box, count) as select_similar returns them; box None and count 0 when no pixel centre is covered"""
+        plane = self.model.lasso_fill_u8(edges, int(frame_hw[0]), int(frame_hw[1]))
+        if grow > 0:
+            plane = self.model.select_grow_u8(plane, grow)
+        box, count = tiles_box(self.tiles(plane, 32))
+        return plane, box, count
+
+    def combine(self, a, b, op):
+        """two selection planes (b None for the inversion) -> (plane, box, count) of a NEW plane, a op b; op is
+        SE_COMBINE_*'s value"""
+        plane = self.model.plane_combine_u8(a, b, op)
+        box, count = tiles_box(self.tiles(plane, 32))
+        return plane, box, count
+
+    def copy(self, plane):
+        """a copy of a plane that is on the device, made there"""
+        return plane.clone()
 
     def save(self, frames, origins, window_hw):
         """the windows' rectangles -> one new journal slot each, on the stream the edit follows on"""
@@ -668,7 +747,15 @@ class EditSession:
     def set_lock(self, mask):
         """`mask`: (Hi,Wi), a uint8 or bool array or a PIL 'L' image, non-zero = locked; uploaded once (as 0 / 255) and kept
         on the device until the next set_lock.  None frees it.  Every later edit leaves the locked pixels' bytes as they
-        are.  Not an edit: nothing is journalled, and `undo` does not bring an earlier lock back."""
+        are.  Not an edit: nothing is journalled, and `undo` does not bring an earlier lock back.
+        A Selection of this frame's size locks its pixels: the lock plane is a COPY of its plane made on the
+        device -- nothing is uploaded, and what is combined from the selection later cannot reach the lock; an empty selection
+        is None."""
+        if isinstance(mask, Selection):
+            self._check_selection(mask, "set_lock")
+            with self._lock:
+                self._lock_plane = None if mask.box is None else self.backend.copy(mask.plane)
+            return
         if mask is not None:
             if hasattr(mask, "mode"):
                 if mask.mode != "L":
@@ -1076,9 +1163,7 @@ class EditSession:
             raise ValueError("seed is (y, x), two ints inside the %dx%d frame (got %r)" % (Wi, Hi, seed))
         if not integer(tolerance) or not 0 <= tolerance <= 255:
             raise ValueError("tolerance is an int 0 .. 255, the largest difference in any channel (got %r)" % (tolerance,))
-        if not integer(grow) or not 0 <= grow <= SELECT_MAX_GROW:
-            raise ValueError("grow is an int 0 .. %d, in frame pixels (got %r)" % (SELECT_MAX_GROW, grow))
-        return (int(sy), int(sx)), int(tolerance), int(grow)
+        return (int(sy), int(sx)), int(tolerance), self._check_grow(grow)
 
     def _check_fill_args(self, box, sketch, window, margin, max_side):
         """what a fill of a selection refuses before its first backend call: a sketch of another size, a bad window or margin
@@ -1128,11 +1213,9 @@ class EditSession:
         ValueError for a selection made on a frame of another size and for what `fill` refuses."""
         encode = _check_encode(encode)
         feather = _check_feather(feather)
-        if not isinstance(selection, Selection):
-            raise TypeError("fill_selection takes what select_similar returned (got %s)" % type(selection).__name__)
-        if tuple(selection.frame_hw) != self.frame_hw:
-            raise ValueError("the selection was made on a %dx%d frame, this one is %dx%d"
-                             % (selection.frame_hw[1], selection.frame_hw[0], self.frame_hw[1], self.frame_hw[0]))
+        self._check_selection(selection, "fill_selection")
+        if selection.box is None:
+            raise ValueError("empty selection: nothing to fill")
         sk = self._check_fill_args(selection.box, sketch, window, margin, max_side)
         with self._lock:
             return self._fill_selected(selection, sk, window, margin, low_latency, max_side, encode, feather)
@@ -1149,6 +1232,81 @@ class EditSession:
         with self._lock:
             return self._fill_selected(self._select(seed, tolerance, contiguous, grow), sk, window, margin, low_latency, max_side,
                                        encode, feather)
+
+    # ---- lasso selections and the algebra of selections -----------------------------------------------------------
+    def _check_selection(self, selection, what):
+        """a Selection made on a frame of this size, or TypeError / ValueError; no backend call"""
+        if not isinstance(selection, Selection):
+            raise TypeError("%s takes a Selection, what select_similar / select_lasso / combine returned (got %s)"
+                            % (what, type(selection).__name__))
+        if tuple(selection.frame_hw) != self.frame_hw:
+            raise ValueError("the selection was made on a %dx%d frame, this one is %dx%d"
+                             % (selection.frame_hw[1], selection.frame_hw[0], self.frame_hw[1], self.frame_hw[0]))
+
+    @staticmethod
+    def _check_grow(grow):
+        if not isinstance(grow, (int, np.integer)) or isinstance(grow, (bool, np.bool_)) or not 0 <= grow <= SELECT_MAX_GROW:
+            raise ValueError("grow is an int 0 .. %d, in frame pixels (got %r)" % (SELECT_MAX_GROW, grow))
+        return int(grow)
+
+    def _select_lasso(self, edges, grow):
+        """with the session's lock held: the edges go up, ONE backend call makes the selection"""
+        be = self.backend
+        plane, box, count = be.select_lasso(be.upload(edges), self.frame_hw, grow)
+        return Selection(be, plane, box, count, self.frame_hw)
+
+    def select_lasso(self, rings, grow=0):
+        """"Draw an outline around it" (DESIGN.md 6p): the pixels whose centres lie inside the closed outlines `rings` = [[(x, y),
+        ...], ...] (floats in frame pixels, at least 3 points each, as lasso_edges takes them) by the even-odd rule -- a ring
+        inside a ring is a hole, and so is the middle of a self-crossing outline -- and every pixel within `grow` (0 .. 16)
+        pixels of one.  Rasterised on the device: only the edges go up, and the tile records of the result come down.
+        -> Selection; EMPTY (.box None, .count 0) when the outline covers no pixel centre.  Not an edit: nothing is journalled;
+        the frame and the lock play no part.  ValueError for what lasso_edges refuses and a grow outside its range."""
+        edges = lasso_edges(rings, self.frame_hw)
+        grow = self._check_grow(grow)
+        with self._lock:
+            return self._select_lasso(edges, grow)
+
+    def combine(self, a, b, op):
+        """Two selections of this frame -> a NEW one, made on the device: `op` "add" (a or b), "subtract" (a and
+        not b), "intersect" (a and b) or "xor".  a and b stay what they were; the result may be empty.  TypeError for an
+        operand that is not a Selection, ValueError for one made on a frame of another size and for an unknown op, all before
+        the one backend call."""
+        self._check_selection(a, "combine")
+        self._check_selection(b, "combine")
+        if not isinstance(op, str) or op not in COMBINE_OPS:
+            raise ValueError("op is one of %s (got %r)" % (", ".join(repr(k) for k in COMBINE_OPS), op))
+        with self._lock:
+            plane, box, count = self.backend.combine(a.plane, b.plane, COMBINE_OPS[op])
+        return Selection(self.backend, plane, box, count, self.frame_hw)
+
+    def invert(self, a):
+        """Everything but `a`: a NEW selection, made on the device; `a` stays what it was."""
+        self._check_selection(a, "invert")
+        with self._lock:
+            plane, box, count = self.backend.combine(a.plane, None, COMBINE_INVERT)
+        return Selection(self.backend, plane, box, count, self.frame_hw)
+
+    def fill_lasso(self, rings, grow=2, sketch=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None,
+                   feather=None):
+        """select_lasso(rings, grow) and fill_selection of the result under ONE hold of the session's lock: "draw
+        around it, fill it in".  Only the edges go up; nothing frame-sized crosses the bus in either direction.
+        -> what fill_selection returns; ONE undo step.  Every ValueError comes before the first backend call (the window
+        arguments are tried on lasso_box of the edges) but one: "the lasso covers no pixel centre" may be known only after
+        the selection was made -- a sliver between two columns of centres has a box and no pixel; nothing was changed then."""
+        encode = _check_encode(encode)
+        feather = _check_feather(feather)
+        edges = lasso_edges(rings, self.frame_hw)
+        grow = self._check_grow(grow)
+        box = lasso_box(edges, self.frame_hw)
+        if box is None:
+            raise ValueError("the lasso covers no pixel centre")
+        sk = self._check_fill_args(box, sketch, window, margin, max_side)
+        with self._lock:
+            selection = self._select_lasso(edges, grow)
+            if selection.box is None:
+                raise ValueError("the lasso covers no pixel centre")
+            return self._fill_selected(selection, sk, window, margin, low_latency, max_side, encode, feather)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""

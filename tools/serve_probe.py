@@ -134,6 +134,20 @@ plus the host route's three parts timed alone, the passes the disc took, that (b
 se_profile_report's per-kernel times of one (b) request.
 
     python tools/serve_probe.py --select [--reps N] [--out FILE]
+
+--lasso: lasso selections: the outline of a disc of --select's size as a polygon of 300 vertices, filled through
+the 512 x 512 window of --fill, the same protocol, all in one build; the frame is put back (a device copy, not timed) in front
+of every timed call:
+  (a) edit:       EditSession.edit(window=..., max_grow=0), the unchanged control (run with --lasso-parent on the parent commit's
+                  build: only this leg),
+  (b) fill_lasso: EditSession.fill_lasso([outline], grow=2, window=...) -- the edges go up, the even-odd fill, the grow and the
+                  tile records on the device, then the fill; nothing frame-sized crosses the bus,
+  (c) host_route: PIL.ImageDraw.polygon into an 'L' image of the frame's size, EditSession.fill(mask, window=...) (the scan and
+                  the 2 MB upload),
+plus the host route's two parts timed alone, select_lasso and a combine alone, the pixels on which the two routes' masks differ
+(Pillow's rule at an edge is not the header's), and se_profile_report's per-kernel times of one (b) request and of one combine.
+
+    python tools/serve_probe.py --lasso [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -908,6 +922,110 @@ def select_leg(model, reps, parent=False, side=512, tolerance=16, grow=2):
     return out
 
 
+def lasso_leg(model, reps, parent=False, side=512, grow=2, vertices=300):
+    """(a), (b), (c) of the module docstring; parent=True: the leg (a) only, with the calls a build without lassos has"""
+    import math
+    import numpy as np
+    import torch
+    from PIL import Image, ImageDraw
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    win = (283, 705, side, side)
+    cy, cx = win[0] + side // 2 + 0.5, win[1] + side // 2 + 0.5
+    ring = [(cx + 126 * math.cos(2 * math.pi * k / vertices), cy + 126 * math.sin(2 * math.pi * k / vertices)) for k in range(vertices)]
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    dev0 = torch.from_numpy(frame).cuda()
+
+    def fresh(session):
+        def put_back():
+            session._frame.copy_(dev0)
+            torch.cuda.synchronize()
+        return put_back
+
+    def timed(fn, put_back):
+        def rounds():
+            for _ in range(2):                 # warm-up: plans, workspace, code objects
+                put_back()
+                fn()
+            ts = []
+            for _ in range(reps):
+                put_back()
+                t0 = time.perf_counter()
+                fn()                           # ends in a device-to-host copy: the request is complete
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts.sort()
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    def host_lasso():
+        """the outline rasterised on the host, grown as the device grows it -> the (H,W) uint8 mask"""
+        img = Image.new("L", (w, h), 0)
+        ImageDraw.Draw(img).polygon(ring, fill=255)
+        mask = np.asarray(img)
+        if grow:
+            try:
+                from scipy import ndimage
+                mask = ndimage.maximum_filter(mask, size=2 * grow + 1, mode="constant")
+            except ImportError:
+                from PIL import ImageFilter
+                mask = np.asarray(img.filter(ImageFilter.MaxFilter(2 * grow + 1)))
+        return mask
+
+    s1 = serve.EditSession(model, frame)
+    legs = dict(edit=timed(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True), fresh(s1)))
+    out = dict(tool="serve_probe --lasso" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               window=list(win), vertices=vertices, grow=grow)
+    if not parent:
+        s2, s3 = serve.EditSession(model, frame), serve.EditSession(model, frame)
+
+        def host_route():
+            return s3.fill(host_lasso(), window=win, low_latency=True)
+        legs.update(fill_lasso=timed(lambda: s2.fill_lasso([ring], grow=grow, window=win, low_latency=True), fresh(s2)),
+                    host_route=timed(host_route, fresh(s3)))
+        mask = host_lasso()
+        sel = s2.select_lasso([ring], grow=grow)
+        other = s2.select_lasso([[(x + 60.0, y) for x, y in ring]])
+
+        def combine():
+            return s2.combine(sel, other, "subtract").count
+        parts = dict(host_polygon=timed(host_lasso, lambda: None), fill_of_the_mask=timed(lambda: s3.fill(mask, window=win, low_latency=True), fresh(s3)),
+                     select_lasso=timed(lambda: s2.select_lasso([ring], grow=grow), lambda: None), combine=timed(combine, lambda: None))
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    if not parent:
+        out["parts_ms"] = {k: fn() for k, fn in parts.items()}
+        fresh(s2)()
+        fresh(s3)()
+        eng = model.engine()
+        eng.profile(True)
+        _, _, info = s2.fill_lasso([ring], grow=grow, window=win, low_latency=True)
+        rep = eng.profile_report()
+        eng.profile(False)
+        eng.profile(True)
+        combine()
+        rep2 = eng.profile_report()
+        eng.profile(False)
+        ks = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        ks2 = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep2["kernels"]}
+        out.update(selected=info["selected"], selected_by_the_host=int((mask > 0).sum()),
+                   masks_differ_on_pixels=int((sel.plane.cpu().numpy() != mask).sum()),
+                   pixels_changed=int((s2.frame() != frame).any(2).sum()),
+                   kernels_profiled=dict(total_ms=round(sum(k["ms"] for k in ks.values()), 3), launches=sum(k["launches"] for k in ks.values()),
+                                         around_the_forward={n: k for n, k in ks.items()
+                                                             if n.startswith(("window_", "resize_", "fill_", "select_", "sketch_", "lasso_", "plane_"))}),
+                   combine_profiled=ks2,
+                   fill_lasso_minus_host_route_ms=round(out["ms"]["fill_lasso"]["median"] - out["ms"]["host_route"]["median"], 3),
+                   fill_lasso_minus_edit_ms=round(out["ms"]["fill_lasso"]["median"] - out["ms"]["edit"]["median"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -933,6 +1051,8 @@ def main():
     ap.add_argument("--fill-parent", action="store_true", help="the edit legs of --fill only")
     ap.add_argument("--select", action="store_true", help="the selection by colour (see the module docstring)")
     ap.add_argument("--select-parent", action="store_true", help="the edit leg of --select only")
+    ap.add_argument("--lasso", action="store_true", help="lasso selections (see the module docstring)")
+    ap.add_argument("--lasso-parent", action="store_true", help="the edit leg of --lasso only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -944,8 +1064,10 @@ def main():
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
-            or args.select or args.select_parent):
-        if args.select or args.select_parent:
+            or args.select or args.select_parent or args.lasso or args.lasso_parent):
+        if args.lasso or args.lasso_parent:
+            res = lasso_leg(model, args.reps, parent=args.lasso_parent)
+        elif args.select or args.select_parent:
             res = select_leg(model, args.reps, parent=args.select_parent)
         elif args.fill or args.fill_parent:
             res = fill_leg(model, args.reps, parent=args.fill_parent)
