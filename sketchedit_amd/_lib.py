@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -65,6 +65,9 @@ SELECT_MAX_GROW, SELECT_MAX_PASSES = 16, 64   # SE_SELECT_MAX_GROW, SE_SELECT_MA
 LASSO_SYMBOLS = ["se_lasso_fill_u8", "se_plane_combine_u8"]
 LASSO_MAX_EDGES, LASSO_MAX_EXTENT = 65536, 8192   # SE_LASSO_MAX_EDGES, SE_LASSO_MAX_EXTENT
 COMBINE_ADD, COMBINE_SUBTRACT, COMBINE_INTERSECT, COMBINE_XOR, COMBINE_INVERT = range(5)   # SE_COMBINE_*
+# every symbol declared in include/sketchedit_outline.h (the outline of a selection)
+OUTLINE_SYMBOLS = ["se_outline_u8_workspace_bytes", "se_outline_u8"]
+OUTLINE_TILE, OUTLINE_MAX_CAP = 64, 1 << 24       # SE_OUTLINE_TILE, SE_OUTLINE_MAX_CAP
 
 
 class SketchEditHipError(RuntimeError):
@@ -100,6 +103,7 @@ def build_library(force=False, verbose=False, extra_flags=()):
             os.path.join(_HERE, "..", "include", "sketchedit_jpg2.h"), os.path.join(_HERE, "..", "include", "sketchedit_feather.h"),
             os.path.join(_HERE, "..", "include", "sketchedit_fill.h"), os.path.join(_HERE, "..", "include", "sketchedit_select.h"),
             os.path.join(_HERE, "..", "include", "sketchedit_lasso.h"),
+            os.path.join(_HERE, "..", "include", "sketchedit_outline.h"),
             os.path.join(CSRC, "se_jpg_tables.h")]
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "lib", "obj")
@@ -290,6 +294,10 @@ def load_library():
         lib.se_lasso_fill_u8.restype = ci
         lib.se_plane_combine_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
         lib.se_plane_combine_u8.restype = ci
+        lib.se_outline_u8_workspace_bytes.argtypes = [vp, ci, ci]
+        lib.se_outline_u8_workspace_bytes.restype = sz
+        lib.se_outline_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, sz]
+        lib.se_outline_u8.restype = ci
         lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
         lib.se_resample_coeffs.restype = ci
         lib.se_profile_enable.argtypes = [vp, ci]
@@ -1129,6 +1137,27 @@ class Engine:
             raise SketchEditHipError("plane_combine_u8: out is a plane of a's shape")
         if self.lib.se_plane_combine_u8(self.h, self._stream(), _ptr(a), _ptr(b), Hi, Wi, int(op), _ptr(out)):
             self._err("se_plane_combine_u8")
+        return out
+
+    # ---- the outline of a selection (include/sketchedit_outline.h) ------------------------------------------------------
+    def outline_u8(self, plane, cap):
+        """se_outline_u8: a plane (Hi,Wi) uint8 on the device, non-zero = selected -> ONE int32 tensor of 2 + 4 cap words there:
+        [total, written], then the first written = min(total, cap) boundary records [ax, ay, bx, by] in quarter pixels, in the
+        header's order (a valid `edges` argument of lasso_fill_u8 once reshaped to (-1, 4)); the words behind the written
+        records are not written.  One download gives a caller everything.  cap: 0 .. OUTLINE_MAX_CAP."""
+        import torch
+        Hi, Wi = self._state_plane(plane, "outline_u8: plane")
+        if not isinstance(cap, (int, np.integer)) or isinstance(cap, (bool, np.bool_)) or not 0 <= cap <= OUTLINE_MAX_CAP:
+            raise SketchEditHipError("outline_u8: cap is an int 0 .. %d (got %r)" % (OUTLINE_MAX_CAP, cap))
+        cap = int(cap)
+        out = torch.empty((2 + 4 * cap,), dtype=torch.int32, device=plane.device)
+        need = self.lib.se_outline_u8_workspace_bytes(self.h, Hi, Wi)
+        if need == 0:
+            self._err("se_outline_u8_workspace_bytes")
+        ws_t = self._workspace_bytes(need)
+        edges = ctypes.c_void_p(out.data_ptr() + 8) if cap else None
+        if self.lib.se_outline_u8(self.h, self._stream(), _ptr(plane), Hi, Wi, edges, cap, _ptr(out), _ptr(ws_t), ws_t.numel()):
+            self._err("se_outline_u8")
         return out
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------

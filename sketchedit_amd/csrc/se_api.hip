@@ -14,6 +14,7 @@
 #include "../../include/sketchedit_fill.h"
 #include "../../include/sketchedit_select.h"
 #include "../../include/sketchedit_lasso.h"
+#include "../../include/sketchedit_outline.h"
 #include "se_kernels.h"
 #include "se_pack.h"
 
@@ -2479,6 +2480,57 @@ int se_plane_combine_u8(se_ctx* c, void* stream, const unsigned char* a, const u
   HIPCHK(c, hipSetDevice(c->device));
   set_profiler(&c->prof);
   HIPCHK(c, launch_plane_combine(a, b, Hi, Wi, op, out, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- the outline of a selection (include/sketchedit_outline.h) ---------------------------------------------
+// Every check on the host, then three launches (two when cap == 0: nothing to emit).  The workspace is one block, the tiles' run
+// counts: SE_TEST_POISON fills it on the stream before the count kernel, which writes every word of it, is enqueued.
+namespace {
+
+size_t outline_ws_bytes(int Hi, int Wi) {
+  return pad256((size_t)((Hi + SE_OUTLINE_TILE - 1) / SE_OUTLINE_TILE) * ((Wi + SE_OUTLINE_TILE - 1) / SE_OUTLINE_TILE) * 4 * sizeof(int));
+}
+
+}  // namespace
+
+size_t se_outline_u8_workspace_bytes(se_ctx* c, int Hi, int Wi) {
+  if (!c) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (lasso_check_plane(c, Hi, Wi)) return 0;
+  return outline_ws_bytes(Hi, Wi);
+}
+
+int se_outline_u8(se_ctx* c, void* stream, const unsigned char* plane, int Hi, int Wi, int* edges_out, int cap, int* info_out,
+                  void* workspace, size_t workspace_bytes) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (lasso_check_plane(c, Hi, Wi)) return 1;
+  if (cap < 0 || cap > SE_OUTLINE_MAX_CAP) return fail(c, "bad cap=%d (0 .. %d records)", cap, SE_OUTLINE_MAX_CAP);
+  if (!plane) return fail(c, "null pointer argument: plane");
+  if (!edges_out && cap > 0) return fail(c, "null pointer argument: edges_out");
+  if (!info_out) return fail(c, "null pointer argument: info_out");
+  if (!workspace) return fail(c, "null pointer argument: workspace");
+  if (edges_out && !aligned_to(edges_out, 4)) return fail(c, "edges_out must be 4-byte aligned");
+  if (!aligned_to(info_out, 4)) return fail(c, "info_out must be 4-byte aligned");
+  const size_t need = outline_ws_bytes(Hi, Wi);
+  if (workspace_bytes < need) return fail(c, "workspace too small: %zu bytes, need %zu", workspace_bytes, need);
+  if (!aligned_to(workspace, 256)) return fail(c, "workspace must be 256-byte aligned");
+  const size_t pn = (size_t)Hi * Wi, en = edges_out ? (size_t)cap * 4 * sizeof(int) : 0, in = 2 * sizeof(int);
+  if (en && select_meets(edges_out, en, plane, pn)) return fail(c, "edges_out overlaps plane");
+  if (select_meets(info_out, in, plane, pn)) return fail(c, "info_out overlaps plane");
+  if (select_meets(workspace, need, plane, pn)) return fail(c, "workspace overlaps plane");
+  if (en && select_meets(edges_out, en, info_out, in)) return fail(c, "edges_out overlaps info_out");
+  if (en && select_meets(edges_out, en, workspace, need)) return fail(c, "edges_out overlaps the workspace");
+  if (select_meets(info_out, in, workspace, need)) return fail(c, "info_out overlaps the workspace");
+  HIPCHK(c, hipSetDevice(c->device));
+  set_profiler(&c->prof);
+  const hipStream_t st = (hipStream_t)stream;
+  if (poison(c, workspace, need, st)) return 1;
+  int* cnt = (int*)workspace;
+  HIPCHK(c, launch_outline_count(plane, Hi, Wi, cnt, st));
+  HIPCHK(c, launch_outline_scan(cnt, Hi, Wi, cap, info_out, st));
+  if (cap > 0) HIPCHK(c, launch_outline_emit(plane, Hi, Wi, cnt, edges_out, cap, st));
   return 0;
 }
 

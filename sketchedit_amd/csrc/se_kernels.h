@@ -22,7 +22,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
                  PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW,
-                 PL_LASSO_FILL, PL_PLANE_COMBINE, PL_COUNT };
+                 PL_LASSO_FILL, PL_PLANE_COMBINE, PL_OUTLINE_COUNT, PL_OUTLINE_SCAN, PL_OUTLINE_EMIT, PL_COUNT };
 const char* prof_label_name(int l);
 // Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
 // know which kernel the dispatcher chose; the label's name where the launcher has one form only
@@ -456,6 +456,14 @@ hipError_t launch_select_grow(const unsigned char* state, int Hi, int Wi, int gr
 hipError_t launch_lasso_fill(const int* edges, int N, int Hi, int Wi, unsigned char* plane_out, hipStream_t st);
 // plane_combine: out <- a op b as 0 / 255 (op: SE_COMBINE_*; b null for INVERT); out may be exactly a or exactly b
 hipError_t launch_plane_combine(const unsigned char* a, const unsigned char* b, int Hi, int Wi, int op, unsigned char* out, hipStream_t st);
+// the outline of a selection (include/sketchedit_outline.h; se_outline.hip): the boundary runs of plane != 0 per
+// 64 x 64 tile as lasso edges.  Any Hi, Wi >= 16 and any alignment of the plane; no byte outside it is read.  cnt: 4 int32 per
+// tile (N, S, E, W).  count: every cnt word <- its tile's run count.  scan: cnt <- its exclusive scan, in place;
+// info_out = {total, min(total, cap)}.  emit: the records whose index in the definition's order is < cap -> edges_out (4-byte
+// aligned); no other byte of it is written.
+hipError_t launch_outline_count(const unsigned char* plane, int Hi, int Wi, int* cnt, hipStream_t st);
+hipError_t launch_outline_scan(int* cnt, int Hi, int Wi, int cap, int* info_out, hipStream_t st);
+hipError_t launch_outline_emit(const unsigned char* plane, int Hi, int Wi, const int* offs, int* edges_out, int cap, hipStream_t st);
 // the device PNG encoder (include/sketchedit_png.h): the hs x ws rectangles of d_wins (B records) -> their zlib
 // streams.  rows: ftype (B,hs) uint8, each row's filter type.  stripes: one workgroup per stripe of 32 rows -> its deflate blocks
 // in its slot of png_slot_bytes(ws) bytes (16-byte aligned), its size in sizes (B,S) and its Adler parts in parts (B,S,2), S =

@@ -47,6 +47,10 @@ KERNEL_LABELS = {
     # lasso selections and their algebra (se_lasso.hip)
     "(anonymous namespace)::lasso_fill_kernel": "lasso_fill", "(anonymous namespace)::plane_combine_kernel": "plane_combine",
     "lasso_fill_kernel": "lasso_fill", "plane_combine_kernel": "plane_combine",
+    # the outline of a selection (se_outline.hip): one tile kernel in two forms, and the scan between them
+    "(anonymous namespace)::outline_tile_kernel<false>": "outline_count", "(anonymous namespace)::outline_tile_kernel<true>": "outline_emit",
+    "(anonymous namespace)::outline_scan_kernel": "outline_scan",
+    "outline_tile_kernel<false>": "outline_count", "outline_tile_kernel<true>": "outline_emit", "outline_scan_kernel": "outline_scan",
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",

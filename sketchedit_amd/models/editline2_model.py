@@ -229,6 +229,12 @@ class EditLine2Model(torch.nn.Module):
         b None (Engine.plane_combine_u8)."""
         return self.engine().plane_combine_u8(a, b, op, out=out)
 
+    def outline_u8(self, plane, cap):
+        """The outline of a selection plane (serve.Selection.rings is the caller-facing form): ONE int32 device
+        tensor, [total, written] and then the first min(total, cap) boundary records in the lasso's edge format
+        (Engine.outline_u8)."""
+        return self.engine().outline_u8(plane, cap)
+
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
         slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""

@@ -320,6 +320,64 @@ def lasso_box(edges, frame_hw):
     return (y0, x0, y1, x1) if y0 < y1 and x0 < x1 else None
 
 
+def outline_rings(records):
+    """The boundary records of a selection (se_outline_u8 / Selection.edges: (N,4) [ax, ay, bx, by] in quarter pixels, axis
+    parallel, clockwise with the interior on the right) -> its outline as closed rings (pure host arithmetic, time linear in N;
+    DESIGN.md 6q).  Each record's end is linked to the record that starts there; where two start at a vertex -- two selected
+    pixels touching diagonally -- the RIGHT turn is taken, so the selected set is traced 4-connected (as select_similar connects
+    it) and the background 8-connected.  Collinear neighbours are merged, which removes the splits at tile boundaries.
+    -> [[(x, y), ...], ...]: integer corner points in frame pixels, the format select_lasso takes.  A ring starts at its
+    smallest vertex in (y, x) order (no two rings share it) and the rings are sorted by it; outer rings run clockwise on the
+    screen (positive shoelace area with y down), holes counter-clockwise, and the signed areas sum to the selection's count.
+    ValueError for records that are not the whole outline of a pixel set (a capped download, say)."""
+    e = np.asarray(records, np.int64).reshape(-1, 4)
+    n = e.shape[0]
+    if n == 0:
+        return []
+    dx, dy = np.sign(e[:, 2] - e[:, 0]), np.sign(e[:, 3] - e[:, 1])
+    if ((dx != 0) == (dy != 0)).any() or (e % STROKE_Q != 0).any():
+        raise ValueError("outline records are axis-parallel edges of non-zero length between pixel corners")
+    dirs = list(zip(dx.tolist(), dy.tolist()))
+    rows = e.tolist()
+    starts = {}
+    for i, r in enumerate(rows):
+        starts.setdefault((r[0], r[1]), []).append(i)
+    succ = [0] * n
+    for i, r in enumerate(rows):
+        c = starts.get((r[2], r[3]), ())
+        if len(c) == 1:
+            succ[i] = c[0]
+        else:
+            right = (-dirs[i][1], dirs[i][0])
+            c = [j for j in c if dirs[j] == right]
+            if len(c) != 1:
+                raise ValueError("the records are not the closed outline of a pixel set (a record's end starts no other)")
+            succ[i] = c[0]
+    seen, rings = [False] * n, []
+    for first in range(n):
+        if seen[first]:
+            continue
+        pts, i, prev = [], first, None
+        while not seen[i]:
+            seen[i] = True
+            pts.append((i, prev))
+            prev, i = i, succ[i]
+        if i != first:
+            raise ValueError("the records are not the closed outline of a pixel set (two records share a successor)")
+        ring = [(rows[j][0] // STROKE_Q, rows[j][1] // STROKE_Q) for j, pj in pts if dirs[j] != dirs[prev if pj is None else pj]]
+        k = min(range(len(ring)), key=lambda t: (ring[t][1], ring[t][0]))
+        rings.append(ring[k:] + ring[:k])
+    rings.sort(key=lambda r: (r[0][1], r[0][0]))
+    return rings
+
+
+def rings_svg_path(rings):
+    """Rings as outline_rings returns them -> the `d` attribute of ONE SVG path: "M x0 y0 L x1 y1 ... Z" per ring (an "L" in
+    front of every further point), the rings joined by single spaces; "" for no rings.  Holes wind the other way, so the
+    path fills as the selection under either fill rule."""
+    return " ".join("M %d %d " % tuple(r[0]) + "".join("L %d %d " % tuple(q) for q in r[1:]) + "Z" for r in rings)
+
+
 def png_from_zlib(stream, h, w):
     """The PNG file around a zlib stream of filtered 8-bit RGB rows: signature, IHDR, ONE IDAT holding
     `stream` as it is, IEND -- the chunk framing and its CRCs are the host's part of a patch that was encoded on the device."""
@@ -532,6 +590,46 @@ class Selection:
         y0, x0, y1, x1 = self.box
         return self._backend.crop(self.plane, y0, x0, y1 - y0, x1 - x0)
 
+    def edges(self, first_cap=4096):
+        """The boundary of the selection as raw records on the host: an (N,4) int32 array of [ax, ay, bx, by] in
+        quarter pixels, one per boundary run of a 64 x 64 tile, in se_outline_u8's order -- a valid argument for the lasso's
+        rasteriser, which re-makes the plane from them bit for bit.  Extracted on the device: 16 bytes per run come down, not
+        the plane.  An empty selection gives a (0,4) array and no backend call; otherwise ONE backend call with room for
+        `first_cap` records and, only if there are more, exactly one more with room for all.  NotImplementedError from a backend
+        that cannot extract outlines."""
+        if not isinstance(first_cap, (int, np.integer)) or isinstance(first_cap, (bool, np.bool_)) or not 0 <= first_cap <= OUTLINE_MAX_CAP:
+            raise ValueError("first_cap is an int 0 .. %d (got %r)" % (OUTLINE_MAX_CAP, first_cap))
+        if self.box is None:
+            return np.zeros((0, 4), np.int32)
+        return _outline_records(self._backend, self.plane, int(first_cap))
+
+    def rings(self, first_cap=4096):
+        """The outline of the selection as closed rings: outline_rings of `edges(first_cap)` -- integer corner
+        points in frame pixels, outer rings clockwise on the screen and holes counter-clockwise, each from its smallest vertex
+        in (y, x) order, sorted by it.  What a front end draws (rings_svg_path), the serialised form of a selection, and an exact
+        round trip: select_lasso(selection.rings()) on a frame of this size re-makes the plane, box and count (while the rings
+        have at most 65 536 edges, the lasso's limit).  [] for an empty selection, with no backend call."""
+        return outline_rings(self.edges(first_cap))
+
+
+OUTLINE_MAX_CAP = 1 << 24     # SE_OUTLINE_MAX_CAP
+
+
+def _outline_records(be, plane, first_cap):
+    """all boundary records of a plane on the device: one `outline` call of the backend, and exactly one more when the first
+    capacity was too small"""
+    if not hasattr(be, "outline"):
+        raise NotImplementedError("this session's backend (%s) cannot extract outlines: it has no `outline`" % type(be).__name__)
+    total, rec = be.outline(plane, first_cap)
+    if total > OUTLINE_MAX_CAP:
+        raise ValueError("the outline has %d runs, more than one call returns (%d)" % (total, OUTLINE_MAX_CAP))
+    if total > first_cap:
+        total, rec = be.outline(plane, total)
+    rec = np.asarray(rec, np.int32).reshape(-1, 4)
+    if rec.shape[0] != total:
+        raise RuntimeError("outline: %d records came back, %d were counted" % (rec.shape[0], total))
+    return rec
+
 
 class _ModelBackend:
     """The device side of an editing session: an EditLine2Model's engine and torch for the copies.  (A seam: the host
@@ -627,6 +725,13 @@ class _ModelBackend:
         plane = self.model.plane_combine_u8(a, b, op)
         box, count = tiles_box(self.tiles(plane, 32))
         return plane, box, count
+
+    def outline(self, plane, cap):
+        """the boundary records of a plane on the device: three launches and ONE download, of 8 + 16 cap bytes
+        -> (total, records (min(total, cap), 4) int32 on the host)"""
+        words = self.model.outline_u8(plane, int(cap)).cpu().numpy()
+        total, written = int(words[0]), int(words[1])
+        return total, words[2:2 + 4 * written].reshape(-1, 4)
 
     def copy(self, plane):
         """a copy of a plane that is on the device, made there"""
@@ -778,6 +883,14 @@ class EditSession:
     @property
     def locked(self):
         return self._lock_plane is not None
+
+    def lock_rings(self, first_cap=4096):
+        """The outline of the lock plane as rings (Selection.rings describes them), extracted on the device; []
+        without a lock.  NotImplementedError from a backend that cannot extract outlines."""
+        with self._lock:
+            if self._lock_plane is None:
+                return []
+            return outline_rings(_outline_records(self.backend, self._lock_plane, int(first_cap)))
 
     # ---- the undo journal (DESIGN.md 6f); the helpers below run with the session's lock held ---------------------------------
     def _journals(self, h, w):
@@ -1261,7 +1374,10 @@ class EditSession:
         inside a ring is a hole, and so is the middle of a self-crossing outline -- and every pixel within `grow` (0 .. 16)
         pixels of one.  Rasterised on the device: only the edges go up, and the tile records of the result come down.
         -> Selection; EMPTY (.box None, .count 0) when the outline covers no pixel centre.  Not an edit: nothing is journalled;
-        the frame and the lock play no part.  ValueError for what lasso_edges refuses and a grow outside its range."""
+        the frame and the lock play no part.  ValueError for what lasso_edges refuses and a grow outside its range.
+        `selection.rings()` is a valid argument: integer points are exact under floor(4 v + 0.5) and no pixel
+        centre lies on an edge between pixel corners, so the plane, box and count of that selection come back bit for bit --
+        within the limit of 65 536 edges, which stays as it is (one edge per ring point)."""
         edges = lasso_edges(rings, self.frame_hw)
         grow = self._check_grow(grow)
         with self._lock:

@@ -148,6 +148,17 @@ plus the host route's two parts timed alone, select_lasso and a combine alone, t
 (Pillow's rule at an edge is not the header's), and se_profile_report's per-kernel times of one (b) request and of one combine.
 
     python tools/serve_probe.py --lasso [--reps N] [--out FILE]
+
+--outline: the outline of a selection: --select's disc on a 1921x1081 frame, selected by colour, then outlined:
+  (a) edit:         EditSession.edit(window=..., max_grow=0), the unchanged control (run with --outline-parent on the parent commit's
+                    build: only this leg),
+  (b) rings:        select_similar then Selection.rings() -- the boundary runs extracted on the device, 16 bytes per run come down,
+                    linked into rings on the host,
+  (c) mask_route:   select_similar then Selection.mask() -- the box's crop of the plane comes down -- and the rings traced from its
+                    pixels on the host by tests/outline_util.spec_rings, in the same build;
+plus the parts timed alone (select_similar, rings(), edges(), mask(), the two host linkings, a combine for 6p's comparison), the
+bytes each route downloads, whether the two routes' rings are equal, and the in-library profile of one rings() call:
+    python tools/serve_probe.py --outline [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -1026,6 +1037,92 @@ def lasso_leg(model, reps, parent=False, side=512, grow=2, vertices=300):
     return out
 
 
+def outline_leg(model, reps, parent=False, side=512, tolerance=16):
+    """(a), (b), (c) of the module docstring; parent=True: the leg (a) only, with the calls a build without outlines has"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    frame[..., 0] = frame[..., 0] % 90                               # no noise pixel is similar to the disc's colour
+    win = (283, 705, side, side)
+    seed = (win[0] + side // 2, win[1] + side // 2)
+    yy, xx = np.mgrid[0:h, 0:w]
+    disc = (yy - seed[0]) ** 2 + (xx - seed[1]) ** 2 <= 126 ** 2
+    frame[disc] = 128
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    dev0 = torch.from_numpy(frame).cuda()
+
+    def fresh(session):
+        def put_back():
+            session._frame.copy_(dev0)
+            torch.cuda.synchronize()
+        return put_back
+
+    def timed(fn, put_back=lambda: None):
+        def rounds():
+            for _ in range(2):                 # warm-up: plans, workspace, code objects
+                put_back()
+                fn()
+            ts = []
+            for _ in range(reps):
+                put_back()
+                t0 = time.perf_counter()
+                fn()                           # ends in a device-to-host copy or on the host: the request is complete
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts.sort()
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    s1 = serve.EditSession(model, frame)
+    legs = dict(edit=timed(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True), fresh(s1)))
+    out = dict(tool="serve_probe --outline" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               window=list(win), seed=list(seed), tolerance=tolerance, disc_pixels=int(disc.sum()))
+    if not parent:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import outline_util
+        s2 = serve.EditSession(model, frame)
+
+        def mask_rings(sel):
+            y0, x0 = sel.box[:2]
+            return [[(x + x0, y + y0) for x, y in r] for r in outline_util.spec_rings(sel.mask())]
+        legs.update(rings=timed(lambda: s2.select_similar(seed, tolerance=tolerance).rings()),
+                    mask_route=timed(lambda: mask_rings(s2.select_similar(seed, tolerance=tolerance))))
+        sel = s2.select_similar(seed, tolerance=tolerance)
+        other = s2.select_lasso([[(seed[1] - 40.0, seed[0] - 40.0), (seed[1] + 90.0, seed[0] - 30.0), (seed[1] + 10.0, seed[0] + 95.0)]])
+        records, crop = sel.edges(), sel.mask()
+        parts = dict(select_similar=timed(lambda: s2.select_similar(seed, tolerance=tolerance)), rings=timed(sel.rings), edges=timed(sel.edges),
+                     mask=timed(sel.mask), link_records_on_host=timed(lambda: serve.outline_rings(records)),
+                     trace_mask_on_host=timed(lambda: outline_util.spec_rings(crop)),
+                     combine=timed(lambda: s2.combine(sel, other, "subtract").count))
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    if not parent:
+        out["parts_ms"] = {k: fn() for k, fn in parts.items()}
+        eng = model.engine()
+        eng.profile(True)
+        rings = sel.rings()
+        rep = eng.profile_report()
+        eng.profile(False)
+        ks = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        back = s2.select_lasso(rings)
+        out.update(selected=sel.count, box=list(sel.box), records=int(records.shape[0]), rings=len(rings), ring_points=sum(len(r) for r in rings),
+                   bytes_down_rings=8 + 16 * 4096 if records.shape[0] <= 4096 else 2 * 8 + 16 * (4096 + int(records.shape[0])),
+                   bytes_of_the_records=16 * int(records.shape[0]), bytes_down_mask=int(crop.size),
+                   same_rings_as_the_mask_route=bool(rings == mask_rings(sel)),
+                   round_trip_is_the_plane=bool(torch.equal(back.plane, sel.plane) and (back.box, back.count) == (sel.box, sel.count)),
+                   svg_path_chars=len(serve.rings_svg_path(rings)), rings_profiled=ks,
+                   rings_minus_mask_route_ms=round(out["ms"]["rings"]["median"] - out["ms"]["mask_route"]["median"], 3),
+                   rings_alone_minus_combine_ms=round(out["parts_ms"]["rings"]["median"] - out["parts_ms"]["combine"]["median"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -1053,6 +1150,8 @@ def main():
     ap.add_argument("--select-parent", action="store_true", help="the edit leg of --select only")
     ap.add_argument("--lasso", action="store_true", help="lasso selections (see the module docstring)")
     ap.add_argument("--lasso-parent", action="store_true", help="the edit leg of --lasso only")
+    ap.add_argument("--outline", action="store_true", help="the outline of a selection (see the module docstring)")
+    ap.add_argument("--outline-parent", action="store_true", help="the edit leg of --outline only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -1064,8 +1163,10 @@ def main():
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
-            or args.select or args.select_parent or args.lasso or args.lasso_parent):
-        if args.lasso or args.lasso_parent:
+            or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent):
+        if args.outline or args.outline_parent:
+            res = outline_leg(model, args.reps, parent=args.outline_parent)
+        elif args.lasso or args.lasso_parent:
             res = lasso_leg(model, args.reps, parent=args.lasso_parent)
         elif args.select or args.select_parent:
             res = select_leg(model, args.reps, parent=args.select_parent)
