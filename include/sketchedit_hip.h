@@ -363,6 +363,13 @@ int se_profile_report(se_ctx* ctx, char* buf, size_t cap);
 int se_debug_set_option(const char* name, int value);
 int se_debug_get_option(const char* name, int* value);
 void se_debug_reset_options(void);
+/* Which kernel form(s) se_gated_conv2d_ex would launch for this call, without running it: the comma-separated
+ * form names of its conv launches as se_profile_report records them, e.g. "wino24", "vecbias,rconv16", "small_conv".  cin1 = 0:
+ * one source.  exec_flags: SE_FLAG_LOW_LATENCY | SE_FLAG_BF16 | SE_FLAG_CONSERVATIVE; net_id: the network whose layer it is taken
+ * to be (SE_NET_G for the per-op entries).  Needs no ctx and no device: host arithmetic on the arguments and the developer
+ * switches.  Returns 1 for a layer se_gated_conv2d_ex refuses or a buffer that is too small. */
+int se_debug_gconv_form(int cin, int cin1, int src1_is_vector, int cout, int k, int stride, int rate, int act, int upsample,
+                        int B, int H, int W, int exec_flags, int net_id, char* out, size_t cap);
 
 /* ---- per-op entry points (unit tests; same kernels as the forwards) ----------------------------
  * gen_conv / gen_deconv (models/networks/utils.py:9-51): x (B,Cin,H,W) device, w (Cout,Cin,k,k) and

@@ -35,7 +35,7 @@ LOW_LATENCY_MAX_SINGLE_IMAGE = 512 * 512
 SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_weights", "se_weights_ready",
            "se_workspace_bytes", "se_netM_forward", "se_netM_forward_ex", "se_netG_forward", "se_netG_forward_taps", "se_inference", "se_inference_u8", "se_gated_conv2d",
            "se_gated_conv2d_ex", "se_attention", "se_attention_ex", "se_quantize_u8", "se_dequantize_u8", "se_inference_u8io", "se_profile_enable",
-           "se_profile_report", "se_debug_set_option", "se_debug_get_option", "se_debug_reset_options",
+           "se_profile_report", "se_debug_set_option", "se_debug_get_option", "se_debug_reset_options", "se_debug_gconv_form",
            "se_resize_u8", "se_prepare_u8", "se_edit_u8", "se_edit_u8_workspace_bytes", "se_resample_coeffs",
            "se_window_gather_u8", "se_window_border_u8", "se_window_paste_u8", "se_edit_window_u8", "se_edit_window_u8_workspace_bytes",
            "se_window_gather_resize_u8", "se_window_paste_resize_u8", "se_edit_window_scaled_u8", "se_edit_window_scaled_u8_workspace_bytes",
@@ -98,13 +98,8 @@ def build_library(force=False, verbose=False, extra_flags=()):
     an exclusive file lock, so concurrent builders (ranks, test workers) do not write the same objects."""
     import fcntl
     from concurrent.futures import ThreadPoolExecutor
-    hdrs = [os.path.join(CSRC, "se_kernels.h"), os.path.join(CSRC, "se_device.h"), os.path.join(CSRC, "se_pack.h"), os.path.join(_HERE, "..", "include", "sketchedit_hip.h"),
-            os.path.join(_HERE, "..", "include", "sketchedit_png.h"), os.path.join(_HERE, "..", "include", "sketchedit_jpg.h"),
-            os.path.join(_HERE, "..", "include", "sketchedit_jpg2.h"), os.path.join(_HERE, "..", "include", "sketchedit_feather.h"),
-            os.path.join(_HERE, "..", "include", "sketchedit_fill.h"), os.path.join(_HERE, "..", "include", "sketchedit_select.h"),
-            os.path.join(_HERE, "..", "include", "sketchedit_lasso.h"),
-            os.path.join(_HERE, "..", "include", "sketchedit_outline.h"),
-            os.path.join(CSRC, "se_jpg_tables.h")]
+    import glob
+    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(_HERE, "..", "include", "*.h"))
     hdr_t = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
@@ -342,6 +337,21 @@ def get_option(name):
 
 def reset_options():
     load_library().se_debug_reset_options()
+
+
+def gconv_form(cin, cout, H, W, k=3, stride=1, rate=1, act="elu", upsample=False, cin1=0, x1_is_vector=False, B=1,
+               low_latency=False, bf16=False, conservative=False, net=SE_NET_G):
+    """The conv launches gated_conv2d would make for this call, as a list of form names (['vecbias', 'wino24'], ['small_conv']):
+    se_debug_gconv_form, the library's own rule (choose_form) evaluated on the host -- no device, nothing runs.  cin: the first
+    source's channels; cin1: the second's (0: none)."""
+    flags = (FLAG_LOW_LATENCY if low_latency else 0) | (FLAG_BF16 if bf16 else 0) | (FLAG_CONSERVATIVE if conservative else 0)
+    buf = ctypes.create_string_buffer(64)
+    fn = load_library().se_debug_gconv_form      # (bound here, not at load: a build from before the entry still loads through SKETCHEDIT_HIP_LIB)
+    fn.argtypes, fn.restype = [ctypes.c_int] * 14 + [ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int
+    if fn(cin, cin1, int(bool(x1_is_vector)), cout, k, stride, rate, {"elu": 0, "relu": 1, None: 2}[act],
+          int(bool(upsample)), B, H, W, flags, net, buf, len(buf)):
+        raise SketchEditHipError("gconv_form: not a layer gated_conv2d takes")
+    return buf.value.decode().split(",")
 
 
 def flags_from_opt(opt):

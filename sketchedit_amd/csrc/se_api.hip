@@ -235,239 +235,162 @@ int poison(se_ctx* c, void* p, size_t bytes, hipStream_t st) {
   return 0;
 }
 
-// ---- narrow layers in raw-tile form (se_rtile.hip): returns 0 and sets *done when the layer was launched there ------
-int try_rtile(se_ctx* c, const Layer& L, bool bf, const float* src0, int C0, const float* src1, float* dst, int B, int Hin, int Win,
-              int Ho, int Wo, int pad, bool* done) {
-  *done = false;
-  const LayerDef& d = L.def;
-  if (!opt(OPT_RTILE) || src1 || d.stride != 1 || d.rate != 1 || (L.cfg != GC_N48 && L.cfg != GC_N24)) return 0;
-  {
-    // low-latency mode: only when the tiles still cover the CUs (the small-grid gather-GEMM splits rows over blockIdx.y).
-    // Counted PER IMAGE like the Winograd grids of run_gconv: the kernel a layer runs depends on the image size and the
-    // mode only, never on the batch (with B in the count a 128x128 image took the raw-tile kernel at B = 2 and the
-    // gather-GEMM at B = 1, and its bits differed between the two calls)
-    const int TR0 = rtile_rows(bf);
-    const long tiles = (long)((Hin + TR0 - 1) / TR0) * ((Win + 15) / 16) * (d.up ? 4 : 1);
-    if (c->low_latency && tiles < opt(OPT_RTILE_LL_MIN)) return 0;
+// ---- launching one gated conv ---------------------------------------------------------------------------------------
+// choose_form (se_dispatch.h) decides the kernel form of a call; run_gconv below switches into one launcher per family, which
+// fills that family's params and launch cost and launches.  A launcher decides nothing: what it reads of `ch` is the choice.
+struct ConvLaunch {       // one call: where it runs, the layer, the sources (src1: a tensor, a vector or null), the sizes
+  se_ctx* c;
+  const Layer& L; const LayerDef& d; const LayerFacts& f;
+  const float* src0; int C0; const float* src1; int C1, src1_vec; float* dst;
+  int B, Hin, Win, Ho, Wo, pad;
+  bool bf;
+  double alg(int taps) const { return 2.0 * (double)B * Ho * Wo * d.cout * d.cin * taps; }       // the layer's cost as the reference defines it
+
+  // a Winograd launch on tiles of 2 rows x `tcols` columns at dilation `dil` (no second source, no folded bias: the caller sets those)
+  WinoParams wino_params(const float* upk, const float* bias, int dil, int tcols) const {
+    WinoParams wp;
+    memset(&wp, 0, sizeof wp);
+    wp.src = src0; wp.upk = upk; wp.bias = bias; wp.dst = dst;
+    wp.B = B; wp.h = Hin; wp.w = Win; wp.d = dil; wp.th = Hin / 2; wp.tw = Win / tcols;
+    wp.total_tiles = B * wp.th * wp.tw; wp.act = d.act;
+    wp.xcd = xcd_remap_enabled();
+    udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
+    udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
+    udiv_magic_host((unsigned)wp.d, &wp.div_d_m, &wp.div_d_l);
+    return wp;
   }
-  const int es = bf ? 2 : 4, gran = bf ? 8 : 4;
-  const DirectImage& di = L.direct[bf];
-  const int CG = di.CG, nch = di.nch;
-  const float* wimg = di.w;
-  if (!wimg || C0 != CG * gran) return 0;
-  // 24 -> 24 3x3: F(2,3) along x on the raw tile (se_rtilew.hip): 160 instead of 224 MFMAs per wave.  SE_RTILE_WX=0: the direct form
-  {
-    const int wx_mode = opt(OPT_RTILE_WX);
-    if (wx_mode != 0 && !bf && L.d_wx && d.k == 3 && !d.up && C0 == 24 && d.cin == 24 && d.cout == 24 && (Win % 2) == 0 &&
-        (long long)B * Hin * Win * 96 < (1ll << 31)) {
-      RTileParams p;
-      memset(&p, 0, sizeof p);
-      p.src = src0; p.wpk = L.d_wx; p.bias = L.d_b; p.dst = dst;
-      p.B = B; p.Hin = Hin; p.Win = Win; p.C = C0; p.G = L.G; p.OH = Ho; p.OW = Wo;
-      p.ty = (Hin + 15) / 16; p.tx = (Win + 15) / 16;       // blocks of 16 x 16 outputs
-      p.act = d.act; p.xcd = xcd_remap_enabled(); p.NP = 32;
-      udiv_magic_host((unsigned)(p.ty * p.tx), &p.div_cg_m, &p.div_cg_l);      // (reused fields: blk / (ty * tx), t2 / tx)
-      udiv_magic_host((unsigned)p.tx, &p.div_rw_m, &p.div_rw_l);
-      const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-      const bool two_d = wx_mode != 1 && L.d_wx2 && (Hin % 2) == 0;       // SE_RTILE_WX=1: the one-dimensional form
-      set_launch_cost(alg, 4.0 * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name,
-                      (double)B * p.ty * p.tx * 8.0 * (two_d ? 96.0 : 160.0) * 2048.0);       // MFMAs of 16x16x4 per wave and block
-      if (two_d) {
-        p.wpk = L.d_wx2;
-        HIPCHK(c, launch_rtilew2(p, c->st));
-        *done = true;
-        return 0;
-      }
-      HIPCHK(c, launch_rtilew(p, c->st));
-      *done = true;
+  // 96 (+ 96) -> 192 and 48 -> 192: F(2x2,3x3), 16 of 36 products (se_wino.hip); hybrid F(2,3) x F(4,3) on 2x4 tiles, 24 of 72
+  // (se_wino24.hip).  Folded vector source: half the positions' K, only the first source's half executed (311 -> 170 us at 256x256 B=32)
+  int launch_form_wino(const Choice& ch) const {
+    const double alg3x3 = alg(9);
+    if (ch.form == F_WINO24_C48) {       // xconv5: 2 chunks per position, the second half empty
+      const WinoParams wp = wino_params(L.d_u24, L.d_ub24, d.rate, 4);
+      set_launch_cost(alg3x3, 4.0 * ((double)B * Hin * Win * 48 + (double)B * Hin * Win * 96), d.name, alg3x3 * 24.0 / 72.0);
+      HIPCHK(c, launch_wino24_c48(wp, c->st));
       return 0;
     }
+    const bool folded = ch.fold, f43 = ch.form == F_WINO24;
+    if (folded) HIPCHK(c, launch_vecbias(L.d_wv, src1, c->vbias_ws, B, 96, c->st));
+    const float* s1 = folded ? nullptr : src1;
+    WinoParams wp = f43 ? wino_params(s1 ? L.d_u24b : L.d_u24, L.d_ub24, d.rate, 4) : wino_params(folded ? L.d_u1 : L.d_u, L.d_b, d.rate, 2);
+    wp.src1 = s1; wp.src1_vec = folded ? 0 : src1_vec; wp.vbias = folded ? c->vbias_ws : nullptr;
+    if ((double)B * Hin * Win * 384.0 >= 2147483648.0) return fail(c, "layer %s: tensor exceeds 2^31 bytes", d.name);
+    set_launch_cost(alg3x3, 4.0 * 2.0 * (double)B * Hin * Win * 96, d.name,
+                    f43 ? alg3x3 * 24.0 / 72.0 * (folded ? 0.5 : 1.0) : alg3x3 * 16.0 / 36.0 * (folded ? 0.5 : 1.0));
+    HIPCHK(c, f43 ? launch_wino24(wp, c->st) : launch_wino(wp, c->st));
+    return 0;
   }
-  // dense-K form of the 5x5 first layers (fp32): SE_RTILE_DENSE=0 keeps the channel-padded K
-  if (opt(OPT_RTILE_DENSE) != 0 && !bf && L.d_wd && L.dense && d.k == 5 && !d.up && L.cfg == GC_N48 && (long long)Hin * Win * C0 * 4 < (1ll << 31)) {
-    // The kernel addresses its source with 32-bit byte offsets.  A batch beyond that range is run as sub-launches of the
-    // SAME kernel form over image ranges (switching to the channel-padded kernel would change the summation
-    // order, i.e. the bit-identity of an image's result across batch compositions within one execution mode).
+  // 48 -> 96, and 24 -> 96 with one chunk per position (se_wino48.hip): 16 of 36 products
+  int launch_form_wino48(const Choice& ch) const {
+    const WinoParams wp = wino_params(L.d_u, L.d_ub, d.rate, 2);
+    const bool c24 = ch.form == F_WINO48_C24;
+    set_launch_cost(alg(9), c24 ? 4.0 * ((double)B * Hin * Win * 24 + (double)B * Hin * Win * 48) : 4.0 * 2.0 * (double)B * Hin * Win * 48, d.name,
+                    alg(9) * 16.0 / 36.0);
+    HIPCHK(c, c24 ? launch_wino48_c24(wp, c->st) : launch_wino48(wp, c->st));
+    return 0;
+  }
+  // gen_deconv 96 -> 96 and 48 -> 48: F(2x2,2x2) on the sub-pixel classes, 9 of 36 products (se_wino_up.hip, se_wino_up48.hip;
+  // 48: in the K pairing of the 48-channel kernels, 28 k-halves executed for 27 of work)
+  int launch_form_winoup(const Choice& ch) const {
+    const WinoParams wp = wino_params(L.d_u, L.d_ub, 1, 2);
+    if (ch.form == F_WINOUP) {
+      set_launch_cost(alg(9), 4.0 * ((double)B * Hin * Win * 96 + (double)B * Ho * Wo * 48), d.name, alg(9) * 9.0 / 36.0);
+      HIPCHK(c, launch_winoup(wp, c->st));
+      return 0;
+    }
+    set_launch_cost(alg(9), 4.0 * ((double)B * Hin * Win * 48 + (double)B * Ho * Wo * 24), d.name, alg(9) * 9.0 / 36.0 * 28.0 / 27.0);
+    HIPCHK(c, launch_winoup48(wp, c->st));
+    return 0;
+  }
+
+  // what every raw-tile launch of the narrow layers starts from: `trows` output rows x 16 columns per tile
+  RTileParams rtile_params(const float* wpk, int trows) const {
+    RTileParams p;
+    memset(&p, 0, sizeof p);
+    p.src = src0; p.wpk = wpk; p.bias = L.d_b; p.dst = dst;
+    p.B = B; p.Hin = Hin; p.Win = Win; p.C = C0; p.OH = Ho; p.OW = Wo;
+    p.G = bf ? (f.G + 7) & ~7 : f.G; p.NP = f.NP;
+    p.ty = (Hin + trows - 1) / trows; p.tx = (Win + 15) / 16;
+    p.act = d.act; p.bf16 = bf ? 1 : 0; p.xcd = xcd_remap_enabled();
+    return p;
+  }
+  // 24 -> 24 3x3: F(2,3) along x on the raw tile, 160 instead of 224 MFMAs per wave, or two-dimensional, 96 (se_rtilew.hip)
+  int launch_form_rtilew(const Choice& ch) const {
+    const bool two_d = ch.form == F_RTILEW2;
+    RTileParams p = rtile_params(two_d ? L.d_wx2 : L.d_wx, 16);       // blocks of 16 x 16 outputs
+    udiv_magic_host((unsigned)(p.ty * p.tx), &p.div_cg_m, &p.div_cg_l);      // (reused fields: blk / (ty * tx), t2 / tx)
+    udiv_magic_host((unsigned)p.tx, &p.div_rw_m, &p.div_rw_l);
+    set_launch_cost(alg(9), 4.0 * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name,
+                    (double)B * p.ty * p.tx * 8.0 * (two_d ? 96.0 : 160.0) * 2048.0);       // MFMAs of 16x16x4 per wave and block
+    HIPCHK(c, two_d ? launch_rtilew2(p, c->st) : launch_rtilew(p, c->st));
+    return 0;
+  }
+  // dense-K form of the 5x5 first layers (fp32), direct or F(2,5) along x (rtile_dense5w_kernel: 6 positions x ceil(5 Cd / 4)
+  // k-steps per 2 outputs).  The kernel addresses its source with 32-bit byte offsets: a batch beyond that range is run as
+  // sub-launches of the SAME kernel form over image ranges (switching to the channel-padded kernel would change the
+  // summation order, i.e. the bit-identity of an image's result across batch compositions within one execution mode).
+  int launch_form_rtile_dense5(const Choice& ch) const {
+    const bool along_x = ch.form == F_RTILE_DENSE5W;
     const long long per_img = (long long)Hin * Win * C0 * 4;
     const long long lim = addr_limit();       // (SE_TEST_OFFSET_LIMIT, a test aid: a smaller byte range forces the sub-launches)
     const int bmax = (int)std::max<long long>(1, (lim - 1) / per_img);
     for (int b0 = 0; b0 < B; b0 += bmax) {
       const int nb = std::min(bmax, B - b0);
-      RTileParams p;
-      memset(&p, 0, sizeof p);
-      p.src = src0 + (size_t)b0 * Hin * Win * C0; p.wpk = L.d_wd; p.bias = L.d_b; p.dst = dst + (size_t)b0 * Ho * Wo * L.G;
-      p.B = nb; p.Hin = Hin; p.Win = Win; p.C = C0; p.G = L.G; p.OH = Ho; p.OW = Wo;
-      p.ty = (Hin + 7) / 8; p.tx = (Win + 15) / 16;
-      p.act = d.act; p.xcd = xcd_remap_enabled(); p.dense = L.dense; p.nch = L.nchd; p.NP = 48;
-      const double alg = 2.0 * (double)nb * Ho * Wo * d.cout * d.cin * 25;
-      // F(2,5) along x (rtile_dense5w_kernel; even widths): 6 positions x ceil(5 Cd / 4) k-steps per 2 outputs.  SE_RTILE_D5W=0: direct
-      if (opt(OPT_RTILE_D5W) != 0 && L.d_wdw && (Win % 2) == 0) {
-        p.wpk = L.d_wdw; p.dense = L.dense + 100;
-        set_launch_cost(alg, 4.0 * ((double)nb * Hin * Win * d.cin + (double)nb * Ho * Wo * (d.cout / 2)), d.name,
-                        (double)nb * p.ty * p.tx * 4.0 * (6.0 * ((5 * L.dense + 3) / 4) * 3.0) * 2048.0);
-        HIPCHK(c, launch_rtile(p, c->st));
-        continue;
-      }
-      set_launch_cost(alg, 4.0 * ((double)nb * Hin * Win * d.cin + (double)nb * Ho * Wo * (d.cout / 2)), d.name,
-                      2.0 * (double)nb * Hin * Win * 48.0 * (4.0 * ((25 * L.dense + 3) / 4)));       // ceil(K / 4) k-steps of 4
+      RTileParams p = rtile_params(along_x ? L.d_wdw : L.d_wd, 8);
+      p.src = src0 + (size_t)b0 * Hin * Win * C0; p.dst = dst + (size_t)b0 * Ho * Wo * f.G; p.B = nb;
+      p.dense = along_x ? f.dense + 100 : f.dense; p.nch = f.nchd;
+      const double algn = 2.0 * (double)nb * Ho * Wo * d.cout * d.cin * 25;
+      set_launch_cost(algn, 4.0 * ((double)nb * Hin * Win * d.cin + (double)nb * Ho * Wo * (d.cout / 2)), d.name,
+                      along_x ? (double)nb * p.ty * p.tx * 4.0 * (6.0 * ((5 * f.dense + 3) / 4) * 3.0) * 2048.0
+                              : 2.0 * (double)nb * Hin * Win * 48.0 * (4.0 * ((25 * f.dense + 3) / 4)));       // ceil(K / 4) k-steps of 4
       HIPCHK(c, launch_rtile(p, c->st));
     }
-    *done = true;
     return 0;
   }
-  // bf16: pair-of-taps form of the 5x5 first layers whose stored NHWC8 input has at most four real channels (SE_RTILE_DENSE=0:
-  // the 8-channel-granule K)
-  if (opt(OPT_RTILE_DENSE) != 0 && bf && L.d_w16d && d.k == 5 && !d.up && L.cfg == GC_N48 && C0 == 8 &&
-      (long long)B * Hin * Win * 16 < (1ll << 31)) {
-    RTileParams p;
-    memset(&p, 0, sizeof p);
-    p.src = src0; p.wpk = L.d_w16d; p.bias = L.d_b; p.dst = dst;
-    p.B = B; p.Hin = Hin; p.Win = Win; p.C = C0; p.CG = 1; p.T = 25; p.KW = 5;
-    p.pad = pad; p.OH = Ho; p.OW = Wo; p.G = (L.G + 7) & ~7;
-    p.nch = 2; p.NP = 48; p.RH = 32 + 4; p.RW = 21;                     // one column more than the halo: the sixth tap of a pair row
-    p.raw_bytes = (p.RH * p.RW * 8 + 1023) & ~1023;
-    udiv_magic_host((unsigned)p.RW, &p.div_rw_m, &p.div_rw_l);
-    udiv_magic_host(1u, &p.div_cg_m, &p.div_cg_l);
-    p.ty = (Hin + 31) / 32; p.tx = (Win + 15) / 16;
-    p.act = d.act; p.bf16 = 1; p.xcd = xcd_remap_enabled(); p.dense = 204;
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 25;
-    set_launch_cost(alg, 2.0 * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name,
-                    2.0 * (double)B * Hin * Win * 48.0 * 128.0);
-    HIPCHK(c, launch_rtile(p, c->st));
-    *done = true;
-    return 0;
-  }
-  const int KW = d.up ? 2 : d.k, KH = KW;
-  RTileParams p;
-  memset(&p, 0, sizeof p);
-  const int TR = rtile_rows(bf);
-  p.RH = TR + KH - 1; p.RW = 16 + KW - 1;
-  p.raw_bytes = (p.RH * p.RW * C0 * es + 1023) & ~1023;
-  if (p.raw_bytes + nch * L.NP * 128 > 80 * 1024) return 0;                 // two workgroups per CU or not at all
-  if ((long long)B * Hin * Win * C0 * es >= (1ll << 31)) return 0;
-  p.src = src0; p.wpk = wimg; p.bias = L.d_b; p.dst = dst;
-  p.B = B; p.Hin = Hin; p.Win = Win; p.C = C0; p.CG = CG; p.T = L.T; p.KW = KW;
-  p.magicCG = (65536 + CG - 1) / CG; p.magicKW = 256 / KW + 1;
-  for (int gi = 0; gi < nch * 8 + 8; ++gi)
-    if (((gi * p.magicCG) >> 16) != gi / CG) return 0;
-  for (int t = 0; t <= L.T + 8; ++t)
-    if (((t * p.magicKW) >> 8) != t / KW) return 0;
-  p.pad = pad; p.up2 = d.up ? 1 : 0; p.OH = Ho; p.OW = Wo;
-  p.G = bf ? (L.G + 7) & ~7 : L.G;
-  p.nch = nch; p.NP = L.NP;
-  udiv_magic_host((unsigned)(C0 * es / 16), &p.div_cg_m, &p.div_cg_l);
-  udiv_magic_host((unsigned)p.RW, &p.div_rw_m, &p.div_rw_l);
-  p.ty = (Hin + TR - 1) / TR; p.tx = (Win + 15) / 16;
-  p.act = d.act; p.bf16 = bf ? 1 : 0; p.xcd = xcd_remap_enabled();
-  {
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * d.k * d.k;
-    const double exec = 2.0 * (double)B * Hin * Win * (d.up ? 4.0 : 1.0) * L.NP * (nch * (bf ? 64.0 : 32.0));
-    set_launch_cost(alg, (double)es * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name, exec);
-  }
-  HIPCHK(c, launch_rtile(p, c->st));
-  *done = true;
-  return 0;
-}
-
-// ---- the direct gather-GEMM (se_gconv.hip) on the image of one precision: the fallback of every gated conv ----------
-int run_gather(se_ctx* c, const Layer& L, bool bf, const float* src0, int C0, const float* src1, int C1, int src1_vec, float* dst,
-               int B, int Hin, int Win, int Ho, int Wo, int pad) {
-  const LayerDef& d = L.def;
-  const DirectImage& di = L.direct[bf];
-  const int es = bf ? 2 : 4, gran = bf ? 8 : 4;
-  GConvParams p;
-  memset(&p, 0, sizeof p);
-  p.bf16 = bf ? 1 : 0;
-  p.src0 = src0; p.src1 = src1 ? src1 : src0; p.wpk = di.w; p.bias = L.d_b; p.dst = dst; p.zeros = c->zeros;
-  p.B = B; p.Hin = Hin; p.Win = Win; p.Ho = d.up ? Hin : Ho; p.Wo = d.up ? Win : Wo;   // up2: rows walk the source grid
-  p.up2 = d.up ? 1 : 0; p.OH = Ho; p.OW = Wo;
-  p.C0 = C0; p.C1 = C1 ? C1 : C0; p.C0g = C0 / gran; p.CG = di.CG;
-  const int KW = d.up ? 2 : d.k;
-  p.T = L.T; p.KW = KW; p.stride = d.stride; p.dil = d.rate; p.pad = pad;
-  p.magicCG = (65536 + di.CG - 1) / di.CG; p.magicKW = 256 / KW + 1; p.magicKH = L.T / KW;
-  for (int gi = 0; gi < di.nch * 8 + 8; ++gi)
-    if (((gi * p.magicCG) >> 16) != gi / di.CG) return fail(c, "layer %s: magic division check failed", d.name);
-  for (int t = 0; t <= L.T + 8; ++t)
-    if (((t * p.magicKW) >> 8) != t / KW) return fail(c, "layer %s: magic tap division check failed", d.name);
-  const int Gs = bf ? (L.G + 7) & ~7 : L.G;      // stored channel stride of the output
-  // 32-bit byte offsets (sentinel 0x80000000): source and destination below 2^31 BYTES
-  if ((double)B * Hin * Win * (C0 > C1 ? C0 : C1) * es >= 2147483648.0 || (double)B * Ho * Wo * Gs * es >= 2147483648.0)
-    return fail(c, "layer %s: a tensor of this launch exceeds 2^31 bytes (32-bit byte offsets) -- split the batch", d.name);
-  for (int j = 0; j < p.magicKH; ++j) p.rep |= 1u << (j * KW);
-  udiv_magic_host((unsigned)(p.Ho * p.Wo), &p.div_hw_m, &p.div_hw_l);
-  udiv_magic_host((unsigned)p.Wo, &p.div_w_m, &p.div_w_l);
-  p.Hlim = Hin; p.Wlim = Win;
-  p.src1_vec = src1_vec; p.nch = di.nch; p.G = Gs; p.act = d.act; p.total_pix = B * p.Ho * p.Wo;
-  p.xcd = xcd_remap_enabled();
-  p.np_full = L.NP; p.nf_full = L.NP / 32; p.small_grid = c->low_latency ? 1 : 0;
-  // algorithmic cost as the reference defines the layer (3x3 on the upsampled grid for gen_deconv)
-  {
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * d.k * d.k;
-    // executed: the packed K (channels padded to granules, taps x channels padded to whole chunks) and row (NP) sizes the
-    // MFMAs really run over; the sub-pixel form of gen_deconv runs 4 classes x 4 taps instead of 9 taps on the upsampled grid
-    const double exec = 2.0 * (double)B * p.Ho * p.Wo * (d.up ? 4.0 : 1.0) * L.NP * (di.nch * (bf ? 64.0 : 32.0));
-    set_launch_cost(alg, (double)es * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name, exec);
-  }
-  HIPCHK(c, launch_gconv(L.cfg, p, c->st));
-  return 0;
-}
-
-// ---- bf16 mode: every gated conv is the direct gather-GEMM on v_mfma_f32_16x16x32_bf16 (se_gconv.hip, BF16) -----------
-// (The Winograd transforms would have to run in fp32 on bf16 data and round the transformed tiles again; at 16x the
-// MFMA rate the layers are bound by the LDS fill, not by multiply-adds, so there is nothing for them to buy.)
-// two polyphase sub-images of 8 columns (and at most 8 rows) share one 8 x 16 raw tile (rconv16b_kernel, p.dual)
-static bool rconv16_dual_ok(const Layer& L, const LayerDef& d, int Hin, int Win) {
-  if (opt(OPT_RCONV16_DUAL) == 0) return false;
-  return L.d_w16s && (d.rate % 2) == 0 && Win / d.rate == 8 && Hin / d.rate <= 8 && Hin / d.rate >= 4;
-}
-
-int run_gconv16(se_ctx* c, const Layer& L, const float* src0, int C0, const float* src1, int C1, int src1_vec, float* dst,
-                int B, int Hin, int Win, int Ho, int Wo, int pad) {
-  const LayerDef& d = L.def;
-  if (!L.direct[1].w) return fail(c, "layer %s: no bf16 weight image", d.name);
-  if ((C0 + C1) != L.direct[1].CG * 8) return fail(c, "layer %s: bf16 source channels %d+%d != packed %d", d.name, C0, C1, L.direct[1].CG * 8);
-  // the dominant shape (96 -> 192, 3x3, stride 1) runs in the raw-tile form when its polyphase sub-images are large
-  // enough to fill 8 x 16 tiles reasonably (se_rconv16.hip); SE_RCONV16=0 keeps it on the gather-GEMM
-  const bool use_rconv = opt(OPT_RCONV16) != 0;
-  // conv11 of netG: the spatially constant second source folded into a bias table (run_gconv / launch_vecbias), the layer on
-  // the 8 x 16 raw-tile kernel with the first source alone
-  {
-    if (opt(OPT_VECBIAS) != 0 && use_rconv && !c->low_latency && src1 && src1_vec && c->vbias_ws && c->vec32 && L.d_w16s && L.d_wv16 &&
-        d.k == 3 && d.stride == 1 && d.rate == 1 && !d.up && d.cin == 192 && d.cout == 192 && C0 == 96 && C1 == 96 &&
-        Hin >= 12 && Win >= 12 && (long long)B * Hin * Win * 192 < (1ll << 31)) {
-      HIPCHK(c, launch_vecbias(L.d_wv16, c->vec32, c->vbias_ws, B, 96, c->st, 1));
-      RConvParams rp;
-      memset(&rp, 0, sizeof rp);
-      rp.src = src0; rp.wpk = L.d_w16s; rp.bias = L.d_b; rp.dst = dst; rp.vbias = c->vbias_ws;
-      rp.B = B; rp.h = Hin; rp.w = Win; rp.d = 1; rp.hs = Hin; rp.ws = Win;
-      rp.ty = (Hin + 7) / 8; rp.tx = (Win + 15) / 16;
-      rp.act = d.act; rp.xcd = xcd_remap_enabled();
-      const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-      set_launch_cost(alg, 2.0 * 2.0 * (double)B * Hin * Win * 96, d.name, 2.0 * (double)B * Hin * Win * 192.0 * 864.0);
-      HIPCHK(c, launch_rconv16(rp, c->st));
-      return 0;
+  // the raw-tile kernel on the direct image (se_rtile.hip), fp32 and bf16; bf16 pair-of-taps form of the 5x5 first layers
+  int launch_form_rtile(const Choice& ch) const {
+    const int es = bf ? 2 : 4, TR = rtile_rows(bf);
+    RTileParams p = rtile_params(ch.form == F_RTILE_D4 ? L.d_w16d : L.direct[bf], TR);
+    p.pad = pad;
+    if (ch.form == F_RTILE_D4) {
+      p.CG = 1; p.T = 25; p.KW = 5; p.nch = 2; p.dense = 204;
+      p.RH = 32 + 4; p.RW = 21;                     // one column more than the halo: the sixth tap of a pair row
+      p.raw_bytes = (p.RH * p.RW * 8 + 1023) & ~1023;
+      udiv_magic_host(1u, &p.div_cg_m, &p.div_cg_l);
+      set_launch_cost(alg(25), 2.0 * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name, 2.0 * (double)B * Hin * Win * 48.0 * 128.0);
+    } else {
+      const int KW = d.up ? 2 : d.k, CG = f.CG[bf], nch = f.nch[bf];
+      p.CG = CG; p.T = f.T; p.KW = KW; p.nch = nch; p.up2 = d.up ? 1 : 0;
+      p.RH = TR + KW - 1; p.RW = 16 + KW - 1;
+      p.raw_bytes = (p.RH * p.RW * C0 * es + 1023) & ~1023;
+      p.magicCG = (65536 + CG - 1) / CG; p.magicKW = 256 / KW + 1;        // (choose_form verified both on the ranges used)
+      udiv_magic_host((unsigned)(C0 * es / 16), &p.div_cg_m, &p.div_cg_l);
+      set_launch_cost(alg(d.k * d.k), (double)es * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name,
+                      2.0 * (double)B * Hin * Win * (d.up ? 4.0 : 1.0) * f.NP * (nch * (bf ? 64.0 : 32.0)));
     }
+    udiv_magic_host((unsigned)p.RW, &p.div_rw_m, &p.div_rw_l);
+    HIPCHK(c, launch_rtile(p, c->st));
+    return 0;
   }
-  if (use_rconv && !c->low_latency && d.k == 3 && d.stride == 1 && !d.up && d.cin == 96 && d.cout == 192 && !src1 && C0 == 96 &&
-      (Hin % d.rate) == 0 && (Win % d.rate) == 0 && L.direct[1].nch == 14 && L.d_w16s && (long long)B * Hin * Win * 192 < (1ll << 31) &&
-      ((Hin / d.rate >= 12 && Win / d.rate >= 12) || rconv16_dual_ok(L, d, Hin, Win))) {
+
+  // bf16, 96 -> 192 3x3 stride 1 on 8 x 16 raw tiles of the polyphase sub-images (se_rconv16.hip).  dual: sub-images of 8 x 8
+  // (dilation 16 at 128 x 128, 8 at 64 x 64), two phases share a tile.  fold (conv11 of netG): the spatially constant second
+  // source folded into a bias table, the layer on the first source alone
+  int launch_form_rconv16(const Choice& ch) const {
+    if (ch.fold) HIPCHK(c, launch_vecbias(L.d_wv16, c->vec32, c->vbias_ws, B, 96, c->st, 1));
     RConvParams rp;
     memset(&rp, 0, sizeof rp);
-    // sub-images of 8 x 8 (dilation 16 at 128 x 128, 8 at 64 x 64): two phases share an 8 x 16 tile (SE_RCONV16_DUAL=0: gather-GEMM)
-    rp.dual = !(Hin / d.rate >= 12 && Win / d.rate >= 12);
-    rp.src = src0; rp.wpk = L.d_w16s; rp.bias = L.d_b; rp.dst = dst;
+    rp.dual = ch.form == F_RCONV16_DUAL;
+    rp.src = src0; rp.wpk = L.d_w16s; rp.bias = L.d_b; rp.dst = dst; rp.vbias = ch.fold ? c->vbias_ws : nullptr;
     rp.B = B; rp.h = Hin; rp.w = Win; rp.d = d.rate; rp.hs = Hin / d.rate; rp.ws = Win / d.rate;
     rp.ty = (rp.hs + 7) / 8; rp.tx = (rp.ws + 15) / 16;
     rp.act = d.act; rp.xcd = xcd_remap_enabled();
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-    set_launch_cost(alg, 2.0 * 2.0 * (double)B * Hin * Win * 96, d.name, 2.0 * (double)B * Hin * Win * 192.0 * 864.0);
+    set_launch_cost(alg(9), 2.0 * 2.0 * (double)B * Hin * Win * 96, d.name, 2.0 * (double)B * Hin * Win * 192.0 * 864.0);
     HIPCHK(c, launch_rconv16(rp, c->st));
     return 0;
   }
-  // 96-row stride-1 layers (3x3 48/24 -> 96, gen_deconv 96 -> 96): raw-tile form, se_rconv96.hip (SE_RCONV96=0: gather-GEMM)
-  const bool use_rconv96 = opt(OPT_RCONV96) != 0;
-  if (use_rconv96 && !c->low_latency && L.d_w96 && !src1 && C0 == d.cin && Hin >= 12 && Win >= 12 &&
-      (long long)B * Ho * Wo * 96 < (1ll << 31) && (long long)B * Hin * Win * C0 * 2 < (1ll << 31)) {
+  // bf16, the 96-row layers (3x3 48/24 -> 96 at stride 1, 24 -> 96 at stride 2, gen_deconv 96 -> 96): se_rconv96.hip
+  int launch_form_rconv96(const Choice&) const {
     RConv96Params rp;
     memset(&rp, 0, sizeof rp);
     rp.src = src0; rp.wpk = L.d_w96; rp.bias = L.d_b; rp.dst = dst;
@@ -476,161 +399,80 @@ int run_gconv16(se_ctx* c, const Layer& L, const float* src0, int C0, const floa
     rp.ty = ((d.stride == 2 ? Ho : Hin) + 15) / 16; rp.tx = ((d.stride == 2 ? Wo : Win) + 15) / 16;
     rp.up2 = d.up ? 1 : 0; rp.act = d.act; rp.xcd = xcd_remap_enabled();
     const int T = d.up ? 4 : 9, nstep = (T * rp.CG + 3) / 4;
-    const double alg = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;
-    set_launch_cost(alg, 2.0 * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * 48), d.name,
+    set_launch_cost(alg(9), 2.0 * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * 48), d.name,
                     2.0 * (double)B * (d.stride == 2 ? (double)Ho * Wo : (double)Hin * Win) * (d.up ? 4.0 : 1.0) * 96.0 * (nstep * 32.0));
     HIPCHK(c, launch_rconv96(rp, c->st));
     return 0;
   }
-  {
-    bool done = false;
-    if (try_rtile(c, L, true, src0, C0, src1, dst, B, Hin, Win, Ho, Wo, pad, &done)) return 1;
-    if (done) return 0;
-  }
-  return run_gather(c, L, true, src0, C0, src1, C1, src1_vec, dst, B, Hin, Win, Ho, Wo, pad);
-}
 
-// ---- launching one gated conv -----------------------------------------------------------------------
-// parameters of a Winograd launch on tiles of 2 rows x `tcols` columns of an h x w source at dilation d (no second source,
-// no folded bias: the caller sets those)
-static WinoParams wino_params(const float* src, const float* upk, const float* bias, float* dst, int B, int h, int w, int d,
-                              int tcols, int act) {
-  WinoParams wp;
-  memset(&wp, 0, sizeof wp);
-  wp.src = src; wp.upk = upk; wp.bias = bias; wp.dst = dst;
-  wp.B = B; wp.h = h; wp.w = w; wp.d = d; wp.th = h / 2; wp.tw = w / tcols;
-  wp.total_tiles = B * wp.th * wp.tw; wp.act = act;
-  wp.xcd = xcd_remap_enabled();
-  udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
-  udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
-  udiv_magic_host((unsigned)wp.d, &wp.div_d_m, &wp.div_d_l);
-  return wp;
-}
+  // the direct gather-GEMM (se_gconv.hip) on the image of one precision: the fallback of every gated conv
+  int launch_form_gather(const Choice&) const {
+    const int es = bf ? 2 : 4, gran = bf ? 8 : 4, CG = f.CG[bf], nch = f.nch[bf], KW = d.up ? 2 : d.k;
+    GConvParams p;
+    memset(&p, 0, sizeof p);
+    p.bf16 = bf ? 1 : 0;
+    p.src0 = src0; p.src1 = src1 ? src1 : src0; p.wpk = L.direct[bf]; p.bias = L.d_b; p.dst = dst; p.zeros = c->zeros;
+    p.B = B; p.Hin = Hin; p.Win = Win; p.Ho = d.up ? Hin : Ho; p.Wo = d.up ? Win : Wo;   // up2: rows walk the source grid
+    p.up2 = d.up ? 1 : 0; p.OH = Ho; p.OW = Wo;
+    p.C0 = C0; p.C1 = C1 ? C1 : C0; p.C0g = C0 / gran; p.CG = CG;
+    p.T = f.T; p.KW = KW; p.stride = d.stride; p.dil = d.rate; p.pad = pad;
+    p.magicCG = (65536 + CG - 1) / CG; p.magicKW = 256 / KW + 1; p.magicKH = f.T / KW;
+    if (!magic_cg_ok(CG, nch)) return fail(c, "layer %s: magic division check failed", d.name);
+    if (!magic_kw_ok(KW, f.T)) return fail(c, "layer %s: magic tap division check failed", d.name);
+    const int Gs = bf ? (f.G + 7) & ~7 : f.G;      // stored channel stride of the output
+    // 32-bit byte offsets (sentinel 0x80000000): source and destination below 2^31 BYTES
+    if ((double)B * Hin * Win * (C0 > C1 ? C0 : C1) * es >= 2147483648.0 || (double)B * Ho * Wo * Gs * es >= 2147483648.0)
+      return fail(c, "layer %s: a tensor of this launch exceeds 2^31 bytes (32-bit byte offsets) -- split the batch", d.name);
+    for (int j = 0; j < p.magicKH; ++j) p.rep |= 1u << (j * KW);
+    udiv_magic_host((unsigned)(p.Ho * p.Wo), &p.div_hw_m, &p.div_hw_l);
+    udiv_magic_host((unsigned)p.Wo, &p.div_w_m, &p.div_w_l);
+    p.Hlim = Hin; p.Wlim = Win;
+    p.src1_vec = src1_vec; p.nch = nch; p.G = Gs; p.act = d.act; p.total_pix = B * p.Ho * p.Wo;
+    p.xcd = xcd_remap_enabled();
+    p.np_full = f.NP; p.nf_full = f.NP / 32; p.small_grid = c->low_latency ? 1 : 0;
+    // cost: algorithmic as the reference defines the layer (3x3 on the upsampled grid for gen_deconv); executed: the packed K
+    // (channels padded to granules, taps x channels padded to whole chunks) and row (NP) sizes the MFMAs really run over; the
+    // sub-pixel form of gen_deconv runs 4 classes x 4 taps instead of 9 taps on the upsampled grid
+    set_launch_cost(alg(d.k * d.k), (double)es * ((double)B * Hin * Win * d.cin + (double)B * Ho * Wo * (d.cout / 2)), d.name,
+                    2.0 * (double)B * p.Ho * p.Wo * (d.up ? 4.0 : 1.0) * f.NP * (nch * (bf ? 64.0 : 32.0)));
+    HIPCHK(c, launch_gconv(f.cfg, p, c->st));
+    return 0;
+  }
+};
 
 int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float* src1, int C1, int src1_vec, float* dst,
               int B, int Hin, int Win) {
   const LayerDef& d = L.def;
+  const LayerFacts& f = L.facts;
   const ConvShape sh = conv_shape(d, Hin, Win);
-  const int Ho = sh.Ho, Wo = sh.Wo, pad = sh.pad;
+  const bool bf = c->bf16;
   if (!L.packed) return fail(c, "layer %s: weights not loaded", d.name);
-  if (c->bf16) return run_gconv16(c, L, src0, C0, src1, C1, src1_vec, dst, B, Hin, Win, Ho, Wo, pad);
-  if ((C0 + C1) != L.direct[0].CG * 4) return fail(c, "layer %s: source channels %d+%d != packed %d", d.name, C0, C1, L.direct[0].CG * 4);
-  // Low-latency mode (SE_FLAG_LOW_LATENCY, one or two images): the Winograd kernels' 64/128-tile workgroups would
-  // occupy 16-32 of the 256 CUs, so every gated conv takes the direct kernel in its small-grid shape instead
-  // (launch_gconv: 64-pixel tiles, rows split over blockIdx.y).  2.25x more multiply-adds on ~10x more CUs.
-  // ... unless the layer's Winograd grid still covers enough of the chip (round 6; 0: never).  Measured (tools/ll_wino_sweep.sh):
-  // the 96 -> 192 kernels pay from 64 workgroups on (a third of the multiply-adds outweighs a quarter of the CUs: one 512x512
-  // image 3.22 -> 2.83 ms), the 96- and 48-row kernels only from 128 on (at 64 workgroups they cost one 256x256 image
-  // 1.20 -> 1.31 ms) -- SE_LL_WINO_MIN_WG / SE_LL_WINO48_MIN_WG.  The grid is counted PER IMAGE (the call's batch size does not
-  // enter): which kernel a layer runs must depend on the image size and the mode only, so that an image's result stays
-  // bit-identical across batch sizes, batch positions and ranks within the mode.
-  const int ll_min_wg = opt(OPT_LL_WINO_MIN_WG), ll_min_wg48 = opt(OPT_LL_WINO48_MIN_WG);
-  auto wino_grid_ok = [&](long wgs, bool n192 = false) {
-    const int m = n192 ? ll_min_wg : ll_min_wg48;
-    return !c->low_latency || (m > 0 && wgs >= m);
-  };
-  const bool use_wino = opt(OPT_WINOGRAD) != 0;
-  const bool wino_src_ok = (!src1 && C0 == 96 && d.cin == 96) || (src1 && C0 == 96 && C1 == 96 && d.cin == 192);
-  // the kernel addresses a source through 32-bit byte offsets (96 floats per pixel)
-  const bool wino_addr_ok = (long long)B * Hin * Win * 384 < (1ll << 31);
-  const double alg3x3 = 2.0 * (double)B * Ho * Wo * d.cout * d.cin * 9;     // the Winograd layers' cost as the reference defines it
-  if (use_wino && !d.up && L.d_u && wino_src_ok && !wino_addr_ok) {
-    static bool said = false;
-    if (!said) {
-      said = true;
-      fprintf(stderr, "sketchedit_hip: layer %s: %d x %dx%d x 96 floats exceed the Winograd kernel's 32-bit byte offsets; "
-                      "using the direct kernel (about 2x slower) -- split the batch\n", d.name, B, Hin, Win);
-    }
+  if (bf && !L.direct[1]) return fail(c, "layer %s: no bf16 weight image", d.name);
+  if (bf && (C0 + C1) != f.CG[1] * 8) return fail(c, "layer %s: bf16 source channels %d+%d != packed %d", d.name, C0, C1, f.CG[1] * 8);
+  if (!bf && (C0 + C1) != f.CG[0] * 4) return fail(c, "layer %s: source channels %d+%d != packed %d", d.name, C0, C1, f.CG[0] * 4);
+  const ConvCall q = {d, f, B, Hin, Win, C0, C1, src1 ? (src1_vec ? SRC2_VECTOR : SRC2_TENSOR) : SRC2_NONE, bf, c->low_latency,
+                      c->conservative, c->cur_net, c->vbias_ws && (!bf || c->vec32)};
+  const Choice ch = choose_form(q);
+  static bool said = false;
+  if (ch.wino_range && !said) {
+    said = true;
+    fprintf(stderr, "sketchedit_hip: layer %s: %d x %dx%d x 96 floats exceed the Winograd kernel's 32-bit byte offsets; "
+                    "using the direct kernel (about 2x slower) -- split the batch\n", d.name, B, Hin, Win);
   }
-  if (use_wino && !d.up && L.d_u && wino_src_ok && wino_addr_ok && (Hin % (2 * d.rate)) == 0 && (Win % (2 * d.rate)) == 0 &&
-      wino_grid_ok(((long)(Hin / 2) * (Win / 2) + 63) / 64, true)) {
-    // A spatially constant second source is folded into a per-image, per-border-configuration bias (launch_vecbias) and
-    // the layer runs as the SINGLE-source kernel: half the positions' K, 311 -> 170 us at 256x256 B=32 (SE_VECBIAS=0: the
-    // two-source kernel reads the vector as a second input)
-    const bool folded = opt(OPT_VECBIAS) != 0 && src1 && src1_vec && d.rate == 1 && L.d_u1 && L.d_wv && c->vbias_ws && Hin >= 2 && Win >= 2;
-    if (folded) HIPCHK(c, launch_vecbias(L.d_wv, src1, c->vbias_ws, B, 96, c->st));
-    const float* s1 = folded ? nullptr : src1;
-    // Hybrid F(2,3) x F(4,3) (se_wino24.hip) for the single-source form where the width allows 4-column tiles: 24 instead of
-    // 32 positions per 8 outputs.  SE_WINOGRAD_F43=0: F(2x2,3x3) everywhere; 1 (default): the hybrid kernel everywhere; 2: netG
-    // only (netM's soft mask feeds the 0.5 threshold, editline2_model.py:346-347).  Measured in round 5 over 72 images / 4.7 M
-    // mask pixels of the three weight sets (tools/f43_flips.py, DESIGN.md 3.1b'): hard-mask flips against the oracle 1 (mode 0),
-    // 4 (mode 1), 1 (mode 2) -- under one pixel per ten images either way -- for 11.10 / 11.29 ms per step (modes 1 / 2): by the
-    // rule VERDICT r4 set (switch only if it costs < 1 %) the default stays 1.  (A mode that kept F(2x2,3x3) for netM's mask
-    // decoder alone was measured too: 4 flips, no better than mode 1 -- the error comes from the encoder; removed.)
-    const int f43_mode = opt(OPT_WINOGRAD_F43);
-    // SE_FLAG_CONSERVATIVE is mode 2 for this call, chosen by the caller through the ABI instead of the process-wide table
-    const bool f43_net_ok = c->cur_net == SE_NET_G || (f43_mode == 1 && !c->conservative);
-    const bool f43 = (f43_mode == 1 || f43_mode == 2) && f43_net_ok && (s1 ? (!src1_vec && L.d_u24b) : L.d_u24 != nullptr) && L.d_ub24 && (Win % (4 * d.rate)) == 0;
-    WinoParams wp = f43 ? wino_params(src0, s1 ? L.d_u24b : L.d_u24, L.d_ub24, dst, B, Hin, Win, d.rate, 4, d.act)
-                        : wino_params(src0, folded ? L.d_u1 : L.d_u, L.d_b, dst, B, Hin, Win, d.rate, 2, d.act);
-    wp.src1 = s1; wp.src1_vec = folded ? 0 : src1_vec; wp.vbias = folded ? c->vbias_ws : nullptr;
-    if ((double)B * Hin * Win * 384.0 >= 2147483648.0) return fail(c, "layer %s: tensor exceeds 2^31 bytes", d.name);
-    if (f43) {
-      // 24 of 72 products per 2x4 outputs; with the vector source folded away only the first source's half of K is executed
-      set_launch_cost(alg3x3, 4.0 * 2.0 * (double)B * Hin * Win * 96, d.name, alg3x3 * 24.0 / 72.0 * (folded ? 0.5 : 1.0));
-      HIPCHK(c, launch_wino24(wp, c->st));
-      return 0;
-    }
-    // F(2x2,3x3): 16 of 36 products; with the vector source folded away only the first source's half of K is executed
-    set_launch_cost(alg3x3, 4.0 * 2.0 * (double)B * Hin * Win * 96, d.name, alg3x3 * 16.0 / 36.0 * (folded ? 0.5 : 1.0));
-    HIPCHK(c, launch_wino(wp, c->st));
-    return 0;
+  const ConvLaunch a = {c, L, d, f, src0, C0, src1, C1, src1_vec, dst, B, Hin, Win, sh.Ho, sh.Wo, sh.pad, bf};
+  switch (ch.form) {
+    case F_WINO: case F_WINO24: case F_WINO24_C48: return a.launch_form_wino(ch);
+    case F_WINO48: case F_WINO48_C24: return a.launch_form_wino48(ch);
+    case F_WINOUP: case F_WINOUP48: return a.launch_form_winoup(ch);
+    case F_RTILEW: case F_RTILEW2: return a.launch_form_rtilew(ch);
+    case F_RTILE_DENSE5: case F_RTILE_DENSE5W: return a.launch_form_rtile_dense5(ch);
+    case F_RTILE: case F_RTILE_D4: return a.launch_form_rtile(ch);
+    case F_RCONV16: case F_RCONV16_DUAL: return a.launch_form_rconv16(ch);
+    case F_RCONV96: return a.launch_form_rconv96(ch);
+    case F_GATHER: return a.launch_form_gather(ch);
+    case F_SMALL_CONV: break;      // (a raw layer has no gated image: refused above)
   }
-  // 48 -> 192 (xconv5 of netG) on the hybrid kernel's 48-channel instantiation: 2 chunks per position, the second half empty
-  {
-    if (use_wino && opt(OPT_WINOGRAD_F43) != 0 && !d.up && !src1 && C0 == 48 && d.cin == 48 && d.cout == 192 && d.stride == 1 && L.d_u24 && L.d_ub24 &&
-        (long long)B * Hin * Win * 384 < (1ll << 31) && (Hin % (2 * d.rate)) == 0 && (Win % (4 * d.rate)) == 0 &&
-        wino_grid_ok(((long)(Hin / 2) * (Win / 4) + 31) / 32, true)) {
-      const WinoParams wp = wino_params(src0, L.d_u24, L.d_ub24, dst, B, Hin, Win, d.rate, 4, d.act);
-      set_launch_cost(alg3x3, 4.0 * ((double)B * Hin * Win * 48 + (double)B * Hin * Win * 96), d.name, alg3x3 * 24.0 / 72.0);
-      HIPCHK(c, launch_wino24_c48(wp, c->st));
-      return 0;
-    }
-  }
-  const bool use_wino48 = opt(OPT_WINOGRAD48) != 0;
-  if (use_wino && use_wino48 && !d.up && L.d_u && L.d_ub && !src1 && C0 == 48 && d.cin == 48 && (long long)B * Hin * Win * 192 < (1ll << 31) &&
-      (Hin % (2 * d.rate)) == 0 && (Win % (2 * d.rate)) == 0 && wino_grid_ok(((long)(Hin / 2) * (Win / 2) + 63) / 64)) {
-    const WinoParams wp = wino_params(src0, L.d_u, L.d_ub, dst, B, Hin, Win, d.rate, 2, d.act);
-    set_launch_cost(alg3x3, 4.0 * 2.0 * (double)B * Hin * Win * 48, d.name, alg3x3 * 16.0 / 36.0);
-    HIPCHK(c, launch_wino48(wp, c->st));
-    return 0;
-  }
-  // 24 -> 96 (xconv3 / pmconv3 of netG) on the same kernel, one chunk per position (se_wino48.hip CIN = 24): 16 of 36 products
-  if (use_wino && use_wino48 && !d.up && L.d_u && L.d_ub && !src1 && C0 == 24 && d.cin == 24 && d.cout == 96 && d.stride == 1 &&
-      (long long)B * Hin * Win * 192 < (1ll << 31) && (Hin % (2 * d.rate)) == 0 && (Win % (2 * d.rate)) == 0 &&
-      wino_grid_ok(((long)(Hin / 2) * (Win / 2) + 63) / 64)) {
-    const WinoParams wp = wino_params(src0, L.d_u, L.d_ub, dst, B, Hin, Win, d.rate, 2, d.act);
-    set_launch_cost(alg3x3, 4.0 * ((double)B * Hin * Win * 24 + (double)B * Hin * Win * 48), d.name, alg3x3 * 16.0 / 36.0);
-    HIPCHK(c, launch_wino48_c24(wp, c->st));
-    return 0;
-  }
-  const bool use_winoup = opt(OPT_WINOGRAD_UP) != 0;
-  if (use_wino && use_winoup && d.up && L.d_u && L.d_ub && !src1 && C0 == 96 && d.cin == 96 &&
-      (long long)B * Hin * Win * 384 < (1ll << 31) && (Hin % 2) == 0 && (Win % 2) == 0 &&
-      wino_grid_ok(4 * (((long)(Hin / 2) * (Win / 2) + 63) / 64))) {
-    const WinoParams wp = wino_params(src0, L.d_u, L.d_ub, dst, B, Hin, Win, 1, 2, d.act);
-    set_launch_cost(alg3x3, 4.0 * ((double)B * Hin * Win * 96 + (double)B * Ho * Wo * 48), d.name,
-                    alg3x3 * 9.0 / 36.0);                       // F(2x2,2x2) on the sub-pixel classes: 9 of 36 products
-    HIPCHK(c, launch_winoup(wp, c->st));
-    return 0;
-  }
-  // gen_deconv 48 -> 48: F(2x2,2x2) on the sub-pixel classes with the K pairing of the 48-channel kernels (se_wino_up48.hip)
-  const bool use_winoup48 = opt(OPT_WINOGRAD_UP48) != 0;
-  if (use_wino && use_winoup && use_winoup48 && d.up && L.d_u && L.d_ub && !src1 && C0 == 48 && d.cin == 48 && d.cout == 48 &&
-      (long long)B * Hin * Win * 192 < (1ll << 31) && (long long)B * Ho * Wo * 96 < (1ll << 31) && (Hin % 2) == 0 && (Win % 2) == 0 &&
-      wino_grid_ok(4 * (((long)(Hin / 2) * (Win / 2) + 63) / 64))) {
-    const WinoParams wp = wino_params(src0, L.d_u, L.d_ub, dst, B, Hin, Win, 1, 2, d.act);
-    set_launch_cost(alg3x3, 4.0 * ((double)B * Hin * Win * 48 + (double)B * Ho * Wo * 24), d.name,
-                    alg3x3 * 9.0 / 36.0 * 28.0 / 27.0);         // 9 of 36 products, 28 k-halves executed for 27 of work
-    HIPCHK(c, launch_winoup48(wp, c->st));
-    return 0;
-  }
-  {
-    bool done = false;
-    if (try_rtile(c, L, false, src0, C0, src1, dst, B, Hin, Win, Ho, Wo, pad, &done)) return 1;
-    if (done) return 0;
-  }
-  return run_gather(c, L, false, src0, C0, src1, C1, src1_vec, dst, B, Hin, Win, Ho, Wo, pad);
+  return fail(c, "layer %s: not a gated conv", d.name);
 }
 
 struct Act {   // an NHWC activation living in the arena
@@ -761,7 +603,7 @@ int small(Plan& P, const char* name, Act& in, int mode, float* out_nchw, float* 
     if (!L.packed) return P.rc = fail(c, "layer %s: weights not loaded", name);
     SmallConvParams sp;
     memset(&sp, 0, sizeof sp);
-    sp.x = in.p; sp.w = L.direct[c->bf16].w; sp.b = L.d_b; sp.B = P.B; sp.H = in.H; sp.W = in.W; sp.cout = L.def.cout;
+    sp.x = in.p; sp.w = L.direct[c->bf16]; sp.b = L.d_b; sp.B = P.B; sp.H = in.H; sp.W = in.W; sp.cout = L.def.cout;
     sp.bf16 = c->bf16 ? 1 : 0;
     sp.mode = mode; sp.out_nchw = out_nchw; sp.hard = hard; sp.img = img; sp.mask = mask; sp.xnow = xnow;
     sp.composed = composed; sp.no_mask_coarse = no_mask_coarse;
@@ -3004,6 +2846,33 @@ int se_debug_set_option(const char* name, int value) { return opt_set(name, valu
 int se_debug_get_option(const char* name, int* value) { return opt_get(name, value); }
 void se_debug_reset_options(void) { opt_reset(); }
 
+// the ConvCall of se_gated_conv2d_ex for these arguments, chosen and named (no ctx, no device)
+int se_debug_gconv_form(int cin, int cin1, int src1_is_vector, int cout, int k, int stride, int rate, int act, int upsample,
+                        int B, int H, int W, int exec_flags, int net_id, char* out, size_t cap) {
+  if (!out || cin <= 0 || cin1 < 0 || cout <= 0 || k <= 0 || stride <= 0 || rate <= 0 || B <= 0 || H <= 0 || W <= 0) return 1;
+  const bool bf = (exec_flags & SE_FLAG_BF16) != 0;
+  const int gran = bf ? 8 : 4;
+  if (cin1 && ((cin % gran) || (cin1 % gran))) return 1;
+  const LayerDef d = {"test", cin + cin1, cout, k, stride, rate, act, upsample};
+  const bool raw = small_layer(d);
+  if (raw && (k != 3 || cin != 12 || cin1 || (cout != 1 && cout != 3) || stride != 1 || rate != 1 || upsample)) return 1;
+  if (!raw && (cout % 8)) return 1;
+  const LayerFacts f = layer_facts(d, cin + cin1);       // chans: the identity
+  if (!raw && f.cfg < 0) return 1;
+  const int Cp = (cin + gran - 1) & ~(gran - 1);
+  if (!raw && Cp + cin1 != f.CG[bf] * gran) return 1;
+  const bool vec = cin1 && src1_is_vector;               // ... for which the entry point brings the fold scratch
+  const ConvCall q = {d, f, B, H, W, Cp, cin1, cin1 ? (vec ? SRC2_VECTOR : SRC2_TENSOR) : SRC2_NONE, bf,
+                      (exec_flags & SE_FLAG_LOW_LATENCY) != 0, (exec_flags & SE_FLAG_CONSERVATIVE) != 0, net_id, vec};
+  const Choice ch = choose_form(q);
+  const char* name = form_name(ch, q);
+  if (!name) return 1;
+  const std::string s = std::string(ch.fold ? "vecbias," : "") + name;
+  if (s.size() + 1 > cap) return 1;
+  memcpy(out, s.c_str(), s.size() + 1);
+  return 0;
+}
+
 // ---- unit-test entry points (allocate scratch internally; synchronise the stream before freeing) ----
 int se_gated_conv2d_ex(se_ctx* c, void* stream, const float* x, const float* x1, int x1_is_vector, const float* w_host,
                        const float* b_host, float* y, int B, int Cin, int Cin1, int H, int W, int Cout, int k, int stride,
@@ -3053,7 +2922,7 @@ int se_gated_conv2d_ex(se_ctx* c, void* stream, const float* x, const float* x1,
   if (!rc && raw) {
     SmallConvParams sp;
     memset(&sp, 0, sizeof sp);
-    sp.x = xin; sp.w = L.direct[bf].w; sp.b = L.d_b; sp.B = B; sp.H = H; sp.W = W; sp.cout = Cout; sp.mode = 4;
+    sp.x = xin; sp.w = L.direct[bf]; sp.b = L.d_b; sp.B = B; sp.H = H; sp.W = W; sp.cout = Cout; sp.mode = 4;
     sp.bf16 = bf ? 1 : 0;
     sp.out_nchw = y;
     rc = launch_small_conv(sp, c->st) != hipSuccess;
@@ -3203,7 +3072,7 @@ int se_output_conv(se_ctx* c, void* stream, const float* x, const float* w_host,
   HIPCHK(c, (bf ? launch_nchw_to_nhwc16 : launch_nchw_to_nhwc)(x, xin, B, 12, Cp, H, W, c->st));
   SmallConvParams sp;      // filled as small() fills it
   memset(&sp, 0, sizeof sp);
-  sp.x = xin; sp.w = L.direct[bf].w; sp.b = L.d_b; sp.B = B; sp.H = H; sp.W = W; sp.cout = cout;
+  sp.x = xin; sp.w = L.direct[bf]; sp.b = L.d_b; sp.B = B; sp.H = H; sp.W = W; sp.cout = cout;
   sp.bf16 = bf ? 1 : 0;
   sp.mode = mode; sp.out_nchw = io->out; sp.hard = io->hard; sp.img = io->img; sp.mask = io->mask; sp.xnow = (float*)io->xnow;
   sp.composed = io->composed; sp.no_mask_coarse = no_mask_coarse ? 1 : 0;

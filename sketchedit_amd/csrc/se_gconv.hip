@@ -14,6 +14,7 @@
 //   gen_deconv  models/networks/utils.py:35-51     nearest x2 (src = dst>>1) then 3x3 conv
 //   concat      models/networks/editline_g.py:166-167,211 (second source = other tensor / pooled vector)
 #include "se_device.h"
+#include "se_dispatch.h"
 
 #include <cstdlib>
 
@@ -320,15 +321,9 @@ static hipError_t launch_gconv_t(const GConvParams& p, hipStream_t st, int label
 // and is slower: 66 KiB of LDS leave two instead of three workgroups per CU, N48 2.91 -> 3.38 ms.)
 // Tile shapes (chosen by sweeps).  Shapes with LDS <= 80 KiB and <= 256 registers run two workgroups
 // per CU, so the staging code, LDS-read latency and epilogue of one overlap the MFMAs of the other.
-// the form name of a launch (Profiler::Rec::form): gconv_n<rows>[_small][_up2][_2src][_bf16]
+// the form name of a launch (Profiler::Rec::form): the one choose_form's form_name predicts (se_dispatch.h)
 static const char* gconv_form(int cfg, const GConvParams& p) {
-#define SE_GF(n) n, n "_bf16", n "_2src", n "_2src_bf16", n "_up2", n "_up2_bf16", n "_up2_2src", n "_up2_2src_bf16"
-#define SE_GS(n) { SE_GF(n), SE_GF(n "_small") }
-  static const char* const names[4][16] = {SE_GS("gconv_n192"), SE_GS("gconv_n96"), SE_GS("gconv_n48"), SE_GS("gconv_n24")};
-#undef SE_GS
-#undef SE_GF
-  if (cfg < 0 || cfg > 3) return nullptr;
-  return names[cfg][(p.small_grid ? 8 : 0) | (p.up2 ? 4 : 0) | (p.C0g != p.CG ? 2 : 0) | (p.bf16 ? 1 : 0)];
+  return gconv_form_name(cfg, p.small_grid != 0, p.up2 != 0, p.C0g != p.CG, p.bf16 != 0);
 }
 
 hipError_t launch_gconv(int cfg, const GConvParams& p, hipStream_t st) {

@@ -216,7 +216,7 @@ hipError_t launch_rconv96(const RConv96Params& p, hipStream_t st);
 // ---------------------------------------------------------------------------------------------
 struct RTileParams {
   const float* src;    // NHWC [B][Hin][Win][C] (fp32, or bf16 when `bf16`)
-  const float* wpk;    // packed weight image of pack_layer / pack_layer16 ([class][chunk][NP rows][128 bytes])
+  const float* wpk;    // packed weight image of pack_direct ([class][chunk][NP rows][128 bytes])
   const float* bias;   // [NP] packed-row order
   float* dst;          // NHWC [B][OH][OW][G]
   int B, Hin, Win;     // source grid (= output grid; for up2 the output grid is 2x)

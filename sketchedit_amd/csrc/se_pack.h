@@ -1,32 +1,16 @@
-// Internal (host-only) interface of the weight packer (se_pack.hip): the layer definitions, the device images a layer
-// holds and the one function that decides and builds them.  The dispatch in se_api.hip reads these images.
+// Internal (host-only) interface of the weight packer (se_pack.hip): the device images a layer holds and the function that
+// builds them.  WHICH images a layer gets is layer_facts (se_dispatch.h), the same facts choose_form reads: pack_layer_images
+// builds exactly those and checks that it did.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "se_dispatch.h"
 
 #include <cstddef>
 #include <string>
 #include <vector>
 
 namespace se {
-
-enum { ACT_ELU = 0, ACT_RELU = 1, ACT_NONE = 2 };
-
-struct LayerDef {
-  const char* name;
-  int cin, cout, k, stride, rate, act, up;
-};
-
-// raw (ungated) 3x3 conv 12 -> {1, 3}: the last layer of a decoder (utils.py:27)
-inline bool small_layer(const LayerDef& d) { return d.act == ACT_NONE || d.cout == 3; }
-
-// output size and padding of a gated conv on an Hin x Win source (utils.py:20); gen_deconv doubles the grid
-struct ConvShape { int Ho, Wo, pad; };
-inline ConvShape conv_shape(const LayerDef& d, int Hin, int Win) {
-  const int pad = d.rate * (d.k - 1) / 2;
-  if (d.up) return {2 * Hin, 2 * Win, pad};
-  const int span = d.rate * (d.k - 1) + 1;
-  return {(Hin + 2 * pad - span) / d.stride + 1, (Win + 2 * pad - span) / d.stride + 1, pad};
-}
 
 // sole owner of one device allocation (move-only): freed when reallocated, reset or destroyed; reads as the raw pointer
 class DevBuf {
@@ -51,20 +35,14 @@ class DevBuf {
   float* p_ = nullptr;
 };
 
-// the image of the direct kernels (gather-GEMM, raw tile) in one precision: `nch` chunks of 128-byte rows and CG granules
-// per tap (4 fp32 or 8 bf16 channels each); for a raw layer the [cout][9][12] fp32 weights
-struct DirectImage {
-  DevBuf w;
-  int nch = 0, CG = 0;
-};
-
 struct Layer {
   LayerDef def;
   std::vector<float> w, b;    // host copies in checkpoint layout
   bool have_w = false, have_b = false, packed = false;
-  int cfg = -1, NP = 0, G = 0, T = 0;
-  DirectImage direct[2];      // [0] fp32, [1] bf16: same row order and slot swizzle, 64 bf16 k-values per 128-byte row
-                              //   (raw layers: the bf16-rounded weights, kept as fp32)
+  LayerFacts facts = {};      // layer_facts(def, stored channels): the packing numbers and which images below exist
+  DevBuf direct[2];           // the image of the direct kernels (gather-GEMM, raw tile), [0] fp32, [1] bf16: facts.nch chunks of
+                              //   128-byte rows (32 fp32 or 64 bf16 k-values), same row order and slot swizzle; for a raw layer
+                              //   the [cout][9][12] fp32 weights ([1]: rounded to bf16, kept as fp32)
   DevBuf d_b;       // bias in the row order of the direct image (raw layers: as in the checkpoint)
   DevBuf d_u;       // Winograd-transformed weights (eligible layers only)
   DevBuf d_ub;      // bias in the row order of the 48 -> 96 Winograd kernel (MIXED tiles)
@@ -81,12 +59,12 @@ struct Layer {
   DevBuf d_wx2;     //   and of its two-dimensional F(2x2,3x3) form
   DevBuf d_wd;      // 5x5 layers with padding channels in their stored input (fp32): dense-K image (se_rtile.hip)
   DevBuf d_wdw;     //   and the image of its F(2,5)-along-x form (rtile_dense5w_kernel)
-  int dense = 0, nchd = 0;    //   real channels per pixel (3 or 5), 32-k chunks of the dense image
 };
 
-// Builds every device image of a layer, in both precisions, from its host weights: the one rule for which kernel forms a
-// layer can run.  `chans` lists the checkpoint input channels its stored input carries, in stored order -- the identity
-// for every layer but the 4-channel form of wconv1.  Returns 1 with the reason in `err`.
+// Builds every device image of a layer, in both precisions, from its host weights: those layer_facts names, no other (checked
+// before it returns) -- the one rule for which kernel forms a layer can run.  `chans` lists the checkpoint input channels its
+// stored input carries, in stored order -- the identity for every layer but the 4-channel form of wconv1.  Returns 1 with the
+// reason in `err`.
 int pack_layer_images(Layer& L, const std::vector<int>& chans, std::string& err);
 
 }  // namespace se

@@ -1,6 +1,6 @@
 // Weight packing (host only): a layer's checkpoint weights (OIHW) transformed, reordered and swizzled into the exact LDS
-// image of every kernel form that may run it, and uploaded once at load.  pack_layer_images is the one rule for which
-// images a layer gets; the dispatch in se_api.hip runs a form only where its image exists.
+// image of every kernel form that may run it, and uploaded once at load.  Which images a layer gets, and their numbers, is
+// layer_facts (se_dispatch.h): pack_layer_images builds those, and choose_form picks a form only where the facts name its image.
 #include "se_pack.h"
 #include "se_kernels.h"
 
@@ -33,14 +33,6 @@ float bf16_round(float f) {
   float r;
   memcpy(&r, &u, 4);
   return r;
-}
-
-int choose_cfg(int G) {
-  if (G <= 16) return GC_N24;
-  if (G <= 24) return GC_N48;
-  if (G <= 48) return GC_N96;
-  if (G <= 96) return GC_N192;
-  return -1;
 }
 
 // MIXED row order: tile t = features 8t..8t+7, then their gates.  Checkpoint output channel of row n, or -1 past G
@@ -122,19 +114,18 @@ template <> unsigned short to_elem<unsigned short>(float v) { return bf16_bits(v
 // number of slots per tap), or -1 for zero padding.  gen_deconv is packed in its sub-pixel form, the sums formed in fp32 and
 // rounded once.
 template <class E>
-int pack_direct(Layer& L, const std::vector<int>& cin_map, DirectImage& di, std::string& err) {
-  constexpr int KC = 128 / sizeof(E), PER = 16 / sizeof(E);
+int pack_direct(Layer& L, const std::vector<int>& cin_map, std::string& err) {
+  constexpr int KC = 128 / sizeof(E), PER = 16 / sizeof(E), BF = sizeof(E) == 2;
   const LayerDef& d = L.def;
-  const int G = d.cout / 2;
-  const int cfg = choose_cfg(G);
-  if (cfg < 0 || (G % 4)) {
-    err = std::string("layer ") + d.name + ": unsupported gated width " + std::to_string(G);
+  const LayerFacts& f = L.facts;
+  if (f.cfg < 0) {
+    err = std::string("layer ") + d.name + ": unsupported gated width " + std::to_string(f.G);
     return 1;
   }
-  const int NP = gconv_np(cfg);
+  const int cfg = f.cfg, G = f.G, NP = f.NP, nch = f.nch[BF];
   const int Cp = (int)cin_map.size();
   const bool up2 = d.up != 0;
-  const int KW = up2 ? 2 : d.k, T = KW * KW, K = T * Cp, nch = (K + KC - 1) / KC, ncls = up2 ? 4 : 1;
+  const int KW = up2 ? 2 : d.k, K = f.T * Cp, ncls = up2 ? 4 : 1;
   std::vector<E> img((size_t)ncls * nch * NP * KC, E(0));
   for (int cls = 0; cls < ncls; ++cls)
     for (int n = 0; n < NP; ++n) {
@@ -149,10 +140,7 @@ int pack_direct(Layer& L, const std::vector<int>& cin_map, DirectImage& di, std:
         img[(((size_t)cls * nch + kf / KC) * NP + n) * KC + swz(n, kin / PER, kin % PER, PER)] = to_elem<E>(v);
       }
     }
-  if (upload(di.w, img, err)) return 1;
-  di.nch = nch; di.CG = Cp / PER;
-  L.cfg = cfg; L.NP = NP; L.G = G; L.T = T;
-  return 0;
+  return upload(L.direct[BF], img, err);
 }
 
 int pack_wino(Layer& L, std::string& err);
@@ -163,35 +151,25 @@ int pack_wino48_c24(Layer& L, std::string& err);
 int pack_winoup(Layer& L, std::string& err);
 int pack_winoup48(Layer& L, std::string& err);
 
-// fp32 direct image (cin_map: a multiple of 4 channels per tap) and its bias, then the Winograd-type image of the 3x3
-// stride-1 layers whose packed channels are exactly the layer's
+// fp32 direct image (cin_map: a multiple of 4 channels per tap) and its bias, then the Winograd-type image the facts name,
+// in the layout of the kernel that runs a layer of this width
 int pack_layer(Layer& L, const std::vector<int>& cin_map, std::string& err) {
-  if (pack_direct<float>(L, cin_map, L.direct[0], err)) return 1;
-  std::vector<float> bias(L.NP, 0.f);
-  for (int n = 0; n < L.NP; ++n) {
-    const int oc = out_channel_of_row(L.cfg, n, L.G);
+  const LayerDef& d = L.def;
+  const LayerFacts& f = L.facts;
+  if (pack_direct<float>(L, cin_map, err)) return 1;
+  std::vector<float> bias(f.NP, 0.f);
+  for (int n = 0; n < f.NP; ++n) {
+    const int oc = out_channel_of_row(f.cfg, n, f.G);
     if (oc >= 0) bias[n] = L.b[oc];
   }
   if (upload(L.d_b, bias, err)) return 1;
   L.packed = true;
-  const LayerDef& d = L.def;
-  if (d.k != 3 || d.stride != 1 || d.act == ACT_NONE || (int)cin_map.size() != d.cin) return 0;
-  if (d.up) {
-    if (d.cin == 96 && d.cout == 96) return pack_winoup(L, err);
-    if (d.cin == 48 && d.cout == 48) return pack_winoup48(L, err);
-    return 0;
-  }
-  if ((d.cin == 96 || d.cin == 192) && d.cout == 192) return pack_wino(L, err);
-  if (d.cin == 48 && d.cout == 192) return pack_wino24(L, err);                     // xconv5
-  if (d.cin == 24 && d.cout == 24 && d.rate == 1) return pack_rtilew(L, err);       // conv16
-  if (d.cin == 48 && d.cout == 96) return pack_wino48(L, err);
-  if (d.cin == 24 && d.cout == 96) return pack_wino48_c24(L, err);                  // xconv3, pmconv3
+  if (f.u && d.up) return d.cin == 96 ? pack_winoup(L, err) : pack_winoup48(L, err);
+  if (f.u && f.u24) return pack_wino(L, err);                                       // ... and pack_wino24
+  if (f.u24) return pack_wino24(L, err);                                            // xconv5
+  if (f.wx) return pack_rtilew(L, err);                                             // conv16
+  if (f.u) return d.cin == 48 ? pack_wino48(L, err) : pack_wino48_c24(L, err);      // (24: xconv3, pmconv3)
   return 0;
-}
-
-// bf16 direct image: the channels of a tap padded to whole 8-channel granules
-int pack_layer16(Layer& L, const std::vector<int>& cin_map, std::string& err) {
-  return pack_direct<unsigned short>(L, cin_map, L.direct[1], err);
 }
 
 // dense_kin: j-th k of a chunk -> k-step j / 4, lane group j % 4 (instruction-major).  In the last chunk that packs the
@@ -208,8 +186,8 @@ int dense_kin(int j) {
 // Rows in the MIXED order of the N=48 configuration, slot swizzle as pack_layer.
 int pack_layer_dense(Layer& L, const std::vector<int>& cin_map, std::string& err) {
   const LayerDef& d = L.def;
-  const int Cd = (int)cin_map.size();
-  const int G = d.cout / 2, NP = 48, T = d.k * d.k, K = T * Cd, nch = (K + 31) / 32;
+  const int Cd = L.facts.dense;
+  const int G = d.cout / 2, NP = 48, T = d.k * d.k, K = T * Cd, nch = L.facts.nchd;
   std::vector<float> img((size_t)nch * NP * 32, 0.f);
   for (int n = 0; n < NP; ++n) {
     const int oc = out_channel_of_row(GC_N48, n, G);
@@ -221,7 +199,6 @@ int pack_layer_dense(Layer& L, const std::vector<int>& cin_map, std::string& err
     }
   }
   if (upload(L.d_wd, img, err)) return 1;
-  L.dense = Cd; L.nchd = nch;
   // F(2,5)-along-x form (rtile_dense5w_kernel): U[nu][ky][c] = sum_kx Gx[nu][kx] w[ky][kx], formed in double; one chunk
   // per position with k = ky * Cd + c in the same instruction-major order
   static const double Gx[6][5] = {{1. / 4, 0., 0., 0., 0.}, {-1. / 6, -1. / 6, -1. / 6, -1. / 6, -1. / 6}, {-1. / 6, 1. / 6, -1. / 6, 1. / 6, -1. / 6},
@@ -247,7 +224,7 @@ int pack_layer_dense(Layer& L, const std::vector<int>& cin_map, std::string& err
 // bf16 pair-of-taps image of a 5x5 first layer whose stored NHWC8 input carries at most four real channels (rtile_kernel<3, 8,
 // true, true>): granule gi = 3 ky + j (j = 0..2) holds the taps (ky, 2j) and (ky, 2j + 1) x stored channels 0-3, i.e. element
 // e = 4 (kx & 1) + c; kx = 5 does not exist (zero).  15 granules -> 2 chunks of 64 k; rows in the MIXED N=48 order, slot swizzle
-// as pack_layer16.  cin4[c] = checkpoint input channel of stored channel c, or -1.
+// as the bf16 direct image.  cin4[c] = checkpoint input channel of stored channel c, or -1.
 int pack_layer16_d4(Layer& L, const std::vector<int>& cin4, std::string& err) {
   const LayerDef& d = L.def;
   const int G = d.cout / 2, NP = 48, nch = 2;
@@ -291,12 +268,6 @@ int pack_rconv16(Layer& L, std::string& err) {
 // bf16 image for rconv96_kernel (96 packed rows: 3x3 24/48 -> 96, gen_deconv 96 -> 96):
 // [class][step][6 row tiles][16 rows][32 k], k = granule (8 channels) index tap * CG + cg, four granules per step; rows in
 // the N=96 order (features, then gates); granule g of row r at slot g ^ F[r >> 2], F = {0, 2, 3, 1}.
-bool rconv96_eligible(const LayerDef& d) {
-  if (d.cout != 96 || d.rate != 1 || d.k != 3 || d.act == ACT_NONE) return false;
-  if (d.stride == 2) return !d.up && d.cin == 24;                     // stride 2: the 24 -> 96 downsampling layers
-  if (d.stride != 1) return false;
-  return d.up ? d.cin == 96 : (d.cin == 48 || d.cin == 24);
-}
 int pack_rconv96(Layer& L, std::string& err) {
   const LayerDef& d = L.def;
   static const int F[4] = {0, 2, 3, 1};
@@ -336,7 +307,7 @@ int pack_wino(Layer& L, std::string& err) {
     }
   }
   if (upload(L.d_u, img, err)) return 1;
-  if (d.cin == 192) {
+  if (L.facts.u1) {
     // for a spatially constant second source (conv11 of netG: the pooled style vector) the layer runs as the single-source
     // kernel on the first 96 channels plus a per-image bias table (launch_vecbias): the first source's Winograd image
     // ([16 positions][3 chunks][192][32], the first three chunks of every position of `img`) and the second source's
@@ -400,7 +371,7 @@ int pack_wino24(Layer& L, std::string& err) {
   // two images for the two-source layers: the first source alone (vector source folded into a bias: conv11) and both
   // sources (allconv11: 6 chunks per position)
   // (a 48-channel layer -- xconv5 -- has one image of 2 chunks per position, the second half empty)
-  const int nchk_first = d.cin == 48 ? 2 : 3, nchk_last = d.cin == 48 ? 2 : d.cin / 32;
+  const int nchk_first = d.cin == 48 ? 2 : 3, nchk_last = L.facts.u24b ? 6 : nchk_first;
   for (int nchk = nchk_first; nchk <= nchk_last; nchk += 3) {
     std::vector<float> img((size_t)24 * nchk * NP * 32, 0.f);
     for (int n = 0; n < NP; ++n) {
@@ -523,36 +494,48 @@ int pack_small(Layer& L, std::string& err) {
   for (int oc = 0; oc < d.cout; ++oc)
     for (int t = 0; t < 9; ++t)
       for (int ic = 0; ic < 12; ++ic) img[((size_t)oc * 9 + t) * 12 + ic] = L.w[(((size_t)oc * 12 + ic) * 3 + t / 3) * 3 + t % 3];
-  if (upload(L.direct[0].w, img, err) || upload(L.d_b, L.b, err)) return 1;
+  if (upload(L.direct[0], img, err) || upload(L.d_b, L.b, err)) return 1;
   for (auto& v : img) v = bf16_round(v);
-  if (upload(L.direct[1].w, img, err)) return 1;
+  if (upload(L.direct[1], img, err)) return 1;
   L.packed = true;
   return 0;
 }
 
-}  // namespace
-
-int pack_layer_images(Layer& L, const std::vector<int>& chans, std::string& err) {
-  const LayerDef& d = L.def;
-  if (small_layer(d)) return pack_small(L, err);
+// the images of a gated layer, as L.facts names them
+int pack_gated(Layer& L, const std::vector<int>& chans, std::string& err) {
+  const LayerFacts& f = L.facts;
   const int nc = (int)chans.size();
   auto padded = [&](int per) {      // the stored channels padded to whole granules of `per`
     std::vector<int> m(chans);
     m.resize((nc + per - 1) / per * per, -1);
     return m;
   };
-  // 5x5 first layers whose stored input has padding channels (5 of 8, 3 of 4): images over the real channels alone
-  // beside the padded ones -- bf16 pair-of-taps (at most four real channels), fp32 dense K
-  const bool first = d.k == 5 && d.stride == 1 && d.rate == 1 && d.cout == 48;
   // bf16: conv16's 12 gated outputs are stored with a 16-channel stride, so conv17 is not a gated layer and everything
   // else reads whole granules
-  if (pack_layer16(L, padded(8), err)) return 1;
-  if (first && nc >= 3 && nc <= 4 && pack_layer16_d4(L, padded(4), err)) return 1;
-  // (cin == 192: the image of the FIRST source's 96 channels, for the folded-vector form of conv11)
-  if (d.k == 3 && d.stride == 1 && !d.up && (d.cin == 96 || d.cin == 192) && d.cout == 192 && pack_rconv16(L, err)) return 1;
-  if (rconv96_eligible(d) && pack_rconv96(L, err)) return 1;
-  if (first && nc >= 3 && nc <= 5 && pack_layer_dense(L, chans, err)) return 1;
+  if (pack_direct<unsigned short>(L, padded(8), err)) return 1;
+  if (f.w16d && pack_layer16_d4(L, padded(4), err)) return 1;
+  if (f.w16s && pack_rconv16(L, err)) return 1;
+  if (f.w96 && pack_rconv96(L, err)) return 1;
+  if (f.wd && pack_layer_dense(L, chans, err)) return 1;
   return pack_layer(L, padded(4), err);
+}
+
+}  // namespace
+
+int pack_layer_images(Layer& L, const std::vector<int>& chans, std::string& err) {
+  const LayerFacts f = L.facts = layer_facts(L.def, (int)chans.size());
+  if (f.small ? pack_small(L, err) : pack_gated(L, chans, err)) return 1;
+  // the images that exist are the images the facts name: choose_form decides on the facts, the launchers read the images
+  const struct { const char* name; const float* img; bool fact; } have[] = {
+      {"u", L.d_u, f.u}, {"ub", L.d_ub, f.ub}, {"u1", L.d_u1, f.u1}, {"wv", L.d_wv, f.wv}, {"wv16", L.d_wv16, f.wv16},
+      {"u24", L.d_u24, f.u24}, {"ub24", L.d_ub24, f.ub24}, {"u24b", L.d_u24b, f.u24b}, {"wx", L.d_wx, f.wx}, {"wx2", L.d_wx2, f.wx2},
+      {"wd", L.d_wd, f.wd}, {"wdw", L.d_wdw, f.wdw}, {"w16d", L.d_w16d, f.w16d}, {"w16s", L.d_w16s, f.w16s}, {"w96", L.d_w96, f.w96}};
+  for (const auto& h : have)
+    if ((h.img != nullptr) != h.fact) {
+      err = std::string("layer ") + L.def.name + ": weight image " + h.name + (h.fact ? " is missing" : " was built against the layer's facts");
+      return 1;
+    }
+  return 0;
 }
 
 }  // namespace se

@@ -1,10 +1,10 @@
 """The kernel forms of a gated convolution, one table: which call reaches which form at which sizes.
 
-run_gconv / run_gconv16 / try_rtile (sketchedit_amd/csrc/se_api.hip) choose among some thirty kernel forms; every launch
-records the form it took (Engine.launch_forms()).  FORMS holds one row per form and per just-ineligible neighbour of a
-form: the call, the sizes, and the form that must run there.  tests/test_gpu_forms.py runs every (row, size) on its own --
-dispatch and values against a float64 reference -- and asserts that a whole forward launches no conv form that has no row
-here.
+choose_form (sketchedit_amd/csrc/se_dispatch.h) chooses among some thirty kernel forms and run_gconv (se_api.hip) launches its
+choice; every launch records the form it took (Engine.launch_forms()).  FORMS holds one row per form and per just-ineligible neighbour of a
+form: the call, the sizes, and the form that must run there.  tests/test_forms_host.py asks the rule for every (row, size) on
+the host; tests/test_gpu_forms.py runs every (row, size) on its own -- dispatch and values against a float64 reference -- and
+asserts that a whole forward launches no conv form that has no row here.
 
 Sizes are the smallest at which a form can go wrong, not the network's: the smallest eligible size, and one with at least
 two tiles on each axis and a ragged last tile (for the workgroup-tiled Winograd kernels: a tile count of B = 2 images that is
@@ -295,6 +295,26 @@ def reference(r, x, x1, w, b):
         if bf:
             y = y.to(torch.bfloat16).double()
     return y
+
+
+def predict(r, shape, B=BATCH, mode=None):
+    """The conv launches of row r's call as the library's rule answers on the host (se_debug_gconv_form: choose_form, the function
+    run_gconv launches by) -- no device."""
+    from sketchedit_amd import _lib
+    mode = r.mode if mode is None else mode
+    c1 = 96 if r.src2 else 0
+    return _lib.gconv_form(r.cin - c1, r.cout, shape[0], shape[1], k=r.k, stride=r.stride, rate=r.rate, act=r.act, upsample=r.up, cin1=c1,
+                           x1_is_vector=r.src2 == "vector", B=B, low_latency="lowlat" in mode, bf16=mode.startswith("bf16"))
+
+
+def dump_rows():
+    """Every (row, shape) of FORMS as a line of tools/dispatch_host_check.hip's input: the arguments of se_debug_gconv_form, the
+    expected launches, the row's switches."""
+    for r, (H, W) in cases():
+        c1 = 96 if r.src2 else 0
+        flags = (32 if "lowlat" in r.mode else 0) | (256 if r.mode.startswith("bf16") else 0)
+        print(r.cin - c1, c1, int(r.src2 == "vector"), r.cout, r.k, r.stride, r.rate, {"elu": 0, "relu": 1, None: 2}[r.act], int(r.up), BATCH, H, W,
+              flags, 0, ",".join(list(r.pre) + [r.form]), *["%s=%d" % kv for kv in sorted(r.switches.items())])
 
 
 def run(eng, r, x, x1, w, b):

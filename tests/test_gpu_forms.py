@@ -1,5 +1,5 @@
-"""Every kernel form of a gated convolution on its own: the dispatcher (run_gconv / run_gconv16 / try_rtile,
-sketchedit_amd/csrc/se_api.hip) must choose the form the table says (tests/forms_util.py FORMS), and that form
+"""Every kernel form of a gated convolution on its own: the dispatcher (choose_form, sketchedit_amd/csrc/se_dispatch.h, launched
+by run_gconv, se_api.hip) must choose the form the table says (tests/forms_util.py FORMS), and that form
 must compute the layer -- against a float64 reference of the same operation on the CPU, every element compared.
 
 A row whose dispatch condition is narrowed by mistake fails here on the form's NAME (Engine.launch_forms()), where a value
@@ -61,6 +61,8 @@ def _run_row(eng, r, shape, seopt, expect=None):
     # (a) dispatch: the conv launches are exactly the expected form (where folded: vecbias, then the form)
     want = list(r.pre) + [r.form] if expect is None else expect
     assert FU.conv_launches(launches) == want, (FU.row_id(r, shape), launches)
+    # ... and what the rule answers on the host for the same call (tests/test_forms_host.py) is what was launched
+    assert FU.predict(r, shape) == FU.conv_launches(launches), (FU.row_id(r, shape), launches)
     # (b) values
     _check_values(r, y, FU.reference(r, x, x1, w, b))
 
@@ -88,7 +90,7 @@ def test_low_latency_threshold(eng, t, seopt):
 
 @pytest.mark.parametrize("B", [1, 2, 3])
 def test_low_latency_choice_ignores_the_batch(eng, B, seopt):
-    """The thresholds count workgroups PER IMAGE (se_api.hip, run_gconv): 24 -> 24 at 18x34 is 9 raw tiles per image whatever
+    """The thresholds count workgroups PER IMAGE (se_dispatch.h, choose_form): 24 -> 24 at 18x34 is 9 raw tiles per image whatever
     the batch, so SE_RTILE_LL_MIN = 9 runs rtilew2 and 10 the small-grid gather-GEMM at every B (try_rtile once counted B x 9)."""
     r = FU.row("rtilew2", 24, 24, [(18, 34)], mode="lowlat")
     x, x1, w, b = FU.make_inputs(r, (18, 34), B=B)
@@ -160,7 +162,7 @@ def _check_forward(seq, mode):
 @pytest.mark.parametrize("size", [(64, 64), (40, 72)], ids=lambda s: "%dx%d" % s)
 def test_forward_forms_have_rows_and_ignore_the_batch(eng_w, size, mode):
     """Every conv form a forward launches has a row in FORMS; the (layer, form) sequence of B = 3 is that of B = 1 (the kernel a
-    layer runs depends on image size and mode only, se_api.hip run_gconv); SE_FLAG_CONSERVATIVE keeps netM off wino24."""
+    layer runs depends on image size and mode only, se_dispatch.h choose_form); SE_FLAG_CONSERVATIVE keeps netM off wino24."""
     H, W = size
     one = _forward_launches(eng_w, 1, H, W, mode)
     three = _forward_launches(eng_w, 3, H, W, mode)

@@ -589,7 +589,7 @@ def test_abi_has_two_new_symbols_in_a_header_of_their_own():
     declared = re.findall(r"^(?:int|size_t) (se_\w+)\(", hdr, re.M)
     assert declared == _lib.LASSO_SYMBOLS == ["se_lasso_fill_u8", "se_plane_combine_u8"]
     assert (len(_lib.SYMBOLS), len(_lib.PNG_SYMBOLS), len(_lib.JPG_SYMBOLS), len(_lib.JPG2_SYMBOLS), len(_lib.FEATHER_SYMBOLS),
-            len(_lib.FILL_SYMBOLS), len(_lib.SELECT_SYMBOLS)) == (53, 3, 3, 5, 1, 4, 3)
+            len(_lib.FILL_SYMBOLS), len(_lib.SELECT_SYMBOLS)) == (54, 3, 3, 5, 1, 4, 3)
     assert not set(_lib.LASSO_SYMBOLS) & set(_lib.SYMBOLS + _lib.PNG_SYMBOLS + _lib.JPG_SYMBOLS + _lib.JPG2_SYMBOLS + _lib.FEATHER_SYMBOLS +
                                              _lib.FILL_SYMBOLS + _lib.SELECT_SYMBOLS)
     for name in ("sketchedit_hip.h", "sketchedit_fill.h", "sketchedit_feather.h", "sketchedit_select.h"):

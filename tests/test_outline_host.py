@@ -395,7 +395,7 @@ def test_abi_has_two_new_symbols_in_a_header_of_their_own():
     declared = re.findall(r"^(?:int|size_t)\s+(se_\w+)\(", hdr, re.M)
     assert declared == _lib.OUTLINE_SYMBOLS == ["se_outline_u8_workspace_bytes", "se_outline_u8"]
     assert (len(_lib.SYMBOLS), len(_lib.PNG_SYMBOLS), len(_lib.JPG_SYMBOLS), len(_lib.JPG2_SYMBOLS), len(_lib.FEATHER_SYMBOLS),
-            len(_lib.FILL_SYMBOLS), len(_lib.SELECT_SYMBOLS), len(_lib.LASSO_SYMBOLS)) == (53, 3, 3, 5, 1, 4, 3, 2)
+            len(_lib.FILL_SYMBOLS), len(_lib.SELECT_SYMBOLS), len(_lib.LASSO_SYMBOLS)) == (54, 3, 3, 5, 1, 4, 3, 2)
     assert not set(_lib.OUTLINE_SYMBOLS) & set(_lib.SYMBOLS + _lib.PNG_SYMBOLS + _lib.JPG_SYMBOLS + _lib.JPG2_SYMBOLS + _lib.FEATHER_SYMBOLS +
                                                _lib.FILL_SYMBOLS + _lib.SELECT_SYMBOLS + _lib.LASSO_SYMBOLS)
     for name in sorted(os.listdir(os.path.join(ROOT, "include"))):
