@@ -1,7 +1,7 @@
 // Which kernel form a gated convolution runs, as two pure host functions of integers:
 //   layer_facts  -- the packing numbers of a layer and which weight images it has (se_pack.hip builds exactly these);
 //   choose_form  -- the form of one call, from the layer, its facts, the sizes, the mode and the developer switches (opt()).
-// No memory, no device, no se_ctx: se_api.hip (run_gconv) launches what choose_form says, se_debug_gconv_form reports it, and
+// No memory, no device, no se_ctx: se_plan.hip (run_gconv) launches what choose_form says, se_debug_gconv_form reports it, and
 // tests/test_forms_host.py holds it against the table of tests/forms_util.py without a GPU.
 #pragma once
 #include "se_kernels.h"      // opt(), GC_*, gconv_np(), rtile_rows()

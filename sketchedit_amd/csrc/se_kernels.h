@@ -1,4 +1,4 @@
-// Internal (C++) interface between the host-side forward plan (se_api.hip) and the
+// Internal (C++) interface between the host files (se_plan.hip, se_api*.hip; se_host.h) and the
 // gfx950 kernels (se_gconv.hip, se_wino.hip, se_wino48.hip, se_attention.hip, se_misc.hip).  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -57,7 +57,7 @@ hipError_t ensure_max_lds(const void* func, int bytes);
   X(RTILE_DENSE, 1)      /* 0: channel-padded K for the 5x5 first layers */                                    \
   X(RTILE_D5W, 1)        /* 0: 5x5 first layers on the direct dense-K kernel */                                \
   X(TEST_OFFSET_LIMIT, 0) /* test aid, se_debug_set_option only: byte range of the 32-bit-offset kernels (0: 2^31) */ \
-  X(TEST_POISON, 0)      /* test aid, se_debug_set_option only: 1..255 fills every scratch region with that byte when it is handed out, any other value is off (se_api.hip poison) */ \
+  X(TEST_POISON, 0)      /* test aid, se_debug_set_option only: 1..255 fills every scratch region with that byte when it is handed out, any other value is off (se_host.h poison) */ \
   X(RCONV16, 1) X(RCONV16_DUAL, 1) X(RCONV96, 1) X(VECBIAS, 1)                                                  \
   X(WINOGRAD, 1) X(WINOGRAD48, 1) X(WINOGRAD_UP, 1) X(WINOGRAD_UP48, 1)                                         \
   X(WINOGRAD_F43, 1)     /* hybrid F(2,3)xF(4,3): 0 off, 1 everywhere, 2 netG only */ \

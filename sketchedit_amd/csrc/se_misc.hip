@@ -538,7 +538,7 @@ hipError_t launch_quantize_u8(const float* composed, const float* mask, unsigned
 
 // ---- input dequantisation (data/testimage_dataset.py:89-111 of the reference: ToTensor + Normalize(0.5, 0.5), sketch > 0):
 // 4 consecutive pixels per thread -- 12 + 4 input bytes, four float4 stores.  The 256 possible image values come from a table
-// the HOST computed with IEEE fp32 division in the dataset's operation order (se_api.hip dequant_table): bit-identical to the
+// the HOST computed with IEEE fp32 division in the dataset's operation order (se_api.hip se_create): bit-identical to the
 // float tensors the CPU dataset builds, whatever the device's division does.
 __global__ void dequant_u8_kernel(const unsigned char* __restrict__ rgb, const unsigned char* __restrict__ sk8,
                                   const float* __restrict__ lut, float* __restrict__ image, float* __restrict__ sketch, int B, int HW) {

@@ -1,6 +1,6 @@
 // Window edits of a resident frame: the three memory-bound helpers around the forward when it runs on an
 // H x W window of a larger uint8 frame that stays on the device.  B requests per launch, each with its own frame; a request
-// is one se_window record (include/sketchedit_hip.h) of a device table the ctx owns (se_api.hip win_put).
+// is one se_window record (include/sketchedit_hip.h) of a device table the ctx owns (se_api_window.hip win_put).
 //
 //  gather: the window of each frame -> that request's slot of the forward's fp32 NCHW inputs, through the ctx's
 //          dequantisation table (bit-identical to se_dequantize_u8 on a contiguous crop), and the window's sketch as (v > 0);

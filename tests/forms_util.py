@@ -1,6 +1,6 @@
 """The kernel forms of a gated convolution, one table: which call reaches which form at which sizes.
 
-choose_form (sketchedit_amd/csrc/se_dispatch.h) chooses among some thirty kernel forms and run_gconv (se_api.hip) launches its
+choose_form (sketchedit_amd/csrc/se_dispatch.h) chooses among some thirty kernel forms and run_gconv (se_plan.hip) launches its
 choice; every launch records the form it took (Engine.launch_forms()).  FORMS holds one row per form and per just-ineligible neighbour of a
 form: the call, the sizes, and the form that must run there.  tests/test_forms_host.py asks the rule for every (row, size) on
 the host; tests/test_gpu_forms.py runs every (row, size) on its own -- dispatch and values against a float64 reference -- and

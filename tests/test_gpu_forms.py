@@ -1,5 +1,5 @@
 """Every kernel form of a gated convolution on its own: the dispatcher (choose_form, sketchedit_amd/csrc/se_dispatch.h, launched
-by run_gconv, se_api.hip) must choose the form the table says (tests/forms_util.py FORMS), and that form
+by run_gconv, se_plan.hip) must choose the form the table says (tests/forms_util.py FORMS), and that form
 must compute the layer -- against a float64 reference of the same operation on the CPU, every element compared.
 
 A row whose dispatch condition is narrowed by mistake fails here on the form's NAME (Engine.launch_forms()), where a value

@@ -38,6 +38,22 @@ def test_header_symbols_exported(built_lib):
     assert b"gfx950" in built_lib.se_version()
 
 
+def test_exported_c_names_are_the_declared_symbols(built_lib):
+    """The library's unmangled se_ names are the *_SYMBOLS lists of the binding, no more and no fewer: a helper shared between
+    the host files stays a C++ name in namespace se, and every declared entry is defined in some file."""
+    import shutil
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path=os.path.join(rocm, "llvm", "bin"))
+    if nm is None:
+        pytest.skip("neither nm nor llvm-nm on this machine")
+    out = subprocess.check_output([nm, "-D", "--defined-only", _lib.LIB_PATH], text=True)
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("se_")}
+    lists = [getattr(_lib, n) for n in dir(_lib) if n == "SYMBOLS" or n.endswith("_SYMBOLS")]
+    declared = [s for lst in lists for s in lst]
+    assert len(declared) == len(set(declared)) >= len(_lib.SYMBOLS)
+    assert exported == set(declared), exported ^ set(declared)
+
+
 def test_library_contains_gfx950_code():
     assert b"gfx950" in open(_lib.LIB_PATH, "rb").read()
 
