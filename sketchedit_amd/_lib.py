@@ -17,8 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
-           "se_plan.hip", "se_api_window.hip", "se_api_select.hip", "se_api_codec.hip", "se_api_debug.hip", "se_api.hip"]
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_move.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
+           "se_plan.hip", "se_api_window.hip", "se_api_select.hip", "se_api_move.hip", "se_api_codec.hip", "se_api_debug.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
@@ -69,6 +69,10 @@ COMBINE_ADD, COMBINE_SUBTRACT, COMBINE_INTERSECT, COMBINE_XOR, COMBINE_INVERT = 
 # every symbol declared in include/sketchedit_outline.h (the outline of a selection)
 OUTLINE_SYMBOLS = ["se_outline_u8_workspace_bytes", "se_outline_u8"]
 OUTLINE_TILE, OUTLINE_MAX_CAP = 64, 1 << 24       # SE_OUTLINE_TILE, SE_OUTLINE_MAX_CAP
+# every symbol declared in include/sketchedit_move.h (move or clone a selection)
+MOVE_SYMBOLS = ["se_move_drop_u8", "se_plane_shift_u8"]
+MOVE_MAX_OFFSET, MOVE_MAX_RADIUS = 16384, 16      # SE_MOVE_MAX_OFFSET, SE_MOVE_MAX_RADIUS
+MOVE_FLIP_X, MOVE_FLIP_Y = 1, 2                   # SE_MOVE_FLIP_*
 
 
 class SketchEditHipError(RuntimeError):
@@ -290,6 +294,10 @@ def load_library():
         lib.se_lasso_fill_u8.restype = ci
         lib.se_plane_combine_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
         lib.se_plane_combine_u8.restype = ci
+        lib.se_move_drop_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8
+        lib.se_move_drop_u8.restype = ci
+        lib.se_plane_shift_u8.argtypes = [vp, vp, vp, ci, ci] + [ci] * 7 + [vp]
+        lib.se_plane_shift_u8.restype = ci
         lib.se_outline_u8_workspace_bytes.argtypes = [vp, ci, ci]
         lib.se_outline_u8_workspace_bytes.restype = sz
         lib.se_outline_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, sz]
@@ -1169,6 +1177,45 @@ class Engine:
         edges = ctypes.c_void_p(out.data_ptr() + 8) if cap else None
         if self.lib.se_outline_u8(self.h, self._stream(), _ptr(plane), Hi, Wi, edges, cap, _ptr(out), _ptr(ws_t), ws_t.numel()):
             self._err("se_outline_u8")
+        return out
+
+    # ---- move or clone a selection (include/sketchedit_move.h) -------------------------------------------------------
+    def move_drop_u8(self, frame, lift, lift_rect, sel, lock, box, offset, flip=0, radius=0):
+        """se_move_drop_u8, in place on `frame` (Hi,Wi,3) uint8 on the device: the pixels of `box` = (by0, bx0, by1, bx1) that
+        `sel` (an (Hi,Wi) plane, non-zero = selected) selects, as `lift` holds them -- the journal slot window_save_u8 made of
+        `lift_rect` = (ly0, lx0, lh, lw), a rectangle that holds the box -- land `offset` = (dy, dx) away, mirrored about the box
+        by `flip` (MOVE_FLIP_X | MOVE_FLIP_Y), where `lock` (a plane or None) is 0; `radius` 0 .. 16 fades their rim into the
+        frame.  No other byte changes.  One launch; none when the whole box lands outside the frame."""
+        _check_dev_u8(frame)
+        if frame.dim() != 3 or frame.shape[2] != 3:
+            raise SketchEditHipError("move_drop_u8: a frame is an (Hi,Wi,3) uint8 tensor")
+        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
+        if self._state_plane(sel, "move_drop_u8: sel") != (Hi, Wi) or (lock is not None and self._state_plane(lock, "move_drop_u8: lock") != (Hi, Wi)):
+            raise SketchEditHipError("move_drop_u8: sel and lock are the frame's (Hi,Wi) planes")
+        ly0, lx0, lh, lw = (int(v) for v in lift_rect)
+        _check_dev_u8(lift)
+        need = self.window_saved_bytes(lh, lw)
+        if need and lift.numel() < need:
+            raise SketchEditHipError("move_drop_u8: a lift holds window_saved_bytes(lh, lw) = %d bytes" % need)
+        by0, bx0, by1, bx1 = (int(v) for v in box)
+        if self.lib.se_move_drop_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
+                                    by0, bx0, by1, bx1, int(offset[0]), int(offset[1]), int(flip), int(radius)):
+            self._err("se_move_drop_u8")
+
+    def plane_shift_u8(self, sel, box, offset, flip=0, out=None):
+        """se_plane_shift_u8: `sel` (Hi,Wi) uint8 on the device, non-zero = selected -> `out` (a new plane, or another plane of
+        that shape at any alignment; every byte is written), 0 / 255: the selected pixels of `box` = (by0, bx0, by1, bx1) moved by
+        `offset` = (dy, dx) and mirrored about the box by `flip`; what leaves the frame is dropped."""
+        import torch
+        Hi, Wi = self._state_plane(sel, "plane_shift_u8: sel")
+        if out is None:
+            out = torch.empty((Hi, Wi), dtype=torch.uint8, device=sel.device)
+        if self._state_plane(out, "plane_shift_u8: out") != (Hi, Wi):
+            raise SketchEditHipError("plane_shift_u8: out is a plane of sel's shape")
+        by0, bx0, by1, bx1 = (int(v) for v in box)
+        if self.lib.se_plane_shift_u8(self.h, self._stream(), _ptr(sel), Hi, Wi, by0, bx0, by1, bx1, int(offset[0]), int(offset[1]), int(flip),
+                                      _ptr(out)):
+            self._err("se_plane_shift_u8")
         return out
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // Host side of libsketchedit_hip.so behind the C-ABI declared in include/sketchedit_hip.h: the context and its weights, the
 // forwards of netM / netG / inference with the hipGraph cache, the uint8 ends, and the Pillow-exact resize with its resources.
 // The plans themselves: se_plan.hip; the context and what the host files share: se_host.h; weight images: se_pack.hip; the
-// entries of the editing sessions: se_api_window.hip, se_api_select.hip, se_api_codec.hip; profiler, switches and per-op
+// entries of the editing sessions: se_api_window.hip, se_api_select.hip, se_api_move.hip, se_api_codec.hip; profiler, switches and per-op
 // entries: se_api_debug.hip.
 #include "se_host.h"
 

@@ -1,0 +1,79 @@
+// The editing sessions' move entries behind include/sketchedit_move.h: the drop of a lifted selection and the shift of its plane
+// (kernels: se_move.hip).
+#include "../../include/sketchedit_move.h"
+#include "se_host.h"
+
+using namespace se;
+
+// ====================================================================================================
+extern "C" {
+
+// Every check on the host, then ONE launch that writes the caller's frame or plane directly: no workspace, nothing for
+// SE_TEST_POISON to fill.
+namespace {
+
+// The frame's size.  What the launches take: plane_shift walks Hi Wi / 4 dwords, 256 to a workgroup, along grid.x (< 2^31
+// workgroups); move_drop's grid is the destination rectangle's 64 x 16 tiles, at most (Wi + 63) / 64 along x and (Hi + 15) / 16
+// along y, where a grid holds 65 535.
+int move_check_frame(se_ctx* c, int Hi, int Wi) {
+  if (Hi < 16 || Wi < 16) return fail(c, "bad Hi=%d Wi=%d (a frame is at least 16 x 16)", Hi, Wi);
+  if ((Hi + 15) / 16 > 65535 || (long long)Hi * Wi / 1024 >= (1ll << 31))
+    return fail(c, "move: Hi=%d Wi=%d is more than one launch takes", Hi, Wi);
+  return 0;
+}
+
+// the box against the rectangle (ry0, rx0, rh, rw) that must hold it, the offset and the flip
+int move_check_map(se_ctx* c, int by0, int bx0, int by1, int bx1, int ry0, int rx0, int rh, int rw, const char* holder, int dy, int dx,
+                   int flip) {
+  if (by1 <= by0 || bx1 <= bx0) return fail(c, "bad box (%d, %d, %d, %d): a box (by0, bx0, by1, bx1) is half open and not empty", by0, bx0, by1, bx1);
+  if (by0 < ry0 || bx0 < rx0 || by1 > ry0 + rh || bx1 > rx0 + rw)
+    return fail(c, "the box (%d, %d, %d, %d) lies outside the %s (y0=%d x0=%d, %d x %d)", by0, bx0, by1, bx1, holder, ry0, rx0, rh, rw);
+  if (dy < -SE_MOVE_MAX_OFFSET || dy > SE_MOVE_MAX_OFFSET) return fail(c, "bad dy=%d (|dy| <= %d)", dy, SE_MOVE_MAX_OFFSET);
+  if (dx < -SE_MOVE_MAX_OFFSET || dx > SE_MOVE_MAX_OFFSET) return fail(c, "bad dx=%d (|dx| <= %d)", dx, SE_MOVE_MAX_OFFSET);
+  if (flip < 0 || flip > 3) return fail(c, "bad flip=%d (0 .. 3)", flip);
+  return 0;
+}
+
+}  // namespace
+
+int se_move_drop_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh,
+                    int lw, const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, int dy, int dx,
+                    int flip, int radius) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!frame_u8) return fail(c, "null pointer argument: frame_u8");
+  if (!lift) return fail(c, "null pointer argument: lift");
+  if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
+  if (move_check_frame(c, Hi, Wi)) return 1;
+  if (lh < 16 || lw < 16) return fail(c, "bad lift rectangle lh=%d lw=%d (a side is at least 16)", lh, lw);
+  if (ly0 < 0 || lx0 < 0 || lh > Hi || lw > Wi || ly0 > Hi - lh || lx0 > Wi - lw)
+    return fail(c, "the lift rectangle (ly0=%d lx0=%d, %d x %d) lies outside the frame (Hi=%d Wi=%d)", ly0, lx0, lh, lw, Hi, Wi);
+  if (!aligned_to(lift, 16)) return fail(c, "lift must be 16-byte aligned");
+  if (move_check_map(c, by0, bx0, by1, bx1, ly0, lx0, lh, lw, "lift rectangle", dy, dx, flip)) return 1;
+  if (radius < 0 || radius > SE_MOVE_MAX_RADIUS) return fail(c, "bad radius=%d (0 .. %d)", radius, SE_MOVE_MAX_RADIUS);
+  const size_t pn = (size_t)Hi * Wi, lpitch = ((size_t)3 * lw + 15) & ~(size_t)15, ln = (size_t)lh * lpitch;
+  if (overlaps(lift, ln, frame_u8, 3 * pn)) return fail(c, "lift overlaps frame_u8");
+  if (overlaps(sel_u8, pn, frame_u8, 3 * pn)) return fail(c, "sel_u8 overlaps frame_u8");
+  if (lock_u8 && overlaps(lock_u8, pn, frame_u8, 3 * pn)) return fail(c, "lock_u8 overlaps frame_u8");
+  if (device_enter(c)) return 1;
+  HIPCHK(c, launch_move_drop(frame_u8, Hi, Wi, lift, ly0, lx0, lw, (int)lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, dy, dx, flip, radius,
+                             (hipStream_t)stream));
+  return 0;
+}
+
+int se_plane_shift_u8(se_ctx* c, void* stream, const unsigned char* sel_u8, int Hi, int Wi, int by0, int bx0, int by1, int bx1, int dy,
+                      int dx, int flip, unsigned char* plane_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
+  if (!plane_out) return fail(c, "null pointer argument: plane_out");
+  if (move_check_frame(c, Hi, Wi)) return 1;
+  if (move_check_map(c, by0, bx0, by1, bx1, 0, 0, Hi, Wi, "frame", dy, dx, flip)) return 1;
+  const size_t pn = (size_t)Hi * Wi;
+  if (overlaps(plane_out, pn, sel_u8, pn)) return fail(c, "plane_out overlaps sel_u8");
+  if (device_enter(c)) return 1;
+  HIPCHK(c, launch_plane_shift(sel_u8, Hi, Wi, by0, bx0, by1, bx1, dy, dx, flip, plane_out, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

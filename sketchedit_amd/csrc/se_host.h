@@ -1,5 +1,5 @@
 // Host-only internals of libsketchedit_hip.so, shared by its host files (se_plan.hip, se_api.hip, se_api_window.hip,
-// se_api_select.hip, se_api_codec.hip, se_api_debug.hip): the context, the workspace arena, the error and entry helpers, and
+// se_api_select.hip, se_api_move.hip, se_api_codec.hip, se_api_debug.hip): the context, the workspace arena, the error and entry helpers, and
 // the few functions that one of those files defines and another calls.  Like se_dispatch.h it holds no __global__ code; it is
 // not part of the C-ABI.
 #pragma once

@@ -22,7 +22,8 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
                  PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW,
-                 PL_LASSO_FILL, PL_PLANE_COMBINE, PL_OUTLINE_COUNT, PL_OUTLINE_SCAN, PL_OUTLINE_EMIT, PL_COUNT };
+                 PL_LASSO_FILL, PL_PLANE_COMBINE, PL_OUTLINE_COUNT, PL_OUTLINE_SCAN, PL_OUTLINE_EMIT, PL_MOVE_DROP,
+                 PL_PLANE_SHIFT, PL_COUNT };
 const char* prof_label_name(int l);
 // Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
 // know which kernel the dispatcher chose; the label's name where the launcher has one form only
@@ -464,6 +465,15 @@ hipError_t launch_plane_combine(const unsigned char* a, const unsigned char* b, 
 hipError_t launch_outline_count(const unsigned char* plane, int Hi, int Wi, int* cnt, hipStream_t st);
 hipError_t launch_outline_scan(int* cnt, int Hi, int Wi, int cap, int* info_out, hipStream_t st);
 hipError_t launch_outline_emit(const unsigned char* plane, int Hi, int Wi, const int* offs, int* edges_out, int cap, hipStream_t st);
+// move or clone a selection (include/sketchedit_move.h; se_move.hip).  Any Hi, Wi >= 16 and any alignment of the
+// frame and the planes.  move_drop: the selected pixels of the box, as the lift (a journal slot of the rectangle at (ly0, lx0),
+// lw wide, rows of lpitch bytes) holds them, blended into the frame at the offset / flip; only the tiles of the shifted box
+// clipped to the frame are launched, none when that is empty.  plane_shift: every byte of `out` <- the moved selection, 0 / 255.
+hipError_t launch_move_drop(unsigned char* frame, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lw, int lpitch,
+                            const unsigned char* sel, const unsigned char* lock, int by0, int bx0, int by1, int bx1, int dy, int dx, int flip,
+                            int radius, hipStream_t st);
+hipError_t launch_plane_shift(const unsigned char* sel, int Hi, int Wi, int by0, int bx0, int by1, int bx1, int dy, int dx, int flip,
+                              unsigned char* out, hipStream_t st);
 // the device PNG encoder (include/sketchedit_png.h): the hs x ws rectangles of d_wins (B records) -> their zlib
 // streams.  rows: ftype (B,hs) uint8, each row's filter type.  stripes: one workgroup per stripe of 32 rows -> its deflate blocks
 // in its slot of png_slot_bytes(ws) bytes (16-byte aligned), its size in sizes (B,S) and its Adler parts in parts (B,S,2), S =

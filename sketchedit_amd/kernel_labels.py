@@ -51,6 +51,10 @@ KERNEL_LABELS = {
     "(anonymous namespace)::outline_tile_kernel<false>": "outline_count", "(anonymous namespace)::outline_tile_kernel<true>": "outline_emit",
     "(anonymous namespace)::outline_scan_kernel": "outline_scan",
     "outline_tile_kernel<false>": "outline_count", "outline_tile_kernel<true>": "outline_emit", "outline_scan_kernel": "outline_scan",
+    # move or clone a selection (se_move.hip): the drop without and with a soft edge, and the shift of the plane
+    "(anonymous namespace)::move_drop_kernel<false>": "move_drop", "(anonymous namespace)::move_drop_kernel<true>": "move_drop",
+    "(anonymous namespace)::plane_shift_kernel": "plane_shift",
+    "move_drop_kernel<false>": "move_drop", "move_drop_kernel<true>": "move_drop", "plane_shift_kernel": "plane_shift",
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",

@@ -235,6 +235,16 @@ class EditLine2Model(torch.nn.Module):
         (Engine.outline_u8)."""
         return self.engine().outline_u8(plane, cap)
 
+    def move_drop_u8(self, frame, lift, lift_rect, sel, lock, box, offset, flip=0, radius=0):
+        """The drop of a moved selection (serve.EditSession.move_selection is the caller-facing form): the selected
+        pixels of `box`, as the journal slot `lift` of `lift_rect` holds them, blended into the resident frame `offset` away
+        (Engine.move_drop_u8)."""
+        self.engine().move_drop_u8(frame, lift, lift_rect, sel, lock, box, offset, flip=flip, radius=radius)
+
+    def plane_shift_u8(self, sel, box, offset, flip=0, out=None):
+        """A selection plane moved as move_drop_u8 moves its pixels: a new 0 / 255 plane (Engine.plane_shift_u8)."""
+        return self.engine().plane_shift_u8(sel, box, offset, flip=flip, out=out)
+
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
         slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""

@@ -378,6 +378,34 @@ def rings_svg_path(rings):
     return " ".join("M %d %d " % tuple(r[0]) + "".join("L %d %d " % tuple(q) for q in r[1:]) + "Z" for r in rings)
 
 
+MOVE_MAX_OFFSET = 16384      # SE_MOVE_MAX_OFFSET
+MOVE_FLIPS = {None: 0, "h": 1, "v": 2, "hv": 3}     # SE_MOVE_FLIP_X | SE_MOVE_FLIP_Y
+MOVE_MIN_SIDE = 16           # the smallest side of a journal slot's rectangle
+
+
+def move_rect(box, offset, frame_hw):
+    """The rectangle of the frame a moved selection lands in (pure host arithmetic): `box` = (y0, x0, y1, x1), half
+    open, shifted by `offset` = (dy, dx) and clipped to the frame of `frame_hw` = (Hi, Wi), both >= 16.  A side under 16 -- what a
+    journal slot takes at least -- is then widened to 16 inside the frame: by half the missing pixels at its low end (rounded
+    down), the rest at its high end, and where that would leave the frame the rectangle is shifted back into it, towards the
+    interior.  It always holds the clipped box.  A mirrored move lands in the same rectangle: the flips mirror about the box.
+    -> (y0, x0, h, w), or None when nothing of the box lands in the frame.  offset (0, 0) gives the rectangle a move LIFTS."""
+    by0, bx0, by1, bx1 = (int(v) for v in box)
+    dy, dx = int(offset[0]), int(offset[1])
+
+    def axis(lo, hi, extent):
+        lo, hi = max(lo, 0), min(hi, extent)
+        if hi <= lo:
+            return None
+        if hi - lo < MOVE_MIN_SIDE:
+            lo = min(max(lo - (MOVE_MIN_SIDE - (hi - lo)) // 2, 0), extent - MOVE_MIN_SIDE)
+            hi = lo + MOVE_MIN_SIDE
+        return lo, hi - lo
+
+    ya, xa = axis(by0 + dy, by1 + dy, int(frame_hw[0])), axis(bx0 + dx, bx1 + dx, int(frame_hw[1]))
+    return None if ya is None or xa is None else (ya[0], xa[0], ya[1], xa[1])
+
+
 def png_from_zlib(stream, h, w):
     """The PNG file around a zlib stream of filtered 8-bit RGB rows: signature, IHDR, ONE IDAT holding
     `stream` as it is, IEND -- the chunk framing and its CRCs are the host's part of a patch that was encoded on the device."""
@@ -520,6 +548,11 @@ def _by_size(windows):
 
 class _Regions(tuple):
     """the windows of a region edit's journal entry (its slots are a list in the same order)"""
+
+
+class _Sequence(tuple):
+    """the rectangles of a move's journal entry, in the order its steps wrote them: they may overlap, so undo
+    exchanges them in reverse order and redo in this one (its slots are a list in the same order)"""
 
 
 def _run_windows(be, frames, origins, crops, window_hw, work, locks, commit, low_latency):
@@ -737,6 +770,24 @@ class _ModelBackend:
         """a copy of a plane that is on the device, made there"""
         return plane.clone()
 
+    def grow(self, plane, grow):
+        """a NEW plane: the pixels within `grow` (1 .. 16) pixels of a selected one (DESIGN.md 6o's grow; a selection's 0 / 255
+        plane is a state plane as it is)"""
+        return self.model.select_grow_u8(plane, grow)
+
+    def move_drop(self, frame, lift, lift_rect, plane, lock, box, offset, flip, radius):
+        """the drop of a move, ONE launch in place on the frame: the pixels of `box` that `plane` selects, as the
+        slot `lift` of `lift_rect` holds them, land `offset` away under `flip` (SE_MOVE_FLIP_*) where `lock` (or None) is 0, with a
+        soft edge of `radius`"""
+        self.model.move_drop_u8(frame, lift, lift_rect, plane, lock, box, offset, flip=flip, radius=radius)
+
+    def shift(self, plane, box, offset, flip):
+        """a selection's plane moved as move_drop moves its pixels -> (plane, box, count) of a NEW plane: one
+        launch, then the tile records of the result -- the one download"""
+        out = self.model.plane_shift_u8(plane, box, offset, flip=flip)
+        b, count = tiles_box(self.tiles(out, 32))
+        return out, b, count
+
     def save(self, frames, origins, window_hw):
         """the windows' rectangles -> one new journal slot each, on the stream the edit follows on"""
         return self.model.window_save_u8(frames, origins, window_hw)
@@ -934,6 +985,28 @@ class EditSession:
         info = dict(windows=list(wins), undo_depth=len(self._undo), redo_depth=len(self._redo))
         return [self.backend.crop(self._frame, *w) for w in wins], [(w[1], w[0]) for w in wins], info
 
+    def _record_sequence(self, windows, slots):
+        """`_record` for a move: ONE entry with its rectangles in the order they were written and their slots (None: not
+        journalled)"""
+        self._redo.clear()
+        if slots is None:
+            self._undo.clear()
+            return False
+        self._push((_Sequence(windows), list(slots), sum(window_saved_bytes(w[2], w[3]) for w in windows)))
+        return True
+
+    def _exchange_sequence(self, src, dst, reverse):
+        """the move's entry `src` ends in <-> the frame: one swap call per rectangle -- they may overlap -- in the
+        order they were written (redo) or the REVERSE of it (undo: a later slot holds what the earlier steps left); -> what
+        undo / redo return for it, in the region entries' shape"""
+        wins, slots, _ = src[-1]
+        order = range(len(wins) - 1, -1, -1) if reverse else range(len(wins))
+        for i in order:
+            self.backend.swap([self._frame], [wins[i][:2]], wins[i][2:], [slots[i]])
+        dst.append(src.pop())
+        info = dict(windows=list(wins), undo_depth=len(self._undo), redo_depth=len(self._redo))
+        return [self.backend.crop(self._frame, *w) for w in wins], [(w[1], w[0]) for w in wins], info
+
     def _exchanged(self, src, dst):
         """the entry `src` ends in was exchanged with the frame: it moves to `dst`; -> what undo / redo return"""
         dst.append(src.pop())
@@ -945,6 +1018,8 @@ class EditSession:
         with self._lock:
             if not src:
                 raise IndexError("nothing to " + what)
+            if isinstance(src[-1][0], _Sequence):
+                return self._exchange_sequence(src, dst, src is self._undo)
             if isinstance(src[-1][0], _Regions):
                 return self._exchange_regions(src, dst)
             (y0, x0, h, w), slot, _ = src[-1]
@@ -955,7 +1030,9 @@ class EditSession:
         """Takes the last edit back: the frame is byte-identical to what it was before it.  -> (patch, (x0, y0), info) in
         `edit`'s shape: the window after the exchange (the only download), info = dict(window, undo_depth, redo_depth).
         A region edit (edit_regions) is one step: all its windows are exchanged and the three are lists in ITS shape, with
-        info = dict(windows, undo_depth, redo_depth).  IndexError when there is nothing to undo."""
+        info = dict(windows, undo_depth, redo_depth).  A move (move_selection) is one step too and returns in that shape; its
+        rectangles may overlap, so they are exchanged in the reverse of the order they were written, and by `redo` in that
+        order.  IndexError when there is nothing to undo."""
         return self._exchange(self._undo, self._redo, "undo")
 
     def redo(self):
@@ -1193,23 +1270,32 @@ class EditSession:
             return self._check_window(window, max_side is not None)
         return choose_window(box, self.frame_hw, margin=margin)
 
+    def _fill_steps(self, fill_plane, crop, win, low_latency, max_side, feather, journal):
+        """The steps of a fill that change the frame, with the session's lock held: keep plane, the forward, the journal's save
+        when `journal`, ONE paste; no download in between.  The caller owns the journal entry.
+        -> (slot or None, work, planes)"""
+        be = self.backend
+        y0, x0, h, w = win
+        frames, origins = [self._frame], [(y0, x0)]
+        planes = None if self._lock_plane is None else [self._lock_plane]
+        work = choose_working_size((h, w), max_side) if max_side is not None else None
+        keep = be.fill_keep(frames, origins, [fill_plane], planes, (h, w))
+        rgb, m8 = be.run_fill(frames, origins, [crop], [fill_plane], planes, (h, w), work, low_latency)
+        slot = be.save(frames, origins, (h, w))[0] if journal else None
+        if feather is not None:
+            be.paste_feather(frames, origins, keep, (h, w), feather, rgb, m8)
+        else:
+            be.paste_locked(frames, origins, keep, (h, w), rgb, m8)
+        return slot, work, planes
+
     def _fill(self, fill_plane, crop, win, low_latency, max_side, encode, feather):
         """The device part of fill and fill_strokes, with the session's lock held: `fill_plane` the frame-sized plane and `crop`
         the window's sketch (or None), both on the device.  Keep plane, the forward, the journal's save, ONE paste, the
         patch: no download in between."""
         be = self.backend
-        scaled = max_side is not None
         y0, x0, h, w = win
-        frames, origins = [self._frame], [(y0, x0)]
-        planes = None if self._lock_plane is None else [self._lock_plane]
-        work = choose_working_size((h, w), max_side) if scaled else None
-        keep = be.fill_keep(frames, origins, [fill_plane], planes, (h, w))
-        rgb, m8 = be.run_fill(frames, origins, [crop], [fill_plane], planes, (h, w), work, low_latency)
-        slot = be.save(frames, origins, (h, w))[0] if self._journals(h, w) else None
-        if feather is not None:
-            be.paste_feather(frames, origins, keep, (h, w), feather, rgb, m8)
-        else:
-            be.paste_locked(frames, origins, keep, (h, w), rgb, m8)
+        frames = [self._frame]
+        slot, work, planes = self._fill_steps(fill_plane, crop, win, low_latency, max_side, feather, self._journals(h, w))
         undoable = self._record(win, slot) if self.history > 0 else None
         patch = be.crop(self._frame, y0, x0, h, w) if encode is None else _encoded(be, encode, frames, [win])[0]
         return patch, (x0, y0), _edit_info(dict(window=win, fill=True), planes is not None, work, undoable, feather)
@@ -1423,6 +1509,99 @@ class EditSession:
             if selection.box is None:
                 raise ValueError("the lasso covers no pixel centre")
             return self._fill_selected(selection, sk, window, margin, low_latency, max_side, encode, feather)
+
+    # ---- move or clone a selection ------------------------------------------------------------------------------------
+    def move_selection(self, selection, offset, flip=None, keep_source=False, hole_grow=2, window=None, margin=0.5, low_latency=None,
+                       max_side=None, encode=None, feather=None):
+        """"Drag this over there and mend the place it came from" (DESIGN.md 6r): the selected pixels land `offset` = (dy, dx) away
+        -- two ints, each at most 16 384 in magnitude -- mirrored about the selection's box by `flip` (None, "h", "v" or "hv"),
+        and the place they came from is filled.  Everything happens on the device under ONE hold of the session's lock:
+          1. the LIFT: the rectangle move_rect(box, (0, 0)) of the frame is saved into a scratch slot (not a journal entry), so the
+             object's pixels are the ORIGINAL ones whatever the next step does, and source and destination may overlap freely;
+          2. unless `keep_source`, the HOLE -- the selection grown by `hole_grow` (0 .. 16) pixels, to cover the object's soft edge
+             -- is filled exactly as fill_selection fills a selection: netG alone through choose_window of the grown box at
+             `margin`, or `window` as given, with `max_side`, the lock plane and `feather` as there;
+          3. the DROP: the lifted pixels are written at the destination, always at frame scale and always exact, whatever
+             `max_side` is: a plain copy, or with `feather` = r the blend of the feathered paste, c / n of the object and
+             (n - c) / n of the frame, c counted on the moved selection alone (an object pushed partly over the frame's edge
+             does not fade towards the edge);
+          4. the moved SELECTION is made: the selection's plane shifted the same way, with its box and count -- the call's one
+             extra download.  What leaves the frame is dropped; the selection that was passed in stays what it was.
+        Locked source pixels are not filled; they are still copied.  Locked destination pixels never change.
+        -> (patches, positions, info) in edit_regions' shape over [fill window, destination rectangle] (the destination
+        rectangle, move_rect(box, offset), alone with `keep_source`); `encode` applies to each patch.  info = dict(windows,
+        move=True, offset, flip, selected, selection=the moved Selection) plus work / undoable / locked / feather where `fill`
+        reports them.  With history on the call is ONE undo step: each rectangle is saved in front of its own step and the entry
+        holds both slots, exchanged in reverse order by `undo` and in forward order by `redo`, since the two may overlap; if
+        the slots exceed `history_bytes` together the move commits unjournalled and clears the history.  A backend call that
+        fails once the frame was written clears the history too: no entry could restore a state the frame was in.
+        clone_selection(...) is move_selection(..., keep_source=True).
+        TypeError / ValueError, all before the first backend call: a selection that is none, of another frame size or empty, an
+        offset that is not two ints or is above the limit, one that moves the whole selection out of the frame, a bad flip,
+        hole_grow, window, max_side, encode or feather."""
+        encode = _check_encode(encode)
+        feather = _check_feather(feather)
+        self._check_selection(selection, "move_selection")
+        if selection.box is None:
+            raise ValueError("empty selection: nothing to move")
+        try:
+            dy, dx = offset
+        except (TypeError, ValueError):
+            raise ValueError("offset is (dy, dx), two ints (got %r)" % (offset,))
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and abs(int(v)) <= MOVE_MAX_OFFSET for v in (dy, dx)):
+            raise ValueError("offset is (dy, dx), two ints of at most %d in magnitude (got %r)" % (MOVE_MAX_OFFSET, offset))
+        offset = (int(dy), int(dx))
+        if not (flip is None or isinstance(flip, str)) or flip not in MOVE_FLIPS:
+            raise ValueError("flip is None, 'h', 'v' or 'hv' (got %r)" % (flip,))
+        if not isinstance(hole_grow, (int, np.integer)) or isinstance(hole_grow, (bool, np.bool_)) or not 0 <= hole_grow <= SELECT_MAX_GROW:
+            raise ValueError("hole_grow is an int 0 .. %d, in frame pixels (got %r)" % (SELECT_MAX_GROW, hole_grow))
+        hole_grow = int(hole_grow)
+        Hi, Wi = self.frame_hw
+        box = selection.box
+        dst = move_rect(box, offset, self.frame_hw)
+        if dst is None:
+            raise ValueError("offset %r moves the whole selection out of the frame" % (offset,))
+        grown = (max(box[0] - hole_grow, 0), max(box[1] - hole_grow, 0), min(box[2] + hole_grow, Hi), min(box[3] + hole_grow, Wi))
+        self._check_fill_args(grown, None, window, margin, max_side)
+        win = None if keep_source else self._fill_window(grown, window, margin, max_side)
+        wins = ([] if win is None else [win]) + [dst]
+        journal = self.history > 0 and (self.history_bytes is None or
+                                        sum(window_saved_bytes(w[2], w[3]) for w in wins) <= self.history_bytes)
+        be = self.backend
+        with self._lock:
+            frames = [self._frame]
+            lift_rect = move_rect(box, (0, 0), self.frame_hw)
+            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
+            slots, work, pasted = [], None, False
+            try:
+                if win is not None:
+                    hole = selection.plane if hole_grow == 0 else be.grow(selection.plane, hole_grow)
+                    slot, work, _ = self._fill_steps(hole, None, win, low_latency, max_side, feather, journal)
+                    slots.append(slot)
+                    pasted = True
+                if journal:
+                    slots.append(be.save(frames, [dst[:2]], dst[2:])[0])
+                be.move_drop(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, offset, MOVE_FLIPS[flip], feather or 0)
+                pasted = True
+                plane, mbox, count = be.shift(selection.plane, box, offset, MOVE_FLIPS[flip])
+            except Exception:
+                if pasted:                       # the fill or the drop is in the frame: no entry restores a state it was in
+                    self._undo.clear()
+                    self._redo.clear()
+                raise
+            # the moved selection exists before the step is recorded: a caller who gets an entry gets the selection too
+            undoable = self._record_sequence(wins, slots if journal else None) if self.history > 0 else None
+            moved = Selection(be, plane, mbox, count, self.frame_hw)
+            patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames * len(wins), wins)
+            locked = self._lock_plane is not None
+        info = dict(windows=wins, move=True, offset=offset, flip=flip, selected=selection.count, selection=moved)
+        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, work, undoable, feather)
+
+    def clone_selection(self, selection, offset, **kw):
+        """move_selection(selection, offset, keep_source=True, ...): a copy of the selected pixels lands `offset`
+        away and the source stays what it is -- no forward runs; ONE undo step over the destination rectangle."""
+        kw["keep_source"] = True
+        return self.move_selection(selection, offset, **kw)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""
@@ -1722,8 +1901,9 @@ class BatchingServer:
         return outs
 
     def _run_history(self, group):
-        """One group of undo / redo requests, each of another session (_candidates): one swap launch per window size.  A
-        request with nothing to undo / redo fails alone (IndexError)."""
+        """One group of undo / redo requests, each of another session (_candidates): one swap launch per window size; a region
+        edit's or a move's entry takes the session's own exchange.  A request with nothing to undo / redo fails alone
+        (IndexError)."""
         reqs = [q[1] for q in group]
         be = reqs[0]["session"].backend
         outs = [None] * len(reqs)
@@ -1738,6 +1918,8 @@ class BatchingServer:
                 if not stacks[i][0]:
                     group[i][3]["err"] = IndexError("nothing to " + r["op"])
                     outs[i] = False
+                elif isinstance(stacks[i][0][-1][0], _Sequence):     # a move's entry: the session's own ordered exchange
+                    outs[i] = s._exchange_sequence(*stacks[i], r["op"] == "undo")
                 elif isinstance(stacks[i][0][-1][0], _Regions):      # a region edit's entry: the session's own exchange
                     outs[i] = s._exchange_regions(*stacks[i])
                 else:

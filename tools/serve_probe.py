@@ -159,6 +159,20 @@ plus the host route's two parts timed alone, select_lasso and a combine alone, t
 plus the parts timed alone (select_similar, rings(), edges(), mask(), the two host linkings, a combine for 6p's comparison), the
 bytes each route downloads, whether the two routes' rings are equal, and the in-library profile of one rings() call:
     python tools/serve_probe.py --outline [--reps N] [--out FILE]
+
+--move: move a selection: --select's disc on a 1921x1081 frame, selected by colour once (not timed), moved by
+(150, 300) with its hole filled through the 512 x 512 window of --fill; the frame is put back (a device copy, not timed) in front
+of every timed call:
+  (a) edit:       EditSession.edit(window=..., max_grow=0), the unchanged control (run with --move-parent on the parent commit's
+                  build: only this leg),
+  (b) move:       EditSession.move_selection(selection, (150, 300), window=...) -- lift, grow, fill, drop, shift and the tile
+                  records on the device; the two patches come down,
+  (c) host_route: session.frame() (the 6 MB download), the disc's pixels copied to the destination in numpy, a NEW session of the
+                  result (the 6 MB upload), EditSession.fill(grown mask, window=...) (the 2 MB upload) -- what a front end does
+                  without move_selection, and it loses the undo journal on the way,
+plus the parts timed alone (fill_selection of the grown selection, a combine, clone_selection, the move with history on and its
+undo), and se_profile_report's per-kernel times of one (b) request:
+    python tools/serve_probe.py --move [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -1123,6 +1137,102 @@ def outline_leg(model, reps, parent=False, side=512, tolerance=16):
     return out
 
 
+def move_leg(model, reps, parent=False, side=512, tolerance=16, offset=(150, 300)):
+    """(a), (b), (c) of the module docstring; parent=True: the leg (a) only, with the calls a build without moves has"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    frame[..., 0] = frame[..., 0] % 90                               # no noise pixel is similar to the disc's colour
+    win = (283, 705, side, side)
+    seed = (win[0] + side // 2, win[1] + side // 2)
+    yy, xx = np.mgrid[0:h, 0:w]
+    disc = (yy - seed[0]) ** 2 + (xx - seed[1]) ** 2 <= 126 ** 2
+    frame[disc] = 128
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    dev0 = torch.from_numpy(frame).cuda()
+
+    def fresh(session):
+        def put_back():
+            session._frame.copy_(dev0)
+            torch.cuda.synchronize()
+        return put_back
+
+    def timed(fn, put_back=lambda: None):
+        def rounds():
+            for _ in range(2):                 # warm-up: plans, workspace, code objects
+                put_back()
+                fn()
+            ts = []
+            for _ in range(reps):
+                put_back()
+                t0 = time.perf_counter()
+                fn()                           # ends in a device-to-host copy: the request is complete
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts.sort()
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    s1 = serve.EditSession(model, frame)
+    legs = dict(edit=timed(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True), fresh(s1)))
+    out = dict(tool="serve_probe --move" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               window=list(win), seed=list(seed), tolerance=tolerance, offset=list(offset), disc_pixels=int(disc.sum()))
+    if not parent:
+        s2, s3, s4 = serve.EditSession(model, frame), serve.EditSession(model, frame), serve.EditSession(model, frame, history=4)
+        sel = s2.select_similar(seed, tolerance=tolerance)
+        grown = s2.select_similar(seed, tolerance=tolerance, grow=2)
+        other = s2.select_lasso([[(seed[1] - 40.0, seed[0] - 40.0), (seed[1] + 90.0, seed[0] - 30.0), (seed[1] + 10.0, seed[0] + 95.0)]])
+        sel4 = s4.select_similar(seed, tolerance=tolerance)
+        dy, dx = offset
+
+        def host_route():
+            f = s3.frame()
+            mask = (np.abs(f.astype(np.int16) - f[seed]).max(axis=2) <= tolerance)          # (the disc: no flood on this route)
+            ys, xs = np.nonzero(mask)
+            f[ys + dy, xs + dx] = f[ys, xs]
+            hole = np.zeros((h, w), bool)
+            for ey in range(-2, 3):            # the grow by 2, as shifts
+                for ex in range(-2, 3):
+                    hole[max(ey, 0):h + min(ey, 0), max(ex, 0):w + min(ex, 0)] |= mask[max(-ey, 0):h + min(-ey, 0), max(-ex, 0):w + min(-ex, 0)]
+            return serve.EditSession(model, f).fill(hole, window=win, low_latency=True)
+
+        def journalled():
+            s4.move_selection(sel4, offset, window=win, low_latency=True)
+            s4.undo()
+        legs.update(move=timed(lambda: s2.move_selection(sel, offset, window=win, low_latency=True), fresh(s2)),
+                    host_route=timed(host_route, fresh(s3)))
+        parts = dict(fill_selection=timed(lambda: s2.fill_selection(grown, window=win, low_latency=True), fresh(s2)),
+                     combine=timed(lambda: s2.combine(sel, other, "subtract").count),
+                     clone_selection=timed(lambda: s2.clone_selection(sel, offset), fresh(s2)),
+                     clone_selection_feather8=timed(lambda: s2.clone_selection(sel, offset, feather=8), fresh(s2)),
+                     move_and_undo_with_history=timed(journalled, fresh(s4)))
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    if not parent:
+        out["parts_ms"] = {k: fn() for k, fn in parts.items()}
+        eng = model.engine()
+        fresh(s2)()
+        eng.profile(True)
+        _, _, info = s2.move_selection(sel, offset, window=win, low_latency=True)
+        rep = eng.profile_report()
+        eng.profile(False)
+        ks = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        fill_plus_combine = out["parts_ms"]["fill_selection"]["median"] + out["parts_ms"]["combine"]["median"]
+        out.update(selected=sel.count, box=list(sel.box), windows=[list(v) for v in info["windows"]], moved_box=list(info["selection"].box),
+                   moved_count=info["selection"].count, move_profiled={k: v for k, v in ks.items() if v["ms"] >= 0.001},
+                   move_minus_host_route_ms=round(out["ms"]["move"]["median"] - out["ms"]["host_route"]["median"], 3),
+                   fill_selection_plus_combine_ms=round(fill_plus_combine, 3),
+                   move_minus_fill_selection_plus_combine_ms=round(out["ms"]["move"]["median"] - fill_plus_combine, 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -1152,6 +1262,8 @@ def main():
     ap.add_argument("--lasso-parent", action="store_true", help="the edit leg of --lasso only")
     ap.add_argument("--outline", action="store_true", help="the outline of a selection (see the module docstring)")
     ap.add_argument("--outline-parent", action="store_true", help="the edit leg of --outline only")
+    ap.add_argument("--move", action="store_true", help="move a selection (see the module docstring)")
+    ap.add_argument("--move-parent", action="store_true", help="the edit leg of --move only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -1163,8 +1275,11 @@ def main():
     if (args.window or args.window_scaled or args.window_history or args.window_history_parent or args.window_lock or args.window_lock_parent
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
-            or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent):
-        if args.outline or args.outline_parent:
+            or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent
+            or args.move or args.move_parent):
+        if args.move or args.move_parent:
+            res = move_leg(model, args.reps, parent=args.move_parent)
+        elif args.outline or args.outline_parent:
             res = outline_leg(model, args.reps, parent=args.outline_parent)
         elif args.lasso or args.lasso_parent:
             res = lasso_leg(model, args.reps, parent=args.lasso_parent)
