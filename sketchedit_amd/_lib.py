@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_move.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_move.hip", "se_warp.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
            "se_plan.hip", "se_api_window.hip", "se_api_select.hip", "se_api_move.hip", "se_api_codec.hip", "se_api_debug.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
@@ -73,6 +73,9 @@ OUTLINE_TILE, OUTLINE_MAX_CAP = 64, 1 << 24       # SE_OUTLINE_TILE, SE_OUTLINE_
 MOVE_SYMBOLS = ["se_move_drop_u8", "se_plane_shift_u8"]
 MOVE_MAX_OFFSET, MOVE_MAX_RADIUS = 16384, 16      # SE_MOVE_MAX_OFFSET, SE_MOVE_MAX_RADIUS
 MOVE_FLIP_X, MOVE_FLIP_Y = 1, 2                   # SE_MOVE_FLIP_*
+# every symbol declared in include/sketchedit_warp.h (scale and rotate a selection)
+WARP_SYMBOLS = ["se_warp_drop_u8", "se_plane_warp_u8"]
+WARP_MAX_COEF, WARP_MAX_TRANSLATION = 1 << 20, 1 << 40      # SE_WARP_MAX_COEF, SE_WARP_MAX_TRANSLATION
 
 
 class SketchEditHipError(RuntimeError):
@@ -298,6 +301,10 @@ def load_library():
         lib.se_move_drop_u8.restype = ci
         lib.se_plane_shift_u8.argtypes = [vp, vp, vp, ci, ci] + [ci] * 7 + [vp]
         lib.se_plane_shift_u8.restype = ci
+        lib.se_warp_drop_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8 + [vp]
+        lib.se_warp_drop_u8.restype = ci
+        lib.se_plane_warp_u8.argtypes = [vp, vp, vp, ci, ci] + [ci] * 4 + [vp, vp]
+        lib.se_plane_warp_u8.restype = ci
         lib.se_outline_u8_workspace_bytes.argtypes = [vp, ci, ci]
         lib.se_outline_u8_workspace_bytes.restype = sz
         lib.se_outline_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, sz]
@@ -1216,6 +1223,58 @@ class Engine:
         if self.lib.se_plane_shift_u8(self.h, self._stream(), _ptr(sel), Hi, Wi, by0, bx0, by1, bx1, int(offset[0]), int(offset[1]), int(flip),
                                       _ptr(out)):
             self._err("se_plane_shift_u8")
+        return out
+
+    # ---- scale and rotate a selection (include/sketchedit_warp.h) ------------------------------------------------------
+    @staticmethod
+    def _warp_map(m, what):
+        """the six Q16 ints of an inverse map -> a host array of six long long"""
+        try:
+            vals = [int(v) for v in m]
+        except (TypeError, ValueError):
+            vals = []
+        if len(vals) != 6 or any(abs(v) >= 1 << 63 for v in vals):
+            raise SketchEditHipError("%s: m is six ints (ayy, ayx, ay0, axy, axx, ax0) in Q16" % what)
+        return (ctypes.c_longlong * 6)(*vals)
+
+    def warp_drop_u8(self, frame, lift, lift_rect, sel, lock, box, rect, m):
+        """se_warp_drop_u8, in place on `frame` (Hi,Wi,3) uint8 on the device: the pixels of `box` = (by0, bx0, by1, bx1) that
+        `sel` (an (Hi,Wi) plane, non-zero = selected) selects, as `lift` holds them -- the journal slot window_save_u8 made of
+        `lift_rect` = (ly0, lx0, lh, lw), a rectangle that holds the box -- gathered through the inverse map `m` (six Q16 ints)
+        with bilinear taps and blended by their coverage into `rect` = (ry0, rx0, rh, rw) of the frame where `lock` (a plane or
+        None) is 0.  No other byte changes.  One launch."""
+        _check_dev_u8(frame)
+        if frame.dim() != 3 or frame.shape[2] != 3:
+            raise SketchEditHipError("warp_drop_u8: a frame is an (Hi,Wi,3) uint8 tensor")
+        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
+        if self._state_plane(sel, "warp_drop_u8: sel") != (Hi, Wi) or (lock is not None and self._state_plane(lock, "warp_drop_u8: lock") != (Hi, Wi)):
+            raise SketchEditHipError("warp_drop_u8: sel and lock are the frame's (Hi,Wi) planes")
+        ly0, lx0, lh, lw = (int(v) for v in lift_rect)
+        _check_dev_u8(lift)
+        need = self.window_saved_bytes(lh, lw)
+        if need and lift.numel() < need:
+            raise SketchEditHipError("warp_drop_u8: a lift holds window_saved_bytes(lh, lw) = %d bytes" % need)
+        by0, bx0, by1, bx1 = (int(v) for v in box)
+        ry0, rx0, rh, rw = (int(v) for v in rect)
+        mm = self._warp_map(m, "warp_drop_u8")
+        if self.lib.se_warp_drop_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
+                                    by0, bx0, by1, bx1, ry0, rx0, rh, rw, mm):
+            self._err("se_warp_drop_u8")
+
+    def plane_warp_u8(self, sel, box, m, out=None):
+        """se_plane_warp_u8: `sel` (Hi,Wi) uint8 on the device, non-zero = selected -> `out` (a new plane, or another plane of
+        that shape at any alignment; every byte is written), 255 where the selected pixels of `box` = (by0, bx0, by1, bx1),
+        gathered through the inverse map `m` as warp_drop_u8 gathers them, cover at least half a pixel, else 0."""
+        import torch
+        Hi, Wi = self._state_plane(sel, "plane_warp_u8: sel")
+        if out is None:
+            out = torch.empty((Hi, Wi), dtype=torch.uint8, device=sel.device)
+        if self._state_plane(out, "plane_warp_u8: out") != (Hi, Wi):
+            raise SketchEditHipError("plane_warp_u8: out is a plane of sel's shape")
+        by0, bx0, by1, bx1 = (int(v) for v in box)
+        mm = self._warp_map(m, "plane_warp_u8")
+        if self.lib.se_plane_warp_u8(self.h, self._stream(), _ptr(sel), Hi, Wi, by0, bx0, by1, bx1, mm, _ptr(out)):
+            self._err("se_plane_warp_u8")
         return out
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------

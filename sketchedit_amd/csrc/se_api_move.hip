@@ -1,6 +1,8 @@
 // The editing sessions' move entries behind include/sketchedit_move.h: the drop of a lifted selection and the shift of its plane
-// (kernels: se_move.hip).
+// (kernels: se_move.hip); and behind include/sketchedit_warp.h the drop through an affine map and the warp
+// of the plane (kernels: se_warp.hip).
 #include "../../include/sketchedit_move.h"
+#include "../../include/sketchedit_warp.h"
 #include "se_host.h"
 
 using namespace se;
@@ -31,6 +33,20 @@ int move_check_map(se_ctx* c, int by0, int bx0, int by1, int bx1, int ry0, int r
   if (dy < -SE_MOVE_MAX_OFFSET || dy > SE_MOVE_MAX_OFFSET) return fail(c, "bad dy=%d (|dy| <= %d)", dy, SE_MOVE_MAX_OFFSET);
   if (dx < -SE_MOVE_MAX_OFFSET || dx > SE_MOVE_MAX_OFFSET) return fail(c, "bad dx=%d (|dx| <= %d)", dx, SE_MOVE_MAX_OFFSET);
   if (flip < 0 || flip > 3) return fail(c, "bad flip=%d (0 .. 3)", flip);
+  return 0;
+}
+
+// the box against the rectangle that must hold it, and the six values of the inverse map (a host pointer)
+int warp_check_map(se_ctx* c, int by0, int bx0, int by1, int bx1, int ry0, int rx0, int rh, int rw, const char* holder, const long long* m) {
+  if (move_check_map(c, by0, bx0, by1, bx1, ry0, rx0, rh, rw, holder, 0, 0, 0)) return 1;
+  if (!m) return fail(c, "null pointer argument: m");
+  static const char* const names[6] = {"ayy", "ayx", "ay0", "axy", "axx", "ax0"};
+  for (int i = 0; i < 6; ++i) {
+    const bool tr = i == 2 || i == 5;
+    const long long lim = tr ? SE_WARP_MAX_TRANSLATION : (long long)SE_WARP_MAX_COEF;
+    if (m[i] < -lim || m[i] > lim)
+      return fail(c, "bad m: %s=%lld (a %s is at most %lld in magnitude)", names[i], m[i], tr ? "translation" : "coefficient", lim);
+  }
   return 0;
 }
 
@@ -73,6 +89,48 @@ int se_plane_shift_u8(se_ctx* c, void* stream, const unsigned char* sel_u8, int 
   if (overlaps(plane_out, pn, sel_u8, pn)) return fail(c, "plane_out overlaps sel_u8");
   if (device_enter(c)) return 1;
   HIPCHK(c, launch_plane_shift(sel_u8, Hi, Wi, by0, bx0, by1, bx1, dy, dx, flip, plane_out, (hipStream_t)stream));
+  return 0;
+}
+
+int se_warp_drop_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh,
+                    int lw, const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, int ry0, int rx0,
+                    int rh, int rw, const long long* m) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!frame_u8) return fail(c, "null pointer argument: frame_u8");
+  if (!lift) return fail(c, "null pointer argument: lift");
+  if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
+  if (move_check_frame(c, Hi, Wi)) return 1;
+  if (lh < 16 || lw < 16) return fail(c, "bad lift rectangle lh=%d lw=%d (a side is at least 16)", lh, lw);
+  if (ly0 < 0 || lx0 < 0 || lh > Hi || lw > Wi || ly0 > Hi - lh || lx0 > Wi - lw)
+    return fail(c, "the lift rectangle (ly0=%d lx0=%d, %d x %d) lies outside the frame (Hi=%d Wi=%d)", ly0, lx0, lh, lw, Hi, Wi);
+  if (!aligned_to(lift, 16)) return fail(c, "lift must be 16-byte aligned");
+  if (warp_check_map(c, by0, bx0, by1, bx1, ly0, lx0, lh, lw, "lift rectangle", m)) return 1;
+  if (rh <= 0 || rw <= 0) return fail(c, "bad destination rectangle rh=%d rw=%d: it is not empty", rh, rw);
+  if (ry0 < 0 || rx0 < 0 || rh > Hi || rw > Wi || ry0 > Hi - rh || rx0 > Wi - rw)
+    return fail(c, "the destination rectangle (ry0=%d rx0=%d, %d x %d) lies outside the frame (Hi=%d Wi=%d)", ry0, rx0, rh, rw, Hi, Wi);
+  const size_t pn = (size_t)Hi * Wi, lpitch = ((size_t)3 * lw + 15) & ~(size_t)15, ln = (size_t)lh * lpitch;
+  if (overlaps(lift, ln, frame_u8, 3 * pn)) return fail(c, "lift overlaps frame_u8");
+  if (overlaps(sel_u8, pn, frame_u8, 3 * pn)) return fail(c, "sel_u8 overlaps frame_u8");
+  if (lock_u8 && overlaps(lock_u8, pn, frame_u8, 3 * pn)) return fail(c, "lock_u8 overlaps frame_u8");
+  if (device_enter(c)) return 1;
+  HIPCHK(c, launch_warp_drop(frame_u8, Hi, Wi, lift, ly0, lx0, lw, (int)lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, ry0, rx0, rh, rw, m,
+                             (hipStream_t)stream));
+  return 0;
+}
+
+int se_plane_warp_u8(se_ctx* c, void* stream, const unsigned char* sel_u8, int Hi, int Wi, int by0, int bx0, int by1, int bx1,
+                     const long long* m, unsigned char* plane_out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
+  if (!plane_out) return fail(c, "null pointer argument: plane_out");
+  if (move_check_frame(c, Hi, Wi)) return 1;
+  if (warp_check_map(c, by0, bx0, by1, bx1, 0, 0, Hi, Wi, "frame", m)) return 1;
+  const size_t pn = (size_t)Hi * Wi;
+  if (overlaps(plane_out, pn, sel_u8, pn)) return fail(c, "plane_out overlaps sel_u8");
+  if (device_enter(c)) return 1;
+  HIPCHK(c, launch_plane_warp(sel_u8, Hi, Wi, by0, bx0, by1, bx1, m, plane_out, (hipStream_t)stream));
   return 0;
 }
 

@@ -23,7 +23,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
                  PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW,
                  PL_LASSO_FILL, PL_PLANE_COMBINE, PL_OUTLINE_COUNT, PL_OUTLINE_SCAN, PL_OUTLINE_EMIT, PL_MOVE_DROP,
-                 PL_PLANE_SHIFT, PL_COUNT };
+                 PL_PLANE_SHIFT, PL_WARP_DROP, PL_PLANE_WARP, PL_COUNT };
 const char* prof_label_name(int l);
 // Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
 // know which kernel the dispatcher chose; the label's name where the launcher has one form only
@@ -474,6 +474,15 @@ hipError_t launch_move_drop(unsigned char* frame, int Hi, int Wi, const unsigned
                             int radius, hipStream_t st);
 hipError_t launch_plane_shift(const unsigned char* sel, int Hi, int Wi, int by0, int bx0, int by1, int bx1, int dy, int dx, int flip,
                               unsigned char* out, hipStream_t st);
+// scale and rotate a selection (include/sketchedit_warp.h; se_warp.hip).  Any Hi, Wi >= 16 and any alignment of the
+// frame and the planes.  m: the six Q16 values of the inverse map, on the host.  warp_drop: the selected pixels of the box, as
+// the lift holds them, gathered through m with bilinear taps and blended by their coverage into the rectangle (ry0, rx0, rh, rw)
+// of the frame, whose tiles are the grid.  plane_warp: every byte of `out` <- 255 where the coverage is at least a half, else 0.
+hipError_t launch_warp_drop(unsigned char* frame, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lw, int lpitch,
+                            const unsigned char* sel, const unsigned char* lock, int by0, int bx0, int by1, int bx1, int ry0, int rx0,
+                            int rh, int rw, const long long* m, hipStream_t st);
+hipError_t launch_plane_warp(const unsigned char* sel, int Hi, int Wi, int by0, int bx0, int by1, int bx1, const long long* m,
+                             unsigned char* out, hipStream_t st);
 // the device PNG encoder (include/sketchedit_png.h): the hs x ws rectangles of d_wins (B records) -> their zlib
 // streams.  rows: ftype (B,hs) uint8, each row's filter type.  stripes: one workgroup per stripe of 32 rows -> its deflate blocks
 // in its slot of png_slot_bytes(ws) bytes (16-byte aligned), its size in sizes (B,S) and its Adler parts in parts (B,S,2), S =

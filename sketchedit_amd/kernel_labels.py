@@ -55,6 +55,9 @@ KERNEL_LABELS = {
     "(anonymous namespace)::move_drop_kernel<false>": "move_drop", "(anonymous namespace)::move_drop_kernel<true>": "move_drop",
     "(anonymous namespace)::plane_shift_kernel": "plane_shift",
     "move_drop_kernel<false>": "move_drop", "move_drop_kernel<true>": "move_drop", "plane_shift_kernel": "plane_shift",
+    # scale and rotate a selection (se_warp.hip): the resampling drop, and the warp of the plane
+    "(anonymous namespace)::warp_drop_kernel": "warp_drop", "(anonymous namespace)::plane_warp_kernel": "plane_warp",
+    "warp_drop_kernel": "warp_drop", "plane_warp_kernel": "plane_warp",
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",

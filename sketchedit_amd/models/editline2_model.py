@@ -245,6 +245,16 @@ class EditLine2Model(torch.nn.Module):
         """A selection plane moved as move_drop_u8 moves its pixels: a new 0 / 255 plane (Engine.plane_shift_u8)."""
         return self.engine().plane_shift_u8(sel, box, offset, flip=flip, out=out)
 
+    def warp_drop_u8(self, frame, lift, lift_rect, sel, lock, box, rect, m):
+        """The drop of a scaled or turned selection (serve.EditSession.transform_selection is the caller-facing
+        form): the selected pixels of `box`, as the journal slot `lift` of `lift_rect` holds them, gathered through the inverse
+        map `m` and blended into `rect` of the resident frame (Engine.warp_drop_u8)."""
+        self.engine().warp_drop_u8(frame, lift, lift_rect, sel, lock, box, rect, m)
+
+    def plane_warp_u8(self, sel, box, m, out=None):
+        """A selection plane warped as warp_drop_u8 warps its pixels: a new 0 / 255 plane (Engine.plane_warp_u8)."""
+        return self.engine().plane_warp_u8(sel, box, m, out=out)
+
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
         slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""

@@ -5,8 +5,10 @@ with one worker per GPU when several models are given.
 
 No web framework here -- the Flask UI is out of scope; these are the pieces of it that touch the hot path.
 """
+import math
 import threading
 import time
+from fractions import Fraction
 
 import numpy as np
 
@@ -406,6 +408,113 @@ def move_rect(box, offset, frame_hw):
     return None if ya is None or xa is None else (ya[0], xa[0], ya[1], xa[1])
 
 
+WARP_ONE = 1 << 16                   # 1.0 in the Q16 of a warp's inverse map
+WARP_MAX_COEF = 1 << 20              # SE_WARP_MAX_COEF
+WARP_MAX_TRANSLATION = 1 << 40       # SE_WARP_MAX_TRANSLATION
+WARP_MIN_SCALE, WARP_MAX_SCALE = 0.125, 8.0
+
+
+def _warp_number(v, what):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+        raise ValueError("%s is a finite number (got %r)" % (what, v))
+    return float(v)
+
+
+def warp_matrix(box, scale=1.0, angle=0.0, offset=(0, 0), flip=None):
+    """The inverse map of a scale, a turn, a mirror and an offset of a selection's box, as six ints in Q16 (pure host arithmetic,
+    exact and the same on every machine): (ayy, ayx, ay0, axy, axx, ax0) take a destination pixel (y, x) to its
+    source position sy = ayy y + ayx x + ay0, sx = axy y + axx x + ax0, where k << 16 is the centre of source row or column k.
+    The forward map turns the object by `angle` degrees, counter-clockwise on the screen, about the centre c of `box` =
+    (y0, x0, y1, x1), half open; scales it by `scale`, a number or a (sy, sx) pair, each in 1/8 .. 8, along the object's own axes;
+    mirrors it by `flip` (None, "h", "v" or "hv", about the box as move_selection mirrors) and puts the centre at c + `offset` =
+    (dy, dx), ints or floats that are quantised to half pixels -- a quarter turn of a box whose sides differ in parity leaves
+    the object half a pixel off the grid, and a front end cancels that with an offset of one half.  The inverse's linear part is
+    Fl diag(1 / sy, 1 / sx) R^T, each entry round(float64 * 65536) with the cosine and sine of a multiple of 90 degrees taken as
+    exactly 0 and +-1; the translation is made from doubled coordinates in integers.  Below a scale of 1/2 the bilinear taps
+    undersample: there is no prefilter and no claim of quality, as with max_side.  ValueError for a bad argument."""
+    try:
+        by0, bx0, by1, bx1 = (int(v) for v in box)
+    except (TypeError, ValueError):
+        raise ValueError("box is (y0, x0, y1, x1) (got %r)" % (box,))
+    if by1 <= by0 or bx1 <= bx0:
+        raise ValueError("box (y0, x0, y1, x1) is half open and not empty (got %r)" % (box,))
+    if isinstance(scale, (tuple, list)):
+        if len(scale) != 2:
+            raise ValueError("scale is a number or a (sy, sx) pair (got %r)" % (scale,))
+        scy, scx = _warp_number(scale[0], "scale"), _warp_number(scale[1], "scale")
+    else:
+        scy = scx = _warp_number(scale, "scale")
+    if not (WARP_MIN_SCALE <= scy <= WARP_MAX_SCALE and WARP_MIN_SCALE <= scx <= WARP_MAX_SCALE):
+        raise ValueError("scale lies in 1/8 .. 8 (got %r)" % (scale,))
+    angle = _warp_number(angle, "angle")
+    try:
+        dy, dx = offset
+    except (TypeError, ValueError):
+        raise ValueError("offset is (dy, dx), two numbers (got %r)" % (offset,))
+    dy, dx = _warp_number(dy, "offset"), _warp_number(dx, "offset")
+    if abs(dy) > MOVE_MAX_OFFSET or abs(dx) > MOVE_MAX_OFFSET:
+        raise ValueError("offset is (dy, dx), at most %d in magnitude (got %r)" % (MOVE_MAX_OFFSET, offset))
+    if not (flip is None or isinstance(flip, str)) or flip not in MOVE_FLIPS:
+        raise ValueError("flip is None, 'h', 'v' or 'hv' (got %r)" % (flip,))
+    quarter = angle % 360.0
+    if quarter % 90.0 == 0.0:
+        cos, sin = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(quarter // 90.0)]
+    else:
+        cos, sin = math.cos(math.radians(angle)), math.sin(math.radians(angle))
+    fy, fx = (-1.0 if MOVE_FLIPS[flip] & 2 else 1.0), (-1.0 if MOVE_FLIPS[flip] & 1 else 1.0)
+    ayy, ayx = round(fy * (1.0 / scy) * cos * WARP_ONE), round(fy * (1.0 / scy) * sin * WARP_ONE)
+    axy, axx = round(fx * (1.0 / scx) * -sin * WARP_ONE), round(fx * (1.0 / scx) * cos * WARP_ONE)
+    cy2, cx2 = by0 + by1 - 1, bx0 + bx1 - 1                            # the centre, doubled
+    dy2, dx2 = cy2 + round(2 * dy), cx2 + round(2 * dx)                # where it lands, doubled
+    return (ayy, ayx, (cy2 * WARP_ONE - (ayy * dy2 + ayx * dx2)) >> 1, axy, axx, (cx2 * WARP_ONE - (axy * dy2 + axx * dx2)) >> 1)
+
+
+def _check_warp_map(m):
+    """six ints within the limits of include/sketchedit_warp.h -> a tuple of Python ints"""
+    try:
+        vals = tuple(m)
+    except TypeError:
+        raise TypeError("matrix is six ints (ayy, ayx, ay0, axy, axx, ax0) in Q16 (got %r)" % (m,))
+    if len(vals) != 6 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in vals):
+        raise ValueError("matrix is six ints (ayy, ayx, ay0, axy, axx, ax0) in Q16 (got %r)" % (m,))
+    vals = tuple(int(v) for v in vals)
+    if any(abs(vals[i]) > WARP_MAX_COEF for i in (0, 1, 3, 4)) or any(abs(vals[i]) > WARP_MAX_TRANSLATION for i in (2, 5)):
+        raise ValueError("matrix: a coefficient is at most 2^20 and a translation at most 2^40 in magnitude (got %r)" % (vals,))
+    return vals
+
+
+def warp_rect(box, m, frame_hw):
+    """The rectangle of the frame a warped selection lands in (pure host arithmetic in exact integers and fractions; DESIGN.md
+    6s): no pixel outside it has a tap with weight inside `box` = (y0, x0, y1, x1) under the inverse map `m` (six Q16 ints).  A
+    pixel has one only where its source position lies in [y0 - 1, y1] x [x0 - 1, x1]; the forward image of that rectangle's four
+    corners under the inverse of `m` bounds those pixels: floor of the minimum to ceil of the maximum, plus one.  Clipped to the
+    frame of `frame_hw` = (Hi, Wi), and a side under 16 widened to 16 inside the frame exactly as move_rect widens it.
+    -> (y0, x0, h, w), or None when nothing lands in the frame.  ValueError for a singular `m`."""
+    by0, bx0, by1, bx1 = (int(v) for v in box)
+    ayy, ayx, ay0, axy, axx, ax0 = (int(v) for v in m)
+    det = ayy * axx - ayx * axy
+    if det == 0:
+        raise ValueError("the map %r is singular" % (tuple(m),))
+    ys, xs = [], []
+    for qy in (by0 - 1, by1):
+        for qx in (bx0 - 1, bx1):
+            u, v = qy * WARP_ONE - ay0, qx * WARP_ONE - ax0
+            ys.append(Fraction(axx * u - ayx * v, det))
+            xs.append(Fraction(ayy * v - axy * u, det))
+
+    def axis(vals, extent):
+        lo, hi = max(math.floor(min(vals)), 0), min(math.ceil(max(vals)) + 1, extent)
+        if hi <= lo:
+            return None
+        if hi - lo < MOVE_MIN_SIDE:
+            lo = min(max(lo - (MOVE_MIN_SIDE - (hi - lo)) // 2, 0), extent - MOVE_MIN_SIDE)
+            hi = lo + MOVE_MIN_SIDE
+        return lo, hi - lo
+
+    ya, xa = axis(ys, int(frame_hw[0])), axis(xs, int(frame_hw[1]))
+    return None if ya is None or xa is None else (ya[0], xa[0], ya[1], xa[1])
+
+
 def png_from_zlib(stream, h, w):
     """The PNG file around a zlib stream of filtered 8-bit RGB rows: signature, IHDR, ONE IDAT holding
     `stream` as it is, IEND -- the chunk framing and its CRCs are the host's part of a patch that was encoded on the device."""
@@ -785,6 +894,18 @@ class _ModelBackend:
         """a selection's plane moved as move_drop moves its pixels -> (plane, box, count) of a NEW plane: one
         launch, then the tile records of the result -- the one download"""
         out = self.model.plane_shift_u8(plane, box, offset, flip=flip)
+        b, count = tiles_box(self.tiles(out, 32))
+        return out, b, count
+
+    def warp_drop(self, frame, lift, lift_rect, plane, lock, box, rect, m):
+        """the drop of a transform, ONE launch in place on the frame: the pixels of `box` that `plane` selects, as
+        the slot `lift` of `lift_rect` holds them, gathered through the inverse map `m` into `rect` where `lock` (or None) is 0"""
+        self.model.warp_drop_u8(frame, lift, lift_rect, plane, lock, box, rect, m)
+
+    def warp(self, plane, box, m):
+        """a selection's plane warped as warp_drop warps its pixels -> (plane, box, count) of a NEW plane: one
+        launch, then the tile records of the result -- the one download"""
+        out = self.model.plane_warp_u8(plane, box, m)
         b, count = tiles_box(self.tiles(out, 32))
         return out, b, count
 
@@ -1602,6 +1723,90 @@ class EditSession:
         away and the source stays what it is -- no forward runs; ONE undo step over the destination rectangle."""
         kw["keep_source"] = True
         return self.move_selection(selection, offset, **kw)
+
+    # ---- scale and rotate a selection (DESIGN.md 6s) -----------------------------------------------------------------------------------
+    def transform_selection(self, selection, scale=1.0, angle=0.0, offset=(0, 0), flip=None, matrix=None, keep_source=False, hole_grow=2,
+                            window=None, margin=0.5, low_latency=None, max_side=None, encode=None, feather=None):
+        """"Make this bigger, turn it, and mend the place it came from" (DESIGN.md 6s): move_selection with a drop that resamples.
+        The selected pixels are turned by `angle` degrees (counter-clockwise on the screen) about the centre of the selection's
+        box, scaled by `scale` (a number or a (sy, sx) pair, each in 1/8 .. 8), mirrored by `flip` and their centre put `offset` =
+        (dy, dx) away (ints or floats, quantised to half pixels): the map is warp_matrix(selection.box, scale, angle, offset,
+        flip).  `matrix` = six ints gives the inverse map in Q16 itself and excludes scale, angle, offset and flip.  Everything
+        happens on the device under ONE hold of the session's lock, in move_selection's steps:
+          1. the LIFT of move_rect(box, (0, 0)) into a scratch slot;
+          2. unless `keep_source`, the fill of the HOLE, the selection grown by `hole_grow` (0 .. 16), exactly as fill_selection
+             fills (`window`, `margin`, `max_side`, the lock plane); `feather` applies to this fill only -- the drop's soft edge
+             is the interpolation's;
+          3. the DROP: ONE launch at frame scale whatever `max_side` is, bilinear taps of the lifted pixels blended by their
+             coverage (include/sketchedit_warp.h) into warp_rect(box, m): integers only, the same bytes on every machine.  Below a
+             scale of 1/2 the taps undersample; there is no prefilter and no claim of quality;
+          4. the warped SELECTION: the plane through the same map, selected where the coverage is at least a half, with its box
+             and count -- the call's one extra download.
+        Locked source pixels are not filled; they are still copied.  Locked destination pixels never change.
+        -> (patches, positions, info) in move_selection's shape over [fill window, destination rectangle] (the destination alone
+        with `keep_source`); info = dict(windows, transform=True, matrix=the six ints, selected, selection=the warped Selection)
+        plus work / undoable / locked / feather where `fill` reports them.  With history on the call is ONE undo step, the
+        ordered entry of a move; a backend call that fails once the frame was written clears the history.
+        TypeError / ValueError, all before the first backend call: a selection that is none, of another frame size or empty, a bad
+        scale, angle, offset, flip or matrix, a matrix together with one of those four, a singular map, a map that puts nothing in
+        the frame, a bad hole_grow, window, max_side, encode or feather."""
+        encode = _check_encode(encode)
+        feather = _check_feather(feather)
+        self._check_selection(selection, "transform_selection")
+        if selection.box is None:
+            raise ValueError("empty selection: nothing to transform")
+        box = selection.box
+        if matrix is not None:
+            try:
+                alone = bool(scale == 1.0 and angle == 0.0 and flip is None and tuple(offset) == (0, 0))
+            except (TypeError, ValueError):
+                alone = False
+            if not alone:
+                raise ValueError("matrix excludes scale, angle, offset and flip")
+            m = _check_warp_map(matrix)
+        else:
+            m = _check_warp_map(warp_matrix(box, scale, angle, offset, flip))
+        if not isinstance(hole_grow, (int, np.integer)) or isinstance(hole_grow, (bool, np.bool_)) or not 0 <= hole_grow <= SELECT_MAX_GROW:
+            raise ValueError("hole_grow is an int 0 .. %d, in frame pixels (got %r)" % (SELECT_MAX_GROW, hole_grow))
+        hole_grow = int(hole_grow)
+        Hi, Wi = self.frame_hw
+        dst = warp_rect(box, m, self.frame_hw)
+        if dst is None:
+            raise ValueError("the map %r puts nothing of the selection in the frame" % (m,))
+        grown = (max(box[0] - hole_grow, 0), max(box[1] - hole_grow, 0), min(box[2] + hole_grow, Hi), min(box[3] + hole_grow, Wi))
+        self._check_fill_args(grown, None, window, margin, max_side)
+        win = None if keep_source else self._fill_window(grown, window, margin, max_side)
+        wins = ([] if win is None else [win]) + [dst]
+        journal = self.history > 0 and (self.history_bytes is None or
+                                        sum(window_saved_bytes(w[2], w[3]) for w in wins) <= self.history_bytes)
+        be = self.backend
+        with self._lock:
+            frames = [self._frame]
+            lift_rect = move_rect(box, (0, 0), self.frame_hw)
+            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
+            slots, work, pasted = [], None, False
+            try:
+                if win is not None:
+                    hole = selection.plane if hole_grow == 0 else be.grow(selection.plane, hole_grow)
+                    slot, work, _ = self._fill_steps(hole, None, win, low_latency, max_side, feather, journal)
+                    slots.append(slot)
+                    pasted = True
+                if journal:
+                    slots.append(be.save(frames, [dst[:2]], dst[2:])[0])
+                be.warp_drop(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, dst, m)
+                pasted = True
+                plane, wbox, count = be.warp(selection.plane, box, m)
+            except Exception:
+                if pasted:                       # the fill or the drop is in the frame: no entry restores a state it was in
+                    self._undo.clear()
+                    self._redo.clear()
+                raise
+            undoable = self._record_sequence(wins, slots if journal else None) if self.history > 0 else None
+            warped = Selection(be, plane, wbox, count, self.frame_hw)
+            patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames * len(wins), wins)
+            locked = self._lock_plane is not None
+        info = dict(windows=wins, transform=True, matrix=m, selected=selection.count, selection=warped)
+        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, work, undoable, feather if win is not None else None)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""

@@ -173,6 +173,19 @@ of every timed call:
 plus the parts timed alone (fill_selection of the grown selection, a combine, clone_selection, the move with history on and its
 undo), and se_profile_report's per-kernel times of one (b) request:
     python tools/serve_probe.py --move [--reps N] [--out FILE]
+
+--warp: scale and rotate a selection: --move's frame, disc, window and offset; the frame is put back (a device copy,
+not timed) in front of every timed call:
+  (a) edit:               EditSession.edit(window=..., max_grow=0), the unchanged control,
+  (b) move:               EditSession.move_selection(selection, (150, 300), window=...), as --move times it,
+  (c) transform_identity: EditSession.transform_selection(selection, offset=(150, 300), window=...) -- the same bytes through the
+                          resampling drop,
+  (d) transform:          the same with scale=1.5, angle=30,
+  (e) host_route:         session.frame() (the 6 MB download), the object and its mask through Pillow's Image.transform (affine,
+                          bilinear) and a composite in numpy, a NEW session of the result (the 6 MB upload), EditSession.fill(grown
+                          mask, window=...) -- what a front end does without transform_selection; the undo journal is lost,
+plus se_profile_report's per-kernel times of one (c) and one (d) request (warp_drop, plane_warp among them):
+    python tools/serve_probe.py --warp [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -1233,6 +1246,103 @@ def move_leg(model, reps, parent=False, side=512, tolerance=16, offset=(150, 300
     return out
 
 
+def warp_leg(model, reps, side=512, tolerance=16, offset=(150, 300), scale=1.5, angle=30.0):
+    """(a) .. (e) of the module docstring"""
+    import numpy as np
+    import torch
+    from PIL import Image
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    frame[..., 0] = frame[..., 0] % 90                               # no noise pixel is similar to the disc's colour
+    win = (283, 705, side, side)
+    seed = (win[0] + side // 2, win[1] + side // 2)
+    yy, xx = np.mgrid[0:h, 0:w]
+    disc = (yy - seed[0]) ** 2 + (xx - seed[1]) ** 2 <= 126 ** 2
+    frame[disc] = 128
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    dev0 = torch.from_numpy(frame).cuda()
+
+    def fresh(session):
+        def put_back():
+            session._frame.copy_(dev0)
+            torch.cuda.synchronize()
+        return put_back
+
+    def timed(fn, put_back=lambda: None):
+        def rounds():
+            for _ in range(2):                 # warm-up: plans, workspace, code objects
+                put_back()
+                fn()
+            ts = []
+            for _ in range(reps):
+                put_back()
+                t0 = time.perf_counter()
+                fn()                           # ends in a device-to-host copy: the request is complete
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts.sort()
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    s1, s2, s3 = serve.EditSession(model, frame), serve.EditSession(model, frame), serve.EditSession(model, frame)
+    sel = s2.select_similar(seed, tolerance=tolerance)
+    m = serve.warp_matrix(sel.box, scale, angle, offset)
+    one = float(serve.WARP_ONE)
+    # Pillow's affine data (a, b, c, d, e, f): input (x, y) = (a x + b y + c, d x + e y + f) on pixel CORNERS; m is on centres
+    a, b, d, e = m[4] / one, m[3] / one, m[1] / one, m[0] / one
+    data = (a, b, m[5] / one + 0.5 - 0.5 * (a + b), d, e, m[2] / one + 0.5 - 0.5 * (d + e))
+
+    def host_route():
+        f = s3.frame()
+        mask = (np.abs(f.astype(np.int16) - f[seed]).max(axis=2) <= tolerance)              # (the disc: no flood on this route)
+        rgba = Image.fromarray(np.dstack([f * mask[..., None], np.where(mask, 255, 0).astype(np.uint8)]), "RGBA")
+        got = np.asarray(rgba.transform((w, h), Image.AFFINE, data, resample=Image.BILINEAR)).astype(np.int32)
+        alpha = got[..., 3:]                                                                 # premultiplied: the object's rim by its coverage
+        f = ((got[..., :3] * 255 + (255 - alpha) * f + 127) // 255).astype(np.uint8)
+        hole = np.zeros((h, w), bool)
+        for ey in range(-2, 3):                # the grow by 2, as shifts
+            for ex in range(-2, 3):
+                hole[max(ey, 0):h + min(ey, 0), max(ex, 0):w + min(ex, 0)] |= mask[max(-ey, 0):h + min(-ey, 0), max(-ex, 0):w + min(-ex, 0)]
+        return serve.EditSession(model, f).fill(hole, window=win, low_latency=True)
+
+    legs = dict(edit=timed(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True), fresh(s1)),
+                move=timed(lambda: s2.move_selection(sel, offset, window=win, low_latency=True), fresh(s2)),
+                transform_identity=timed(lambda: s2.transform_selection(sel, offset=offset, window=win, low_latency=True), fresh(s2)),
+                transform=timed(lambda: s2.transform_selection(sel, scale=scale, angle=angle, offset=offset, window=win, low_latency=True), fresh(s2)),
+                host_route=timed(host_route, fresh(s3)))
+    out = dict(tool="serve_probe --warp", B=1, reps=reps, mode="low_latency", frame=[w, h], window=list(win), seed=list(seed), tolerance=tolerance,
+               offset=list(offset), scale=scale, angle=angle, matrix=list(m), disc_pixels=int(disc.sum()))
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    eng = model.engine()
+    for name, kw in (("transform_identity", dict()), ("transform", dict(scale=scale, angle=angle))):
+        fresh(s2)()
+        eng.profile(True)
+        _, _, info = s2.transform_selection(sel, offset=offset, window=win, low_latency=True, **kw)
+        rep = eng.profile_report()
+        eng.profile(False)
+        ks = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        out[name + "_profiled"] = {k: v for k, v in ks.items() if v["ms"] >= 0.001}
+        out[name + "_windows"] = [list(v) for v in info["windows"]]
+        out[name + "_count"] = info["selection"].count
+    fresh(s2)()
+    _, _, moved = s2.move_selection(sel, offset, window=win, low_latency=True)
+    after_move = s2._frame.clone()
+    fresh(s2)()
+    _, _, ident = s2.transform_selection(sel, offset=offset, window=win, low_latency=True)
+    out.update(selected=sel.count, box=list(sel.box),
+               identity_is_the_move=bool(torch.equal(after_move, s2._frame) and torch.equal(moved["selection"].plane, ident["selection"].plane)),
+               transform_minus_move_ms=round(out["ms"]["transform"]["median"] - out["ms"]["move"]["median"], 3),
+               transform_minus_host_route_ms=round(out["ms"]["transform"]["median"] - out["ms"]["host_route"]["median"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -1264,6 +1374,7 @@ def main():
     ap.add_argument("--outline-parent", action="store_true", help="the edit leg of --outline only")
     ap.add_argument("--move", action="store_true", help="move a selection (see the module docstring)")
     ap.add_argument("--move-parent", action="store_true", help="the edit leg of --move only")
+    ap.add_argument("--warp", action="store_true", help="scale and rotate a selection (see the module docstring)")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -1276,8 +1387,10 @@ def main():
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
             or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent
-            or args.move or args.move_parent):
-        if args.move or args.move_parent:
+            or args.move or args.move_parent or args.warp):
+        if args.warp:
+            res = warp_leg(model, args.reps)
+        elif args.move or args.move_parent:
             res = move_leg(model, args.reps, parent=args.move_parent)
         elif args.outline or args.outline_parent:
             res = outline_leg(model, args.reps, parent=args.outline_parent)
