@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_move.hip", "se_warp.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_move.hip", "se_warp.hip", "se_filter.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
            "se_plan.hip", "se_api_window.hip", "se_api_select.hip", "se_api_move.hip", "se_api_codec.hip", "se_api_debug.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
@@ -76,6 +76,10 @@ MOVE_FLIP_X, MOVE_FLIP_Y = 1, 2                   # SE_MOVE_FLIP_*
 # every symbol declared in include/sketchedit_warp.h (scale and rotate a selection)
 WARP_SYMBOLS = ["se_warp_drop_u8", "se_plane_warp_u8"]
 WARP_MAX_COEF, WARP_MAX_TRANSLATION = 1 << 20, 1 << 40      # SE_WARP_MAX_COEF, SE_WARP_MAX_TRANSLATION
+# every symbol declared in include/sketchedit_filter.h (blur, sharpen or pixelate a selection)
+FILTER_SYMBOLS = ["se_filter_blur_u8", "se_filter_mosaic_u8"]
+FILTER_MAX_RADIUS, FILTER_ONE, FILTER_MAX_CELL = 32, 4096, 64      # SE_FILTER_MAX_RADIUS, SE_FILTER_ONE, SE_FILTER_MAX_CELL
+FILTER_MIN_AMOUNT, FILTER_MAX_AMOUNT, FILTER_MAX_FEATHER = -256, 1024, 16      # SE_FILTER_MIN_AMOUNT, SE_FILTER_MAX_AMOUNT, SE_FILTER_MAX_FEATHER
 
 
 class SketchEditHipError(RuntimeError):
@@ -305,6 +309,10 @@ def load_library():
         lib.se_warp_drop_u8.restype = ci
         lib.se_plane_warp_u8.argtypes = [vp, vp, vp, ci, ci] + [ci] * 4 + [vp, vp]
         lib.se_plane_warp_u8.restype = ci
+        lib.se_filter_blur_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 4 + [vp, ci, ci, ci]
+        lib.se_filter_blur_u8.restype = ci
+        lib.se_filter_mosaic_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 7
+        lib.se_filter_mosaic_u8.restype = ci
         lib.se_outline_u8_workspace_bytes.argtypes = [vp, ci, ci]
         lib.se_outline_u8_workspace_bytes.restype = sz
         lib.se_outline_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, sz]
@@ -1276,6 +1284,50 @@ class Engine:
         if self.lib.se_plane_warp_u8(self.h, self._stream(), _ptr(sel), Hi, Wi, by0, bx0, by1, bx1, mm, _ptr(out)):
             self._err("se_plane_warp_u8")
         return out
+
+    # ---- blur, sharpen or pixelate a selection (include/sketchedit_filter.h) ----------------------------------------------
+    def _filter_args(self, what, frame, lift, lift_rect, sel, lock, box):
+        """the checks the two filters share -> (Hi, Wi, lift rectangle, box) as ints"""
+        _check_dev_u8(frame)
+        if frame.dim() != 3 or frame.shape[2] != 3:
+            raise SketchEditHipError("%s: a frame is an (Hi,Wi,3) uint8 tensor" % what)
+        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
+        if self._state_plane(sel, what + ": sel") != (Hi, Wi) or (lock is not None and self._state_plane(lock, what + ": lock") != (Hi, Wi)):
+            raise SketchEditHipError("%s: sel and lock are the frame's (Hi,Wi) planes" % what)
+        lr = tuple(int(v) for v in lift_rect)
+        _check_dev_u8(lift)
+        need = self.window_saved_bytes(lr[2], lr[3])
+        if need and lift.numel() < need:
+            raise SketchEditHipError("%s: a lift holds window_saved_bytes(lh, lw) = %d bytes" % (what, need))
+        return Hi, Wi, lr, tuple(int(v) for v in box)
+
+    def filter_blur_u8(self, frame, lift, lift_rect, sel, lock, box, taps, amount=-256, feather=0):
+        """se_filter_blur_u8, in place on `frame` (Hi,Wi,3) uint8 on the device: the pixels of `box` = (by0, bx0, by1, bx1) that
+        `sel` (an (Hi,Wi) plane, non-zero = selected) selects and `lock` (a plane or None) does not lock become the separable
+        filter `taps` = [t0 .. tR] (R = 1 .. 32, t0 + 2 (t1 + .. + tR) = 4096) of the frame as `lift` holds it -- the journal slot
+        window_save_u8 made of `lift_rect` = (ly0, lx0, lh, lw), a rectangle that holds the box grown by R and clipped to the
+        frame -- mixed with the lifted pixel by `amount` (Q8: -256 the blur, > 0 an unsharp mask) and faded over `feather`
+        pixels at the selection's rim.  No other byte changes; the frame is never read.  One launch."""
+        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._filter_args("filter_blur_u8", frame, lift, lift_rect, sel, lock, box)
+        try:
+            vals = [int(v) for v in taps]
+        except (TypeError, ValueError):
+            vals = []
+        if not 2 <= len(vals) <= FILTER_MAX_RADIUS + 1 or any(abs(v) >= 1 << 31 for v in vals):
+            raise SketchEditHipError("filter_blur_u8: taps are 2 .. %d ints [t0 .. tR]" % (FILTER_MAX_RADIUS + 1))
+        tp = (ctypes.c_int * len(vals))(*vals)
+        if self.lib.se_filter_blur_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
+                                      by0, bx0, by1, bx1, tp, len(vals) - 1, int(amount), int(feather)):
+            self._err("se_filter_blur_u8")
+
+    def filter_mosaic_u8(self, frame, lift, lift_rect, sel, lock, box, cell, amount=-256, feather=0):
+        """se_filter_mosaic_u8, in place on `frame`: as filter_blur_u8 with the mean of the pixel's `cell` x `cell` block (2 .. 64,
+        anchored at the box's origin and clipped to the box, taken over all its lifted pixels) in place of the blur; `lift_rect`
+        holds the box.  One launch."""
+        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._filter_args("filter_mosaic_u8", frame, lift, lift_rect, sel, lock, box)
+        if self.lib.se_filter_mosaic_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
+                                        by0, bx0, by1, bx1, int(cell), int(amount), int(feather)):
+            self._err("se_filter_mosaic_u8")
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------
     def sketch_tiles_u8(self, sketch_u8, tile, out=None):

@@ -1,6 +1,8 @@
 // The editing sessions' move entries behind include/sketchedit_move.h: the drop of a lifted selection and the shift of its plane
 // (kernels: se_move.hip); and behind include/sketchedit_warp.h the drop through an affine map and the warp
-// of the plane (kernels: se_warp.hip).
+// of the plane (kernels: se_warp.hip); and behind include/sketchedit_filter.h the blur and the mosaic of a
+// selection (kernels: se_filter.hip).
+#include "../../include/sketchedit_filter.h"
 #include "../../include/sketchedit_move.h"
 #include "../../include/sketchedit_warp.h"
 #include "se_host.h"
@@ -47,6 +49,34 @@ int warp_check_map(se_ctx* c, int by0, int bx0, int by1, int bx1, int ry0, int r
     if (m[i] < -lim || m[i] > lim)
       return fail(c, "bad m: %s=%lld (a %s is at most %lld in magnitude)", names[i], m[i], tr ? "translation" : "coefficient", lim);
   }
+  return 0;
+}
+
+// what both filters share: the frame, the lift, the box inside it, the overlaps, the amount and the feather; `grow` = the blur's
+// radius (0 for the mosaic): the lift rectangle holds the box grown by it and clipped to the frame
+int filter_check(se_ctx* c, const unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh, int lw,
+                 const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, int grow, int amount, int feather) {
+  if (!frame_u8) return fail(c, "null pointer argument: frame_u8");
+  if (!lift) return fail(c, "null pointer argument: lift");
+  if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
+  if (move_check_frame(c, Hi, Wi)) return 1;
+  if (lh < 16 || lw < 16) return fail(c, "bad lift rectangle lh=%d lw=%d (a side is at least 16)", lh, lw);
+  if (ly0 < 0 || lx0 < 0 || lh > Hi || lw > Wi || ly0 > Hi - lh || lx0 > Wi - lw)
+    return fail(c, "the lift rectangle (ly0=%d lx0=%d, %d x %d) lies outside the frame (Hi=%d Wi=%d)", ly0, lx0, lh, lw, Hi, Wi);
+  if (!aligned_to(lift, 16)) return fail(c, "lift must be 16-byte aligned");
+  if (move_check_map(c, by0, bx0, by1, bx1, ly0, lx0, lh, lw, "lift rectangle", 0, 0, 0)) return 1;
+  if (amount < SE_FILTER_MIN_AMOUNT || amount > SE_FILTER_MAX_AMOUNT)
+    return fail(c, "bad amount=%d (%d .. %d, Q8)", amount, SE_FILTER_MIN_AMOUNT, SE_FILTER_MAX_AMOUNT);
+  if (feather < 0 || feather > SE_FILTER_MAX_FEATHER) return fail(c, "bad feather=%d (0 .. %d)", feather, SE_FILTER_MAX_FEATHER);
+  const int gy0 = by0 - grow > 0 ? by0 - grow : 0, gx0 = bx0 - grow > 0 ? bx0 - grow : 0;
+  const int gy1 = by1 + grow < Hi ? by1 + grow : Hi, gx1 = bx1 + grow < Wi ? bx1 + grow : Wi;
+  if (gy0 < ly0 || gx0 < lx0 || gy1 > ly0 + lh || gx1 > lx0 + lw)
+    return fail(c, "the lift rectangle (ly0=%d lx0=%d, %d x %d) does not contain the box (%d, %d, %d, %d) grown by radius=%d and clipped to the frame",
+                ly0, lx0, lh, lw, by0, bx0, by1, bx1, grow);
+  const size_t pn = (size_t)Hi * Wi, lpitch = ((size_t)3 * lw + 15) & ~(size_t)15, ln = (size_t)lh * lpitch;
+  if (overlaps(lift, ln, frame_u8, 3 * pn)) return fail(c, "lift overlaps frame_u8");
+  if (overlaps(sel_u8, pn, frame_u8, 3 * pn)) return fail(c, "sel_u8 overlaps frame_u8");
+  if (lock_u8 && overlaps(lock_u8, pn, frame_u8, 3 * pn)) return fail(c, "lock_u8 overlaps frame_u8");
   return 0;
 }
 
@@ -131,6 +161,41 @@ int se_plane_warp_u8(se_ctx* c, void* stream, const unsigned char* sel_u8, int H
   if (overlaps(plane_out, pn, sel_u8, pn)) return fail(c, "plane_out overlaps sel_u8");
   if (device_enter(c)) return 1;
   HIPCHK(c, launch_plane_warp(sel_u8, Hi, Wi, by0, bx0, by1, bx1, m, plane_out, (hipStream_t)stream));
+  return 0;
+}
+
+int se_filter_blur_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh,
+                      int lw, const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, const int* taps,
+                      int radius, int amount, int feather) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!taps) return fail(c, "null pointer argument: taps");
+  if (radius < 1 || radius > SE_FILTER_MAX_RADIUS) return fail(c, "bad radius=%d (1 .. %d)", radius, SE_FILTER_MAX_RADIUS);
+  long long sum = 0;
+  for (int k = 0; k <= radius; ++k) {
+    if (taps[k] < 0) return fail(c, "bad taps: taps[%d]=%d is negative", k, taps[k]);
+    sum += k ? 2ll * taps[k] : (long long)taps[k];
+  }
+  if (sum != SE_FILTER_ONE) return fail(c, "bad taps: taps[0] + 2 (taps[1] + .. + taps[%d]) = %lld, not %d", radius, sum, SE_FILTER_ONE);
+  if (filter_check(c, frame_u8, Hi, Wi, lift, ly0, lx0, lh, lw, sel_u8, lock_u8, by0, bx0, by1, bx1, radius, amount, feather)) return 1;
+  if (device_enter(c)) return 1;
+  const int lpitch = (3 * lw + 15) & ~15;
+  HIPCHK(c, launch_filter_blur(frame_u8, Hi, Wi, lift, ly0, lx0, lw, lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, taps, radius, amount, feather,
+                               (hipStream_t)stream));
+  return 0;
+}
+
+int se_filter_mosaic_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh,
+                        int lw, const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, int cell,
+                        int amount, int feather) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (cell < 2 || cell > SE_FILTER_MAX_CELL) return fail(c, "bad cell=%d (2 .. %d)", cell, SE_FILTER_MAX_CELL);
+  if (filter_check(c, frame_u8, Hi, Wi, lift, ly0, lx0, lh, lw, sel_u8, lock_u8, by0, bx0, by1, bx1, 0, amount, feather)) return 1;
+  if (device_enter(c)) return 1;
+  const int lpitch = (3 * lw + 15) & ~15;
+  HIPCHK(c, launch_filter_mosaic(frame_u8, Hi, Wi, lift, ly0, lx0, lw, lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, cell, amount, feather,
+                                 (hipStream_t)stream));
   return 0;
 }
 

@@ -58,6 +58,11 @@ KERNEL_LABELS = {
     # scale and rotate a selection (se_warp.hip): the resampling drop, and the warp of the plane
     "(anonymous namespace)::warp_drop_kernel": "warp_drop", "(anonymous namespace)::plane_warp_kernel": "plane_warp",
     "warp_drop_kernel": "warp_drop", "plane_warp_kernel": "plane_warp",
+    # blur, sharpen or pixelate a selection (se_filter.hip): the separable filter by radius class, and the block mean
+    "(anonymous namespace)::filter_blur_kernel<8>": "filter_blur", "(anonymous namespace)::filter_blur_kernel<16>": "filter_blur",
+    "(anonymous namespace)::filter_blur_kernel<32>": "filter_blur", "(anonymous namespace)::filter_mosaic_kernel": "filter_mosaic",
+    "filter_blur_kernel<8>": "filter_blur", "filter_blur_kernel<16>": "filter_blur", "filter_blur_kernel<32>": "filter_blur",
+    "filter_mosaic_kernel": "filter_mosaic",
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",

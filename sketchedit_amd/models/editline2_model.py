@@ -255,6 +255,17 @@ class EditLine2Model(torch.nn.Module):
         """A selection plane warped as warp_drop_u8 warps its pixels: a new 0 / 255 plane (Engine.plane_warp_u8)."""
         return self.engine().plane_warp_u8(sel, box, m, out=out)
 
+    def filter_blur_u8(self, frame, lift, lift_rect, sel, lock, box, taps, amount=-256, feather=0):
+        """The blur or unsharp mask of a selection (serve.EditSession.filter_selection is the caller-facing form):
+        the selected pixels of `box` become the separable filter `taps` of the frame as the journal slot `lift` of `lift_rect`
+        holds it (Engine.filter_blur_u8)."""
+        self.engine().filter_blur_u8(frame, lift, lift_rect, sel, lock, box, taps, amount=amount, feather=feather)
+
+    def filter_mosaic_u8(self, frame, lift, lift_rect, sel, lock, box, cell, amount=-256, feather=0):
+        """The mosaic of a selection: the selected pixels of `box` become the mean of their `cell` x `cell` block of
+        the lift (Engine.filter_mosaic_u8)."""
+        self.engine().filter_mosaic_u8(frame, lift, lift_rect, sel, lock, box, cell, amount=amount, feather=feather)
+
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
         slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""

@@ -408,6 +408,52 @@ def move_rect(box, offset, frame_hw):
     return None if ya is None or xa is None else (ya[0], xa[0], ya[1], xa[1])
 
 
+FILTER_ONE = 4096                    # SE_FILTER_ONE: the sum of a filter's taps, t[0] + 2 (t[1] + .. + t[R])
+FILTER_MAX_RADIUS = 32               # SE_FILTER_MAX_RADIUS
+FILTER_MAX_CELL = 64                 # SE_FILTER_MAX_CELL
+FILTER_MAX_AMOUNT = 4.0              # SE_FILTER_MAX_AMOUNT / 256: the strongest unsharp mask
+FILTER_KINDS = ("blur", "box", "sharpen", "pixelate")
+
+
+def _filter_int(v, lo, hi, what):
+    if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or not lo <= v <= hi:
+        raise ValueError("%s is an int %d .. %d (got %r)" % (what, lo, hi, v))
+    return int(v)
+
+
+def filter_taps(kind, radius, sigma=None):
+    """The taps [t0 .. tR] of a separable filter of `radius` R = 1 .. 32 (pure host arithmetic): ints >= 0 with
+    t0 + 2 (t1 + .. + tR) == 4096, t0 > 0 and t1 >= t2 >= .. >= tR.  `kind` "gauss": w_k = exp(-k^2 / (2 sigma^2)) with `sigma` =
+    max(R / 3, 0.5) unless given (0 < sigma <= R), t_k = floor(4096 w_k / sum of w + 0.5) for k >= 1 and t0 the rest -- for a wide
+    sigma t0 may be a unit below t1.  `kind` "box": t_k = 4096 // (2R + 1) for k >= 1 and t0 the rest; it takes no sigma.
+    ValueError for a bad argument."""
+    if not isinstance(kind, str) or kind not in ("gauss", "box"):
+        raise ValueError("kind is 'gauss' or 'box' (got %r)" % (kind,))
+    R = _filter_int(radius, 1, FILTER_MAX_RADIUS, "radius")
+    if kind == "box":
+        if sigma is not None:
+            raise ValueError("a box filter takes no sigma (got %r)" % (sigma,))
+        t = [FILTER_ONE // (2 * R + 1)] * R
+    else:
+        if sigma is None:
+            sigma = max(R / 3.0, 0.5)
+        if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not 0 < sigma <= R:
+            raise ValueError("sigma is a number in (0, radius] (got %r)" % (sigma,))
+        w = [math.exp(-k * k / (2.0 * float(sigma) ** 2)) for k in range(R + 1)]
+        total = w[0] + 2.0 * sum(w[1:])
+        t = [int(math.floor(FILTER_ONE * w[k] / total + 0.5)) for k in range(1, R + 1)]
+    return [FILTER_ONE - 2 * sum(t)] + t
+
+
+def filter_rect(box, radius, frame_hw):
+    """The rectangle a filter LIFTS (pure host arithmetic): `box` = (y0, x0, y1, x1), half open, grown by `radius` on
+    every side and clipped to the frame of `frame_hw`, sides under 16 widened exactly as move_rect widens them.  It holds every
+    pixel a tap of that radius reads and every pixel the filter writes.  -> (y0, x0, h, w)."""
+    by0, bx0, by1, bx1 = (int(v) for v in box)
+    r = int(radius)
+    return move_rect((by0 - r, bx0 - r, by1 + r, bx1 + r), (0, 0), frame_hw)
+
+
 WARP_ONE = 1 << 16                   # 1.0 in the Q16 of a warp's inverse map
 WARP_MAX_COEF = 1 << 20              # SE_WARP_MAX_COEF
 WARP_MAX_TRANSLATION = 1 << 40       # SE_WARP_MAX_TRANSLATION
@@ -908,6 +954,17 @@ class _ModelBackend:
         out = self.model.plane_warp_u8(plane, box, m)
         b, count = tiles_box(self.tiles(out, 32))
         return out, b, count
+
+    def filter_blur(self, frame, lift, lift_rect, plane, lock, box, taps, amount, feather):
+        """the blur or unsharp mask of a selection, ONE launch in place on the frame: the pixels of `box` that `plane`
+        selects and `lock` (or None) leaves become the filter `taps` of the frame as the slot `lift` of `lift_rect` holds it, mixed
+        by `amount` (Q8), with a soft edge of `feather`"""
+        self.model.filter_blur_u8(frame, lift, lift_rect, plane, lock, box, taps, amount=amount, feather=feather)
+
+    def filter_mosaic(self, frame, lift, lift_rect, plane, lock, box, cell, amount, feather):
+        """the mosaic of a selection, ONE launch in place on the frame: as filter_blur with the mean of the pixel's
+        `cell` x `cell` block of the lift"""
+        self.model.filter_mosaic_u8(frame, lift, lift_rect, plane, lock, box, cell, amount=amount, feather=feather)
 
     def save(self, frames, origins, window_hw):
         """the windows' rectangles -> one new journal slot each, on the stream the edit follows on"""
@@ -1807,6 +1864,81 @@ class EditSession:
             locked = self._lock_plane is not None
         info = dict(windows=wins, transform=True, matrix=m, selected=selection.count, selection=warped)
         return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, work, undoable, feather if win is not None else None)
+
+    # ---- blur, sharpen or pixelate a selection --------------------------------------------------------------------------
+    def filter_selection(self, selection, kind="blur", radius=None, amount=None, sigma=None, cell=None, feather=None, encode=None):
+        """"Blur that face, pixelate that number plate, sharpen what I just scaled up" (DESIGN.md 6t): the selected pixels become a
+        filter of the frame as it is now.  `kind`:
+          "blur"      a Gaussian of `radius` (1 .. 32, default 8) and `sigma` (default max(radius / 3, 0.5), at most radius);
+          "box"       the box filter of `radius` (default 8);
+          "sharpen"   an unsharp mask: the pixel plus `amount` (a float in (0, 4], default 1.0) times its difference from the
+                      Gaussian of `radius` (default 2) and `sigma`, clamped to 0 .. 255;
+          "pixelate"  the mean of the pixel's `cell` x `cell` block (2 .. 64, default 16), the blocks anchored at the top left
+                      corner of the selection's box and averaged over all their pixels, selected or not.
+        An argument the kind does not take must be None.  `feather` = f (None or 0 .. 16) fades the filter in over f pixels at
+        the selection's rim.  Integer arithmetic (include/sketchedit_filter.h): the same bytes on every machine.  Everything
+        happens on the device under ONE hold of the session's lock:
+          1. the LIFT: filter_rect(box, radius) of the frame -- the box with the taps' margin -- is saved into a slot;
+          2. ONE launch filters the lifted pixels into the frame where the selection selects and the lock plane does not lock;
+          3. with history on the lift IS the journal entry's slot -- everything that changed lies inside it -- so the call is one
+             undo step of the single-window kind and makes no second save; a lift above `history_bytes` commits unjournalled
+             and clears the history, and so does a backend call that fails once the filter was launched.
+        The selection stays what it was; no new Selection is made.
+        -> (patches, positions, info) in edit_regions' shape over ONE window, move_rect(box, (0, 0)); `encode` applies.
+        info = dict(windows, filter=kind, radius, amount, cell, selected) plus undoable / locked / feather where `edit` reports
+        them (radius or cell None where the kind has none; amount -1.0 but for "sharpen").
+        TypeError / ValueError, all before the first backend call: a selection that is none, of another frame size or empty, a bad
+        kind, radius, sigma, amount, cell, feather or encode, an argument the kind does not take."""
+        encode = _check_encode(encode)
+        feather = _check_feather(feather)
+        self._check_selection(selection, "filter_selection")
+        if selection.box is None:
+            raise ValueError("empty selection: nothing to filter")
+        if not isinstance(kind, str) or kind not in FILTER_KINDS:
+            raise ValueError("kind is one of %s (got %r)" % (", ".join(repr(k) for k in FILTER_KINDS), kind))
+        takes = dict(blur=("radius", "sigma"), box=("radius",), sharpen=("radius", "sigma", "amount"), pixelate=("cell",))[kind]
+        for name, v in (("radius", radius), ("amount", amount), ("sigma", sigma), ("cell", cell)):
+            if v is not None and name not in takes:
+                raise ValueError("kind %r takes no %s (got %r)" % (kind, name, v))
+        q8, taps = -256, None
+        if kind == "pixelate":
+            cell = _filter_int(16 if cell is None else cell, 2, FILTER_MAX_CELL, "cell")
+        else:
+            radius = _filter_int((2 if kind == "sharpen" else 8) if radius is None else radius, 1, FILTER_MAX_RADIUS, "radius")
+            taps = filter_taps("box" if kind == "box" else "gauss", radius, sigma)
+        if kind == "sharpen":
+            amount = 1.0 if amount is None else amount
+            if (isinstance(amount, (bool, np.bool_)) or not isinstance(amount, (int, float, np.integer, np.floating))
+                    or not 0 < amount <= FILTER_MAX_AMOUNT):
+                raise ValueError("amount is a number in (0, %g] (got %r)" % (FILTER_MAX_AMOUNT, amount))
+            amount = float(amount)
+            q8 = int(round(256 * amount))
+            if q8 < 1:
+                raise ValueError("amount %r rounds to no sharpening at all" % (amount,))
+        else:
+            amount = -1.0
+        box = selection.box
+        lift_rect = filter_rect(box, radius or 0, self.frame_hw)
+        wins = [move_rect(box, (0, 0), self.frame_hw)]
+        journal = self._journals(lift_rect[2], lift_rect[3])
+        be = self.backend
+        with self._lock:
+            frames = [self._frame]
+            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
+            try:
+                if kind == "pixelate":
+                    be.filter_mosaic(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, cell, q8, feather or 0)
+                else:
+                    be.filter_blur(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, taps, q8, feather or 0)
+                undoable = self._record(lift_rect, lift if journal else None) if self.history > 0 else None
+                patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames, wins)
+            except Exception:                    # the filter may be in the frame: no entry restores a state it was in
+                self._undo.clear()
+                self._redo.clear()
+                raise
+            locked = self._lock_plane is not None
+        info = dict(windows=wins, filter=kind, radius=radius, amount=amount, cell=cell, selected=selection.count)
+        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, None, undoable, feather)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""

@@ -186,6 +186,21 @@ not timed) in front of every timed call:
                           mask, window=...) -- what a front end does without transform_selection; the undo journal is lost,
 plus se_profile_report's per-kernel times of one (c) and one (d) request (warp_drop, plane_warp among them):
     python tools/serve_probe.py --warp [--reps N] [--out FILE]
+
+--filter: blur, sharpen or pixelate a selection: --move's frame, disc and window; the frame is put back (a device
+copy, not timed) in front of every timed call:
+  (a) edit:        EditSession.edit(window=..., max_grow=0), the unchanged control,
+  (b) blur_r8:     EditSession.filter_selection(selection, "blur"), radius 8,
+  (c) blur_r32:    the same at radius 32, the largest tile of LDS,
+  (d) pixelate_16: filter_selection(selection, "pixelate"), cell 16,
+  (e) sharpen:     filter_selection(selection, "sharpen"), radius 2, amount 1.0,
+  (f) host_route:  session.frame() (the 6 MB download), PIL.ImageFilter.GaussianBlur of the selection's box composited through
+                   the mask in numpy, a NEW session of the result (the 6 MB upload) -- what a front end does without
+                   filter_selection; the undo journal, the lock plane and every Selection are lost,
+plus se_profile_report's per-kernel times of one (b), (c) and (d) request (filter_blur, filter_mosaic, window_save among them).
+--move on the parent commit's build in the same job is the comparison leg (its clone_selection: a lift, one small launch, one
+patch download):
+    python tools/serve_probe.py --filter [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -1343,6 +1358,92 @@ def warp_leg(model, reps, side=512, tolerance=16, offset=(150, 300), scale=1.5, 
     return out
 
 
+def filter_leg(model, reps, side=512, tolerance=16):
+    """(a) .. (f) of the module docstring"""
+    import numpy as np
+    import torch
+    from PIL import Image, ImageFilter
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    frame[..., 0] = frame[..., 0] % 90                               # no noise pixel is similar to the disc's colour
+    win = (283, 705, side, side)
+    seed = (win[0] + side // 2, win[1] + side // 2)
+    yy, xx = np.mgrid[0:h, 0:w]
+    disc = (yy - seed[0]) ** 2 + (xx - seed[1]) ** 2 <= 126 ** 2
+    frame[disc] = 128
+    frame[disc & ((yy // 8 + xx // 8) % 2 == 0), 1] = 140            # a pattern inside the disc, within the tolerance: a filter has work to do
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    dev0 = torch.from_numpy(frame).cuda()
+
+    def fresh(session):
+        def put_back():
+            session._frame.copy_(dev0)
+            torch.cuda.synchronize()
+        return put_back
+
+    def timed(fn, put_back=lambda: None):
+        def rounds():
+            for _ in range(2):                 # warm-up: plans, workspace, code objects
+                put_back()
+                fn()
+            ts = []
+            for _ in range(reps):
+                put_back()
+                t0 = time.perf_counter()
+                fn()                           # ends in a device-to-host copy: the request is complete
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts.sort()
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    s1, s2, s3 = serve.EditSession(model, frame), serve.EditSession(model, frame), serve.EditSession(model, frame)
+    sel = s2.select_similar(seed, tolerance=tolerance)
+    by0, bx0, by1, bx1 = sel.box
+
+    def host_route():
+        f = s3.frame()
+        mask = (np.abs(f.astype(np.int16) - f[seed]).max(axis=2) <= tolerance)              # (the disc: no flood on this route)
+        y0, x0, y1, x1 = max(by0 - 8, 0), max(bx0 - 8, 0), min(by1 + 8, h), min(bx1 + 8, w)
+        soft = np.asarray(Image.fromarray(f[y0:y1, x0:x1]).filter(ImageFilter.GaussianBlur(8 / 3.0)))
+        f = f.copy()
+        crop = f[y0:y1, x0:x1]
+        crop[mask[y0:y1, x0:x1]] = soft[mask[y0:y1, x0:x1]]
+        s = serve.EditSession(model, f)
+        return s._frame[by0:by1, bx0:bx1].contiguous().cpu().numpy()                        # the patch a front end shows
+
+    F = s2.filter_selection
+    legs = dict(edit=timed(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True), fresh(s1)),
+                blur_r8=timed(lambda: F(sel, "blur", radius=8), fresh(s2)),
+                blur_r32=timed(lambda: F(sel, "blur", radius=32), fresh(s2)),
+                pixelate_16=timed(lambda: F(sel, "pixelate", cell=16), fresh(s2)),
+                sharpen=timed(lambda: F(sel, "sharpen"), fresh(s2)),
+                host_route=timed(host_route, fresh(s3)))
+    out = dict(tool="serve_probe --filter", B=1, reps=reps, mode="low_latency", frame=[w, h], window=list(win), seed=list(seed), tolerance=tolerance,
+               disc_pixels=int(disc.sum()))
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    eng = model.engine()
+    for name, kw in (("blur_r8", dict(kind="blur", radius=8)), ("blur_r32", dict(kind="blur", radius=32)), ("pixelate_16", dict(kind="pixelate", cell=16))):
+        fresh(s2)()
+        eng.profile(True)
+        _, _, info = F(sel, **kw)
+        rep = eng.profile_report()
+        eng.profile(False)
+        out[name + "_profiled"] = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        out[name + "_windows"] = [list(v) for v in info["windows"]]
+        out[name + "_changed_bytes"] = int((s2._frame != dev0).sum())
+    out.update(selected=sel.count, box=list(sel.box),
+               blur_r8_minus_host_route_ms=round(out["ms"]["blur_r8"]["median"] - out["ms"]["host_route"]["median"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -1375,6 +1476,7 @@ def main():
     ap.add_argument("--move", action="store_true", help="move a selection (see the module docstring)")
     ap.add_argument("--move-parent", action="store_true", help="the edit leg of --move only")
     ap.add_argument("--warp", action="store_true", help="scale and rotate a selection (see the module docstring)")
+    ap.add_argument("--filter", action="store_true", help="blur, sharpen or pixelate a selection (see the module docstring)")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -1387,8 +1489,10 @@ def main():
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
             or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent
-            or args.move or args.move_parent or args.warp):
-        if args.warp:
+            or args.move or args.move_parent or args.warp or args.filter):
+        if args.filter:
+            res = filter_leg(model, args.reps)
+        elif args.warp:
             res = warp_leg(model, args.reps)
         elif args.move or args.move_parent:
             res = move_leg(model, args.reps, parent=args.move_parent)
