@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_move.hip", "se_warp.hip", "se_filter.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_move.hip", "se_warp.hip", "se_filter.hip", "se_adjust.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
            "se_plan.hip", "se_api_window.hip", "se_api_select.hip", "se_api_move.hip", "se_api_codec.hip", "se_api_debug.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
@@ -80,6 +80,13 @@ WARP_MAX_COEF, WARP_MAX_TRANSLATION = 1 << 20, 1 << 40      # SE_WARP_MAX_COEF, 
 FILTER_SYMBOLS = ["se_filter_blur_u8", "se_filter_mosaic_u8"]
 FILTER_MAX_RADIUS, FILTER_ONE, FILTER_MAX_CELL = 32, 4096, 64      # SE_FILTER_MAX_RADIUS, SE_FILTER_ONE, SE_FILTER_MAX_CELL
 FILTER_MIN_AMOUNT, FILTER_MAX_AMOUNT, FILTER_MAX_FEATHER = -256, 1024, 16      # SE_FILTER_MIN_AMOUNT, SE_FILTER_MAX_AMOUNT, SE_FILTER_MAX_FEATHER
+
+# every symbol declared in include/sketchedit_adjust.h (adjust a selection's tone and colour)
+ADJUST_SYMBOLS = ["se_adjust_u8", "se_adjust_hist_u8_workspace_bytes", "se_adjust_hist_u8", "se_adjust_lut_u8"]
+ADJUST_MAX_COEF, ADJUST_MAX_OFFSET, ADJUST_ONE_AMOUNT = 32768, 1 << 20, 256      # SE_ADJUST_MAX_COEF, SE_ADJUST_MAX_OFFSET, SE_ADJUST_ONE_AMOUNT
+ADJUST_MAX_FEATHER, ADJUST_MAX_CLIP, ADJUST_HIST_GROUPS = 16, 200, 256      # SE_ADJUST_MAX_FEATHER, SE_ADJUST_MAX_CLIP, SE_ADJUST_HIST_GROUPS
+ADJUST_STRETCH, ADJUST_EQUALIZE, ADJUST_MATCH = 0, 1, 2      # SE_ADJUST_STRETCH, SE_ADJUST_EQUALIZE, SE_ADJUST_MATCH
+ADJUST_PER_CHANNEL, ADJUST_LUMA = 0, 1      # SE_ADJUST_PER_CHANNEL, SE_ADJUST_LUMA
 
 
 class SketchEditHipError(RuntimeError):
@@ -313,6 +320,14 @@ def load_library():
         lib.se_filter_blur_u8.restype = ci
         lib.se_filter_mosaic_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 7
         lib.se_filter_mosaic_u8.restype = ci
+        lib.se_adjust_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 4 + [vp, vp, ci, ci]
+        lib.se_adjust_u8.restype = ci
+        lib.se_adjust_hist_u8_workspace_bytes.argtypes = [ci, ci]
+        lib.se_adjust_hist_u8_workspace_bytes.restype = sz
+        lib.se_adjust_hist_u8.argtypes = [vp, vp, vp, ci, ci, vp] + [ci] * 4 + [vp, vp, sz]
+        lib.se_adjust_hist_u8.restype = ci
+        lib.se_adjust_lut_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
+        lib.se_adjust_lut_u8.restype = ci
         lib.se_outline_u8_workspace_bytes.argtypes = [vp, ci, ci]
         lib.se_outline_u8_workspace_bytes.restype = sz
         lib.se_outline_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, sz]
@@ -1328,6 +1343,79 @@ class Engine:
         if self.lib.se_filter_mosaic_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
                                         by0, bx0, by1, bx1, int(cell), int(amount), int(feather)):
             self._err("se_filter_mosaic_u8")
+
+    # ---- adjust a selection's tone and colour (include/sketchedit_adjust.h) ------------------------------------------------
+    def adjust_u8(self, frame, lift, lift_rect, sel, lock, box, lut=None, matrix=None, amount=256, feather=0):
+        """se_adjust_u8, in place on `frame` (Hi,Wi,3) uint8 on the device: the pixels of `box` = (by0, bx0, by1, bx1) that `sel`
+        selects and `lock` (a plane or None) does not lock become a pointwise function of the frame as `lift` holds it -- the
+        journal slot window_save_u8 made of `lift_rect` = (ly0, lx0, lh, lw), which holds the box: `lut`, 768 bytes on the device
+        (a row per channel; None: the identity), THEN `matrix`, 12 ints (m[c][j] in Q12 row by row, then o[c]; None: none) --
+        mixed with the lifted pixel by `amount` (Q8: 0 .. 256) and faded over `feather` pixels at the selection's rim.  No other
+        byte changes; the frame is never read.  One launch."""
+        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._filter_args("adjust_u8", frame, lift, lift_rect, sel, lock, box)
+        if lut is not None:
+            _check_dev_u8(lut)
+            if lut.numel() != 768:
+                raise SketchEditHipError("adjust_u8: lut is 3 x 256 uint8 on the device")
+        mp = None
+        if matrix is not None:
+            try:
+                vals = [int(v) for v in matrix]
+            except (TypeError, ValueError):
+                vals = []
+            if len(vals) != 12 or any(abs(v) >= 1 << 31 for v in vals):
+                raise SketchEditHipError("adjust_u8: matrix is 12 ints, m[c][j] row by row then o[c]")
+            mp = (ctypes.c_int * 12)(*vals)
+        if self.lib.se_adjust_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
+                                 by0, bx0, by1, bx1, _ptr(lut), mp, int(amount), int(feather)):
+            self._err("se_adjust_u8")
+
+    @staticmethod
+    def _hist_record(t, what):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == 1024):
+            raise SketchEditHipError("%s: a hist record is 4 x 256 int32 words on the device (the counts are unsigned)" % what)
+
+    def adjust_hist_u8(self, frame, sel, box, out=None):
+        """se_adjust_hist_u8: the histogram of the pixels of `box` = (by0, bx0, by1, bx1) of `frame` (Hi,Wi,3) uint8 on the device
+        that `sel` selects (an (Hi,Wi) plane; None: every pixel of the box) -> a (4, 256) int32 tensor there, rows R, G, B and
+        Y = (77 R + 150 G + 29 B + 128) >> 8, the counts unsigned 32-bit words.  Two launches, nothing comes down."""
+        import torch
+        _check_dev_u8(frame)
+        if frame.dim() != 3 or frame.shape[2] != 3:
+            raise SketchEditHipError("adjust_hist_u8: a frame is an (Hi,Wi,3) uint8 tensor")
+        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
+        if sel is not None and self._state_plane(sel, "adjust_hist_u8: sel") != (Hi, Wi):
+            raise SketchEditHipError("adjust_hist_u8: sel is the frame's (Hi,Wi) plane")
+        if out is None:
+            out = torch.empty((4, 256), dtype=torch.int32, device=frame.device)
+        self._hist_record(out, "adjust_hist_u8: out")
+        need = int(self.lib.se_adjust_hist_u8_workspace_bytes(Hi, Wi))
+        if need == 0:
+            raise SketchEditHipError("adjust_hist_u8: bad Hi=%d Wi=%d (a frame is at least 16 x 16)" % (Hi, Wi))
+        ws_t = self._workspace_bytes(need)
+        by0, bx0, by1, bx1 = (int(v) for v in box)
+        if self.lib.se_adjust_hist_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(sel), by0, bx0, by1, bx1, _ptr(out), _ptr(ws_t),
+                                      ws_t.numel()):
+            self._err("se_adjust_hist_u8")
+        return out
+
+    def adjust_lut_u8(self, hist_src, hist_ref, mode, which, clip=0, out=None):
+        """se_adjust_lut_u8: one hist record of adjust_hist_u8 (and `hist_ref`, a second one, for ADJUST_MATCH only; None otherwise)
+        -> the (3, 256) uint8 table on the device that adjust_u8 takes.  `mode` ADJUST_STRETCH (with `clip` 0 .. 200 per mille),
+        ADJUST_EQUALIZE or ADJUST_MATCH; `which` ADJUST_PER_CHANNEL or ADJUST_LUMA.  One launch, nothing comes down."""
+        import torch
+        self._hist_record(hist_src, "adjust_lut_u8: hist_src")
+        if hist_ref is not None:
+            self._hist_record(hist_ref, "adjust_lut_u8: hist_ref")
+        if out is None:
+            out = torch.empty((3, 256), dtype=torch.uint8, device=hist_src.device)
+        _check_dev_u8(out)
+        if out.numel() != 768:
+            raise SketchEditHipError("adjust_lut_u8: out is 3 x 256 uint8 on the device")
+        if self.lib.se_adjust_lut_u8(self.h, self._stream(), _ptr(hist_src), _ptr(hist_ref), int(mode), int(which), int(clip), _ptr(out)):
+            self._err("se_adjust_lut_u8")
+        return out
 
     # ---- region edits (DESIGN.md 6h) ------------------------------------------------------------------------------------------
     def sketch_tiles_u8(self, sketch_u8, tile, out=None):

@@ -1,7 +1,9 @@
 // The editing sessions' move entries behind include/sketchedit_move.h: the drop of a lifted selection and the shift of its plane
 // (kernels: se_move.hip); and behind include/sketchedit_warp.h the drop through an affine map and the warp
 // of the plane (kernels: se_warp.hip); and behind include/sketchedit_filter.h the blur and the mosaic of a
-// selection (kernels: se_filter.hip).
+// selection (kernels: se_filter.hip); and behind include/sketchedit_adjust.h the tone and colour of a selection,
+// the histogram and the table made of it (kernels: se_adjust.hip).
+#include "../../include/sketchedit_adjust.h"
 #include "../../include/sketchedit_filter.h"
 #include "../../include/sketchedit_move.h"
 #include "../../include/sketchedit_warp.h"
@@ -52,10 +54,9 @@ int warp_check_map(se_ctx* c, int by0, int bx0, int by1, int bx1, int ry0, int r
   return 0;
 }
 
-// what both filters share: the frame, the lift, the box inside it, the overlaps, the amount and the feather; `grow` = the blur's
-// radius (0 for the mosaic): the lift rectangle holds the box grown by it and clipped to the frame
-int filter_check(se_ctx* c, const unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh, int lw,
-                 const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, int grow, int amount, int feather) {
+// what the filters (6t) and the adjustment (6u) share, in two steps: the frame, the lift and the box inside it ...
+int lift_check_shape(se_ctx* c, const unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh, int lw,
+                     const unsigned char* sel_u8, int by0, int bx0, int by1, int bx1) {
   if (!frame_u8) return fail(c, "null pointer argument: frame_u8");
   if (!lift) return fail(c, "null pointer argument: lift");
   if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
@@ -64,7 +65,24 @@ int filter_check(se_ctx* c, const unsigned char* frame_u8, int Hi, int Wi, const
   if (ly0 < 0 || lx0 < 0 || lh > Hi || lw > Wi || ly0 > Hi - lh || lx0 > Wi - lw)
     return fail(c, "the lift rectangle (ly0=%d lx0=%d, %d x %d) lies outside the frame (Hi=%d Wi=%d)", ly0, lx0, lh, lw, Hi, Wi);
   if (!aligned_to(lift, 16)) return fail(c, "lift must be 16-byte aligned");
-  if (move_check_map(c, by0, bx0, by1, bx1, ly0, lx0, lh, lw, "lift rectangle", 0, 0, 0)) return 1;
+  return move_check_map(c, by0, bx0, by1, bx1, ly0, lx0, lh, lw, "lift rectangle", 0, 0, 0);
+}
+
+// ... and the lift and the planes against the frame's bytes
+int lift_check_overlaps(se_ctx* c, const unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int lh, int lw,
+                        const unsigned char* sel_u8, const unsigned char* lock_u8) {
+  const size_t pn = (size_t)Hi * Wi, lpitch = ((size_t)3 * lw + 15) & ~(size_t)15, ln = (size_t)lh * lpitch;
+  if (overlaps(lift, ln, frame_u8, 3 * pn)) return fail(c, "lift overlaps frame_u8");
+  if (overlaps(sel_u8, pn, frame_u8, 3 * pn)) return fail(c, "sel_u8 overlaps frame_u8");
+  if (lock_u8 && overlaps(lock_u8, pn, frame_u8, 3 * pn)) return fail(c, "lock_u8 overlaps frame_u8");
+  return 0;
+}
+
+// what both filters share: the above, the amount and the feather; `grow` = the blur's radius (0 for the mosaic): the lift rectangle
+// holds the box grown by it and clipped to the frame
+int filter_check(se_ctx* c, const unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh, int lw,
+                 const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, int grow, int amount, int feather) {
+  if (lift_check_shape(c, frame_u8, Hi, Wi, lift, ly0, lx0, lh, lw, sel_u8, by0, bx0, by1, bx1)) return 1;
   if (amount < SE_FILTER_MIN_AMOUNT || amount > SE_FILTER_MAX_AMOUNT)
     return fail(c, "bad amount=%d (%d .. %d, Q8)", amount, SE_FILTER_MIN_AMOUNT, SE_FILTER_MAX_AMOUNT);
   if (feather < 0 || feather > SE_FILTER_MAX_FEATHER) return fail(c, "bad feather=%d (0 .. %d)", feather, SE_FILTER_MAX_FEATHER);
@@ -73,11 +91,7 @@ int filter_check(se_ctx* c, const unsigned char* frame_u8, int Hi, int Wi, const
   if (gy0 < ly0 || gx0 < lx0 || gy1 > ly0 + lh || gx1 > lx0 + lw)
     return fail(c, "the lift rectangle (ly0=%d lx0=%d, %d x %d) does not contain the box (%d, %d, %d, %d) grown by radius=%d and clipped to the frame",
                 ly0, lx0, lh, lw, by0, bx0, by1, bx1, grow);
-  const size_t pn = (size_t)Hi * Wi, lpitch = ((size_t)3 * lw + 15) & ~(size_t)15, ln = (size_t)lh * lpitch;
-  if (overlaps(lift, ln, frame_u8, 3 * pn)) return fail(c, "lift overlaps frame_u8");
-  if (overlaps(sel_u8, pn, frame_u8, 3 * pn)) return fail(c, "sel_u8 overlaps frame_u8");
-  if (lock_u8 && overlaps(lock_u8, pn, frame_u8, 3 * pn)) return fail(c, "lock_u8 overlaps frame_u8");
-  return 0;
+  return lift_check_overlaps(c, frame_u8, Hi, Wi, lift, lh, lw, sel_u8, lock_u8);
 }
 
 }  // namespace
@@ -196,6 +210,79 @@ int se_filter_mosaic_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi
   const int lpitch = (3 * lw + 15) & ~15;
   HIPCHK(c, launch_filter_mosaic(frame_u8, Hi, Wi, lift, ly0, lx0, lw, lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, cell, amount, feather,
                                  (hipStream_t)stream));
+  return 0;
+}
+
+int se_adjust_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh, int lw,
+                 const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, const unsigned char* lut,
+                 const int* matrix, int amount, int feather) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (lift_check_shape(c, frame_u8, Hi, Wi, lift, ly0, lx0, lh, lw, sel_u8, by0, bx0, by1, bx1)) return 1;
+  for (int k = 0; matrix && k < 12; ++k) {
+    const int lim = k < 9 ? SE_ADJUST_MAX_COEF : SE_ADJUST_MAX_OFFSET;
+    if (matrix[k] < -lim || matrix[k] > lim)
+      return fail(c, "bad matrix: matrix[%d]=%d (%s at most %d in magnitude)", k, matrix[k], k < 9 ? "a coefficient is" : "an offset is", lim);
+  }
+  if (amount < 0 || amount > SE_ADJUST_ONE_AMOUNT) return fail(c, "bad amount=%d (0 .. %d, Q8)", amount, SE_ADJUST_ONE_AMOUNT);
+  if (feather < 0 || feather > SE_ADJUST_MAX_FEATHER) return fail(c, "bad feather=%d (0 .. %d)", feather, SE_ADJUST_MAX_FEATHER);
+  if (lift_check_overlaps(c, frame_u8, Hi, Wi, lift, lh, lw, sel_u8, lock_u8)) return 1;
+  if (lut && overlaps(lut, 768, frame_u8, (size_t)3 * Hi * Wi)) return fail(c, "lut overlaps frame_u8");
+  if (device_enter(c)) return 1;
+  const int lpitch = (3 * lw + 15) & ~15;
+  HIPCHK(c, launch_adjust(frame_u8, Hi, Wi, lift, ly0, lx0, lw, lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, lut, matrix, amount, feather,
+                          (hipStream_t)stream));
+  return 0;
+}
+
+size_t se_adjust_hist_u8_workspace_bytes(int Hi, int Wi) {
+  if (Hi < 16 || Wi < 16) return 0;
+  return (size_t)adjust_hist_groups(Hi, Wi) * 4096;
+}
+
+int se_adjust_hist_u8(se_ctx* c, void* stream, const unsigned char* frame_u8, int Hi, int Wi, const unsigned char* sel_u8, int by0, int bx0,
+                      int by1, int bx1, unsigned int* hist, void* workspace, size_t workspace_bytes) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!frame_u8) return fail(c, "null pointer argument: frame_u8");
+  if (!hist) return fail(c, "null pointer argument: hist_dev");
+  if (!workspace) return fail(c, "null pointer argument: workspace");
+  if (move_check_frame(c, Hi, Wi)) return 1;
+  if (move_check_map(c, by0, bx0, by1, bx1, 0, 0, Hi, Wi, "frame", 0, 0, 0)) return 1;
+  if (!aligned_to(hist, 4)) return fail(c, "hist_dev must be 4-byte aligned");
+  const size_t need = se_adjust_hist_u8_workspace_bytes(Hi, Wi), pn = (size_t)Hi * Wi;
+  if (workspace_bytes < need) return fail(c, "workspace too small: %zu bytes, need %zu", workspace_bytes, need);
+  if (!aligned_to(workspace, 256)) return fail(c, "workspace must be 256-byte aligned");
+  if (overlaps(hist, 4096, frame_u8, 3 * pn)) return fail(c, "hist_dev overlaps frame_u8");
+  if (overlaps(workspace, need, frame_u8, 3 * pn)) return fail(c, "workspace overlaps frame_u8");
+  if (overlaps(hist, 4096, workspace, need)) return fail(c, "hist_dev overlaps the workspace");
+  if (sel_u8 && overlaps(hist, 4096, sel_u8, pn)) return fail(c, "hist_dev overlaps sel_u8");
+  if (sel_u8 && overlaps(workspace, need, sel_u8, pn)) return fail(c, "workspace overlaps sel_u8");
+  if (device_enter(c)) return 1;
+  const hipStream_t st = (hipStream_t)stream;
+  if (poison(c, workspace, need, st)) return 1;
+  HIPCHK(c, launch_hist_tiles(frame_u8, Wi, sel_u8, by0, bx0, by1, bx1, (unsigned*)workspace, st));
+  HIPCHK(c, launch_hist_sum((const unsigned*)workspace, adjust_hist_groups(by1 - by0, bx1 - bx0), hist, st));
+  return 0;
+}
+
+int se_adjust_lut_u8(se_ctx* c, void* stream, const unsigned int* hist_src, const unsigned int* hist_ref, int mode, int which, int clip,
+                     unsigned char* lut) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!hist_src) return fail(c, "null pointer argument: hist_src_dev");
+  if (!lut) return fail(c, "null pointer argument: lut_dev");
+  if (mode != SE_ADJUST_STRETCH && mode != SE_ADJUST_EQUALIZE && mode != SE_ADJUST_MATCH) return fail(c, "bad mode=%d (SE_ADJUST_STRETCH, _EQUALIZE or _MATCH)", mode);
+  if (which != SE_ADJUST_PER_CHANNEL && which != SE_ADJUST_LUMA) return fail(c, "bad which=%d (SE_ADJUST_PER_CHANNEL or _LUMA)", which);
+  if (clip < 0 || clip > SE_ADJUST_MAX_CLIP) return fail(c, "bad clip=%d (0 .. %d per mille)", clip, SE_ADJUST_MAX_CLIP);
+  if (mode == SE_ADJUST_MATCH && !hist_ref) return fail(c, "null pointer argument: hist_ref_dev (SE_ADJUST_MATCH takes a reference)");
+  if (mode != SE_ADJUST_MATCH && hist_ref) return fail(c, "hist_ref_dev is for SE_ADJUST_MATCH only (mode=%d)", mode);
+  if (!aligned_to(hist_src, 4)) return fail(c, "hist_src_dev must be 4-byte aligned");
+  if (hist_ref && !aligned_to(hist_ref, 4)) return fail(c, "hist_ref_dev must be 4-byte aligned");
+  if (overlaps(lut, 768, hist_src, 4096)) return fail(c, "lut_dev overlaps hist_src_dev");
+  if (hist_ref && overlaps(lut, 768, hist_ref, 4096)) return fail(c, "lut_dev overlaps hist_ref_dev");
+  if (device_enter(c)) return 1;
+  HIPCHK(c, launch_adjust_lut(hist_src, hist_ref, mode, which, clip, lut, (hipStream_t)stream));
   return 0;
 }
 

@@ -22,7 +22,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
                  PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW,
-                 PL_LASSO_FILL, PL_PLANE_COMBINE, PL_OUTLINE_COUNT, PL_OUTLINE_SCAN, PL_OUTLINE_EMIT, PL_FILTER_BLUR, PL_FILTER_MOSAIC, PL_MOVE_DROP,
+                 PL_LASSO_FILL, PL_PLANE_COMBINE, PL_ADJUST, PL_HIST_TILES, PL_HIST_SUM, PL_ADJUST_LUT, PL_OUTLINE_COUNT, PL_OUTLINE_SCAN, PL_OUTLINE_EMIT, PL_FILTER_BLUR, PL_FILTER_MOSAIC, PL_MOVE_DROP,
                  PL_PLANE_SHIFT, PL_WARP_DROP, PL_PLANE_WARP, PL_COUNT };
 const char* prof_label_name(int l);
 // Rec::form: the kernel form of the launch (a static string, finer than the label: DESIGN.md 3.1f) -- what a test reads to
@@ -483,6 +483,18 @@ hipError_t launch_filter_blur(unsigned char* frame, int Hi, int Wi, const unsign
 hipError_t launch_filter_mosaic(unsigned char* frame, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lw, int lpitch,
                                 const unsigned char* sel, const unsigned char* lock, int by0, int bx0, int by1, int bx1, int cell, int amount,
                                 int feather, hipStream_t st);
+// adjust a selection's tone and colour (include/sketchedit_adjust.h; se_adjust.hip).  Any Hi, Wi >= 16 and any
+// alignment of the frame, the planes and the table.  adjust: the grid is the box's 64 x 16 tiles, the frame is only written, every
+// input pixel comes from the lift; lut: 768 bytes on the device or nullptr, matrix: 12 ints on the host or nullptr.  hist_tiles:
+// adjust_hist_groups(box height, box width) workgroups, each writing 1024 words of `slabs`; hist_sum adds them into `hist`.
+int adjust_hist_groups(int bh, int bw);
+hipError_t launch_adjust(unsigned char* frame, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lw, int lpitch,
+                         const unsigned char* sel, const unsigned char* lock, int by0, int bx0, int by1, int bx1, const unsigned char* lut,
+                         const int* matrix, int amount, int feather, hipStream_t st);
+hipError_t launch_hist_tiles(const unsigned char* frame, int Wi, const unsigned char* sel, int by0, int bx0, int by1, int bx1, unsigned* slabs,
+                             hipStream_t st);
+hipError_t launch_hist_sum(const unsigned* slabs, int groups, unsigned* hist, hipStream_t st);
+hipError_t launch_adjust_lut(const unsigned* hist_src, const unsigned* hist_ref, int mode, int which, int clip, unsigned char* lut, hipStream_t st);
 // scale and rotate a selection (include/sketchedit_warp.h; se_warp.hip).  Any Hi, Wi >= 16 and any alignment of the
 // frame and the planes.  m: the six Q16 values of the inverse map, on the host.  warp_drop: the selected pixels of the box, as
 // the lift holds them, gathered through m with bilinear taps and blended by their coverage into the rectangle (ry0, rx0, rh, rw)

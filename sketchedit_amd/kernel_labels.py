@@ -63,6 +63,10 @@ KERNEL_LABELS = {
     "(anonymous namespace)::filter_blur_kernel<32>": "filter_blur", "(anonymous namespace)::filter_mosaic_kernel": "filter_mosaic",
     "filter_blur_kernel<8>": "filter_blur", "filter_blur_kernel<16>": "filter_blur", "filter_blur_kernel<32>": "filter_blur",
     "filter_mosaic_kernel": "filter_mosaic",
+    # adjust a selection's tone and colour (se_adjust.hip): the pointwise kernel, the histogram's two steps, the table builder
+    "(anonymous namespace)::adjust_kernel": "adjust", "(anonymous namespace)::hist_tiles_kernel": "hist_tiles",
+    "(anonymous namespace)::hist_sum_kernel": "hist_sum", "(anonymous namespace)::adjust_lut_kernel": "adjust_lut",
+    "adjust_kernel": "adjust", "hist_tiles_kernel": "hist_tiles", "hist_sum_kernel": "hist_sum", "adjust_lut_kernel": "adjust_lut",
     # the undo journal of a session (se_window.hip)
     "(anonymous namespace)::window_save_kernel": "window_save", "(anonymous namespace)::window_swap_kernel": "window_swap",
     "window_save_kernel": "window_save", "window_swap_kernel": "window_swap",

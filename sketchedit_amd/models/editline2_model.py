@@ -266,6 +266,22 @@ class EditLine2Model(torch.nn.Module):
         the lift (Engine.filter_mosaic_u8)."""
         self.engine().filter_mosaic_u8(frame, lift, lift_rect, sel, lock, box, cell, amount=amount, feather=feather)
 
+    def adjust_u8(self, frame, lift, lift_rect, sel, lock, box, lut=None, matrix=None, amount=256, feather=0):
+        """The tone and colour of a selection (serve.EditSession.adjust_selection is the caller-facing form): the
+        selected pixels of `box` become the table `lut`, then the `matrix`, of the frame as the journal slot `lift` of `lift_rect`
+        holds it (Engine.adjust_u8)."""
+        self.engine().adjust_u8(frame, lift, lift_rect, sel, lock, box, lut=lut, matrix=matrix, amount=amount, feather=feather)
+
+    def adjust_hist_u8(self, frame, sel, box, out=None):
+        """The histogram of the selected pixels of `box`: a (4, 256) int32 tensor on the device, rows R, G, B and
+        luma (Engine.adjust_hist_u8)."""
+        return self.engine().adjust_hist_u8(frame, sel, box, out=out)
+
+    def adjust_lut_u8(self, hist_src, hist_ref, mode, which, clip=0, out=None):
+        """A table for adjust_u8 made on the device from one or two hist records: stretch, equalize or match
+        (Engine.adjust_lut_u8)."""
+        return self.engine().adjust_lut_u8(hist_src, hist_ref, mode, which, clip=clip, out=out)
+
     def window_save_u8(self, frames, origins, window_hw):
         """The undo journal's save: the (hs, ws) rectangle at origins[i] of every resident frame -> one new
         slot tensor per request; called in front of a committing edit_window_u8 it keeps the bytes the paste replaces."""

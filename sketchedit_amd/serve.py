@@ -454,6 +454,140 @@ def filter_rect(box, radius, frame_hw):
     return move_rect((by0 - r, bx0 - r, by1 + r, bx1 + r), (0, 0), frame_hw)
 
 
+ADJUST_ONE = 4096                    # 1.0 in the Q12 of an adjustment's matrix
+ADJUST_MAX_COEF = 32768              # SE_ADJUST_MAX_COEF
+ADJUST_MAX_OFFSET = 1 << 20          # SE_ADJUST_MAX_OFFSET
+ADJUST_MAX_CLIP = 200                # SE_ADJUST_MAX_CLIP, per mille
+ADJUST_GREY = (1225, 2404, 467)      # the luma weights in Q12: a row of the matrix of saturation 0
+ADJUST_AUTO = {"levels": 0, "equalize": 1, "match": 2}      # SE_ADJUST_STRETCH, SE_ADJUST_EQUALIZE, SE_ADJUST_MATCH
+ADJUST_WHICH = {"channels": 0, "luma": 1}                   # SE_ADJUST_PER_CHANNEL, SE_ADJUST_LUMA
+
+
+def _adjust_number(v, lo, hi, what):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not lo <= v <= hi:
+        raise ValueError("%s is a number %g .. %g (got %r)" % (what, lo, hi, v))
+    return float(v)
+
+
+def adjust_lut(brightness=0, contrast=0, gamma=1.0, levels=None, curve=None, invert=False, posterize=None):
+    """A table for EditSession.adjust_selection (pure host arithmetic) -> a (3, 256) uint8 array, the same row for the
+    three channels.  Every value v = 0 .. 255 goes through the steps below IN THIS ORDER, as a float clamped to 0 .. 255 after each
+    step, and is rounded once at the end, floor(x + 0.5):
+      1. `levels` = (black, white) or (black, white, out_black, out_white), ints 0 .. 255 with black < white:
+         x = out_black + (out_white - out_black) clamp((x - black) / (white - black), 0, 1);
+      2. `gamma` 0.1 .. 10: x = 255 (x / 255) ^ (1 / gamma) -- above 1 lifts the mid-tones;
+      3. `contrast` -100 .. 100 about the pivot 128 and `brightness` -255 .. 255: x = (x - 128) (100 + contrast) / 100 + 128 + brightness;
+      4. `curve` = [(x0, y0), (x1, y1), ...], ints 0 .. 255, at least two points, x strictly increasing: linear between the points,
+         flat outside them;
+      5. `posterize` = n in 2 .. 256 levels: x = floor(x n / 256) 255 / (n - 1);
+      6. `invert`: x = 255 - x.
+    ValueError for a bad argument."""
+    b = _adjust_number(brightness, -255, 255, "brightness")
+    c = _adjust_number(contrast, -100, 100, "contrast")
+    g = _adjust_number(gamma, 0.1, 10, "gamma")
+    if levels is not None:
+        try:
+            levels = tuple(levels)
+        except TypeError:
+            raise ValueError("levels is (black, white) or (black, white, out_black, out_white) (got %r)" % (levels,))
+        if len(levels) not in (2, 4):
+            raise ValueError("levels is (black, white) or (black, white, out_black, out_white) (got %r)" % (levels,))
+        levels = tuple(_filter_int(v, 0, 255, "a level") for v in levels)
+        if not levels[0] < levels[1]:
+            raise ValueError("levels: black < white (got %r)" % (levels,))
+    if curve is not None:
+        try:
+            curve = [(_filter_int(px, 0, 255, "a curve point's x"), _filter_int(py, 0, 255, "a curve point's y")) for px, py in curve]
+        except TypeError:
+            raise ValueError("curve is a list of (x, y) points (got %r)" % (curve,))
+        if len(curve) < 2 or any(a[0] >= b_[0] for a, b_ in zip(curve, curve[1:])):
+            raise ValueError("curve: at least two points, x strictly increasing (got %r)" % (curve,))
+    if not isinstance(invert, (bool, np.bool_)):
+        raise ValueError("invert is a bool (got %r)" % (invert,))
+    if posterize is not None:
+        posterize = _filter_int(posterize, 2, 256, "posterize")
+    clamp = lambda x: min(max(x, 0.0), 255.0)       # noqa: E731
+    row = []
+    for v in range(256):
+        x = float(v)
+        if levels is not None:
+            t = min(max((x - levels[0]) / float(levels[1] - levels[0]), 0.0), 1.0)
+            x = clamp(t * 255.0) if len(levels) == 2 else clamp(levels[2] + (levels[3] - levels[2]) * t)
+        if g != 1.0:
+            x = clamp(255.0 * (x / 255.0) ** (1.0 / g))
+        x = clamp((x - 128.0) * (100.0 + c) / 100.0 + 128.0 + b)
+        if curve is not None:
+            if x <= curve[0][0]:
+                x = float(curve[0][1])
+            elif x >= curve[-1][0]:
+                x = float(curve[-1][1])
+            else:
+                k = max(i for i in range(len(curve) - 1) if curve[i][0] <= x)
+                (xa, ya), (xb, yb) = curve[k], curve[k + 1]
+                x = ya + (yb - ya) * (x - xa) / float(xb - xa)
+        if posterize is not None:
+            x = clamp(math.floor(x * posterize / 256.0) * 255.0 / (posterize - 1))
+        if invert:
+            x = 255.0 - x
+        row.append(int(math.floor(x + 0.5)))
+    return np.tile(np.asarray(row, np.uint8), (3, 1))
+
+
+def adjust_matrix(saturation=1.0, hue=0.0, mix=None):
+    """The 12 ints of an adjustment's matrix (pure host arithmetic): m[c][j] in Q12 row by row, then o[c].
+    `hue` (degrees, -360 .. 360) turns the colour about the grey axis, then `saturation` (0 .. 4) scales its distance from the luma
+    (77, 150, 29) / 256 -- in Q12 (1225, 2404, 467): saturation 0 gives three such rows, the grey matrix; 1 and hue 0 the identity.
+    Every row sums to exactly 4096 -- a grey pixel stays what it is: the off-diagonal entries are rounded, the diagonal takes the
+    rest; o = 0.  `mix` gives the matrix itself and excludes the other two: three rows of three floats (1.0 = 4096, |v| <= 8) or of
+    four, the fourth an offset in pixel values (|v| <= 256).  ValueError for a bad argument."""
+    s = _adjust_number(saturation, 0, 4, "saturation")
+    h = _adjust_number(hue, -360, 360, "hue")
+    if mix is not None:
+        if s != 1.0 or h != 0.0:
+            raise ValueError("mix gives the matrix itself: it excludes saturation and hue")
+        try:
+            rows = [[v for v in r] for r in mix]
+        except TypeError:
+            raise ValueError("mix is three rows of three or four numbers (got %r)" % (mix,))
+        if len(rows) != 3 or len(rows[0]) not in (3, 4) or any(len(r) != len(rows[0]) for r in rows):
+            raise ValueError("mix is three rows of three or four numbers (got %r)" % (mix,))
+        m = [int(round(ADJUST_ONE * _adjust_number(r[j], -8, 8, "a mix coefficient"))) for r in rows for j in range(3)]
+        o = [int(round(ADJUST_ONE * _adjust_number(r[3], -256, 256, "a mix offset"))) if len(r) == 4 else 0 for r in rows]
+        return m + o
+    w = [v / float(ADJUST_ONE) for v in ADJUST_GREY]
+    cs, sn = math.cos(math.radians(h)), math.sin(math.radians(h))
+    k = sn / math.sqrt(3.0)
+    rot = [[cs + (1 - cs) / 3.0, (1 - cs) / 3.0 - k, (1 - cs) / 3.0 + k],
+           [(1 - cs) / 3.0 + k, cs + (1 - cs) / 3.0, (1 - cs) / 3.0 - k],
+           [(1 - cs) / 3.0 - k, (1 - cs) / 3.0 + k, cs + (1 - cs) / 3.0]]
+    sat = [[(1 - s) * w[j] + (s if i == j else 0.0) for j in range(3)] for i in range(3)]
+    a = [[sum(sat[i][t] * rot[t][j] for t in range(3)) for j in range(3)] for i in range(3)]
+    m = [[int(round(ADJUST_ONE * a[i][j])) for j in range(3)] for i in range(3)]
+    for i in range(3):
+        m[i][i] = ADJUST_ONE - sum(m[i][j] for j in range(3) if j != i)
+    return [m[i][j] for i in range(3) for j in range(3)] + [0, 0, 0]
+
+
+def _check_adjust_matrix(matrix):
+    try:
+        vals = list(matrix)
+    except TypeError:
+        vals = []
+    if len(vals) != 12 or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in vals):
+        raise ValueError("matrix is 12 ints, what adjust_matrix returns (got %r)" % (matrix,))
+    vals = [int(v) for v in vals]
+    if any(abs(v) > ADJUST_MAX_COEF for v in vals[:9]) or any(abs(v) > ADJUST_MAX_OFFSET for v in vals[9:]):
+        raise ValueError("matrix: a coefficient is at most %d and an offset at most %d in magnitude (got %r)" % (ADJUST_MAX_COEF, ADJUST_MAX_OFFSET, vals))
+    return vals
+
+
+def _check_adjust_lut(lut):
+    a = np.asarray(lut)
+    if a.dtype.kind not in "iu" or a.shape not in ((256,), (3, 256)) or a.min() < 0 or a.max() > 255:
+        raise ValueError("lut is a (3, 256) or (256,) array of ints 0 .. 255, what adjust_lut returns")
+    return np.ascontiguousarray(np.broadcast_to(a.astype(np.uint8), (3, 256)))
+
+
 WARP_ONE = 1 << 16                   # 1.0 in the Q16 of a warp's inverse map
 WARP_MAX_COEF = 1 << 20              # SE_WARP_MAX_COEF
 WARP_MAX_TRANSLATION = 1 << 40       # SE_WARP_MAX_TRANSLATION
@@ -965,6 +1099,21 @@ class _ModelBackend:
         """the mosaic of a selection, ONE launch in place on the frame: as filter_blur with the mean of the pixel's
         `cell` x `cell` block of the lift"""
         self.model.filter_mosaic_u8(frame, lift, lift_rect, plane, lock, box, cell, amount=amount, feather=feather)
+
+    def adjust(self, frame, lift, lift_rect, plane, lock, box, lut, matrix, amount, feather):
+        """the tone and colour of a selection, ONE launch in place on the frame: the pixels of `box` that `plane`
+        selects and `lock` (or None) leaves become the table `lut` (768 bytes on the device, or None), then the `matrix` (12 ints,
+        or None), of the frame as the slot `lift` of `lift_rect` holds it, mixed by `amount` (Q8), with a soft edge of `feather`"""
+        self.model.adjust_u8(frame, lift, lift_rect, plane, lock, box, lut=lut, matrix=matrix, amount=amount, feather=feather)
+
+    def hist(self, frame, plane, box):
+        """the histogram of the pixels of `box` that `plane` selects (None: all of them) -> a (4, 256) record that STAYS on the
+        device: two launches, no download"""
+        return self.model.adjust_hist_u8(frame, plane, box)
+
+    def hist_lut(self, src, ref, mode, which, clip):
+        """one or two hist records -> the table `adjust` takes, made and left on the device: one launch, no download"""
+        return self.model.adjust_lut_u8(src, ref, mode, which, clip=clip)
 
     def save(self, frames, origins, window_hw):
         """the windows' rectangles -> one new journal slot each, on the stream the edit follows on"""
@@ -1939,6 +2088,113 @@ class EditSession:
             locked = self._lock_plane is not None
         info = dict(windows=wins, filter=kind, radius=radius, amount=amount, cell=cell, selected=selection.count)
         return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, None, undoable, feather)
+
+    # ---- adjust a selection's tone and colour ---------------------------------------------------------------------------
+    def adjust_selection(self, selection, lut=None, matrix=None, auto=None, reference=None, which="luma", clip=0, amount=1.0, feather=None,
+                         encode=None):
+        """"Brighten that face, desaturate the background, make what I just dropped match the place it landed in" (DESIGN.md 6u):
+        the selected pixels become a pointwise function of the frame as it is now -- a table, then a matrix.
+          `lut`     a (3, 256) or (256,) table of ints 0 .. 255 (adjust_lut makes them), or
+          `auto`    a table made ON THE DEVICE from histograms of the frame, nothing coming down: "levels" (the selection's range
+                    stretched to 0 .. 255, `clip` per mille, 0 .. 200, of its pixels cut off at either end), "equalize", or "match"
+                    (the selection's distribution made that of `reference`: a Selection of this session -- "make this look like
+                    that" -- or ("rim", r), r = 1 .. 16: the ring of pixels within r of the selection and outside it -- "match
+                    where it landed").  `which`: "luma" (one table from the luma of the pixels, for all three channels) or
+                    "channels" (a table per channel).  `auto` excludes `lut`; `reference` and `clip` go with their mode only;
+          `matrix`  12 ints (adjust_matrix makes them), applied AFTER the table, with either of the above or alone;
+          `amount`  0.0 .. 1.0, the opacity of the adjustment; `feather` = f (None or 0 .. 16) fades it in over f pixels at the rim.
+        Integer arithmetic (include/sketchedit_adjust.h): the same bytes on every machine.  Everything happens on the device under
+        ONE hold of the session's lock:
+          1. the LIFT: move_rect(box, (0, 0)) of the frame is saved into a slot;
+          2. with `auto`: the ring, if one is asked for (grow and combine); the histogram of the selection and, for "match", of
+             the reference; the table made of them -- no download between them;
+          3. ONE launch adjusts the lifted pixels into the frame where the selection selects and the lock plane does not lock;
+          4. with history on the lift IS the journal entry's slot, so the call is one undo step of the single-window kind and makes
+             no second save; a lift above `history_bytes` commits unjournalled and clears the history, and so does a backend call
+             that fails once the adjustment was launched.
+        The selection stays what it was.  -> (patches, positions, info) in edit_regions' shape over ONE window, the lift's;
+        `encode` applies.  info = dict(windows, adjust="lut" | "auto" | "matrix" | "lut+matrix" | "auto+matrix", auto, which,
+        amount, selected) plus undoable / locked / feather where `edit` reports them (which None without `auto`).
+        TypeError / ValueError, all before the first backend call: a selection that is none, of another frame size or empty,
+        nothing to apply, a bad lut, matrix, auto, reference, which, clip, amount, feather or encode."""
+        encode = _check_encode(encode)
+        feather = _check_feather(feather)
+        self._check_selection(selection, "adjust_selection")
+        if selection.box is None:
+            raise ValueError("empty selection: nothing to adjust")
+        if auto is not None and (not isinstance(auto, str) or auto not in ADJUST_AUTO):
+            raise ValueError("auto is None or one of %s (got %r)" % (", ".join(repr(k) for k in ADJUST_AUTO), auto))
+        if lut is not None and auto is not None:
+            raise ValueError("auto makes the table: it excludes lut")
+        if lut is None and auto is None and matrix is None:
+            raise ValueError("nothing to adjust: give lut, auto or matrix")
+        if lut is not None:
+            lut = _check_adjust_lut(lut)
+        if matrix is not None:
+            matrix = _check_adjust_matrix(matrix)
+        if not isinstance(which, str) or which not in ADJUST_WHICH:
+            raise ValueError("which is one of %s (got %r)" % (", ".join(repr(k) for k in ADJUST_WHICH), which))
+        clip = _filter_int(clip, 0, ADJUST_MAX_CLIP, "clip")
+        if clip and auto != "levels":
+            raise ValueError("clip goes with auto='levels' only (got %r)" % (clip,))
+        rim = None
+        if auto == "match":
+            if isinstance(reference, Selection):
+                self._check_selection(reference, "adjust_selection: reference")
+                if reference.box is None:
+                    raise ValueError("empty reference: nothing to match")
+            elif isinstance(reference, tuple) and len(reference) == 2 and isinstance(reference[0], str) and reference[0] == "rim":
+                rim = _filter_int(reference[1], 1, SELECT_MAX_GROW, "the rim's width")
+            else:
+                raise TypeError("auto='match' takes reference=<a Selection> or ('rim', r) (got %r)" % (reference,))
+        elif reference is not None:
+            raise ValueError("reference goes with auto='match' only")
+        amount = _adjust_number(amount, 0, 1, "amount")
+        q8 = int(round(256 * amount))
+        box = selection.box
+        lift_rect = move_rect(box, (0, 0), self.frame_hw)
+        wins = [lift_rect]
+        journal = self._journals(lift_rect[2], lift_rect[3])
+        be = self.backend
+        with self._lock:
+            frames = [self._frame]
+            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
+            table = be.upload(lut) if lut is not None else None
+            if auto is not None:
+                ref = None
+                if rim is not None:
+                    ring, rbox, _ = be.combine(be.grow(selection.plane, rim), selection.plane, COMBINE_OPS["subtract"])
+                    ref = (ring, rbox or box)                    # no ring at all (the selection is the frame): an empty record, the identity
+                elif auto == "match":
+                    ref = (reference.plane, reference.box)
+                src = be.hist(self._frame, selection.plane, box)
+                ref = be.hist(self._frame, ref[0], ref[1]) if ref is not None else None
+                table = be.hist_lut(src, ref, ADJUST_AUTO[auto], ADJUST_WHICH[which], clip)
+            try:
+                be.adjust(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, table, matrix, q8, feather or 0)
+                undoable = self._record(lift_rect, lift if journal else None) if self.history > 0 else None
+                patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames, wins)
+            except Exception:                    # the adjustment may be in the frame: no entry restores a state it was in
+                self._undo.clear()
+                self._redo.clear()
+                raise
+            locked = self._lock_plane is not None
+        what = "+".join(k for k, on in (("lut", lut is not None), ("auto", auto is not None), ("matrix", matrix is not None)) if on)
+        info = dict(windows=wins, adjust=what, auto=auto, which=which if auto is not None else None, amount=amount, selected=selection.count)
+        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, None, undoable, feather)
+
+    def histogram(self, selection=None):
+        """The histogram of the frame (`selection` None) or of a selection's pixels, for a front end's display: a
+        (4, 256) uint32 array on the host, rows R, G, B and luma Y = (77 R + 150 G + 29 B + 128) >> 8.  Counted on the device; ONE
+        download of 4 KB.  The lock plays no part.  An empty selection gives zeros without a backend call."""
+        if selection is not None:
+            self._check_selection(selection, "histogram")
+            if selection.box is None:
+                return np.zeros((4, 256), np.uint32)
+        with self._lock:
+            box = selection.box if selection is not None else (0, 0) + self.frame_hw
+            rec = self.backend.hist(self._frame, selection.plane if selection is not None else None, box)
+            return np.ascontiguousarray(self.backend.download(rec)).view(np.uint32).reshape(4, 256)
 
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""

@@ -201,6 +201,22 @@ plus se_profile_report's per-kernel times of one (b), (c) and (d) request (filte
 --move on the parent commit's build in the same job is the comparison leg (its clone_selection: a lift, one small launch, one
 patch download):
     python tools/serve_probe.py --filter [--reps N] [--out FILE]
+
+--adjust: adjust a selection's tone and colour: --move's frame and disc; every leg but the histograms runs on the FLAT
+disc (select_similar's selection: every lane of a histogram wave on one counter) and on a disc of the same size in the NOISE (a
+lasso); the frame is put back (a device copy, not timed) in front of every timed call:
+  (a) edit:        EditSession.edit(window=..., max_grow=0), the unchanged control,
+  (b) blur_r8:     EditSession.filter_selection(selection, "blur"), radius 8 -- the leg --filter has on the parent commit's build,
+  (c) manual:      EditSession.adjust_selection(selection, lut=adjust_lut(brightness=30, contrast=20), matrix=adjust_matrix(1.3)),
+  (d) levels:      adjust_selection(selection, auto="levels", clip=5),
+  (e) match_rim8:  adjust_selection(selection, auto="match", reference=("rim", 8)),
+  (f) histogram:   EditSession.histogram(selection), the 4 KB download,
+  (g) host_route:  session.frame() (the 6 MB download), the table applied through the mask in numpy, a NEW session of the result
+                   (the 6 MB upload) -- what a front end does without adjust_selection; the undo journal, the lock plane and
+                   every Selection are lost,
+plus se_profile_report's per-kernel times of one (c), (d), (e) and (f) request (adjust, hist_tiles, hist_sum, adjust_lut, window_save
+among them).  --filter on the parent commit's build in the same job is the comparison leg:
+    python tools/serve_probe.py --adjust [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -1444,6 +1460,97 @@ def filter_leg(model, reps, side=512, tolerance=16):
     return out
 
 
+def adjust_leg(model, reps, side=512, tolerance=16):
+    """(a) .. (g) of the module docstring"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    frame[..., 0] = frame[..., 0] % 90                               # no noise pixel is similar to the disc's colour
+    win = (283, 705, side, side)
+    seed = (win[0] + side // 2, win[1] + side // 2)
+    yy, xx = np.mgrid[0:h, 0:w]
+    disc = (yy - seed[0]) ** 2 + (xx - seed[1]) ** 2 <= 126 ** 2
+    frame[disc] = 128
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    dev0 = torch.from_numpy(frame).cuda()
+
+    def fresh(session):
+        def put_back():
+            session._frame.copy_(dev0)
+            torch.cuda.synchronize()
+        return put_back
+
+    def timed(fn, put_back=lambda: None):
+        def rounds():
+            for _ in range(2):                 # warm-up: plans, workspace, code objects
+                put_back()
+                fn()
+            ts = []
+            for _ in range(reps):
+                put_back()
+                t0 = time.perf_counter()
+                fn()                           # ends in a device-to-host copy: the request is complete
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts.sort()
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    s1, s2, s3 = serve.EditSession(model, frame), serve.EditSession(model, frame), serve.EditSession(model, frame)
+    flat = s2.select_similar(seed, tolerance=tolerance)
+    cy, cx = 300, 300                                                # a disc of the same radius in the noise, as a lasso of 256 points
+    ring = [(cx + 0.5 + 126.2 * np.cos(t), cy + 0.5 + 126.2 * np.sin(t)) for t in np.linspace(0, 2 * np.pi, 256, endpoint=False)]
+    noise = s2.select_lasso([ring])
+    table, matrix = serve.adjust_lut(brightness=30, contrast=20), serve.adjust_matrix(1.3)
+
+    def host_route():
+        f = s3.frame()
+        mask = (np.abs(f.astype(np.int16) - f[seed]).max(axis=2) <= tolerance)              # (the disc: no flood on this route)
+        by0, bx0, by1, bx1 = flat.box
+        f = f.copy()
+        crop = f[by0:by1, bx0:bx1]
+        m = mask[by0:by1, bx0:bx1]
+        crop[m] = table[0][crop[m]]
+        s = serve.EditSession(model, f)
+        return s._frame[by0:by1, bx0:bx1].contiguous().cpu().numpy()                        # the patch a front end shows
+
+    T = s2.adjust_selection
+    legs = dict(edit=timed(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True), fresh(s1)),
+                blur_r8=timed(lambda: s2.filter_selection(flat, "blur", radius=8), fresh(s2)),
+                host_route=timed(host_route, fresh(s3)))
+    for name, sel in (("flat", flat), ("noise", noise)):
+        legs["manual_" + name] = timed(lambda sel=sel: T(sel, lut=table, matrix=matrix), fresh(s2))
+        legs["levels_" + name] = timed(lambda sel=sel: T(sel, auto="levels", clip=5), fresh(s2))
+        legs["match_rim8_" + name] = timed(lambda sel=sel: T(sel, auto="match", reference=("rim", 8)), fresh(s2))
+        legs["histogram_" + name] = timed(lambda sel=sel: s2.histogram(sel))
+    out = dict(tool="serve_probe --adjust", B=1, reps=reps, mode="low_latency", frame=[w, h], window=list(win), seed=list(seed), tolerance=tolerance,
+               disc_pixels=int(disc.sum()))
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    eng = model.engine()
+    for name, sel in (("flat", flat), ("noise", noise)):
+        for leg, call in (("manual", lambda sel=sel: T(sel, lut=table, matrix=matrix)), ("levels", lambda sel=sel: T(sel, auto="levels", clip=5)),
+                          ("match_rim8", lambda sel=sel: T(sel, auto="match", reference=("rim", 8))), ("histogram", lambda sel=sel: s2.histogram(sel))):
+            fresh(s2)()
+            eng.profile(True)
+            call()
+            rep = eng.profile_report()
+            eng.profile(False)
+            out["%s_%s_profiled" % (leg, name)] = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+            out["%s_%s_changed_bytes" % (leg, name)] = int((s2._frame != dev0).sum())
+    out.update(selected=dict(flat=flat.count, noise=noise.count), box=dict(flat=list(flat.box), noise=list(noise.box)),
+               manual_minus_blur_r8_ms=round(out["ms"]["manual_flat"]["median"] - out["ms"]["blur_r8"]["median"], 3),
+               manual_minus_host_route_ms=round(out["ms"]["manual_flat"]["median"] - out["ms"]["host_route"]["median"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -1477,6 +1584,7 @@ def main():
     ap.add_argument("--move-parent", action="store_true", help="the edit leg of --move only")
     ap.add_argument("--warp", action="store_true", help="scale and rotate a selection (see the module docstring)")
     ap.add_argument("--filter", action="store_true", help="blur, sharpen or pixelate a selection (see the module docstring)")
+    ap.add_argument("--adjust", action="store_true", help="adjust a selection's tone and colour (see the module docstring)")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -1489,8 +1597,10 @@ def main():
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
             or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent
-            or args.move or args.move_parent or args.warp or args.filter):
-        if args.filter:
+            or args.move or args.move_parent or args.warp or args.filter or args.adjust):
+        if args.adjust:
+            res = adjust_leg(model, args.reps)
+        elif args.filter:
             res = filter_leg(model, args.reps)
         elif args.warp:
             res = warp_leg(model, args.reps)
