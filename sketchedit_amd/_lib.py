@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_outline.hip", "se_move.hip", "se_warp.hip", "se_filter.hip", "se_adjust.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_modify.hip", "se_outline.hip", "se_move.hip", "se_warp.hip", "se_filter.hip", "se_adjust.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
            "se_plan.hip", "se_api_window.hip", "se_api_select.hip", "se_api_move.hip", "se_api_codec.hip", "se_api_debug.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
@@ -87,6 +87,10 @@ ADJUST_MAX_COEF, ADJUST_MAX_OFFSET, ADJUST_ONE_AMOUNT = 32768, 1 << 20, 256     
 ADJUST_MAX_FEATHER, ADJUST_MAX_CLIP, ADJUST_HIST_GROUPS = 16, 200, 256      # SE_ADJUST_MAX_FEATHER, SE_ADJUST_MAX_CLIP, SE_ADJUST_HIST_GROUPS
 ADJUST_STRETCH, ADJUST_EQUALIZE, ADJUST_MATCH = 0, 1, 2      # SE_ADJUST_STRETCH, SE_ADJUST_EQUALIZE, SE_ADJUST_MATCH
 ADJUST_PER_CHANNEL, ADJUST_LUMA = 0, 1      # SE_ADJUST_PER_CHANNEL, SE_ADJUST_LUMA
+# every symbol declared in include/sketchedit_modify.h (modify a selection's shape)
+MODIFY_SYMBOLS = ["se_plane_modify_u8"]
+MODIFY_MAX_RADIUS = 32                            # SE_MODIFY_MAX_RADIUS
+MODIFY_EXPAND, MODIFY_CONTRACT, MODIFY_SMOOTH = range(3)      # SE_MODIFY_*
 
 
 class SketchEditHipError(RuntimeError):
@@ -308,7 +312,9 @@ def load_library():
         lib.se_lasso_fill_u8.restype = ci
         lib.se_plane_combine_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
         lib.se_plane_combine_u8.restype = ci
-        lib.se_move_drop_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8
+        lib.se_plane_modify_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
+        lib.se_plane_modify_u8.restype = ci
+        lib.se_move_drop_u8.argtypes =[vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8
         lib.se_move_drop_u8.restype = ci
         lib.se_plane_shift_u8.argtypes = [vp, vp, vp, ci, ci] + [ci] * 7 + [vp]
         lib.se_plane_shift_u8.restype = ci
@@ -1186,6 +1192,22 @@ class Engine:
             raise SketchEditHipError("plane_combine_u8: out is a plane of a's shape")
         if self.lib.se_plane_combine_u8(self.h, self._stream(), _ptr(a), _ptr(b), Hi, Wi, int(op), _ptr(out)):
             self._err("se_plane_combine_u8")
+        return out
+
+    # ---- modify a selection's shape (include/sketchedit_modify.h) ----------------------------------------------------
+    def plane_modify_u8(self, plane, op, radius, out=None):
+        """se_plane_modify_u8: a plane (Hi,Wi) uint8 on the device, non-zero = selected -> `out` (a NEW plane, or another plane of
+        that shape that shares no byte with it; any alignment; every byte is written), 0 / 255: op MODIFY_EXPAND the pixels
+        within the disc of `radius` (1 .. 32) of a selected one, MODIFY_CONTRACT the selected pixels with no unselected pixel
+        of the frame in their disc, MODIFY_SMOOTH the majority vote in the disc (a tie keeps the pixel).  One launch."""
+        import torch
+        Hi, Wi = self._state_plane(plane, "plane_modify_u8: plane")
+        if out is None:
+            out = torch.empty((Hi, Wi), dtype=torch.uint8, device=plane.device)
+        if self._state_plane(out, "plane_modify_u8: out") != (Hi, Wi):
+            raise SketchEditHipError("plane_modify_u8: out is a plane of the plane's shape")
+        if self.lib.se_plane_modify_u8(self.h, self._stream(), _ptr(plane), Hi, Wi, int(op), int(radius), _ptr(out)):
+            self._err("se_plane_modify_u8")
         return out
 
     # ---- the outline of a selection (DESIGN.md 6q, include/sketchedit_outline.h) ------------------------------------------------------

@@ -1,8 +1,9 @@
-// The editing sessions' selection entries behind include/sketchedit_select.h, sketchedit_lasso.h and sketchedit_outline.h:
-// selection by colour, lasso selections and their algebra, and the outline of a selection (kernels: se_select.hip, se_lasso.hip,
-// se_outline.hip).
+// The editing sessions' selection entries behind include/sketchedit_select.h, sketchedit_lasso.h, sketchedit_modify.h and
+// sketchedit_outline.h: selection by colour, lasso selections and their algebra, the modification of a selection's shape, and the
+// outline of a selection (kernels: se_select.hip, se_lasso.hip, se_modify.hip, se_outline.hip).
 #include "../../include/sketchedit_select.h"
 #include "../../include/sketchedit_lasso.h"
+#include "../../include/sketchedit_modify.h"
 #include "../../include/sketchedit_outline.h"
 #include "se_host.h"
 
@@ -115,6 +116,24 @@ int se_plane_combine_u8(se_ctx* c, void* stream, const unsigned char* a, const u
   if (b && out != b && overlaps(out, n, b, n)) return fail(c, "out overlaps b (it may be b itself)");
   if (device_enter(c)) return 1;
   HIPCHK(c, launch_plane_combine(a, b, Hi, Wi, op, out, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- modify a selection's shape (include/sketchedit_modify.h) ------------------------------------------------
+// Every check on the host, then ONE launch that writes the caller's plane directly: no workspace, nothing for SE_TEST_POISON to
+// fill.
+int se_plane_modify_u8(se_ctx* c, void* stream, const unsigned char* plane, int Hi, int Wi, int op, int radius, unsigned char* out) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (lasso_check_plane(c, Hi, Wi)) return 1;
+  if (op < SE_MODIFY_EXPAND || op > SE_MODIFY_SMOOTH) return fail(c, "bad op=%d (0 .. 2)", op);
+  if (radius < 1 || radius > SE_MODIFY_MAX_RADIUS) return fail(c, "bad radius=%d (1 .. %d)", radius, SE_MODIFY_MAX_RADIUS);
+  if (!plane) return fail(c, "null pointer argument: plane");
+  if (!out) return fail(c, "null pointer argument: out");
+  const size_t n = (size_t)Hi * Wi;
+  if (overlaps(out, n, plane, n)) return fail(c, "out overlaps plane (a tile reads the halo its neighbours store: not in place)");
+  if (device_enter(c)) return 1;
+  HIPCHK(c, launch_plane_modify(plane, Hi, Wi, op, radius, out, (hipStream_t)stream));
   return 0;
 }
 

@@ -21,7 +21,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
-                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW,
+                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW, PL_MODIFY_DISC, PL_MODIFY_VOTE,
                  PL_LASSO_FILL, PL_PLANE_COMBINE, PL_ADJUST, PL_HIST_TILES, PL_HIST_SUM, PL_ADJUST_LUT, PL_OUTLINE_COUNT, PL_OUTLINE_SCAN, PL_OUTLINE_EMIT, PL_FILTER_BLUR, PL_FILTER_MOSAIC, PL_MOVE_DROP,
                  PL_PLANE_SHIFT, PL_WARP_DROP, PL_PLANE_WARP, PL_COUNT };
 const char* prof_label_name(int l);
@@ -451,6 +451,10 @@ hipError_t launch_select_similar(const unsigned char* frame, int Hi, int Wi, int
 hipError_t launch_select_flood(unsigned char* state, int Hi, int Wi, unsigned* changed, hipStream_t st);
 // grow: out (another buffer) = 255 where a reached byte lies within Chebyshev distance `grow` (0 .. 16), else 0; every byte written
 hipError_t launch_select_grow(const unsigned char* state, int Hi, int Wi, int grow, unsigned char* out, hipStream_t st);
+// modify a selection's shape (include/sketchedit_modify.h; se_modify.hip).  Any Hi, Wi >= 16 and any alignment of the
+// planes; no byte outside a plane is read or written.  Every byte of `out` (another buffer) <- `plane` expanded or contracted by
+// the disc of `radius` (1 .. 32), or smoothed by the majority vote in it (op: SE_MODIFY_*), as 0 / 255.  ONE launch.
+hipError_t launch_plane_modify(const unsigned char* plane, int Hi, int Wi, int op, int radius, unsigned char* out, hipStream_t st);
 // lasso selections and their algebra (include/sketchedit_lasso.h; se_lasso.hip).  Any Hi, Wi >= 16 and any alignment
 // of the planes; no byte outside a plane or the edge buffer is read or written.
 // lasso_fill: every byte of plane_out (Hi,Wi) <- the even-odd fill of the N edges [ax, ay, bx, by] (int32, quarter pixels)

@@ -44,6 +44,9 @@ KERNEL_LABELS = {
     "(anonymous namespace)::select_similar_kernel": "select_similar", "(anonymous namespace)::select_flood_kernel": "select_flood",
     "(anonymous namespace)::select_grow_kernel": "select_grow",
     "select_similar_kernel": "select_similar", "select_flood_kernel": "select_flood", "select_grow_kernel": "select_grow",
+    # modify a selection's shape (se_modify.hip): expand / contract by a disc, and the majority vote in it
+    "(anonymous namespace)::modify_disc_kernel": "modify_disc", "(anonymous namespace)::modify_vote_kernel": "modify_vote",
+    "modify_disc_kernel": "modify_disc", "modify_vote_kernel": "modify_vote",
     # lasso selections and their algebra (se_lasso.hip)
     "(anonymous namespace)::lasso_fill_kernel": "lasso_fill", "(anonymous namespace)::plane_combine_kernel": "plane_combine",
     "lasso_fill_kernel": "lasso_fill", "plane_combine_kernel": "plane_combine",

@@ -229,6 +229,12 @@ class EditLine2Model(torch.nn.Module):
         b None (Engine.plane_combine_u8)."""
         return self.engine().plane_combine_u8(a, b, op, out=out)
 
+    def plane_modify_u8(self, plane, op, radius, out=None):
+        """A selection plane expanded or contracted by a disc of `radius`, or smoothed by the majority vote in it (DESIGN.md 6w;
+        serve.EditSession.modify_selection is the caller-facing form): a new 0 / 255 plane; op = _lib.MODIFY_EXPAND / CONTRACT /
+        SMOOTH (Engine.plane_modify_u8)."""
+        return self.engine().plane_modify_u8(plane, op, radius, out=out)
+
     def outline_u8(self, plane, cap):
         """The outline of a selection plane (serve.Selection.rings is the caller-facing form): ONE int32 device
         tensor, [total, written] and then the first min(total, cap) boundary records in the lasso's edge format

@@ -270,6 +270,10 @@ def stroke_box(segs, frame_hw):
 LASSO_MAX_EDGES = 65536     # SE_LASSO_MAX_EDGES
 COMBINE_OPS = {"add": 0, "subtract": 1, "intersect": 2, "xor": 3}     # SE_COMBINE_*
 COMBINE_INVERT = 4
+MODIFY_OPS = {"expand": 0, "contract": 1, "smooth": 2}                  # SE_MODIFY_*
+MODIFY_KINDS = ("expand", "contract", "border", "smooth")
+MODIFY_SIDES = ("inside", "outside", "both")
+MODIFY_MAX_RADIUS = 32       # SE_MODIFY_MAX_RADIUS
 
 
 def lasso_edges(rings, frame_hw):
@@ -1048,6 +1052,16 @@ class _ModelBackend:
         box, count = tiles_box(self.tiles(plane, 32))
         return plane, box, count
 
+    def modify(self, plane, op, radius, tiles=True):
+        """a selection plane expanded, contracted or smoothed by the disc of `radius` -> (plane, box, count) of a NEW
+        plane: one launch, then the tile records of the result -- the one download; op is SE_MODIFY_*'s value.  tiles=False: an
+        intermediate of a border, nothing comes down and box and count are None"""
+        out = self.model.plane_modify_u8(plane, op, radius)
+        if not tiles:
+            return out, None, None
+        box, count = tiles_box(self.tiles(out, 32))
+        return out, box, count
+
     def outline(self, plane, cap):
         """the boundary records of a plane on the device: three launches and ONE download, of 8 + 16 cap bytes
         -> (total, records (min(total, cap), 4) int32 on the host)"""
@@ -1815,6 +1829,47 @@ class EditSession:
         with self._lock:
             plane, box, count = self.backend.combine(a.plane, None, COMBINE_INVERT)
         return Selection(self.backend, plane, box, count, self.frame_hw)
+
+    # ---- modify a selection's shape -----------------------------------------------------------------------------------
+    def modify_selection(self, selection, kind, radius, side="both"):
+        """"Select > Modify" (DESIGN.md 6w): a selection of this frame -> a NEW one whose shape is changed by a round brush of
+        `radius` (an int 1 .. 32, in frame pixels), made on the device.  `kind`:
+          "expand"    every pixel within `radius` (Euclidean) of a selected one;
+          "contract"  the selected pixels with no unselected pixel of the frame within `radius`: a selection that touches the
+                      frame's edge does not shrink away from it;
+          "border"    a rim of the selection: `side` "inside" (the selection minus its contraction), "outside" (its expansion
+                      minus the selection) or "both" (the expansion minus the contraction);
+          "smooth"    the majority vote in the disc: specks and pinholes smaller than half a disc go, corners are rounded.
+        `side` belongs to "border" alone.  One hold of the session's lock; one backend call, or for a border one or two
+        modifications and one subtraction, of which only the last one's tile records come down.  The operand stays what it was;
+        the result may be empty.  Not an edit: nothing is journalled; the frame and the lock play no part.
+        An empty operand gives the empty selection with no backend call (the result shares the operand's all-zero plane).
+        TypeError for an operand that is not a Selection; ValueError for one made on a frame of another size, an unknown kind
+        or side, a side with another kind than "border", a radius that is not an int 1 .. 32; NotImplementedError from a backend
+        that cannot modify selections -- all before the first backend call."""
+        self._check_selection(selection, "modify_selection")
+        if not isinstance(kind, str) or kind not in MODIFY_KINDS:
+            raise ValueError("kind is one of %s (got %r)" % (", ".join(repr(k) for k in MODIFY_KINDS), kind))
+        if not isinstance(side, str) or side not in MODIFY_SIDES:
+            raise ValueError("side is one of %s (got %r)" % (", ".join(repr(k) for k in MODIFY_SIDES), side))
+        if kind != "border" and side != "both":
+            raise ValueError("side belongs to kind 'border' alone (got side=%r with kind=%r)" % (side, kind))
+        if not isinstance(radius, (int, np.integer)) or isinstance(radius, (bool, np.bool_)) or not 1 <= radius <= MODIFY_MAX_RADIUS:
+            raise ValueError("radius is an int 1 .. %d, in frame pixels (got %r)" % (MODIFY_MAX_RADIUS, radius))
+        radius = int(radius)
+        be = self.backend
+        if not hasattr(be, "modify"):
+            raise NotImplementedError("this session's backend (%s) cannot modify selections: it has no `modify`" % type(be).__name__)
+        if selection.box is None:
+            return Selection(be, selection.plane, None, 0, self.frame_hw)
+        with self._lock:
+            if kind != "border":
+                plane, box, count = be.modify(selection.plane, MODIFY_OPS[kind], radius)
+            else:
+                outer = selection.plane if side == "inside" else be.modify(selection.plane, MODIFY_OPS["expand"], radius, tiles=False)[0]
+                inner = selection.plane if side == "outside" else be.modify(selection.plane, MODIFY_OPS["contract"], radius, tiles=False)[0]
+                plane, box, count = be.combine(outer, inner, COMBINE_OPS["subtract"])
+        return Selection(be, plane, box, count, self.frame_hw)
 
     def fill_lasso(self, rings, grow=2, sketch=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None,
                    feather=None):

@@ -217,6 +217,20 @@ lasso); the frame is put back (a device copy, not timed) in front of every timed
 plus se_profile_report's per-kernel times of one (c), (d), (e) and (f) request (adjust, hist_tiles, hist_sum, adjust_lut, window_save
 among them).  --filter on the parent commit's build in the same job is the comparison leg:
     python tools/serve_probe.py --adjust [--reps N] [--out FILE]
+
+--modify: expand, contract, border and smooth a selection: --move's frame and its disc of 49 861 pixels, selected by
+colour; nothing changes the frame, every timed call ends in the download of the tile records:
+  (a) combine:       EditSession.combine(selection, lasso, "subtract"), the unchanged control: one launch and the tile records,
+  (b) expand_r2 / expand_r32, contract_r2 / contract_r32, smooth_r2 / smooth_r32: EditSession.modify_selection,
+  (c) border_r8:     modify_selection(selection, "border", 8): two modifications, one subtraction, one download,
+  (d) grow_r16:      the backend's Chebyshev grow by 16 and the tile records -- the kernel an expand is measured against,
+  (e) host_route:    selection.mask() (the box's download), scipy.ndimage.binary_dilation by the disc of radius 8, the result
+                     pasted into a frame-sized mask and uploaded -- what a front end does without modify_selection (no box and
+                     no count come of it); only where scipy is installed,
+plus se_profile_report's per-kernel times of one request of every kind (modify_disc, modify_vote, plane_combine, select_grow,
+sketch_tiles).  --modify-parent runs (a) alone, with the calls a build without modifications has: the comparison leg on the parent
+commit's build in the same job:
+    python tools/serve_probe.py --modify [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -1551,6 +1565,91 @@ def adjust_leg(model, reps, side=512, tolerance=16):
     return out
 
 
+def modify_leg(model, reps, parent=False, side=512, tolerance=16):
+    """(a) .. (e) of the module docstring; parent=True: the leg (a) only, with the calls a build without modifications has"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    frame[..., 0] = frame[..., 0] % 90                               # no noise pixel is similar to the disc's colour
+    win = (283, 705, side, side)
+    seed = (win[0] + side // 2, win[1] + side // 2)
+    yy, xx = np.mgrid[0:h, 0:w]
+    disc = (yy - seed[0]) ** 2 + (xx - seed[1]) ** 2 <= 126 ** 2
+    frame[disc] = 128
+
+    def timed(fn):
+        def rounds():
+            for _ in range(2):                 # warm-up: code objects, the allocator's blocks
+                fn()
+            ts = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()                           # ends in a device-to-host copy (or, host_route, an upload waited for)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts.sort()
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    s = serve.EditSession(model, frame)
+    sel = s.select_similar(seed, tolerance=tolerance)
+    other = s.select_lasso([[(seed[1] - 40.0, seed[0] - 40.0), (seed[1] + 90.0, seed[0] - 30.0), (seed[1] + 10.0, seed[0] + 95.0)]])
+    legs = dict(combine=timed(lambda: s.combine(sel, other, "subtract").count))
+    out = dict(tool="serve_probe --modify" + ("-parent" if parent else ""), B=1, reps=reps, frame=[w, h], seed=list(seed), tolerance=tolerance,
+               disc_pixels=int(disc.sum()), selected=sel.count, box=list(sel.box))
+    not_measured = []
+    if not parent:
+        be = s.backend
+        for kind in ("expand", "contract", "smooth"):
+            for r in (2, 32):
+                legs["%s_r%d" % (kind, r)] = timed(lambda kind=kind, r=r: s.modify_selection(sel, kind, r).count)
+        legs["border_r8"] = timed(lambda: s.modify_selection(sel, "border", 8).count)
+        legs["grow_r16"] = timed(lambda: serve.tiles_box(be.tiles(be.grow(sel.plane, 16), 32)))
+        try:
+            from scipy import ndimage
+        except ImportError:
+            ndimage = None
+            not_measured.append("host_route: scipy is not installed")
+        if ndimage is not None:
+            dd = np.arange(-8, 9)
+            structure = dd[:, None] ** 2 + dd[None, :] ** 2 <= 64
+
+            def host_route():
+                y0, x0, y1, x1 = sel.box
+                m = np.zeros((h, w), bool)
+                m[y0:y1, x0:x1] = sel.mask() != 0
+                grown = ndimage.binary_dilation(m[y0 - 8:y1 + 8, x0 - 8:x1 + 8], structure=structure)
+                full = np.zeros((h, w), np.uint8)
+                full[y0 - 8:y1 + 8, x0 - 8:x1 + 8] = np.where(grown, 255, 0)
+                be.upload(full)
+                torch.cuda.synchronize()
+            legs["host_route"] = timed(host_route)
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    if not parent:
+        eng = model.engine()
+        calls = {"%s_r%d" % (kind, r): (lambda kind=kind, r=r: s.modify_selection(sel, kind, r)) for kind in ("expand", "contract", "smooth") for r in (2, 32)}
+        calls.update(border_r8=lambda: s.modify_selection(sel, "border", 8), grow_r16=lambda: be.tiles(be.grow(sel.plane, 16), 32),
+                     combine=lambda: s.combine(sel, other, "subtract"))
+        out["profiled"] = {}
+        for name, call in calls.items():       # one request each: the profiler's records start afresh when it is turned on
+            eng.profile(True)
+            call()
+            rep = eng.profile_report()
+            eng.profile(False)
+            out["profiled"][name] = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        out["expand_r32_minus_combine_ms"] = round(out["ms"]["expand_r32"]["median"] - out["ms"]["combine"]["median"], 3)
+        out["not_measured"] = not_measured
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -1585,6 +1684,8 @@ def main():
     ap.add_argument("--warp", action="store_true", help="scale and rotate a selection (see the module docstring)")
     ap.add_argument("--filter", action="store_true", help="blur, sharpen or pixelate a selection (see the module docstring)")
     ap.add_argument("--adjust", action="store_true", help="adjust a selection's tone and colour (see the module docstring)")
+    ap.add_argument("--modify", action="store_true", help="expand, contract, border and smooth a selection (see the module docstring)")
+    ap.add_argument("--modify-parent", action="store_true", help="the combine leg of --modify only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -1597,8 +1698,10 @@ def main():
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
             or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent
-            or args.move or args.move_parent or args.warp or args.filter or args.adjust):
-        if args.adjust:
+            or args.move or args.move_parent or args.warp or args.filter or args.adjust or args.modify or args.modify_parent):
+        if args.modify or args.modify_parent:
+            res = modify_leg(model, args.reps, parent=args.modify_parent)
+        elif args.adjust:
             res = adjust_leg(model, args.reps)
         elif args.filter:
             res = filter_leg(model, args.reps)
