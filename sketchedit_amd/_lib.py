@@ -1232,24 +1232,28 @@ class Engine:
         return out
 
     # ---- move or clone a selection (include/sketchedit_move.h) -------------------------------------------------------
+    def _lift_args(self, what, frame, lift, lift_rect, sel, lock, box):
+        """the checks every entry that takes a lift shares -> (Hi, Wi, lift rectangle, box) as ints"""
+        _check_dev_u8(frame)
+        if frame.dim() != 3 or frame.shape[2] != 3:
+            raise SketchEditHipError("%s: a frame is an (Hi,Wi,3) uint8 tensor" % what)
+        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
+        if self._state_plane(sel, what + ": sel") != (Hi, Wi) or (lock is not None and self._state_plane(lock, what + ": lock") != (Hi, Wi)):
+            raise SketchEditHipError("%s: sel and lock are the frame's (Hi,Wi) planes" % what)
+        lr = tuple(int(v) for v in lift_rect)
+        _check_dev_u8(lift)
+        need = self.window_saved_bytes(lr[2], lr[3])
+        if need and lift.numel() < need:
+            raise SketchEditHipError("%s: a lift holds window_saved_bytes(lh, lw) = %d bytes" % (what, need))
+        return Hi, Wi, lr, tuple(int(v) for v in box)
+
     def move_drop_u8(self, frame, lift, lift_rect, sel, lock, box, offset, flip=0, radius=0):
         """se_move_drop_u8, in place on `frame` (Hi,Wi,3) uint8 on the device: the pixels of `box` = (by0, bx0, by1, bx1) that
         `sel` (an (Hi,Wi) plane, non-zero = selected) selects, as `lift` holds them -- the journal slot window_save_u8 made of
         `lift_rect` = (ly0, lx0, lh, lw), a rectangle that holds the box -- land `offset` = (dy, dx) away, mirrored about the box
         by `flip` (MOVE_FLIP_X | MOVE_FLIP_Y), where `lock` (a plane or None) is 0; `radius` 0 .. 16 fades their rim into the
         frame.  No other byte changes.  One launch; none when the whole box lands outside the frame."""
-        _check_dev_u8(frame)
-        if frame.dim() != 3 or frame.shape[2] != 3:
-            raise SketchEditHipError("move_drop_u8: a frame is an (Hi,Wi,3) uint8 tensor")
-        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
-        if self._state_plane(sel, "move_drop_u8: sel") != (Hi, Wi) or (lock is not None and self._state_plane(lock, "move_drop_u8: lock") != (Hi, Wi)):
-            raise SketchEditHipError("move_drop_u8: sel and lock are the frame's (Hi,Wi) planes")
-        ly0, lx0, lh, lw = (int(v) for v in lift_rect)
-        _check_dev_u8(lift)
-        need = self.window_saved_bytes(lh, lw)
-        if need and lift.numel() < need:
-            raise SketchEditHipError("move_drop_u8: a lift holds window_saved_bytes(lh, lw) = %d bytes" % need)
-        by0, bx0, by1, bx1 = (int(v) for v in box)
+        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._lift_args("move_drop_u8", frame, lift, lift_rect, sel, lock, box)
         if self.lib.se_move_drop_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
                                     by0, bx0, by1, bx1, int(offset[0]), int(offset[1]), int(flip), int(radius)):
             self._err("se_move_drop_u8")
@@ -1288,18 +1292,7 @@ class Engine:
         `lift_rect` = (ly0, lx0, lh, lw), a rectangle that holds the box -- gathered through the inverse map `m` (six Q16 ints)
         with bilinear taps and blended by their coverage into `rect` = (ry0, rx0, rh, rw) of the frame where `lock` (a plane or
         None) is 0.  No other byte changes.  One launch."""
-        _check_dev_u8(frame)
-        if frame.dim() != 3 or frame.shape[2] != 3:
-            raise SketchEditHipError("warp_drop_u8: a frame is an (Hi,Wi,3) uint8 tensor")
-        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
-        if self._state_plane(sel, "warp_drop_u8: sel") != (Hi, Wi) or (lock is not None and self._state_plane(lock, "warp_drop_u8: lock") != (Hi, Wi)):
-            raise SketchEditHipError("warp_drop_u8: sel and lock are the frame's (Hi,Wi) planes")
-        ly0, lx0, lh, lw = (int(v) for v in lift_rect)
-        _check_dev_u8(lift)
-        need = self.window_saved_bytes(lh, lw)
-        if need and lift.numel() < need:
-            raise SketchEditHipError("warp_drop_u8: a lift holds window_saved_bytes(lh, lw) = %d bytes" % need)
-        by0, bx0, by1, bx1 = (int(v) for v in box)
+        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._lift_args("warp_drop_u8", frame, lift, lift_rect, sel, lock, box)
         ry0, rx0, rh, rw = (int(v) for v in rect)
         mm = self._warp_map(m, "warp_drop_u8")
         if self.lib.se_warp_drop_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
@@ -1323,21 +1316,6 @@ class Engine:
         return out
 
     # ---- blur, sharpen or pixelate a selection (include/sketchedit_filter.h) ----------------------------------------------
-    def _filter_args(self, what, frame, lift, lift_rect, sel, lock, box):
-        """the checks the two filters share -> (Hi, Wi, lift rectangle, box) as ints"""
-        _check_dev_u8(frame)
-        if frame.dim() != 3 or frame.shape[2] != 3:
-            raise SketchEditHipError("%s: a frame is an (Hi,Wi,3) uint8 tensor" % what)
-        Hi, Wi = int(frame.shape[0]), int(frame.shape[1])
-        if self._state_plane(sel, what + ": sel") != (Hi, Wi) or (lock is not None and self._state_plane(lock, what + ": lock") != (Hi, Wi)):
-            raise SketchEditHipError("%s: sel and lock are the frame's (Hi,Wi) planes" % what)
-        lr = tuple(int(v) for v in lift_rect)
-        _check_dev_u8(lift)
-        need = self.window_saved_bytes(lr[2], lr[3])
-        if need and lift.numel() < need:
-            raise SketchEditHipError("%s: a lift holds window_saved_bytes(lh, lw) = %d bytes" % (what, need))
-        return Hi, Wi, lr, tuple(int(v) for v in box)
-
     def filter_blur_u8(self, frame, lift, lift_rect, sel, lock, box, taps, amount=-256, feather=0):
         """se_filter_blur_u8, in place on `frame` (Hi,Wi,3) uint8 on the device: the pixels of `box` = (by0, bx0, by1, bx1) that
         `sel` (an (Hi,Wi) plane, non-zero = selected) selects and `lock` (a plane or None) does not lock become the separable
@@ -1345,7 +1323,7 @@ class Engine:
         window_save_u8 made of `lift_rect` = (ly0, lx0, lh, lw), a rectangle that holds the box grown by R and clipped to the
         frame -- mixed with the lifted pixel by `amount` (Q8: -256 the blur, > 0 an unsharp mask) and faded over `feather`
         pixels at the selection's rim.  No other byte changes; the frame is never read.  One launch."""
-        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._filter_args("filter_blur_u8", frame, lift, lift_rect, sel, lock, box)
+        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._lift_args("filter_blur_u8", frame, lift, lift_rect, sel, lock, box)
         try:
             vals = [int(v) for v in taps]
         except (TypeError, ValueError):
@@ -1361,7 +1339,7 @@ class Engine:
         """se_filter_mosaic_u8, in place on `frame`: as filter_blur_u8 with the mean of the pixel's `cell` x `cell` block (2 .. 64,
         anchored at the box's origin and clipped to the box, taken over all its lifted pixels) in place of the blur; `lift_rect`
         holds the box.  One launch."""
-        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._filter_args("filter_mosaic_u8", frame, lift, lift_rect, sel, lock, box)
+        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._lift_args("filter_mosaic_u8", frame, lift, lift_rect, sel, lock, box)
         if self.lib.se_filter_mosaic_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
                                         by0, bx0, by1, bx1, int(cell), int(amount), int(feather)):
             self._err("se_filter_mosaic_u8")
@@ -1374,7 +1352,7 @@ class Engine:
         (a row per channel; None: the identity), THEN `matrix`, 12 ints (m[c][j] in Q12 row by row, then o[c]; None: none) --
         mixed with the lifted pixel by `amount` (Q8: 0 .. 256) and faded over `feather` pixels at the selection's rim.  No other
         byte changes; the frame is never read.  One launch."""
-        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._filter_args("adjust_u8", frame, lift, lift_rect, sel, lock, box)
+        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._lift_args("adjust_u8", frame, lift, lift_rect, sel, lock, box)
         if lut is not None:
             _check_dev_u8(lut)
             if lut.numel() != 768:

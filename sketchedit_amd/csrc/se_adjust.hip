@@ -3,16 +3,14 @@
 // LDS), nothing polled, any alignment of the frame, the planes, the table and Wi, no byte outside the frame, a plane, the table's
 // 768 or the first 3 lw bytes of the slot's rows read or written.
 //
-//  adjust:      the grid covers the 64 x 16 tiles of the BOX, never the frame; one workgroup = one tile, 256 lanes, a lane owns 4
-//               consecutive pixels of a row.  The frame is only WRITTEN: every input pixel comes from the lift.
-//                select: the lane's 4 bytes of S, bounded by the tile's row; no selected pixel in the tile: return before any
-//                        other load.  Then the lock's bytes of the selected pixels; no target left: return.
+//  adjust:      the grid covers se_seltile.h's tiles of the BOX, never the frame.  The frame is only WRITTEN: every input pixel
+//               comes from the lift.
+//                select: select_targets; no selected pixel in the tile: return before any other load.  Then unlocked_targets; no
+//                        target left: return.
 //                stage:  the table's 768 bytes -> LDS, a dword per lane of the first 192 (load4_within: any alignment); with f > 0
-//                        the box's S around the tile and its horizontal counts exactly as filter_blur stages them (6t).
+//                        stage_sel_in_box and count_rows.
 //                point:  a target's lane reads its 12 bytes of the lift (three bounded dwords), looks each byte up, applies the
-//                        matrix in int32, mixes by the amount, blends by the count.  Stores follow se_window.hip's ownership
-//                        rule: three dwords where all four pixels are targets and the address is aligned, single bytes of
-//                        targets otherwise.
+//                        matrix in int32, mixes by the amount, blends by the count (count4, BoxDiv).  Stores: store_targets.
 //  hist_tiles:  at most SE_ADJUST_HIST_GROUPS workgroups stride over the box's 64 x 16 tiles; 4 x 4 x 256 counters in LDS, a
 //               sub-histogram per WAVE.  A flat selection (what select_similar makes) puts every lane on one counter: a wave whose
 //               active lanes all hold one value adds their number once, from one lane; otherwise each lane adds 1.  At the end
@@ -23,10 +21,8 @@
 //               by a binary search over cdf_ref.  768 byte stores, one writer each.
 #include "../../include/sketchedit_hip.h"
 #include "../../include/sketchedit_adjust.h"
-#include "se_device.h"
 #include "se_kernels.h"
-
-#include <cstdint>
+#include "se_seltile.h"
 
 namespace se {
 
@@ -34,11 +30,7 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int AJ_W = 64, AJ_H = 16, AJ_FMAX = SE_ADJUST_MAX_FEATHER;
-constexpr int AJ_SEL_PITCH = 192;                     // bytes: 48 dwords = 16 mod 32 (se_feather.hip)
-constexpr int AJ_SEL_ROWS = AJ_H + 2 * AJ_FMAX;       // staged rows of S at the largest feather
 constexpr int AJ_LUT_BYTES = 768;
-constexpr int AJ_F_BYTES = AJ_SEL_ROWS * AJ_SEL_PITCH + AJ_SEL_ROWS * AJ_W;
 
 // the matrix by value: m[3 c + j], then o[c]; on = 0: none
 struct AdjustMatrix {
@@ -46,108 +38,45 @@ struct AdjustMatrix {
   int on;
 };
 
-// the lift: the slot's row of frame row y is [p + (y - ly0) lpitch, + 3 lw), its pixel x at 3 (x - lx0)
-struct Lift {
-  const unsigned char* p;
-  int ly0, lx0, lw, lpitch;
-};
-
-// each non-zero byte of u -> 1
-__device__ __forceinline__ unsigned bytes_nonzero(unsigned u) {
-  return ((u & 0xffu) ? 1u : 0u) | ((u & 0xff00u) ? 0x100u : 0u) | ((u & 0xff0000u) ? 0x10000u : 0u) | ((u & 0xff000000u) ? 0x1000000u : 0u);
-}
-
-// S != 0 of the pixels (y, x .. x + 3) that lie in the box, a byte of {0, 1} each; nothing outside the box's row of S is read
-__device__ __forceinline__ unsigned sel4_in_box(const unsigned char* sel, int Wi, int by0, int bx0, int by1, int bx1, int y, int x) {
-  if (y < by0 || y >= by1 || x + 3 < bx0 || x >= bx1) return 0u;
-  const unsigned char* row = sel + (size_t)y * Wi;
-  return bytes_nonzero(load4_within(row + x, row + bx0, row + bx1));
-}
-
 __global__ void __launch_bounds__(256) adjust_kernel(unsigned char* __restrict__ frame, int Wi, Lift lift, const unsigned char* __restrict__ sel,
                                                      const unsigned char* __restrict__ lock, int by0, int bx0, int by1, int bx1,
                                                      const unsigned char* __restrict__ lut, AdjustMatrix mx, int amount, int f) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
   unsigned* s_lut = (unsigned*)s_mem;                                       // the table: 192 dwords
-  unsigned* s_sel = (unsigned*)(s_mem + AJ_LUT_BYTES);                      // f > 0: {0, 1} per pixel; row pitch AJ_SEL_PITCH bytes
-  unsigned* s_row = s_sel + AJ_SEL_ROWS * AJ_SEL_PITCH / 4;                 // f > 0: horizontal counts, a byte per pixel; pitch AJ_W
+  unsigned* s_sel = (unsigned*)(s_mem + AJ_LUT_BYTES);                      // f > 0: {0, 1} per pixel; row pitch SEL_PITCH bytes
+  unsigned* s_row = s_sel + SEL_ROWS * SEL_PITCH / 4;                       // f > 0: horizontal counts, a byte per pixel; pitch SEL_W
   const int tid = threadIdx.x;
-  const int tx0 = bx0 + blockIdx.x * AJ_W, ty0 = by0 + blockIdx.y * AJ_H;   // the tile, in frame pixels, clipped to the box
-  const int tx1 = min(tx0 + AJ_W, bx1), ty1 = min(ty0 + AJ_H, by1);
+  const int tx0 = bx0 + blockIdx.x * SEL_W, ty0 = by0 + blockIdx.y * SEL_H; // the tile, in frame pixels, clipped to the box
+  const int tx1 = min(tx0 + SEL_W, bx1), ty1 = min(ty0 + SEL_H, by1);
   const int lx = 4 * (tid & 15), ly = tid >> 4;
   const int x = tx0 + lx, y = ty0 + ly;                                     // the lane's 4 pixels (y, x .. x + 3)
 
   // ---- select: S of the lane's pixels, then the lock of the selected ones
-  unsigned tg = 0;                                                          // a byte per pixel, {0, 1}: selected, then target
-  int npx = 0;
-  if (y < ty1 && x < tx1) {
-    npx = min(4, tx1 - x);
-    const unsigned char* srow = sel + (size_t)y * Wi + x;                   // the lane's bytes of S: [srow, srow + npx)
-    tg = bytes_nonzero(load4_within(srow, srow, srow + npx));
-  }
+  int npx;
+  unsigned tg = select_targets(sel, Wi, y, x, ty1, tx1, npx);               // a byte per pixel, {0, 1}: selected, then target
   if (!__syncthreads_or((int)tg)) return;                                   // nothing selected under the tile: nothing else is loaded
-  if (lock && tg) {
-    const unsigned char* lrow = lock + (size_t)y * Wi + x;
-    tg &= ~bytes_nonzero(load4_within(lrow, lrow, lrow + npx));
-  }
+  tg = unlocked_targets(tg, lock, Wi, y, x, npx);
   if (!__syncthreads_or((int)tg)) return;
 
   // ---- stage: the table, and with a feather S around the tile
   if (lut && tid < AJ_LUT_BYTES / 4) s_lut[tid] = load4_within(lut + 4 * tid, lut, lut + AJ_LUT_BYTES);
-  const int frows = AJ_H + 2 * f;
-  if (f > 0) {                                                              // staged S (i, j) = S != 0 in the box at (ty0 - f + i, tx0 - f + j)
-    const int cols4 = (AJ_W + 2 * f + 3) >> 2;
-    for (int t = tid; t < frows * cols4; t += 256) {
-      const int i = t / cols4, j4 = t % cols4;
-      s_sel[i * (AJ_SEL_PITCH / 4) + j4] = sel4_in_box(sel, Wi, by0, bx0, by1, bx1, ty0 - f + i, tx0 - f + 4 * j4);
-    }
+  if (f > 0) {
+    stage_sel_in_box(s_sel, sel, Wi, by0, bx0, by1, bx1, ty0, tx0, f, tid);
     __syncthreads();
-    for (int t = tid; t < frows * (AJ_W / 4); t += 256) {                   // s_row (i, x) = sum of staged S (i, x .. x + 2f): se_move.hip's rows
-      const int i = t >> 4, k = t & 15;
-      const unsigned* s = s_sel + i * (AJ_SEL_PITCH / 4) + k;
-      const int nd = (2 * f + 4 + 3) >> 2;
-      unsigned char e[2 * AJ_FMAX + 4];
-#pragma unroll
-      for (int q = 0; q < (2 * AJ_FMAX + 4) / 4; ++q) {
-        const unsigned d = q < nd ? s[q] : 0u;
-#pragma unroll
-        for (int z = 0; z < 4; ++z) e[4 * q + z] = (unsigned char)((d >> (8 * z)) & 255u);
-      }
-      unsigned s0 = 0;
-#pragma unroll
-      for (int z = 0; z < 2 * AJ_FMAX + 1; ++z) s0 += z <= 2 * f ? e[z] : 0u;
-      unsigned in1 = 0, in2 = 0, in3 = 0;
-#pragma unroll
-      for (int z = 1; z < 2 * AJ_FMAX + 4; ++z) {
-        in1 = z == 2 * f + 1 ? e[z] : in1;
-        in2 = z == 2 * f + 2 ? e[z] : in2;
-        in3 = z == 2 * f + 3 ? e[z] : in3;
-      }
-      const unsigned s1 = s0 - e[0] + in1, s2 = s1 - e[1] + in2, s3 = s2 - e[2] + in3;
-      s_row[i * (AJ_W / 4) + k] = s0 | (s1 << 8) | (s2 << 16) | (s3 << 24);
-    }
+    count_rows(s_sel, s_row, SEL_H + 2 * f, f, tid);
   }
   __syncthreads();
 
   // ---- point: the lane's targets
   if (!tg) return;
-  const unsigned n = (unsigned)((2 * f + 1) * (2 * f + 1));
-  unsigned c[4] = {n, n, n, n};
-  if (f > 0) {
-    unsigned lo = 0, hi = 0;                                                // pixels 0, 2 and 1, 3 in 16-bit fields
-    for (int d = 0; d <= 2 * f; ++d) {
-      const unsigned v = s_row[(ly + d) * (AJ_W / 4) + (tid & 15)];
-      lo += v & 0x00ff00ffu;
-      hi += (v >> 8) & 0x00ff00ffu;
-    }
-    c[0] = lo & 0xffffu; c[1] = hi & 0xffffu; c[2] = lo >> 16; c[3] = hi >> 16;
-  }
-  const unsigned char* src = lift.p + (size_t)(y - lift.ly0) * lift.lpitch + 3 * (x - lift.lx0);    // the lane's bytes of P: [src, src + 3 npx)
+  const BoxDiv bd(box_area(f));
+  unsigned c[4] = {bd.n, bd.n, bd.n, bd.n};
+  if (f > 0) count4(s_row, ly, tid & 15, f, c);
+  const unsigned char* src = lift.row(y) + 3 * (x - lift.lx0);              // the lane's bytes of P: [src, src + 3 npx)
   unsigned pw[3];
 #pragma unroll
   for (int q = 0; q < 3; ++q) pw[q] = load4_within(src + 4 * q, src, src + 3 * npx);
   const unsigned char* tb = (const unsigned char*)s_lut;
-  const unsigned magic = (unsigned)((1ull << 32) / n) + 1u, half = (n - 1u) >> 1;
   unsigned o[3] = {0u, 0u, 0u};
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
@@ -167,27 +96,12 @@ __global__ void __launch_bounds__(256) adjust_kernel(unsigned char* __restrict__
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       const int j = 3 * p + ch;
-      unsigned v = (unsigned)(P[ch] + ((amount * (M[ch] - P[ch]) + 128) >> 8));
-      if (c[p] != n) v = __umulhi(c[p] * v + (n - c[p]) * (unsigned)P[ch] + half, magic);
-      o[j >> 2] |= v << (8 * (j & 3));
+      const unsigned v = (unsigned)(P[ch] + ((amount * (M[ch] - P[ch]) + 128) >> 8));
+      o[j >> 2] |= bd.blend(c[p], v, (unsigned)P[ch]) << (8 * (j & 3));
     }
   }
   unsigned char* dst = frame + ((size_t)y * Wi + x) * 3;
-  if (tg == 0x01010101u && ((uintptr_t)dst & 3) == 0) {
-    unsigned* d = (unsigned*)dst;
-    d[0] = o[0]; d[1] = o[1]; d[2] = o[2];
-    return;
-  }
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    if ((tg >> (8 * p)) & 1u) {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const int j = 3 * p + ch;
-        dst[j] = (unsigned char)((o[j >> 2] >> (8 * (j & 3))) & 255u);
-      }
-    }
-  }
+  store_targets(dst, o, tg);
 }
 
 // one counter of a wave's sub-histogram: every lane of the wave calls this (`on`: the lane has a value).  All active lanes on one
@@ -213,8 +127,8 @@ __global__ void __launch_bounds__(256) hist_tiles_kernel(const unsigned char* __
   __syncthreads();
   const int lx = 4 * (tid & 15), ly = tid >> 4;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {           // the same trips for every lane of the workgroup
-    const int tx0 = bx0 + (tile % ntx) * AJ_W, ty0 = by0 + (tile / ntx) * AJ_H;
-    const int tx1 = min(tx0 + AJ_W, bx1), ty1 = min(ty0 + AJ_H, by1);
+    const int tx0 = bx0 + (tile % ntx) * SEL_W, ty0 = by0 + (tile / ntx) * SEL_H;
+    const int tx1 = min(tx0 + SEL_W, bx1), ty1 = min(ty0 + SEL_H, by1);
     const int x = tx0 + lx, y = ty0 + ly;
     unsigned on = 0;                                                        // a byte per pixel, {0, 1}: counted
     unsigned pw[3] = {0u, 0u, 0u};
@@ -321,7 +235,7 @@ __global__ void __launch_bounds__(256) adjust_lut_kernel(const unsigned* __restr
 }  // namespace
 
 int adjust_hist_groups(int bh, int bw) {
-  const long tiles = (long)((bw + AJ_W - 1) / AJ_W) * ((bh + AJ_H - 1) / AJ_H);
+  const long tiles = (long)((bw + SEL_W - 1) / SEL_W) * ((bh + SEL_H - 1) / SEL_H);
   return (int)(tiles < SE_ADJUST_HIST_GROUPS ? tiles : SE_ADJUST_HIST_GROUPS);
 }
 
@@ -329,24 +243,24 @@ hipError_t launch_adjust(unsigned char* frame, int Hi, int Wi, const unsigned ch
                          const unsigned char* sel, const unsigned char* lock, int by0, int bx0, int by1, int bx1, const unsigned char* lut,
                          const int* matrix, int amount, int feather, hipStream_t st) {
   (void)Hi;
-  const dim3 grid((unsigned)((bx1 - bx0 + AJ_W - 1) / AJ_W), (unsigned)((by1 - by0 + AJ_H - 1) / AJ_H));
+  const dim3 grid((unsigned)((bx1 - bx0 + SEL_W - 1) / SEL_W), (unsigned)((by1 - by0 + SEL_H - 1) / SEL_H));
   const Lift lf{lift, ly0, lx0, lw, lpitch};
   AdjustMatrix mx;
   for (int k = 0; k < 12; ++k) mx.m[k] = matrix ? matrix[k] : 0;
   mx.on = matrix ? 1 : 0;
   // bytes: an upper bound (every pixel a target): S with the feather's halo, the lock, the lift, the box written
-  const double fhalo = feather ? (double)(AJ_W + 2 * feather) * (AJ_H + 2 * feather) / (double)(AJ_W * AJ_H) : 0.0;
+  const double fhalo = feather ? (double)(SEL_W + 2 * feather) * (SEL_H + 2 * feather) / (double)(SEL_W * SEL_H) : 0.0;
   set_launch_cost(0.0, (double)(by1 - by0) * (bx1 - bx0) * (1.0 + fhalo + (lock ? 1.0 : 0.0) + 6.0), "adjust");
   set_launch_grid((long)grid.x * grid.y);
   ProfScope ps_(st, PL_ADJUST);
-  hipLaunchKernelGGL(adjust_kernel, grid, dim3(256), AJ_LUT_BYTES + (feather > 0 ? AJ_F_BYTES : 0), st, frame, Wi, lf, sel, lock, by0, bx0, by1,
+  hipLaunchKernelGGL(adjust_kernel, grid, dim3(256), AJ_LUT_BYTES + (feather > 0 ? SEL_LDS_BYTES : 0), st, frame, Wi, lf, sel, lock, by0, bx0, by1,
                      bx1, lut, mx, amount, feather);
   return hipGetLastError();
 }
 
 hipError_t launch_hist_tiles(const unsigned char* frame, int Wi, const unsigned char* sel, int by0, int bx0, int by1, int bx1, unsigned* slabs,
                              hipStream_t st) {
-  const int ntx = (bx1 - bx0 + AJ_W - 1) / AJ_W, nty = (by1 - by0 + AJ_H - 1) / AJ_H;
+  const int ntx = (bx1 - bx0 + SEL_W - 1) / SEL_W, nty = (by1 - by0 + SEL_H - 1) / SEL_H;
   const int groups = adjust_hist_groups(by1 - by0, bx1 - bx0);
   set_launch_cost(0.0, (double)(by1 - by0) * (bx1 - bx0) * (sel ? 4.0 : 3.0) + 4096.0 * groups, "hist_tiles");
   set_launch_grid(groups);

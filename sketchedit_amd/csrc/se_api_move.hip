@@ -28,21 +28,24 @@ int move_check_frame(se_ctx* c, int Hi, int Wi) {
   return 0;
 }
 
-// the box against the rectangle (ry0, rx0, rh, rw) that must hold it, the offset and the flip
-int move_check_map(se_ctx* c, int by0, int bx0, int by1, int bx1, int ry0, int rx0, int rh, int rw, const char* holder, int dy, int dx,
-                   int flip) {
+// the box against the rectangle (ry0, rx0, rh, rw) that must hold it ...
+int move_check_box(se_ctx* c, int by0, int bx0, int by1, int bx1, int ry0, int rx0, int rh, int rw, const char* holder) {
   if (by1 <= by0 || bx1 <= bx0) return fail(c, "bad box (%d, %d, %d, %d): a box (by0, bx0, by1, bx1) is half open and not empty", by0, bx0, by1, bx1);
   if (by0 < ry0 || bx0 < rx0 || by1 > ry0 + rh || bx1 > rx0 + rw)
     return fail(c, "the box (%d, %d, %d, %d) lies outside the %s (y0=%d x0=%d, %d x %d)", by0, bx0, by1, bx1, holder, ry0, rx0, rh, rw);
+  return 0;
+}
+
+// ... the offset and the flip of a move ...
+int move_check_offset(se_ctx* c, int dy, int dx, int flip) {
   if (dy < -SE_MOVE_MAX_OFFSET || dy > SE_MOVE_MAX_OFFSET) return fail(c, "bad dy=%d (|dy| <= %d)", dy, SE_MOVE_MAX_OFFSET);
   if (dx < -SE_MOVE_MAX_OFFSET || dx > SE_MOVE_MAX_OFFSET) return fail(c, "bad dx=%d (|dx| <= %d)", dx, SE_MOVE_MAX_OFFSET);
   if (flip < 0 || flip > 3) return fail(c, "bad flip=%d (0 .. 3)", flip);
   return 0;
 }
 
-// the box against the rectangle that must hold it, and the six values of the inverse map (a host pointer)
-int warp_check_map(se_ctx* c, int by0, int bx0, int by1, int bx1, int ry0, int rx0, int rh, int rw, const char* holder, const long long* m) {
-  if (move_check_map(c, by0, bx0, by1, bx1, ry0, rx0, rh, rw, holder, 0, 0, 0)) return 1;
+// ... and the six values of a warp's inverse map (a host pointer)
+int warp_check_map(se_ctx* c, const long long* m) {
   if (!m) return fail(c, "null pointer argument: m");
   static const char* const names[6] = {"ayy", "ayx", "ay0", "axy", "axx", "ax0"};
   for (int i = 0; i < 6; ++i) {
@@ -54,7 +57,7 @@ int warp_check_map(se_ctx* c, int by0, int bx0, int by1, int bx1, int ry0, int r
   return 0;
 }
 
-// what the filters (6t) and the adjustment (6u) share, in two steps: the frame, the lift and the box inside it ...
+// what every entry that takes a lift shares, in two steps: the frame, the lift and the box inside it ...
 int lift_check_shape(se_ctx* c, const unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh, int lw,
                      const unsigned char* sel_u8, int by0, int bx0, int by1, int bx1) {
   if (!frame_u8) return fail(c, "null pointer argument: frame_u8");
@@ -65,7 +68,7 @@ int lift_check_shape(se_ctx* c, const unsigned char* frame_u8, int Hi, int Wi, c
   if (ly0 < 0 || lx0 < 0 || lh > Hi || lw > Wi || ly0 > Hi - lh || lx0 > Wi - lw)
     return fail(c, "the lift rectangle (ly0=%d lx0=%d, %d x %d) lies outside the frame (Hi=%d Wi=%d)", ly0, lx0, lh, lw, Hi, Wi);
   if (!aligned_to(lift, 16)) return fail(c, "lift must be 16-byte aligned");
-  return move_check_map(c, by0, bx0, by1, bx1, ly0, lx0, lh, lw, "lift rectangle", 0, 0, 0);
+  return move_check_box(c, by0, bx0, by1, bx1, ly0, lx0, lh, lw, "lift rectangle");
 }
 
 // ... and the lift and the planes against the frame's bytes
@@ -101,22 +104,13 @@ int se_move_drop_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, in
                     int flip, int radius) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (!frame_u8) return fail(c, "null pointer argument: frame_u8");
-  if (!lift) return fail(c, "null pointer argument: lift");
-  if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
-  if (move_check_frame(c, Hi, Wi)) return 1;
-  if (lh < 16 || lw < 16) return fail(c, "bad lift rectangle lh=%d lw=%d (a side is at least 16)", lh, lw);
-  if (ly0 < 0 || lx0 < 0 || lh > Hi || lw > Wi || ly0 > Hi - lh || lx0 > Wi - lw)
-    return fail(c, "the lift rectangle (ly0=%d lx0=%d, %d x %d) lies outside the frame (Hi=%d Wi=%d)", ly0, lx0, lh, lw, Hi, Wi);
-  if (!aligned_to(lift, 16)) return fail(c, "lift must be 16-byte aligned");
-  if (move_check_map(c, by0, bx0, by1, bx1, ly0, lx0, lh, lw, "lift rectangle", dy, dx, flip)) return 1;
+  if (lift_check_shape(c, frame_u8, Hi, Wi, lift, ly0, lx0, lh, lw, sel_u8, by0, bx0, by1, bx1)) return 1;
+  if (move_check_offset(c, dy, dx, flip)) return 1;
   if (radius < 0 || radius > SE_MOVE_MAX_RADIUS) return fail(c, "bad radius=%d (0 .. %d)", radius, SE_MOVE_MAX_RADIUS);
-  const size_t pn = (size_t)Hi * Wi, lpitch = ((size_t)3 * lw + 15) & ~(size_t)15, ln = (size_t)lh * lpitch;
-  if (overlaps(lift, ln, frame_u8, 3 * pn)) return fail(c, "lift overlaps frame_u8");
-  if (overlaps(sel_u8, pn, frame_u8, 3 * pn)) return fail(c, "sel_u8 overlaps frame_u8");
-  if (lock_u8 && overlaps(lock_u8, pn, frame_u8, 3 * pn)) return fail(c, "lock_u8 overlaps frame_u8");
+  if (lift_check_overlaps(c, frame_u8, Hi, Wi, lift, lh, lw, sel_u8, lock_u8)) return 1;
   if (device_enter(c)) return 1;
-  HIPCHK(c, launch_move_drop(frame_u8, Hi, Wi, lift, ly0, lx0, lw, (int)lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, dy, dx, flip, radius,
+  const int lpitch = (3 * lw + 15) & ~15;
+  HIPCHK(c, launch_move_drop(frame_u8, Hi, Wi, lift, ly0, lx0, lw, lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, dy, dx, flip, radius,
                              (hipStream_t)stream));
   return 0;
 }
@@ -128,7 +122,8 @@ int se_plane_shift_u8(se_ctx* c, void* stream, const unsigned char* sel_u8, int 
   if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
   if (!plane_out) return fail(c, "null pointer argument: plane_out");
   if (move_check_frame(c, Hi, Wi)) return 1;
-  if (move_check_map(c, by0, bx0, by1, bx1, 0, 0, Hi, Wi, "frame", dy, dx, flip)) return 1;
+  if (move_check_box(c, by0, bx0, by1, bx1, 0, 0, Hi, Wi, "frame")) return 1;
+  if (move_check_offset(c, dy, dx, flip)) return 1;
   const size_t pn = (size_t)Hi * Wi;
   if (overlaps(plane_out, pn, sel_u8, pn)) return fail(c, "plane_out overlaps sel_u8");
   if (device_enter(c)) return 1;
@@ -141,24 +136,15 @@ int se_warp_drop_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, in
                     int rh, int rw, const long long* m) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (!frame_u8) return fail(c, "null pointer argument: frame_u8");
-  if (!lift) return fail(c, "null pointer argument: lift");
-  if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
-  if (move_check_frame(c, Hi, Wi)) return 1;
-  if (lh < 16 || lw < 16) return fail(c, "bad lift rectangle lh=%d lw=%d (a side is at least 16)", lh, lw);
-  if (ly0 < 0 || lx0 < 0 || lh > Hi || lw > Wi || ly0 > Hi - lh || lx0 > Wi - lw)
-    return fail(c, "the lift rectangle (ly0=%d lx0=%d, %d x %d) lies outside the frame (Hi=%d Wi=%d)", ly0, lx0, lh, lw, Hi, Wi);
-  if (!aligned_to(lift, 16)) return fail(c, "lift must be 16-byte aligned");
-  if (warp_check_map(c, by0, bx0, by1, bx1, ly0, lx0, lh, lw, "lift rectangle", m)) return 1;
+  if (lift_check_shape(c, frame_u8, Hi, Wi, lift, ly0, lx0, lh, lw, sel_u8, by0, bx0, by1, bx1)) return 1;
+  if (warp_check_map(c, m)) return 1;
   if (rh <= 0 || rw <= 0) return fail(c, "bad destination rectangle rh=%d rw=%d: it is not empty", rh, rw);
   if (ry0 < 0 || rx0 < 0 || rh > Hi || rw > Wi || ry0 > Hi - rh || rx0 > Wi - rw)
     return fail(c, "the destination rectangle (ry0=%d rx0=%d, %d x %d) lies outside the frame (Hi=%d Wi=%d)", ry0, rx0, rh, rw, Hi, Wi);
-  const size_t pn = (size_t)Hi * Wi, lpitch = ((size_t)3 * lw + 15) & ~(size_t)15, ln = (size_t)lh * lpitch;
-  if (overlaps(lift, ln, frame_u8, 3 * pn)) return fail(c, "lift overlaps frame_u8");
-  if (overlaps(sel_u8, pn, frame_u8, 3 * pn)) return fail(c, "sel_u8 overlaps frame_u8");
-  if (lock_u8 && overlaps(lock_u8, pn, frame_u8, 3 * pn)) return fail(c, "lock_u8 overlaps frame_u8");
+  if (lift_check_overlaps(c, frame_u8, Hi, Wi, lift, lh, lw, sel_u8, lock_u8)) return 1;
   if (device_enter(c)) return 1;
-  HIPCHK(c, launch_warp_drop(frame_u8, Hi, Wi, lift, ly0, lx0, lw, (int)lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, ry0, rx0, rh, rw, m,
+  const int lpitch = (3 * lw + 15) & ~15;
+  HIPCHK(c, launch_warp_drop(frame_u8, Hi, Wi, lift, ly0, lx0, lw, lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, ry0, rx0, rh, rw, m,
                              (hipStream_t)stream));
   return 0;
 }
@@ -170,7 +156,8 @@ int se_plane_warp_u8(se_ctx* c, void* stream, const unsigned char* sel_u8, int H
   if (!sel_u8) return fail(c, "null pointer argument: sel_u8");
   if (!plane_out) return fail(c, "null pointer argument: plane_out");
   if (move_check_frame(c, Hi, Wi)) return 1;
-  if (warp_check_map(c, by0, bx0, by1, bx1, 0, 0, Hi, Wi, "frame", m)) return 1;
+  if (move_check_box(c, by0, bx0, by1, bx1, 0, 0, Hi, Wi, "frame")) return 1;
+  if (warp_check_map(c, m)) return 1;
   const size_t pn = (size_t)Hi * Wi;
   if (overlaps(plane_out, pn, sel_u8, pn)) return fail(c, "plane_out overlaps sel_u8");
   if (device_enter(c)) return 1;
@@ -248,7 +235,7 @@ int se_adjust_hist_u8(se_ctx* c, void* stream, const unsigned char* frame_u8, in
   if (!hist) return fail(c, "null pointer argument: hist_dev");
   if (!workspace) return fail(c, "null pointer argument: workspace");
   if (move_check_frame(c, Hi, Wi)) return 1;
-  if (move_check_map(c, by0, bx0, by1, bx1, 0, 0, Hi, Wi, "frame", 0, 0, 0)) return 1;
+  if (move_check_box(c, by0, bx0, by1, bx1, 0, 0, Hi, Wi, "frame")) return 1;
   if (!aligned_to(hist, 4)) return fail(c, "hist_dev must be 4-byte aligned");
   const size_t need = se_adjust_hist_u8_workspace_bytes(Hi, Wi), pn = (size_t)Hi * Wi;
   if (workspace_bytes < need) return fail(c, "workspace too small: %zu bytes, need %zu", workspace_bytes, need);

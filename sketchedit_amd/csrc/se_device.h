@@ -259,12 +259,41 @@ DEVFN unsigned load4_within(const unsigned char* a, const unsigned char* lo, con
   if (!sh) return d0;
   return (d0 >> sh) | (load_dword_within(a0 + 4, lo, hi) << (32 - sh));
 }
+// the 12 bytes at `a` (any alignment), of which only those inside [lo, hi) are read (the others are 0)
+DEVFN void load12_within(const unsigned char* a, const unsigned char* lo, const unsigned char* hi, unsigned u[3]) {
+  const unsigned char* a0 = (const unsigned char*)((size_t)a & ~(size_t)3);
+  const int sh = (int)((size_t)a & 3) * 8;
+  unsigned d[4];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) d[i] = load_dword_within(a0 + 4 * i, lo, hi);
+  d[3] = sh ? load_dword_within(a0 + 12, lo, hi) : 0u;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) u[i] = sh ? (d[i] >> sh) | (d[i + 1] << (32 - sh)) : d[i];
+}
+// each non-zero byte of u -> 1
+DEVFN unsigned bytes_nonzero(unsigned u) {
+  return ((u & 0xffu) ? 1u : 0u) | ((u & 0xff00u) ? 0x100u : 0u) | ((u & 0xff0000u) ? 0x10000u : 0u) | ((u & 0xff000000u) ? 0x1000000u : 0u);
+}
 // the bytes of `sel` (one per pixel, 4 pixels) whose byte of `lk` is non-zero, cleared
 DEVFN unsigned clear_locked(unsigned sel, unsigned lk) {
 #pragma unroll
   for (int p = 0; p < 4; ++p)
     if ((lk >> (8 * p)) & 255u) sel &= ~(255u << (8 * p));
   return sel;
+}
+
+// the walk of a plane's n flat bytes in the ALIGNED dwords that hold them (plane_combine, plane_shift, plane_warp): the dword
+// at out + p0 holds the pixels p0 .. p0 + 3, of which those in [0, n) are the plane's: a whole dword, or single bytes at the
+// plane's two ends; every byte written, one writer per byte
+DEVFN void store_plane_dword(unsigned char* out, long p0, long n, unsigned v) {
+  unsigned char* dst = out + p0;                                     // 4-byte aligned
+  if (p0 >= 0 && p0 + 4 <= n) {
+    *(unsigned*)dst = v;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (p0 + e >= 0 && p0 + e < n) dst[e] = (unsigned char)((v >> (8 * e)) & 255u);
+  }
 }
 
 // ---- host: launch profiler scope -------------------------------------------------------------------

@@ -110,14 +110,7 @@ __global__ void __launch_bounds__(256) plane_combine_kernel(const unsigned char*
                    op == SE_COMBINE_XOR ? sa != sb : !sa;
     v |= s ? 255u << (8 * e) : 0u;
   }
-  unsigned char* dst = out + p0;                                     // 4-byte aligned
-  if (p0 >= 0 && p0 + 4 <= n) {
-    *(unsigned*)dst = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (p0 + e >= 0 && p0 + e < n) dst[e] = (unsigned char)((v >> (8 * e)) & 255u);
-  }
+  store_plane_dword(out, p0, n, v);
 }
 
 }  // namespace

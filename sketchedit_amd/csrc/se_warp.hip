@@ -16,12 +16,11 @@
 //               columns: < 2^27).  An affine map takes its extremes at the tile's corners: where their source bounding box misses
 //               the box the workgroup returns before any load.  A pixel with a > 0 that is not locked reads its taps of P, its
 //               own three frame bytes where a < 65 536, and stores three bytes: one writer per byte.
-//  plane_warp:  plane_combine's walk (se_lasso.hip): the output's Hi Wi flat bytes in the ALIGNED dwords that hold them, one lane
-//               per dword, single bytes at the plane's two ends; every byte written, one writer per byte.
+//  plane_warp:  plane_combine's walk (se_lasso.hip; store_plane_dword): one lane per aligned dword of the output's Hi Wi flat bytes.
 #include "../../include/sketchedit_hip.h"
 #include "../../include/sketchedit_warp.h"
-#include "se_device.h"
 #include "se_kernels.h"
+#include "se_seltile.h"
 
 #include <cstdint>
 
@@ -29,7 +28,7 @@ namespace se {
 
 namespace {
 
-constexpr int WP_W = 64, WP_H = 16;
+constexpr int WP_W = SEL_W, WP_H = SEL_H;
 
 struct WarpMap {
   long long ayy, ayx, ay0, axy, axx, ax0;
@@ -72,12 +71,6 @@ __device__ __forceinline__ unsigned warp_taps(const WarpSel& ws, long long sy, l
   return a;
 }
 
-// the lift: the slot's row of source row sy is [lift + (sy - ly0) lpitch, + 3 lw), its pixel sx at 3 (sx - lx0)
-struct Lift {
-  const unsigned char* p;
-  int ly0, lx0, lw, lpitch;
-};
-
 __global__ void __launch_bounds__(256) warp_drop_kernel(unsigned char* __restrict__ frame, int Wi, Lift lift, WarpSel ws, WarpMap m,
                                                         const unsigned char* __restrict__ lock, int ry0, int rx0, int ry1, int rx1) {
   const int tid = threadIdx.x;
@@ -108,7 +101,7 @@ __global__ void __launch_bounds__(256) warp_drop_kernel(unsigned char* __restric
       const unsigned w0 = t.w[2 * r], w1 = t.w[2 * r + 1];
       if (!(w0 | w1)) continue;
       // the row's taps: six consecutive bytes of the slot row, of which those of the pixels xlo .. xhi - 1 are read
-      const unsigned char* prow = lift.p + (size_t)(t.iy + r - lift.ly0) * lift.lpitch;
+      const unsigned char* prow = lift.row(t.iy + r);
       const unsigned char* at = prow + 3 * (ptrdiff_t)(t.ix - lift.lx0);
       const unsigned char *lo = prow + 3 * (ptrdiff_t)(t.xlo - lift.lx0), *hi = prow + 3 * (ptrdiff_t)(t.xhi - lift.lx0);
       const unsigned u0 = load4_within(at, lo, hi), u1 = load4_within(at + 4, lo, hi);
@@ -141,14 +134,7 @@ __global__ void __launch_bounds__(256) plane_warp_kernel(WarpSel ws, WarpMap m, 
     Taps t;
     if (warp_taps(ws, m.ayy * y + m.ayx * x + m.ay0, m.axy * y + m.axx * x + m.ax0, t) >= 32768u) v |= 255u << (8 * e);
   }
-  unsigned char* dst = out + p0;                                     // 4-byte aligned
-  if (p0 >= 0 && p0 + 4 <= n) {
-    *(unsigned*)dst = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (p0 + e >= 0 && p0 + e < n) dst[e] = (unsigned char)((v >> (8 * e)) & 255u);
-  }
+  store_plane_dword(out, p0, n, v);
 }
 
 }  // namespace

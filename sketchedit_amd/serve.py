@@ -822,6 +822,12 @@ def _check_feather(feather):
     return int(feather) or None
 
 
+def _check_hole_grow(hole_grow):
+    if not isinstance(hole_grow, (int, np.integer)) or isinstance(hole_grow, (bool, np.bool_)) or not 0 <= hole_grow <= SELECT_MAX_GROW:
+        raise ValueError("hole_grow is an int 0 .. %d, in frame pixels (got %r)" % (SELECT_MAX_GROW, hole_grow))
+    return int(hole_grow)
+
+
 def _encoded(be, encode, frames, windows):
     """the windows of `frames` as files, by a checked `encode` that is not None: one backend call"""
     if encode == "png":
@@ -1892,6 +1898,74 @@ class EditSession:
                 raise ValueError("the lasso covers no pixel centre")
             return self._fill_selected(selection, sk, window, margin, low_latency, max_side, encode, feather)
 
+    # ---- what the operators on a lifted selection share (DESIGN.md 6r .. 6u) -----------------------------------------------------------
+    def _lift_fill_drop(self, selection, dst, window, margin, low_latency, max_side, encode, feather, keep_source, hole_grow, drop, remap,
+                        info, drop_feathers):
+        """move_selection and transform_selection once their own arguments are checked: the lift, the fill of the hole -- the
+        selection grown by `hole_grow` -- unless `keep_source`, `drop(lift, lift_rect)` into the rectangle `dst`, and `remap()` ->
+        (plane, box, count) of the new Selection; ONE ordered undo step.  `info`: the caller's own keys.  `drop_feathers`: the
+        drop takes `feather` itself, so info reports it even where no fill ran."""
+        Hi, Wi = self.frame_hw
+        box = selection.box
+        grown = (max(box[0] - hole_grow, 0), max(box[1] - hole_grow, 0), min(box[2] + hole_grow, Hi), min(box[3] + hole_grow, Wi))
+        self._check_fill_args(grown, None, window, margin, max_side)
+        win = None if keep_source else self._fill_window(grown, window, margin, max_side)
+        wins = ([] if win is None else [win]) + [dst]
+        journal = self.history > 0 and (self.history_bytes is None or
+                                        sum(window_saved_bytes(w[2], w[3]) for w in wins) <= self.history_bytes)
+        be = self.backend
+        with self._lock:
+            frames = [self._frame]
+            lift_rect = move_rect(box, (0, 0), self.frame_hw)
+            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
+            slots, work, pasted = [], None, False
+            try:
+                if win is not None:
+                    hole = selection.plane if hole_grow == 0 else be.grow(selection.plane, hole_grow)
+                    slot, work, _ = self._fill_steps(hole, None, win, low_latency, max_side, feather, journal)
+                    slots.append(slot)
+                    pasted = True
+                if journal:
+                    slots.append(be.save(frames, [dst[:2]], dst[2:])[0])
+                drop(lift, lift_rect)
+                pasted = True
+                plane, nbox, count = remap()
+            except Exception:
+                if pasted:                       # the fill or the drop is in the frame: no entry restores a state it was in
+                    self._undo.clear()
+                    self._redo.clear()
+                raise
+            # the new selection exists before the step is recorded: a caller who gets an entry gets the selection too
+            undoable = self._record_sequence(wins, slots if journal else None) if self.history > 0 else None
+            made = Selection(be, plane, nbox, count, self.frame_hw)
+            patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames * len(wins), wins)
+            locked = self._lock_plane is not None
+        info = dict(windows=wins, **info, selected=selection.count, selection=made)
+        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, work, undoable, feather if drop_feathers or win is not None else None)
+
+    def _lift_apply(self, selection, lift_rect, wins, apply, encode, info, feather, prepare=None):
+        """filter_selection and adjust_selection once their arguments are checked: the lift of `lift_rect`, `apply(lift, *extra)` --
+        ONE launch into the frame -- and the lift as the journal entry's slot.  `extra` = `prepare()`, backend calls that write
+        nothing into the frame: they run after the lift and in front of the `try`, so a failure there leaves the history alone.
+        `info`: the caller's own keys."""
+        journal = self._journals(lift_rect[2], lift_rect[3])
+        be = self.backend
+        with self._lock:
+            frames = [self._frame]
+            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
+            extra = prepare() if prepare is not None else ()
+            try:
+                apply(lift, *extra)
+                undoable = self._record(lift_rect, lift if journal else None) if self.history > 0 else None
+                patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames, wins)
+            except Exception:                    # the launch may be in the frame: no entry restores a state it was in
+                self._undo.clear()
+                self._redo.clear()
+                raise
+            locked = self._lock_plane is not None
+        info = dict(windows=wins, **info, selected=selection.count)
+        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, None, undoable, feather)
+
     # ---- move or clone a selection (DESIGN.md 6r) ------------------------------------------------------------------------------------
     def move_selection(self, selection, offset, flip=None, keep_source=False, hole_grow=2, window=None, margin=0.5, low_latency=None,
                        max_side=None, encode=None, feather=None):
@@ -1935,49 +2009,16 @@ class EditSession:
         offset = (int(dy), int(dx))
         if not (flip is None or isinstance(flip, str)) or flip not in MOVE_FLIPS:
             raise ValueError("flip is None, 'h', 'v' or 'hv' (got %r)" % (flip,))
-        if not isinstance(hole_grow, (int, np.integer)) or isinstance(hole_grow, (bool, np.bool_)) or not 0 <= hole_grow <= SELECT_MAX_GROW:
-            raise ValueError("hole_grow is an int 0 .. %d, in frame pixels (got %r)" % (SELECT_MAX_GROW, hole_grow))
-        hole_grow = int(hole_grow)
-        Hi, Wi = self.frame_hw
-        box = selection.box
+        hole_grow = _check_hole_grow(hole_grow)
+        box, flips = selection.box, MOVE_FLIPS[flip]
         dst = move_rect(box, offset, self.frame_hw)
         if dst is None:
             raise ValueError("offset %r moves the whole selection out of the frame" % (offset,))
-        grown = (max(box[0] - hole_grow, 0), max(box[1] - hole_grow, 0), min(box[2] + hole_grow, Hi), min(box[3] + hole_grow, Wi))
-        self._check_fill_args(grown, None, window, margin, max_side)
-        win = None if keep_source else self._fill_window(grown, window, margin, max_side)
-        wins = ([] if win is None else [win]) + [dst]
-        journal = self.history > 0 and (self.history_bytes is None or
-                                        sum(window_saved_bytes(w[2], w[3]) for w in wins) <= self.history_bytes)
         be = self.backend
-        with self._lock:
-            frames = [self._frame]
-            lift_rect = move_rect(box, (0, 0), self.frame_hw)
-            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
-            slots, work, pasted = [], None, False
-            try:
-                if win is not None:
-                    hole = selection.plane if hole_grow == 0 else be.grow(selection.plane, hole_grow)
-                    slot, work, _ = self._fill_steps(hole, None, win, low_latency, max_side, feather, journal)
-                    slots.append(slot)
-                    pasted = True
-                if journal:
-                    slots.append(be.save(frames, [dst[:2]], dst[2:])[0])
-                be.move_drop(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, offset, MOVE_FLIPS[flip], feather or 0)
-                pasted = True
-                plane, mbox, count = be.shift(selection.plane, box, offset, MOVE_FLIPS[flip])
-            except Exception:
-                if pasted:                       # the fill or the drop is in the frame: no entry restores a state it was in
-                    self._undo.clear()
-                    self._redo.clear()
-                raise
-            # the moved selection exists before the step is recorded: a caller who gets an entry gets the selection too
-            undoable = self._record_sequence(wins, slots if journal else None) if self.history > 0 else None
-            moved = Selection(be, plane, mbox, count, self.frame_hw)
-            patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames * len(wins), wins)
-            locked = self._lock_plane is not None
-        info = dict(windows=wins, move=True, offset=offset, flip=flip, selected=selection.count, selection=moved)
-        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, work, undoable, feather)
+        return self._lift_fill_drop(
+            selection, dst, window, margin, low_latency, max_side, encode, feather, keep_source, hole_grow,
+            lambda lift, lift_rect: be.move_drop(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, offset, flips, feather or 0),
+            lambda: be.shift(selection.plane, box, offset, flips), dict(move=True, offset=offset, flip=flip), True)
 
     def clone_selection(self, selection, offset, **kw):
         """move_selection(selection, offset, keep_source=True, ...): a copy of the selected pixels lands `offset`
@@ -2027,47 +2068,15 @@ class EditSession:
             m = _check_warp_map(matrix)
         else:
             m = _check_warp_map(warp_matrix(box, scale, angle, offset, flip))
-        if not isinstance(hole_grow, (int, np.integer)) or isinstance(hole_grow, (bool, np.bool_)) or not 0 <= hole_grow <= SELECT_MAX_GROW:
-            raise ValueError("hole_grow is an int 0 .. %d, in frame pixels (got %r)" % (SELECT_MAX_GROW, hole_grow))
-        hole_grow = int(hole_grow)
-        Hi, Wi = self.frame_hw
+        hole_grow = _check_hole_grow(hole_grow)
         dst = warp_rect(box, m, self.frame_hw)
         if dst is None:
             raise ValueError("the map %r puts nothing of the selection in the frame" % (m,))
-        grown = (max(box[0] - hole_grow, 0), max(box[1] - hole_grow, 0), min(box[2] + hole_grow, Hi), min(box[3] + hole_grow, Wi))
-        self._check_fill_args(grown, None, window, margin, max_side)
-        win = None if keep_source else self._fill_window(grown, window, margin, max_side)
-        wins = ([] if win is None else [win]) + [dst]
-        journal = self.history > 0 and (self.history_bytes is None or
-                                        sum(window_saved_bytes(w[2], w[3]) for w in wins) <= self.history_bytes)
         be = self.backend
-        with self._lock:
-            frames = [self._frame]
-            lift_rect = move_rect(box, (0, 0), self.frame_hw)
-            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
-            slots, work, pasted = [], None, False
-            try:
-                if win is not None:
-                    hole = selection.plane if hole_grow == 0 else be.grow(selection.plane, hole_grow)
-                    slot, work, _ = self._fill_steps(hole, None, win, low_latency, max_side, feather, journal)
-                    slots.append(slot)
-                    pasted = True
-                if journal:
-                    slots.append(be.save(frames, [dst[:2]], dst[2:])[0])
-                be.warp_drop(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, dst, m)
-                pasted = True
-                plane, wbox, count = be.warp(selection.plane, box, m)
-            except Exception:
-                if pasted:                       # the fill or the drop is in the frame: no entry restores a state it was in
-                    self._undo.clear()
-                    self._redo.clear()
-                raise
-            undoable = self._record_sequence(wins, slots if journal else None) if self.history > 0 else None
-            warped = Selection(be, plane, wbox, count, self.frame_hw)
-            patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames * len(wins), wins)
-            locked = self._lock_plane is not None
-        info = dict(windows=wins, transform=True, matrix=m, selected=selection.count, selection=warped)
-        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, work, undoable, feather if win is not None else None)
+        return self._lift_fill_drop(
+            selection, dst, window, margin, low_latency, max_side, encode, feather, keep_source, hole_grow,
+            lambda lift, lift_rect: be.warp_drop(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, dst, m),
+            lambda: be.warp(selection.plane, box, m), dict(transform=True, matrix=m), False)
 
     # ---- blur, sharpen or pixelate a selection --------------------------------------------------------------------------
     def filter_selection(self, selection, kind="blur", radius=None, amount=None, sigma=None, cell=None, feather=None, encode=None):
@@ -2124,25 +2133,14 @@ class EditSession:
         box = selection.box
         lift_rect = filter_rect(box, radius or 0, self.frame_hw)
         wins = [move_rect(box, (0, 0), self.frame_hw)]
-        journal = self._journals(lift_rect[2], lift_rect[3])
         be = self.backend
-        with self._lock:
-            frames = [self._frame]
-            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
-            try:
-                if kind == "pixelate":
-                    be.filter_mosaic(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, cell, q8, feather or 0)
-                else:
-                    be.filter_blur(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, taps, q8, feather or 0)
-                undoable = self._record(lift_rect, lift if journal else None) if self.history > 0 else None
-                patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames, wins)
-            except Exception:                    # the filter may be in the frame: no entry restores a state it was in
-                self._undo.clear()
-                self._redo.clear()
-                raise
-            locked = self._lock_plane is not None
-        info = dict(windows=wins, filter=kind, radius=radius, amount=amount, cell=cell, selected=selection.count)
-        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, None, undoable, feather)
+
+        def apply(lift):
+            if kind == "pixelate":
+                be.filter_mosaic(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, cell, q8, feather or 0)
+            else:
+                be.filter_blur(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, taps, q8, feather or 0)
+        return self._lift_apply(selection, lift_rect, wins, apply, encode, dict(filter=kind, radius=radius, amount=amount, cell=cell), feather)
 
     # ---- adjust a selection's tone and colour ---------------------------------------------------------------------------
     def adjust_selection(self, selection, lut=None, matrix=None, auto=None, reference=None, which="luma", clip=0, amount=1.0, feather=None,
@@ -2209,34 +2207,25 @@ class EditSession:
         box = selection.box
         lift_rect = move_rect(box, (0, 0), self.frame_hw)
         wins = [lift_rect]
-        journal = self._journals(lift_rect[2], lift_rect[3])
         be = self.backend
-        with self._lock:
-            frames = [self._frame]
-            lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
-            table = be.upload(lut) if lut is not None else None
-            if auto is not None:
-                ref = None
-                if rim is not None:
-                    ring, rbox, _ = be.combine(be.grow(selection.plane, rim), selection.plane, COMBINE_OPS["subtract"])
-                    ref = (ring, rbox or box)                    # no ring at all (the selection is the frame): an empty record, the identity
-                elif auto == "match":
-                    ref = (reference.plane, reference.box)
-                src = be.hist(self._frame, selection.plane, box)
-                ref = be.hist(self._frame, ref[0], ref[1]) if ref is not None else None
-                table = be.hist_lut(src, ref, ADJUST_AUTO[auto], ADJUST_WHICH[which], clip)
-            try:
-                be.adjust(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, table, matrix, q8, feather or 0)
-                undoable = self._record(lift_rect, lift if journal else None) if self.history > 0 else None
-                patches = [be.crop(self._frame, *w) for w in wins] if encode is None else _encoded(be, encode, frames, wins)
-            except Exception:                    # the adjustment may be in the frame: no entry restores a state it was in
-                self._undo.clear()
-                self._redo.clear()
-                raise
-            locked = self._lock_plane is not None
+
+        def table():                             # after the lift, in front of the launch's `try`: a failure here leaves the history alone
+            if auto is None:
+                return (be.upload(lut) if lut is not None else None,)
+            ref = None
+            if rim is not None:
+                ring, rbox, _ = be.combine(be.grow(selection.plane, rim), selection.plane, COMBINE_OPS["subtract"])
+                ref = (ring, rbox or box)                    # no ring at all (the selection is the frame): an empty record, the identity
+            elif auto == "match":
+                ref = (reference.plane, reference.box)
+            src = be.hist(self._frame, selection.plane, box)
+            ref = be.hist(self._frame, ref[0], ref[1]) if ref is not None else None
+            return (be.hist_lut(src, ref, ADJUST_AUTO[auto], ADJUST_WHICH[which], clip),)
         what = "+".join(k for k, on in (("lut", lut is not None), ("auto", auto is not None), ("matrix", matrix is not None)) if on)
-        info = dict(windows=wins, adjust=what, auto=auto, which=which if auto is not None else None, amount=amount, selected=selection.count)
-        return patches, [(w[1], w[0]) for w in wins], _edit_info(info, locked, None, undoable, feather)
+        return self._lift_apply(
+            selection, lift_rect, wins,
+            lambda lift, tb: be.adjust(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, tb, matrix, q8, feather or 0),
+            encode, dict(adjust=what, auto=auto, which=which if auto is not None else None, amount=amount), feather, prepare=table)
 
     def histogram(self, selection=None):
         """The histogram of the frame (`selection` None) or of a selection's pixels, for a front end's display: a

@@ -826,3 +826,12 @@ def test_the_kernels_cross_compile_for_gfx950(tmp_path):
     obj = str(tmp_path / "se_adjust.o")
     subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(_lib.CSRC, "se_adjust.hip"), "-o", obj])
     assert os.path.getsize(obj) > 0
+
+
+def test_the_selection_tile_is_written_once():
+    """What the operators on a selection share on the device lives in one file under csrc/ (se_seltile.h, se_device.h): an operator
+    that copied its predecessor's text instead of calling it would define one of these a second time."""
+    texts = {name: open(os.path.join(_lib.CSRC, name)).read() for name in sorted(os.listdir(_lib.CSRC))}
+    for piece in ("bytes_nonzero(unsigned", "load12_within(const", "sel4_in_box(const", "struct Lift", "in1 = z =="):
+        holders = [name for name, text in texts.items() if piece in text]
+        assert len(holders) == 1 and texts[holders[0]].count(piece) == 1, (piece, holders)
