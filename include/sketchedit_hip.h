@@ -359,7 +359,12 @@ int se_profile_report(se_ctx* ctx, char* buf, size_t cap);
  * mask / counts / lock regions of the window entries where the caller passed NULL, the resample intermediates) and the
  * ctx-owned resize intermediate at each use -- not the weight images, not the window record ring.  A result that changes
  * with v depends on a byte nobody wrote (tests/test_gpu_poison.py).  While it is set, a call with SE_FLAG_GRAPH runs
- * uncaptured and enters nothing into the graph cache. */
+ * uncaptured and enters nothing into the graph cache.
+ * "SE_PAIR_MIN_PIXELS" (DESIGN.md section 6): in the default mode se_inference, se_inference_locked and the uint8 forwards run a
+ * pass of B >= 2 images with B H W >= this value as two half-batch chains on the caller's stream and the ctx's side stream (0:
+ * never; never while the profiler is on); results do not depend on it, bit for bit.  se_debug_get_option also answers one
+ * derived, read-only name, "SE_PAIR_RULE:B,H,W,exec_flags" (decimal integers): 1 if such a pass is paired, 0 if not -- host
+ * arithmetic on the arguments and the switch, no ctx, no device; a malformed query or B, H, W < 1 returns 1. */
 int se_debug_set_option(const char* name, int value);
 int se_debug_get_option(const char* name, int* value);
 void se_debug_reset_options(void);

@@ -399,6 +399,17 @@ def gconv_form(cin, cout, H, W, k=3, stride=1, rate=1, act="elu", upsample=False
     return buf.value.decode().split(",")
 
 
+def pair_rule(B, H, W, low_latency=False):
+    """Whether the forwards run a pass of B images of H x W as two half-batch chains on two streams: the library's own rule
+    (se_host.h pair_rule, SE_PAIR_MIN_PIXELS included) asked on the host through the derived entry "SE_PAIR_RULE:B,H,W,flags" of
+    se_debug_get_option -- no device, nothing runs.  Results never depend on the answer."""
+    v = ctypes.c_int(-1)
+    name = "SE_PAIR_RULE:%d,%d,%d,%d" % (B, H, W, FLAG_LOW_LATENCY if low_latency else 0)
+    if load_library().se_debug_get_option(name.encode(), ctypes.byref(v)):
+        raise SketchEditHipError("pair_rule: bad shape B=%d H=%d W=%d" % (B, H, W))
+    return bool(v.value)
+
+
 def flags_from_opt(opt):
     """netG flag word from a reference-style options namespace (editline_g.py:15-23, base_options.py:19)."""
     f = 0

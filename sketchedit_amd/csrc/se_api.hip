@@ -118,18 +118,27 @@ int inference_u8_locked(se_ctx* c, void* stream, const float* image, const float
   const int nb = pass_size(c, B, H, W, flags);       // passes over image ranges beyond the kernels' 32-bit byte offsets
   if (!nb) return 1;
   if (poison(c, soft_all, 2 * plane, (hipStream_t)stream)) return 1;      // (the caller's tail planes are the caller's to fill)
-  for (int b0 = 0; b0 < B; b0 += nb) {
-    const int bb = std::min(nb, B - b0);
-    const se_ctx::Peaks pk = plan_peaks(c, 3, bb, H, W, flags, false);
+  for (int p0 = 0; p0 < B; p0 += nb) {
+    const int pb = std::min(nb, B - p0);
+    // a paired pass (pair_rule): two half-batch chains, planned one after the other, on the two streams and arenas
+    const bool pair = pair_pass(c, pb, H, W, flags);
+    const se_ctx::Peaks pk = plan_peaks(c, 3, pb, H, W, flags, false, pair);
     if (carve(c, pk, ws, ws_bytes, tail)) return 1;
-    const float *img = image + b0 * 3 * HW, *sk = sketch + b0 * HW;
-    float *hard = hard_all + b0 * HW, *soft = soft_all + b0 * HW;
-    begin_call(c, stream, flags);
-    int rc = plan_netM(c, img, sk, soft, hard, nullptr, bb, H, W, 0, lock8 ? lock8 + b0 * HW : nullptr);
-    if (rc) return rc;
-    if (carve(c, pk, ws, ws_bytes, tail)) return 1;
-    c->rgb8 = rgb_out + b0 * 3 * HW; c->m8 = mask_u8_out ? mask_u8_out + b0 * HW : nullptr;
-    rc = plan_netG(c, img, img, hard, hard, sk, nullptr, nullptr, soft, nullptr, bb, H, W, flags);
+    if (pair && pair_fork(c, (hipStream_t)stream)) return 1;
+    int rc = 0;
+    for (int half = 0; half < (pair ? 2 : 1) && !rc; ++half) {
+      const int b0 = p0 + (half ? pair_first(pb) : 0), bb = !pair ? pb : half ? pb - pair_first(pb) : pair_first(pb);
+      const float *img = image + b0 * 3 * HW, *sk = sketch + b0 * HW;
+      float *hard = hard_all + b0 * HW, *soft = soft_all + b0 * HW;
+      begin_call(c, stream, flags);
+      if (pair) pair_half(c, half);
+      rc = plan_netM(c, img, sk, soft, hard, nullptr, bb, H, W, 0, lock8 ? lock8 + b0 * HW : nullptr);
+      if (!rc) rc = carve(c, pk, ws, ws_bytes, tail);
+      if (rc) break;
+      c->rgb8 = rgb_out + b0 * 3 * HW; c->m8 = mask_u8_out ? mask_u8_out + b0 * HW : nullptr;
+      rc = plan_netG(c, img, img, hard, hard, sk, nullptr, nullptr, soft, nullptr, bb, H, W, flags);
+    }
+    if (pair && pair_join(c, (hipStream_t)stream) && !rc) rc = 1;      // (joined after a failed half too: the streams stay ordered)
     if (rc) return rc;
   }
   return 0;
@@ -354,6 +363,12 @@ size_t se_workspace_bytes(se_ctx* c, int B, int H, int W) {
                 c->serial = ser != 0;
                 const se_ctx::Peaks pk = plan_peaks(c, 3, bb, H, W, flags, mi != 0);
                 if (pk.main + pk.side > peak) peak = pk.main + pk.side;
+                // ... and as the two half-batch chains se_inference makes of such a pass (pair_pass; se_netM_forward and
+                // se_netG_forward never pair: the single chain above stays counted)
+                if (pair_pass(c, bb, H, W, flags)) {
+                  const se_ctx::Peaks pp = plan_peaks(c, 3, bb, H, W, flags, mi != 0, true);
+                  if (pp.main + pp.side > peak) peak = pp.main + pp.side;
+                }
               }
           c->serial = false;
         }
@@ -436,20 +451,32 @@ int enqueue_inference(se_ctx* c, void* stream, const float* image, const float* 
   const int nb = pass_size(c, B, H, W, flags);
   if (!nb) return 1;
   if (!hard_out && poison(c, hard_all, plane, (hipStream_t)stream)) return 1;
-  for (int b0 = 0; b0 < B; b0 += nb) {
-    const int bb = std::min(nb, B - b0);
-    const se_ctx::Peaks pk = plan_peaks(c, 3, bb, H, W, flags, maskim_out != nullptr);
+  for (int p0 = 0; p0 < B; p0 += nb) {
+    const int pb = std::min(nb, B - p0);
+    // A paired pass (pair_rule): images [p0, p0 + ceil(pb / 2)) as one netM -> netG chain on the caller's stream
+    // and the main arena, the rest as another on the side stream and the side arena, between one fork and one join.  The host
+    // plans and enqueues the halves one after the other, so the ctx's per-plan state is never live for both; what the halves
+    // share on the device is read-only (inputs, weights), everything written is addressed per image or lives in the half's arena.
+    const bool pair = pair_pass(c, pb, H, W, flags);
+    const se_ctx::Peaks pk = plan_peaks(c, 3, pb, H, W, flags, maskim_out != nullptr, pair);
     if (carve(c, pk, ws, ws_bytes, plane)) return 1;
-    const float *img = image + b0 * 3 * HW, *sk = sketch + b0 * HW;
-    float *hard = hard_all + b0 * HW, *mk = mask_out + b0 * mask_bs;
-    begin_call(c, stream, flags);
-    int rc = plan_netM(c, img, sk, mk, hard, maskim_out ? maskim_out + b0 * 3 * HW : nullptr, bb, H, W, packed_bs,     // editline2_model.py:339,346-347
-                       lock8 ? lock8 + b0 * HW : nullptr);
-    if (rc) return rc;
-    if (carve(c, pk, ws, ws_bytes, plane)) return 1;
-    // netG(inputs, inputs, mask_inpaint, mask_inpaint, line)  :366-368 ; composite with the soft mask :132
-    rc = plan_netG(c, img, img, hard, hard, sk, coarse_out ? coarse_out + b0 * 3 * HW : nullptr, fine_out ? fine_out + b0 * 3 * HW : nullptr,
-                   mk, composed_out + b0 * comp_bs, bb, H, W, flags, packed_bs);
+    if (pair && pair_fork(c, (hipStream_t)stream)) return 1;
+    int rc = 0;
+    for (int half = 0; half < (pair ? 2 : 1) && !rc; ++half) {
+      const int b0 = p0 + (half ? pair_first(pb) : 0), bb = !pair ? pb : half ? pb - pair_first(pb) : pair_first(pb);
+      const float *img = image + b0 * 3 * HW, *sk = sketch + b0 * HW;
+      float *hard = hard_all + b0 * HW, *mk = mask_out + b0 * mask_bs;
+      begin_call(c, stream, flags);
+      if (pair) pair_half(c, half);
+      rc = plan_netM(c, img, sk, mk, hard, maskim_out ? maskim_out + b0 * 3 * HW : nullptr, bb, H, W, packed_bs,     // editline2_model.py:339,346-347
+                     lock8 ? lock8 + b0 * HW : nullptr);
+      if (!rc) rc = carve(c, pk, ws, ws_bytes, plane);
+      if (rc) break;
+      // netG(inputs, inputs, mask_inpaint, mask_inpaint, line)  :366-368 ; composite with the soft mask :132
+      rc = plan_netG(c, img, img, hard, hard, sk, coarse_out ? coarse_out + b0 * 3 * HW : nullptr, fine_out ? fine_out + b0 * 3 * HW : nullptr,
+                     mk, composed_out + b0 * comp_bs, bb, H, W, flags, packed_bs);
+    }
+    if (pair && pair_join(c, (hipStream_t)stream) && !rc) rc = 1;      // (joined after a failed half too: the streams stay ordered)
     if (rc) return rc;
   }
   return 0;

@@ -83,7 +83,19 @@ int se_profile_report(se_ctx* c, char* buf, size_t cap) {
 
 // ---- developer switches (se_kernels.h SE_OPTIONS): process-wide, read from the environment once ----
 int se_debug_set_option(const char* name, int value) { return opt_set(name, value); }
-int se_debug_get_option(const char* name, int* value) { return opt_get(name, value); }
+// ... and one derived, read-only entry: "SE_PAIR_RULE:B,H,W,exec_flags" answers pair_rule (se_host.h) for a pass of B images --
+// 1 two half-batch chains, 0 one chain -- from the arguments and SE_PAIR_MIN_PIXELS alone: no ctx, no device (the set of
+// exported names is fixed; the query rides on the entry that reads the table the rule reads)
+int se_debug_get_option(const char* name, int* value) {
+  static const char q[] = "SE_PAIR_RULE:";
+  if (name && value && !strncmp(name, q, sizeof q - 1)) {
+    int B = 0, H = 0, W = 0, flags = 0, end = 0;
+    if (sscanf(name + sizeof q - 1, "%d,%d,%d,%d%n", &B, &H, &W, &flags, &end) != 4 || name[sizeof q - 1 + end] || B < 1 || H < 1 || W < 1) return 1;
+    *value = pair_rule(B, H, W, flags) ? 1 : 0;
+    return 0;
+  }
+  return opt_get(name, value);
+}
 void se_debug_reset_options(void) { opt_reset(); }
 
 // the ConvCall of se_gated_conv2d_ex for these arguments, chosen and named (no ctx, no device)

@@ -88,6 +88,8 @@ struct se_ctx {
   bool bf16 = false;        // SE_FLAG_BF16 of the running call: bf16 activations / weights, fp32 accumulate
   bool serial = false;             // default mode on one stream (set while the profiler is on: per-kernel durations)
   bool fork2 = true;               // SE_FORK_DEFAULT, snapshot taken where a call enters the library
+  bool paired = false;             // the plan being made is one half of a paired pass (pair_rule): no inner fork, its own arena
+  int half = 0;                    // ... which half: 0 on the caller's stream and the main arena, 1 on st_side and the side arena
   bool conservative = false;       // SE_FLAG_CONSERVATIVE of the running call: netM's 96 -> 192 layers on F(2x2,3x3)
   const se_netG_taps* taps = nullptr;      // se_netG_forward_taps: intermediate outputs of the running netG plan
   float* vbias_ws = nullptr;       // [B][9][192] scratch for the folded vector source of the next two-source layer (plan_netG)
@@ -210,6 +212,7 @@ inline void begin_call(se_ctx* c, void* stream, int flags) {
   c->serial = c->prof.on;
   c->taps = nullptr;
   c->rgb8 = nullptr; c->m8 = nullptr;
+  c->paired = false; c->half = 0;
   c->cur_net = SE_NET_G;       // per-op entry points run as netG layers whatever plan ran last; the plans set their own
   set_profiler(&c->prof);
 }
@@ -247,7 +250,9 @@ struct Plan {
   int B;
   int rc = 0;
   Arena* ar;                // arena of the branch being planned
-  Plan(se_ctx* c_, std::map<std::string, Layer>& n, int B_) : c(c_), net(n), B(B_), ar(&c_->arena) {}
+  Plan(se_ctx* c_, std::map<std::string, Layer>& n, int B_) : c(c_), net(n), B(B_), ar(home()) {}
+  // the arena a plan starts in and returns to after a side branch: the main one, or the side one for the second half of a paired pass
+  Arena* home() const { return c->paired && c->half ? &c->arena2 : &c->arena; }
   float* alloc_raw(size_t nfloats) {
     float* p = ar->alloc(nfloats);
     if (!p && !rc) rc = fail(c, "workspace too small (need more than %zu bytes)", ar->cap);
@@ -258,6 +263,8 @@ struct Plan {
     // everything the main stream did with side-arena blocks before (the style input, `vec`, a previous plan's joined side
     // branch).  A block both branches read (xnow, vec, pm) is released only after join(), and nothing is allocated from the
     // side arena between a side_end() and the next side_begin() except before the first fork, when that arena is still unused.
+    // A paired pass (pair_rule): each half allocates from its own arena only and is enqueued on its own stream, behind the fork
+    // event of the pass, so the same ordering holds per half.
     if (p && !rc && !c->dry && poison(c, p, (nfloats * 4 + 255) & ~(size_t)255, c->st)) rc = 1;
     return p;
   }
@@ -287,7 +294,8 @@ struct Plan {
   // planned on ONE stream (c->serial): an event pair around a launch measures that kernel only when nothing else shares the chip.
   // (c->fork2 = SE_FORK_DEFAULT as it was when the call entered the library: one snapshot per call, so a switch flipped by
   // another thread cannot leave a plan with a fork and no join)
-  bool forked() const { return (c->low_latency || (c->fork2 && !c->serial)) && c->st_side; }
+  // (a half of a paired pass is one chain on one stream: the side stream and arena belong to the other half)
+  bool forked() const { return !c->paired && (c->low_latency || (c->fork2 && !c->serial)) && c->st_side; }
   int side_begin() {
     if (!forked()) return 0;
     ar = &c->arena2;
@@ -336,7 +344,23 @@ int att_row_stride(int R, bool bf);
 bool att_streaming(int h, int w, bool bf, bool want_similar);
 int run_attention(se_ctx* c, Plan& P, Act& x, const float* mask_full, Act& out, float* similar_nchw);
 int pass_size(se_ctx* c, int B, int H, int W, int flags);
-se_ctx::Peaks plan_peaks(se_ctx* c, int which, int B, int H, int W, int flags, bool want_maskim);
+// Paired passes: whether a pass of `bb` images of the default mode runs as two half-batch chains, images
+// [0, ceil(bb / 2)) on the caller's stream and the main arena, the rest on the side stream and the side arena, between one fork
+// and one join.  Pure: the arguments and SE_PAIR_MIN_PIXELS (0: never).  A half runs the kernels a pass of its size runs, and
+// which kernel a layer runs does not depend on the batch (se_dispatch.h), so an image's bits do not depend on the pairing.
+inline bool pair_rule(int bb, int H, int W, int flags) {
+  const int min_pixels = opt(OPT_PAIR_MIN_PIXELS);
+  return !(flags & SE_FLAG_LOW_LATENCY) && bb >= 2 && min_pixels > 0 && (long long)bb * H * W >= min_pixels;
+}
+inline int pair_first(int bb) { return (bb + 1) / 2; }       // images of the first half
+// ... and whether THIS call pairs: never while the profiler is on (c->serial: one stream, per-kernel durations) or with taps
+inline bool pair_pass(const se_ctx* c, int bb, int H, int W, int flags) {
+  return pair_rule(bb, H, W, flags) && !c->serial && !c->taps && c->st_side;
+}
+se_ctx::Peaks plan_peaks(se_ctx* c, int which, int B, int H, int W, int flags, bool want_maskim, bool pair = false);
+int pair_fork(se_ctx* c, hipStream_t main);
+void pair_half(se_ctx* c, int half);
+int pair_join(se_ctx* c, hipStream_t main);
 int carve(se_ctx* c, const se_ctx::Peaks& pk, void* ws, size_t ws_bytes, size_t tail);
 
 // ---- se_api.hip: the resize resources of the ctx, and the forward that leaves uint8 (the window edits and fills end in it) ----

@@ -64,7 +64,8 @@ hipError_t ensure_max_lds(const void* func, int bytes);
   X(WINOGRAD_F43, 1)     /* hybrid F(2,3)xF(4,3): 0 off, 1 everywhere, 2 netG only */ \
   X(GCONV_FAST, 1) X(FORK_DEFAULT, 1) X(LL_WINO_MIN_WG, 64) X(LL_WINO48_MIN_WG, 128)                            \
   X(ATT_FUSED, -1) X(ATT_FUSED_BF16, -1) X(ATT_PTILDE_LDS, 1) X(ATT_STATS_LDS, 1) X(ATT_E16, 1) X(ATT_SYM, 1)   \
-  X(ATT_STREAM, 0)       /* attention form: 0 by size (streaming where R Rp 4 >= 2^31), 1 streaming wherever possible */
+  X(ATT_STREAM, 0)       /* attention form: 0 by size (streaming where R Rp 4 >= 2^31), 1 streaming wherever possible */ \
+  X(PAIR_MIN_PIXELS, 1 << 21) /* default mode: fewest pixels (images x H x W) of a pass that runs as two half-batch chains on the two streams (se_host.h pair_rule); 0: never */
 enum Opt {
 #define X(name, dflt) OPT_##name,
   SE_OPTIONS(X)

@@ -393,9 +393,9 @@ int plan_netG(se_ctx* c, const float* x, const float* x2, const float* mask, con
   const int joint = (flags & SE_FLAG_JOINT_TRAIN_INP) ? 1 : 0;
   // joint_train_inp: the style input is packed without its (zero) guide channel and wconv1 runs as a 4-channel conv
   Act cin = P.alloc(H, W, 8);
-  P.ar = P.forked() ? &c->arena2 : &c->arena;       // the style branch's input lives in the style branch's arena
+  P.ar = P.forked() ? &c->arena2 : P.home();        // the style branch's input lives in the style branch's arena
   Act sin = P.alloc(H, W, joint ? 4 : 8);
-  P.ar = &c->arena;
+  P.ar = P.home();
   if (P.rc) return P.rc;
   if (!c->dry)
     HIPCHK(c, (c->bf16 ? launch_pack_g16 : launch_pack_g)(x, x2, mask, mask2, guide, cin.p, sin.p, B, H, W,
@@ -571,15 +571,15 @@ long long max_act_bytes_per_image(se_ctx* c, int H, int W, int flags) {
   const std::vector<long long> key = {H, W, (flags & SE_FLAG_BF16) ? 1 : 0};
   auto it = c->act_per_img.find(key);
   if (it != c->act_per_img.end()) return it->second;
-  const bool dry0 = c->dry, ll0 = c->low_latency, bf0 = c->bf16;
-  c->dry = true; c->low_latency = false; c->bf16 = (flags & SE_FLAG_BF16) != 0;
+  const bool dry0 = c->dry, ll0 = c->low_latency, bf0 = c->bf16, pair0 = c->paired;
+  c->dry = true; c->low_latency = false; c->bf16 = (flags & SE_FLAG_BF16) != 0; c->paired = false;
   c->dry_max_act = 0;
   float dummy;
   c->arena.reset(nullptr, 0, true, 0); c->arena2.reset(nullptr, 0, true, 1);
   plan_netM(c, nullptr, nullptr, nullptr, nullptr, &dummy, 1, H, W, 0);
   c->arena.reset(nullptr, 0, true, 0); c->arena2.reset(nullptr, 0, true, 1);
   plan_netG(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, H, W, SE_FLAG_USE_CAM | SE_FLAG_POOL_MAX, 0);
-  c->dry = dry0; c->low_latency = ll0; c->bf16 = bf0;
+  c->dry = dry0; c->low_latency = ll0; c->bf16 = bf0; c->paired = pair0;
   const long long v = (long long)c->dry_max_act;
   c->act_per_img[key] = v;
   return v;
@@ -605,35 +605,63 @@ int pass_size(se_ctx* c, int B, int H, int W, int flags) {
 
 // Arena peaks of a forward, from a dry run of the very plan that will be launched (nothing is enqueued): main-branch
 // arena and, in low-latency mode, the side-branch arena.  which: 1 netM, 2 netG, 3 netM then netG (se_inference).
-se_ctx::Peaks plan_peaks(se_ctx* c, int which, int B, int H, int W, int flags, bool want_maskim) {
+// pair (pair_pass): the B images run as two halves, each planned as the enqueue loop plans it -- the first half's chain in the
+// main arena, the second's in the side arena; the peaks are those of the two chains.
+se_ctx::Peaks plan_peaks(se_ctx* c, int which, int B, int H, int W, int flags, bool want_maskim, bool pair) {
   const std::vector<long long> key = {which, B, H, W,
                                       flags & (SE_FLAG_USE_CAM | SE_FLAG_JOINT_TRAIN_INP | SE_FLAG_LOW_LATENCY | SE_FLAG_BF16),
-                                      want_maskim ? 1 : 0, c->fork2 ? 1 : 0, opt_epoch(), c->serial ? 1 : 0};
+                                      want_maskim ? 1 : 0, c->fork2 ? 1 : 0, opt_epoch(), c->serial ? 1 : 0, pair ? 1 : 0};
   auto it = c->peaks.find(key);
   if (it != c->peaks.end()) return it->second;
-  const bool dry0 = c->dry, ll0 = c->low_latency, bf0 = c->bf16;
+  const bool dry0 = c->dry, ll0 = c->low_latency, bf0 = c->bf16, pair0 = c->paired;
+  const int half0 = c->half;
   c->dry = true;
   c->low_latency = (flags & SE_FLAG_LOW_LATENCY) != 0;
   c->bf16 = (flags & SE_FLAG_BF16) != 0;
   float dummy;      // non-null marker for optional outputs
   se_ctx::Peaks pk{0, 0};
-  if (which & 1) {
-    c->arena.reset(nullptr, 0, true, 0); c->arena2.reset(nullptr, 0, true, 1);
-    plan_netM(c, nullptr, nullptr, nullptr, nullptr, want_maskim ? &dummy : nullptr, B, H, W);
-    pk.main = c->arena.peak; pk.side = c->arena2.peak;
+  for (int half = 0; half < (pair ? 2 : 1); ++half) {
+    const int nb = !pair ? B : half ? B - pair_first(B) : pair_first(B);
+    c->paired = pair; c->half = half;
+    if (which & 1) {
+      c->arena.reset(nullptr, 0, true, 0); c->arena2.reset(nullptr, 0, true, 1);
+      plan_netM(c, nullptr, nullptr, nullptr, nullptr, want_maskim ? &dummy : nullptr, nb, H, W);
+      if (c->arena.peak > pk.main) pk.main = c->arena.peak;
+      if (c->arena2.peak > pk.side) pk.side = c->arena2.peak;
+    }
+    if (which & 2) {
+      c->arena.reset(nullptr, 0, true, 0); c->arena2.reset(nullptr, 0, true, 1);
+      plan_netG(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nb, H, W, flags);
+      if (c->arena.peak > pk.main) pk.main = c->arena.peak;
+      if (c->arena2.peak > pk.side) pk.side = c->arena2.peak;
+    }
   }
-  if (which & 2) {
-    c->arena.reset(nullptr, 0, true, 0); c->arena2.reset(nullptr, 0, true, 1);
-    plan_netG(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, H, W, flags);
-    if (c->arena.peak > pk.main) pk.main = c->arena.peak;
-    if (c->arena2.peak > pk.side) pk.side = c->arena2.peak;
-  }
-  c->dry = dry0; c->low_latency = ll0; c->bf16 = bf0;
+  c->dry = dry0; c->low_latency = ll0; c->bf16 = bf0; c->paired = pair0; c->half = half0;
   c->peaks[key] = pk;
   return pk;
 }
 
-// carve the caller's workspace into the arenas of this call; `tail` bytes at the end stay reserved
+// One fork in front of both halves of a paired pass and one join behind them, with the ctx's own events: the side stream starts
+// behind everything the caller's stream holds so far (the previous pass and call with it), the caller's stream goes on behind both halves.
+int pair_fork(se_ctx* c, hipStream_t main) {
+  HIPCHK(c, hipEventRecord(c->ev_fork, main));
+  HIPCHK(c, hipStreamWaitEvent(c->st_side, c->ev_fork, 0));
+  return 0;
+}
+// after begin_call: the plans that follow are half `half` of a paired pass (Plan::home, Plan::forked)
+void pair_half(se_ctx* c, int half) {
+  c->paired = true; c->half = half;
+  c->st = half ? c->st_side : c->st_main;
+}
+int pair_join(se_ctx* c, hipStream_t main) {
+  c->paired = false; c->half = 0; c->st = main;
+  HIPCHK(c, hipEventRecord(c->ev_join, c->st_side));
+  HIPCHK(c, hipStreamWaitEvent(main, c->ev_join, 0));
+  return 0;
+}
+
+// carve the caller's workspace into the arenas of this call; `tail` bytes at the end stay reserved.  (A paired pass: pk holds
+// the two halves' peaks, the same two regions serve them.)
 int carve(se_ctx* c, const se_ctx::Peaks& pk, void* ws, size_t ws_bytes, size_t tail) {
   if (ws_bytes < pk.main + pk.side + tail)
     return fail(c, "workspace too small: %zu bytes, this call needs %zu", ws_bytes, pk.main + pk.side + tail);
