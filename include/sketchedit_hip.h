@@ -364,7 +364,14 @@ int se_profile_report(se_ctx* ctx, char* buf, size_t cap);
  * pass of B >= 2 images with B H W >= this value as two half-batch chains on the caller's stream and the ctx's side stream (0:
  * never; never while the profiler is on); results do not depend on it, bit for bit.  se_debug_get_option also answers one
  * derived, read-only name, "SE_PAIR_RULE:B,H,W,exec_flags" (decimal integers): 1 if such a pass is paired, 0 if not -- host
- * arithmetic on the arguments and the switch, no ctx, no device; a malformed query or B, H, W < 1 returns 1. */
+ * arithmetic on the arguments and the switch, no ctx, no device; a malformed query or B, H, W < 1 returns 1.
+ * "SE_S2_POLY" (DESIGN.md 3.1g): the polyphase F(2,2) form of the 3x3 stride-2 layers with 48 input channels ("s2poly48"): 0 off,
+ * 1 (default) everywhere, 2 netG only.  Two more derived, read-only names answer what that form is built from, on the host:
+ * "SE_S2POLY_TABLE:q,j" -- entry j of 1-D position q = 0..4: [source +, source - (or -1), coefficient of w0, w1, w2, fold into
+ * o0, o1], the sources indexing the patch in[4t-1 .. 4t+3] of the output pair o0 = out[2t], o1 = out[2t+1]; and
+ * "SE_S2POLY_PACK:cout,i" -- the bits of float i of [weight image (cout/96, 38, 96, 32), bias (cout)] as the library's packer
+ * (csrc/se_s2poly.h) builds them for the probe layer w.flat[n] = p(n), b[n] = p(10007 + n), p(n) = ((7919 n) % 2053 - 1026) / 1024,
+ * w (cout,48,3,3), cout 96 or 192. */
 int se_debug_set_option(const char* name, int value);
 int se_debug_get_option(const char* name, int* value);
 void se_debug_reset_options(void);

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SKETCHEDIT_HIP_LIB points at another build of the same library (developer builds, e.g. tools/wino_trace.py)
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
+SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_s2poly.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
            "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_modify.hip", "se_outline.hip", "se_move.hip", "se_warp.hip", "se_filter.hip", "se_adjust.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
            "se_plan.hip", "se_api_window.hip", "se_api_select.hip", "se_api_move.hip", "se_api_codec.hip", "se_api_debug.hip", "se_api.hip"]
 
@@ -397,6 +397,35 @@ def gconv_form(cin, cout, H, W, k=3, stride=1, rate=1, act="elu", upsample=False
           int(bool(upsample)), B, H, W, flags, net, buf, len(buf)):
         raise SketchEditHipError("gconv_form: not a layer gated_conv2d takes")
     return buf.value.decode().split(",")
+
+
+def s2poly_tables():
+    """The 1-D tables of the polyphase F(2,2) form (csrc/se_s2poly.h) as a (5, 7) int32 array: per position [source +, source -
+    (or -1), coefficient of w0, w1, w2, fold into o0, o1] -- the derived entry "SE_S2POLY_TABLE:q,j" of se_debug_get_option, no
+    device."""
+    return np.array([[get_option("SE_S2POLY_TABLE:%d,%d" % (q, j)) for j in range(7)] for q in range(5)], np.int32)
+
+
+def s2poly_probe_layer(cout):
+    """The probe layer of include/sketchedit_hip.h ("SE_S2POLY_PACK"): w (cout,48,3,3) and b (cout,) float32, every value a
+    multiple of 1/1024 below 1.01 in magnitude."""
+    p = lambda n: (((7919 * n) % 2053 - 1026) / 1024.0).astype(np.float32)      # noqa: E731
+    return p(np.arange(cout * 48 * 9, dtype=np.int64)).reshape(cout, 48, 3, 3), p(10007 + np.arange(cout, dtype=np.int64))
+
+
+def s2poly_probe_pack(cout):
+    """The weight image (cout/96, 38, 96, 32) and bias (cout,) the library's packer builds for s2poly_probe_layer(cout), cout 96 or
+    192, read float by float through the derived entry "SE_S2POLY_PACK:cout,i" of se_debug_get_option -- host only, no device."""
+    fn = load_library().se_debug_get_option
+    n = (cout // 96) * 38 * 96 * 32
+    out = np.zeros(n + cout, np.int32)
+    v = ctypes.c_int(0)
+    for i in range(n + cout):
+        if fn(("SE_S2POLY_PACK:%d,%d" % (cout, i)).encode(), ctypes.byref(v)):
+            raise SketchEditHipError("SE_S2POLY_PACK: cout must be 96 or 192")
+        out[i] = v.value
+    f = out.view(np.float32)
+    return f[:n].reshape(cout // 96, 38, 96, 32).copy(), f[n:].copy()
 
 
 def pair_rule(B, H, W, low_latency=False):

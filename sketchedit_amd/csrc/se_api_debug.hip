@@ -1,6 +1,7 @@
 // Measurement and test support behind include/sketchedit_hip.h: the in-library profiler's report, the developer switches, and
 // the per-op entries the unit tests call (one gated conv, the attention, the kernels between the convolutions).
 #include "se_host.h"
+#include "se_s2poly.h"
 
 using namespace se;
 
@@ -92,6 +93,35 @@ int se_debug_get_option(const char* name, int* value) {
     int B = 0, H = 0, W = 0, flags = 0, end = 0;
     if (sscanf(name + sizeof q - 1, "%d,%d,%d,%d%n", &B, &H, &W, &flags, &end) != 4 || name[sizeof q - 1 + end] || B < 1 || H < 1 || W < 1) return 1;
     *value = pair_rule(B, H, W, flags) ? 1 : 0;
+    return 0;
+  }
+  // ... and two for the polyphase form (se_s2poly.h): an entry of its 1-D tables, and a float of the image its packer builds for
+  // the probe layer of the header (built once per width and kept)
+  static const char qt[] = "SE_S2POLY_TABLE:", qp[] = "SE_S2POLY_PACK:";
+  if (name && value && !strncmp(name, qt, sizeof qt - 1)) {
+    int q = -1, j = -1, end = 0;
+    if (sscanf(name + sizeof qt - 1, "%d,%d%n", &q, &j, &end) != 2 || name[sizeof qt - 1 + end] || q < 0 || q > 4 || j < 0 || j > 6) return 1;
+    *value = j == 0 ? s2poly_src_a(q) : j == 1 ? s2poly_src_b(q) : j < 5 ? s2poly_wcoef(q, j - 2) : s2poly_fold(q, j - 5);
+    return 0;
+  }
+  if (name && value && !strncmp(name, qp, sizeof qp - 1)) {
+    int cout = 0, end = 0;
+    long long i = -1;
+    if (sscanf(name + sizeof qp - 1, "%d,%lld%n", &cout, &i, &end) != 2 || name[sizeof qp - 1 + end] || (cout != 96 && cout != 192) || i < 0) return 1;
+    static std::mutex mu;
+    static std::vector<float> kept[2];
+    std::lock_guard<std::mutex> lk(mu);
+    std::vector<float>& all = kept[cout == 192];
+    if (all.empty()) {
+      auto probe = [](long long n) { return (float)((7919 * n) % 2053 - 1026) / 1024.f; };
+      std::vector<float> w((size_t)cout * 48 * 9), b(cout), bias;
+      for (size_t n = 0; n < w.size(); ++n) w[n] = probe((long long)n);
+      for (int n = 0; n < cout; ++n) b[n] = probe(10007 + n);
+      if (!s2poly_pack_host(w.data(), b.data(), cout, all, bias)) return 1;
+      all.insert(all.end(), bias.begin(), bias.end());
+    }
+    if ((size_t)i >= all.size()) return 1;
+    memcpy(value, &all[(size_t)i], sizeof(int));
     return 0;
   }
   return opt_get(name, value);

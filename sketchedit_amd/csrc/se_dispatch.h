@@ -51,6 +51,7 @@ struct LayerFacts {
   int nch[2], CG[2];          // chunks of 128-byte rows, granules (4 fp32 / 8 bf16 channels) per tap
   int dense, nchd;            // dense-K image of a 5x5 first layer: real channels per pixel, 32-k chunks (0: none)
   bool u, ub, u1, wv, wv16, u24, ub24, u24b, wx, wx2, wd, wdw, w16d, w16s, w96;
+  bool s2p;                   // polyphase F(2,2) image of a 3x3 stride-2 layer with 48 stored input channels (se_s2poly.hip)
 };
 
 inline LayerFacts layer_facts(const LayerDef& d, int nchans) {
@@ -79,6 +80,8 @@ inline LayerFacts layer_facts(const LayerDef& d, int nchans) {
   // bf16 raw-tile images (cin == 192: of the FIRST source's 96 channels, for the folded-vector form of conv11)
   f.w16s = d.k == 3 && d.stride == 1 && !d.up && (d.cin == 96 || d.cin == 192) && d.cout == 192;
   f.w96 = rconv96_eligible(d);
+  // the polyphase image of the 48-channel downsampling layers (48 -> 96, 48 -> 192): whole 96-row halves
+  f.s2p = d.k == 3 && d.stride == 2 && d.rate == 1 && !d.up && nchans == 48 && d.cin == 48 && (d.cout == 96 || d.cout == 192);
   // the Winograd-type image of the 3x3 stride-1 layers whose packed channels are exactly the layer's
   if (d.k != 3 || d.stride != 1 || (nchans + 3) / 4 * 4 != d.cin) return f;
   if (d.up) {
@@ -109,7 +112,7 @@ struct ConvCall {
 
 enum Form {
   F_SMALL_CONV, F_WINO, F_WINO24, F_WINO24_C48, F_WINO48, F_WINO48_C24, F_WINOUP, F_WINOUP48, F_RTILEW, F_RTILEW2,
-  F_RTILE_DENSE5, F_RTILE_DENSE5W, F_RTILE_D4, F_RTILE, F_RCONV16, F_RCONV16_DUAL, F_RCONV96, F_GATHER
+  F_RTILE_DENSE5, F_RTILE_DENSE5W, F_RTILE_D4, F_RTILE, F_RCONV16, F_RCONV16_DUAL, F_RCONV96, F_S2POLY48, F_GATHER
 };
 struct Choice {
   Form form;
@@ -247,6 +250,13 @@ inline Choice choose_form(const ConvCall& q) {
     if (C0 == 96 && d.cin == 96 && fits96) return is(F_WINOUP);
     if (opt(OPT_WINOGRAD_UP48) != 0 && C0 == 48 && d.cin == 48 && d.cout == 48 && fits48 && B * sh.Ho * sh.Wo * 96 < (1ll << 31)) return is(F_WINOUP48);
   }
+  // 3x3 stride 2, 48 -> 96 / 192: polyphase F(2,2), 25 of 36 products on tiles of 2x2 outputs = 4x4 source pixels (se_s2poly.hip).
+  // SE_S2_POLY=0: the gather-GEMM; 1 (default): everywhere; 2: netG only (netM's soft mask feeds the 0.5 threshold, as SE_WINOGRAD_F43).
+  // Never in low-latency mode: a 64-tile workgroup covers 1024 source pixels, a 128x128 source is 16 workgroups per row half
+  const int s2_mode = opt(OPT_S2_POLY);
+  if ((s2_mode == 1 || (s2_mode == 2 && q.net == 0)) && !ll && f.s2p && !two && d.k == 3 && d.stride == 2 && d.rate == 1 && !d.up && C0 == 48 &&
+      d.cin == 48 && (d.cout == 96 || d.cout == 192) && (Hin % 4) == 0 && (Win % 4) == 0 && fits48)
+    return is(F_S2POLY48);
   return is(choose_rtile(q));
 }
 
@@ -282,6 +292,7 @@ inline const char* form_name(const Choice& ch, const ConvCall& q) {
     case F_RTILE: return q.bf16 ? (d.up ? "rtile_bf16_up2" : "rtile_bf16") : (d.up ? "rtile_up2" : "rtile");
     case F_RCONV16: return "rconv16";
     case F_RCONV16_DUAL: return "rconv16_dual";
+    case F_S2POLY48: return "s2poly48";
     case F_RCONV96: return d.up ? "rconv96_up" : d.stride == 2 ? "rconv96_s2" : q.C0 == 24 ? "rconv96_c24" : "rconv96";
     case F_GATHER: return gconv_form_name(q.facts.cfg, q.low_latency, d.up != 0, q.C0 / (q.bf16 ? 8 : 4) != q.facts.CG[q.bf16], q.bf16);
   }

@@ -62,6 +62,7 @@ hipError_t ensure_max_lds(const void* func, int bytes);
   X(RCONV16, 1) X(RCONV16_DUAL, 1) X(RCONV96, 1) X(VECBIAS, 1)                                                  \
   X(WINOGRAD, 1) X(WINOGRAD48, 1) X(WINOGRAD_UP, 1) X(WINOGRAD_UP48, 1)                                         \
   X(WINOGRAD_F43, 1)     /* hybrid F(2,3)xF(4,3): 0 off, 1 everywhere, 2 netG only */ \
+  X(S2_POLY, 1)          /* polyphase F(2,2) form of the 48-channel stride-2 layers: 0 off, 1 everywhere, 2 netG only */ \
   X(GCONV_FAST, 1) X(FORK_DEFAULT, 1) X(LL_WINO_MIN_WG, 64) X(LL_WINO48_MIN_WG, 128)                            \
   X(ATT_FUSED, -1) X(ATT_FUSED_BF16, -1) X(ATT_PTILDE_LDS, 1) X(ATT_STATS_LDS, 1) X(ATT_E16, 1) X(ATT_SYM, 1)   \
   X(ATT_STREAM, 0)       /* attention form: 0 by size (streaming where R Rp 4 >= 2^31), 1 streaming wherever possible */ \
@@ -177,6 +178,10 @@ hipError_t launch_winoup(const WinoParams& p, hipStream_t st);
 // gen_deconv 48 -> 48 (24 gated) in the same form (se_wino_up48.hip): src NHWC 48 at (h, w), dst NHWC 24 at (2h, 2w), upk
 // [4 classes][14 iterations][48 MIXED rows][32] in the K pairing of the 48-channel kernels, bias [48] MIXED order
 hipError_t launch_winoup48(const WinoParams& p, hipStream_t st);
+// 3x3 stride 2, 48 -> 96 / 192, polyphase F(2,2) form, 25 of 36 products (se_s2poly.hip): src NHWC 48 at (h, w), h % 4 == w % 4 == 0,
+// dst NHWC 48 `halves` at (h/2, w/2), upk [halves][38 iterations][96 MIXED rows][32] (pack_s2poly48), bias [96 halves] MIXED order;
+// th = h/4, tw = w/4: tiles of 2x2 outputs
+hipError_t launch_s2poly48(const WinoParams& p, int halves, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
 // bf16 raw-tile form of the 3x3 stride-1 gated conv 96 -> 192 (se_rconv16.hip)

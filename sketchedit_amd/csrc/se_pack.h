@@ -59,6 +59,8 @@ struct Layer {
   DevBuf d_wx2;     //   and of its two-dimensional F(2x2,3x3) form
   DevBuf d_wd;      // 5x5 layers with padding channels in their stored input (fp32): dense-K image (se_rtile.hip)
   DevBuf d_wdw;     //   and the image of its F(2,5)-along-x form (rtile_dense5w_kernel)
+  DevBuf d_s2p;     // 3x3 stride 2, 48 -> 96 / 192 (fp32): polyphase F(2,2) image (se_s2poly.hip)
+  DevBuf d_s2pb;    //   and the bias in its MIXED row order
 };
 
 // Builds every device image of a layer, in both precisions, from its host weights: those layer_facts names, no other (checked

@@ -3,6 +3,7 @@
 // layer_facts (se_dispatch.h): pack_layer_images builds those, and choose_form picks a form only where the facts name its image.
 #include "se_pack.h"
 #include "se_kernels.h"
+#include "se_s2poly.h"
 
 #include <cstring>
 
@@ -486,6 +487,19 @@ int pack_winoup48(Layer& L, std::string& err) {
   return upload(L.d_ub, mixed_bias(L, NP), err);
 }
 
+// 3x3 stride 2, 48 -> 96 / 192 (se_s2poly.hip): the polyphase F(2,2) image and its bias, as s2poly_pack_host (se_s2poly.h) lays
+// them out
+int pack_s2poly48(Layer& L, std::string& err) {
+  const LayerDef& d = L.def;
+  std::vector<float> img, bias;
+  if (d.cin != 48 || (int)L.w.size() != d.cout * 48 * 9 || !s2poly_pack_host(L.w.data(), L.b.data(), d.cout, img, bias)) {
+    err = std::string("layer ") + d.name + ": no polyphase image for this shape";
+    return 1;
+  }
+  if (upload(L.d_s2p, img, err)) return 1;
+  return upload(L.d_s2pb, bias, err);
+}
+
 // raw 3x3 conv 12 -> cout: [cout][9][12]; the bf16 mode runs the same fp32 kernel with bf16-rounded weights (every conv
 // weight is rounded in that mode)
 int pack_small(Layer& L, std::string& err) {
@@ -517,6 +531,11 @@ int pack_gated(Layer& L, const std::vector<int>& chans, std::string& err) {
   if (f.w16s && pack_rconv16(L, err)) return 1;
   if (f.w96 && pack_rconv96(L, err)) return 1;
   if (f.wd && pack_layer_dense(L, chans, err)) return 1;
+  if (f.s2p) {      // (48 stored channels that are the layer's 48, in order: layer_facts counts them, the identity is checked here)
+    for (int i = 0; i < nc; ++i)
+      if (chans[i] != i) { err = std::string("layer ") + L.def.name + ": the polyphase image needs its input channels in checkpoint order"; return 1; }
+    if (pack_s2poly48(L, err)) return 1;
+  }
   return pack_layer(L, padded(4), err);
 }
 
@@ -529,7 +548,8 @@ int pack_layer_images(Layer& L, const std::vector<int>& chans, std::string& err)
   const struct { const char* name; const float* img; bool fact; } have[] = {
       {"u", L.d_u, f.u}, {"ub", L.d_ub, f.ub}, {"u1", L.d_u1, f.u1}, {"wv", L.d_wv, f.wv}, {"wv16", L.d_wv16, f.wv16},
       {"u24", L.d_u24, f.u24}, {"ub24", L.d_ub24, f.ub24}, {"u24b", L.d_u24b, f.u24b}, {"wx", L.d_wx, f.wx}, {"wx2", L.d_wx2, f.wx2},
-      {"wd", L.d_wd, f.wd}, {"wdw", L.d_wdw, f.wdw}, {"w16d", L.d_w16d, f.w16d}, {"w16s", L.d_w16s, f.w16s}, {"w96", L.d_w96, f.w96}};
+      {"wd", L.d_wd, f.wd}, {"wdw", L.d_wdw, f.wdw}, {"w16d", L.d_w16d, f.w16d}, {"w16s", L.d_w16s, f.w16s}, {"w96", L.d_w96, f.w96},
+      {"s2p", L.d_s2p, f.s2p}, {"s2pb", L.d_s2pb, f.s2p}};
   for (const auto& h : have)
     if ((h.img != nullptr) != h.fact) {
       err = std::string("layer ") + L.def.name + ": weight image " + h.name + (h.fact ? " is missing" : " was built against the layer's facts");

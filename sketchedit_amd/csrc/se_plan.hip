@@ -109,6 +109,18 @@ struct ConvLaunch {       // one call: where it runs, the layer, the sources (sr
     HIPCHK(c, c24 ? launch_wino48_c24(wp, c->st) : launch_wino48(wp, c->st));
     return 0;
   }
+  // 3x3 stride 2, 48 -> 96 / 192: polyphase F(2,2), 25 of 36 products (se_s2poly.hip; 75 k-halves executed, 76 staged); a
+  // 192-row layer as two 96-row halves that both transform the source
+  int launch_form_s2poly(const Choice&) const {
+    const int halves = d.cout / 96;
+    WinoParams wp = wino_params(L.d_s2p, L.d_s2pb, 1, 2);
+    wp.th = Hin / 4; wp.tw = Win / 4; wp.total_tiles = B * wp.th * wp.tw;
+    udiv_magic_host((unsigned)(wp.th * wp.tw), &wp.div_tpi_m, &wp.div_tpi_l);
+    udiv_magic_host((unsigned)wp.tw, &wp.div_tw_m, &wp.div_tw_l);
+    set_launch_cost(alg(9), 4.0 * ((double)halves * B * Hin * Win * 48 + (double)B * Ho * Wo * (d.cout / 2)), d.name, alg(9) * 25.0 / 36.0);
+    HIPCHK(c, launch_s2poly48(wp, halves, c->st));
+    return 0;
+  }
   // gen_deconv 96 -> 96 and 48 -> 48: F(2x2,2x2) on the sub-pixel classes, 9 of 36 products (se_wino_up.hip, se_wino_up48.hip;
   // 48: in the K pairing of the 48-channel kernels, 28 k-halves executed for 27 of work)
   int launch_form_winoup(const Choice& ch) const {
@@ -293,6 +305,7 @@ int run_gconv(se_ctx* c, const Layer& L, const float* src0, int C0, const float*
     case F_RTILE: case F_RTILE_D4: return a.launch_form_rtile(ch);
     case F_RCONV16: case F_RCONV16_DUAL: return a.launch_form_rconv16(ch);
     case F_RCONV96: return a.launch_form_rconv96(ch);
+    case F_S2POLY48: return a.launch_form_s2poly(ch);
     case F_GATHER: return a.launch_form_gather(ch);
     case F_SMALL_CONV: break;      // (a raw layer has no gated image: refused above)
   }

@@ -8,6 +8,8 @@ KERNEL_LABELS = {
     "wino_kernel": "wino_n192", "wino24_kernel": "wino_n192", "rconv16": "gconv_n192", "gconv_kernel<12": "gconv_n192",
     # 48 -> 96 / 24 -> 96
     "wino48_kernel": "wino_n96", "rconv96": "gconv_n96", "gconv_kernel<6": "gconv_n96",
+    # 48 -> 96 / 192 at stride 2 in 96-row halves (polyphase F(2,2), se_s2poly.hip)
+    "s2poly48_kernel": "wino_n96",
     "winoup_kernel": "wino_up96",
     # 48 output rows: 5x5 heads, 24 -> 48 stride 2, gen_deconv 48 -> 48
     "winoup48_kernel": "gconv_n48", "rtile_dense5w_kernel": "gconv_n48", "rtile_dense5_kernel": "gconv_n48",

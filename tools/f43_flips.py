@@ -9,7 +9,9 @@ rounding error of F(2x2,3x3); this tool measures what that costs, per mode
                                        as mode 1, removed from the library)
 against the fp32 oracle: flips of the hard mask, max / mean |soft mask error|, and the mean error over the pixels whose
 oracle value lies in [0.4, 0.6] (the ones a larger error could flip), over the three procedural weight sets and N seeded
-inputs per set at 256x256 (+ N/4 at 512x512).   usage: python tools/f43_flips.py [N=16] > f43_flips.json
+inputs per set at 256x256 (+ N/4 at 512x512).   usage: python tools/f43_flips.py [N=16] [SWITCH] > f43_flips.json
+SWITCH (default SE_WINOGRAD_F43) names another three-valued switch of the same kind to walk instead, every other switch at its
+default: SE_S2_POLY (0 gather-GEMM, 1 the polyphase F(2,2) form of the 48-channel stride-2 layers everywhere, 2 in netG only).
 """
 import json
 import os
@@ -27,6 +29,7 @@ from sketchedit_amd.hostinfo import effective_cpus  # noqa: E402
 
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 16
+    switch = sys.argv[2] if len(sys.argv) > 2 else "SE_WINOGRAD_F43"
     torch.set_num_threads(min(32, effective_cpus()))
     res = {m: {"flips": 0, "pixels": 0, "max_abs": 0.0, "sum_abs": 0.0, "near": 0, "near_sum_abs": 0.0, "near_max_abs": 0.0} for m in (0, 1, 2)}
     per_set = {}
@@ -42,7 +45,7 @@ def main():
                 ref = O.netM_forward(WMt, torch.from_numpy(img), torch.from_numpy(sk), want_image=False)[0].numpy()
                 near = np.abs(ref - 0.5) < 0.1
                 for m in res:
-                    _lib.set_option("SE_WINOGRAD_F43", m)
+                    _lib.set_option(switch, m)
                     got = eng.netM(torch.from_numpy(img).cuda(), torch.from_numpy(sk).cuda(), want_image=False)[0].cpu().numpy()
                     err = np.abs(got.astype(np.float64) - ref.astype(np.float64))
                     r = res[m]
@@ -64,7 +67,7 @@ def main():
         out[str(m)] = {"hard_mask_flips": r["flips"], "pixels": r["pixels"], "max_abs_soft_mask": r["max_abs"],
                        "mean_abs_soft_mask": r["sum_abs"] / max(r["pixels"], 1), "pixels_within_0.1_of_threshold": r["near"],
                        "mean_abs_near_threshold": r["near_sum_abs"] / max(r["near"], 1), "max_abs_near_threshold": r["near_max_abs"]}
-    print(json.dumps({"modes": out, "per_weight_set_and_size": {k: {str(m): v for m, v in d.items()} for k, d in per_set.items()},
+    print(json.dumps({"switch": switch, "modes": out, "per_weight_set_and_size": {k: {str(m): v for m, v in d.items()} for k, d in per_set.items()},
                       "inputs_per_set": {"256": n, "512": max(1, n // 4)}}, indent=1))
 
 
