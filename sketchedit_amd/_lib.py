@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_s2poly.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_modify.hip", "se_outline.hip", "se_move.hip", "se_warp.hip", "se_filter.hip", "se_adjust.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_modify.hip", "se_outline.hip", "se_move.hip", "se_blend.hip", "se_warp.hip", "se_filter.hip", "se_adjust.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
            "se_plan.hip", "se_api_window.hip", "se_api_select.hip", "se_api_move.hip", "se_api_codec.hip", "se_api_debug.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
@@ -73,6 +73,10 @@ OUTLINE_TILE, OUTLINE_MAX_CAP = 64, 1 << 24       # SE_OUTLINE_TILE, SE_OUTLINE_
 MOVE_SYMBOLS = ["se_move_drop_u8", "se_plane_shift_u8"]
 MOVE_MAX_OFFSET, MOVE_MAX_RADIUS = 16384, 16      # SE_MOVE_MAX_OFFSET, SE_MOVE_MAX_RADIUS
 MOVE_FLIP_X, MOVE_FLIP_Y = 1, 2                   # SE_MOVE_FLIP_*
+# every entry declared in include/sketchedit_blend.h (seamless move and clone).  They carry the library's name, not se_,
+# and this list is not a *_SYMBOLS list: the se_ names, those lists and their number are what the earlier entries' tests pin
+BLEND_ENTRIES = ["sketchedit_move_blend_u8_workspace_bytes", "sketchedit_move_blend_u8"]
+BLEND_MAX_SIDE = 2048                             # SE_BLEND_MAX_SIDE
 # every symbol declared in include/sketchedit_warp.h (scale and rotate a selection)
 WARP_SYMBOLS = ["se_warp_drop_u8", "se_plane_warp_u8"]
 WARP_MAX_COEF, WARP_MAX_TRANSLATION = 1 << 20, 1 << 40      # SE_WARP_MAX_COEF, SE_WARP_MAX_TRANSLATION
@@ -316,6 +320,10 @@ def load_library():
         lib.se_plane_modify_u8.restype = ci
         lib.se_move_drop_u8.argtypes =[vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8
         lib.se_move_drop_u8.restype = ci
+        lib.sketchedit_move_blend_u8_workspace_bytes.argtypes = [ci, ci]
+        lib.sketchedit_move_blend_u8_workspace_bytes.restype = sz
+        lib.sketchedit_move_blend_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 7 + [vp, sz]
+        lib.sketchedit_move_blend_u8.restype = ci
         lib.se_plane_shift_u8.argtypes = [vp, vp, vp, ci, ci] + [ci] * 7 + [vp]
         lib.se_plane_shift_u8.restype = ci
         lib.se_warp_drop_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8 + [vp]
@@ -1297,6 +1305,21 @@ class Engine:
         if self.lib.se_move_drop_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
                                     by0, bx0, by1, bx1, int(offset[0]), int(offset[1]), int(flip), int(radius)):
             self._err("se_move_drop_u8")
+
+    def move_blend_u8(self, frame, lift, lift_rect, sel, lock, box, offset, flip=0):
+        """sketchedit_move_blend_u8 (include/sketchedit_blend.h), in place on `frame`: move_drop_u8's arguments without the
+        radius; the object keeps its own detail and takes the local colour of the place it lands in -- the lift's bytes plus a
+        membrane that equals frame - lift on the object's rim, made by a fixed schedule of integer steps.  `lift_rect` should
+        hold the box grown by one pixel (the rim's sources); a side of the box is at most BLEND_MAX_SIDE.  The launches depend
+        on the box's size alone; none when the whole box lands outside the frame."""
+        Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._lift_args("move_blend_u8", frame, lift, lift_rect, sel, lock, box)
+        need = self.lib.sketchedit_move_blend_u8_workspace_bytes(by1 - by0, bx1 - bx0)
+        if need == 0:
+            raise SketchEditHipError("move_blend_u8: a side of the box %r is outside 1 .. %d" % ((by0, bx0, by1, bx1), BLEND_MAX_SIDE))
+        ws_t = self._workspace_bytes(need)
+        if self.lib.sketchedit_move_blend_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
+                                     by0, bx0, by1, bx1, int(offset[0]), int(offset[1]), int(flip), _ptr(ws_t), ws_t.numel()):
+            self._err("sketchedit_move_blend_u8")
 
     def plane_shift_u8(self, sel, box, offset, flip=0, out=None):
         """se_plane_shift_u8: `sel` (Hi,Wi) uint8 on the device, non-zero = selected -> `out` (a new plane, or another plane of

@@ -2,8 +2,10 @@
 // (kernels: se_move.hip); and behind include/sketchedit_warp.h the drop through an affine map and the warp
 // of the plane (kernels: se_warp.hip); and behind include/sketchedit_filter.h the blur and the mosaic of a
 // selection (kernels: se_filter.hip); and behind include/sketchedit_adjust.h the tone and colour of a selection,
-// the histogram and the table made of it (kernels: se_adjust.hip).
+// the histogram and the table made of it (kernels: se_adjust.hip); and behind include/sketchedit_blend.h the
+// seamless drop (kernels: se_blend.hip).
 #include "../../include/sketchedit_adjust.h"
+#include "../../include/sketchedit_blend.h"
 #include "../../include/sketchedit_filter.h"
 #include "../../include/sketchedit_move.h"
 #include "../../include/sketchedit_warp.h"
@@ -112,6 +114,41 @@ int se_move_drop_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, in
   const int lpitch = (3 * lw + 15) & ~15;
   HIPCHK(c, launch_move_drop(frame_u8, Hi, Wi, lift, ly0, lx0, lw, lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, dy, dx, flip, radius,
                              (hipStream_t)stream));
+  return 0;
+}
+
+size_t sketchedit_move_blend_u8_workspace_bytes(int box_h, int box_w) {
+  if (box_h < 1 || box_w < 1 || box_h > SE_BLEND_MAX_SIDE || box_w > SE_BLEND_MAX_SIDE) return 0;
+  return blend_workspace_bytes(box_h + 2, box_w + 2);
+}
+
+// The plain drop's checks, then the workspace's; the launches are a function of the rectangle's size alone (se_blend.hip).  The
+// workspace is the one scratch region: SE_TEST_POISON fills it, and the kernels write every record in front of its first read.
+int sketchedit_move_blend_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh,
+                     int lw, const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, int dy, int dx,
+                     int flip, void* workspace, size_t workspace_bytes) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (lift_check_shape(c, frame_u8, Hi, Wi, lift, ly0, lx0, lh, lw, sel_u8, by0, bx0, by1, bx1)) return 1;
+  if (move_check_offset(c, dy, dx, flip)) return 1;
+  if (by1 - by0 > SE_BLEND_MAX_SIDE || bx1 - bx0 > SE_BLEND_MAX_SIDE)
+    return fail(c, "the box (%d, %d, %d, %d) has a side above %d", by0, bx0, by1, bx1, SE_BLEND_MAX_SIDE);
+  if (lift_check_overlaps(c, frame_u8, Hi, Wi, lift, lh, lw, sel_u8, lock_u8)) return 1;
+  if (!workspace) return fail(c, "null pointer argument: workspace");
+  const size_t need = sketchedit_move_blend_u8_workspace_bytes(by1 - by0, bx1 - bx0), pn = (size_t)Hi * Wi;
+  if (workspace_bytes < need) return fail(c, "workspace too small: %zu bytes, need %zu", workspace_bytes, need);
+  if (!aligned_to(workspace, 16)) return fail(c, "workspace must be 16-byte aligned");
+  const size_t ln = (size_t)lh * (((size_t)3 * lw + 15) & ~(size_t)15);
+  if (overlaps(workspace, need, frame_u8, 3 * pn)) return fail(c, "workspace overlaps frame_u8");
+  if (overlaps(workspace, need, lift, ln)) return fail(c, "workspace overlaps lift");
+  if (overlaps(workspace, need, sel_u8, pn)) return fail(c, "workspace overlaps sel_u8");
+  if (lock_u8 && overlaps(workspace, need, lock_u8, pn)) return fail(c, "workspace overlaps lock_u8");
+  if (device_enter(c)) return 1;
+  const hipStream_t st = (hipStream_t)stream;
+  const int lpitch = (3 * lw + 15) & ~15;
+  const bool lands = (by0 + dy > 0 ? by0 + dy : 0) < (by1 + dy < Hi ? by1 + dy : Hi) && (bx0 + dx > 0 ? bx0 + dx : 0) < (bx1 + dx < Wi ? bx1 + dx : Wi);
+  if (lands && poison(c, workspace, need, st)) return 1;             // the whole box outside the frame: nothing is enqueued
+  HIPCHK(c, launch_move_blend(frame_u8, Hi, Wi, lift, ly0, lx0, lh, lw, lpitch, sel_u8, lock_u8, by0, bx0, by1, bx1, dy, dx, flip, workspace, st));
   return 0;
 }
 

@@ -21,7 +21,8 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
-                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW, PL_MODIFY_DISC, PL_MODIFY_VOTE,
+                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_BLEND_INIT, PL_BLEND_PULL, PL_BLEND_RELAX, PL_BLEND_APPLY,
+                 PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW, PL_MODIFY_DISC, PL_MODIFY_VOTE,
                  PL_LASSO_FILL, PL_PLANE_COMBINE, PL_ADJUST, PL_HIST_TILES, PL_HIST_SUM, PL_ADJUST_LUT, PL_OUTLINE_COUNT, PL_OUTLINE_SCAN, PL_OUTLINE_EMIT, PL_FILTER_BLUR, PL_FILTER_MOSAIC, PL_MOVE_DROP,
                  PL_PLANE_SHIFT, PL_WARP_DROP, PL_PLANE_WARP, PL_COUNT };
 const char* prof_label_name(int l);
@@ -484,6 +485,13 @@ hipError_t launch_move_drop(unsigned char* frame, int Hi, int Wi, const unsigned
                             int radius, hipStream_t st);
 hipError_t launch_plane_shift(const unsigned char* sel, int Hi, int Wi, int by0, int bx0, int by1, int bx1, int dy, int dx, int flip,
                               unsigned char* out, hipStream_t st);
+// seamless move and clone (include/sketchedit_blend.h; se_blend.hip): move_drop's arguments and a workspace of
+// blend_workspace_bytes(eh, ew) bytes, 16-byte aligned, for the eh x ew rectangle E -- the shifted box clipped to the frame, grown
+// by one pixel and clipped again.  The launches are a function of eh and ew alone; none when the box lands outside the frame.
+size_t blend_workspace_bytes(int eh, int ew);
+hipError_t launch_move_blend(unsigned char* frame, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh, int lw, int lpitch,
+                             const unsigned char* sel, const unsigned char* lock, int by0, int bx0, int by1, int bx1, int dy, int dx, int flip,
+                             void* ws, hipStream_t st);
 // blur, sharpen or pixelate a selection (include/sketchedit_filter.h; se_filter.hip).  Any Hi, Wi >= 16 and any
 // alignment of the frame and the planes; the frame is only written, every input pixel comes from the lift.  taps: radius + 1 ints
 // on the host.  filter_blur: the grid is the box's 64 x 16 tiles, the LDS that of the radius' class; filter_mosaic: a wave per cell.

@@ -2,10 +2,7 @@
 // tests/move_util.py).  Two integer-only kernels, plain vector loads and stores, no atomics, nothing polled, any alignment of the
 // frame, the planes and Wi, no byte outside the frame, a plane or the slot's rows read or written.
 //
-//  moved(y, x) = S[q] != 0 with q = (y - dy, x - dx), mirrored about the box by the flip bits, where q lies in the box; else 0.
-//                q is a function of the DESTINATION pixel: the kernels gather.  Four neighbouring x have four neighbouring qx,
-//                ascending without the x flip and descending with it, so they are one load4_within bounded by the box's row of S
-//                (bytes outside the box read as 0 without a load), byte-swapped under the flip.
+//  moved(y, x): MoveMap (se_movemap.h), the gather that the seamless drop (se_blend.hip) shares.
 //
 //  move_drop<FEATHER>: window_paste_feather's shape (se_feather.hip) on se_seltile.h's tile.  The grid covers the tiles of the shifted box
 //                clipped to the frame, never the frame.  FEATHER (r > 0), three steps over LDS:
@@ -23,6 +20,7 @@
 #include "../../include/sketchedit_hip.h"
 #include "../../include/sketchedit_move.h"
 #include "se_kernels.h"
+#include "se_movemap.h"
 #include "se_seltile.h"
 
 #include <cstdint>
@@ -30,28 +28,6 @@
 namespace se {
 
 namespace {
-
-// the offset / flip map and the box it gathers from
-struct MoveMap {
-  const unsigned char* sel;
-  int Wi, by0, bx0, by1, bx1, dy, dx, flip;
-  __device__ __forceinline__ int qy(int y) const { return (flip & SE_MOVE_FLIP_Y) ? by0 + by1 - 1 - (y - dy) : y - dy; }
-  // the source column of destination column x; the columns x + 1 .. follow it ascending, descending with the x flip
-  __device__ __forceinline__ int qx(int x) const { return (flip & SE_MOVE_FLIP_X) ? bx0 + bx1 - 1 - (x - dx) : x - dx; }
-  // moved of the destination pixels (y, x .. x + 3): a byte of {0, 1} each
-  __device__ __forceinline__ unsigned moved4(int y, int x) const {
-    const int sy = qy(y);
-    if (sy < by0 || sy >= by1) return 0u;
-    const unsigned char* row = sel + (size_t)sy * Wi;                     // the box's row of S: [row + bx0, row + bx1)
-    const int sx = qx(x);
-    if (flip & SE_MOVE_FLIP_X) {
-      if (sx < bx0 || sx - 3 >= bx1) return 0u;
-      return bytes_nonzero(__builtin_bswap32(load4_within(row + (sx - 3), row + bx0, row + bx1)));
-    }
-    if (sx + 3 < bx0 || sx >= bx1) return 0u;
-    return bytes_nonzero(load4_within(row + sx, row + bx0, row + bx1));
-  }
-};
 
 template <bool FEATHER>
 __global__ void __launch_bounds__(256) move_drop_kernel(unsigned char* __restrict__ frame, int Wi, Lift lift, MoveMap mm,

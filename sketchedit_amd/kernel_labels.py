@@ -60,6 +60,11 @@ KERNEL_LABELS = {
     "(anonymous namespace)::move_drop_kernel<false>": "move_drop", "(anonymous namespace)::move_drop_kernel<true>": "move_drop",
     "(anonymous namespace)::plane_shift_kernel": "plane_shift",
     "move_drop_kernel<false>": "move_drop", "move_drop_kernel<true>": "move_drop", "plane_shift_kernel": "plane_shift",
+    # seamless move and clone (se_blend.hip): the rim's classification, the pull, the sweeps of a level, the drop
+    "(anonymous namespace)::blend_init_kernel": "blend_init", "(anonymous namespace)::blend_pull_kernel": "blend_pull",
+    "(anonymous namespace)::blend_relax_kernel": "blend_relax", "(anonymous namespace)::blend_apply_kernel": "blend_apply",
+    "blend_init_kernel": "blend_init", "blend_pull_kernel": "blend_pull", "blend_relax_kernel": "blend_relax",
+    "blend_apply_kernel": "blend_apply",
     # scale and rotate a selection (se_warp.hip): the resampling drop, and the warp of the plane
     "(anonymous namespace)::warp_drop_kernel": "warp_drop", "(anonymous namespace)::plane_warp_kernel": "plane_warp",
     "warp_drop_kernel": "warp_drop", "plane_warp_kernel": "plane_warp",

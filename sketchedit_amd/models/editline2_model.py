@@ -247,6 +247,11 @@ class EditLine2Model(torch.nn.Module):
         (Engine.move_drop_u8)."""
         self.engine().move_drop_u8(frame, lift, lift_rect, sel, lock, box, offset, flip=flip, radius=radius)
 
+    def move_blend_u8(self, frame, lift, lift_rect, sel, lock, box, offset, flip=0):
+        """The seamless drop of a move (DESIGN.md 6x), in place on a resident frame: move_drop_u8's arguments without the radius;
+        the lifted pixels plus a membrane that matches them to the place they land in (Engine.move_blend_u8)."""
+        self.engine().move_blend_u8(frame, lift, lift_rect, sel, lock, box, offset, flip=flip)
+
     def plane_shift_u8(self, sel, box, offset, flip=0, out=None):
         """A selection plane moved as move_drop_u8 moves its pixels: a new 0 / 255 plane (Engine.plane_shift_u8)."""
         return self.engine().plane_shift_u8(sel, box, offset, flip=flip, out=out)

@@ -387,6 +387,8 @@ def rings_svg_path(rings):
 MOVE_MAX_OFFSET = 16384      # SE_MOVE_MAX_OFFSET
 MOVE_FLIPS = {None: 0, "h": 1, "v": 2, "hv": 3}     # SE_MOVE_FLIP_X | SE_MOVE_FLIP_Y
 MOVE_MIN_SIDE = 16           # the smallest side of a journal slot's rectangle
+MOVE_BLENDS = (None, "seamless")                    # move_selection's `blend`
+BLEND_MAX_SIDE = 2048        # SE_BLEND_MAX_SIDE
 
 
 def move_rect(box, offset, frame_hw):
@@ -1089,6 +1091,12 @@ class _ModelBackend:
         slot `lift` of `lift_rect` holds them, land `offset` away under `flip` (SE_MOVE_FLIP_*) where `lock` (or None) is 0, with a
         soft edge of `radius`"""
         self.model.move_drop_u8(frame, lift, lift_rect, plane, lock, box, offset, flip=flip, radius=radius)
+
+    def move_blend(self, frame, lift, lift_rect, plane, lock, box, offset, flip):
+        """the seamless drop of a move, in place on the frame: move_drop's arguments without the radius; the lifted
+        pixels plus a membrane that equals frame - lift on the object's rim.  `lift_rect` holds the box grown by one pixel.  A
+        fixed schedule of launches that depends on the box's size alone"""
+        self.model.move_blend_u8(frame, lift, lift_rect, plane, lock, box, offset, flip=flip)
 
     def shift(self, plane, box, offset, flip):
         """a selection's plane moved as move_drop moves its pixels -> (plane, box, count) of a NEW plane: one
@@ -1900,11 +1908,12 @@ class EditSession:
 
     # ---- what the operators on a lifted selection share (DESIGN.md 6r .. 6u) -----------------------------------------------------------
     def _lift_fill_drop(self, selection, dst, window, margin, low_latency, max_side, encode, feather, keep_source, hole_grow, drop, remap,
-                        info, drop_feathers):
+                        info, drop_feathers, lift_grow=0):
         """move_selection and transform_selection once their own arguments are checked: the lift, the fill of the hole -- the
         selection grown by `hole_grow` -- unless `keep_source`, `drop(lift, lift_rect)` into the rectangle `dst`, and `remap()` ->
         (plane, box, count) of the new Selection; ONE ordered undo step.  `info`: the caller's own keys.  `drop_feathers`: the
-        drop takes `feather` itself, so info reports it even where no fill ran."""
+        drop takes `feather` itself, so info reports it even where no fill ran.  `lift_grow`: the lift holds the box grown by
+        that many pixels and clipped to the frame (the seamless drop reads the object's rim)."""
         Hi, Wi = self.frame_hw
         box = selection.box
         grown = (max(box[0] - hole_grow, 0), max(box[1] - hole_grow, 0), min(box[2] + hole_grow, Hi), min(box[3] + hole_grow, Wi))
@@ -1916,7 +1925,8 @@ class EditSession:
         be = self.backend
         with self._lock:
             frames = [self._frame]
-            lift_rect = move_rect(box, (0, 0), self.frame_hw)
+            lift_box = (max(box[0] - lift_grow, 0), max(box[1] - lift_grow, 0), min(box[2] + lift_grow, Hi), min(box[3] + lift_grow, Wi))
+            lift_rect = move_rect(lift_box, (0, 0), self.frame_hw)
             lift = be.save(frames, [lift_rect[:2]], lift_rect[2:])[0]
             slots, work, pasted = [], None, False
             try:
@@ -1968,7 +1978,7 @@ class EditSession:
 
     # ---- move or clone a selection ------------------------------------------------------------------------------------
     def move_selection(self, selection, offset, flip=None, keep_source=False, hole_grow=2, window=None, margin=0.5, low_latency=None,
-                       max_side=None, encode=None, feather=None):
+                       max_side=None, encode=None, feather=None, blend=None):
         """"Drag this over there and mend the place it came from" (DESIGN.md 6r): the selected pixels land `offset` = (dy, dx) away
         -- two ints, each at most 16 384 in magnitude -- mirrored about the selection's box by `flip` (None, "h", "v" or "hv"),
         and the place they came from is filled.  Everything happens on the device under ONE hold of the session's lock:
@@ -1992,9 +2002,17 @@ class EditSession:
         the slots exceed `history_bytes` together the move commits unjournalled and clears the history.  A backend call that
         fails once the frame was written clears the history too: no entry could restore a state the frame was in.
         clone_selection(...) is move_selection(..., keep_source=True).
+        `blend` = "seamless"  makes step 3 a gradient-domain drop: the object keeps its own detail and takes the local
+        colour of the place it lands in -- the lifted pixels plus a smooth membrane that equals frame - lift on the object's
+        rim, made by a fixed schedule of integer steps (include/sketchedit_blend.h): the same bytes on every machine, and no claim
+        of closeness to the harmonic solution beyond DESIGN.md's measured figures.  The lift is then of the box grown by one
+        pixel (the rim's sources; only the frame's edge leaves a side of the object without a rim), `feather` goes to the fill of
+        the hole only, info["blend"] = "seamless"; the journal, the lock, `keep_source` and the moved selection are as above.
+        A side of the selection's box is at most 2048 pixels.
         TypeError / ValueError, all before the first backend call: a selection that is none, of another frame size or empty, an
         offset that is not two ints or is above the limit, one that moves the whole selection out of the frame, a bad flip,
-        hole_grow, window, max_side, encode or feather."""
+        hole_grow, window, max_side, encode, feather or blend, a box too large for the blend.  NotImplementedError, before it
+        too: `blend` on a backend without move_blend."""
         encode = _check_encode(encode)
         feather = _check_feather(feather)
         self._check_selection(selection, "move_selection")
@@ -2010,11 +2028,22 @@ class EditSession:
         if not (flip is None or isinstance(flip, str)) or flip not in MOVE_FLIPS:
             raise ValueError("flip is None, 'h', 'v' or 'hv' (got %r)" % (flip,))
         hole_grow = _check_hole_grow(hole_grow)
+        if not (blend is None or isinstance(blend, str)) or blend not in MOVE_BLENDS:
+            raise ValueError("blend is None or 'seamless' (got %r)" % (blend,))
         box, flips = selection.box, MOVE_FLIPS[flip]
         dst = move_rect(box, offset, self.frame_hw)
         if dst is None:
             raise ValueError("offset %r moves the whole selection out of the frame" % (offset,))
         be = self.backend
+        if blend is not None:
+            if max(box[2] - box[0], box[3] - box[1]) > BLEND_MAX_SIDE:
+                raise ValueError("blend=%r takes a selection whose box has sides of at most %d (got %r)" % (blend, BLEND_MAX_SIDE, box))
+            if not callable(getattr(be, "move_blend", None)):
+                raise NotImplementedError("this backend has no move_blend: blend=%r needs the seamless drop (DESIGN.md 6x)" % (blend,))
+            return self._lift_fill_drop(
+                selection, dst, window, margin, low_latency, max_side, encode, feather, keep_source, hole_grow,
+                lambda lift, lift_rect: be.move_blend(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, offset, flips),
+                lambda: be.shift(selection.plane, box, offset, flips), dict(move=True, offset=offset, flip=flip, blend=blend), False, lift_grow=1)
         return self._lift_fill_drop(
             selection, dst, window, margin, low_latency, max_side, encode, feather, keep_source, hole_grow,
             lambda lift, lift_rect: be.move_drop(self._frame, lift, lift_rect, selection.plane, self._lock_plane, box, offset, flips, feather or 0),

@@ -1,0 +1,400 @@
+"""The statement of DESIGN.md 6x (include/sketchedit_blend.h) in plain numpy, restated independently of sketchedit_amd.serve: the
+seamless drop of a lifted selection -- the lift's bytes plus a membrane made by a FIXED schedule of integer steps -- and, below
+it, the kernels of se_blend.hip restated on one flat byte array with every access checked."""
+import numpy as np
+
+import move_util as M
+
+MAX_SIDE = 2048
+OUT, KNOWN, UNKNOWN = 0, 1, 2
+U_ZERO = 4096
+
+
+def rects(box, offset, frame_hw):
+    """D, the shifted box clipped to the frame, and E, D grown by one pixel and clipped to the frame, each (y0, x0, y1, x1) half
+    open; (None, None) when D is empty"""
+    Hi, Wi = frame_hw
+    d = (max(box[0] + offset[0], 0), max(box[1] + offset[1], 0), min(box[2] + offset[0], Hi), min(box[3] + offset[1], Wi))
+    if d[0] >= d[2] or d[1] >= d[3]:
+        return None, None
+    return d, (max(d[0] - 1, 0), max(d[1] - 1, 0), min(d[2] + 1, Hi), min(d[3] + 1, Wi))
+
+
+def sweeps_of(level):
+    """J_l = min(4 << l, 64)"""
+    return min(4 << min(level, 4), 64)
+
+
+def level_sizes(h, w):
+    """[(h, w)] of levels 0 .. T"""
+    out = [(h, w)]
+    while out[-1] != (1, 1):
+        out.append(((out[-1][0] + 1) // 2, (out[-1][1] + 1) // 2))
+    return out
+
+
+def _src(box, offset, flip, ys, xs):
+    """src(p) for the pixels ys x xs, any integers, NOT clipped"""
+    qy, qx = np.asarray(ys, np.int64) - offset[0], np.asarray(xs, np.int64) - offset[1]
+    if flip & 2:
+        qy = box[0] + box[2] - 1 - qy
+    if flip & 1:
+        qx = box[1] + box[3] - 1 - qx
+    return qy, qx
+
+
+def level0(frame, lift, lift_rect, sel, lock, box, offset, flip):
+    """-> (E, state (eh, ew), u (eh, ew, 3) int64 -- set on KNOWN cells, 0 elsewhere), or None when D is empty"""
+    Hi, Wi = sel.shape
+    ly0, lx0, lh, lw = lift_rect
+    assert ly0 <= box[0] < box[2] <= ly0 + lh and lx0 <= box[1] < box[3] <= lx0 + lw
+    assert max(box[2] - box[0], box[3] - box[1]) <= MAX_SIDE
+    d, e = rects(box, offset, (Hi, Wi))
+    if d is None:
+        return None
+    ys, xs = np.arange(e[0] - 1, e[2] + 1), np.arange(e[1] - 1, e[3] + 1)          # E and one pixel around it
+    moved, _, _ = M._moved(sel, box, offset, flip, ys, xs)
+    iny, inx = (ys >= 0) & (ys < Hi), (xs >= 0) & (xs < Wi)
+    target = moved & iny[:, None] & inx[None, :]
+    if lock is not None:
+        target &= np.asarray(lock)[np.clip(ys, 0, Hi - 1)[:, None], np.clip(xs, 0, Wi - 1)[None, :]] == 0
+    qy, qx = _src(box, offset, flip, ys[1:-1], xs[1:-1])
+    held = ((qy >= ly0) & (qy < ly0 + lh))[:, None] & ((qx >= lx0) & (qx < lx0 + lw))[None, :]
+    omega = target[1:-1, 1:-1]
+    beside = target[:-2, 1:-1] | target[2:, 1:-1] | target[1:-1, :-2] | target[1:-1, 2:]
+    known = ~omega & beside & held                                           # (every pixel of E is in the frame)
+    state = np.where(omega, UNKNOWN, np.where(known, KNOWN, OUT)).astype(np.uint8)
+    P = np.asarray(lift)[:, :3 * lw].reshape(lh, lw, 3).astype(np.int64)
+    srcv = P[np.clip(qy - ly0, 0, lh - 1)[:, None], np.clip(qx - lx0, 0, lw - 1)[None, :]]
+    F = np.asarray(frame)[e[0]:e[2], e[1]:e[3]].astype(np.int64)
+    u = np.where(known[..., None], 16 * (F - srcv) + U_ZERO, 0)
+    return e, state, u
+
+
+def pull(state, u):
+    """level l from level l - 1"""
+    h, w = state.shape
+    ph, pw = (h + 1) // 2, (w + 1) // 2
+    st = np.full((2 * ph, 2 * pw), OUT, np.uint8)
+    st[:h, :w] = state
+    uu = np.zeros((2 * ph, 2 * pw, 3), np.int64)
+    uu[:h, :w] = u
+    st4 = st.reshape(ph, 2, pw, 2)
+    k4 = st4 == KNOWN
+    cnt = k4.sum(axis=(1, 3)).astype(np.int64)
+    total = (uu.reshape(ph, 2, pw, 2, 3) * k4[..., None]).sum(axis=(1, 3))
+    c = np.maximum(cnt, 1)[..., None]
+    pu = np.where(cnt[..., None] > 0, (2 * total + c) // (2 * c), 0)
+    ps = np.where(cnt > 0, KNOWN, np.where((st4 == UNKNOWN).any(axis=(1, 3)), UNKNOWN, OUT)).astype(np.uint8)
+    return ps, pu
+
+
+def half_sweep(state, u, parity):
+    """one half-sweep in place"""
+    h, w = state.shape
+    live = np.zeros((h + 2, w + 2), bool)
+    live[1:-1, 1:-1] = state != OUT
+    up = np.zeros((h + 2, w + 2, 3), np.int64)
+    up[1:-1, 1:-1] = u
+    up *= live[..., None]
+    k = (live[:-2, 1:-1].astype(np.int64) + live[2:, 1:-1] + live[1:-1, :-2] + live[1:-1, 2:])
+    total = up[:-2, 1:-1] + up[2:, 1:-1] + up[1:-1, :-2] + up[1:-1, 2:]
+    yy, xx = np.mgrid[0:h, 0:w]
+    m = (state == UNKNOWN) & (((yy + xx) & 1) == parity) & (k > 0)
+    kk = np.maximum(k, 1)[..., None]
+    u[m] = ((2 * total + kk) // (2 * kk))[m]
+
+
+def membrane(state0, u0):
+    """pull and push -> [(state, u)] of levels 0 .. T after their sweeps"""
+    levels = [(state0, np.array(u0))]
+    while levels[-1][0].shape != (1, 1):
+        levels.append(pull(*levels[-1]))
+    T = len(levels) - 1
+    for l in range(T, -1, -1):
+        state, u = levels[l]
+        h, w = state.shape
+        if l == T:
+            start = np.full((h, w, 3), U_ZERO, np.int64)
+        else:
+            start = np.repeat(np.repeat(levels[l + 1][1], 2, axis=0), 2, axis=1)[:h, :w]
+        u[state == UNKNOWN] = start[state == UNKNOWN]
+        for _ in range(sweeps_of(l)):
+            half_sweep(state, u, 0)
+            half_sweep(state, u, 1)
+    return levels
+
+
+def spec_blend(frame, lift, lift_rect, sel, lock, box, offset, flip, want_levels=False):
+    """the statement -> the new frame (the arguments are only read); want_levels: -> (frame, E, levels) for the properties"""
+    out = np.array(frame)
+    l0 = level0(frame, lift, lift_rect, sel, lock, box, offset, flip)
+    if l0 is None:
+        return (out, None, None) if want_levels else out
+    e, state, u = l0
+    levels = membrane(state, u)
+    ly0, lx0, lh, lw = lift_rect
+    P = np.asarray(lift)[:, :3 * lw].reshape(lh, lw, 3).astype(np.int64)
+    qy, qx = _src(box, offset, flip, np.arange(e[0], e[2]), np.arange(e[1], e[3]))
+    srcv = P[np.clip(qy - ly0, 0, lh - 1)[:, None], np.clip(qx - lx0, 0, lw - 1)[None, :]]
+    v = np.clip(((16 * srcv + levels[0][1] + 8) >> 4) - 256, 0, 255).astype(np.uint8)
+    omega = state == UNKNOWN
+    out[e[0]:e[2], e[1]:e[3]][omega] = v[omega]
+    return (out, e, levels) if want_levels else out
+
+
+def workspace_bytes(box_h, box_w):
+    """sketchedit_move_blend_u8_workspace_bytes"""
+    if not (1 <= box_h <= MAX_SIDE and 1 <= box_w <= MAX_SIDE):
+        return 0
+    return sum(16 * h * w for h, w in level_sizes(box_h + 2, box_w + 2))
+
+
+def launches(box, offset, frame_hw):
+    """the number of launches of one call: a function of E's size alone"""
+    d, e = rects(box, offset, frame_hw)
+    if d is None:
+        return 0
+    sizes = level_sizes(e[2] - e[0], e[3] - e[1])
+    return 1 + (len(sizes) - 1) + sum(1 if h <= RX_H and w <= RX_W else sweeps_of(l) // 4 for l, (h, w) in enumerate(sizes)) + 1
+
+
+# ---- the kernels' arithmetic (se_blend.hip) on ONE flat byte array with every access checked ----------------------------------------
+RX_H, RX_W, RX_HALO = 32, 80, 8
+TILE_W, TILE_H = 64, 16
+
+
+class Memory(M.Memory):
+    """move_util's memory, and 8-byte cell records inside a span: a record that is read must have been written by a kernel"""
+
+    def __init__(self, size, fill=0xA5):
+        super().__init__(size, fill)
+        self.written = np.zeros(size, bool)
+        self.writers = np.zeros(size, np.int32)              # of the frame's bytes, by blend_apply
+
+    def read_cells(self, base, idx, span):
+        """the records base + 8 idx (an int array) -> (u (..., 3), state (...)); span = (lo, hi) bytes"""
+        idx = np.asarray(idx, np.int64)
+        a = base + 8 * idx
+        if a.size:
+            assert span[0] <= a.min() and a.max() + 8 <= span[1], "a record read outside its buffer"
+        b = self.mem[a[..., None] + np.arange(8)].astype(np.int64)
+        assert self.written[a[..., None] + np.arange(8)].all(), "a record read that no kernel wrote"
+        f = b[..., 0::2] | (b[..., 1::2] << 8)
+        return f[..., :3], f[..., 3]
+
+    def write_cells(self, base, idx, u, state, span):
+        idx = np.asarray(idx, np.int64)
+        a = base + 8 * idx
+        if a.size:
+            assert span[0] <= a.min() and a.max() + 8 <= span[1], "a record written outside its buffer"
+        f = np.concatenate([np.asarray(u, np.int64), np.asarray(state, np.int64)[..., None]], axis=-1)
+        assert (0 <= f).all() and (f < 1 << 16).all()
+        b = np.empty(f.shape[:-1] + (8,), np.uint8)
+        b[..., 0::2], b[..., 1::2] = f & 255, f >> 8
+        self.mem[a[..., None] + np.arange(8)] = b
+        self.written[a[..., None] + np.arange(8)] = True
+
+
+def _mean_round(total, n):
+    """(2 total + n) / (2 n) as mean_round forms it for n = 1 .. 4"""
+    return {1: total, 2: (total + 1) >> 1, 3: (2 * total + 3) // 6, 4: (total + 2) >> 2}[n]
+
+
+def _targets4(mem, sel, lock, Hi, Wi, box, offset, flip, y, x):
+    """targets4: a byte of {0, 1} for each of the pixels (y, x .. x + 3), any integers"""
+    if y < 0 or y >= Hi or x + 3 < 0 or x >= Wi:
+        return 0
+    m = M._moved4(mem, sel, Wi, box, offset, flip, y, x)
+    if not m:
+        return 0
+    lo, hi = max(x, 0), min(x + 4, Wi)
+    for p in range(4):
+        if not lo <= x + p < hi:
+            m &= ~(255 << (8 * p))
+    if lock is not None and m:
+        lrow = lock + y * Wi
+        m &= ~M._nonzero(mem.load4_within(lrow + x, lrow + lo, lrow + hi))
+    return m & 0xffffffff
+
+
+def _levels(ws, eh, ew):
+    """Levels: [(h, w, address of buffer 0, address of buffer 1)]"""
+    out, a = [], ws
+    for h, w in level_sizes(eh, ew):
+        out.append((h, w, a, a + 8 * h * w))
+        a += 16 * h * w
+    return out, a
+
+
+def _tiled_init(mem, frame, Hi, Wi, lift, lift_rect, sel, lock, box, offset, flip, e, out, span):
+    ly0, lx0, lh, lw = lift_rect
+    lpitch = (3 * lw + 15) // 16 * 16
+    ey0, ex0, eh, ew = e[0], e[1], e[2] - e[0], e[3] - e[1]
+    for ty0 in range(ey0, ey0 + eh, TILE_H):
+        for tx0 in range(ex0, ex0 + ew, TILE_W):
+            st = np.zeros((TILE_H + 2, 68), np.int64)
+            for i in range(TILE_H + 2):
+                for j4 in range(17):
+                    v = _targets4(mem, sel, lock, Hi, Wi, box, offset, flip, ty0 - 1 + i, tx0 - 1 + 4 * j4)
+                    st[i, 4 * j4:4 * j4 + 4] = [(v >> (8 * k)) & 1 for k in range(4)]
+            for ly in range(TILE_H):
+                y = ty0 + ly
+                if y >= ey0 + eh:
+                    continue
+                sy = box[0] + box[2] - 1 - (y - offset[0]) if flip & 2 else y - offset[0]
+                rowin = ly0 <= sy < ly0 + lh
+                for lx in range(TILE_W):
+                    x = tx0 + lx
+                    if x >= ex0 + ew:
+                        break
+                    i, j = ly + 1, lx + 1
+                    state, u = OUT, [0, 0, 0]
+                    if st[i, j]:
+                        state = UNKNOWN
+                    elif st[i - 1, j] | st[i + 1, j] | st[i, j - 1] | st[i, j + 1]:
+                        sx = box[1] + box[3] - 1 - (x - offset[1]) if flip & 1 else x - offset[1]
+                        if rowin and lx0 <= sx < lx0 + lw:
+                            assert 0 <= y < Hi and 0 <= x < Wi
+                            f = frame + (y * Wi + x) * 3
+                            q = lift + (sy - ly0) * lpitch + 3 * (sx - lx0)
+                            u = [16 * int(mem.mem[f + c]) + U_ZERO - 16 * int(mem.mem[q + c]) for c in range(3)]
+                            state = KNOWN
+                    mem.write_cells(out, (y - ey0) * ew + (x - ex0), u, state, span)
+
+
+def _tiled_pull(mem, child, ch, cw, cspan, out, ph, pw, ospan):
+    for y in range(ph):
+        for x in range(pw):
+            tot, n, unknown = [0, 0, 0], 0, False
+            for a in range(2):
+                for b in range(2):
+                    cy, cx = 2 * y + a, 2 * x + b
+                    if cy < ch and cx < cw:
+                        u, s = mem.read_cells(child, cy * cw + cx, cspan)
+                        if s == KNOWN:
+                            tot = [tot[c] + int(u[c]) for c in range(3)]
+                            n += 1
+                        elif s == UNKNOWN:
+                            unknown = True
+            if n:
+                mem.write_cells(out, y * pw + x, [_mean_round(t, n) for t in tot], KNOWN, ospan)
+            else:
+                mem.write_cells(out, y * pw + x, [0, 0, 0], UNKNOWN if unknown else OUT, ospan)
+
+
+def _mean_round_v(total, k):
+    """_mean_round on arrays, k in 0 .. 4 (0: unused)"""
+    return np.select([k == 1, k == 2, k == 3, k == 4], [total, (total + 1) >> 1, (2 * total + 3) // 6, (total + 2) >> 2], 0)
+
+
+def _tiled_relax(mem, src, sspan, dst, dspan, parent, pspan, h, w, pw, halo, sweeps, first):
+    """one launch of blend_relax: every workgroup stages its 32 x 80 cells, sweeps them, writes the cells `halo` inside"""
+    th, tw = RX_H - 2 * halo, RX_W - 2 * halo
+    ii, jj = np.mgrid[0:RX_H, 0:RX_W]
+    for by in range(1 if not halo else (h + TILE_H - 1) // TILE_H):
+        for bx in range(1 if not halo else (w + TILE_W - 1) // TILE_W):
+            gy, gx = by * th - halo + ii, bx * tw - halo + jj
+            ing = (gy >= 0) & (gy < h) & (gx >= 0) & (gx < w)
+            s = np.full((RX_H, RX_W), OUT, np.int64)
+            u = np.zeros((RX_H, RX_W, 3), np.int64)
+            u[ing], s[ing] = mem.read_cells(src, gy[ing] * w + gx[ing], sspan)
+            if first:
+                m = ing & (s == UNKNOWN)
+                if parent is None:
+                    u[m] = U_ZERO
+                else:
+                    u[m], ps = mem.read_cells(parent, (gy[m] >> 1) * pw + (gx[m] >> 1), pspan)
+                    assert (ps != OUT).all()
+            live = s != OUT
+            for _ in range(sweeps):
+                for par in (0, 1):
+                    lp = np.zeros((RX_H + 2, RX_W + 2), bool)
+                    lp[1:-1, 1:-1] = live                            # a neighbour outside the staged rectangle is not read
+                    up = np.zeros((RX_H + 2, RX_W + 2, 3), np.int64)
+                    up[1:-1, 1:-1] = u * live[..., None]
+                    k = lp[:-2, 1:-1].astype(np.int64) + lp[2:, 1:-1] + lp[1:-1, :-2] + lp[1:-1, 2:]
+                    total = up[:-2, 1:-1] + up[2:, 1:-1] + up[1:-1, :-2] + up[1:-1, 2:]
+                    m = (s == UNKNOWN) & (((gy + gx) & 1) == par) & (k > 0)
+                    u[m] = _mean_round_v(total, k[..., None])[m]
+            wr = ing & (ii >= halo) & (ii < halo + th) & (jj >= halo) & (jj < halo + tw)
+            mem.write_cells(dst, gy[wr] * w + gx[wr], u[wr], s[wr], dspan)
+
+
+def _tiled_apply(mem, frame, Hi, Wi, lift, lift_rect, sel, lock, box, offset, flip, d, e, u0, uspan):
+    ly0, lx0, lh, lw = lift_rect
+    lpitch = (3 * lw + 15) // 16 * 16
+    ry0, rx0, ry1, rx1 = d
+    ey0, ex0, ew = e[0], e[1], e[3] - e[1]
+    for ty0 in range(ry0, ry1, TILE_H):
+        for tx0 in range(rx0, rx1, TILE_W):
+            for ly in range(TILE_H):
+                for lx in range(0, TILE_W, 4):
+                    y, x = ty0 + ly, tx0 + lx
+                    if y >= ry1 or x >= rx1:
+                        continue
+                    npx = min(4, rx1 - x)
+                    v = M._moved4(mem, sel, Wi, box, offset, flip, y, x)
+                    s4 = [(v >> (8 * p)) & 1 if p < npx else 0 for p in range(4)]
+                    if not any(s4):
+                        continue
+                    if lock is not None:
+                        lrow = lock + y * Wi
+                        lk = mem.load4_within(lrow + x, lrow + x, lrow + x + npx)
+                        s4 = [s4[p] if not (lk >> (8 * p)) & 255 else 0 for p in range(4)]
+                        if not any(s4):
+                            continue
+                    sy = box[0] + box[2] - 1 - (y - offset[0]) if flip & 2 else y - offset[0]
+                    sx = box[1] + box[3] - 1 - (x - offset[1]) if flip & 1 else x - offset[1]
+                    assert ly0 <= sy < ly0 + lh
+                    prow = lift + (sy - ly0) * lpitch
+                    s = mem.load12_within(prow + 3 * ((sx - 3 if flip & 1 else sx) - lx0), prow, prow + 3 * lw)
+                    o = [0] * 12
+                    for p in range(4):
+                        if not s4[p]:
+                            continue
+                        u, state = mem.read_cells(u0, (y - ey0) * ew + (x + p - ex0), uspan)
+                        assert state == UNKNOWN
+                        for c in range(3):
+                            a = s[3 * (3 - p) + c] if flip & 1 else s[3 * p + c]
+                            o[3 * p + c] = min(max(((16 * a + int(u[c]) + 8) >> 4) - 256, 0), 255)
+                    frow, dst = frame + (y * Wi + rx0) * 3, frame + (y * Wi + x) * 3
+                    if all(s4) and dst % 4 == 0:                     # three aligned dwords
+                        slots = [(dst + 4 * k, 4) for k in range(3)]
+                    else:                                            # the targets' single bytes
+                        slots = [(dst + 3 * p + c, 1) for p in range(4) if s4[p] for c in range(3)]
+                    for a, n in slots:
+                        assert frow <= a and a + n <= frow + 3 * (rx1 - rx0), "a store outside the destination row"
+                        mem.mem[a:a + n] = o[a - dst:a - dst + n]
+                        mem.writers[a:a + n] += 1
+
+
+def tiled_blend(mem, frame, Hi, Wi, lift, lift_rect, sel, lock, box, offset, flip, ws, ws_bytes):
+    """sketchedit_move_blend_u8's launches on `mem`, addresses for pointers -> the number of launches"""
+    assert ws % 16 == 0 and ws_bytes >= workspace_bytes(box[2] - box[0], box[3] - box[1])
+    d, e = rects(box, offset, (Hi, Wi))
+    if d is None:
+        return 0
+    eh, ew = e[2] - e[0], e[3] - e[1]
+    lv, end = _levels(ws, eh, ew)
+    assert end <= ws + ws_bytes
+    span = lambda l, k: (lv[l][2 + k], lv[l][2 + k] + 8 * lv[l][0] * lv[l][1])      # noqa: E731
+    n = 1
+    _tiled_init(mem, frame, Hi, Wi, lift, lift_rect, sel, lock, box, offset, flip, e, lv[0][2], span(0, 0))
+    T = len(lv) - 1
+    for l in range(1, T + 1):
+        _tiled_pull(mem, lv[l - 1][2], lv[l - 1][0], lv[l - 1][1], span(l - 1, 0), lv[l][2], lv[l][0], lv[l][1], span(l, 0))
+        n += 1
+    parent, pspan = None, None
+    for l in range(T, -1, -1):
+        h, w = lv[l][:2]
+        pw = lv[l + 1][1] if l < T else 0
+        whole = h <= RX_H and w <= RX_W
+        count = 1 if whole else sweeps_of(l) // 4
+        for k in range(count):
+            _tiled_relax(mem, lv[l][2 + (k & 1)], span(l, k & 1), lv[l][2 + ((k + 1) & 1)], span(l, (k + 1) & 1), parent, pspan, h, w, pw,
+                         0 if whole else RX_HALO, sweeps_of(l) if whole else 4, k == 0)
+            n += 1
+        parent, pspan = lv[l][2 + (count & 1)], span(l, count & 1)
+    _tiled_apply(mem, frame, Hi, Wi, lift, lift_rect, sel, lock, box, offset, flip, d, e, parent, pspan)
+    return n + 1

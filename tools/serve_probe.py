@@ -218,6 +218,17 @@ plus se_profile_report's per-kernel times of one (c), (d), (e) and (f) request (
 among them).  --filter on the parent commit's build in the same job is the comparison leg:
     python tools/serve_probe.py --adjust [--reps N] [--out FILE]
 
+--blend: seamless move and clone: --move's frame, disc (253 x 253), window and offset; the frame is put back (a device
+copy, outside the clock) in front of every call, each call ends in the patches' download.  Legs:
+  (a) edit:             EditSession.edit(window=..., max_grow=0), the unchanged control,
+  (b) clone:            EditSession.clone_selection(selection, (150, 300)), the hard drop -- the two legs --blend-parent runs on the
+                        parent commit's build in the same job, before and after, for the comparison and its own spread,
+  (c) clone_seamless:   clone_selection(..., blend="seamless"): the lift of the grown box, the fixed schedule, the shift,
+  (d) move_seamless:    move_selection(..., window=..., blend="seamless"),
+and, once under the profiler, the launches and device time of the blend kernels of (c).  The expectation to confirm or refute:
+(c) costs (b) plus the device time of its small launches.
+    python tools/serve_probe.py --blend [--reps N] [--out FILE]
+
 --modify: expand, contract, border and smooth a selection: --move's frame and its disc of 49 861 pixels, selected by
 colour; nothing changes the frame, every timed call ends in the download of the tile records:
   (a) combine:       EditSession.combine(selection, lasso, "subtract"), the unchanged control: one launch and the tile records,
@@ -1565,6 +1576,67 @@ def adjust_leg(model, reps, side=512, tolerance=16):
     return out
 
 
+def blend_leg(model, reps, parent=False, side=512, tolerance=16, offset=(150, 300)):
+    """(a) .. (d) of the module docstring; parent=True: the legs (a) and (b) only, with the calls a build without the blend has"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    frame[..., 0] = frame[..., 0] % 90                               # no noise pixel is similar to the disc's colour
+    win = (283, 705, side, side)
+    seed = (win[0] + side // 2, win[1] + side // 2)
+    yy, xx = np.mgrid[0:h, 0:w]
+    disc = (yy - seed[0]) ** 2 + (xx - seed[1]) ** 2 <= 126 ** 2
+    frame[disc] = 128
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    dev0 = torch.from_numpy(frame).cuda()
+
+    def timed(fn, session):
+        def rounds():
+            ts = []
+            for k in range(2 + reps):              # two warm-ups: plans, workspace, code objects
+                session._frame.copy_(dev0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()                               # ends in a device-to-host copy: the request is complete
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts = sorted(ts[2:])
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    s1, s2 = serve.EditSession(model, frame), serve.EditSession(model, frame)
+    sel = s2.select_similar(seed, tolerance=tolerance)
+    legs = dict(edit=timed(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True), s1),
+                clone=timed(lambda: s2.clone_selection(sel, offset), s2))
+    if not parent:
+        legs.update(clone_seamless=timed(lambda: s2.clone_selection(sel, offset, blend="seamless"), s2),
+                    move_seamless=timed(lambda: s2.move_selection(sel, offset, window=win, low_latency=True, blend="seamless"), s2))
+    out = dict(tool="serve_probe --blend" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h], window=list(win),
+               seed=list(seed), tolerance=tolerance, offset=list(offset), selected=sel.count, box=list(sel.box))
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    if not parent:
+        eng = model.engine()
+        s2._frame.copy_(dev0)
+        eng.profile(True)
+        s2.clone_selection(sel, offset, blend="seamless")
+        rep = eng.profile_report()
+        eng.profile(False)
+        ks = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+        blend = {k: v for k, v in ks.items() if k.startswith("blend_")}
+        out.update(clone_seamless_profiled=ks, blend_launches=sum(v["launches"] for v in blend.values()),
+                   blend_device_ms=round(sum(v["ms"] for v in blend.values()), 4),
+                   clone_seamless_minus_clone_ms=round(out["ms"]["clone_seamless"]["median"] - out["ms"]["clone"]["median"], 3))
+    return out
+
+
 def modify_leg(model, reps, parent=False, side=512, tolerance=16):
     """(a) .. (e) of the module docstring; parent=True: the leg (a) only, with the calls a build without modifications has"""
     import numpy as np
@@ -1686,6 +1758,8 @@ def main():
     ap.add_argument("--adjust", action="store_true", help="adjust a selection's tone and colour (see the module docstring)")
     ap.add_argument("--modify", action="store_true", help="expand, contract, border and smooth a selection (see the module docstring)")
     ap.add_argument("--modify-parent", action="store_true", help="the combine leg of --modify only")
+    ap.add_argument("--blend", action="store_true", help="seamless move and clone (see the module docstring)")
+    ap.add_argument("--blend-parent", action="store_true", help="the edit and the plain clone legs of --blend only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -1698,8 +1772,11 @@ def main():
             or args.regions or args.regions_parent or args.strokes or args.strokes_parent or args.png or args.png_parent
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
             or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent
-            or args.move or args.move_parent or args.warp or args.filter or args.adjust or args.modify or args.modify_parent):
-        if args.modify or args.modify_parent:
+            or args.move or args.move_parent or args.warp or args.filter or args.adjust or args.modify or args.modify_parent
+            or args.blend or args.blend_parent):
+        if args.blend or args.blend_parent:
+            res = blend_leg(model, args.reps, parent=args.blend_parent)
+        elif args.modify or args.modify_parent:
             res = modify_leg(model, args.reps, parent=args.modify_parent)
         elif args.adjust:
             res = adjust_leg(model, args.reps)
