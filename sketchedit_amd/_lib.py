@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKETCHEDIT_HIP_LIB") or os.path.join(_HERE, "lib", "libsketchedit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["se_gconv.hip", "se_rconv16.hip", "se_rconv96.hip", "se_rtile.hip", "se_rtilew.hip", "se_wino.hip", "se_wino24.hip", "se_wino48.hip", "se_wino_up.hip", "se_wino_up48.hip", "se_s2poly.hip", "se_attention.hip", "se_att_stream.hip", "se_misc.hip", "se_resize.hip",
-           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_modify.hip", "se_outline.hip", "se_move.hip", "se_blend.hip", "se_warp.hip", "se_filter.hip", "se_adjust.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
+           "se_window.hip", "se_feather.hip", "se_fill.hip", "se_select.hip", "se_lasso.hip", "se_modify.hip", "se_outline.hip", "se_move.hip", "se_blend.hip", "se_canvas.hip", "se_warp.hip", "se_filter.hip", "se_adjust.hip", "se_png.hip", "se_jpg.hip", "se_pack.hip",
            "se_plan.hip", "se_api_window.hip", "se_api_select.hip", "se_api_move.hip", "se_api_codec.hip", "se_api_debug.hip", "se_api.hip"]
 
 SE_NET_G, SE_NET_M = 0, 1
@@ -77,6 +77,12 @@ MOVE_FLIP_X, MOVE_FLIP_Y = 1, 2                   # SE_MOVE_FLIP_*
 # and this list is not a *_SYMBOLS list: the se_ names, those lists and their number are what the earlier entries' tests pin
 BLEND_ENTRIES = ["sketchedit_move_blend_u8_workspace_bytes", "sketchedit_move_blend_u8"]
 BLEND_MAX_SIDE = 2048                             # SE_BLEND_MAX_SIDE
+# the entry declared in include/sketchedit_canvas.h (the canvas of a session): like the list above, not a *_SYMBOLS list,
+# and its name starts with neither of the prefixes that the earlier entries' tests pin
+CANVAS_ENTRIES = ["skedit_canvas_u8"]
+CANVAS_MIRROR_X, CANVAS_MIRROR_Y, CANVAS_TRANSPOSE = 1, 2, 4      # SKEDIT_CANVAS_MIRROR_X, _MIRROR_Y, _TRANSPOSE
+CANVAS_EDGE, CANVAS_REFLECT, CANVAS_CONSTANT = 0, 1, 2            # SKEDIT_CANVAS_EDGE, _REFLECT, _CONSTANT
+CANVAS_MAX_SIDE, CANVAS_MAX_OFFSET = 32768, 1 << 20               # SKEDIT_CANVAS_MAX_SIDE, SKEDIT_CANVAS_MAX_OFFSET
 # every symbol declared in include/sketchedit_warp.h (scale and rotate a selection)
 WARP_SYMBOLS = ["se_warp_drop_u8", "se_plane_warp_u8"]
 WARP_MAX_COEF, WARP_MAX_TRANSLATION = 1 << 20, 1 << 40      # SE_WARP_MAX_COEF, SE_WARP_MAX_TRANSLATION
@@ -324,6 +330,8 @@ def load_library():
         lib.sketchedit_move_blend_u8_workspace_bytes.restype = sz
         lib.sketchedit_move_blend_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 7 + [vp, sz]
         lib.sketchedit_move_blend_u8.restype = ci
+        lib.skedit_canvas_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, ctypes.c_uint]
+        lib.skedit_canvas_u8.restype = ci
         lib.se_plane_shift_u8.argtypes = [vp, vp, vp, ci, ci] + [ci] * 7 + [vp]
         lib.se_plane_shift_u8.restype = ci
         lib.se_warp_drop_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8 + [vp]
@@ -1335,6 +1343,40 @@ class Engine:
         if self.lib.se_plane_shift_u8(self.h, self._stream(), _ptr(sel), Hi, Wi, by0, bx0, by1, bx1, int(offset[0]), int(offset[1]), int(flip),
                                       _ptr(out)):
             self._err("se_plane_shift_u8")
+        return out
+
+    # ---- the canvas of a session (include/sketchedit_canvas.h) ---------------------------------------------------------
+    def canvas_u8(self, src, out_hw, origin=(0, 0), orient=0, pad=CANVAS_EDGE, pad_rgb=0, src_hw=None, out=None, device=None):
+        """skedit_canvas_u8: `src` (Hi,Wi,3) or (Hi,Wi) uint8 on the device -> `out` (a NEW tensor (Hn,Wn,3) / (Hn,Wn), or one of
+        that shape that shares no byte with src; any alignment; every byte is written): the rectangle of `out_hw` = (Hn, Wn) at
+        `origin` = (oy, ox) of src oriented by `orient` (0 .. 7: CANVAS_MIRROR_X | CANVAS_MIRROR_Y | CANVAS_TRANSPOSE, the
+        transpose last), what lies outside filled by `pad` (CANVAS_EDGE, CANVAS_REFLECT, or CANVAS_CONSTANT with the colour
+        `pad_rgb`, byte c of a pixel = (pad_rgb >> 8 c) & 255).  src None: a plane of zeros of `src_hw` that is never read --
+        with CANVAS_CONSTANT 255 the plane of the NEW area.  One launch."""
+        import torch
+        Hn, Wn = (int(v) for v in out_hw)
+        if src is None:
+            if src_hw is None:
+                raise SketchEditHipError("canvas_u8: without src, src_hw = (Hi, Wi) says what the rectangle is taken of")
+            Hi, Wi, C = int(src_hw[0]), int(src_hw[1]), 1
+            dev = out.device if out is not None else (device if device is not None else torch.device("cuda", self.device))
+        else:
+            _check_dev_u8(src)
+            if not (src.dim() == 2 or (src.dim() == 3 and src.shape[2] == 3)):
+                raise SketchEditHipError("canvas_u8: src is an (Hi,Wi,3) frame or an (Hi,Wi) plane")
+            Hi, Wi, C = int(src.shape[0]), int(src.shape[1]), 1 if src.dim() == 2 else 3
+            dev = src.device
+        shape = (Hn, Wn) if C == 1 else (Hn, Wn, 3)
+        if out is None:
+            if not (1 <= Hn <= CANVAS_MAX_SIDE and 1 <= Wn <= CANVAS_MAX_SIDE and C * Hn * Wn < 1 << 31):
+                raise SketchEditHipError("canvas_u8: bad out_hw=%r (sides 1 .. %d, C Hn Wn < 2^31)" % ((Hn, Wn), CANVAS_MAX_SIDE))
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        _check_dev_u8(out)
+        if tuple(out.shape) != shape:
+            raise SketchEditHipError("canvas_u8: out is a uint8 tensor of shape %r" % (shape,))
+        if self.lib.skedit_canvas_u8(self.h, self._stream(), _ptr(src), Hi, Wi, C, _ptr(out), Hn, Wn, int(origin[0]), int(origin[1]),
+                                     int(orient), int(pad), int(pad_rgb) & 0xffffffff):
+            self._err("skedit_canvas_u8")
         return out
 
     # ---- scale and rotate a selection (DESIGN.md 6s, include/sketchedit_warp.h) ------------------------------------------------------

@@ -3,9 +3,11 @@
 // of the plane (kernels: se_warp.hip); and behind include/sketchedit_filter.h the blur and the mosaic of a
 // selection (kernels: se_filter.hip); and behind include/sketchedit_adjust.h the tone and colour of a selection,
 // the histogram and the table made of it (kernels: se_adjust.hip); and behind include/sketchedit_blend.h the
-// seamless drop (kernels: se_blend.hip).
+// seamless drop (kernels: se_blend.hip); and behind include/sketchedit_canvas.h the canvas of a session
+// (kernels: se_canvas.hip).
 #include "../../include/sketchedit_adjust.h"
 #include "../../include/sketchedit_blend.h"
+#include "../../include/sketchedit_canvas.h"
 #include "../../include/sketchedit_filter.h"
 #include "../../include/sketchedit_move.h"
 #include "../../include/sketchedit_warp.h"
@@ -165,6 +167,30 @@ int se_plane_shift_u8(se_ctx* c, void* stream, const unsigned char* sel_u8, int 
   if (overlaps(plane_out, pn, sel_u8, pn)) return fail(c, "plane_out overlaps sel_u8");
   if (device_enter(c)) return 1;
   HIPCHK(c, launch_plane_shift(sel_u8, Hi, Wi, by0, bx0, by1, bx1, dy, dx, flip, plane_out, (hipStream_t)stream));
+  return 0;
+}
+
+// The canvas: out of place, every check on the host, ONE launch that writes every byte of `out`.  What the launch takes: canvas_map
+// walks C Hn Wn / 4 < 2^29 dwords, 256 to a workgroup; canvas_turn's grid is at most 1024 x 512 tiles.
+int skedit_canvas_u8(se_ctx* c, void* stream, const unsigned char* in, int Hi, int Wi, int C, unsigned char* out, int Hn, int Wn, int oy, int ox,
+                     int orient, int pad_mode, unsigned pad_rgb) {
+  if (!c) return 1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!out) return fail(c, "null pointer argument: out");
+  if (C != 1 && C != 3) return fail(c, "bad C=%d (1: a plane, 3: a frame)", C);
+  if (!in && C != 1) return fail(c, "null pointer argument: in (only a plane, C = 1, may be NULL)");
+  if (orient < 0 || orient > 7) return fail(c, "bad orient=%d (0 .. 7)", orient);
+  if (pad_mode != SKEDIT_CANVAS_EDGE && pad_mode != SKEDIT_CANVAS_REFLECT && pad_mode != SKEDIT_CANVAS_CONSTANT)
+    return fail(c, "bad pad_mode=%d (SKEDIT_CANVAS_EDGE, _REFLECT or _CONSTANT)", pad_mode);
+  if (Hi < 1 || Wi < 1 || Hi > SKEDIT_CANVAS_MAX_SIDE || Wi > SKEDIT_CANVAS_MAX_SIDE || (long long)C * Hi * Wi >= (1ll << 31))
+    return fail(c, "bad Hi=%d Wi=%d (1 .. %d, C Hi Wi < 2^31)", Hi, Wi, SKEDIT_CANVAS_MAX_SIDE);
+  if (Hn < 1 || Wn < 1 || Hn > SKEDIT_CANVAS_MAX_SIDE || Wn > SKEDIT_CANVAS_MAX_SIDE || (long long)C * Hn * Wn >= (1ll << 31))
+    return fail(c, "bad Hn=%d Wn=%d (1 .. %d, C Hn Wn < 2^31)", Hn, Wn, SKEDIT_CANVAS_MAX_SIDE);
+  if (oy < -SKEDIT_CANVAS_MAX_OFFSET || oy > SKEDIT_CANVAS_MAX_OFFSET) return fail(c, "bad oy=%d (|oy| <= %d)", oy, SKEDIT_CANVAS_MAX_OFFSET);
+  if (ox < -SKEDIT_CANVAS_MAX_OFFSET || ox > SKEDIT_CANVAS_MAX_OFFSET) return fail(c, "bad ox=%d (|ox| <= %d)", ox, SKEDIT_CANVAS_MAX_OFFSET);
+  if (in && overlaps(in, (size_t)C * Hi * Wi, out, (size_t)C * Hn * Wn)) return fail(c, "out overlaps in");
+  if (device_enter(c)) return 1;
+  HIPCHK(c, launch_canvas(in, Hi, Wi, C, out, Hn, Wn, oy, ox, orient, pad_mode, pad_rgb, (hipStream_t)stream));
   return 0;
 }
 

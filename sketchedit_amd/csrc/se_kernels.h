@@ -21,7 +21,7 @@ enum ProfLabel { PL_GCONV_N192 = 0, PL_GCONV_N96, PL_GCONV_N48, PL_GCONV_N24, PL
                  PL_WINDOW_RESAMPLE_H, PL_WINDOW_PASTE_V, PL_WINDOW_SAVE, PL_WINDOW_SWAP, PL_WINDOW_LOCK_GATHER, PL_WINDOW_PASTE_LOCKED,
                  PL_WINDOW_PASTE_V_LOCKED, PL_SKETCH_TILES, PL_SKETCH_STROKES, PL_PNG_ROWS, PL_PNG_STRIPES,
                  PL_PNG_FINISH, PL_JPG_BLOCKS, PL_JPG_ROWS, PL_JPG_FINISH, PL_JPG2_BLOCKS, PL_JPG2_HIST, PL_JPG2_TABLES,
-                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_BLEND_INIT, PL_BLEND_PULL, PL_BLEND_RELAX, PL_BLEND_APPLY,
+                 PL_WINDOW_PASTE_FEATHER, PL_FILL_MASKS, PL_FILL_KEEP, PL_BLEND_INIT, PL_BLEND_PULL, PL_BLEND_RELAX, PL_BLEND_APPLY, PL_CANVAS_MAP, PL_CANVAS_TURN,
                  PL_SELECT_SIMILAR, PL_SELECT_FLOOD, PL_SELECT_GROW, PL_MODIFY_DISC, PL_MODIFY_VOTE,
                  PL_LASSO_FILL, PL_PLANE_COMBINE, PL_ADJUST, PL_HIST_TILES, PL_HIST_SUM, PL_ADJUST_LUT, PL_OUTLINE_COUNT, PL_OUTLINE_SCAN, PL_OUTLINE_EMIT, PL_FILTER_BLUR, PL_FILTER_MOSAIC, PL_MOVE_DROP,
                  PL_PLANE_SHIFT, PL_WARP_DROP, PL_PLANE_WARP, PL_COUNT };
@@ -492,6 +492,11 @@ size_t blend_workspace_bytes(int eh, int ew);
 hipError_t launch_move_blend(unsigned char* frame, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh, int lw, int lpitch,
                              const unsigned char* sel, const unsigned char* lock, int by0, int bx0, int by1, int bx1, int dy, int dx, int flip,
                              void* ws, hipStream_t st);
+// the canvas of a session (include/sketchedit_canvas.h; se_canvas.hip): out (Hn,Wn,C) <- the rectangle at (oy, ox) of
+// in (Hi,Wi,C; NULL: zeros) under `orient`, folded by `pad` (SKEDIT_CANVAS_*; rgb: the constant's C bytes).  Any sizes >= 1 and any
+// alignment.  ONE launch: canvas_map without the transpose bit, canvas_turn (64 x 32 tiles through the LDS) with it.
+hipError_t launch_canvas(const unsigned char* in, int Hi, int Wi, int C, unsigned char* out, int Hn, int Wn, int oy, int ox, int orient,
+                         int pad, unsigned rgb, hipStream_t st);
 // blur, sharpen or pixelate a selection (include/sketchedit_filter.h; se_filter.hip).  Any Hi, Wi >= 16 and any
 // alignment of the frame and the planes; the frame is only written, every input pixel comes from the lift.  taps: radius + 1 ints
 // on the host.  filter_blur: the grid is the box's 64 x 16 tiles, the LDS that of the radius' class; filter_mosaic: a wave per cell.

@@ -109,7 +109,7 @@ const char* prof_label_name(int l) {
                                     "window_paste", "window_resample_h", "window_paste_v", "window_save", "window_swap", "window_lock_gather",
                                     "window_paste_locked", "window_paste_v_locked", "sketch_tiles", "sketch_strokes", "png_rows", "png_stripes",
                                     "png_finish", "jpg_blocks", "jpg_rows", "jpg_finish", "jpg2_blocks420", "jpg2_hist", "jpg2_tables", "window_paste_feather",
-                                    "fill_masks", "fill_keep", "blend_init", "blend_pull", "blend_relax", "blend_apply", "select_similar", "select_flood", "select_grow", "modify_disc", "modify_vote", "lasso_fill", "plane_combine",
+                                    "fill_masks", "fill_keep", "blend_init", "blend_pull", "blend_relax", "blend_apply", "canvas_map", "canvas_turn", "select_similar", "select_flood", "select_grow", "modify_disc", "modify_vote", "lasso_fill", "plane_combine",
                                     "adjust", "hist_tiles", "hist_sum", "adjust_lut",
                                     "outline_count", "outline_scan", "outline_emit", "filter_blur", "filter_mosaic",
                                     "move_drop", "plane_shift", "warp_drop", "plane_warp"};

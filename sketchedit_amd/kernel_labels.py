@@ -65,6 +65,9 @@ KERNEL_LABELS = {
     "(anonymous namespace)::blend_relax_kernel": "blend_relax", "(anonymous namespace)::blend_apply_kernel": "blend_apply",
     "blend_init_kernel": "blend_init", "blend_pull_kernel": "blend_pull", "blend_relax_kernel": "blend_relax",
     "blend_apply_kernel": "blend_apply",
+    # the canvas of a session (se_canvas.hip): the walk of the output's bytes, and the quarter turn through the LDS
+    "(anonymous namespace)::canvas_map_kernel": "canvas_map", "(anonymous namespace)::canvas_turn_kernel": "canvas_turn",
+    "canvas_map_kernel": "canvas_map", "canvas_turn_kernel": "canvas_turn",
     # scale and rotate a selection (se_warp.hip): the resampling drop, and the warp of the plane
     "(anonymous namespace)::warp_drop_kernel": "warp_drop", "(anonymous namespace)::plane_warp_kernel": "plane_warp",
     "warp_drop_kernel": "warp_drop", "plane_warp_kernel": "plane_warp",

@@ -256,6 +256,12 @@ class EditLine2Model(torch.nn.Module):
         """A selection plane moved as move_drop_u8 moves its pixels: a new 0 / 255 plane (Engine.plane_shift_u8)."""
         return self.engine().plane_shift_u8(sel, box, offset, flip=flip, out=out)
 
+    def canvas_u8(self, src, out_hw, origin=(0, 0), orient=0, pad=0, pad_rgb=0, src_hw=None, out=None):
+        """The canvas of a session (serve.EditSession.canvas is the caller-facing form): a NEW frame or plane, the
+        rectangle `out_hw` at `origin` of `src` oriented by `orient` and padded by `pad`; src None: the plane of the new area's
+        form, of a `src_hw` plane of zeros (Engine.canvas_u8)."""
+        return self.engine().canvas_u8(src, out_hw, origin=origin, orient=orient, pad=pad, pad_rgb=pad_rgb, src_hw=src_hw, out=out)
+
     def warp_drop_u8(self, frame, lift, lift_rect, sel, lock, box, rect, m):
         """The drop of a scaled or turned selection (serve.EditSession.transform_selection is the caller-facing
         form): the selected pixels of `box`, as the journal slot `lift` of `lift_rect` holds them, gathered through the inverse

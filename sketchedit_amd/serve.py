@@ -701,6 +701,87 @@ def warp_rect(box, m, frame_hw):
     return None if ya is None or xa is None else (ya[0], xa[0], ya[1], xa[1])
 
 
+# ---- the canvas of a session (include/sketchedit_canvas.h) -----------------------------------------------------------
+CANVAS_ORIENTS = {None: 0, "h": 1, "v": 2, "180": 3, "transpose": 4, "ccw": 5, "cw": 6, "transverse": 7}      # SKEDIT_CANVAS_MIRROR_X | _MIRROR_Y | _TRANSPOSE
+CANVAS_PADS = {"edge": 0, "reflect": 1}          # SKEDIT_CANVAS_EDGE, SKEDIT_CANVAS_REFLECT
+CANVAS_CONSTANT = 2                              # SKEDIT_CANVAS_CONSTANT
+CANVAS_MAX_SIDE = 32768                          # SKEDIT_CANVAS_MAX_SIDE
+CANVAS_MAX_OFFSET = 1 << 20                      # SKEDIT_CANVAS_MAX_OFFSET
+CANVAS_FILLS = (None, "network")                 # extend_canvas' `fill`
+
+
+def _canvas_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def canvas_orient(name):
+    """An orientation's name -> its value 0 .. 7 (bit 0 mirrors x, bit 1 mirrors y, bit 2 transposes after the mirrors): None, "h"
+    (flip horizontal), "v" (flip vertical), "180", "transpose", "ccw" and "cw" (quarter turns), "transverse".  ValueError for
+    anything else."""
+    if not (name is None or isinstance(name, str)) or name not in CANVAS_ORIENTS:
+        raise ValueError("orient is one of %s (got %r)" % (", ".join(repr(k) for k in CANVAS_ORIENTS), name))
+    return CANVAS_ORIENTS[name]
+
+
+def canvas_pad(pad):
+    """`pad` -> (mode, colour): "edge", "reflect", or an (r, g, b) triple of ints 0 .. 255 -- the constant's colour as the library
+    takes it, r in the low byte.  ValueError for anything else."""
+    if isinstance(pad, str) and pad in CANVAS_PADS:
+        return CANVAS_PADS[pad], 0
+    try:
+        r, g, b = pad
+    except (TypeError, ValueError):
+        raise ValueError("pad is 'edge', 'reflect' or an (r, g, b) triple (got %r)" % (pad,))
+    if not all(_canvas_int(v) and 0 <= v <= 255 for v in (r, g, b)):
+        raise ValueError("pad is 'edge', 'reflect' or an (r, g, b) triple of ints 0 .. 255 (got %r)" % (pad,))
+    return CANVAS_CONSTANT, int(r) | int(g) << 8 | int(b) << 16
+
+
+def canvas_size(frame_hw, orient, rect):
+    """The geometry of a canvas step, pure host arithmetic: a frame of `frame_hw` oriented by `orient` (a name canvas_orient
+    takes) and cut or extended to `rect` = (y0, x0, h, w) in ORIENTED coordinates -- either origin may be negative and the
+    rectangle may reach past the oriented frame; None: the whole oriented frame.  -> ((Hn, Wn), (oy, ox)): the new frame's
+    size and the rectangle's origin.  ValueError for a rect that is not four ints, a side outside 1 .. 32768, 3 Hn Wn >= 2^31,
+    an origin above 2^20 in magnitude, and a new frame below a session's minimum (H // 8 * 8 >= 16, likewise W)."""
+    o = canvas_orient(orient)
+    Ho, Wo = (frame_hw[1], frame_hw[0]) if o & 4 else (frame_hw[0], frame_hw[1])
+    if rect is None:
+        rect = (0, 0, Ho, Wo)
+    try:
+        y0, x0, h, w = rect
+    except (TypeError, ValueError):
+        raise ValueError("rect is (y0, x0, h, w), four ints in oriented coordinates (got %r)" % (rect,))
+    if not all(_canvas_int(v) for v in (y0, x0, h, w)):
+        raise ValueError("rect is (y0, x0, h, w), four ints in oriented coordinates (got %r)" % (rect,))
+    y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+    if not (1 <= h <= CANVAS_MAX_SIDE and 1 <= w <= CANVAS_MAX_SIDE) or 3 * h * w >= 1 << 31:
+        raise ValueError("rect %r: sides are 1 .. %d and 3 h w < 2^31" % ((y0, x0, h, w), CANVAS_MAX_SIDE))
+    if abs(y0) > CANVAS_MAX_OFFSET or abs(x0) > CANVAS_MAX_OFFSET:
+        raise ValueError("rect %r: an origin is at most %d in magnitude" % ((y0, x0, h, w), CANVAS_MAX_OFFSET))
+    if h // 8 * 8 < 16 or w // 8 * 8 < 16:
+        raise ValueError("rect %r: the new frame would be too small for a session: %dx%d" % ((y0, x0, h, w), w, h))
+    return (h, w), (y0, x0)
+
+
+def canvas_new_box(oriented_hw, new_hw, origin):
+    """The tight box (y0, x0, y1, x1), half open, in the NEW frame's coordinates, of the area a canvas step adds -- the pixels of
+    the rectangle that lie outside the oriented frame -- in closed form; None when the rectangle adds none (a crop)."""
+    (Ho, Wo), (Hn, Wn), (oy, ox) = oriented_hw, new_hw, origin
+    iy0, iy1, ix0, ix1 = max(-oy, 0), min(Ho - oy, Hn), max(-ox, 0), min(Wo - ox, Wn)      # the old pixels' rectangle
+    if iy0 >= iy1 or ix0 >= ix1:
+        return (0, 0, Hn, Wn)
+    rows_full, cols_full = iy0 == 0 and iy1 == Hn, ix0 == 0 and ix1 == Wn
+    if rows_full and cols_full:
+        return None
+
+    def axis(lo, hi, n, other_full):
+        if not other_full or (lo > 0 and hi < n):
+            return 0, n
+        return (0, lo) if lo > 0 else (hi, n)
+    (y0, y1), (x0, x1) = axis(iy0, iy1, Hn, cols_full), axis(ix0, ix1, Wn, rows_full)
+    return (y0, x0, y1, x1)
+
+
 def png_from_zlib(stream, h, w):
     """The PNG file around a zlib stream of filtered 8-bit RGB rows: signature, IHDR, ONE IDAT holding
     `stream` as it is, IEND -- the chunk framing and its CRCs are the host's part of a patch that was encoded on the device."""
@@ -854,6 +935,11 @@ class _Regions(tuple):
 class _Sequence(tuple):
     """the rectangles of a move's journal entry, in the order its steps wrote them: they may overlap, so undo
     exchanges them in reverse order and redo in this one (its slots are a list in the same order)"""
+
+
+class _Canvas(tuple):
+    """the (H, W) of the state a canvas step's journal entry HOLDS: its slot is [frame, frame_hw, lock plane] whole --
+    the other state of the session -- and undo / redo exchange the session's three fields with it: no kernel, no download"""
 
 
 def _run_windows(be, frames, origins, crops, window_hw, work, locks, commit, low_latency):
@@ -1105,6 +1191,17 @@ class _ModelBackend:
         b, count = tiles_box(self.tiles(out, 32))
         return out, b, count
 
+    def canvas(self, src, src_hw, out_hw, origin, orient, pad, rgb, tiles=False):
+        """a NEW frame or plane, ONE launch: the rectangle `out_hw` at `origin` of `src` -- a frame, a plane, or None:
+        a plane of zeros of `src_hw` that is never read -- oriented by `orient` (0 .. 7) and padded by `pad` (SKEDIT_CANVAS_*) with
+        the colour `rgb`.  tiles=True (a carried selection): -> (plane, box, count), the tile records of the result being the one
+        download"""
+        out = self.model.canvas_u8(src, out_hw, origin=origin, orient=orient, pad=pad, pad_rgb=rgb, src_hw=src_hw)
+        if not tiles:
+            return out
+        b, count = tiles_box(self.tiles(out, 32))
+        return out, b, count
+
     def warp_drop(self, frame, lift, lift_rect, plane, lock, box, rect, m):
         """the drop of a transform, ONE launch in place on the frame: the pixels of `box` that `plane` selects, as
         the slot `lift` of `lift_rect` holds them, gathered through the inverse map `m` into `rect` where `lock` (or None) is 0"""
@@ -1231,7 +1328,10 @@ class EditSession:
     (info["undoable"] = False).  A new edit drops the redo entries.
     `set_lock` gives the frame a lock plane: pixels no later edit may change.  The lock enters the forward
     where the mask is made -- a locked pixel is known context for the generator, not a hole it fills -- and the paste; it
-    is the session's state like the frame, but not an edit: `undo` does not touch it."""
+    is the session's state like the frame, but not an edit: `undo` does not touch it -- but for a canvas step,
+    whose undo brings back the frame's old size and, with it, the lock plane of that size.
+    `canvas` and its wrappers crop_canvas, extend_canvas and orient_canvas replace the frame by a rectangle of
+    itself, oriented, cut or extended, made on the device; frame_hw then changes."""
 
     def __init__(self, model, image, backend=None, history=0, history_bytes=None):
         if hasattr(image, "convert"):
@@ -1258,7 +1358,9 @@ class EditSession:
     def set_lock(self, mask):
         """`mask`: (Hi,Wi), a uint8 or bool array or a PIL 'L' image, non-zero = locked; uploaded once (as 0 / 255) and kept
         on the device until the next set_lock.  None frees it.  Every later edit leaves the locked pixels' bytes as they
-        are.  Not an edit: nothing is journalled, and `undo` does not bring an earlier lock back.
+        are.  Not an edit: nothing is journalled, and `undo` does not bring an earlier lock back -- with ONE exception: a canvas
+        step changes the frame's geometry, so its undo and redo restore the lock plane that belonged to the
+        geometry they return to, whatever set_lock did in between.
         A Selection of this frame's size locks its pixels: the lock plane is a COPY of its plane made on the
         device -- nothing is uploaded, and what is combined from the selection later cannot reach the lock; an empty selection
         is None."""
@@ -1362,6 +1464,31 @@ class EditSession:
         info = dict(windows=list(wins), undo_depth=len(self._undo), redo_depth=len(self._redo))
         return [self.backend.crop(self._frame, *w) for w in wins], [(w[1], w[0]) for w in wins], info
 
+    @staticmethod
+    def _canvas_bytes(frame_hw, lock_plane):
+        """the bytes a canvas entry holds: the frame's 3 H W and a lock plane's H W"""
+        return (3 if lock_plane is None else 4) * frame_hw[0] * frame_hw[1]
+
+    def _record_canvas(self, held):
+        """`_record` for a canvas step: `held` = [frame, frame_hw, lock plane] of the state the step replaced.  An
+        entry that does not fit `history_bytes` is not made, and then every older entry goes too: they name the old geometry"""
+        self._redo.clear()
+        nbytes = self._canvas_bytes(held[1], held[2])
+        if self.history <= 0 or (self.history_bytes is not None and nbytes > self.history_bytes):
+            self._undo.clear()
+            return False
+        self._push((_Canvas(held[1]), list(held), nbytes))
+        return True
+
+    def _exchange_canvas(self, src, dst):
+        """the canvas entry `src` ends in <-> the session's frame, size and lock plane: a pointer exchange, no backend call; the
+        entry moves to `dst` holding the state that was current; -> what undo / redo return for it"""
+        _, slot, _ = src.pop()
+        held = [self._frame, self.frame_hw, self._lock_plane]
+        self._frame, self.frame_hw, self._lock_plane = slot
+        dst.append((_Canvas(held[1]), held, self._canvas_bytes(held[1], held[2])))
+        return None, (0, 0), dict(canvas=self.frame_hw, undo_depth=len(self._undo), redo_depth=len(self._redo))
+
     def _exchanged(self, src, dst):
         """the entry `src` ends in was exchanged with the frame: it moves to `dst`; -> what undo / redo return"""
         dst.append(src.pop())
@@ -1373,6 +1500,8 @@ class EditSession:
         with self._lock:
             if not src:
                 raise IndexError("nothing to " + what)
+            if isinstance(src[-1][0], _Canvas):
+                return self._exchange_canvas(src, dst)
             if isinstance(src[-1][0], _Sequence):
                 return self._exchange_sequence(src, dst, src is self._undo)
             if isinstance(src[-1][0], _Regions):
@@ -1387,7 +1516,9 @@ class EditSession:
         A region edit (edit_regions) is one step: all its windows are exchanged and the three are lists in ITS shape, with
         info = dict(windows, undo_depth, redo_depth).  A move (move_selection) is one step too and returns in that shape; its
         rectangles may overlap, so they are exchanged in the reverse of the order they were written, and by `redo` in that
-        order.  IndexError when there is nothing to undo."""
+        order.  A canvas step is one step: the frame, its size and the lock plane of that size come
+        back by a pointer exchange, nothing is downloaded, and it returns (None, (0, 0), dict(canvas=(H, W), undo_depth,
+        redo_depth)).  IndexError when there is nothing to undo."""
         return self._exchange(self._undo, self._redo, "undo")
 
     def redo(self):
@@ -2269,6 +2400,134 @@ class EditSession:
             rec = self.backend.hist(self._frame, selection.plane if selection is not None else None, box)
             return np.ascontiguousarray(self.backend.download(rec)).view(np.uint32).reshape(4, 256)
 
+    # ---- the canvas: crop, extend, rotate and flip ---------------------------------------------------------------------
+    def _canvas_args(self, orient, rect, pad, selections):
+        """what every canvas call refuses, all before the first backend call -> (o, (Hn, Wn), (oy, ox), pad mode, colour, selections)"""
+        o = canvas_orient(orient)
+        new_hw, origin = canvas_size(self.frame_hw, orient, rect)
+        mode, rgb = canvas_pad(pad)
+        try:
+            selections = list(selections)
+        except TypeError:
+            raise TypeError("selections is a sequence of Selections (got %s)" % type(selections).__name__)
+        for sel in selections:
+            self._check_selection(sel, "canvas")
+        if not callable(getattr(self.backend, "canvas", None)):
+            raise NotImplementedError("this session's backend (%s) has no `canvas` (DESIGN.md 6y)" % type(self.backend).__name__)
+        return o, new_hw, origin, mode, rgb, selections
+
+    def _canvas_steps(self, o, new_hw, origin, mode, rgb, selections):
+        """The launches of a canvas step, with the session's lock held: ONE for the new frame, one per carried plane -- the lock
+        plane, if any, and each selection, with the constant 0: new area is neither locked nor selected.  The session's fields
+        are not touched.  -> (frame, lock plane or None, the carried Selections)"""
+        be, hw = self.backend, self.frame_hw
+        frame = be.canvas(self._frame, hw, new_hw, origin, o, mode, rgb)
+        lock = None if self._lock_plane is None else be.canvas(self._lock_plane, hw, new_hw, origin, o, CANVAS_CONSTANT, 0)
+        made = []
+        for sel in selections:
+            plane, box, count = be.canvas(sel.plane, hw, new_hw, origin, o, CANVAS_CONSTANT, 0, tiles=True)
+            made.append(Selection(be, plane, box, count, new_hw))
+        return frame, lock, made
+
+    def _canvas(self, orient, rect, pad, selections, fill=None):
+        """canvas and extend_canvas(fill="network") once the wrappers' own arguments are checked.  `fill`: None, or the outpaint's
+        (window, margin, low_latency, max_side, feather, encode), checked"""
+        o, new_hw, origin, mode, rgb, selections = self._canvas_args(orient, rect, pad, selections)
+        be = self.backend
+        if fill is not None:
+            window, margin, low_latency, max_side, feather, encode = fill
+            Ho, Wo = (self.frame_hw[1], self.frame_hw[0]) if o & 4 else self.frame_hw
+            box = canvas_new_box((Ho, Wo), new_hw, origin)
+            if box is None:
+                raise ValueError("fill='network' fills the new area: the rectangle adds none")
+            if window is not None:
+                y0, x0, h, w = (int(v) for v in window)
+                scaled = max_side is not None
+                if h < 16 or w < 16 or (not scaled and (h % 8 or w % 8)) or y0 < 0 or x0 < 0 or y0 + h > new_hw[0] or x0 + w > new_hw[1]:
+                    raise ValueError("window %r: sides are multiples of 8, >= 16, and the window lies inside the new %dx%d frame"
+                                     % (window, new_hw[1], new_hw[0]))
+                win = (y0, x0, h, w)
+            else:
+                win = choose_window(box, new_hw, margin=margin)
+            if max_side is not None:
+                choose_working_size(win[2:], max_side)
+        with self._lock:
+            previous = self.frame_hw
+            held = [self._frame, self.frame_hw, self._lock_plane]
+            frame, lock, made = self._canvas_steps(o, new_hw, origin, mode, rgb, selections)
+            patch, pos, extra = None, (0, 0), {}
+            if fill is None:
+                self._frame, self.frame_hw, self._lock_plane = frame, new_hw, lock
+            else:
+                # the plane of the new area, made on the device: the input is NULL, the constant 255
+                new_area = be.canvas(None, (Ho, Wo), new_hw, origin, 0, CANVAS_CONSTANT, 255)
+                self._frame, self.frame_hw, self._lock_plane = frame, new_hw, lock
+                try:
+                    _, work, _ = self._fill_steps(new_area, None, win, low_latency, max_side, feather, False)
+                    patch = be.crop(self._frame, *win) if encode is None else _encoded(be, encode, [self._frame], [win])[0]
+                except Exception:                # out of place: the state the call found is still whole
+                    self._frame, self.frame_hw, self._lock_plane = held
+                    raise
+                pos = (win[1], win[0])
+                extra = _edit_info(dict(window=win, fill=True), False, work, None, feather)
+            undoable = self._record_canvas(held)
+        info = dict(canvas=new_hw, previous=previous, orient=orient, rect=origin + new_hw, undoable=undoable, selections=made,
+                    locked=lock is not None, **extra)
+        return patch, pos, info
+
+    def canvas(self, orient=None, rect=None, pad="edge", selections=()):
+        """Changes the frame's rectangle: "straighten it, crop it, add room".  The frame is ORIENTED -- `orient` None,
+        "cw", "ccw" (quarter turns), "180", "h", "v" (mirrors), "transpose" or "transverse" -- and then cut or extended to `rect` =
+        (y0, x0, h, w) in oriented coordinates, which may reach outside (None: the whole oriented frame); what lies outside is
+        filled by `pad`: "edge" (the nearest pixel), "reflect" (numpy's "reflect") or an (r, g, b) colour.  Made on the device,
+        out of place, under ONE hold of the session's lock: ONE launch makes the new frame, one each carries the lock plane, if
+        any, and every Selection in `selections` -- new area is neither locked nor selected -- and the session's frame, frame_hw
+        and lock plane are replaced.  Nothing frame-sized crosses the bus; a carried selection's tile records are its one
+        download.  Selections that are not handed in keep the old frame_hw and are refused afterwards where the size changed.
+        -> (None, (0, 0), info): info = dict(canvas=(H, W), previous=(H, W), orient, rect, undoable, selections=[the carried
+        Selections, NEW objects of the new frame_hw whose box and count are what the step left of them], locked).
+        With history on the step is ONE undo entry that holds the old frame and lock plane whole (3 H W + H W bytes): undo and
+        redo exchange them with the session's, without a kernel, and return (None, (0, 0), dict(canvas, undo_depth,
+        redo_depth)); older entries are valid again exactly when the stack reaches them.  A step whose entry does not fit
+        `history_bytes` clears the history (undoable = False): older entries name the old geometry.
+        ValueError / TypeError, all before the first backend call: an unknown orient or pad, a rect that is not four ints, a side
+        outside 1 .. 32768, an origin above 2^20, a new frame below a session's minimum, a selection of another frame size."""
+        return self._canvas(orient, rect, pad, selections)
+
+    def crop_canvas(self, rect, selections=()):
+        """canvas(rect=rect) with a `rect` = (y0, x0, h, w) that lies inside the frame: ValueError otherwise."""
+        canvas_size(self.frame_hw, None, rect)
+        y0, x0, h, w = (int(v) for v in rect)
+        if y0 < 0 or x0 < 0 or y0 + h > self.frame_hw[0] or x0 + w > self.frame_hw[1]:
+            raise ValueError("rect %r: a crop lies inside the %dx%d frame" % (tuple(rect), self.frame_hw[1], self.frame_hw[0]))
+        return self._canvas(None, (y0, x0, h, w), "edge", selections)
+
+    def extend_canvas(self, top=0, bottom=0, left=0, right=0, pad="edge", fill=None, selections=(), window=None, margin=0.5,
+                      low_latency=None, max_side=None, feather=None, encode=None):
+        """canvas(rect=(-top, -left, H + top + bottom, W + left + right), pad=pad): room on each side, four ints >= 0 of which one
+        at least is > 0.
+        fill="network" is the outpaint, "add room and let the network fill it": DEFINED as this call without `fill` followed by
+        fill(the plane of the new area, window=..., margin=..., low_latency=..., max_side=..., feather=..., encode=...) on the
+        extended frame, in ONE undo step and under one hold of the lock.  The plane of the new area is made on the device;
+        the window is choose_window of its box at `margin` unless given; the lock plane, carried first, is respected as every
+        fill respects it; `pad` is what the generator sees under the hole's rim and what stays where the window does not
+        reach.  -> (patch, (x0, y0), info): the window after the paste as `fill` returns it, info as canvas' plus window,
+        fill=True and work / feather where `fill` reports them.  No quality claim is made, as for `fill`."""
+        if not all(_canvas_int(v) and v >= 0 for v in (top, bottom, left, right)) or not (top or bottom or left or right):
+            raise ValueError("top, bottom, left, right are ints >= 0, one of them > 0 (got %r)" % ((top, bottom, left, right),))
+        if not (fill is None or isinstance(fill, str)) or fill not in CANVAS_FILLS:
+            raise ValueError("fill is None or 'network' (got %r)" % (fill,))
+        rect = (-int(top), -int(left), self.frame_hw[0] + int(top) + int(bottom), self.frame_hw[1] + int(left) + int(right))
+        if fill is None:
+            return self._canvas(None, rect, pad, selections)
+        return self._canvas(None, rect, pad, selections, (window, margin, low_latency, max_side, _check_feather(feather), _check_encode(encode)))
+
+    def orient_canvas(self, op, selections=()):
+        """canvas(orient=op): "cw", "ccw", "180", "h", "v", "transpose" or "transverse" (DESIGN.md 6y)."""
+        if op is None:
+            raise ValueError("op is one of %s" % ", ".join(repr(k) for k in CANVAS_ORIENTS if k is not None))
+        return self._canvas(op, None, "edge", selections)
+
     def frame(self):
         """The whole frame as an (H,W,3) uint8 array (a download of the frame)."""
         with self._lock:
@@ -2568,7 +2827,7 @@ class BatchingServer:
 
     def _run_history(self, group):
         """One group of undo / redo requests, each of another session (_candidates): one swap launch per window size; a region
-        edit's or a move's entry takes the session's own exchange.  A request with nothing to undo / redo fails alone
+        edit's, a move's or a canvas step's entry takes the session's own exchange.  A request with nothing to undo / redo fails alone
         (IndexError)."""
         reqs = [q[1] for q in group]
         be = reqs[0]["session"].backend
@@ -2584,6 +2843,8 @@ class BatchingServer:
                 if not stacks[i][0]:
                     group[i][3]["err"] = IndexError("nothing to " + r["op"])
                     outs[i] = False
+                elif isinstance(stacks[i][0][-1][0], _Canvas):       # a canvas step's entry: the session's own pointer exchange
+                    outs[i] = s._exchange_canvas(*stacks[i])
                 elif isinstance(stacks[i][0][-1][0], _Sequence):     # a move's entry: the session's own ordered exchange
                     outs[i] = s._exchange_sequence(*stacks[i], r["op"] == "undo")
                 elif isinstance(stacks[i][0][-1][0], _Regions):      # a region edit's entry: the session's own exchange

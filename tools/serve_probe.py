@@ -242,6 +242,18 @@ plus se_profile_report's per-kernel times of one request of every kind (modify_d
 sketch_tiles).  --modify-parent runs (a) alone, with the calls a build without modifications has: the comparison leg on the parent
 commit's build in the same job:
     python tools/serve_probe.py --modify [--reps N] [--out FILE]
+
+--canvas: crop, extend, rotate and flip the canvas: the 1921 x 1081 noise frame with a lock plane; the session's frame,
+size and lock plane are put back (three pointers, outside the clock) in front of every call, and every timed call ends in a
+device synchronisation -- a canvas call downloads nothing.  Legs:
+  (a) edit:            EditSession.edit(window=..., max_grow=0), the unchanged control -- the one leg --canvas-parent runs, with the
+                       calls a build without the canvas has: the comparison leg on the parent commit's build in the same job,
+  (b) orient_cw / crop / extend: orient_canvas("cw"), crop_canvas((100, 200, 800, 1400)), extend_canvas(64 on every side, "reflect"),
+  (c) host_orient_cw / host_crop / host_extend: frame() and lock() (the downloads), numpy, a new EditSession and set_lock (the
+      uploads) -- what a front end does without the canvas calls; the undo journal and every Selection are lost,
+plus, under the profiler, the device time of canvas_turn (a quarter turn) and canvas_map (a half turn) of the same frame, their
+ratio and the bytes per second each moves:
+    python tools/serve_probe.py --canvas [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -1637,6 +1649,80 @@ def blend_leg(model, reps, parent=False, side=512, tolerance=16, offset=(150, 30
     return out
 
 
+def canvas_leg(model, reps, parent=False, side=512):
+    """(a) .. (c) of the module docstring; parent=True: the leg (a) only, with the calls a build without the canvas has"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    lock = np.zeros((h, w), np.uint8)
+    lock[100:300, 200:900] = 255
+    win = (283, 705, side, side)
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    s1 = serve.EditSession(model, frame)
+    legs = dict(edit=lambda: wall_ms(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True), reps))
+    out = dict(tool="serve_probe --canvas" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h], window=list(win))
+    if not parent:
+        s2 = serve.EditSession(model, frame)
+        s2.set_lock(lock)
+        state = (s2._frame, s2.frame_hw, s2._lock_plane)
+
+        def timed(fn):
+            def rounds():
+                ts = []
+                for k in range(2 + reps):              # two warm-ups: code objects, the allocator's blocks
+                    s2._frame, s2.frame_hw, s2._lock_plane = state
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()           # the new frame and lock plane are made
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                ts = sorted(ts[2:])
+                return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+            return rounds
+
+        def host(fn):
+            def route():
+                f, lk = s2.frame(), s2.lock()
+                s = serve.EditSession(model, np.ascontiguousarray(fn(f)))
+                s.set_lock(np.ascontiguousarray(fn(lk)))
+            return route
+        legs.update(orient_cw=timed(lambda: s2.orient_canvas("cw")), crop=timed(lambda: s2.crop_canvas((100, 200, 800, 1400))),
+                    extend=timed(lambda: s2.extend_canvas(64, 64, 64, 64, pad="reflect")),
+                    host_orient_cw=timed(host(lambda a: np.rot90(a, -1))), host_crop=timed(host(lambda a: a[100:900, 200:1600])),
+                    host_extend=timed(host(lambda a: np.pad(a, ((64, 64), (64, 64)) + ((0, 0),) * (a.ndim - 2), mode="reflect"))))
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    if not parent:
+        eng = model.engine()
+        dev = {}
+        for name, op, label in (("turn_cw", "cw", "canvas_turn"), ("map_180", "180", "canvas_map")):
+            ts = []
+            for _ in range(5):
+                s2._frame, s2.frame_hw, s2._lock_plane = state[0], state[1], None
+                eng.profile(True)
+                s2.orient_canvas(op)
+                rep = eng.profile_report()
+                eng.profile(False)
+                ks = {k["kernel"]: k for k in rep["kernels"]}
+                assert list(ks) == [label] and ks[label]["launches"] == 1, ks
+                ts.append(ks[label]["total_ms"])
+            ts.sort()
+            dev[name] = dict(kernel=label, device_ms=round(ts[2], 4), min=round(ts[0], 4), max=round(ts[-1], 4),
+                             gbps=round(2 * 3 * h * w / (ts[2] * 1e-3) / 1e9, 1) if ts[2] else None)
+        out.update(device=dev, turn_over_map=round(dev["turn_cw"]["device_ms"] / dev["map_180"]["device_ms"], 3) if dev["map_180"]["device_ms"] else None)
+        for k in ("orient_cw", "crop", "extend"):
+            out["host_over_device_" + k] = round(out["ms"]["host_" + k]["median"] / out["ms"][k]["median"], 1)
+    return out
+
+
 def modify_leg(model, reps, parent=False, side=512, tolerance=16):
     """(a) .. (e) of the module docstring; parent=True: the leg (a) only, with the calls a build without modifications has"""
     import numpy as np
@@ -1760,6 +1846,8 @@ def main():
     ap.add_argument("--modify-parent", action="store_true", help="the combine leg of --modify only")
     ap.add_argument("--blend", action="store_true", help="seamless move and clone (see the module docstring)")
     ap.add_argument("--blend-parent", action="store_true", help="the edit and the plain clone legs of --blend only")
+    ap.add_argument("--canvas", action="store_true", help="crop, extend, rotate and flip the canvas (see the module docstring)")
+    ap.add_argument("--canvas-parent", action="store_true", help="the edit leg of --canvas only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -1773,8 +1861,10 @@ def main():
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
             or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent
             or args.move or args.move_parent or args.warp or args.filter or args.adjust or args.modify or args.modify_parent
-            or args.blend or args.blend_parent):
-        if args.blend or args.blend_parent:
+            or args.blend or args.blend_parent or args.canvas or args.canvas_parent):
+        if args.canvas or args.canvas_parent:
+            res = canvas_leg(model, args.reps, parent=args.canvas_parent)
+        elif args.blend or args.blend_parent:
             res = blend_leg(model, args.reps, parent=args.blend_parent)
         elif args.modify or args.modify_parent:
             res = modify_leg(model, args.reps, parent=args.modify_parent)
