@@ -59,14 +59,14 @@ extern "C" {
 
 /* The workspace of one call for a box of box_h x box_w: two buffers of 8 bytes a cell for every level of the largest E, (box_h +
  * 2) x (box_w + 2).  0 for a side outside 1 .. SE_BLEND_MAX_SIDE. */
-size_t sketchedit_move_blend_u8_workspace_bytes(int box_h, int box_w);
+size_t se_move_blend_u8_workspace_bytes(int box_h, int box_w);
 
 /* The seamless drop, in place on frame_u8.  Launches: one that classifies E and reads F and P, one per level of the pull, at most
  * 16 per level of the push, one that writes D's targets.  Their number and every loop's trip count depend on E's size alone, never
  * on data in memory; there is no synchronisation between workgroups but the launch boundaries, no atomics, nothing polled, and no
  * host synchronisation.  Any alignment of the frame, the planes and Wi; no byte outside the frame's 3 Hi Wi, the planes' Hi Wi,
  * the slot's rows or the workspace is touched, and every workspace byte the kernels read was written by them. */
-int sketchedit_move_blend_u8(se_ctx* ctx, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0,
+int se_move_blend_u8(se_ctx* ctx, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0,
                      int lh, int lw, const unsigned char* sel_u8, const unsigned char* lock_u8_or_NULL, int by0, int bx0, int by1,
                      int bx1, int dy, int dx, int flip, void* workspace, size_t workspace_bytes);
 

@@ -32,75 +32,30 @@ FLAG_LOW_LATENCY, FLAG_GRAPH, FLAG_PACKED_OUT, FLAG_BF16, FLAG_CONSERVATIVE = 32
 LOW_LATENCY_MAX_PIXELS = 3 * 256 * 256
 LOW_LATENCY_MAX_SINGLE_IMAGE = 512 * 512
 
-# every symbol declared in include/sketchedit_hip.h
-SYMBOLS = ["se_create", "se_destroy", "se_last_error", "se_version", "se_load_weights", "se_weights_ready",
-           "se_workspace_bytes", "se_netM_forward", "se_netM_forward_ex", "se_netG_forward", "se_netG_forward_taps", "se_inference", "se_inference_u8", "se_gated_conv2d",
-           "se_gated_conv2d_ex", "se_attention", "se_attention_ex", "se_quantize_u8", "se_dequantize_u8", "se_inference_u8io", "se_profile_enable",
-           "se_profile_report", "se_debug_set_option", "se_debug_get_option", "se_debug_reset_options", "se_debug_gconv_form",
-           "se_resize_u8", "se_prepare_u8", "se_edit_u8", "se_edit_u8_workspace_bytes", "se_resample_coeffs",
-           "se_window_gather_u8", "se_window_border_u8", "se_window_paste_u8", "se_edit_window_u8", "se_edit_window_u8_workspace_bytes",
-           "se_window_gather_resize_u8", "se_window_paste_resize_u8", "se_edit_window_scaled_u8", "se_edit_window_scaled_u8_workspace_bytes",
-           "se_window_saved_bytes", "se_window_save_u8", "se_window_swap_u8",
-           "se_inference_locked", "se_inference_u8_locked", "se_window_gather_lock_u8", "se_window_paste_locked_u8",
-           "se_edit_window_locked_u8", "se_edit_window_locked_u8_workspace_bytes", "se_sketch_tiles_u8",
-           "se_sketch_strokes_u8",
-           "se_pack_inputs", "se_column_reduce", "se_output_conv"]
-# every symbol declared in include/sketchedit_png.h (the PNG entries of the editing sessions)
-PNG_SYMBOLS = ["se_png_bound", "se_png_encode_u8", "se_png_encode_u8_workspace_bytes"]
-# every symbol declared in include/sketchedit_jpg.h (the JPEG entries of the editing sessions)
-JPG_SYMBOLS = ["se_jpg_bound", "se_jpg_encode_u8", "se_jpg_encode_u8_workspace_bytes"]
-# every symbol declared in include/sketchedit_jpg2.h (4:2:0 sampling and per-image Huffman tables)
-JPG2_SYMBOLS = ["se_jpg2_bound", "se_jpg2_encode_u8", "se_jpg2_encode_u8_workspace_bytes", "se_jpg2_code_i16",
-                "se_jpg2_code_i16_workspace_bytes"]
-SE_JPG_420, SE_JPG_OPTIMIZE = 1, 2            # the flags of include/sketchedit_jpg2.h
+# The #define'd limits and codes of include/*.h, each once on the Python side: SE_<NAME> is <NAME> here (tests/test_abi_host.py
+# holds every define against its mirror).  serve.py imports them from here
+SE_JPG_420, SE_JPG_OPTIMIZE = 1, 2            # the flags of sketchedit_jpg2.h
 JPG_TABLE_RECORD_BYTES = 1088                 # one image's four tables as se_jpg2_encode_u8 leaves them
-# every symbol declared in include/sketchedit_feather.h (the feathered paste of the editing sessions)
-FEATHER_SYMBOLS = ["se_window_paste_feather_u8"]
-FEATHER_MAX_RADIUS = 16                       # SE_FEATHER_MAX_RADIUS
-# every symbol declared in include/sketchedit_fill.h (fills of a painted region)
-FILL_SYMBOLS = ["se_fill", "se_fill_window_u8", "se_fill_window_u8_workspace_bytes", "se_fill_keep_u8"]
-# every symbol declared in include/sketchedit_select.h (selection by colour)
-SELECT_SYMBOLS = ["se_select_similar_u8", "se_select_flood_u8", "se_select_grow_u8"]
-SELECT_MAX_GROW, SELECT_MAX_PASSES = 16, 64   # SE_SELECT_MAX_GROW, SE_SELECT_MAX_PASSES
-# every symbol declared in include/sketchedit_lasso.h (lasso selections and their algebra)
-LASSO_SYMBOLS = ["se_lasso_fill_u8", "se_plane_combine_u8"]
-LASSO_MAX_EDGES, LASSO_MAX_EXTENT = 65536, 8192   # SE_LASSO_MAX_EDGES, SE_LASSO_MAX_EXTENT
-COMBINE_ADD, COMBINE_SUBTRACT, COMBINE_INTERSECT, COMBINE_XOR, COMBINE_INVERT = range(5)   # SE_COMBINE_*
-# every symbol declared in include/sketchedit_outline.h (the outline of a selection)
-OUTLINE_SYMBOLS = ["se_outline_u8_workspace_bytes", "se_outline_u8"]
-OUTLINE_TILE, OUTLINE_MAX_CAP = 64, 1 << 24       # SE_OUTLINE_TILE, SE_OUTLINE_MAX_CAP
-# every symbol declared in include/sketchedit_move.h (move or clone a selection)
-MOVE_SYMBOLS = ["se_move_drop_u8", "se_plane_shift_u8"]
-MOVE_MAX_OFFSET, MOVE_MAX_RADIUS = 16384, 16      # SE_MOVE_MAX_OFFSET, SE_MOVE_MAX_RADIUS
-MOVE_FLIP_X, MOVE_FLIP_Y = 1, 2                   # SE_MOVE_FLIP_*
-# every entry declared in include/sketchedit_blend.h (seamless move and clone).  They carry the library's name, not se_,
-# and this list is not a *_SYMBOLS list: the se_ names, those lists and their number are what the earlier entries' tests pin
-BLEND_ENTRIES = ["sketchedit_move_blend_u8_workspace_bytes", "sketchedit_move_blend_u8"]
-BLEND_MAX_SIDE = 2048                             # SE_BLEND_MAX_SIDE
-# the entry declared in include/sketchedit_canvas.h (the canvas of a session): like the list above, not a *_SYMBOLS list,
-# and its name starts with neither of the prefixes that the earlier entries' tests pin
-CANVAS_ENTRIES = ["skedit_canvas_u8"]
-CANVAS_MIRROR_X, CANVAS_MIRROR_Y, CANVAS_TRANSPOSE = 1, 2, 4      # SKEDIT_CANVAS_MIRROR_X, _MIRROR_Y, _TRANSPOSE
-CANVAS_EDGE, CANVAS_REFLECT, CANVAS_CONSTANT = 0, 1, 2            # SKEDIT_CANVAS_EDGE, _REFLECT, _CONSTANT
-CANVAS_MAX_SIDE, CANVAS_MAX_OFFSET = 32768, 1 << 20               # SKEDIT_CANVAS_MAX_SIDE, SKEDIT_CANVAS_MAX_OFFSET
-# every symbol declared in include/sketchedit_warp.h (scale and rotate a selection)
-WARP_SYMBOLS = ["se_warp_drop_u8", "se_plane_warp_u8"]
-WARP_MAX_COEF, WARP_MAX_TRANSLATION = 1 << 20, 1 << 40      # SE_WARP_MAX_COEF, SE_WARP_MAX_TRANSLATION
-# every symbol declared in include/sketchedit_filter.h (blur, sharpen or pixelate a selection)
-FILTER_SYMBOLS = ["se_filter_blur_u8", "se_filter_mosaic_u8"]
-FILTER_MAX_RADIUS, FILTER_ONE, FILTER_MAX_CELL = 32, 4096, 64      # SE_FILTER_MAX_RADIUS, SE_FILTER_ONE, SE_FILTER_MAX_CELL
-FILTER_MIN_AMOUNT, FILTER_MAX_AMOUNT, FILTER_MAX_FEATHER = -256, 1024, 16      # SE_FILTER_MIN_AMOUNT, SE_FILTER_MAX_AMOUNT, SE_FILTER_MAX_FEATHER
-
-# every symbol declared in include/sketchedit_adjust.h (adjust a selection's tone and colour)
-ADJUST_SYMBOLS = ["se_adjust_u8", "se_adjust_hist_u8_workspace_bytes", "se_adjust_hist_u8", "se_adjust_lut_u8"]
-ADJUST_MAX_COEF, ADJUST_MAX_OFFSET, ADJUST_ONE_AMOUNT = 32768, 1 << 20, 256      # SE_ADJUST_MAX_COEF, SE_ADJUST_MAX_OFFSET, SE_ADJUST_ONE_AMOUNT
-ADJUST_MAX_FEATHER, ADJUST_MAX_CLIP, ADJUST_HIST_GROUPS = 16, 200, 256      # SE_ADJUST_MAX_FEATHER, SE_ADJUST_MAX_CLIP, SE_ADJUST_HIST_GROUPS
-ADJUST_STRETCH, ADJUST_EQUALIZE, ADJUST_MATCH = 0, 1, 2      # SE_ADJUST_STRETCH, SE_ADJUST_EQUALIZE, SE_ADJUST_MATCH
-ADJUST_PER_CHANNEL, ADJUST_LUMA = 0, 1      # SE_ADJUST_PER_CHANNEL, SE_ADJUST_LUMA
-# every symbol declared in include/sketchedit_modify.h (modify a selection's shape)
-MODIFY_SYMBOLS = ["se_plane_modify_u8"]
-MODIFY_MAX_RADIUS = 32                            # SE_MODIFY_MAX_RADIUS
-MODIFY_EXPAND, MODIFY_CONTRACT, MODIFY_SMOOTH = range(3)      # SE_MODIFY_*
+FEATHER_MAX_RADIUS = 16
+SELECT_MAX_GROW, SELECT_MAX_PASSES = 16, 64
+LASSO_MAX_EDGES, LASSO_MAX_EXTENT = 65536, 8192
+COMBINE_ADD, COMBINE_SUBTRACT, COMBINE_INTERSECT, COMBINE_XOR, COMBINE_INVERT = range(5)
+OUTLINE_TILE, OUTLINE_MAX_CAP = 64, 1 << 24
+MOVE_MAX_OFFSET, MOVE_MAX_RADIUS = 16384, 16
+MOVE_FLIP_X, MOVE_FLIP_Y = 1, 2
+BLEND_MAX_SIDE = 2048
+CANVAS_MIRROR_X, CANVAS_MIRROR_Y, CANVAS_TRANSPOSE = 1, 2, 4
+CANVAS_EDGE, CANVAS_REFLECT, CANVAS_CONSTANT = 0, 1, 2
+CANVAS_MAX_SIDE, CANVAS_MAX_OFFSET = 32768, 1 << 20
+WARP_MAX_COEF, WARP_MAX_TRANSLATION = 1 << 20, 1 << 40
+FILTER_MAX_RADIUS, FILTER_ONE, FILTER_MAX_CELL = 32, 4096, 64
+FILTER_MIN_AMOUNT, FILTER_MAX_AMOUNT, FILTER_MAX_FEATHER = -256, 1024, 16
+ADJUST_MAX_COEF, ADJUST_MAX_OFFSET, ADJUST_ONE_AMOUNT = 32768, 1 << 20, 256
+ADJUST_MAX_FEATHER, ADJUST_MAX_CLIP, ADJUST_HIST_GROUPS = 16, 200, 256
+ADJUST_STRETCH, ADJUST_EQUALIZE, ADJUST_MATCH = 0, 1, 2
+ADJUST_PER_CHANNEL, ADJUST_LUMA = 0, 1
+MODIFY_MAX_RADIUS = 32
+MODIFY_EXPAND, MODIFY_CONTRACT, MODIFY_SMOOTH = range(3)
 
 
 class SketchEditHipError(RuntimeError):
@@ -122,6 +77,144 @@ class Window(ctypes.Structure):
 class OutputConvIO(ctypes.Structure):
     """se_output_conv_io (include/sketchedit_hip.h): the optional tensors of the output conv's epilogue, device pointers or NULL"""
     _fields_ = [(n, ctypes.c_void_p) for n in ("out", "hard", "lock", "img", "mask", "xnow", "composed", "rgb8", "m8")]
+
+
+# The C ABI, one row per entry: (name, restype, argtypes), keyed by the header that declares it, in the header's order.
+# load_library() binds every row; tests/test_abi_host.py holds the rows against the prototypes and the library's exports
+vp, ci, cu, sz, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.c_char_p      # vp: device and host addresses alike
+pvp, pci, pw = ctypes.POINTER(vp), ctypes.POINTER(ci), ctypes.POINTER(Window)
+ABI = {
+    "sketchedit_hip.h": [
+        ("se_create", ci, [ci, pvp]),
+        ("se_destroy", None, [vp]),
+        ("se_last_error", cs, [vp]),
+        ("se_version", cs, []),
+        ("se_load_weights", ci, [vp, ci, cs, vp, pci, ci]),
+        ("se_weights_ready", ci, [vp]),
+        ("se_workspace_bytes", sz, [vp, ci, ci, ci]),
+        ("se_netM_forward", ci, [vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci]),
+        ("se_netM_forward_ex", ci, [vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]),
+        ("se_netG_forward", ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]),
+        ("se_netG_forward_taps", ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ctypes.POINTER(NetGTaps)]),
+        ("se_inference", ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]),
+        ("se_inference_u8", ci, [vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]),
+        ("se_dequantize_u8", ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci]),
+        ("se_inference_u8io", ci, [vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]),
+        ("se_quantize_u8", ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci]),
+        ("se_resize_u8", ci, [vp, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci]),
+        ("se_prepare_u8", ci, [vp, vp, vp, ci, ci, vp, ci, ci, vp, vp, ci, ci]),
+        ("se_edit_u8", ci, [vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ci, ci]),
+        ("se_edit_u8_workspace_bytes", sz, [vp, ci, ci, ci]),
+        ("se_window_gather_u8", ci, [vp, vp, pw, ci, ci, ci, vp, vp]),
+        ("se_window_border_u8", ci, [vp, vp, pw, ci, ci, ci, vp, vp]),
+        ("se_window_paste_u8", ci, [vp, vp, pw, ci, ci, ci, vp, vp]),
+        ("se_edit_window_u8", ci, [vp, vp, pw, ci, ci, ci, vp, vp, vp, ci, vp, sz, ci]),
+        ("se_edit_window_u8_workspace_bytes", sz, [vp, ci, ci, ci]),
+        ("se_window_gather_resize_u8", ci, [vp, vp, pw, ci, ci, ci, ci, ci, vp, vp]),
+        ("se_window_paste_resize_u8", ci, [vp, vp, pw, ci, ci, ci, ci, ci, vp, vp]),
+        ("se_edit_window_scaled_u8", ci, [vp, vp, pw, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, sz, ci]),
+        ("se_edit_window_scaled_u8_workspace_bytes", sz, [vp, ci, ci, ci, ci, ci]),
+        ("se_window_saved_bytes", sz, [ci, ci]),
+        ("se_window_save_u8", ci, [vp, vp, pw, ci, ci, ci, pvp]),
+        ("se_window_swap_u8", ci, [vp, vp, pw, ci, ci, ci, pvp]),
+        ("se_inference_locked", ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]),
+        ("se_inference_u8_locked", ci, [vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]),
+        ("se_window_gather_lock_u8", ci, [vp, vp, pw, pvp, ci, ci, ci, ci, ci, vp]),
+        ("se_window_paste_locked_u8", ci, [vp, vp, pw, pvp, ci, ci, ci, ci, ci, vp, vp]),
+        ("se_edit_window_locked_u8", ci, [vp, vp, pw, pvp, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, sz, ci]),
+        ("se_edit_window_locked_u8_workspace_bytes", sz, [vp, ci, ci, ci, ci, ci]),
+        ("se_sketch_tiles_u8", ci, [vp, vp, vp, ci, ci, ci, vp]),
+        ("se_sketch_strokes_u8", ci, [vp, vp, vp, ci, ci, ci, vp, ci, vp, vp]),
+        ("se_resample_coeffs", ci, [ci, ci, ci, vp, vp, sz]),
+        ("se_profile_enable", ci, [vp, ci]),
+        ("se_profile_report", ci, [vp, cs, sz]),
+        ("se_debug_set_option", ci, [cs, ci]),
+        ("se_debug_get_option", ci, [cs, pci]),
+        ("se_debug_reset_options", None, []),
+        ("se_debug_gconv_form", ci, [ci] * 14 + [cs, sz]),
+        ("se_gated_conv2d", ci, [vp, vp, vp, vp, vp, vp] + [ci] * 10),
+        ("se_gated_conv2d_ex", ci, [vp, vp, vp, vp, ci, vp, vp, vp] + [ci] * 12),
+        ("se_attention", ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci]),
+        ("se_attention_ex", ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]),
+        ("se_pack_inputs", ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
+        ("se_column_reduce", ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci]),
+        ("se_output_conv", ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(OutputConvIO), ci, ci, ci]),
+    ],
+    "sketchedit_png.h": [
+        ("se_png_bound", sz, [ci, ci]),
+        ("se_png_encode_u8", ci, [vp, vp, pw, ci, ci, ci, vp, sz, vp, vp, sz]),
+        ("se_png_encode_u8_workspace_bytes", sz, [vp, ci, ci, ci]),
+    ],
+    "sketchedit_jpg.h": [
+        ("se_jpg_bound", sz, [ci, ci]),
+        ("se_jpg_encode_u8", ci, [vp, vp, pw, ci, ci, ci, ci, vp, sz, vp, vp, sz]),
+        ("se_jpg_encode_u8_workspace_bytes", sz, [vp, ci, ci, ci]),
+    ],
+    "sketchedit_jpg2.h": [
+        ("se_jpg2_bound", sz, [ci, ci, ci]),
+        ("se_jpg2_encode_u8", ci, [vp, vp, pw, ci, ci, ci, ci, ci, vp, sz, vp, vp, vp, sz]),
+        ("se_jpg2_encode_u8_workspace_bytes", sz, [vp, ci, ci, ci, ci]),
+        ("se_jpg2_code_i16", ci, [vp, vp, vp, ci, ci, ci, ci, vp, sz, vp, vp, vp, sz]),
+        ("se_jpg2_code_i16_workspace_bytes", sz, [vp, ci, ci, ci, ci]),
+    ],
+    "sketchedit_feather.h": [
+        ("se_window_paste_feather_u8", ci, [vp, vp, pw, pvp, ci, ci, ci, ci, vp, vp]),
+    ],
+    "sketchedit_fill.h": [
+        ("se_fill", ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]),
+        ("se_fill_window_u8_workspace_bytes", sz, [vp, ci, ci, ci, ci, ci]),
+        ("se_fill_window_u8", ci, [vp, vp, pw, pvp, pvp, ci, ci, ci, ci, ci, vp, vp, vp, sz, ci]),
+        ("se_fill_keep_u8", ci, [vp, vp, pw, pvp, pvp, pvp, ci, ci, ci]),
+    ],
+    "sketchedit_select.h": [
+        ("se_select_similar_u8", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+        ("se_select_flood_u8", ci, [vp, vp, vp, ci, ci, ci, vp]),
+        ("se_select_grow_u8", ci, [vp, vp, vp, ci, ci, ci, vp]),
+    ],
+    "sketchedit_lasso.h": [
+        ("se_lasso_fill_u8", ci, [vp, vp, vp, ci, ci, ci, vp]),
+        ("se_plane_combine_u8", ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
+    ],
+    "sketchedit_outline.h": [
+        ("se_outline_u8_workspace_bytes", sz, [vp, ci, ci]),
+        ("se_outline_u8", ci, [vp, vp, vp, ci, ci, vp, ci, vp, vp, sz]),
+    ],
+    "sketchedit_move.h": [
+        ("se_move_drop_u8", ci, [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8),
+        ("se_plane_shift_u8", ci, [vp, vp, vp, ci, ci] + [ci] * 7 + [vp]),
+    ],
+    "sketchedit_warp.h": [
+        ("se_warp_drop_u8", ci, [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8 + [vp]),
+        ("se_plane_warp_u8", ci, [vp, vp, vp, ci, ci] + [ci] * 4 + [vp, vp]),
+    ],
+    "sketchedit_filter.h": [
+        ("se_filter_blur_u8", ci, [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 4 + [vp, ci, ci, ci]),
+        ("se_filter_mosaic_u8", ci, [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 7),
+    ],
+    "sketchedit_adjust.h": [
+        ("se_adjust_u8", ci, [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 4 + [vp, vp, ci, ci]),
+        ("se_adjust_hist_u8_workspace_bytes", sz, [ci, ci]),
+        ("se_adjust_hist_u8", ci, [vp, vp, vp, ci, ci, vp] + [ci] * 4 + [vp, vp, sz]),
+        ("se_adjust_lut_u8", ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
+    ],
+    "sketchedit_modify.h": [
+        ("se_plane_modify_u8", ci, [vp, vp, vp, ci, ci, ci, ci, vp]),
+    ],
+    "sketchedit_blend.h": [
+        ("se_move_blend_u8_workspace_bytes", sz, [ci, ci]),
+        ("se_move_blend_u8", ci, [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 7 + [vp, sz]),
+    ],
+    "sketchedit_canvas.h": [
+        ("se_canvas_u8", ci, [vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, cu]),
+    ],
+}
+# bound when present: a build from before the entry still loads through SKETCHEDIT_HIP_LIB
+ABI_OPTIONAL = {"se_debug_gconv_form"}
+
+
+def abi_names(header=None):
+    """The entry names one header declares ("sketchedit_png.h"), in its order, or with no header those of all"""
+    return [row[0] for h in ([header] if header else ABI) for row in ABI[h]]
 
 
 def build_library(force=False, verbose=False, extra_flags=()):
@@ -184,188 +277,12 @@ def load_library():
         # Loaded the other way round the process ends up with two HIP runtimes and hipGetDeviceCount() returns 0.
         import torch  # noqa: F401
         lib = ctypes.CDLL(LIB_PATH)
-        c_f = ctypes.c_void_p  # device/host float pointers are passed as raw addresses
-        vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-        lib.se_create.argtypes = [ci, ctypes.POINTER(vp)]
-        lib.se_create.restype = ci
-        lib.se_destroy.argtypes = [vp]
-        lib.se_destroy.restype = None
-        lib.se_last_error.argtypes = [vp]
-        lib.se_last_error.restype = ctypes.c_char_p
-        lib.se_version.argtypes = []
-        lib.se_version.restype = ctypes.c_char_p
-        lib.se_load_weights.argtypes = [vp, ci, ctypes.c_char_p, c_f, ctypes.POINTER(ci), ci]
-        lib.se_load_weights.restype = ci
-        lib.se_weights_ready.argtypes = [vp]
-        lib.se_weights_ready.restype = ci
-        lib.se_workspace_bytes.argtypes = [vp, ci, ci, ci]
-        lib.se_workspace_bytes.restype = sz
-        lib.se_netM_forward.argtypes = [vp, vp, c_f, c_f, c_f, c_f, vp, sz, ci, ci, ci]
-        lib.se_netM_forward.restype = ci
-        lib.se_netM_forward_ex.argtypes = [vp, vp, c_f, c_f, c_f, c_f, vp, sz, ci, ci, ci, ci]
-        lib.se_netM_forward_ex.restype = ci
-        lib.se_netG_forward.argtypes = [vp, vp, c_f, c_f, c_f, c_f, c_f, c_f, c_f, vp, sz, ci, ci, ci, ci]
-        lib.se_netG_forward.restype = ci
-        lib.se_netG_forward_taps.argtypes = [vp, vp, c_f, c_f, c_f, c_f, c_f, c_f, c_f, vp, sz, ci, ci, ci, ci, ctypes.POINTER(NetGTaps)]
-        lib.se_netG_forward_taps.restype = ci
-        lib.se_inference.argtypes = [vp, vp, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, vp, sz, ci, ci, ci, ci]
-        lib.se_inference.restype = ci
-        lib.se_inference_u8.argtypes = [vp, vp, c_f, c_f, vp, vp, vp, sz, ci, ci, ci, ci]
-        lib.se_inference_u8.restype = ci
-        lib.se_gated_conv2d.argtypes = [vp, vp, c_f, c_f, c_f, c_f] + [ci] * 10
-        lib.se_gated_conv2d.restype = ci
-        lib.se_gated_conv2d_ex.argtypes = [vp, vp, c_f, c_f, ci, c_f, c_f, c_f] + [ci] * 12
-        lib.se_gated_conv2d_ex.restype = ci
-        lib.se_attention.argtypes = [vp, vp, c_f, c_f, c_f, c_f, ci, ci, ci]
-        lib.se_attention.restype = ci
-        lib.se_attention_ex.argtypes = [vp, vp, c_f, c_f, c_f, c_f, ci, ci, ci, ci]
-        lib.se_attention_ex.restype = ci
-        lib.se_quantize_u8.argtypes = [vp, vp, c_f, c_f, vp, vp, ci, ci, ci]
-        lib.se_quantize_u8.restype = ci
-        lib.se_dequantize_u8.argtypes = [vp, vp, vp, vp, c_f, c_f, ci, ci, ci]
-        lib.se_dequantize_u8.restype = ci
-        lib.se_inference_u8io.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci]
-        lib.se_inference_u8io.restype = ci
-        lib.se_resize_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci]
-        lib.se_resize_u8.restype = ci
-        lib.se_prepare_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, c_f, c_f, ci, ci]
-        lib.se_prepare_u8.restype = ci
-        lib.se_edit_u8.argtypes = [vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ci, ci]
-        lib.se_edit_u8.restype = ci
-        lib.se_edit_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
-        lib.se_edit_u8_workspace_bytes.restype = sz
-        lib.se_window_gather_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, c_f, c_f]
-        lib.se_window_gather_u8.restype = ci
-        lib.se_window_border_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, vp, vp]
-        lib.se_window_border_u8.restype = ci
-        lib.se_window_paste_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, vp, vp]
-        lib.se_window_paste_u8.restype = ci
-        lib.se_edit_window_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, vp, vp, vp, ci, vp, sz, ci]
-        lib.se_edit_window_u8.restype = ci
-        lib.se_edit_window_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
-        lib.se_edit_window_u8_workspace_bytes.restype = sz
-        lib.se_window_gather_resize_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, ci, c_f, c_f]
-        lib.se_window_gather_resize_u8.restype = ci
-        lib.se_window_paste_resize_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, ci, vp, vp]
-        lib.se_window_paste_resize_u8.restype = ci
-        lib.se_edit_window_scaled_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, sz, ci]
-        lib.se_edit_window_scaled_u8.restype = ci
-        lib.se_edit_window_scaled_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci, ci]
-        lib.se_edit_window_scaled_u8_workspace_bytes.restype = sz
-        lib.se_window_saved_bytes.argtypes = [ci, ci]
-        lib.se_window_saved_bytes.restype = sz
-        lib.se_window_save_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ctypes.POINTER(vp)]
-        lib.se_window_save_u8.restype = ci
-        lib.se_window_swap_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ctypes.POINTER(vp)]
-        lib.se_window_swap_u8.restype = ci
-        lib.se_inference_locked.argtypes = [vp, vp, c_f, c_f, vp, c_f, c_f, c_f, c_f, c_f, c_f, vp, sz, ci, ci, ci, ci]
-        lib.se_inference_locked.restype = ci
-        lib.se_inference_u8_locked.argtypes = [vp, vp, c_f, c_f, vp, vp, vp, vp, sz, ci, ci, ci, ci]
-        lib.se_inference_u8_locked.restype = ci
-        lib.se_window_gather_lock_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ci, ci, ci, ci, ci, vp]
-        lib.se_window_gather_lock_u8.restype = ci
-        lib.se_window_paste_locked_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ci, ci, ci, ci, ci, vp, vp]
-        lib.se_window_paste_locked_u8.restype = ci
-        lib.se_edit_window_locked_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, sz, ci]
-        lib.se_edit_window_locked_u8.restype = ci
-        lib.se_edit_window_locked_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci, ci]
-        lib.se_edit_window_locked_u8_workspace_bytes.restype = sz
-        lib.se_sketch_tiles_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
-        lib.se_sketch_tiles_u8.restype = ci
-        lib.se_sketch_strokes_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, ci, vp, vp]
-        lib.se_sketch_strokes_u8.restype = ci
-        lib.se_pack_inputs.argtypes = [vp, vp, ci, c_f, c_f, c_f, c_f, c_f, vp, vp, ci, ci, ci, ci, ci]
-        lib.se_pack_inputs.restype = ci
-        lib.se_column_reduce.argtypes = [vp, vp, c_f, c_f, vp, ci, ci, ci, ci, ci, ci]
-        lib.se_column_reduce.restype = ci
-        lib.se_output_conv.argtypes = [vp, vp, c_f, c_f, c_f, ci, ci, ci, ci, ci, ctypes.POINTER(OutputConvIO), ci, ci, ci]
-        lib.se_output_conv.restype = ci
-        lib.se_png_bound.argtypes = [ci, ci]
-        lib.se_png_bound.restype = sz
-        lib.se_png_encode_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, vp, sz, vp, vp, sz]
-        lib.se_png_encode_u8.restype = ci
-        lib.se_png_encode_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
-        lib.se_png_encode_u8_workspace_bytes.restype = sz
-        lib.se_jpg_bound.argtypes = [ci, ci]
-        lib.se_jpg_bound.restype = sz
-        lib.se_jpg_encode_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, vp, sz, vp, vp, sz]
-        lib.se_jpg_encode_u8.restype = ci
-        lib.se_jpg_encode_u8_workspace_bytes.argtypes = [vp, ci, ci, ci]
-        lib.se_jpg_encode_u8_workspace_bytes.restype = sz
-        lib.se_jpg2_bound.argtypes = [ci, ci, ci]
-        lib.se_jpg2_bound.restype = sz
-        lib.se_jpg2_encode_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ci, ci, ci, ci, ci, vp, sz, vp, vp, vp, sz]
-        lib.se_jpg2_encode_u8.restype = ci
-        lib.se_jpg2_encode_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
-        lib.se_jpg2_encode_u8_workspace_bytes.restype = sz
-        lib.se_jpg2_code_i16.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, sz, vp, vp, vp, sz]
-        lib.se_jpg2_code_i16.restype = ci
-        lib.se_jpg2_code_i16_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
-        lib.se_jpg2_code_i16_workspace_bytes.restype = sz
-        lib.se_window_paste_feather_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ci, ci, ci, ci, vp, vp]
-        lib.se_window_paste_feather_u8.restype = ci
-        lib.se_fill.argtypes = [vp, vp, c_f, c_f, vp, vp, c_f, c_f, c_f, c_f, vp, sz, ci, ci, ci, ci]
-        lib.se_fill.restype = ci
-        lib.se_fill_window_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, sz, ci]
-        lib.se_fill_window_u8.restype = ci
-        lib.se_fill_window_u8_workspace_bytes.argtypes = [vp, ci, ci, ci, ci, ci]
-        lib.se_fill_window_u8_workspace_bytes.restype = sz
-        lib.se_fill_keep_u8.argtypes = [vp, vp, ctypes.POINTER(Window), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci]
-        lib.se_fill_keep_u8.restype = ci
-        lib.se_select_similar_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-        lib.se_select_similar_u8.restype = ci
-        lib.se_select_flood_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
-        lib.se_select_flood_u8.restype = ci
-        lib.se_select_grow_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
-        lib.se_select_grow_u8.restype = ci
-        lib.se_lasso_fill_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp]
-        lib.se_lasso_fill_u8.restype = ci
-        lib.se_plane_combine_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
-        lib.se_plane_combine_u8.restype = ci
-        lib.se_plane_modify_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
-        lib.se_plane_modify_u8.restype = ci
-        lib.se_move_drop_u8.argtypes =[vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8
-        lib.se_move_drop_u8.restype = ci
-        lib.sketchedit_move_blend_u8_workspace_bytes.argtypes = [ci, ci]
-        lib.sketchedit_move_blend_u8_workspace_bytes.restype = sz
-        lib.sketchedit_move_blend_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 7 + [vp, sz]
-        lib.sketchedit_move_blend_u8.restype = ci
-        lib.skedit_canvas_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, ctypes.c_uint]
-        lib.skedit_canvas_u8.restype = ci
-        lib.se_plane_shift_u8.argtypes = [vp, vp, vp, ci, ci] + [ci] * 7 + [vp]
-        lib.se_plane_shift_u8.restype = ci
-        lib.se_warp_drop_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 8 + [vp]
-        lib.se_warp_drop_u8.restype = ci
-        lib.se_plane_warp_u8.argtypes = [vp, vp, vp, ci, ci] + [ci] * 4 + [vp, vp]
-        lib.se_plane_warp_u8.restype = ci
-        lib.se_filter_blur_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 4 + [vp, ci, ci, ci]
-        lib.se_filter_blur_u8.restype = ci
-        lib.se_filter_mosaic_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 7
-        lib.se_filter_mosaic_u8.restype = ci
-        lib.se_adjust_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp] + [ci] * 4 + [vp, vp, ci, ci]
-        lib.se_adjust_u8.restype = ci
-        lib.se_adjust_hist_u8_workspace_bytes.argtypes = [ci, ci]
-        lib.se_adjust_hist_u8_workspace_bytes.restype = sz
-        lib.se_adjust_hist_u8.argtypes = [vp, vp, vp, ci, ci, vp] + [ci] * 4 + [vp, vp, sz]
-        lib.se_adjust_hist_u8.restype = ci
-        lib.se_adjust_lut_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
-        lib.se_adjust_lut_u8.restype = ci
-        lib.se_outline_u8_workspace_bytes.argtypes = [vp, ci, ci]
-        lib.se_outline_u8_workspace_bytes.restype = sz
-        lib.se_outline_u8.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, sz]
-        lib.se_outline_u8.restype = ci
-        lib.se_resample_coeffs.argtypes = [ci, ci, ci, vp, vp, sz]
-        lib.se_resample_coeffs.restype = ci
-        lib.se_profile_enable.argtypes = [vp, ci]
-        lib.se_profile_enable.restype = ci
-        lib.se_profile_report.argtypes = [vp, ctypes.c_char_p, sz]
-        lib.se_profile_report.restype = ci
-        lib.se_debug_set_option.argtypes = [ctypes.c_char_p, ci]
-        lib.se_debug_set_option.restype = ci
-        lib.se_debug_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ci)]
-        lib.se_debug_get_option.restype = ci
-        lib.se_debug_reset_options.argtypes = []
-        lib.se_debug_reset_options.restype = None
+        for rows in ABI.values():
+            for name, restype, argtypes in rows:
+                if name in ABI_OPTIONAL and not hasattr(lib, name):
+                    continue
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
         return lib
 
@@ -407,10 +324,8 @@ def gconv_form(cin, cout, H, W, k=3, stride=1, rate=1, act="elu", upsample=False
     source's channels; cin1: the second's (0: none)."""
     flags = (FLAG_LOW_LATENCY if low_latency else 0) | (FLAG_BF16 if bf16 else 0) | (FLAG_CONSERVATIVE if conservative else 0)
     buf = ctypes.create_string_buffer(64)
-    fn = load_library().se_debug_gconv_form      # (bound here, not at load: a build from before the entry still loads through SKETCHEDIT_HIP_LIB)
-    fn.argtypes, fn.restype = [ctypes.c_int] * 14 + [ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int
-    if fn(cin, cin1, int(bool(x1_is_vector)), cout, k, stride, rate, {"elu": 0, "relu": 1, None: 2}[act],
-          int(bool(upsample)), B, H, W, flags, net, buf, len(buf)):
+    if load_library().se_debug_gconv_form(cin, cin1, int(bool(x1_is_vector)), cout, k, stride, rate,
+                                          {"elu": 0, "relu": 1, None: 2}[act], int(bool(upsample)), B, H, W, flags, net, buf, len(buf)):
         raise SketchEditHipError("gconv_form: not a layer gated_conv2d takes")
     return buf.value.decode().split(",")
 
@@ -1315,19 +1230,19 @@ class Engine:
             self._err("se_move_drop_u8")
 
     def move_blend_u8(self, frame, lift, lift_rect, sel, lock, box, offset, flip=0):
-        """sketchedit_move_blend_u8 (include/sketchedit_blend.h), in place on `frame`: move_drop_u8's arguments without the
+        """se_move_blend_u8 (include/sketchedit_blend.h), in place on `frame`: move_drop_u8's arguments without the
         radius; the object keeps its own detail and takes the local colour of the place it lands in -- the lift's bytes plus a
         membrane that equals frame - lift on the object's rim, made by a fixed schedule of integer steps.  `lift_rect` should
         hold the box grown by one pixel (the rim's sources); a side of the box is at most BLEND_MAX_SIDE.  The launches depend
         on the box's size alone; none when the whole box lands outside the frame."""
         Hi, Wi, (ly0, lx0, lh, lw), (by0, bx0, by1, bx1) = self._lift_args("move_blend_u8", frame, lift, lift_rect, sel, lock, box)
-        need = self.lib.sketchedit_move_blend_u8_workspace_bytes(by1 - by0, bx1 - bx0)
+        need = self.lib.se_move_blend_u8_workspace_bytes(by1 - by0, bx1 - bx0)
         if need == 0:
             raise SketchEditHipError("move_blend_u8: a side of the box %r is outside 1 .. %d" % ((by0, bx0, by1, bx1), BLEND_MAX_SIDE))
         ws_t = self._workspace_bytes(need)
-        if self.lib.sketchedit_move_blend_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
+        if self.lib.se_move_blend_u8(self.h, self._stream(), _ptr(frame), Hi, Wi, _ptr(lift), ly0, lx0, lh, lw, _ptr(sel), _ptr(lock),
                                      by0, bx0, by1, bx1, int(offset[0]), int(offset[1]), int(flip), _ptr(ws_t), ws_t.numel()):
-            self._err("sketchedit_move_blend_u8")
+            self._err("se_move_blend_u8")
 
     def plane_shift_u8(self, sel, box, offset, flip=0, out=None):
         """se_plane_shift_u8: `sel` (Hi,Wi) uint8 on the device, non-zero = selected -> `out` (a new plane, or another plane of
@@ -1347,7 +1262,7 @@ class Engine:
 
     # ---- the canvas of a session (include/sketchedit_canvas.h) ---------------------------------------------------------
     def canvas_u8(self, src, out_hw, origin=(0, 0), orient=0, pad=CANVAS_EDGE, pad_rgb=0, src_hw=None, out=None, device=None):
-        """skedit_canvas_u8: `src` (Hi,Wi,3) or (Hi,Wi) uint8 on the device -> `out` (a NEW tensor (Hn,Wn,3) / (Hn,Wn), or one of
+        """se_canvas_u8: `src` (Hi,Wi,3) or (Hi,Wi) uint8 on the device -> `out` (a NEW tensor (Hn,Wn,3) / (Hn,Wn), or one of
         that shape that shares no byte with src; any alignment; every byte is written): the rectangle of `out_hw` = (Hn, Wn) at
         `origin` = (oy, ox) of src oriented by `orient` (0 .. 7: CANVAS_MIRROR_X | CANVAS_MIRROR_Y | CANVAS_TRANSPOSE, the
         transpose last), what lies outside filled by `pad` (CANVAS_EDGE, CANVAS_REFLECT, or CANVAS_CONSTANT with the colour
@@ -1374,9 +1289,9 @@ class Engine:
         _check_dev_u8(out)
         if tuple(out.shape) != shape:
             raise SketchEditHipError("canvas_u8: out is a uint8 tensor of shape %r" % (shape,))
-        if self.lib.skedit_canvas_u8(self.h, self._stream(), _ptr(src), Hi, Wi, C, _ptr(out), Hn, Wn, int(origin[0]), int(origin[1]),
+        if self.lib.se_canvas_u8(self.h, self._stream(), _ptr(src), Hi, Wi, C, _ptr(out), Hn, Wn, int(origin[0]), int(origin[1]),
                                      int(orient), int(pad), int(pad_rgb) & 0xffffffff):
-            self._err("skedit_canvas_u8")
+            self._err("se_canvas_u8")
         return out
 
     # ---- scale and rotate a selection (include/sketchedit_warp.h) ------------------------------------------------------

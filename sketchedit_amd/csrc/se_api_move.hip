@@ -119,14 +119,14 @@ int se_move_drop_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, in
   return 0;
 }
 
-size_t sketchedit_move_blend_u8_workspace_bytes(int box_h, int box_w) {
+size_t se_move_blend_u8_workspace_bytes(int box_h, int box_w) {
   if (box_h < 1 || box_w < 1 || box_h > SE_BLEND_MAX_SIDE || box_w > SE_BLEND_MAX_SIDE) return 0;
   return blend_workspace_bytes(box_h + 2, box_w + 2);
 }
 
 // The plain drop's checks, then the workspace's; the launches are a function of the rectangle's size alone (se_blend.hip).  The
 // workspace is the one scratch region: SE_TEST_POISON fills it, and the kernels write every record in front of its first read.
-int sketchedit_move_blend_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh,
+int se_move_blend_u8(se_ctx* c, void* stream, unsigned char* frame_u8, int Hi, int Wi, const unsigned char* lift, int ly0, int lx0, int lh,
                      int lw, const unsigned char* sel_u8, const unsigned char* lock_u8, int by0, int bx0, int by1, int bx1, int dy, int dx,
                      int flip, void* workspace, size_t workspace_bytes) {
   if (!c) return 1;
@@ -137,7 +137,7 @@ int sketchedit_move_blend_u8(se_ctx* c, void* stream, unsigned char* frame_u8, i
     return fail(c, "the box (%d, %d, %d, %d) has a side above %d", by0, bx0, by1, bx1, SE_BLEND_MAX_SIDE);
   if (lift_check_overlaps(c, frame_u8, Hi, Wi, lift, lh, lw, sel_u8, lock_u8)) return 1;
   if (!workspace) return fail(c, "null pointer argument: workspace");
-  const size_t need = sketchedit_move_blend_u8_workspace_bytes(by1 - by0, bx1 - bx0), pn = (size_t)Hi * Wi;
+  const size_t need = se_move_blend_u8_workspace_bytes(by1 - by0, bx1 - bx0), pn = (size_t)Hi * Wi;
   if (workspace_bytes < need) return fail(c, "workspace too small: %zu bytes, need %zu", workspace_bytes, need);
   if (!aligned_to(workspace, 16)) return fail(c, "workspace must be 16-byte aligned");
   const size_t ln = (size_t)lh * (((size_t)3 * lw + 15) & ~(size_t)15);
@@ -172,7 +172,7 @@ int se_plane_shift_u8(se_ctx* c, void* stream, const unsigned char* sel_u8, int 
 
 // The canvas: out of place, every check on the host, ONE launch that writes every byte of `out`.  What the launch takes: canvas_map
 // walks C Hn Wn / 4 < 2^29 dwords, 256 to a workgroup; canvas_turn's grid is at most 1024 x 512 tiles.
-int skedit_canvas_u8(se_ctx* c, void* stream, const unsigned char* in, int Hi, int Wi, int C, unsigned char* out, int Hn, int Wn, int oy, int ox,
+int se_canvas_u8(se_ctx* c, void* stream, const unsigned char* in, int Hi, int Wi, int C, unsigned char* out, int Hn, int Wn, int oy, int ox,
                      int orient, int pad_mode, unsigned pad_rgb) {
   if (!c) return 1;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -180,14 +180,14 @@ int skedit_canvas_u8(se_ctx* c, void* stream, const unsigned char* in, int Hi, i
   if (C != 1 && C != 3) return fail(c, "bad C=%d (1: a plane, 3: a frame)", C);
   if (!in && C != 1) return fail(c, "null pointer argument: in (only a plane, C = 1, may be NULL)");
   if (orient < 0 || orient > 7) return fail(c, "bad orient=%d (0 .. 7)", orient);
-  if (pad_mode != SKEDIT_CANVAS_EDGE && pad_mode != SKEDIT_CANVAS_REFLECT && pad_mode != SKEDIT_CANVAS_CONSTANT)
-    return fail(c, "bad pad_mode=%d (SKEDIT_CANVAS_EDGE, _REFLECT or _CONSTANT)", pad_mode);
-  if (Hi < 1 || Wi < 1 || Hi > SKEDIT_CANVAS_MAX_SIDE || Wi > SKEDIT_CANVAS_MAX_SIDE || (long long)C * Hi * Wi >= (1ll << 31))
-    return fail(c, "bad Hi=%d Wi=%d (1 .. %d, C Hi Wi < 2^31)", Hi, Wi, SKEDIT_CANVAS_MAX_SIDE);
-  if (Hn < 1 || Wn < 1 || Hn > SKEDIT_CANVAS_MAX_SIDE || Wn > SKEDIT_CANVAS_MAX_SIDE || (long long)C * Hn * Wn >= (1ll << 31))
-    return fail(c, "bad Hn=%d Wn=%d (1 .. %d, C Hn Wn < 2^31)", Hn, Wn, SKEDIT_CANVAS_MAX_SIDE);
-  if (oy < -SKEDIT_CANVAS_MAX_OFFSET || oy > SKEDIT_CANVAS_MAX_OFFSET) return fail(c, "bad oy=%d (|oy| <= %d)", oy, SKEDIT_CANVAS_MAX_OFFSET);
-  if (ox < -SKEDIT_CANVAS_MAX_OFFSET || ox > SKEDIT_CANVAS_MAX_OFFSET) return fail(c, "bad ox=%d (|ox| <= %d)", ox, SKEDIT_CANVAS_MAX_OFFSET);
+  if (pad_mode != SE_CANVAS_EDGE && pad_mode != SE_CANVAS_REFLECT && pad_mode != SE_CANVAS_CONSTANT)
+    return fail(c, "bad pad_mode=%d (SE_CANVAS_EDGE, _REFLECT or _CONSTANT)", pad_mode);
+  if (Hi < 1 || Wi < 1 || Hi > SE_CANVAS_MAX_SIDE || Wi > SE_CANVAS_MAX_SIDE || (long long)C * Hi * Wi >= (1ll << 31))
+    return fail(c, "bad Hi=%d Wi=%d (1 .. %d, C Hi Wi < 2^31)", Hi, Wi, SE_CANVAS_MAX_SIDE);
+  if (Hn < 1 || Wn < 1 || Hn > SE_CANVAS_MAX_SIDE || Wn > SE_CANVAS_MAX_SIDE || (long long)C * Hn * Wn >= (1ll << 31))
+    return fail(c, "bad Hn=%d Wn=%d (1 .. %d, C Hn Wn < 2^31)", Hn, Wn, SE_CANVAS_MAX_SIDE);
+  if (oy < -SE_CANVAS_MAX_OFFSET || oy > SE_CANVAS_MAX_OFFSET) return fail(c, "bad oy=%d (|oy| <= %d)", oy, SE_CANVAS_MAX_OFFSET);
+  if (ox < -SE_CANVAS_MAX_OFFSET || ox > SE_CANVAS_MAX_OFFSET) return fail(c, "bad ox=%d (|ox| <= %d)", ox, SE_CANVAS_MAX_OFFSET);
   if (in && overlaps(in, (size_t)C * Hi * Wi, out, (size_t)C * Hn * Wn)) return fail(c, "out overlaps in");
   if (device_enter(c)) return 1;
   HIPCHK(c, launch_canvas(in, Hi, Wi, C, out, Hn, Wn, oy, ox, orient, pad_mode, pad_rgb, (hipStream_t)stream));

@@ -48,7 +48,7 @@ struct CanvasMap {
 
   DEVFN int fold(int i, int n) const {
     if ((unsigned)i < (unsigned)n) return i;
-    if (pad == SKEDIT_CANVAS_EDGE) return i < 0 ? 0 : n - 1;
+    if (pad == SE_CANVAS_EDGE) return i < 0 ? 0 : n - 1;
     if (n == 1) return 0;
     const int p = 2 * n - 2;
     int j = i % p;
@@ -58,8 +58,8 @@ struct CanvasMap {
   // the pixel (Y, X) of the oriented image, 0 <= Y < Ho, 0 <= X < Wo: C bytes in the low end of a dword
   DEVFN unsigned src(int Y, int X) const {
     if (!in) return 0u;
-    const int a = (orient & SKEDIT_CANVAS_TRANSPOSE) ? X : Y, b = (orient & SKEDIT_CANVAS_TRANSPOSE) ? Y : X;
-    const int sy = (orient & SKEDIT_CANVAS_MIRROR_Y) ? Hi - 1 - a : a, sx = (orient & SKEDIT_CANVAS_MIRROR_X) ? Wi - 1 - b : b;
+    const int a = (orient & SE_CANVAS_TRANSPOSE) ? X : Y, b = (orient & SE_CANVAS_TRANSPOSE) ? Y : X;
+    const int sy = (orient & SE_CANVAS_MIRROR_Y) ? Hi - 1 - a : a, sx = (orient & SE_CANVAS_MIRROR_X) ? Wi - 1 - b : b;
     const unsigned char* row = in + (size_t)sy * Wi * C;
     if (C == 1) return row[sx];
     return load4_within(row + 3 * sx, row, row + 3 * (size_t)Wi) & 0xffffffu;
@@ -67,7 +67,7 @@ struct CanvasMap {
   // the output pixel (y, x)
   DEVFN unsigned px(int y, int x) const {
     const int Y = y + oy, X = x + ox;
-    if (pad == SKEDIT_CANVAS_CONSTANT && ((unsigned)Y >= (unsigned)Ho || (unsigned)X >= (unsigned)Wo)) return rgb;
+    if (pad == SE_CANVAS_CONSTANT && ((unsigned)Y >= (unsigned)Ho || (unsigned)X >= (unsigned)Wo)) return rgb;
     return src(fold(Y, Ho), fold(X, Wo));
   }
 };
@@ -87,10 +87,10 @@ __global__ void __launch_bounds__(256) canvas_map_kernel(CanvasMap cm, unsigned 
   if (cm.in && b + k < rb && (unsigned)Y < (unsigned)cm.Ho && xa + cm.ox >= 0 && xb + cm.ox < cm.Wo) {
     // one row, every pixel inside the oriented image: the source bytes are neighbours in ONE source row (bytes past `last` are
     // never stored)
-    const int sy = (cm.orient & SKEDIT_CANVAS_MIRROR_Y) ? cm.Hi - 1 - Y : Y;
+    const int sy = (cm.orient & SE_CANVAS_MIRROR_Y) ? cm.Hi - 1 - Y : Y;
     const unsigned char* row = cm.in + (size_t)sy * cm.Wi * C;
     const unsigned char* hi = row + (size_t)cm.Wi * C;
-    if (!(cm.orient & SKEDIT_CANVAS_MIRROR_X)) {
+    if (!(cm.orient & SE_CANVAS_MIRROR_X)) {
       v = load4_within(row + (ptrdiff_t)(xa + cm.ox) * C + (b - xa * C), row, hi) << sh;
     } else if (C == 1) {
       const int sx = cm.Wi - 1 - (xa + cm.ox);                        // xa's source; xa + j comes from sx - j
@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(256) canvas_turn_kernel(CanvasMap cm, unsigned
 
 hipError_t launch_canvas(const unsigned char* in, int Hi, int Wi, int C, unsigned char* out, int Hn, int Wn, int oy, int ox, int orient,
                          int pad, unsigned rgb, hipStream_t st) {
-  const bool turn = (orient & SKEDIT_CANVAS_TRANSPOSE) != 0;
+  const bool turn = (orient & SE_CANVAS_TRANSPOSE) != 0;
   const CanvasMap cm{in, Hi, Wi, C, turn ? Wi : Hi, turn ? Hi : Wi, oy, ox, orient, pad, rgb & (C == 1 ? 0xffu : 0xffffffu)};
   const long n = (long)C * Hn * Wn;
   // bytes: the output written once, and read at most as many

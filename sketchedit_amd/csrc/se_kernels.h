@@ -493,7 +493,7 @@ hipError_t launch_move_blend(unsigned char* frame, int Hi, int Wi, const unsigne
                              const unsigned char* sel, const unsigned char* lock, int by0, int bx0, int by1, int bx1, int dy, int dx, int flip,
                              void* ws, hipStream_t st);
 // the canvas of a session (include/sketchedit_canvas.h; se_canvas.hip): out (Hn,Wn,C) <- the rectangle at (oy, ox) of
-// in (Hi,Wi,C; NULL: zeros) under `orient`, folded by `pad` (SKEDIT_CANVAS_*; rgb: the constant's C bytes).  Any sizes >= 1 and any
+// in (Hi,Wi,C; NULL: zeros) under `orient`, folded by `pad` (SE_CANVAS_*; rgb: the constant's C bytes).  Any sizes >= 1 and any
 // alignment.  ONE launch: canvas_map without the transpose bit, canvas_turn (64 x 32 tiles through the LDS) with it.
 hipError_t launch_canvas(const unsigned char* in, int Hi, int Wi, int C, unsigned char* out, int Hn, int Wn, int oy, int ox, int orient,
                          int pad, unsigned rgb, hipStream_t st);

@@ -12,6 +12,12 @@ from fractions import Fraction
 
 import numpy as np
 
+from . import _lib
+# the limits and codes of include/*.h, from their one Python mirror
+from ._lib import (ADJUST_MAX_CLIP, ADJUST_MAX_COEF, ADJUST_MAX_OFFSET, BLEND_MAX_SIDE, CANVAS_CONSTANT, CANVAS_MAX_OFFSET, CANVAS_MAX_SIDE,   # noqa: F401
+                   COMBINE_INVERT, FEATHER_MAX_RADIUS, FILTER_MAX_CELL, FILTER_MAX_RADIUS, FILTER_ONE, LASSO_MAX_EDGES, MODIFY_MAX_RADIUS,
+                   MOVE_MAX_OFFSET, OUTLINE_MAX_CAP, SELECT_MAX_GROW, WARP_MAX_COEF, WARP_MAX_TRANSLATION)
+
 
 def _to_tensors(img, mask):
     """demo.py:40-56: RGB, sizes floored to multiples of 8, image to [-1, 1], mask > 0."""
@@ -267,13 +273,10 @@ def stroke_box(segs, frame_hw):
     return (max(lo(s[:, 1], s[:, 3]), 0), max(lo(s[:, 0], s[:, 2]), 0), min(hi(s[:, 1], s[:, 3]), Hi), min(hi(s[:, 0], s[:, 2]), Wi))
 
 
-LASSO_MAX_EDGES = 65536     # SE_LASSO_MAX_EDGES
-COMBINE_OPS = {"add": 0, "subtract": 1, "intersect": 2, "xor": 3}     # SE_COMBINE_*
-COMBINE_INVERT = 4
-MODIFY_OPS = {"expand": 0, "contract": 1, "smooth": 2}                  # SE_MODIFY_*
+COMBINE_OPS = {"add": _lib.COMBINE_ADD, "subtract": _lib.COMBINE_SUBTRACT, "intersect": _lib.COMBINE_INTERSECT, "xor": _lib.COMBINE_XOR}
+MODIFY_OPS = {"expand": _lib.MODIFY_EXPAND, "contract": _lib.MODIFY_CONTRACT, "smooth": _lib.MODIFY_SMOOTH}
 MODIFY_KINDS = ("expand", "contract", "border", "smooth")
 MODIFY_SIDES = ("inside", "outside", "both")
-MODIFY_MAX_RADIUS = 32       # SE_MODIFY_MAX_RADIUS
 
 
 def lasso_edges(rings, frame_hw):
@@ -384,11 +387,9 @@ def rings_svg_path(rings):
     return " ".join("M %d %d " % tuple(r[0]) + "".join("L %d %d " % tuple(q) for q in r[1:]) + "Z" for r in rings)
 
 
-MOVE_MAX_OFFSET = 16384      # SE_MOVE_MAX_OFFSET
-MOVE_FLIPS = {None: 0, "h": 1, "v": 2, "hv": 3}     # SE_MOVE_FLIP_X | SE_MOVE_FLIP_Y
+MOVE_FLIPS = {None: 0, "h": _lib.MOVE_FLIP_X, "v": _lib.MOVE_FLIP_Y, "hv": _lib.MOVE_FLIP_X | _lib.MOVE_FLIP_Y}
 MOVE_MIN_SIDE = 16           # the smallest side of a journal slot's rectangle
 MOVE_BLENDS = (None, "seamless")                    # move_selection's `blend`
-BLEND_MAX_SIDE = 2048        # SE_BLEND_MAX_SIDE
 
 
 def move_rect(box, offset, frame_hw):
@@ -414,10 +415,8 @@ def move_rect(box, offset, frame_hw):
     return None if ya is None or xa is None else (ya[0], xa[0], ya[1], xa[1])
 
 
-FILTER_ONE = 4096                    # SE_FILTER_ONE: the sum of a filter's taps, t[0] + 2 (t[1] + .. + t[R])
-FILTER_MAX_RADIUS = 32               # SE_FILTER_MAX_RADIUS
-FILTER_MAX_CELL = 64                 # SE_FILTER_MAX_CELL
-FILTER_MAX_AMOUNT = 4.0              # SE_FILTER_MAX_AMOUNT / 256: the strongest unsharp mask
+# (FILTER_ONE is the sum of a filter's taps, t[0] + 2 (t[1] + .. + t[R]))
+FILTER_MAX_AMOUNT = 4.0              # SE_FILTER_MAX_AMOUNT / 256: the strongest unsharp mask, a factor here (_lib's is in 1/256 units)
 FILTER_KINDS = ("blur", "box", "sharpen", "pixelate")
 
 
@@ -461,12 +460,9 @@ def filter_rect(box, radius, frame_hw):
 
 
 ADJUST_ONE = 4096                    # 1.0 in the Q12 of an adjustment's matrix
-ADJUST_MAX_COEF = 32768              # SE_ADJUST_MAX_COEF
-ADJUST_MAX_OFFSET = 1 << 20          # SE_ADJUST_MAX_OFFSET
-ADJUST_MAX_CLIP = 200                # SE_ADJUST_MAX_CLIP, per mille
 ADJUST_GREY = (1225, 2404, 467)      # the luma weights in Q12: a row of the matrix of saturation 0
-ADJUST_AUTO = {"levels": 0, "equalize": 1, "match": 2}      # SE_ADJUST_STRETCH, SE_ADJUST_EQUALIZE, SE_ADJUST_MATCH
-ADJUST_WHICH = {"channels": 0, "luma": 1}                   # SE_ADJUST_PER_CHANNEL, SE_ADJUST_LUMA
+ADJUST_AUTO = {"levels": _lib.ADJUST_STRETCH, "equalize": _lib.ADJUST_EQUALIZE, "match": _lib.ADJUST_MATCH}
+ADJUST_WHICH = {"channels": _lib.ADJUST_PER_CHANNEL, "luma": _lib.ADJUST_LUMA}
 
 
 def _adjust_number(v, lo, hi, what):
@@ -595,8 +591,6 @@ def _check_adjust_lut(lut):
 
 
 WARP_ONE = 1 << 16                   # 1.0 in the Q16 of a warp's inverse map
-WARP_MAX_COEF = 1 << 20              # SE_WARP_MAX_COEF
-WARP_MAX_TRANSLATION = 1 << 40       # SE_WARP_MAX_TRANSLATION
 WARP_MIN_SCALE, WARP_MAX_SCALE = 0.125, 8.0
 
 
@@ -702,11 +696,9 @@ def warp_rect(box, m, frame_hw):
 
 
 # ---- the canvas of a session (include/sketchedit_canvas.h) -----------------------------------------------------------
-CANVAS_ORIENTS = {None: 0, "h": 1, "v": 2, "180": 3, "transpose": 4, "ccw": 5, "cw": 6, "transverse": 7}      # SKEDIT_CANVAS_MIRROR_X | _MIRROR_Y | _TRANSPOSE
-CANVAS_PADS = {"edge": 0, "reflect": 1}          # SKEDIT_CANVAS_EDGE, SKEDIT_CANVAS_REFLECT
-CANVAS_CONSTANT = 2                              # SKEDIT_CANVAS_CONSTANT
-CANVAS_MAX_SIDE = 32768                          # SKEDIT_CANVAS_MAX_SIDE
-CANVAS_MAX_OFFSET = 1 << 20                      # SKEDIT_CANVAS_MAX_OFFSET
+_MX, _MY, _T = _lib.CANVAS_MIRROR_X, _lib.CANVAS_MIRROR_Y, _lib.CANVAS_TRANSPOSE
+CANVAS_ORIENTS = {None: 0, "h": _MX, "v": _MY, "180": _MX | _MY, "transpose": _T, "ccw": _T | _MX, "cw": _T | _MY, "transverse": _T | _MX | _MY}
+CANVAS_PADS = {"edge": _lib.CANVAS_EDGE, "reflect": _lib.CANVAS_REFLECT}
 CANVAS_FILLS = (None, "network")                 # extend_canvas' `fill`
 
 
@@ -892,7 +884,6 @@ def _check_encode(encode):
                      "or ('jpg', quality, '444' | '420', a bool: per-image Huffman tables) (got %r)" % (JPG_QUALITY, encode))
 
 
-FEATHER_MAX_RADIUS = 16                      # the largest radius of the feathered paste (include/sketchedit_feather.h)
 
 
 def _check_feather(feather):
@@ -978,7 +969,6 @@ def _edit_info(info, locked, work, undoable, feather=None):
 
 
 SELECT_PASSES = 8            # flood passes per library call, and per download of their `changed` words
-SELECT_MAX_GROW = 16         # SE_SELECT_MAX_GROW
 
 
 def tiles_box(tiles):
@@ -1032,7 +1022,6 @@ class Selection:
         return outline_rings(self.edges(first_cap))
 
 
-OUTLINE_MAX_CAP = 1 << 24     # SE_OUTLINE_MAX_CAP
 
 
 def _outline_records(be, plane, first_cap):
@@ -1065,7 +1054,6 @@ class _ModelBackend:
         return torch.device("cuda", self.model.engine().device)
 
     def upload(self, a):
-        from . import _lib
         return _lib.upload_u8(a, self._device())
 
     def run(self, frames, origins, sketches, h, w, commit, low_latency):
@@ -1193,7 +1181,7 @@ class _ModelBackend:
 
     def canvas(self, src, src_hw, out_hw, origin, orient, pad, rgb, tiles=False):
         """a NEW frame or plane, ONE launch: the rectangle `out_hw` at `origin` of `src` -- a frame, a plane, or None:
-        a plane of zeros of `src_hw` that is never read -- oriented by `orient` (0 .. 7) and padded by `pad` (SKEDIT_CANVAS_*) with
+        a plane of zeros of `src_hw` that is never read -- oriented by `orient` (0 .. 7) and padded by `pad` (SE_CANVAS_*) with
         the colour `rgb`.  tiles=True (a carried selection): -> (plane, box, count), the tile records of the result being the one
         download"""
         out = self.model.canvas_u8(src, out_hw, origin=origin, orient=orient, pad=pad, pad_rgb=rgb, src_hw=src_hw)
@@ -2874,7 +2862,6 @@ class BatchingServer:
         fused quantisation (the group's execution mode as _forward's), each result resized back to its raw size there."""
         import torch
         from PIL import Image
-        from . import _lib
         model = self.models[k]
         eng = model.engine()
         _, _, H, W = group[0][0]

@@ -144,7 +144,7 @@ def spec_blend(frame, lift, lift_rect, sel, lock, box, offset, flip, want_levels
 
 
 def workspace_bytes(box_h, box_w):
-    """sketchedit_move_blend_u8_workspace_bytes"""
+    """se_move_blend_u8_workspace_bytes"""
     if not (1 <= box_h <= MAX_SIDE and 1 <= box_w <= MAX_SIDE):
         return 0
     return sum(16 * h * w for h, w in level_sizes(box_h + 2, box_w + 2))
@@ -370,7 +370,7 @@ def _tiled_apply(mem, frame, Hi, Wi, lift, lift_rect, sel, lock, box, offset, fl
 
 
 def tiled_blend(mem, frame, Hi, Wi, lift, lift_rect, sel, lock, box, offset, flip, ws, ws_bytes):
-    """sketchedit_move_blend_u8's launches on `mem`, addresses for pointers -> the number of launches"""
+    """se_move_blend_u8's launches on `mem`, addresses for pointers -> the number of launches"""
     assert ws % 16 == 0 and ws_bytes >= workspace_bytes(box[2] - box[0], box[3] - box[1])
     d, e = rects(box, offset, (Hi, Wi))
     if d is None:

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from sketchedit_amd import _lib, serve
+import abi_util
 import adjust_util as A
 import lasso_util as L
 import move_util as M
@@ -762,10 +763,8 @@ def test_model_backend_adjust_calls():
 def test_abi_has_four_new_symbols_in_a_header_of_their_own():
     hdr = open(os.path.join(ROOT, "include", "sketchedit_adjust.h")).read()
     declared = re.findall(r"^(?:int|size_t)\s+(se_\w+)\(", hdr, re.M)
-    assert declared == _lib.ADJUST_SYMBOLS == ["se_adjust_u8", "se_adjust_hist_u8_workspace_bytes", "se_adjust_hist_u8", "se_adjust_lut_u8"]
-    others = (_lib.SYMBOLS + _lib.PNG_SYMBOLS + _lib.JPG_SYMBOLS + _lib.JPG2_SYMBOLS + _lib.FEATHER_SYMBOLS + _lib.FILL_SYMBOLS +
-              _lib.SELECT_SYMBOLS + _lib.LASSO_SYMBOLS + _lib.OUTLINE_SYMBOLS + _lib.MOVE_SYMBOLS + _lib.WARP_SYMBOLS + _lib.FILTER_SYMBOLS)
-    assert len(others) == 83 and not set(_lib.ADJUST_SYMBOLS) & set(others)
+    assert declared == _lib.abi_names("sketchedit_adjust.h") == ["se_adjust_u8", "se_adjust_hist_u8_workspace_bytes", "se_adjust_hist_u8", "se_adjust_lut_u8"]
+    others = [n for n in _lib.abi_names() if n not in declared]
     for name in others:                                               # the header refers to other families by DESIGN section
         assert not re.search(r"\b%s\b" % name, hdr), name
     for fam in ("se_filter", "se_move", "se_warp", "se_outline", "se_lasso", "se_select", "se_window"):
@@ -787,7 +786,7 @@ def test_abi_has_four_new_symbols_in_a_header_of_their_own():
     import ctypes
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
     lib = ctypes.CDLL(_lib.LIB_PATH)                                    # the built library, as the other host tests load it
-    for s in _lib.ADJUST_SYMBOLS:
+    for s in declared:
         getattr(lib, s)
     lib.se_adjust_hist_u8_workspace_bytes.restype = ctypes.c_size_t      # host only: no device is touched
     ws = lambda h, w: lib.se_adjust_hist_u8_workspace_bytes(h, w)       # noqa: E731
@@ -798,10 +797,7 @@ def test_abi_has_four_new_symbols_in_a_header_of_their_own():
         assert kernel_labels.label_of("void se::%s(unsigned char*, int)" % kernel) == label
         assert kernel_labels.label_of("%s(unsigned char*, int)" % kernel) == label
         assert label in set(kernel_labels.KERNEL_LABELS.values())
-    misc = open(os.path.join(_lib.CSRC, "se_misc.hip")).read()
-    enum = open(os.path.join(_lib.CSRC, "se_kernels.h")).read()
-    names = re.findall(r'"(\w+)"', re.search(r"static const char\* n\[PL_COUNT\] = \{(.*?)\};", misc, re.S).group(1))
-    labels = re.findall(r"PL_\w+", re.search(r"enum ProfLabel \{(.*?)\};", enum, re.S).group(1))
+    names, labels = abi_util.prof_labels()
     assert len(names) == len(labels) - 1 and labels[-1] == "PL_COUNT"
     i = names.index("adjust")
     assert names[i - 1:i + 5] == ["plane_combine", "adjust", "hist_tiles", "hist_sum", "adjust_lut", "outline_count"]      # between the two, not appended

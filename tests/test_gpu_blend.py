@@ -1,4 +1,4 @@
-"""GPU tests of the seamless move and clone: sketchedit_move_blend_u8 against the statement of tests/blend_util.py on whole
+"""GPU tests of the seamless move and clone: se_move_blend_u8 against the statement of tests/blend_util.py on whole
 buffers between sentinels, at every alignment, and EditSession.move_selection / clone_selection with blend="seamless" against a
 two-step route -- fill_selection of the grown selection on a twin session, then the statement applied on the host with the
 original pixels.  Every comparison is exact; every case with a rim asserts that the expected bytes are neither the hard drop's
@@ -75,7 +75,7 @@ def _p(t):
 
 
 def _blend(eng, F, P, rect, S, K, box, off, flip, work):
-    rc = eng.lib.sketchedit_move_blend_u8(eng.h, eng._stream(), _p(F), F.shape[0], F.shape[1], _p(P), rect[0], rect[1], rect[2], rect[3], _p(S), _p(K),
+    rc = eng.lib.se_move_blend_u8(eng.h, eng._stream(), _p(F), F.shape[0], F.shape[1], _p(P), rect[0], rect[1], rect[2], rect[3], _p(S), _p(K),
                                   box[0], box[1], box[2], box[3], off[0], off[1], flip, ctypes.c_void_p(work.ptr), work.n)
     assert rc == 0, eng.lib.se_last_error(eng.h).decode()
 
@@ -154,7 +154,7 @@ def test_refusals_enqueue_nothing(eng):
     need = B.workspace_bytes(box[2] - box[0], box[3] - box[1])
     wk = _Work(need)
     lib, h, st = eng.lib, eng.h, eng._stream()
-    assert lib.sketchedit_move_blend_u8_workspace_bytes(box[2] - box[0], box[3] - box[1]) == need
+    assert lib.se_move_blend_u8_workspace_bytes(box[2] - box[0], box[3] - box[1]) == need
     F, S, K, P = fb.view, sb.view, lb.view, pb.view
     by0, bx0, by1, bx1 = box
     ly0, lx0, lh, lw = rect
@@ -177,7 +177,7 @@ def test_refusals_enqueue_nothing(eng):
              (dict(K=mid, W=(mid + Hi * Wi - 1) // 16 * 16), "workspace overlaps lock_u8")]      # its last bytes
     for change, what in cases:
         a = dict(ok, **change)
-        rc = lib.sketchedit_move_blend_u8(h, st, _p(a["F"]), a["Hi"], a["Wi"], _p(a["P"]), a["ly0"], a["lx0"], a["lh"], a["lw"], _p(a["S"]), _p(a["K"]),
+        rc = lib.se_move_blend_u8(h, st, _p(a["F"]), a["Hi"], a["Wi"], _p(a["P"]), a["ly0"], a["lx0"], a["lh"], a["lw"], _p(a["S"]), _p(a["K"]),
                                   a["by0"], a["bx0"], a["by1"], a["bx1"], a["dy"], a["dx"], a["flip"], _p(a["W"]), a["wn"])
         assert rc != 0, (change, what)
         assert what in lib.se_last_error(h).decode(), (what, lib.se_last_error(h).decode())
@@ -185,9 +185,9 @@ def test_refusals_enqueue_nothing(eng):
     wide = torch.zeros((16, 2064, 3), dtype=torch.uint8, device="cuda")
     wsel, wslot = torch.ones((16, 2064), dtype=torch.uint8, device="cuda"), torch.zeros((16 * 6192 + 16,), dtype=torch.uint8, device="cuda")
     wp = wslot[(-wslot.data_ptr()) % 16:]
-    rc = lib.sketchedit_move_blend_u8(h, st, _p(wide), 16, 2064, _p(wp), 0, 0, 16, 2064, _p(wsel), None, 0, 0, 16, 2049, 0, 0, 0, ctypes.c_void_p(wk.ptr), 1 << 40)
+    rc = lib.se_move_blend_u8(h, st, _p(wide), 16, 2064, _p(wp), 0, 0, 16, 2064, _p(wsel), None, 0, 0, 16, 2049, 0, 0, 0, ctypes.c_void_p(wk.ptr), 1 << 40)
     assert rc != 0 and "side above 2048" in lib.se_last_error(h).decode()
-    assert lib.sketchedit_move_blend_u8_workspace_bytes(16, 2049) == 0 and lib.sketchedit_move_blend_u8_workspace_bytes(0, 5) == 0
+    assert lib.se_move_blend_u8_workspace_bytes(16, 2049) == 0 and lib.se_move_blend_u8_workspace_bytes(0, 5) == 0
     # the bindings refuse planes and lifts of another shape or size
     for call in (lambda: eng.move_blend_u8(F.view(-1), P, rect, S, None, box, (0, 0)), lambda: eng.move_blend_u8(F, P, rect, S.view(Wi, Hi), None, box, (0, 0)),
                  lambda: eng.move_blend_u8(F, P, rect, S, K.view(Wi, Hi), box, (0, 0)), lambda: eng.move_blend_u8(F, P[:-1], rect, S, None, box, (0, 0))):

@@ -93,7 +93,7 @@ def test_refusals_enqueue_nothing(eng):
              (dict(O=I.data_ptr() - 3 * Hn * Wn + 1), "overlaps")]
     for change, what in cases:
         a = dict(ok, **change)
-        rc = lib.skedit_canvas_u8(h, st, p(a["I"]), a["Hi"], a["Wi"], a["C"], p(a["O"]), a["Hn"], a["Wn"], a["oy"], a["ox"], a["o"], a["pad"], a["rgb"])
+        rc = lib.se_canvas_u8(h, st, p(a["I"]), a["Hi"], a["Wi"], a["C"], p(a["O"]), a["Hn"], a["Wn"], a["oy"], a["ox"], a["o"], a["pad"], a["rgb"])
         assert rc != 0, (change, what)
         assert what in lib.se_last_error(h).decode(), (what, lib.se_last_error(h).decode())
     # the binding refuses arrays of another shape

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_util
 from sketchedit_amd import _lib, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,7 +32,7 @@ def test_header_symbols_exported(built_lib):
     hdr = open(os.path.join(ROOT, "include", "sketchedit_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     declared = set(re.findall(r"\b(se_[a-z_A-Z0-9]+)\s*\(", hdr))
-    assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
+    assert declared == set(_lib.abi_names("sketchedit_hip.h")), declared ^ set(_lib.abi_names("sketchedit_hip.h"))
     for s in declared:
         assert getattr(built_lib, s) is not None
     built_lib.se_version.restype = ctypes.c_char_p
@@ -39,18 +40,11 @@ def test_header_symbols_exported(built_lib):
 
 
 def test_exported_c_names_are_the_declared_symbols(built_lib):
-    """The library's unmangled se_ names are the *_SYMBOLS lists of the binding, no more and no fewer: a helper shared between
+    """The library's unmangled se_ names are the entries of the binding's table, no more and no fewer: a helper shared between
     the host files stays a C++ name in namespace se, and every declared entry is defined in some file."""
-    import shutil
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path=os.path.join(rocm, "llvm", "bin"))
-    if nm is None:
-        pytest.skip("neither nm nor llvm-nm on this machine")
-    out = subprocess.check_output([nm, "-D", "--defined-only", _lib.LIB_PATH], text=True)
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("se_")}
-    lists = [getattr(_lib, n) for n in dir(_lib) if n == "SYMBOLS" or n.endswith("_SYMBOLS")]
-    declared = [s for lst in lists for s in lst]
-    assert len(declared) == len(set(declared)) >= len(_lib.SYMBOLS)
+    exported = abi_util.exported_names("se_")
+    declared = _lib.abi_names()
+    assert len(declared) == len(set(declared)) >= len(_lib.abi_names("sketchedit_hip.h"))
     assert exported == set(declared), exported ^ set(declared)
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from sketchedit_amd import _lib, serve
+import abi_util
 import lasso_util as L
 import modify_util as M
 import select_util as U
@@ -272,11 +273,8 @@ def test_model_backend_modify():
 def test_abi_has_one_new_symbol_in_a_header_of_its_own():
     hdr = open(os.path.join(ROOT, "include", "sketchedit_modify.h")).read()
     declared = re.findall(r"^(?:int|size_t)\s+(se_\w+)\(", hdr, re.M)
-    assert declared == _lib.MODIFY_SYMBOLS == ["se_plane_modify_u8"]
-    lists = {k: v for k, v in vars(_lib).items() if k.endswith("SYMBOLS") and k != "MODIFY_SYMBOLS"}
-    assert len(lists) == 13 and "SYMBOLS" in lists and "ADJUST_SYMBOLS" in lists
-    others = [s for v in lists.values() for s in v]
-    assert len(others) == 87 and not set(_lib.MODIFY_SYMBOLS) & set(others)
+    assert declared == _lib.abi_names("sketchedit_modify.h") == ["se_plane_modify_u8"]
+    others = [n for n in _lib.abi_names() if n not in declared]
     for name in others:                                               # the header refers to other families by DESIGN section
         assert name == "se_last_error" or not re.search(r"\b%s\b" % name, hdr), name      # (the conventions' error call apart)
     for name in sorted(os.listdir(os.path.join(ROOT, "include"))):
@@ -295,17 +293,14 @@ def test_abi_has_one_new_symbol_in_a_header_of_its_own():
     import ctypes
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
     lib = ctypes.CDLL(_lib.LIB_PATH)                                    # the built library, as the other host tests load it
-    for s in _lib.MODIFY_SYMBOLS:
+    for s in declared:
         getattr(lib, s)
     from sketchedit_amd import kernel_labels
     for kernel, label in (("modify_disc_kernel", "modify_disc"), ("modify_vote_kernel", "modify_vote")):
         assert kernel_labels.label_of("void se::%s(unsigned char const*, unsigned char*, int, int, int, int)" % kernel) == label
         assert kernel_labels.label_of("%s(unsigned char const*, unsigned char*, int, int, int, int)" % kernel) == label
         assert label in set(kernel_labels.KERNEL_LABELS.values())
-    misc = open(os.path.join(_lib.CSRC, "se_misc.hip")).read()
-    enum = open(os.path.join(_lib.CSRC, "se_kernels.h")).read()
-    names = re.findall(r'"(\w+)"', re.search(r"static const char\* n\[PL_COUNT\] = \{(.*?)\};", misc, re.S).group(1))
-    labels = re.findall(r"PL_\w+", re.search(r"enum ProfLabel \{(.*?)\};", enum, re.S).group(1))
+    names, labels = abi_util.prof_labels()
     assert len(names) == len(labels) - 1 and labels[-1] == "PL_COUNT"
     i = names.index("modify_disc")
     assert names[i - 1:i + 3] == ["select_grow", "modify_disc", "modify_vote", "lasso_fill"]           # behind the grow, not appended
