@@ -42,7 +42,11 @@ int se_fill(se_ctx* ctx, void* stream, const float* image, const float* sketch, 
  * fill plane (required, every entry); locks the same for the lock planes, an entry or the whole array may be NULL.  hs x ws is
  * the window in the frame, H x W the size of the forward (equal: the frame's own resolution).  rgb_out (B,H,W,3) and
  * mask_u8_out (B,H,W), 4-byte aligned, either may be NULL (the result then stays in the workspace).  The entry NEVER commits:
- * it leaves rgb and m8 where se_edit_window_locked_u8(commit = 0) leaves them and every paste takes them unchanged. */
+ * it leaves rgb and m8 where se_edit_window_locked_u8(commit = 0) leaves them and every paste takes them unchanged.
+ * With SE_FLAG_RAW_FINE in flags rgb (rgb_out, or its place in the workspace) holds at EVERY pixel the quantisation of netG's
+ * `fine` itself, (unsigned char)(int)(((f + 1) * 0.5f) * 255.f), not of the composite where(hole, fine, image): equal to the
+ * unflagged result on every hole pixel, the generator's own prediction on every other -- the lift a seamless paste needs on
+ * the hole's rim (sketchedit_blend.h).  mask_u8_out is as without the flag, and this is the one entry that honours it. */
 size_t se_fill_window_u8_workspace_bytes(se_ctx* ctx, int B, int hs, int ws, int H, int W);
 int se_fill_window_u8(se_ctx* ctx, void* stream, const se_window* wins, const unsigned char* const* holes, const unsigned char* const* locks,
                       int B, int hs, int ws, int H, int W, unsigned char* rgb_out, unsigned char* mask_u8_out, void* workspace,

@@ -66,7 +66,11 @@ enum {
    * the direct form also has 1), soft-mask max-abs 2.6e-5 vs 1.6e-5, for +1.7 % per step (11.10 -> 11.29 ms at 256x256
    * batch 32).  A caller with a real checkpoint whose logits cluster at the threshold sets it; honoured by se_inference,
    * se_inference_u8, se_netM_forward_ex.  INTEGRATION.md "Precision choice". */
-  SE_FLAG_CONSERVATIVE = 512
+  SE_FLAG_CONSERVATIVE = 512,
+  /* RAW_FINE (the window fill of sketchedit_fill.h only; every other entry clears the bit): the uint8 rgb result is the
+   * quantisation of netG's `fine` at every pixel instead of the composite's -- the same rule, the same last kernel in a
+   * compile-time form of its epilogue, no extra launch.  What a seamless paste of a fill reads on the hole's rim. */
+  SE_FLAG_RAW_FINE = 1024
 };
 
 /* replaces networks.create_network's .cuda() (models/networks/__init__.py:30-38) */

@@ -24,6 +24,7 @@ SE_NET_G, SE_NET_M = 0, 1
 RESAMPLE_LANCZOS, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2, 3   # se_resize_u8 filters = PIL.Image.Resampling values
 FLAG_USE_CAM, FLAG_POOL_MAX, FLAG_NO_MASK_CC, FLAG_NO_MASK_COARSE, FLAG_JOINT_TRAIN_INP = 1, 2, 4, 8, 16
 FLAG_LOW_LATENCY, FLAG_GRAPH, FLAG_PACKED_OUT, FLAG_BF16, FLAG_CONSERVATIVE = 32, 64, 128, 256, 512   # execution options (include/sketchedit_hip.h)
+FLAG_RAW_FINE = 1024   # se_fill_window_u8 only: rgb is the quantised `fine`, uncomposed
 # Which calls run in the low-latency mode unless the caller says otherwise: at most three 256x256 images' worth of pixels, or ONE
 # image of up to 512x512.  Re-measured on MI355X in round 6 (tools/ll_threshold.sh), low-latency vs default, after the default
 # mode learned to overlap netG's branches and the low-latency mode to keep the Winograd kernels where ONE image's grid still
@@ -1023,12 +1024,14 @@ class Engine:
                 raise SketchEditHipError("fill call: a %s plane is the frame's (Hi,Wi) uint8 plane" % what)
         return (ctypes.c_void_p * len(planes))(*[None if t is None else t.data_ptr() for t in planes])
 
-    def fill_window_u8(self, frames, origins, sketches, holes, locks, window_hw, H, W, flags, low_latency=None):
+    def fill_window_u8(self, frames, origins, sketches, holes, locks, window_hw, H, W, flags, low_latency=None, raw=False):
         """se_fill_window_u8: the fill of the (hs, ws) windows at origins[i] of resident frames with the forward at H x W (equal:
         the frame's own resolution), ONE library call.  holes[i]: the frame's (Hi,Wi) uint8 fill plane on the device, non-zero
         = fill; locks: a plane or None per request, or None; sketches: the window's (hs,ws) uint8 sketch or None per request,
         or None.  Never commits.  -> (rgb (B,H,W,3), mask_u8 (B,H,W)) on the device, mask_u8 255 in the hole: what the pastes
-        take, with the keep planes of fill_keep_u8 in place of the locks."""
+        take, with the keep planes of fill_keep_u8 in place of the locks.  raw (SE_FLAG_RAW_FINE): rgb is the quantisation of
+        netG's `fine` at every pixel, not of the composite -- equal in the hole, the generator's own prediction on its rim,
+        which is what a seamless paste (move_blend_u8) reads there; mask_u8 is the same."""
         import torch
         hs, ws = (int(v) for v in window_hw)
         B, dev = len(frames), frames[0].device if frames else None
@@ -1051,7 +1054,7 @@ class Engine:
         wsp = self._workspace_bytes(need)
         rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
         m8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False)
+        flags = (flags & 31) | self.exec_flags(B, H, W, low_latency, False) | (FLAG_RAW_FINE if raw else 0)
         if self.lib.se_fill_window_u8(self.h, self._stream(), wins, hp, lp, B, hs, ws, H, W, _ptr(rgb), _ptr(m8), _ptr(wsp),
                                       wsp.numel() // 16 * 16, flags):
             self._err("se_fill_window_u8")

@@ -108,7 +108,7 @@ unsigned char* rs_scratch(se_ctx* c, size_t bytes) {
 int inference_u8_locked(se_ctx* c, void* stream, const float* image, const float* sketch, unsigned char* rgb_out,
                         unsigned char* mask_u8_out, void* ws, size_t ws_bytes, int B, int H, int W, int flags, int tail_planes,
                         const unsigned char* lock8) {
-  flags &= ~(SE_FLAG_GRAPH | SE_FLAG_PACKED_OUT);
+  flags &= ~(SE_FLAG_GRAPH | SE_FLAG_PACKED_OUT | SE_FLAG_RAW_FINE);
   const size_t plane = ((size_t)B * H * W * 4 + 255) & ~(size_t)255;
   const size_t tail = (2 + (size_t)tail_planes) * plane;
   if (ws_bytes < tail) return fail(c, "workspace too small: %zu bytes", ws_bytes);
@@ -411,6 +411,7 @@ int se_netG_forward_taps(se_ctx* c, void* stream, const float* x, const float* x
   if (check_dims(c, B, H, W)) return 1;
   if (!x || !x2 || !mask || !mask2 || !guide || !fine_out || !ws) return fail(c, "null pointer argument");
   if (forward_enter(c)) return 1;
+  flags &= ~SE_FLAG_RAW_FINE;      // se_fill_window_u8 only
   const int nb = pass_size(c, B, H, W, flags);
   if (!nb) return 1;
   if (taps && nb < B) return fail(c, "se_netG_forward_taps: %d images do not fit one pass (%d)", B, nb);
@@ -491,6 +492,7 @@ int se_inference(se_ctx* c, void* stream, const float* image, const float* sketc
   if (check_dims(c, B, H, W)) return 1;
   if (!image || !sketch || !composed_out || (!mask_out && !(flags & SE_FLAG_PACKED_OUT)) || !ws) return fail(c, "null pointer argument");
   if (forward_enter(c)) return 1;
+  flags &= ~SE_FLAG_RAW_FINE;      // se_fill_window_u8 only
   // (SE_TEST_POISON set: uncaptured, and nothing enters the graph cache -- the fills belong to the test aid, not to a graph)
   if (!(flags & SE_FLAG_GRAPH) || c->prof.on || poison_byte() != 0)
     return enqueue_inference(c, stream, image, sketch, composed_out, mask_out, hard_out, maskim_out, coarse_out, fine_out, ws,
@@ -545,7 +547,7 @@ int se_inference_locked(se_ctx* c, void* stream, const float* image, const float
   if (!image || !sketch || !composed_out || (!mask_out && !(flags & SE_FLAG_PACKED_OUT)) || !ws) return fail(c, "null pointer argument");
   if (forward_enter(c)) return 1;
   return enqueue_inference(c, stream, image, sketch, composed_out, mask_out, hard_out, maskim_out, coarse_out, fine_out, ws,
-                           ws_bytes, B, H, W, flags & ~SE_FLAG_GRAPH, lock_u8);
+                           ws_bytes, B, H, W, flags & ~(SE_FLAG_GRAPH | SE_FLAG_RAW_FINE), lock_u8);
 }
 
 int se_inference_u8(se_ctx* c, void* stream, const float* image, const float* sketch, unsigned char* rgb_out,

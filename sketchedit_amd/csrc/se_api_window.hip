@@ -484,6 +484,7 @@ namespace {
 
 // the passes of a netG-only forward (as se_netG_forward_taps plans them): `hole` (B,H,W) fp32 is read as hard and as soft
 // mask; `tail` bytes at the end of the workspace are the caller's.  rgb8 / m8 (either may be null): the fused uint8 outputs.
+// SE_FLAG_RAW_FINE in flags (se_fill_window_u8 alone lets it through): rgb8 is the quantised `fine`, uncomposed.
 int fill_passes(se_ctx* c, void* stream, const float* image, const float* sketch, const float* hole, float* composed_out,
                 float* coarse_out, float* fine_out, unsigned char* rgb8, unsigned char* m8, void* ws, size_t ws_bytes, size_t tail, int B,
                 int H, int W, int flags) {
@@ -527,7 +528,7 @@ int se_fill(se_ctx* c, void* stream, const float* image, const float* sketch, co
   if (!aligned_to(hole_u8, 16) || !aligned_to(lock_u8, 16) || !aligned_to(hard_out, 16)) return fail(c, "hole_u8 / lock_u8 / hard_out must be 16-byte aligned");
   if (!aligned_to(ws, 256) || (ws_bytes & 15)) return fail(c, "workspace must be 256-byte aligned and workspace_bytes a multiple of 16");
   if (forward_enter(c)) return 1;
-  flags &= ~(SE_FLAG_GRAPH | SE_FLAG_PACKED_OUT);
+  flags &= ~(SE_FLAG_GRAPH | SE_FLAG_PACKED_OUT | SE_FLAG_RAW_FINE);
   // the hole plane and the zero sketch of a call without one live at the end of the workspace for the whole call
   const size_t plane = pad256((size_t)B * H * W * 4), tail = 2 * plane;
   if (ws_bytes < tail) return fail(c, "workspace too small: %zu bytes", ws_bytes);

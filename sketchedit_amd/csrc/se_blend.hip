@@ -10,12 +10,13 @@
 //                row: UNKNOWN where its own byte is set; KNOWN where it is not, a neighbour's is and the lift holds src(p) -- there it
 //                reads F[p] and P[src(p)]; OUT otherwise.  Every record of level 0's first buffer is written.
 //  blend_pull:   one lane per cell of level l: its up to four children of level l - 1's first buffer -> level l's first buffer.
-//  blend_relax:  a workgroup stages RX_H x RX_W = 32 x 80 cells in LDS, cells outside the grid as OUT; UNKNOWN cells take the
-//                parent's value in a level's first launch.  It runs `sweeps` red-black sweeps there and writes the cells `halo`
+//  blend_relax:  a workgroup stages the cells of its RX_H x RX_W = 32 x 80 rectangle that lie inside the grid in LDS (the others are
+//                OUT and are neither written nor read); UNKNOWN cells take the parent's value in a level's first launch.  It runs `sweeps` red-black sweeps there and writes the cells `halo`
 //                inside the staged rectangle.  Two forms, one kernel: halo 8, 4 sweeps, the grid the level's 64 x 16 tiles (a
 //                half-sweep lets a wrong value travel one cell, so after 8 half-sweeps the cells 8 inside the staged edge are
 //                what global sweeps give them: DESIGN.md 6x); halo 0, all J_l sweeps, ONE workgroup, where the level is at most
-//                32 x 80 cells.  A half-sweep reads cells of the other parity only, so its lanes race on nothing.
+//                32 x 80 cells.  A half-sweep reads cells of the other parity only, so its lanes race on nothing.  A block whose
+//                half-sweep has at most 64 candidates runs its sweeps in one wave, without a workgroup barrier.
 //  blend_apply:  move_drop_kernel<false>'s walk over D's tiles and its store (store_targets: one writer per byte): the lift's bytes
 //                plus the membrane of level 0.
 #include "../../include/sketchedit_blend.h"
@@ -134,57 +135,84 @@ __global__ void __launch_bounds__(256) blend_pull_kernel(const uint2* __restrict
   out[t] = s.n ? s.mean(ST_KNOWN) : make_cell(0u, 0u, 0u, unknown ? ST_UNKNOWN : ST_OUT);
 }
 
+// One red-black sweep's half of parity `par` over the staged cells [i0, i1) x [j0, j1): `cells` = (i1 - i0) ceil((j1 - j0) / 2)
+// candidates, `stride` lanes.  A neighbour outside that rectangle is outside the grid, OUT by definition, and is never read.
+DEVFN void relax_half(uint2* s, int tid, int stride, int cells, int half_w, int i0, int i1, int j0, int j1, int phase) {
+  for (int t = tid; t < cells; t += stride) {
+    const int ii = t / half_w, jj = t - ii * half_w;
+    const int i = i0 + ii;
+    const int j = j0 + 2 * jj + ((phase + i) & 1);
+    if (j >= j1) continue;
+    const int c = i * RX_W + j;
+    const uint2 r = s[c];
+    if (cell_state(r) != ST_UNKNOWN) continue;
+    Sum3 n;
+    if (i > i0) { const uint2 v = s[c - RX_W]; if (cell_state(v) != ST_OUT) n.add(v); }
+    if (i < i1 - 1) { const uint2 v = s[c + RX_W]; if (cell_state(v) != ST_OUT) n.add(v); }
+    if (j > j0) { const uint2 v = s[c - 1]; if (cell_state(v) != ST_OUT) n.add(v); }
+    if (j < j1 - 1) { const uint2 v = s[c + 1]; if (cell_state(v) != ST_OUT) n.add(v); }
+    if (n.n) s[c] = n.mean(ST_UNKNOWN);
+  }
+}
+
 // `sweeps` sweeps of the h x w level on the staged rectangle whose corner is the tile's less `halo`; first: UNKNOWN cells start
-// from the parent's value (parent == nullptr: from U_ZERO) instead of their own
+// from the parent's value (parent == nullptr: from U_ZERO) instead of their own.
+// Only the staged cells INSIDE the grid are walked -- rows [i0, i1), columns [j0, j1) of the staged rectangle -- by the stage, the
+// half-sweeps and the write-out alike.  The cells outside are OUT in the statement and never change; here they are NEVER READ (a
+// neighbour test stops at the rectangle's own edge) and so are not initialised either.  Where a half-sweep has at most 64
+// candidates (the coarse levels: the whole form, one workgroup) wave 0 alone sweeps, the other waves leave behind the stage's
+// barrier, and the half-sweeps are ordered by the wave's own program order on the LDS: a wavefront-scope fence pair keeps the
+// compiler from moving an LDS access across it, and no workgroup barrier is executed.  Every trip count is a function of h, w and
+// the block's index.
 __global__ void __launch_bounds__(256) blend_relax_kernel(const uint2* __restrict__ src, uint2* __restrict__ dst, const uint2* __restrict__ parent,
                                                           int h, int w, int pw, int halo, int sweeps, int first) {
   __shared__ uint2 s[RX_H * RX_W];
   const int tid = threadIdx.x;
   const int gy0 = blockIdx.y * (RX_H - 2 * halo) - halo, gx0 = blockIdx.x * (RX_W - 2 * halo) - halo;      // the staged corner
+  const int i0 = max(0, -gy0), i1 = min(RX_H, h - gy0), j0 = max(0, -gx0), j1 = min(RX_W, w - gx0);      // ... and the grid's part of it
+  const int nh = i1 - i0, nw = j1 - j0;
+  if (nh <= 0 || nw <= 0) return;                          // (no block of either form: its tile holds a cell of the grid)
   // ---- stage
-  for (int t = tid; t < RX_H * RX_W; t += 256) {
-    const int i = t / RX_W, j = t - i * RX_W;
+  for (int t = tid; t < nh * nw; t += 256) {
+    const int ii = t / nw, i = i0 + ii, j = j0 + (t - ii * nw);
     const int gy = gy0 + i, gx = gx0 + j;
-    uint2 r = make_cell(0u, 0u, 0u, ST_OUT);
-    if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
-      r = src[(size_t)gy * w + gx];
-      if (first && cell_state(r) == ST_UNKNOWN) {
-        if (parent) {
-          const uint2 q = parent[(size_t)(gy >> 1) * pw + (gx >> 1)];
-          r = make_uint2(q.x, (q.y & 0xffffu) | (ST_UNKNOWN << 16));
-        } else {
-          r = make_cell(U_ZERO, U_ZERO, U_ZERO, ST_UNKNOWN);
-        }
+    uint2 r = src[(size_t)gy * w + gx];
+    if (first && cell_state(r) == ST_UNKNOWN) {
+      if (parent) {
+        const uint2 q = parent[(size_t)(gy >> 1) * pw + (gx >> 1)];
+        r = make_uint2(q.x, (q.y & 0xffffu) | (ST_UNKNOWN << 16));
+      } else {
+        r = make_cell(U_ZERO, U_ZERO, U_ZERO, ST_UNKNOWN);
       }
     }
-    s[t] = r;
+    s[i * RX_W + j] = r;
   }
   __syncthreads();
-  // ---- sweep: the half-sweep of parity 0, then of parity 1, of the GRID's coordinates
+  // ---- sweep: the half-sweep of parity 0, then of parity 1, of the GRID's coordinates: staged (i, j) has parity (gy0 + i + gx0 + j) & 1
+  const int half_w = (nw + 1) / 2, cells = nh * half_w;
+  const int phase0 = gy0 + gx0 + j0;
+  const bool one_wave = cells <= 64;                       // block-uniform: one wave covers a half-sweep
+  if (one_wave && tid >= 64) return;                       // (behind the stage's barrier; wave 0 executes no other)
+  const int stride = one_wave ? 64 : 256;
   for (int sw = 0; sw < sweeps; ++sw) {
     for (int par = 0; par < 2; ++par) {
-      for (int t = tid; t < RX_H * (RX_W / 2); t += 256) {
-        const int i = t / (RX_W / 2), jj = t - i * (RX_W / 2);
-        const int j = 2 * jj + ((par + gy0 + i + gx0) & 1);
-        const int c = i * RX_W + j;
-        const uint2 r = s[c];
-        if (cell_state(r) != ST_UNKNOWN) continue;
-        Sum3 n;
-        if (i > 0) { const uint2 v = s[c - RX_W]; if (cell_state(v) != ST_OUT) n.add(v); }
-        if (i < RX_H - 1) { const uint2 v = s[c + RX_W]; if (cell_state(v) != ST_OUT) n.add(v); }
-        if (j > 0) { const uint2 v = s[c - 1]; if (cell_state(v) != ST_OUT) n.add(v); }
-        if (j < RX_W - 1) { const uint2 v = s[c + 1]; if (cell_state(v) != ST_OUT) n.add(v); }
-        if (n.n) s[c] = n.mean(ST_UNKNOWN);
+      relax_half(s, tid, stride, cells, half_w, i0, i1, j0, j1, phase0 + par);
+      if (one_wave) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      } else {
+        __syncthreads();
       }
-      __syncthreads();
     }
   }
-  // ---- the cells `halo` inside
-  const int th = RX_H - 2 * halo, tw = RX_W - 2 * halo;
-  for (int t = tid; t < th * tw; t += 256) {
-    const int i = t / tw + halo, j = t % tw + halo;
-    const int gy = gy0 + i, gx = gx0 + j;
-    if (gy < h && gx < w) dst[(size_t)gy * w + gx] = s[i * RX_W + j];
+  // ---- the cells `halo` inside, by the lanes that swept them
+  const int a0 = max(i0, halo), a1 = min(i1, RX_H - halo), b0 = max(j0, halo), b1 = min(j1, RX_W - halo);
+  const int ah = a1 - a0, aw = b1 - b0;
+  if (ah <= 0 || aw <= 0) return;
+  for (int t = tid; t < ah * aw; t += stride) {
+    const int ii = t / aw, i = a0 + ii, j = b0 + (t - ii * aw);
+    dst[(size_t)(gy0 + i) * w + (gx0 + j)] = s[i * RX_W + j];
   }
 }
 

@@ -283,6 +283,9 @@ struct SmallConvParams {
   unsigned char* m8;   // (B,H,W)   uint8 = trunc(soft mask * 255)
   // mode 0: (B,H,W) uint8 lock plane of an editing session (may be null): the mask is 0 where it is non-zero
   const unsigned char* lock;
+  // mode 3 with rgb8 (SE_FLAG_RAW_FINE): rgb8 = trunc((fine + 1) / 2 * 255), the tanh output uncomposed, at
+  // every pixel; composed and m8 are unchanged.  The kernel's RAW form; any other use is an invalid value.
+  int raw_fine;
 };
 hipError_t launch_small_conv(const SmallConvParams& p, hipStream_t st);
 

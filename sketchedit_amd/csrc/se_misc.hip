@@ -159,7 +159,9 @@ ProfScope::~ProfScope() {
 //     vertical neighbours come out of the same L2.
 // SR = output rows per lane (a ragged last strip is masked): 4, or 2 for calls of one or two small images, whose 4-row
 // strips would occupy only a quarter of the CUs (one 256x256 image: 64 blocks)
-template <int COUT, bool BF16, int SR>
+// RAW (mode 3, COUT == 3 only; SE_FLAG_RAW_FINE): rgb8 is the quantised tanh output itself, not the
+// composite's.  A compile-time form, so that the default form's code is what it was; composed and m8 are as without it.
+template <int COUT, bool BF16, int SR, bool RAW = false>
 __global__ __launch_bounds__(256) void small_conv_kernel(const SmallConvParams p) {
   const int HW = p.H * p.W;
   const int strips = (p.H + SR - 1) / SR;
@@ -290,7 +292,7 @@ __global__ __launch_bounds__(256) void small_conv_kernel(const SmallConvParams p
           const float v = t[c] * m + im * (1.f - m);                              // editline2_model.py:132
           if (p.composed) p.composed[cb + (long)c * HW + rem] = v;
           // test.py:25-27: (x + 1) / 2 * 255 -> uint8, same fp32 operation order, truncation, no clamp; HWC as test.py:35
-          if (p.rgb8) p.rgb8[idx * 3 + c] = (unsigned char)(int)(((v + 1.f) * 0.5f) * 255.f);
+          if (p.rgb8) p.rgb8[idx * 3 + c] = (unsigned char)(int)((((RAW ? t[c] : v) + 1.f) * 0.5f) * 255.f);
         }
         if (p.m8) p.m8[idx] = (unsigned char)(int)(m * 255.f);
       }
@@ -329,11 +331,20 @@ hipError_t launch_small_conv(const SmallConvParams& p0, hipStream_t st) {
       if (small) hipLaunchKernelGGL((small_conv_kernel<CO, BF, 2>), dim3(grid), dim3(256), 0, st, p);                 \
       else hipLaunchKernelGGL((small_conv_kernel<CO, BF, 4>), dim3(grid), dim3(256), 0, st, p);                       \
     } while (0)
-    if (p.cout == 1 && !p.bf16) SE_SC_LAUNCH(1, false);
+#define SE_SC_LAUNCH_RAW(BF)                                                                                         \
+    do {                                                                                                              \
+      if (small) hipLaunchKernelGGL((small_conv_kernel<3, BF, 2, true>), dim3(grid), dim3(256), 0, st, p);            \
+      else hipLaunchKernelGGL((small_conv_kernel<3, BF, 4, true>), dim3(grid), dim3(256), 0, st, p);                  \
+    } while (0)
+    if (p.raw_fine && (p.cout != 3 || p.mode != 3 || !p.rgb8)) return hipErrorInvalidValue;
+    if (p.raw_fine && !p.bf16) SE_SC_LAUNCH_RAW(false);
+    else if (p.raw_fine) SE_SC_LAUNCH_RAW(true);
+    else if (p.cout == 1 && !p.bf16) SE_SC_LAUNCH(1, false);
     else if (p.cout == 3 && !p.bf16) SE_SC_LAUNCH(3, false);
     else if (p.cout == 1) SE_SC_LAUNCH(1, true);
     else if (p.cout == 3) SE_SC_LAUNCH(3, true);
     else return hipErrorInvalidValue;
+#undef SE_SC_LAUNCH_RAW
 #undef SE_SC_LAUNCH
   }
   return hipGetLastError();

@@ -345,7 +345,7 @@ Act decoder(Plan& P, const std::string& p, Act& in, const float* src1 = nullptr,
 
 int small(Plan& P, const char* name, Act& in, int mode, float* out_nchw, float* hard, const float* img,
           const float* mask, float* xnow, float* composed, int no_mask_coarse, long packed_bs = 0,
-          const unsigned char* lock = nullptr) {
+          const unsigned char* lock = nullptr, bool raw_fine = false) {
   if (P.rc) return P.rc;
   se_ctx* c = P.c;
   if (!c->dry) {
@@ -358,6 +358,7 @@ int small(Plan& P, const char* name, Act& in, int mode, float* out_nchw, float* 
     sp.mode = mode; sp.out_nchw = out_nchw; sp.hard = hard; sp.img = img; sp.mask = mask; sp.xnow = xnow;
     sp.composed = composed; sp.no_mask_coarse = no_mask_coarse;
     if (mode == 3) { sp.rgb8 = c->rgb8; sp.m8 = c->m8; }
+    if (mode == 3 && raw_fine && sp.rgb8) sp.raw_fine = 1;      // SE_FLAG_RAW_FINE: the kernel's RAW form
     if (mode == 0) sp.lock = lock;
     if (packed_bs) {      // SE_FLAG_PACKED_OUT: soft mask and composite live in one (B,4,H,W) buffer
       if (mode == 0) sp.out_bs = packed_bs;
@@ -485,7 +486,8 @@ int plan_netG(se_ctx* c, const float* x, const float* x2, const float* mask, con
   P.free(xnow);                                         // read by both branches: released after the join
   Act d2 = decoder(P, "allconv", hallu, pm.p, 96, 0);   // cat([x_hallu, pm]) :211 is virtual
   P.free(pm);
-  small(P, "allconv17", d2, 3, fine_out, nullptr, x, soft_mask, nullptr, soft_mask ? composed_out : nullptr, 0, packed_bs);
+  small(P, "allconv17", d2, 3, fine_out, nullptr, x, soft_mask, nullptr, soft_mask ? composed_out : nullptr, 0, packed_bs, nullptr,
+        (flags & SE_FLAG_RAW_FINE) != 0);
   c->rgb8 = nullptr; c->m8 = nullptr;
   return P.rc;
 }

@@ -185,11 +185,12 @@ class EditLine2Model(torch.nn.Module):
                                    low_latency=self._mode_for(image.shape[0], image.shape[2], image.shape[3], low_latency))
         return r if visualize else r["composed"]
 
-    def fill_window_u8(self, frames, origins, sketches, holes, H, W, low_latency=None, work_hw=None, locks=None):
+    def fill_window_u8(self, frames, origins, sketches, holes, H, W, low_latency=None, work_hw=None, locks=None, raw=False):
         """The fill of windows of resident frames (serve.EditSession.fill is the caller-facing form): as
         edit_window_u8(commit=False) with the hole taken from holes[i], the frame's (Hi,Wi) uint8 fill plane ON THE DEVICE,
         instead of netM.  sketches[i]: the window's (H,W) uint8 sketch or None; sketches may be None.  -> (rgb, mask_u8) on the
-        device, at the working size with work_hw; nothing is pasted (Engine.fill_window_u8)."""
+        device, at the working size with work_hw; nothing is pasted (Engine.fill_window_u8).  raw: rgb is netG's own prediction
+        at every pixel, uncomposed."""
         if self.training:
             raise NotImplementedError("call model.eval() first: only the eval branch of generate_fake exists here")
         dev = torch.device("cuda", self.opt.gpu_ids[0])
@@ -197,7 +198,7 @@ class EditLine2Model(torch.nn.Module):
         Hw, Ww = (int(v) for v in work_hw) if work_hw is not None else (H, W)
         with torch.no_grad():
             return self.engine().fill_window_u8(frames, origins, sks, holes, locks, (H, W), Hw, Ww, _lib.flags_from_opt(self.opt),
-                                                low_latency=self._mode_for(len(frames), Hw, Ww, low_latency))
+                                                low_latency=self._mode_for(len(frames), Hw, Ww, low_latency), raw=raw)
 
     def fill_keep_u8(self, frames, origins, holes, locks, window_hw, keeps=None):
         """The keep planes a fill's paste takes in place of the locks: 255 where holes[i] is 0 or locks[i] is

@@ -954,6 +954,31 @@ def _paste_windows(be, frames, origins, window_hw, work, locks, rgb, m8):
         be.paste(frames, origins, rgb, m8)
 
 
+def _check_blend(blend, feather, be):
+    """-> whether a fill is pasted seamlessly; its refusals, all in front of the first backend call"""
+    if not (blend is None or isinstance(blend, str)) or blend not in MOVE_BLENDS:
+        raise ValueError("blend is None or 'seamless' (got %r)" % (blend,))
+    if blend is None:
+        return False
+    if feather is not None:
+        raise ValueError("blend=%r and feather=%r are two edge rules for one paste: give one" % (blend, feather))
+    if not all(callable(getattr(be, name, None)) for name in ("move_blend", "fill_lift")):
+        raise NotImplementedError("this backend has no move_blend / fill_lift: blend=%r needs the seamless drop (DESIGN.md 6x, 6z)" % (blend,))
+    return True
+
+
+def _blend_box(box, win):
+    """the box a seamless fill hands to the membrane: `box` (y0, x0, y1, x1) cut to the window -> it, or () where they do not
+    meet (nothing is a target: no launch); ValueError for a side above BLEND_MAX_SIDE"""
+    y0, x0, h, w = win
+    b = (max(box[0], y0), max(box[1], x0), min(box[2], y0 + h), min(box[3], x0 + w))
+    if b[0] >= b[2] or b[1] >= b[3]:
+        return ()
+    if max(b[2] - b[0], b[3] - b[1]) > BLEND_MAX_SIDE:
+        raise ValueError("blend='seamless' takes a region whose box inside the window has sides of at most %d (got %r)" % (BLEND_MAX_SIDE, b))
+    return b
+
+
 def _edit_info(info, locked, work, undoable, feather=None):
     """an edit's `info` with what only some sessions report: locked (a lock plane), work (max_side), undoable (history),
     feather (a feathered paste)"""
@@ -1089,12 +1114,23 @@ class _ModelBackend:
         request, or None"""
         self.model.window_paste_feather_u8(frames, origins, locks, window_hw, radius, rgb, m8)
 
-    def run_fill(self, frames, origins, sketches, holes, locks, window_hw, work_hw, low_latency):
+    def run_fill(self, frames, origins, sketches, holes, locks, window_hw, work_hw, low_latency, raw=False):
         """the fill of a group: holes[i] = the frame's fill plane on the device, sketches[i] the window's sketch
         or None, locks a plane or None per request, or None; never commits and downloads nothing.  -> (rgb, mask_u8), at the
-        working size `work_hw` if that is not None"""
+        working size `work_hw` if that is not None.  raw: rgb is the generator's own prediction at every pixel,
+        not the composite -- the lift of a seamless paste"""
         return self.model.fill_window_u8(frames, origins, sketches, holes, window_hw[0], window_hw[1], low_latency=low_latency,
-                                         work_hw=work_hw, locks=locks)
+                                         work_hw=work_hw, locks=locks, raw=raw)
+
+    def fill_lift(self, rgb, window_hw):
+        """the raw patch of ONE fill, run_fill(raw=True)'s (1,H,W,3), as the lift move_blend takes for the window:
+        resized to the window's (h, w) with Pillow's BICUBIC when it is at a working size (Engine.resize_u8), its rows at a
+        journal slot's pitch -- as it is where 3 w is a multiple of 16, else through the journal's save of the patch itself"""
+        h, w = (int(v) for v in window_hw)
+        eng = self.model.engine()
+        if tuple(rgb.shape[1:3]) != (h, w):
+            rgb = eng.resize_u8(rgb, (h, w))
+        return rgb[0].view(h, 3 * w) if (3 * w) % 16 == 0 else eng.window_save_u8([rgb[0]], [(0, 0)], (h, w))[0]
 
     def fill_keep(self, frames, origins, holes, locks, window_hw):
         """the keep planes of a fill's paste: what paste_locked / paste_feather take in place of the locks"""
@@ -1744,15 +1780,24 @@ class EditSession:
             return self._check_window(window, max_side is not None)
         return choose_window(box, self.frame_hw, margin=margin)
 
-    def _fill_steps(self, fill_plane, crop, win, low_latency, max_side, feather, journal):
+    def _fill_steps(self, fill_plane, crop, win, low_latency, max_side, feather, journal, blend=None):
         """The steps of a fill that change the frame, with the session's lock held: keep plane, the forward, the journal's save
         when `journal`, ONE paste; no download in between.  The caller owns the journal entry.
+        `blend`: None, or _blend_box's result -- then the forward hands out the generator's own prediction, its
+        lift is made, and behind the same save the membrane's drop at offset 0 replaces keep plane and paste.
         -> (slot or None, work, planes)"""
         be = self.backend
         y0, x0, h, w = win
         frames, origins = [self._frame], [(y0, x0)]
         planes = None if self._lock_plane is None else [self._lock_plane]
         work = choose_working_size((h, w), max_side) if max_side is not None else None
+        if blend is not None:
+            rgb, _ = be.run_fill(frames, origins, [crop], [fill_plane], planes, (h, w), work, low_latency, raw=True)
+            lift = be.fill_lift(rgb, (h, w))
+            slot = be.save(frames, origins, (h, w))[0] if journal else None
+            if blend:
+                be.move_blend(self._frame, lift, win, fill_plane, self._lock_plane, blend, (0, 0), MOVE_FLIPS[None])
+            return slot, work, planes
         keep = be.fill_keep(frames, origins, [fill_plane], planes, (h, w))
         rgb, m8 = be.run_fill(frames, origins, [crop], [fill_plane], planes, (h, w), work, low_latency)
         slot = be.save(frames, origins, (h, w))[0] if journal else None
@@ -1762,19 +1807,25 @@ class EditSession:
             be.paste_locked(frames, origins, keep, (h, w), rgb, m8)
         return slot, work, planes
 
-    def _fill(self, fill_plane, crop, win, low_latency, max_side, encode, feather):
+    def _fill(self, fill_plane, crop, win, low_latency, max_side, encode, feather, blend=None):
         """The device part of fill and fill_strokes, with the session's lock held: `fill_plane` the frame-sized plane and `crop`
         the window's sketch (or None), both on the device.  Keep plane, the forward, the journal's save, ONE paste, the
-        patch: no download in between."""
+        patch: no download in between.  `blend`: None, or _blend_box of the region's box for a seamless paste (_fill_steps)."""
         be = self.backend
         y0, x0, h, w = win
         frames = [self._frame]
-        slot, work, planes = self._fill_steps(fill_plane, crop, win, low_latency, max_side, feather, self._journals(h, w))
+        if blend is None:
+            slot, work, planes = self._fill_steps(fill_plane, crop, win, low_latency, max_side, feather, self._journals(h, w))
+        else:
+            slot, work, planes = self._fill_steps(fill_plane, crop, win, low_latency, max_side, feather, self._journals(h, w), blend)
         undoable = self._record(win, slot) if self.history > 0 else None
         patch = be.crop(self._frame, y0, x0, h, w) if encode is None else _encoded(be, encode, frames, [win])[0]
-        return patch, (x0, y0), _edit_info(dict(window=win, fill=True), planes is not None, work, undoable, feather)
+        info = _edit_info(dict(window=win, fill=True), planes is not None, work, undoable, feather)
+        if blend is not None:
+            info["blend"] = "seamless"
+        return patch, (x0, y0), info
 
-    def fill(self, mask, sketch=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None, feather=None):
+    def fill(self, mask, sketch=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None, feather=None, blend=None):
         """One fill: "paint over this, fill it in".  `mask`: (Hi,Wi), a uint8 or bool array or a PIL 'L' image,
         non-zero = fill; uploaded once per call as 0 / 255.  `sketch`: an optional FULL-SIZE sketch that guides the fill, used
         as given (not masked by the hole).  netG alone runs, on the hole mask & ~lock: there is no mask predictor, no
@@ -1783,9 +1834,20 @@ class EditSession:
         (set_lock) is 0, both tested in frame space: at any scale only painted, unlocked pixels can change.
         `max_side`, `encode` and `feather` as in `edit`; with history on the call is ONE undo step.
         -> (patch, (x0, y0), info) in `edit`'s shape, info = dict(window, fill=True) plus work / undoable / locked / feather
-        where `edit` reports them.  ValueError for an all-zero mask, a mask or sketch of another size, a bad window."""
+        where `edit` reports them.  ValueError for an all-zero mask, a mask or sketch of another size, a bad window.
+        `blend` = "seamless" (None: everything above): the fill keeps its detail and takes the local colour of the
+        frame at its rim.  The forward hands out P, the generator's OWN prediction over the whole window (at a working size:
+        its BICUBIC resize to the window), and the new frame is the membrane's drop of include/sketchedit_blend.h with the lift
+        P held by the window, offset 0, no flip, the plane `mask`, the lock plane and the box of `mask` cut to the window:
+        F' = P + m on the targets, m smooth and equal to F - P on their rim.  The targets are mask != 0 and lock == 0 inside
+        the window, tested in frame space -- unscaled exactly the hard paste's; with `max_side` the hard paste's extra clause
+        "the upsampled hole mask > 0" is NOT applied.  The rim is the frame's pixels next to a target that the window holds (a
+        locked neighbour included); the window's and the frame's edges are left out of the sums.  Same save, same undo step,
+        info gains blend="seamless".  ValueError, before the first backend call: a blend that is neither, blend with feather,
+        a box inside the window with a side above 2048; NotImplementedError: a backend without move_blend / fill_lift."""
         encode = _check_encode(encode)
         feather = _check_feather(feather)
+        seamless = _check_blend(blend, feather, self.backend)
         plane = self._fill_plane(mask)
         sk = None if sketch is None else self._full_size(sketch)
         box = sketch_bbox(plane)
@@ -1797,30 +1859,34 @@ class EditSession:
             by0, bx0, by1, bx1 = min(by0, sb[0]), min(bx0, sb[1]), max(by1, sb[2]), max(bx1, sb[3])
         win = self._fill_window((by0, bx0, by1, bx1), window, margin, max_side)
         y0, x0, h, w = win
+        cut = _blend_box(box, win) if seamless else None
         be = self.backend
         with self._lock:
             return self._fill(be.upload(plane), None if sk is None else be.upload(sk[y0:y0 + h, x0:x0 + w]), win, low_latency, max_side,
-                              encode, feather)
+                              encode, feather, cut)
 
     def fill_strokes(self, strokes, sketch_strokes=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None,
-                     feather=None):
+                     feather=None, blend=None):
         """`fill` with the painted region given as POLYLINES with a brush width: `strokes` (and the optional
         `sketch_strokes` that guide the fill) = [(points, width_px)] as stroke_segments takes them.  Each set is rasterised on
         the device into a frame-sized plane (se_sketch_strokes_u8 with the whole frame as its one window) -- nothing but the
         segments is uploaded -- and the call proceeds as `fill` of those planes; the box is stroke_box of all segments.
-        ValueError for no strokes or one stroke_segments refuses."""
+        ValueError for no strokes or one stroke_segments refuses.  `blend` as in `fill`, its box stroke_box of
+        `strokes` (the plane is made on the device: the box is the segments' bound, not a scan of the plane)."""
         encode = _check_encode(encode)
         feather = _check_feather(feather)
+        seamless = _check_blend(blend, feather, self.backend)
         Hi, Wi = self.frame_hw
         segs, _ = stroke_segments(strokes, self.frame_hw)
         sk_segs = None if sketch_strokes is None else stroke_segments(sketch_strokes, self.frame_hw)[0]
         win = self._fill_window(stroke_box(segs if sk_segs is None else np.concatenate([segs, sk_segs]), self.frame_hw), window, margin,
                                 max_side)
+        cut = _blend_box(stroke_box(segs, self.frame_hw), win) if seamless else None
         be = self.backend
         with self._lock:
             plane = be.strokes(be.upload(segs), self.frame_hw, [(0, 0, Hi, Wi)])[0]
             sk = None if sk_segs is None else be.strokes(be.upload(sk_segs), self.frame_hw, [(0, 0, Hi, Wi)])[0]
-            return self._fill(plane, None if sk is None else be.window_of(sk, *win), win, low_latency, max_side, encode, feather)
+            return self._fill(plane, None if sk is None else be.window_of(sk, *win), win, low_latency, max_side, encode, feather, cut)
 
     # ---- selection by colour (DESIGN.md 6o) ------------------------------------------------------------------------------------
     def _check_select(self, seed, tolerance, grow):
@@ -1852,17 +1918,18 @@ class EditSession:
         plane, box, count = self.backend.select_similar(self._frame, seed, tolerance, bool(contiguous), grow)
         return Selection(self.backend, plane, box, count, self.frame_hw)
 
-    def _fill_selected(self, selection, sk, window, margin, low_latency, max_side, encode, feather):
+    def _fill_selected(self, selection, sk, window, margin, low_latency, max_side, encode, feather, seamless=False):
         """with the session's lock held: `_fill` of the selection's plane through the window of its box united with the
-        sketch's"""
+        sketch's; `seamless`: pasted through the membrane with the selection's box cut to the window"""
         by0, bx0, by1, bx1 = selection.box
         sb = None if sk is None else sketch_bbox(sk)
         if sb is not None:
             by0, bx0, by1, bx1 = min(by0, sb[0]), min(bx0, sb[1]), max(by1, sb[2]), max(bx1, sb[3])
         win = self._fill_window((by0, bx0, by1, bx1), window, margin, max_side)
         y0, x0, h, w = win
+        cut = _blend_box(selection.box, win) if seamless else None
         crop = None if sk is None else self.backend.upload(sk[y0:y0 + h, x0:x0 + w])
-        patch, pos, info = self._fill(selection.plane, crop, win, low_latency, max_side, encode, feather)
+        patch, pos, info = self._fill(selection.plane, crop, win, low_latency, max_side, encode, feather, cut)
         info["selected"] = selection.count
         return patch, pos, info
 
@@ -1878,33 +1945,39 @@ class EditSession:
         with self._lock:
             return self._select(seed, tolerance, contiguous, grow)
 
-    def fill_selection(self, selection, sketch=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None, feather=None):
+    def fill_selection(self, selection, sketch=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None, feather=None,
+                       blend=None):
         """`fill` of a Selection: its plane is on the device already, so only the optional sketch's window goes
         up.  The window is choose_window of the selection's box united with the sketch's at `margin`, or `window` as given;
         everything else -- netG alone on selection & ~lock, the paste in frame space, `max_side`, `encode`, `feather`, ONE undo
         step -- is `fill`'s.  -> what `fill` returns, with info["fill"] = True and info["selected"] = the selection's pixels.
-        ValueError for a selection made on a frame of another size and for what `fill` refuses."""
+        ValueError for a selection made on a frame of another size and for what `fill` refuses.  `blend` as in `fill`
+        (DESIGN.md 6z), its box the selection's."""
         encode = _check_encode(encode)
         feather = _check_feather(feather)
+        seamless = _check_blend(blend, feather, self.backend)
         self._check_selection(selection, "fill_selection")
         if selection.box is None:
             raise ValueError("empty selection: nothing to fill")
         sk = self._check_fill_args(selection.box, sketch, window, margin, max_side)
         with self._lock:
-            return self._fill_selected(selection, sk, window, margin, low_latency, max_side, encode, feather)
+            return self._fill_selected(selection, sk, window, margin, low_latency, max_side, encode, feather, seamless)
 
     def fill_similar(self, seed, tolerance=16, contiguous=True, grow=2, sketch=None, window=None, margin=0.5, low_latency=None,
-                     max_side=None, encode=None, feather=None):
+                     max_side=None, encode=None, feather=None, blend=None):
         """select_similar(seed, tolerance, contiguous, grow) and fill_selection of the result under ONE hold of the session's
         lock: "click on it, fill it in".  Nothing frame-sized crosses the bus in either direction.
-        -> what fill_selection returns; ONE undo step.  Every ValueError comes before the first backend call."""
+        -> what fill_selection returns; ONE undo step.  Every ValueError comes before the first backend call -- but, with
+        `blend` (as in `fill`), that of a box side above 2048: the box exists only once the selection is made, and
+        the refusal comes behind it and in front of every call that changes the frame."""
         encode = _check_encode(encode)
         feather = _check_feather(feather)
+        seamless = _check_blend(blend, feather, self.backend)
         seed, tolerance, grow = self._check_select(seed, tolerance, grow)
         sk = self._check_fill_args((seed[0], seed[1], seed[0] + 1, seed[1] + 1), sketch, window, margin, max_side)
         with self._lock:
             return self._fill_selected(self._select(seed, tolerance, contiguous, grow), sk, window, margin, low_latency, max_side,
-                                       encode, feather)
+                                       encode, feather, seamless)
 
     # ---- lasso selections and the algebra of selections (DESIGN.md 6p) -----------------------------------------------------------
     def _check_selection(self, selection, what):
@@ -2005,14 +2078,17 @@ class EditSession:
         return Selection(be, plane, box, count, self.frame_hw)
 
     def fill_lasso(self, rings, grow=2, sketch=None, window=None, margin=0.5, low_latency=None, max_side=None, encode=None,
-                   feather=None):
+                   feather=None, blend=None):
         """select_lasso(rings, grow) and fill_selection of the result under ONE hold of the session's lock: "draw
         around it, fill it in".  Only the edges go up; nothing frame-sized crosses the bus in either direction.
         -> what fill_selection returns; ONE undo step.  Every ValueError comes before the first backend call (the window
         arguments are tried on lasso_box of the edges) but one: "the lasso covers no pixel centre" may be known only after
-        the selection was made -- a sliver between two columns of centres has a box and no pixel; nothing was changed then."""
+        the selection was made -- a sliver between two columns of centres has a box and no pixel; nothing was changed then.
+        `blend` as in `fill`, its box the selection's; as in fill_similar the refusal of a box side above 2048
+        comes behind the selection and in front of every call that changes the frame."""
         encode = _check_encode(encode)
         feather = _check_feather(feather)
+        seamless = _check_blend(blend, feather, self.backend)
         edges = lasso_edges(rings, self.frame_hw)
         grow = self._check_grow(grow)
         box = lasso_box(edges, self.frame_hw)
@@ -2023,7 +2099,7 @@ class EditSession:
             selection = self._select_lasso(edges, grow)
             if selection.box is None:
                 raise ValueError("the lasso covers no pixel centre")
-            return self._fill_selected(selection, sk, window, margin, low_latency, max_side, encode, feather)
+            return self._fill_selected(selection, sk, window, margin, low_latency, max_side, encode, feather, seamless)
 
     # ---- what the operators on a lifted selection share (DESIGN.md 6r .. 6u) -----------------------------------------------------------
     def _lift_fill_drop(self, selection, dst, window, margin, low_latency, max_side, encode, feather, keep_source, hole_grow, drop, remap,
@@ -2419,11 +2495,11 @@ class EditSession:
 
     def _canvas(self, orient, rect, pad, selections, fill=None):
         """canvas and extend_canvas(fill="network") once the wrappers' own arguments are checked.  `fill`: None, or the outpaint's
-        (window, margin, low_latency, max_side, feather, encode), checked"""
+        (window, margin, low_latency, max_side, feather, encode, seamless), checked"""
         o, new_hw, origin, mode, rgb, selections = self._canvas_args(orient, rect, pad, selections)
         be = self.backend
         if fill is not None:
-            window, margin, low_latency, max_side, feather, encode = fill
+            window, margin, low_latency, max_side, feather, encode, seamless = fill
             Ho, Wo = (self.frame_hw[1], self.frame_hw[0]) if o & 4 else self.frame_hw
             box = canvas_new_box((Ho, Wo), new_hw, origin)
             if box is None:
@@ -2439,6 +2515,7 @@ class EditSession:
                 win = choose_window(box, new_hw, margin=margin)
             if max_side is not None:
                 choose_working_size(win[2:], max_side)
+            cut = _blend_box(box, win) if seamless else None
         with self._lock:
             previous = self.frame_hw
             held = [self._frame, self.frame_hw, self._lock_plane]
@@ -2451,13 +2528,18 @@ class EditSession:
                 new_area = be.canvas(None, (Ho, Wo), new_hw, origin, 0, CANVAS_CONSTANT, 255)
                 self._frame, self.frame_hw, self._lock_plane = frame, new_hw, lock
                 try:
-                    _, work, _ = self._fill_steps(new_area, None, win, low_latency, max_side, feather, False)
+                    if cut is None:
+                        _, work, _ = self._fill_steps(new_area, None, win, low_latency, max_side, feather, False)
+                    else:
+                        _, work, _ = self._fill_steps(new_area, None, win, low_latency, max_side, feather, False, cut)
                     patch = be.crop(self._frame, *win) if encode is None else _encoded(be, encode, [self._frame], [win])[0]
                 except Exception:                # out of place: the state the call found is still whole
                     self._frame, self.frame_hw, self._lock_plane = held
                     raise
                 pos = (win[1], win[0])
                 extra = _edit_info(dict(window=win, fill=True), False, work, None, feather)
+                if cut is not None:
+                    extra["blend"] = "seamless"
             undoable = self._record_canvas(held)
         info = dict(canvas=new_hw, previous=previous, orient=orient, rect=origin + new_hw, undoable=undoable, selections=made,
                     locked=lock is not None, **extra)
@@ -2491,7 +2573,7 @@ class EditSession:
         return self._canvas(None, (y0, x0, h, w), "edge", selections)
 
     def extend_canvas(self, top=0, bottom=0, left=0, right=0, pad="edge", fill=None, selections=(), window=None, margin=0.5,
-                      low_latency=None, max_side=None, feather=None, encode=None):
+                      low_latency=None, max_side=None, feather=None, encode=None, blend=None):
         """canvas(rect=(-top, -left, H + top + bottom, W + left + right), pad=pad): room on each side, four ints >= 0 of which one
         at least is > 0.
         fill="network" is the outpaint, "add room and let the network fill it": DEFINED as this call without `fill` followed by
@@ -2500,15 +2582,22 @@ class EditSession:
         the window is choose_window of its box at `margin` unless given; the lock plane, carried first, is respected as every
         fill respects it; `pad` is what the generator sees under the hole's rim and what stays where the window does not
         reach.  -> (patch, (x0, y0), info): the window after the paste as `fill` returns it, info as canvas' plus window,
-        fill=True and work / feather where `fill` reports them.  No quality claim is made, as for `fill`."""
+        fill=True and work / feather where `fill` reports them.  No quality claim is made, as for `fill`.
+        `blend` = "seamless" (with fill="network" only): DEFINED as the extension followed by fill(the plane of the
+        new area, blend="seamless", ...) -- the new area takes the local colour of the old frame along the seam; its box is the
+        new area's.  Refused as `fill` refuses it, before the first backend call."""
         if not all(_canvas_int(v) and v >= 0 for v in (top, bottom, left, right)) or not (top or bottom or left or right):
             raise ValueError("top, bottom, left, right are ints >= 0, one of them > 0 (got %r)" % ((top, bottom, left, right),))
         if not (fill is None or isinstance(fill, str)) or fill not in CANVAS_FILLS:
             raise ValueError("fill is None or 'network' (got %r)" % (fill,))
         rect = (-int(top), -int(left), self.frame_hw[0] + int(top) + int(bottom), self.frame_hw[1] + int(left) + int(right))
         if fill is None:
+            if blend is not None:
+                raise ValueError("blend is the paste of the outpaint's fill: it needs fill='network' (got blend=%r)" % (blend,))
             return self._canvas(None, rect, pad, selections)
-        return self._canvas(None, rect, pad, selections, (window, margin, low_latency, max_side, _check_feather(feather), _check_encode(encode)))
+        feather = _check_feather(feather)
+        return self._canvas(None, rect, pad, selections, (window, margin, low_latency, max_side, feather, _check_encode(encode),
+                                                          _check_blend(blend, feather, self.backend)))
 
     def orient_canvas(self, op, selections=()):
         """canvas(orient=op): "cw", "ccw", "180", "h", "v", "transpose" or "transverse" (DESIGN.md 6y)."""

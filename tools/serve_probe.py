@@ -254,6 +254,19 @@ device synchronisation -- a canvas call downloads nothing.  Legs:
 plus, under the profiler, the device time of canvas_turn (a quarter turn) and canvas_map (a half turn) of the same frame, their
 ratio and the bytes per second each moves:
     python tools/serve_probe.py --canvas [--reps N] [--out FILE]
+
+--seamless-fill: fills pasted through the membrane: --blend's frame, disc (253 x 253) and window; the disc's mask goes
+up with every call (a fill's one upload), the frame is put back (a device copy, outside the clock) in front of every call, each
+call ends in the patch's download.  Legs:
+  (a) edit:                 EditSession.edit(window=..., max_grow=0), the unchanged control,
+  (b) fill / fill_scaled:   EditSession.fill(mask, window=...), the hard paste, at the frame's scale and with max_side=256 -- the
+                            three legs --seamless-fill-parent runs on the parent commit's build in the same job, before and after,
+                            for the comparison and its own spread,
+  (c) fill_seamless / fill_scaled_seamless: the same with blend="seamless": the raw forward, the lift (one resize when scaled), the
+                            fixed schedule on the disc's box,
+and, once under the profiler, the kernels of (c)'s two calls: the blend kernels' launches and device time, the resize's.  The
+expectation to confirm or refute: (c) costs (b) plus the membrane's device time for the hole's box, plus one resize when scaled.
+    python tools/serve_probe.py --seamless-fill [--reps N] [--out FILE]
 """
 import argparse
 import json
@@ -1649,6 +1662,70 @@ def blend_leg(model, reps, parent=False, side=512, tolerance=16, offset=(150, 30
     return out
 
 
+def seamless_fill_leg(model, reps, parent=False, side=512, max_side=256):
+    """(a) .. (c) of the module docstring; parent=True: the legs (a) and (b) only, with the calls a build without the flag has"""
+    import numpy as np
+    import torch
+    from sketchedit_amd import serve
+    rng = np.random.RandomState(0)
+    w, h = 1921, 1081
+    frame = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    win = (283, 705, side, side)
+    centre = (win[0] + side // 2, win[1] + side // 2)
+    yy, xx = np.mgrid[0:h, 0:w]
+    mask = ((yy - centre[0]) ** 2 + (xx - centre[1]) ** 2 <= 126 ** 2).astype(np.uint8)
+    sk = np.zeros((h, w), np.uint8)
+    sk[win[0] + 200:win[0] + 240, win[1] + 250:win[1] + 256] = 255
+    dev0 = torch.from_numpy(frame).cuda()
+    s1 = serve.EditSession(model, frame)
+
+    def timed(fn):
+        def rounds():
+            ts = []
+            for k in range(2 + reps):              # two warm-ups: plans, workspace, code objects
+                s1._frame.copy_(dev0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()                               # ends in a device-to-host copy: the request is complete
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts = sorted(ts[2:])
+            return dict(median=round(ts[len(ts) // 2], 3), min=round(ts[0], 3), max=round(ts[-1], 3))
+        return rounds
+
+    legs = dict(edit=timed(lambda: s1.edit(sk, window=win, max_grow=0, low_latency=True)),
+                fill=timed(lambda: s1.fill(mask, window=win, low_latency=True)),
+                fill_scaled=timed(lambda: s1.fill(mask, window=win, max_side=max_side, low_latency=True)))
+    if not parent:
+        legs.update(fill_seamless=timed(lambda: s1.fill(mask, window=win, low_latency=True, blend="seamless")),
+                    fill_scaled_seamless=timed(lambda: s1.fill(mask, window=win, max_side=max_side, low_latency=True, blend="seamless")))
+    ys, xs = np.nonzero(mask)
+    out = dict(tool="serve_probe --seamless-fill" + ("-parent" if parent else ""), B=1, reps=reps, mode="low_latency", frame=[w, h],
+               window=list(win), max_side=max_side, selected=int(mask.sum()), box=[int(ys.min()), int(xs.min()), int(ys.max()) + 1, int(xs.max()) + 1])
+    rounds = [{k: fn() for k, fn in legs.items()} for _ in range(3)]
+    out["ms"] = {}
+    for k in legs:
+        meds = sorted(r[k]["median"] for r in rounds)
+        out["ms"][k] = dict(median=meds[1], round_medians=[r[k]["median"] for r in rounds], min=min(r[k]["min"] for r in rounds),
+                            max=max(r[k]["max"] for r in rounds))
+    if not parent:
+        eng = model.engine()
+        for key, kw in (("fill_seamless", dict()), ("fill_scaled_seamless", dict(max_side=max_side))):
+            s1._frame.copy_(dev0)
+            eng.profile(True)
+            s1.fill(mask, window=win, low_latency=True, blend="seamless", **kw)
+            rep = eng.profile_report()
+            eng.profile(False)
+            ks = {k["kernel"]: dict(launches=k["launches"], ms=round(k["total_ms"], 4)) for k in rep["kernels"]}
+            blend = {k: v for k, v in ks.items() if k.startswith("blend_")}
+            out[key + "_profiled"] = dict(kernels=ks, blend_launches=sum(v["launches"] for v in blend.values()),
+                                          blend_device_ms=round(sum(v["ms"] for v in blend.values()), 4),
+                                          resize_device_ms=round(sum(v["ms"] for k, v in ks.items() if "resize" in k), 4),
+                                          device_ms=round(sum(v["ms"] for v in ks.values()), 4))
+        out["fill_seamless_minus_fill_ms"] = round(out["ms"]["fill_seamless"]["median"] - out["ms"]["fill"]["median"], 3)
+        out["fill_scaled_seamless_minus_fill_scaled_ms"] = round(out["ms"]["fill_scaled_seamless"]["median"] - out["ms"]["fill_scaled"]["median"], 3)
+    return out
+
+
 def canvas_leg(model, reps, parent=False, side=512):
     """(a) .. (c) of the module docstring; parent=True: the leg (a) only, with the calls a build without the canvas has"""
     import numpy as np
@@ -1848,6 +1925,8 @@ def main():
     ap.add_argument("--blend-parent", action="store_true", help="the edit and the plain clone legs of --blend only")
     ap.add_argument("--canvas", action="store_true", help="crop, extend, rotate and flip the canvas (see the module docstring)")
     ap.add_argument("--canvas-parent", action="store_true", help="the edit leg of --canvas only")
+    ap.add_argument("--seamless-fill", action="store_true", help="fills pasted through the membrane (see the module docstring)")
+    ap.add_argument("--seamless-fill-parent", action="store_true", help="the edit and the hard fill legs of --seamless-fill only")
     args = ap.parse_args()
     import tempfile
     import numpy as np
@@ -1861,8 +1940,10 @@ def main():
             or args.jpg or args.jpg_parent or args.jpg2 or args.feather or args.feather_parent or args.fill or args.fill_parent
             or args.select or args.select_parent or args.lasso or args.lasso_parent or args.outline or args.outline_parent
             or args.move or args.move_parent or args.warp or args.filter or args.adjust or args.modify or args.modify_parent
-            or args.blend or args.blend_parent or args.canvas or args.canvas_parent):
-        if args.canvas or args.canvas_parent:
+            or args.blend or args.blend_parent or args.canvas or args.canvas_parent or args.seamless_fill or args.seamless_fill_parent):
+        if args.seamless_fill or args.seamless_fill_parent:
+            res = seamless_fill_leg(model, args.reps, parent=args.seamless_fill_parent)
+        elif args.canvas or args.canvas_parent:
             res = canvas_leg(model, args.reps, parent=args.canvas_parent)
         elif args.blend or args.blend_parent:
             res = blend_leg(model, args.reps, parent=args.blend_parent)
